@@ -2,7 +2,7 @@
 """
 bench.py -- the BASELINE workloads on MI355X, one JSON line on stdout (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--workload pcg|pd]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--workload pcg|pd] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 --workload pcg (default, the headline metric): PCG matvecs/sec on the 4096 x 4096 x 8-band cube
@@ -17,6 +17,11 @@ time, min / max alongside.  Total work is fixed as N grows => "scaling": "strong
 --workload pd: BASELINE config #4, the backward step of the forward-backward loop: K iterations
 of primal_dual_optimised on a 2048 x 2048 x 4-band cube (psi / psi^H with self + db1..db4, 3
 levels, dual update, one PSF convolution for the gradient), value = iterations / s.
+
+Every timed region runs exactly --steps steps (after --warmup untimed ones).  The inputs are synthetic and seeded
+(synth_problem), identical from run to run for the same arguments.  --dump-outputs DIR writes,
+after the timed regions, what the last one returned to its caller (pcg: x and the solve's record; pd: x and v) as
+DIR/<name>.npy, so that two builds can be compared output for output; large outputs are a fixed sample (dump_index).
 
 `python bench.py --gpus N` WITHOUT a launcher (WORLD_SIZE unset) starts the N ranks itself as a
 child `torch.distributed.run` before anything touches the GPU and relays rank 0's line;
@@ -83,9 +88,17 @@ def parse_args(argv=None):
                          "'configs' on the JSON line; auto = all for the default one-GPU headline run")
     ap.add_argument('--force-dist', action='store_true',
                     help='run the band-sharded code path (all-reduce hook) even at world size 1')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed solve returned as DIR/<name>.npy '
+                         '(see dump_outputs)')
     ap.add_argument('--cpu-worker', nargs=5, metavar=('DIR', 'BAND', 'THREADS', 'ITERS', 'SIGMAINV'),
                     help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    return args
 
 
 # ------------------------------------------------------------------------------ launcher
@@ -158,6 +171,83 @@ def synth_model(band, nx, ny, dtype, device):
         i, j = rng.integers(0.15 * nx, 0.85 * nx), rng.integers(0.15 * ny, 0.85 * ny)
         model[i, j] += 1.0
     return model.to(dtype)
+
+
+def synth_dirty(model, psfhat, Q):
+    """The dirty cube psf * model of each band (psf.py:11-29: zero-pad, r2c, multiply, c2r, crop), computed in fp64
+    with torch.fft and rounded to the model's dtype.  It is set-up, not timed, and it does not run the kernels under
+    test, so that the same arguments give the same inputs whichever build of the library runs."""
+    import torch
+    nx, ny = model.shape[-2:]
+    out = torch.empty_like(model)
+    for k in range(model.shape[0]):
+        xhat = torch.fft.rfft2(model[k].to(torch.float64), s=(2 * nx, Q))
+        xhat *= psfhat[k].to(torch.complex128)
+        out[k] = torch.fft.irfft2(xhat, s=(2 * nx, Q))[:nx, :ny]
+    return out
+
+
+# --dump-outputs: an output of more than DUMP_MAX elements is written as a fixed sample of it (DUMP_MAX fp64 values are
+# 16 MiB; the largest dump, x and v of --workload pd, stays under 64 MiB)
+DUMP_MAX = 1 << 21
+DUMP_SEED = 20261015
+
+
+def dump_index(total):
+    """Flat indices of the elements of a `total`-element output that --dump-outputs keeps: all of them up to DUMP_MAX,
+    else up to DUMP_MAX distinct indices drawn from numpy's default_rng(DUMP_SEED), ascending.  The set depends on
+    `total` alone, so every run and every build samples the same elements."""
+    import numpy as np
+    if total <= DUMP_MAX:
+        return np.arange(total, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_MAX, dtype=np.int64))
+
+
+def dump_outputs(path, outputs, ctx, nband):
+    """Write each output as <path>/<name>.npy in the run's dtype (float32 / float64).  `outputs` maps name -> this
+    rank's tensor, whose leading axis holds bands [band0, band0 + nb) of `nband` (shard_bands); a 1-D tensor is a
+    per-solve record that every rank holds.  Outputs of up to DUMP_MAX elements keep their full shape; larger ones
+    are the 1-D sample dump_index picks from the flattened whole-cube array.  Collective: every rank calls it."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from pfb_clean_amd.dist import shard_bands
+    world, rank = ctx['world'], ctx['rank']
+    band0, nb = shard_bands(nband, rank, world)
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        if t.ndim == 1:
+            if rank == 0:
+                np.save(os.path.join(path, f'{name}.npy'), t.cpu().numpy())
+            continue
+        shape = (nband,) + tuple(t.shape[1:])
+        plane = t[0].numel()
+        idx = dump_index(nband * plane)
+        lo, hi = np.searchsorted(idx, [band0 * plane, (band0 + nb) * plane])
+        local = torch.from_numpy(idx[lo:hi] - band0 * plane).to(t.device)
+        vals = t.contiguous().reshape(-1)[local].cpu().numpy()
+        if world > 1:                                   # ranks hold consecutive band ranges: rank order = index order
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(vals, parts, dst=0)
+            if rank == 0:
+                vals = np.concatenate(parts)
+        if rank == 0:
+            assert vals.size == idx.size
+            np.save(os.path.join(path, f'{name}.npy'), vals.reshape(shape) if idx.size == nband * plane else vals)
+
+
+def synth_problem(band0, nb, nband, n, dtype, device, seed):
+    """psfhat and dirty image of bands [band0, band0 + nb) of an nband-band n x n cube: the dirty image is psf * model
+    (synth_dirty) plus 1e-3 N(0, 1) noise from a device generator seeded with `seed`."""
+    import torch
+    psfhat = torch.stack([synth_band(band0 + k, nband, n, n, dtype, device) for k in range(nb)])
+    model = torch.stack([synth_model(band0 + k, n, n, dtype, device) for k in range(nb)])
+    dirty = synth_dirty(model, psfhat, 2 * n)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    dirty += 1e-3 * torch.randn(dirty.shape, dtype=dtype, device=device, generator=gen)
+    return psfhat, dirty
 
 
 class _stdout_to_stderr:
@@ -257,7 +347,7 @@ def extra_configs(ctx):
     res = {}
     for name, workload, kw in specs:
         a = copy.copy(args)
-        a.no_cpu, a.configs, a.workload = True, 'none', workload
+        a.no_cpu, a.configs, a.workload, a.dump_outputs = True, 'none', workload, None
         for k, v in kw.items():
             setattr(a, k, v)
         try:
@@ -323,16 +413,10 @@ def bench_pcg(ctx):
         raise SystemExit("more ranks than bands")
     Q = 2 * n
 
-    psfhat = torch.stack([synth_band(band0 + k, nband, n, n, dtype, device) for k in range(nb)])
+    psfhat, b = synth_problem(band0, nb, nband, n, dtype, device, 1420 + rank)
     plan = PsfConvPlan(psfhat, n, n, Q)
-    model = torch.stack([synth_model(band0 + k, n, n, dtype, device) for k in range(nb)])
-    b = plan.apply(model).clone()
-    gen = torch.Generator(device=device)
-    gen.manual_seed(1420 + rank)
-    b += 1e-3 * torch.randn(b.shape, dtype=dtype, device=device, generator=gen)
     sigmainv = 1e-3 * global_max(b.abs().max().item(), device)
     A = HessianPsf(plan, n, n, Q, sigmainv=sigmainv)
-    del model
     torch.cuda.synchronize()
 
     def solve(iters):
@@ -352,6 +436,12 @@ def bench_pcg(ctx):
     stage_ms, napply = plan.get_profile()
     plan.set_profiling(False)
     assert res.iters == args.steps and res.matvecs == args.steps + 1, (res.iters, res.matvecs)
+    if args.dump_outputs:
+        # what pcg_fused hands its caller: the iterate x and the solve's record (status, iters, matvecs, backtracks,
+        # eps, rnorm)
+        record = torch.tensor([res.status, res.iters, res.matvecs, res.backtracks, res.eps, res.rnorm],
+                              dtype=torch.float64)
+        dump_outputs(args.dump_outputs, {'x': x, 'pcg_result': record}, ctx, nband)
     matvecs = res.matvecs
     elapsed = _median(times)
     value = matvecs / elapsed
@@ -578,14 +668,8 @@ def bench_pd(ctx):
     bases = ['self', 'db1', 'db2', 'db3', 'db4']
     nlevel = 3
     Q = 2 * n
-    psfhat = torch.stack([synth_band(k, nband, n, n, dtype, device) for k in range(nband)])
+    psfhat, dirty = synth_problem(0, nband, nband, n, dtype, device, 1420)
     plan = PsfConvPlan(psfhat, n, n, Q)
-    model = torch.stack([synth_model(k, n, n, dtype, device) for k in range(nband)])
-    dirty = plan.apply(model).clone()
-    gen = torch.Generator(device=device)
-    gen.manual_seed(1420)
-    dirty += 1e-3 * torch.randn(dirty.shape, dtype=dtype, device=device, generator=gen)
-    del model
     psi = Psi(nband, n, n, bases, nlevel, 1, dtype=dtype)
     nbasis = len(bases)
     grad = PsfGradient(plan, dirty)                          # spotless.py:259-260: conv(x) - dirty
@@ -604,7 +688,9 @@ def bench_pd(ctx):
 
     if args.warmup > 0:
         run(args.warmup)
-    times, _ = _timed_regions(lambda: run(args.steps), barrier, args.repeats, world, device)
+    times, (x, v) = _timed_regions(lambda: run(args.steps), barrier, args.repeats, world, device)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'x': x, 'v': v}, ctx, nband)     # primal_dual_optimised returns (x, v)
     elapsed = _median(times)
     value = args.steps / elapsed
     s = 4 if dtype == torch.float32 else 8

@@ -423,3 +423,20 @@ def test_band_sharded_primal_dual_gloo_world2():
         assert p.exitcode == 0
     for rank, errs in sorted(q.get(timeout=5) for _ in range(2)):
         assert max(errs) < 1e-9, (rank, errs)
+
+
+def test_bench_dump_sample_is_fixed_and_steps_are_checked():
+    """bench.py --dump-outputs keeps the same elements of an output in every run (a seeded sample above DUMP_MAX,
+    everything below it), and --steps / --warmup outside their range are refused."""
+    import bench
+    assert np.array_equal(bench.dump_index(1000), np.arange(1000))
+    total = 8 * 4096 * 4096
+    idx = bench.dump_index(total)
+    assert np.array_equal(idx, bench.dump_index(total))
+    assert 0.9 * bench.DUMP_MAX < idx.size <= bench.DUMP_MAX
+    assert idx[0] >= 0 and idx[-1] < total and (np.diff(idx) > 0).all()
+    a = bench.parse_args(['--steps', '3', '--warmup', '0', '--dump-outputs', 'out'])
+    assert (a.steps, a.warmup, a.dump_outputs) == (3, 0, 'out')
+    for bad in (['--steps', '0'], ['--warmup', '-1']):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)

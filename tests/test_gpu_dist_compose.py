@@ -766,10 +766,11 @@ def test_plain_cg_against_reference_vectors(kind):
     assert np.array_equal(back(x0), g['x0'])                        # x0 is copied, not updated (pcg.py:23)
 
 
-def test_bench_two_ranks_rehearsal():
+def test_bench_two_ranks_rehearsal(tmp_path):
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per GPU, band shard,
     all-reduce hook, max-over-ranks timing, one JSON line from rank 0) -- rehearsed with two ranks sharing
-    the test GPU over gloo (RCCL refuses two ranks on one device; PFB_DIST_BACKEND is a bench-only switch)."""
+    the test GPU over gloo (RCCL refuses two ranks on one device; PFB_DIST_BACKEND is a bench-only switch).
+    --dump-outputs gathers both ranks' bands of x into one file on rank 0."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import json
@@ -780,7 +781,7 @@ def test_bench_two_ranks_rehearsal():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
            os.path.join(root, 'bench.py'), '--gpus', '2', '--size', '1024', '--bands', '4', '--steps', '6',
-           '--warmup', '2', '--no-cpu']
+           '--warmup', '2', '--no-cpu', '--dump-outputs', str(tmp_path)]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -789,3 +790,64 @@ def test_bench_two_ranks_rehearsal():
     assert d['n_gpus'] == 2 and d['steps'] == 6 and d['matvecs'] == 7
     assert d['config']['bands_per_gpu'] == 2 and d['value'] > 0 and d['scaling'] == 'strong'
     assert d['roofline'] is not None and d['cpu_baseline'] is None
+    import bench
+    x = np.load(tmp_path / 'x.npy')
+    assert x.dtype == np.float32 and x.shape == bench.dump_index(4 * 1024 * 1024).shape
+    assert np.isfinite(x).all() and np.abs(x).max() > 0
+    assert np.load(tmp_path / 'pcg_result.npy')[1:3].tolist() == [6, 7]
+
+
+def _run_bench(root, args, timeout=300):
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py')] + args, cwd=root, capture_output=True,
+                         text=True, timeout=timeout)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return out
+
+
+def test_bench_dump_outputs_pcg(tmp_path):
+    """bench.py --dump-outputs: what the last of the timed solves returned -- a fixed sample of x (4 x 1024^2 is above
+    DUMP_MAX) and the solve's record -- the same arrays from two runs with the same arguments, and the same as
+    pcg_fused gives after exactly --steps iterations on bench.py's own inputs."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import bench
+    from pfb_clean_amd.operators.psf import PsfConvPlan
+    from pfb_clean_amd.operators.hessian import HessianPsf
+    from pfb_clean_amd.opt.pcg import pcg_fused
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, nband, steps = 1024, 4, 5
+    args = ['--size', str(n), '--bands', str(nband), '--steps', str(steps), '--warmup', '1', '--repeats', '2',
+            '--no-cpu', '--configs', 'none']
+    runs = []
+    for k in range(2):
+        _run_bench(root, args + ['--dump-outputs', str(tmp_path / f'run{k}')])
+        assert sorted(os.listdir(tmp_path / f'run{k}')) == ['pcg_result.npy', 'x.npy']
+        runs.append({name: np.load(tmp_path / f'run{k}' / f'{name}.npy') for name in ('x', 'pcg_result')})
+    idx = bench.dump_index(nband * n * n)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    psfhat, b = bench.synth_problem(0, nband, nband, n, torch.float32, dev, 1420)
+    sigmainv = 1e-3 * b.abs().max().item()
+    A = HessianPsf(PsfConvPlan(psfhat, n, n, 2 * n), n, n, 2 * n, sigmainv=sigmainv)
+    x, _, res = pcg_fused(A, b, None, mdiv=sigmainv, tol=0.0, maxit=steps, minit=steps, backtrack=True)
+    want = x.cpu().numpy().reshape(-1)[idx]
+    for got in runs:
+        assert got['x'].dtype == np.float32 and got['x'].shape == idx.shape
+        assert np.abs(got['x'] - want).max() <= 1e-6 * np.abs(want).max()
+        assert got['pcg_result'][:4].tolist() == [res.status, steps, steps + 1, res.backtracks]
+        assert np.allclose(got['pcg_result'][4:], [res.eps, res.rnorm], rtol=1e-6, atol=0)
+
+
+def test_bench_dump_outputs_pd(tmp_path):
+    """--workload pd --dump-outputs: x and v as primal_dual_optimised returns them (full shape below DUMP_MAX)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    _run_bench(root, ['--workload', 'pd', '--size', '256', '--bands', '2', '--steps', '3', '--warmup', '1',
+                      '--repeats', '1', '--no-cpu', '--configs', 'none', '--dump-outputs', str(tmp_path)])
+    assert sorted(os.listdir(tmp_path)) == ['v.npy', 'x.npy']
+    x, v = np.load(tmp_path / 'x.npy'), np.load(tmp_path / 'v.npy')
+    assert x.dtype == v.dtype == np.float32
+    assert x.shape == (2, 256, 256) and v.ndim == 4 and v.shape[:2] == (2, 5)
+    assert np.isfinite(x).all() and np.isfinite(v).all() and np.abs(x).max() > 0
