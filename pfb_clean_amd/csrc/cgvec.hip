@@ -22,15 +22,10 @@ constexpr int RED_BLOCK = 256;
 constexpr int RED_MAX_GRID = 1024;
 
 static inline int red_grid(size_t nvec) {
-    static const int cap = [] {           // PFB_RED_GRID: A/B knob for the streaming kernels' grid cap
-        const char* e = getenv("PFB_RED_GRID");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 && v <= 2048 ? v : RED_MAX_GRID;   // 4 sums x grid <= PFB_REDUCE_WS_DOUBLES
-    }();
     size_t g = (nvec + RED_BLOCK - 1) / RED_BLOCK;
     g = (g + 3) / 4;                      // >= 4 vectors per thread when large
     if (g < 1) g = 1;
-    if (g > (size_t)cap) g = cap;
+    if (g > (size_t)RED_MAX_GRID) g = RED_MAX_GRID;   // 4 sums x grid <= PFB_REDUCE_WS_DOUBLES
     return (int)g;
 }
 
@@ -372,11 +367,39 @@ __global__ void k_iter_end_begin(double* S, double mdiv, int predict) {
 // convolution (per-workgroup partials `cp`), the four sums the
 // previous iteration's fused update left in `ws` (when `have_upd`), then -- unless an all-reduce has
 // to come first (`logic` == 0) -- the end of that iteration and the begin of this one.
+// Seven independent sums, each by ONE wave in a fixed lane-strided order (deterministic): wave w takes conv quantity w
+// (w < 3) and update quantity w (w < 4); `vals`: 8 doubles of LDS.
+__device__ __forceinline__ void iter_sums(const double* __restrict__ cp, int ncp, const double* __restrict__ ws, int G,
+                                          int have_upd, double* __restrict__ S, double mdiv, int predict, int logic,
+                                          double* vals) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (w < 3) {
+        double acc = 0.0;
+        for (int k = lane; k < ncp; k += 64) acc += cp[(size_t)w * ncp + k];
+        acc = wave_sum(acc);
+        if (lane == 0) vals[w] = acc;
+    }
+    if (have_upd && w < 4) {
+        double acc = 0.0;
+        for (int g = lane; g < G; g += 64) acc += ws[(size_t)w * G + g];
+        acc = wave_sum(acc);
+        if (lane == 0) vals[3 + w] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        S[S_PAP] = vals[0]; S[S_RAP] = vals[1]; S[S_APAP] = vals[2];
+        if (have_upd) { S[S_RHON] = vals[3]; S[S_NUM] = vals[4]; S[S_DEN] = vals[5]; S[S_ANY] = vals[6]; }
+        if (logic) {
+            if (have_upd) iter_end_dev(S, 1);
+            iter_begin_dev(S, mdiv, predict);
+        }
+    }
+}
 __global__ void __launch_bounds__(256)
 k_iter_sums(const double* __restrict__ cp, int ncp, const double* __restrict__ ws, int G, int have_upd,
             double* __restrict__ S, double mdiv, int predict, int logic) {
     __shared__ double vals[8];
-    pcg_iter_sums<false>(cp, ncp, ws, G, have_upd, S, mdiv, predict, logic, vals);
+    iter_sums(cp, ncp, ws, G, have_upd, S, mdiv, predict, logic, vals);
 }
 __global__ void k_final_check(double* S) {
     if (S[S_DEAD] == 0.0 && S[S_ANY] == 0.0) { S[S_DEAD] = 1.0; S[S_K] -= 1.0; S[S_EPS] = S[S_EPSP]; }
@@ -465,9 +488,7 @@ static int stream_grid(size_t nvec) {
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        const char* e = getenv("PFB_UPD_GRID");        // A/B knob
-        const int o = e ? atoi(e) : 0;
-        return o > 0 && o <= 2048 ? o : v;
+        return v;
     }();
     size_t g = (nvec + RED_BLOCK - 1) / RED_BLOCK;
     g = (g + 3) / 4;
@@ -479,26 +500,19 @@ template <typename T>
 static int launch_update_dir(size_t n, const T* x, const T* r, T* p, const T* Ap, T* xn, T* rn,
                              const double* alpha_dev, T mdiv, double* ws, hipStream_t st) {
     // two strips per trip (all eight loads in flight before the first use): fp64 0.79 -> 0.71 ms at 4 x 4096^2,
-    // fp32 0.64 -> 0.62 ms at 8 x 4096^2 (rocprofv3); PFB_UPD_UNROLL=1 for the single-strip loop
-    static const int unroll = [] { const char* e = getenv("PFB_UPD_UNROLL"); return e ? atoi(e) : 2; }();
+    // fp32 0.64 -> 0.62 ms at 8 x 4096^2 (rocprofv3)
     using PL = std::initializer_list<const void*>;
     constexpr int V = V16<T>::N;
     if (can_vec<T>(n, PL{x, r, p, Ap, xn, rn})) {
         const size_t nvec = n / V;
         const int G = stream_grid(nvec);
-        // x non-temporal only when the vectors are far beyond the caches anyway (>= 32 MB each): small problems live in
-        // L2 / the Infinity Cache between iterations and nt would send x to HBM (1024^2: 0.060 -> 0.066 ms per iteration)
-        static const bool xnt_on = [] { const char* e = getenv("PFB_UPD_XNT"); return !e || atoi(e); }();
-        const bool xnt = xnt_on && n * sizeof(T) >= ((size_t)32 << 20);
-        static const bool rev = [] { const char* e = getenv("PFB_UPD_REV"); return !e || atoi(e); }();
-        if (unroll == 2 && xnt && rev)
+        // x non-temporal (and the walk from the end) only when the vectors are far beyond the caches anyway (>= 32 MB
+        // each): small problems live in L2 / the Infinity Cache between iterations and nt would send x to HBM
+        // (1024^2: 0.060 -> 0.066 ms per iteration)
+        if (n * sizeof(T) >= ((size_t)32 << 20))
             hipLaunchKernelGGL((k_pcg_update_dir<T, V, 2, true, true>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, nvec, ws);
-        else if (unroll == 2 && xnt)
-            hipLaunchKernelGGL((k_pcg_update_dir<T, V, 2, true>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, nvec, ws);
-        else if (unroll == 2)
-            hipLaunchKernelGGL((k_pcg_update_dir<T, V, 2>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, nvec, ws);
         else
-            hipLaunchKernelGGL((k_pcg_update_dir<T, V, 1>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, nvec, ws);
+            hipLaunchKernelGGL((k_pcg_update_dir<T, V, 2>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, nvec, ws);
         return G;
     }
     const int G = stream_grid(n);
@@ -628,16 +642,14 @@ static int pcg_impl(pfb_conv_plan* plan, int band0, int nb, const void* b, void*
         int khost = 0;
         bool pending_end = false;
         bool go = (1.0 > tol || 0 < minit) && 0 < maxit;
-        const char* nf = getenv("PFB_PCG_NO_FUSE_DIR");
-        const bool fuse_dir = !(nf && atoi(nf));     // A/B switch: separate update / direction kernels
         // Past minit the stopping rule needs eps after every iteration.  Looking costs a copy + stream sync
         // (13-24 us, tools/exp_sync_cost.py): a third of an iteration at 1024^2, 1 % at 8 x 4096^2.  Small
         // problems therefore run ONE iteration ahead: iteration j is enqueued, then the pinned snapshot taken
         // after iteration j-1 is read; the device evaluates the rule itself (S_STOP) so that the speculative
         // iteration is a no-op once it fired.  Price: one wasted iteration per solve -- large problems keep
         // the synchronous look.  PFB_PCG_LOOKAHEAD=0/1 overrides the size rule.
-        bool lookahead = fuse_dir && n <= ((size_t)4 << 20);
-        if (const char* la = getenv("PFB_PCG_LOOKAHEAD")) lookahead = fuse_dir && atoi(la) != 0;
+        bool lookahead = n <= ((size_t)4 << 20);
+        if (const char* la = getenv("PFB_PCG_LOOKAHEAD")) lookahead = atoi(la) != 0;
         if (lookahead && !plan->pcg_pin) {
             PFB_HIP_CHECK(hipHostMalloc((void**)&plan->pcg_pin, sizeof(double) * 2 * S_NSCALAR, hipHostMallocDefault));
             PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[0], hipEventDisableTiming));
@@ -646,69 +658,36 @@ static int pcg_impl(pfb_conv_plan* plan, int band0, int nb, const void* b, void*
         int slot = 0;
         bool have_prev = false, stale_h = false;
         while (go) {
-            if (fuse_dir) {
-                // PFB_PCG_TAIL=1 (default OFF): without an exchange the scalar work of the iteration -- summing the
-                // convolution's fused dots and the previous update's sums, ending that iteration, beginning this one --
-                // rides in the TAIL of the convolution's inverse row kernel (its last-arriving workgroup,
-                // pcg_state.hpp): 4 launches per iteration instead of 5, bit-identical iterates (tools/check_tail.py:
-                // 240 solves at six sizes).  Measured (profiles/r03_d_pcg_tail_ab.md): a TIE -- the tail's three
-                // dependent device-scope round trips (ticket, partials, state) cost the ~6 us the launch of k_iter_sums
-                // cost (0.0646 / 0.0658 vs 0.0658 / 0.0645 ms per iteration at 1024^2, 0.3147 / 0.3139 vs 0.3139 / 0.3131
-                // at 4096^2 x 1); with agent-scope fences instead of write-through partials it LOST 8 % (every
-                // workgroup's release fence writes back its XCD's whole L2).  Kept as a switch, not as the default.
-                static const bool tail_on = [] { const char* e = getenv("PFB_PCG_TAIL"); return e && atoi(e); }();
-                plan->tail_done = 0;
-                if (tail_on && !allreduce)
-                    plan->tail = PcgTail{S, ws, plan->tail_counter, mdiv_d, G_used, pending_end ? 1 : 0, backtrack == 2 ? 2 : 3};
-                err = psfconv_apply_partials(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, rcur, (void*)st);
-                plan->tail.S = nullptr;
-            } else if (backtrack == 2)
-                err = pfb_psfconv_apply_dots(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, rcur, S + S_PAP, (void*)st);
-            else
-                err = pfb_psfconv_apply(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, S + S_PAP, (void*)st);
+            err = psfconv_apply_partials(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, rcur, (void*)st);
             if (err != PFB_OK) return err;
-            if (fuse_dir) {
-                // ONE scalar launch per iteration: the convolution's dots, the previous update's sums
-                // (left pending while nobody can look at k / eps, i.e. while k < minit) and the
-                // bookkeeping; with sharded bands the all-reduce of those 7 (or 4) scalars sits between
-                // the sums and the bookkeeping -- one RCCL call per iteration instead of two.
-                const int predict = backtrack == 2 ? 2 : 3;   // beta always comes from rho(alpha)
-                if (!plan->tail_done)
-                hipLaunchKernelGGL(k_iter_sums, dim3(1), dim3(256), 0, st, (const double*)plan->partials,
-                                   plan->last_npartials, (const double*)ws, G_used, pending_end ? 1 : 0, S,
-                                   mdiv_d, predict, allreduce ? 0 : 1);
-                if (allreduce) {
-                    if ((err = reduce_hook(S_PAP, pending_end ? 7 : 4)) != PFB_OK) return err;
-                    if (pending_end)
-                        hipLaunchKernelGGL(k_iter_end_begin, dim3(1), dim3(1), 0, st, S, mdiv_d, predict);
-                    else
-                        hipLaunchKernelGGL(k_iter_begin, dim3(1), dim3(1), 0, st, S, mdiv_d, predict);
-                }
-                pending_end = false;
-                G_used = launch_update_dir<T>(n, xcur, rcur, p, Ap, xnew, rnew, S + S_ALPHA, mdiv, ws, st);
-                if (khost + 1 < minit && khost + 1 < maxit) {
-                    pending_end = true;        // summed by the next iteration's k_iter_sums
-                } else if (!allreduce) {
-                    hipLaunchKernelGGL(k_final_sum_waves_end, dim3(1), dim3(256), 0, st, ws, G_used, S);
-                } else {
-                    hipLaunchKernelGGL(k_final_sum_waves, dim3(1), dim3(256), 0, st, ws, G_used, 4, S,
-                                       (Dst4{{S_RHON, S_NUM, S_DEN, S_ANY}}));
-                    if ((err = reduce_hook(S_RHON, 3)) != PFB_OK) return err;
-                    hipLaunchKernelGGL(k_iter_end, dim3(1), dim3(1), 0, st, S, 1);
-                }
-                { T* t = xcur; xcur = xnew; xnew = t; t = rcur; rcur = rnew; rnew = t; }
-            } else {
-                hipLaunchKernelGGL(k_iter_begin, dim3(1), dim3(1), 0, st, S, mdiv_d, backtrack == 2 ? 1 : 0);
-                PFB_LAUNCH_VEC(T, k_pcg_update, n, (PL{xcur, rcur, p, Ap, xnew, rnew}), (const T*)xcur,
-                               (const T*)rcur, (const T*)p, (const T*)Ap, xnew, rnew,
-                               (const double*)(S + S_ALPHA), mdiv);
-                hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 3, S + S_RHON);
-                if ((err = reduce_hook(S_RHON, 3)) != PFB_OK) return err;
-                hipLaunchKernelGGL(k_iter_end, dim3(1), dim3(1), 0, st, S, 0);
-                { T* t = xcur; xcur = xnew; xnew = t; t = rcur; rcur = rnew; rnew = t; }
-                PFB_LAUNCH_VEC(T, k_pcg_dir, n, (PL{p, rcur}), p, (const T*)rcur, (const double*)(S + S_BETA), mdiv);
-                hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, S + S_ANY);
+            // ONE scalar launch per iteration: the convolution's dots, the previous update's sums
+            // (left pending while nobody can look at k / eps, i.e. while k < minit) and the
+            // bookkeeping; with sharded bands the all-reduce of those 7 (or 4) scalars sits between
+            // the sums and the bookkeeping -- one RCCL call per iteration instead of two.
+            const int predict = backtrack == 2 ? 2 : 3;   // beta always comes from rho(alpha)
+            hipLaunchKernelGGL(k_iter_sums, dim3(1), dim3(256), 0, st, (const double*)plan->partials,
+                               plan->last_npartials, (const double*)ws, G_used, pending_end ? 1 : 0, S,
+                               mdiv_d, predict, allreduce ? 0 : 1);
+            if (allreduce) {
+                if ((err = reduce_hook(S_PAP, pending_end ? 7 : 4)) != PFB_OK) return err;
+                if (pending_end)
+                    hipLaunchKernelGGL(k_iter_end_begin, dim3(1), dim3(1), 0, st, S, mdiv_d, predict);
+                else
+                    hipLaunchKernelGGL(k_iter_begin, dim3(1), dim3(1), 0, st, S, mdiv_d, predict);
             }
+            pending_end = false;
+            G_used = launch_update_dir<T>(n, xcur, rcur, p, Ap, xnew, rnew, S + S_ALPHA, mdiv, ws, st);
+            if (khost + 1 < minit && khost + 1 < maxit) {
+                pending_end = true;        // summed by the next iteration's k_iter_sums
+            } else if (!allreduce) {
+                hipLaunchKernelGGL(k_final_sum_waves_end, dim3(1), dim3(256), 0, st, ws, G_used, S);
+            } else {
+                hipLaunchKernelGGL(k_final_sum_waves, dim3(1), dim3(256), 0, st, ws, G_used, 4, S,
+                                   (Dst4{{S_RHON, S_NUM, S_DEN, S_ANY}}));
+                if ((err = reduce_hook(S_RHON, 3)) != PFB_OK) return err;
+                hipLaunchKernelGGL(k_iter_end, dim3(1), dim3(1), 0, st, S, 1);
+            }
+            { T* t = xcur; xcur = xnew; xnew = t; t = rcur; rcur = rnew; rnew = t; }
             ++khost;
             if (khost < minit && khost < maxit) continue;          // cannot stop yet: no need to look
             if (lookahead && khost < maxit) {

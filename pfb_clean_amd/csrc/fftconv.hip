@@ -475,7 +475,6 @@ int pfb_psfconv_plan_create(int nx, int ny, int nx_psf, int ny_psf, int nband, i
     p->fast = pow2_supported(p) ? 1 : 0;
     if (const char* e = getenv("PFB_FORCE_GENERIC")) { if (atoi(e)) p->fast = 0; }
     int vb = 1;                 // the pow2 kernels are written for VB = 1 (pure transposed T)
-    if (!p->fast) { if (const char* e = getenv("PFB_VB")) { int t = atoi(e); if (t >= 1 && t <= 16) vb = t; } }
     p->partials_per_band = p->fast ? nx / pow2_rows_per_wg(p) : nx;
     if (p->fast) {              // 16-byte column blocks per parity class (fftconv_pow2.hip)
         vb = pow2_nvb(p);
@@ -506,9 +505,6 @@ int pfb_psfconv_plan_create(int nx, int ny, int nx_psf, int ny_psf, int nband, i
     if (rc == PFB_OK && hipMalloc(&p->psf_l, pbytes) != hipSuccess) rc = PFB_ERR_ALLOC;
     if (rc == PFB_OK && hipMalloc((void**)&p->partials, sizeof(double) * 3 * (size_t)nx * nband) != hipSuccess)
         rc = PFB_ERR_ALLOC;
-    if (rc == PFB_OK && (hipMalloc((void**)&p->tail_counter, 256) != hipSuccess ||
-                         hipMemset(p->tail_counter, 0, 256) != hipSuccess))
-        rc = PFB_ERR_ALLOC;
     if (rc == PFB_OK) {
         p->workspace_bytes = tbytes + pbytes;
         rc = (dtype == PFB_F32) ? set_lds_limits<float>(p) : set_lds_limits<double>(p);
@@ -530,7 +526,6 @@ int pfb_psfconv_plan_destroy(pfb_conv_plan* p) {
     if (p->psf_l) (void)hipFree(p->psf_l);
     if (p->T) (void)hipFree(p->T);
     if (p->partials) (void)hipFree(p->partials);
-    if (p->tail_counter) (void)hipFree(p->tail_counter);
     if (p->long_ws) (void)hipFree(p->long_ws);
     pow2_release(p);
     if (p->prof_ev) {

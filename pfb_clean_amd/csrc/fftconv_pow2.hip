@@ -59,11 +59,6 @@ namespace pfb {
 #define PFB_STAMP_ITS 4
 #define PFB_STAMP_FIRST 2
 static __device__ unsigned long long* g_stamp_buf = nullptr;
-// experiment of the diagnostic build (tools/exp_fwd_extra_stream.py): k_row_fwd_pow2q additionally STREAMS the rows of
-// g_xtra_src (same shape as x) through registers, two 8-byte loads per even-bin sweep step, to measure how much extra
-// HBM traffic the kernel absorbs -- the question behind folding the CG update into this kernel
-static __device__ const float* g_xtra_src = nullptr;     // (not void*: hipMemcpyToSymbol's C overload would take the VALUE)
-static __device__ double* g_xtra_sink = nullptr;
 #define STAMP(KID, it, slot)                                                                              \
     do {                                                                                                  \
         const unsigned _si = (unsigned)((it) - PFB_STAMP_FIRST);                                          \
@@ -92,24 +87,12 @@ template <> struct FastCfg<double> { static constexpr int ECOL = 8; static const
 // -> occupancy beats piece size for the latency-bound inverse kernel; the forward kernel
 // keeps 8 rows per workgroup (its strided side is the WRITE, full 128-byte lines).
 template <typename T, int L, int E, int GMAX> constexpr int row_groups();
-#ifndef PFB_ROW_E64_INV          // experiment knobs: elements per thread of the PLAIN fp64 row kernels at L >= 4096 (the persistent
-                                 // inverse kernel has its own: InvPE)
-#define PFB_ROW_E64_INV 8
-#endif
-#ifndef PFB_ROW_E64_FWD
-#define PFB_ROW_E64_FWD 8
-#endif
 template <typename T, int L, bool INVK> struct RowCfg {
-#ifndef PFB_INV_E16          // experiment knob: 16 elements per thread (8-row tiles, 128-byte pieces) in the fp32 inverse rows at L = 2048:
-                             // 128 VGPRs + 232 B of scratch, 0.792 against 0.609 ms per 8-band launch
-#define PFB_INV_E16 0
-#endif
-#ifndef PFB_INV_E16_4096     // 16 elements per thread in the fp32 inverse rows at L = 4096: 4 rows / 64-byte pieces instead of 2 / 32,
-                             // operands read in the epilogue (no registers left to prefetch them): 1.054 against 1.188 ms per 2 x 8192^2
-#define PFB_INV_E16_4096 1
-#endif
-    static constexpr int EMAX = sizeof(T) == 4 ? (INVK ? (((PFB_INV_E16 && L == 2048) || (PFB_INV_E16_4096 && L == 4096)) ? 16 : 8) : 16)
-                                               : (L >= 4096 ? (INVK ? PFB_ROW_E64_INV : PFB_ROW_E64_FWD) : 8);
+    // fp32 inverse rows: 8 elements per thread, except 16 at L = 4096: 4 rows / 64-byte pieces instead of 2 / 32, operands
+    // read in the epilogue (no registers left to prefetch them): 1.054 against 1.188 ms per 2 x 8192^2.  (16 at L = 2048,
+    // 8-row tiles with 128-byte pieces: 128 VGPRs + 232 B of scratch, 0.792 against 0.609 ms per 8-band launch.)
+    // fp64: 8 elements per thread (the persistent inverse kernel has its own: InvPE)
+    static constexpr int EMAX = sizeof(T) == 4 ? (INVK ? (L == 4096 ? 16 : 8) : 16) : 8;
     static constexpr int E = (L / 64 < 8) ? 8 : (L / 64 > EMAX ? EMAX : L / 64);
     static constexpr int TPB = L / E;
     static constexpr bool WAVE = TPB <= 64;
@@ -134,10 +117,8 @@ constexpr int LDS_BUDGET = 152 * 1024;
 // ... and 4 up to H = 1024 (the plain, non-persistent column kernel): at these sizes a launch is ONE wave of workgroups, each a
 // serial chain of four transforms; twice the threads per column halve the chain (1024^2 x 8 fp32: col 93.8 -> 73.2 us,
 // 1024^2 x 1: 23.6 -> 18.1, fp64 27.6 -> 24.1; profiles/r03_ab_col_e4_small.md)
-#ifndef PFB_COL_E4_MAXH
-#define PFB_COL_E4_MAXH 1024
-#endif
-template <typename T, int H> constexpr int ecol() { return (H >= 8192 && sizeof(T) == 8) ? 16 : (H <= PFB_COL_E4_MAXH && H >= 64 ? 4 : FastCfg<T>::ECOL); }
+constexpr int COL_E4_MAXH = 1024;
+template <typename T, int H> constexpr int ecol() { return (H >= 8192 && sizeof(T) == 8) ? 16 : (H <= COL_E4_MAXH && H >= 64 ? 4 : FastCfg<T>::ECOL); }
 
 // rows per workgroup for the row kernels
 template <typename T, int L, int E, int GMAX>
@@ -171,25 +152,6 @@ __device__ __forceinline__ Blk<T, NVB> loadb_nt(const cplx<T>* src) {
     return b;
 }
 
-#ifndef PFB_FWD_ROT
-#define PFB_FWD_ROT 0
-#endif
-#ifndef PFB_COL_ROT
-#define PFB_COL_ROT 0
-#endif
-#ifndef PFB_FWD_ABL             // ablation builds of k_row_fwd_pow2q (timing only, results are wrong): 1 no next-tile rows, 4 no stores
-#define PFB_FWD_ABL 0           // of the sweeps, 8 no transforms
-#endif
-template <typename T, int NVB>
-__device__ __forceinline__ void storeb(cplx<T>* dst, const Blk<T, NVB>& b);
-// the strided stores of the forward sweeps (an ablation build keeps the values alive without the memory operation)
-template <typename T, int NVB>
-__device__ __forceinline__ void storeb_sweep(cplx<T>* dst, const Blk<T, NVB>& b) {
-    if constexpr ((PFB_FWD_ABL & 4) != 0) {
-#pragma unroll
-        for (int c = 0; c < NVB; ++c) asm volatile("" :: "v"(b.c[c].x), "v"(b.c[c].y));
-    } else storeb<T, NVB>(dst, b);
-}
 template <typename T, int NVB>
 __device__ __forceinline__ void storeb(cplx<T>* dst, const Blk<T, NVB>& b) {
     *reinterpret_cast<Blk<T, NVB>*>(dst) = b;
@@ -343,15 +305,12 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
     // L2" going to HBM: +1 GB per 8-band launch).  aw = a .* w_P^n is formed at load time and
     // parked in registers; its live range (first FFT pair) does not overlap ev's (second pair),
     // so the peak register demand is unchanged.
-#ifndef PFB_COL_PREQ2
-#define PFB_COL_PREQ2 1
-#endif
     // PREQ2 (8192-point fp32 column pairs): a .* w_P^n is NOT parked in registers -- the second parity re-reads a
     // (an L2 / Infinity-Cache hit: this workgroup fetched it microseconds ago) -- and its registers take the PSF slices,
     // requested a few per FFT pass: psf_e lands during the first transform, psf_o during the second.  2.19 -> 2.00 ms
-    // per 2 x 8192^2 (128 VGPRs + 244 B of scratch; = 2 with the even-bin result round-tripping through T: 160 B,
+    // per 2 x 8192^2 (128 VGPRs + 244 B of scratch; with the even-bin result round-tripping through T as well: 160 B,
     // 2.03 ms).  The same idea lost on the fp64 columns (fp64-issue and LDS bound); this one is latency bound.
-    constexpr bool PREQ2 = PFB_COL_PREQ2 && sizeof(T) == 4 && H >= 8192;
+    constexpr bool PREQ2 = sizeof(T) == 4 && H >= 8192;
     cplx<T> vv[NVB][E], aw[PREQ2 ? 1 : NVB][PREQ2 ? 1 : E];
     {
         const cplx<T>* tw2 = twP + t;
@@ -368,20 +327,12 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             }
         }
     }
-    // PREQ (OFF): request psf_e BEFORE the first transform and psf_o before the second, so that two of the three HBM
-    // latencies of a block hide behind a transform.  Meant for the 8192-point fp64 columns (one 512-thread workgroup per
-    // CU, 256 VGPRs per thread; the persistent kernel does not fit there), but vv + aw + q are 192 registers before the
-    // radix-16 butterfly's own 64: 84 -> 556 bytes of scratch per lane.  Kept for the record, not compiled in.
-    constexpr bool PREQ = PREQ2 || (false && sizeof(T) == 8 && H >= 8192);
-    constexpr bool QSPR = PREQ2;
+    // (Requesting psf_e before the first transform and psf_o before the second in the 8192-point fp64 columns: vv + aw + q
+    // are 192 registers before the radix-16 butterfly's own 64, 84 -> 556 bytes of scratch per lane.)
     constexpr int NPQ = F::NPASS;
-    Blk<T, NVB> q[PREQ ? E : 1];
-    if constexpr (PREQ && !QSPR) {
-#pragma unroll
-        for (int j = 0; j < E; ++j) q[j] = loadb<T, NVB>(pe + NVB * TPB * j);
-    }
+    Blk<T, NVB> q[PREQ2 ? E : 1];
     // ---- even bins of the column transform
-    if constexpr (QSPR) {
+    if constexpr (PREQ2) {
         F::template runN<false, NVB>(vv, lds, t, ptw, [&](auto k) {
             constexpr int K = decltype(k)::value;
 #pragma unroll
@@ -392,15 +343,11 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
     for (int j = 0; j < E; ++j) {
         Blk<T, NVB> p;
-        if constexpr (PREQ) p = q[j]; else p = loadb<T, NVB>(pe + NVB * TPB * j);
+        if constexpr (PREQ2) p = q[j]; else p = loadb<T, NVB>(pe + NVB * TPB * j);
 #pragma unroll
         for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * p.c[c];
     }
-    if constexpr (PREQ && !QSPR) {
-#pragma unroll
-        for (int j = 0; j < E; ++j) q[j] = loadb<T, NVB>(po + NVB * TPB * j);
-    }
-    if constexpr (QSPR) {
+    if constexpr (PREQ2) {
         F::template runN<true, NVB>(vv, lds, t, ptw, [&](auto k) {
             constexpr int K = decltype(k)::value;
 #pragma unroll
@@ -408,17 +355,11 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         });
     } else
     F::template runN<true, NVB>(vv, lds, t, ptw);
-    // PREQ2 == 2: the even-bin result does not wait in registers either: a is re-read first, then the even-bin result
-    // takes its place in T (same addresses, same thread: the loads have landed before the stores are issued) and comes
-    // back for the final combination -- both round trips stay in the L2 / Infinity Cache
-    constexpr bool EVG = PREQ2 && PFB_COL_PREQ2 >= 2;
-    cplx<T> ev[EVG ? 1 : NVB][EVG ? 1 : E];
-    if constexpr (!EVG) {
+    cplx<T> ev[NVB][E];
 #pragma unroll
-        for (int j = 0; j < E; ++j) {
+    for (int j = 0; j < E; ++j) {
 #pragma unroll
-            for (int c = 0; c < NVB; ++c) { ev[c][j] = vv[c][j]; if constexpr (!PREQ2) vv[c][j] = aw[c][j]; }
-        }
+        for (int c = 0; c < NVB; ++c) { ev[c][j] = vv[c][j]; if constexpr (!PREQ2) vv[c][j] = aw[c][j]; }
     }
     if constexpr (PREQ2) {
         const cplx<T>* tw2 = twP + t;
@@ -426,18 +367,6 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         Blk<T, NVB> a2[E];
 #pragma unroll
         for (int j = 0; j < E; ++j) if (active) a2[j] = loadb<T, NVB>(col2 + NVB * TPB * j);
-        if constexpr (EVG) {
-            __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0): a is in registers before its place is overwritten
-            if (active) {
-#pragma unroll
-                for (int j = 0; j < E; ++j) {
-                    Blk<T, NVB> o;
-#pragma unroll
-                    for (int c = 0; c < NVB; ++c) o.c[c] = vv[c][j];
-                    storeb<T, NVB>(col2 + NVB * TPB * j, o);
-                }
-            }
-        }
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             const cplx<T> w = tw2[TPB * j];
@@ -450,7 +379,7 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
     for (int j = 0; j < E; ++j) {
         Blk<T, NVB> p;
-        if constexpr (PREQ) p = q[j]; else p = loadb<T, NVB>(po + NVB * TPB * j);
+        if constexpr (PREQ2) p = q[j]; else p = loadb<T, NVB>(po + NVB * TPB * j);
 #pragma unroll
         for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * p.c[c];
     }
@@ -461,14 +390,8 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         for (int j = 0; j < E; ++j) {
             const cplx<T> w = tw3[TPB * j];
             Blk<T, NVB> o;
-            if constexpr (EVG) {
-                const Blk<T, NVB> e2 = loadb<T, NVB>(opaque(col) + NVB * TPB * j);
 #pragma unroll
-                for (int c = 0; c < NVB; ++c) o.c[c] = e2.c[c] + mulc(vv[c][j], w);
-            } else {
-#pragma unroll
-                for (int c = 0; c < NVB; ++c) o.c[c] = ev[c][j] + mulc(vv[c][j], w);
-            }
+            for (int c = 0; c < NVB; ++c) o.c[c] = ev[c][j] + mulc(vv[c][j], w);
             storeb<T, NVB>(col + NVB * TPB * j, o);
         }
     }
@@ -484,14 +407,14 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 // so that in steady state no load latency is exposed; the column twiddles w_P^n are
 // loaded once per kernel and stay in registers.
 // DB: a second set of exchange buffers (when the LDS holds it) -- one barrier per exchange instead of two.
-// SPR: the loads are not issued in two bursts (top of the trip / after the first FFT) but a few per FFT PASS
+// The loads are not issued in two bursts (top of the trip / after the first FFT) but a few per FFT PASS
 // (RegFft pass hook): a burst of 16 x 16-byte loads per thread blocks every wave of the workgroup at issue for ~3.8 us
 // of a 16 us trip (profiles/r02_a_phase_stamps_*), with nothing computing meanwhile.  Per trip:
 //     FFT (even)   <- first half of the NEXT item's a          multiply by psf_e (requested during the last IFFT)
 //     IFFT (even)  <- psf_o of this item
 //     FFT (odd)    <- second half of the next item's a         multiply by psf_o
 //     IFFT (odd)   <- psf_e of the NEXT item
-template <typename T, int H, int E, bool DB = false, bool SPR = false, bool NT = false>
+template <typename T, int H, int E, bool DB, bool NT>
 __global__ void __launch_bounds__((col_groups<H, E>() * (H / E)), 2)
 k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             const cplx<T>* __restrict__ twP, const cplx<T>* __restrict__ ptwc,
@@ -524,12 +447,7 @@ k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         return psf_l + (size_t)(band0 + bstep * bl) * psf_band + ((size_t)blk * 2 * H + t) * NVB;
     };
 
-    // PFB_COL_ROT: the workgroup -> item map rotates by that many workgroups per trip (see k_row_inv_pow2p)
-    auto item_of = [&](int it) -> int {
-        if constexpr (PFB_COL_ROT != 0)
-            return (int)(((unsigned)blockIdx.x + (unsigned)it * (unsigned)PFB_COL_ROT) % gridDim.x) * GC + g + it * stride;
-        else return blockIdx.x * GC + g + it * stride;
-    };
+    auto item_of = [&](int it) -> int { return blockIdx.x * GC + g + it * stride; };
     int item = item_of(0);
     Blk<T, NVB> an[E];
     Blk<T, NVB> q[E];
@@ -544,7 +462,7 @@ k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
                 for (int c = 0; c < NVB; ++c) an[j].c[c] = cplx<T>(0, 0);
             }
         }
-        if constexpr (SPR) {
+        {
             const cplx<T>* pe0 = psf_of(act ? item : 0);
 #pragma unroll
             for (int j = 0; j < E; ++j) q[j] = NT ? loadb_nt<T, NVB>(pe0 + NVB * TPB * j) : loadb<T, NVB>(pe0 + NVB * TPB * j);
@@ -569,19 +487,6 @@ k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
             for (int c = 0; c < NVB; ++c) { vv[c][j] = an[j].c[c]; aw[c][j] = vv[c][j] * tw[j]; }
         }
-        if constexpr (!SPR) {
-            // in issue order (vmcnt retires in order): psf_e of this item, then a of the next
-#pragma unroll
-            for (int j = 0; j < E; ++j) q[j] = NT ? loadb_nt<T, NVB>(pe + NVB * TPB * j) : loadb<T, NVB>(pe + NVB * TPB * j);
-#pragma unroll
-            for (int j = 0; j < E; ++j) {
-                if (nact) an[j] = loadb<T, NVB>(cn + NVB * TPB * j);
-                else {
-#pragma unroll
-                    for (int c = 0; c < NVB; ++c) an[j].c[c] = cplx<T>(0, 0);
-                }
-            }
-        }
         // loads [lo, hi) of a group of CNT, slice k of NP
         auto ld_an = [&](auto k, int base) {
             constexpr int K = decltype(k)::value;
@@ -592,8 +497,7 @@ k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         };
         STAMP(1, it, 1);
         // ---- even bins
-        if constexpr (SPR) F::template runN<false, NVB, 0>(vv, lds, t, ltw, [&](auto k) { ld_an(k, 0); });
-        else F::template runN<false, NVB, 0>(vv, lds, t, ltw);
+        F::template runN<false, NVB, 0>(vv, lds, t, ltw, [&](auto k) { ld_an(k, 0); });
         STAMP(1, it, 2);
 #pragma unroll
         for (int j = 0; j < E; ++j) {
@@ -601,17 +505,11 @@ k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * q[j].c[c];
         }
         STAMP(1, it, 3);
-        if constexpr (SPR) {
-            F::template runN<true, NVB, X1>(vv, lds, t, ltw, [&](auto k) {
-                constexpr int K = decltype(k)::value;
+        F::template runN<true, NVB, X1>(vv, lds, t, ltw, [&](auto k) {
+            constexpr int K = decltype(k)::value;
 #pragma unroll
-                for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) q[j] = NT ? loadb_nt<T, NVB>(po + NVB * TPB * j) : loadb<T, NVB>(po + NVB * TPB * j);
-            });
-        } else {
-#pragma unroll
-            for (int j = 0; j < E; ++j) q[j] = NT ? loadb_nt<T, NVB>(po + NVB * TPB * j) : loadb<T, NVB>(po + NVB * TPB * j);
-            F::template runN<true, NVB, X1>(vv, lds, t, ltw);
-        }
+            for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) q[j] = NT ? loadb_nt<T, NVB>(po + NVB * TPB * j) : loadb<T, NVB>(po + NVB * TPB * j);
+        });
         STAMP(1, it, 4);
         cplx<T> ev[NVB][E];
 #pragma unroll
@@ -620,8 +518,7 @@ k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             for (int c = 0; c < NVB; ++c) { ev[c][j] = vv[c][j]; vv[c][j] = aw[c][j]; }
         }
         // ---- odd bins
-        if constexpr (SPR) F::template runN<false, NVB, 0>(vv, lds, t, ltw, [&](auto k) { ld_an(k, E / 2); });
-        else F::template runN<false, NVB, 0>(vv, lds, t, ltw);
+        F::template runN<false, NVB, 0>(vv, lds, t, ltw, [&](auto k) { ld_an(k, E / 2); });
         STAMP(1, it, 5);
 #pragma unroll
         for (int j = 0; j < E; ++j) {
@@ -629,15 +526,11 @@ k_col_pow2p(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * q[j].c[c];
         }
         STAMP(1, it, 6);
-        if constexpr (SPR) {
-            F::template runN<true, NVB, X1>(vv, lds, t, ltw, [&](auto k) {
-                constexpr int K = decltype(k)::value;
+        F::template runN<true, NVB, X1>(vv, lds, t, ltw, [&](auto k) {
+            constexpr int K = decltype(k)::value;
 #pragma unroll
-                for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) q[j] = NT ? loadb_nt<T, NVB>(pen + NVB * TPB * j) : loadb<T, NVB>(pen + NVB * TPB * j);
-            });
-        } else {
-            F::template runN<true, NVB, X1>(vv, lds, t, ltw);
-        }
+            for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) q[j] = NT ? loadb_nt<T, NVB>(pen + NVB * TPB * j) : loadb<T, NVB>(pen + NVB * TPB * j);
+        });
         STAMP(1, it, 7);
         if (active) {
 #pragma unroll
@@ -684,10 +577,7 @@ struct ColX {
     static_assert(E == 8, "root32: the twiddle constants are the 4E-th roots of unity");
 };
 
-#ifndef PFB_COLX_QLATE
-#define PFB_COLX_QLATE 1
-#endif
-template <typename T, int H, int E, bool NT = false, bool QLATE = (PFB_COLX_QLATE != 0)>
+template <typename T, int H, int E, bool NT = false>
 __global__ void __launch_bounds__((ColX<T, H, E>::NT), 2)
 k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             const cplx<T>* __restrict__ twP, const cplx<T>* __restrict__ ptwc,
@@ -722,15 +612,10 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
     {
         const bool act = item < nitems;
         const cplx<T>* c0 = col_of(act ? item : 0);
-        const cplx<T>* p0 = psf_of(act ? item : 0);
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             al[j] = loadb<T, NVB>(c0 + NVB * TPB * j);
             ah[j] = loadb<T, NVB>(c0 + NVB * (HS + TPB * j));
-        }
-        if constexpr (!QLATE) {
-#pragma unroll
-            for (int j = 0; j < E; ++j) q[j] = ldq(p0 + NVB * TPB * j);
         }
     }
     __syncthreads();                                            // tables visible
@@ -742,7 +627,6 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         const int nxt = item + stride;
         const bool nact = nxt < nitems;                         // a trip past the end re-reads a valid block and drops it
         const cplx<T>* cn = col_of(nact ? nxt : (active ? item : 0));
-        const cplx<T>* psn = psf_of(nact ? nxt : (active ? item : 0));
         cplx<T> vv[NVB][E], ol[NVB][E];
         // w_P^t, laundered at every use: t and the table are loop invariant, and the optimiser would otherwise keep
         // w, w^2, w^3 of all E samples live across the whole item loop
@@ -754,8 +638,8 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
                 for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * q[j].c[c];
             }
         };
-        // PSF slices: QLATE requests the slice of round r inside the FORWARD transform of round r (one transform of
-        // lead) instead of inside the inverse transform of the round before (two): q is then dead across every
+        // PSF slices: the slice of round r is requested inside the FORWARD transform of round r (one transform of
+        // lead), not inside the inverse transform of the round before (two): q is then dead across every
         // accumulate / combine step, which is where the registers run out (fp64: 140 B of scratch per lane = 2.35 GB of
         // spill traffic per 2-band launch, a quarter of the kernel's HBM bytes -- profiles/r03_m_c5_hbm_traffic.json)
         auto qslice = [&](auto k, const cplx<T>* pq) __attribute__((always_inline)) {
@@ -763,17 +647,11 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
             for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) q[j] = ldq(pq + NVB * TPB * j);
         };
-        auto fft_q = [&](const cplx<T>* pq, auto&& extra) __attribute__((always_inline)) {     // forward transform of a round
-            F::template runN<false, NVB>(vv, lds, t, ltw, [&](auto k) {
-                if constexpr (QLATE) qslice(k, pq);
-                extra(k);
-            });
+        auto fft_q = [&](const cplx<T>* pq) __attribute__((always_inline)) {     // forward transform of a round
+            F::template runN<false, NVB>(vv, lds, t, ltw, [&](auto k) { qslice(k, pq); });
         };
-        auto ifft_q = [&](const cplx<T>* pq, auto&& extra) __attribute__((always_inline)) {   // inverse transform (!QLATE: requests the slice at pq)
-            F::template runN<true, NVB>(vv, lds, t, ltw, [&](auto k) {
-                if constexpr (!QLATE) qslice(k, pq);
-                else extra(k);
-            });
+        auto ifft_q = [&](auto&& extra) __attribute__((always_inline)) {        // inverse transform
+            F::template runN<true, NVB>(vv, lds, t, ltw, [&](auto k) { extra(k); });
         };
         auto none = [](auto) {};
         STAMP(1, it, 0);
@@ -783,10 +661,10 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
             for (int c = 0; c < NVB; ++c) vv[c][j] = al[j].c[c] + ah[j].c[c];
         }
-        fft_q(ps, none);
+        fft_q(ps);
         STAMP(1, it, 1);
         mulq();
-        ifft_q(ps + (size_t)2 * HS * NVB, none);
+        ifft_q(none);
         STAMP(1, it, 2);
 #pragma unroll
         for (int j = 0; j < E; ++j) {
@@ -804,10 +682,10 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             }
         }
         STAMP(1, it, 3);
-        fft_q(ps + (size_t)2 * HS * NVB, none);
+        fft_q(ps + (size_t)2 * HS * NVB);
         STAMP(1, it, 4);
         mulq();
-        ifft_q(ps + (size_t)1 * HS * NVB, none);
+        ifft_q(none);
         STAMP(1, it, 5);
         {
             const cplx<T> w1 = wt(), wt2 = w1 * w1;
@@ -844,9 +722,9 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         }
         STAMP(1, it, 6);
         // the next item's column: upper half into a_hi's registers (free since the inputs of rounds 1 and 3 were formed),
-        // lower half into a_lo's (free once round 3's input has moved to vv).  Without QLATE they ride in the forward
-        // transforms of rounds 1 / 3; with it those carry the PSF slices and the column rides in the inverse transforms,
-        // so that no transform has more than five arrays of E blocks live.
+        // lower half into a_lo's (free once round 3's input has moved to vv).  The forward transforms of rounds 1 / 3 carry
+        // the PSF slices and the column rides in the inverse transforms, so that no transform has more than five arrays
+        // of E blocks live.
         auto ld_ah = [&](auto k) __attribute__((always_inline)) {
             constexpr int K = decltype(k)::value;
 #pragma unroll
@@ -857,10 +735,10 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
             for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) al[j] = loadb<T, NVB>(cn + NVB * TPB * j);
         };
-        if constexpr (QLATE) fft_q(ps + (size_t)1 * HS * NVB, none); else fft_q(ps + (size_t)1 * HS * NVB, ld_ah);
+        fft_q(ps + (size_t)1 * HS * NVB);
         STAMP(1, it, 7);
         mulq();
-        ifft_q(ps + (size_t)3 * HS * NVB, ld_ah);
+        ifft_q(ld_ah);
         STAMP(1, it, 8);
         {
             const cplx<T> w1t = wt();
@@ -885,10 +763,10 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
             for (int c = 0; c < NVB; ++c) vv[c][j] = al[j].c[c];
         }
         STAMP(1, it, 9);
-        if constexpr (QLATE) fft_q(ps + (size_t)3 * HS * NVB, none); else fft_q(ps + (size_t)3 * HS * NVB, ld_al);
+        fft_q(ps + (size_t)3 * HS * NVB);
         STAMP(1, it, 10);
         mulq();
-        ifft_q(psn, ld_al);
+        ifft_q(ld_al);
         STAMP(1, it, 11);
         if (active) {
             const cplx<T> w1t = wt(), w3t = w1t * (w1t * w1t);
@@ -1009,12 +887,9 @@ __device__ __forceinline__ void row_fwd_post(const cplx<T> (&z)[E], const cplx<T
     constexpr int NBP = PAR ? L / NVB : NBE;                 // blocks of this parity
     constexpr int BSTEP = NT / G;
     cplx<T>* Tp = Tb + ((size_t)(PAR ? NBE : 0) * nx + i0 + rr) * NVB;
-#ifndef PFB_FWD_LIN
-#define PFB_FWD_LIN 1
-#endif
     constexpr int MS = NVB * BSTEP;               // m advances by MS per trip
     // (fp32: 0.0564 -> 0.0547 ms at 2048^2 x 4; the fp64 sweeps measured 1-2 % slower with it and keep the plain form)
-    if constexpr (PFB_FWD_LIN && sizeof(T) == 4 && (L / NVB) % BSTEP == 0 && MS % 16 == 0) {
+    if constexpr (sizeof(T) == 4 && (L / NVB) % BSTEP == 0 && MS % 16 == 0) {
         // incremental addressing (see fwdp_post_lin): the trip advances every index by a multiple of 16, so the two
         // padded LDS streams, the twiddle stream and the store address move by constants instead of being rebuilt
         // from the block index (selects, two pad()s, a 64-bit multiply per trip); the Nyquist block of the even
@@ -1141,39 +1016,28 @@ struct FwdP {
     using F = RegFft<T, L, EOK, false, 0, true, true>;
     static constexpr int TPR = L / EOK;               // threads per row
     // fp64 rows of 4096 points: two rows fill the LDS -> 512-thread workgroups (256 registers per thread)
-#ifndef PFB_FWDP_HALF       // experiment: 2048-point fp32 rows as 4-row, 512-thread tiles with small tables (74 KB of LDS): TWO
-#define PFB_FWDP_HALF 0     // independent workgroups per CU, 64-byte pieces XCD-paired to full lines
-#endif
-    static constexpr bool HALF = PFB_FWDP_HALF && sizeof(T) == 4 && L == 2048;
-    static constexpr int NT = ((BIG && sizeof(T) == 8) || HALF) ? 512 : 1024;
+    static constexpr int NT = (BIG && sizeof(T) == 8) ? 512 : 1024;
     static constexpr int G = NT / TPR;
     static constexpr int STRIDE = F::LDS_ELEMS + 4;
     static constexpr int NVB = FastCfg<T>::NVB;
     static constexpr int NBE = (L + NVB) / NVB;
     static constexpr int NBO = L / NVB;
     static constexpr int BSTEP = NT / G;
-    static constexpr bool SMT = BIG || HALF;
+    static constexpr bool SMT = BIG;
     static constexpr int NTM = SMT ? NVB * BSTEP : L; // entries of the w_M table kept in the LDS
-    static constexpr int WG_PER_CU = HALF ? 2 : 1;
+    static constexpr int WG_PER_CU = 1;
     static constexpr int PTWP = (F::PTWC + 1) & ~1;
     static constexpr size_t LDS = sizeof(cplx<T>) * ((size_t)PTWP + NTM + (size_t)G * STRIDE);
     // (an fp64 version with two-row 512-thread tiles -- what the LDS allows -- writes 32-byte pieces and
     // measured 0.90 vs 0.54 ms for the plain kernel: not used)
     // measured: 0.50 -> 0.42 ms at ny = 4096 (x 8 bands of 4096 rows); at ny = 2048 the plain
     // wave-per-row kernel (E = 16, barrier-free exchanges) is 6 % faster than this one with E = 8
-#ifndef PFB_FWDP_E8          // experiment knob: the persistent forward kernels also at 8 elements per thread (fp32 ny = 2048):
-                             // 0.0633 (sequential parities) / 0.0677 ms against 0.0561 ms for the plain kernel at 2048^2 x 4
-#define PFB_FWDP_E8 0
-#endif
+    // (at 8 elements per thread, fp32 ny = 2048: 0.0633 ms against 0.0561 ms for the plain kernel at 2048^2 x 4)
     // sweep step K advances the bin index by MS = NVB BSTEP: w_M^(MS K) = root32(KR K)
     static constexpr int KR = (32 * NVB * BSTEP) / (2 * L);
     // fp64 rows of 4096 points as 2-row 512-thread persistent tiles: 1.87 against 1.21 ms per 2 x 8192^2 for the plain
-    // kernel (profiles/r03_i_*; the same verdict as at 2048 points in round 1) -- PFB_FWDP_F64BIG=1 builds them anyway
-#ifndef PFB_FWDP_F64BIG
-#define PFB_FWDP_F64BIG 0
-#endif
-    static constexpr bool OK = (E == 16 || (PFB_FWDP_E8 && E == 8 && sizeof(T) == 4)) && LDS <= (size_t)160 * 1024 &&
-                               (PFB_FWDP_F64BIG || !(BIG && sizeof(T) == 8)) &&
+    // kernel (profiles/r03_i_*; the same verdict as at 2048 points in round 1): not used
+    static constexpr bool OK = E == 16 && LDS <= (size_t)160 * 1024 && !(BIG && sizeof(T) == 8) &&
                                (!SMT || (EOK == 16 && 32 * TPR == 2 * L && KR * 2 * L == 32 * NVB * BSTEP && NTM >= TPR));
     // w_M^(t + TPR j) from the table in the LDS
     __device__ __forceinline__ static cplx<T> tw_row(const cplx<T>* ltm, int t, int j) {
@@ -1194,13 +1058,7 @@ struct FwdP {
     }
 };
 
-template <typename T, int L, int PAR, int K, int NIT, typename Hook>
-__device__ __forceinline__ void post_steps(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1, cplx<T>* Tp, int nx,
-                                           int bi, const Hook& hook);
 // hook(PassIdx<k>): called at the top of sweep step k (the kernel issues a slice of the next tile's loads there)
-#ifndef PFB_FWD_LIN
-#define PFB_FWD_LIN 1
-#endif
 template <typename T, int L, int PAR, typename Hook>
 __device__ __forceinline__ void fwdp_post_lin(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1,
                                               cplx<T>* __restrict__ Tb, int nx, int i0, int rr, int bi, const Hook& hook);
@@ -1208,55 +1066,13 @@ template <typename T, int L, int PAR, typename Hook = NoPassHook>
 __device__ __forceinline__ void fwdp_post(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1,
                                           cplx<T>* __restrict__ Tb, int nx, int i0, int rr, int bi,
                                           const Hook& hook = Hook()) {
-    using P = FwdP<T, L>;
-    constexpr int NVB = P::NVB;
-    constexpr int NBP = PAR ? P::NBO : P::NBE;
-    constexpr int NIT = (NBP + P::BSTEP - 1) / P::BSTEP;
-#if PFB_FWD_LIN
     fwdp_post_lin<T, L, PAR, Hook>(zr, ltm, wq1, Tb, nx, i0, rr, bi, hook);
-#else
-    cplx<T>* Tp = Tb + ((size_t)(PAR ? P::NBE : 0) * nx + i0 + rr) * NVB;
-    post_steps<T, L, PAR, 0, NIT>(zr, ltm, wq1, Tp, nx, bi, hook);
-#endif
 }
 
-template <typename T, int L, int PAR, int K, int NIT, typename Hook>
-__device__ __forceinline__ void post_steps(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1, cplx<T>* Tp, int nx,
-                                           int bi, const Hook& hook) {
-    using P = FwdP<T, L>;
-    using F = typename P::F;
-    constexpr int NVB = P::NVB;
-    constexpr int NBP = PAR ? P::NBO : P::NBE;
-    if constexpr (K < NIT) {
-        constexpr int k = K;
-        hook(PassIdx<K>{});
-        int b = bi + k * P::BSTEP;
-        if (b >= NBP) b = NBP - 1;                 // clamped: duplicates of the last block, same data
-        Blk<T, NVB> o;
-#pragma unroll
-        for (int h = 0; h < NVB; ++h) {
-            const int m = NVB * b + h;
-            const bool valid = PAR || m <= L;
-            const int ia = PAR ? m : (m >= L ? 0 : m);
-            const int ib = PAR ? (L - 1 - m) : ((m == 0 || m > L) ? 0 : L - m);
-            cplx<T> w = ltm[m < L ? m : 0];
-            if (PAR) w = w * wq1;
-            else if (m >= L) w = cplx<T>(T(-1), T(0));              // w_Q^(2L) = -1
-            const cplx<T> zv = zr[F::pad(ia)];
-            const cplx<T> zm = zr[F::pad(ib)];
-            o.c[h] = T(0.5) * addrot<false>(addc(zv, zm), w * subc(zv, zm));
-            if (!valid) o.c[h] = cplx<T>(0, 0);
-        }
-        storeb_sweep<T, NVB>(Tp + (size_t)b * nx * NVB, o);
-        __builtin_amdgcn_sched_barrier(0);         // keep the sweeps' LDS reads from piling up (spills)
-        post_steps<T, L, PAR, K + 1, NIT, Hook>(zr, ltm, wq1, Tp, nx, bi, hook);
-    }
-}
-
-// ---- the same sweep with strength-reduced addressing (PFB_FWD_LIN, default on).
-// The sweep above recomputes for every step the clamped block index, two padded LDS indices per value and a 64-bit
-// `block * nx` product for the store: per tile and thread 18 v_mad_u64_u32 / v_mul_lo_u32 (quarter-rate on CDNA) and
-// ~150 index instructions next to ~230 of arithmetic (ISA count).  A step advances m by NVB * BSTEP, a multiple of 16:
+// ---- the sweep with strength-reduced addressing.
+// The plain form of the sweep (removed, the code is at commit e9a762c) recomputed for every step the clamped block
+// index, two padded LDS indices per value and a 64-bit `block * nx` product for the store: per tile and thread 18
+// v_mad_u64_u32 / v_mul_lo_u32 (quarter-rate on CDNA) and ~150 index instructions next to ~230 of arithmetic (ISA count).  A step advances m by NVB * BSTEP, a multiple of 16:
 // pad(m + 16 c) = pad(m) + 17 c, so each LDS stream is ONE base register with compile-time offsets; the store address
 // is a workgroup-uniform base (band + step, scalar unit) plus a 32-bit per-thread offset that never changes.
 // The irregular items -- m = 0 in the first even-bin step, and the last even-bin step, which holds only block NBE - 1
@@ -1282,7 +1098,7 @@ __device__ __forceinline__ void post_steps_lin(const cplx<T>* const (&za)[FastCf
             if constexpr (PAR == 0 && K == 0) { if (first0 && h == 0) zm = zv; }      // m = 0: both are z[0]
             o.c[h] = T(0.5) * addrot<false>(addc(zv, zm), w * subc(zv, zm));
         }
-        storeb_sweep<T, NVB>(ub + (size_t)K * ustep + voff, o);
+        storeb<T, NVB>(ub + (size_t)K * ustep + voff, o);
         __builtin_amdgcn_sched_barrier(0);
         post_steps_lin<T, L, PAR, K + 1, NREG, Hook>(za, zb, lw, wq1, ub, ustep, voff, first0, hook);
     }
@@ -1323,151 +1139,15 @@ __device__ __forceinline__ void fwdp_post_lin(const cplx<T>* zr, const cplx<T>* 
         o.c[0] = T(0.5) * addrot<false>(addc(z0, z0), cplx<T>(T(-1), T(0)) * subc(z0, z0));
 #pragma unroll
         for (int h = 1; h < NVB; ++h) o.c[h] = cplx<T>(0, 0);
-        storeb_sweep<T, NVB>(ub + (size_t)(NBP - 1) * nx * NVB + (unsigned)(i0 + rr) * NVB, o);
+        storeb<T, NVB>(ub + (size_t)(NBP - 1) * nx * NVB + (unsigned)(i0 + rr) * NVB, o);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
-// SPR: the next tile's rows are requested two at a time inside the even-bin sweep (its beam rows inside the odd-bin
-// sweep) instead of in one burst before it: the burst parks all 16 waves at issue (profiles/r02_a_phase_stamps_*).
-template <typename T, int L, bool BEAM, bool SPR = false>
-__global__ void __launch_bounds__((FwdP<T, L>::NT))
-k_row_fwd_pow2p(const T* __restrict__ x, const T* __restrict__ beam, cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
-                const cplx<T>* __restrict__ ptwc, FastDims d, int band0, int tiles_per_band, int ntiles,
-                cplx<T> wq1) {
-    using P = FwdP<T, L>;
-    using F = typename P::F;
-    constexpr int E = P::EOK, TPB = F::TPB, G = P::G, NT = P::NT;
-    using V2 = typename vec2<T>::type;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    cplx<T>* ltw = reinterpret_cast<cplx<T>*>(smem);
-    cplx<T>* ltm = ltw + P::PTWP;
-    cplx<T>* lds0 = ltm + P::NTM;
-    int vb = blockIdx.x;
-    if (vb >= ntiles) return;
-    for (int k = threadIdx.x; k < F::PTWC; k += NT) ltw[k] = ptwc[k];
-    for (int k = threadIdx.x; k < P::NTM; k += NT) ltm[k] = twM[k];
-    V2 xa[E], ba[BEAM ? E : 1];
-    {
-        const int bl = vb / tiles_per_band, i0 = P::tile_row(vb - bl * tiles_per_band, tiles_per_band);
-        const int g = threadIdx.x / TPB, t = threadIdx.x % TPB;
-        const size_t off = (size_t)bl * d.xband + (size_t)(i0 + g) * d.xpitch;
-        const V2* xr = reinterpret_cast<const V2*>(x + off) + t;
-#pragma unroll
-        for (int j = 0; j < E; ++j) xa[j] = xr[TPB * j];
-        if constexpr (BEAM) {
-            const V2* br = reinterpret_cast<const V2*>(beam + off) + t;
-#pragma unroll
-            for (int j = 0; j < E; ++j) ba[j] = br[TPB * j];
-        }
-    }
-    __syncthreads();                                    // tables visible
-    for (int sit = 0;; ++sit) {
-        STAMP(0, sit, 0);
-        const int vbn = vb + (int)gridDim.x < ntiles ? vb + (int)gridDim.x : vb;   // last tile: harmless repeat
-        const int bl = vb / tiles_per_band, i0 = P::tile_row(vb - bl * tiles_per_band, tiles_per_band);
-        cplx<T>* Tb = Tw + (size_t)(band0 + bl) * d.T_band;
-        cplx<T> vv[2][E];
-        {
-            const int tid = launder((int)threadIdx.x);
-            const int g = tid / TPB, t = tid % TPB;
-            cplx<T>* lds = lds0 + (size_t)g * P::STRIDE;
-#pragma unroll
-            for (int j = 0; j < E; ++j) {
-                V2 a = xa[j];
-                if constexpr (BEAM) { a.x *= ba[j].x; a.y *= ba[j].y; }
-                vv[0][j] = cplx<T>(a.x, a.y);                    // z[n] = x[2n] + i x[2n+1]
-                vv[1][j] = vv[0][j] * P::tw_row(ltm, t, j);      // z .* w_M^n  (odd bins)
-                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-            }
-            STAMP(0, sit, 1);
-            F::template runN<false, 2>(vv, lds, t, ltw);
-            STAMP(0, sit, 2);
-        }
-        {   // fresh index: nothing thread-derived stays live (and gets spilled) across the FFT
-            const int tid = launder((int)threadIdx.x);
-            const int g = tid / TPB, t = tid % TPB;
-            __syncthreads();                                     // last exchange's readers are done
-            cplx<T>* wp = lds0 + (size_t)g * P::STRIDE + F::pad(t);
-#pragma unroll
-            for (int j = 0; j < E; ++j) wp[F::cpad(TPB * j)] = vv[0][j];
-            // next tile's rows: in flight during both post-processing sweeps
-            if constexpr (!SPR) {
-                const int bln = vbn / tiles_per_band, i0n = P::tile_row(vbn - bln * tiles_per_band, tiles_per_band);
-                const V2* xr = reinterpret_cast<const V2*>(x + (size_t)bln * d.xband + (size_t)(i0n + g) * d.xpitch) + t;
-#pragma unroll
-                for (int j = 0; j < E; ++j) xa[j] = xr[TPB * j];
-            }
-            __syncthreads();
-        }
-        STAMP(0, sit, 3);
-        constexpr int NITE_ = (P::NBE + P::BSTEP - 1) / P::BSTEP, NITO_ = (P::NBO + P::BSTEP - 1) / P::BSTEP;
-        {
-            const int tid = launder((int)threadIdx.x);
-            if constexpr (SPR) {
-                const int g = tid / TPB, t = tid % TPB;
-                const int bln = vbn / tiles_per_band, i0n = P::tile_row(vbn - bln * tiles_per_band, tiles_per_band);
-                const V2* xr = reinterpret_cast<const V2*>(x + (size_t)bln * d.xband + (size_t)(i0n + g) * d.xpitch) + t;
-                fwdp_post<T, L, 0>(lds0 + (size_t)(tid % G) * P::STRIDE, ltm, wq1, Tb, d.nx, i0, tid % G, tid / G,
-                                   [&](auto k) {
-                                       constexpr int K = decltype(k)::value;
-#pragma unroll
-                                       for (int j = (K * E) / NITE_; j < ((K + 1) * E) / NITE_; ++j) xa[j] = xr[TPB * j];
-                                   });
-            } else {
-                fwdp_post<T, L, 0>(lds0 + (size_t)(tid % G) * P::STRIDE, ltm, wq1, Tb, d.nx, i0, tid % G, tid / G);
-            }
-        }
-        STAMP(0, sit, 4);
-        if constexpr (BEAM && !SPR) {   // the next tile's beam rows: requested once the even-bin registers are free
-            const int tid = launder((int)threadIdx.x);
-            const int g = tid / TPB, t = tid % TPB;
-            const int bln = vbn / tiles_per_band, i0n = P::tile_row(vbn - bln * tiles_per_band, tiles_per_band);
-            const V2* br = reinterpret_cast<const V2*>(beam + (size_t)bln * d.xband + (size_t)(i0n + g) * d.xpitch) + t;
-#pragma unroll
-            for (int j = 0; j < E; ++j) ba[j] = br[TPB * j];
-        }
-        {
-            const int tid = launder((int)threadIdx.x);
-            const int g = tid / TPB, t = tid % TPB;
-            cplx<T>* wp = lds0 + (size_t)g * P::STRIDE + F::pad(t);
-            __syncthreads();                                     // even-bin sweep has read the rows
-#pragma unroll
-            for (int j = 0; j < E; ++j) wp[F::cpad(TPB * j)] = vv[1][j];
-            __syncthreads();
-            STAMP(0, sit, 5);
-            if constexpr (BEAM && SPR) {
-                const int bln = vbn / tiles_per_band, i0n = P::tile_row(vbn - bln * tiles_per_band, tiles_per_band);
-                const V2* br = reinterpret_cast<const V2*>(beam + (size_t)bln * d.xband + (size_t)(i0n + g) * d.xpitch) + t;
-                fwdp_post<T, L, 1>(lds0 + (size_t)(tid % G) * P::STRIDE, ltm, wq1, Tb, d.nx, i0, tid % G, tid / G,
-                                   [&](auto k) {
-                                       constexpr int K = decltype(k)::value;
-#pragma unroll
-                                       for (int j = (K * E) / NITO_; j < ((K + 1) * E) / NITO_; ++j) ba[j] = br[TPB * j];
-                                   });
-            } else {
-                fwdp_post<T, L, 1>(lds0 + (size_t)(tid % G) * P::STRIDE, ltm, wq1, Tb, d.nx, i0, tid % G, tid / G);
-            }
-            STAMP(0, sit, 6);
-            __syncthreads();                                     // rows free for the next transform
-        }
-        STAMP(0, sit, 7);
-        if (vbn == vb) break;
-        vb = vbn;
-    }
-}
-
 // ------------------------------------------- row forward, persistent, parities in sequence
-template <int NP, typename H> __device__ __forceinline__ void fwd_abl_hooks(H&& h) {
-    if constexpr (NP > 0) { fwd_abl_hooks<NP - 1>(h); h(std::integral_constant<int, NP - 1>{}); }
-}
-template <typename F, typename V, typename C, typename H>
-__device__ __forceinline__ void fwd_run(V& vv, C* lds, int t, const C* ltw, H&& h) {
-    if constexpr ((PFB_FWD_ABL & 8) != 0) fwd_abl_hooks<F::NPASS>(h);
-    else F::template run<false>(vv, lds, t, ltw, h);
-}
-// k_row_fwd_pow2p above runs the even-bin and the odd-bin transform of a tile together and then the two
-// post-processing sweeps; the next tile's rows are requested in one burst between them, which parks all 16 waves at
+// The first persistent forward kernel (k_row_fwd_pow2p; removed, the code is at commit e9a762c) ran the even-bin and
+// the odd-bin transform of a tile together and then the two post-processing sweeps; the next tile's rows were requested
+// in one burst between them, which parks all 16 waves at
 // issue (profiles/r02_a_phase_stamps_*: 8.0 of 28 us per trip, and the 9.3 us of the transforms run with NOTHING in
 // flight).  Here the parities run one after the other:
 //     z = x [* beam]              -> FFT  -> LDS -> even-bin sweep (stores)
@@ -1510,14 +1190,7 @@ k_row_fwd_pow2q(const T* __restrict__ x, const T* __restrict__ beam, cplx<T>* __
     __syncthreads();                                    // tables visible
     for (int sit = 0;; ++sit) {
         STAMP(0, sit, 0);
-        int vbn;
-        if constexpr (PFB_FWD_ROT != 0) {      // (see k_row_inv_pow2p: the workgroup -> tile map rotates per trip)
-            const int s1 = sit + 1;
-            const int cand = (int)(((unsigned)blockIdx.x + (unsigned)s1 * (unsigned)PFB_FWD_ROT) % gridDim.x) + s1 * (int)gridDim.x;
-            vbn = cand < ntiles ? cand : vb;
-        } else {
-            vbn = vb + (int)gridDim.x < ntiles ? vb + (int)gridDim.x : vb;   // last tile: harmless repeat
-        }
+        const int vbn = vb + (int)gridDim.x < ntiles ? vb + (int)gridDim.x : vb;   // last tile: harmless repeat
         const int bl = vb / tiles_per_band, i0 = P::tile_row(vb - bl * tiles_per_band, tiles_per_band);
         cplx<T>* Tb = Tw + (size_t)(band0 + bl) * d.T_band;
         cplx<T> vv[E];
@@ -1532,7 +1205,7 @@ k_row_fwd_pow2q(const T* __restrict__ x, const T* __restrict__ beam, cplx<T>* __
                 vv[j] = cplx<T>(xa[j].x, xa[j].y);
             }
             STAMP(0, sit, 1);
-            if constexpr ((PFB_FWD_ABL & 8) == 0) F::template run<false>(vv, lds, t, ltw);
+            F::template run<false>(vv, lds, t, ltw);
             STAMP(0, sit, 2);
         }
         {
@@ -1545,22 +1218,6 @@ k_row_fwd_pow2q(const T* __restrict__ x, const T* __restrict__ beam, cplx<T>* __
             __syncthreads();
         }
         STAMP(0, sit, 3);
-#if PFB_STAMP
-        if (g_xtra_src) {           // diagnostic build only: see g_xtra_src
-            const int tid = launder((int)threadIdx.x);
-            const int g = tid / TPB, t = tid % TPB;
-            constexpr int NITE_ = (P::NBE + P::BSTEP - 1) / P::BSTEP;
-            const V2* er = reinterpret_cast<const V2*>((const T*)g_xtra_src + (size_t)bl * d.xband + (size_t)(i0 + g) * d.xpitch) + t;
-            T esum = 0;
-            fwdp_post<T, L, 0>(lds0 + (size_t)(tid % G) * P::STRIDE, ltm, wq1, Tb, d.nx, i0, tid % G, tid / G,
-                               [&](auto k) {
-                                   constexpr int K = decltype(k)::value;
-#pragma unroll
-                                   for (int j = (K * E) / NITE_; j < ((K + 1) * E) / NITE_; ++j) { const V2 e = er[TPB * j]; esum += e.x + e.y; }
-                               });
-            if (esum == T(12345.678)) g_xtra_sink[0] = (double)esum;
-        } else
-#endif
         {
             const int tid = launder((int)threadIdx.x);
             fwdp_post<T, L, 0>(lds0 + (size_t)(tid % G) * P::STRIDE, ltm, wq1, Tb, d.nx, i0, tid % G, tid / G);
@@ -1581,12 +1238,11 @@ k_row_fwd_pow2q(const T* __restrict__ x, const T* __restrict__ beam, cplx<T>* __
             const V2* xr = reinterpret_cast<const V2*>(x + offn) + t;
             const V2* br = BEAM ? reinterpret_cast<const V2*>(beam + offn) + t : nullptr;
             // the first exchange of this transform waits (barrier) for the even-bin sweep's LDS reads
-            fwd_run<F>(vv, lds, t, ltw, [&](auto k) {
+            F::template run<false>(vv, lds, t, ltw, [&](auto k) {
                 constexpr int K = decltype(k)::value;
 #pragma unroll
                 for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) {
-                    if constexpr ((PFB_FWD_ABL & 1) != 0) { xa[j].x = (T)(t + j); xa[j].y = (T)1; }
-                    else xa[j] = xr[TPB * j];
+                    xa[j] = xr[TPB * j];
                     if constexpr (BEAM) ba[j] = br[TPB * j];
                 }
             });
@@ -1680,7 +1336,7 @@ k_row_inv_pow2(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
                const cplx<T>* __restrict__ twM, const cplx<T>* __restrict__ ptw,
                const T* __restrict__ x, const T* __restrict__ beam,
                const T* __restrict__ dot_with, const T* __restrict__ dot_with2, T* __restrict__ out,
-               double* __restrict__ partials, FastDims d, int band0, T scale, T sigmainv, PcgTail tail) {
+               double* __restrict__ partials, FastDims d, int band0, T scale, T sigmainv) {
     using F = RegFft<T, L, E, RowCfg<T, L, true>::WAVE, InvDb<T, L>::OFF, true>;
     constexpr int TPB = F::TPB;
     constexpr int G = row_groups<T, L, E, RowCfg<T, L, true>::GMAX>();
@@ -1716,24 +1372,17 @@ k_row_inv_pow2(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
     V2* orow = reinterpret_cast<V2*>(out + rowoff) + t;
     const bool dot_is_x = dot_with == x;            // PCG: <p, A p> with x = p
     // fp64: 2 x 32 more registers for the prefetched operands do not exist under the 128-VGPR cap of
-    // a 1024-thread workgroup (it spilled 80-94 registers); they are read in the epilogue instead
-#ifndef PFB_INV_PREF64
-#define PFB_INV_PREF64 2
-#endif
-#ifndef PFB_INV_PREF32E16    // x / x and r prefetched there: 188 / 492 B of scratch, 1.29 / 1.63 ms
-#define PFB_INV_PREF32E16 0
-#endif
-    constexpr bool BIG64 = sizeof(T) == 8 && E >= 16;           // 64-register operands: x only / none (knob)
-    constexpr bool BIG32 = sizeof(T) == 4 && E >= 16 && L >= 4096;      // the same question for fp32 at 16 elements per thread
-    constexpr bool PREF = BIG32 ? PFB_INV_PREF32E16 >= 1 : (sizeof(T) == 4 || (NT < 1024 && (!BIG64 || PFB_INV_PREF64 >= 1)));
-    constexpr bool PREFR = PREF && (BIG32 ? PFB_INV_PREF32E16 >= 2 : (!BIG64 || PFB_INV_PREF64 >= 2));
-    V2 xq[PREF ? E : 1], rq[PREFR ? E : 1];
+    // a 1024-thread workgroup (it spilled 80-94 registers); they are read in the epilogue instead.  The same for fp32 at
+    // 16 elements per thread (L >= 4096): x / x and r prefetched there cost 188 / 492 B of scratch, 1.29 / 1.63 ms
+    constexpr bool BIG32 = sizeof(T) == 4 && E >= 16 && L >= 4096;
+    constexpr bool PREF = !BIG32 && (sizeof(T) == 4 || NT < 1024);
+    V2 xq[PREF ? E : 1], rq[PREF ? E : 1];
     row_inv_phase<T, L, E, 1>([&] {
         if constexpr (PREF) {
 #pragma unroll
             for (int j = 0; j < E; ++j) {
                 xq[j] = xr[TPB * j];
-                if constexpr (PREFR) { if (dr2) rq[j] = dr2[TPB * j]; }
+                if (dr2) rq[j] = dr2[TPB * j];
             }
         }
     }, Tb, twQ, ltw, lds0, lds, d.nx, i0, t, vv);
@@ -1758,7 +1407,7 @@ k_row_inv_pow2(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
             acc[0] += (double)dw.x * (double)val.x + (double)dw.y * (double)val.y;
             if (dr2) {
                 V2 d2;
-                if constexpr (PREFR) d2 = rq[j]; else d2 = dr2[TPB * j];
+                if constexpr (PREF) d2 = rq[j]; else d2 = dr2[TPB * j];
                 acc[1] += (double)d2.x * (double)val.x + (double)d2.y * (double)val.y;
             }
             acc[2] += (double)val.x * (double)val.x + (double)val.y * (double)val.y;
@@ -1769,11 +1418,8 @@ k_row_inv_pow2(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
         block_sum<3>(acc, red);
         if (threadIdx.x == 0) {
             const size_t np = (size_t)gridDim.x * gridDim.y, k = (size_t)bl * gridDim.x + rg;
-            if (tail.S) { pcg_partial_store(partials + k, acc[0]); pcg_partial_store(partials + np + k, acc[1]); pcg_partial_store(partials + 2 * np + k, acc[2]); }
-            else { partials[k] = acc[0]; partials[np + k] = acc[1]; partials[2 * np + k] = acc[2]; }
+            partials[k] = acc[0]; partials[np + k] = acc[1]; partials[2 * np + k] = acc[2];
         }
-        // PCG: the last workgroup to get here sums the partials and does the iteration's scalar bookkeeping
-        pcg_tail(tail, partials, (int)(gridDim.x * gridDim.y), gridDim.x * gridDim.y, red);
     }
 }
 
@@ -1787,19 +1433,15 @@ k_row_inv_pow2(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
 // global load may sit between the request and the FFT's end (s_waitcnt vmcnt retires in
 // order), so w_M^n lives in the LDS as well (w_Q^(2m+1) = w_M^m * w_Q), and the even-bin
 // result is parked in the LDS (not registers) while the odd-bin transform runs.
-#ifndef PFB_INV_BARUP
-#define PFB_INV_BARUP 1
-#endif
-// PFB_INV_ROT: the workgroup -> tile map of k_row_inv_pow2p rotates by that many workgroups per trip.  With the static map
+// INV_ROT: the workgroup -> tile map of k_row_inv_pow2p rotates by that many workgroups per trip.  With the static map
 // (tile = workgroup + trip x grid) a workgroup -- and its whole XCD, workgroup b runs on XCD b mod 8 -- reads the SAME 128 bytes
 // of every 1-KB stretch of a column block for the whole launch, and one XCD ran 13-15 % behind the others from the first trip to
 // the last (profiles/r03_z_phase_stamps_4096x8_f32.md, per-XCD table): the launch lasts as long as its slowest workgroup.
 // Rotating gives every workgroup every row residue in turn: 8 x 4096^2 fp32 0.614 -> 0.541 ms, 4 x 4096^2 fp64 0.716 -> 0.581,
 // 2 x 8192^2 fp64 1.644 -> 1.450, fp32 0.749 -> 0.679, with beam 0.720 -> 0.635; bit-identical results
 // (profiles/r03_ab_tile_rotation.md).  The forward rows and the column kernel show no such spread and no effect.
-#ifndef PFB_INV_ROT
-#define PFB_INV_ROT 3
-#endif
+constexpr int INV_ROT = 3;
+constexpr int INV_HOIST_B = 8;      // operand samples per batch of the HOIST epilogue (InvP::NXE)
 template <typename T, int L, int E>
 struct InvP {
     using C = RowCfg<T, L, true>;
@@ -1809,12 +1451,8 @@ struct InvP {
     // one such workgroup per CU every thread may use 256 VGPRs, so the even-bin result stays in registers
     // (PARK = false) and the prefetched pieces / operands fit as well.
     static constexpr bool PARK = sizeof(T) == 4 && E < 16;     // (E = 16: eight rows fill the LDS, the even-bin result stays in registers)
-#ifndef PFB_INV_HALF
-#define PFB_INV_HALF 0          // experiment: fp32 16-element tiles on 512 threads, two workgroups per CU (de-phased barriers)
-#endif
-    static constexpr bool HALF = PFB_INV_HALF && sizeof(T) == 4 && E >= 16 && L == 2048;
-    static constexpr int WG_PER_CU = HALF ? 2 : 1;
-    static constexpr int G = (sizeof(T) == 4 && !HALF ? 1024 : 512) / F::TPB;
+    static constexpr int WG_PER_CU = 1;
+    static constexpr int G = (sizeof(T) == 4 ? 1024 : 512) / F::TPB;
     static constexpr int NT = G * F::TPB;
     static constexpr int STRIDE = F::LDS_ELEMS + 4;
     static constexpr int NVB = FastCfg<T>::NVB;
@@ -1830,29 +1468,20 @@ struct InvP {
     // NOT prefetched into registers (vv + ev + the strided pieces already take 100 of the 128) but read where they are
     // used; what the persistent kernel still buys over the plain one are the tables loaded once and the strided pieces of
     // the next phase / next tile in flight during every transform.
-    static constexpr bool SMT = E >= 16 && (L >= 4096 || sizeof(T) == 8 || HALF);
+    static constexpr bool SMT = E >= 16 && (L >= 4096 || sizeof(T) == 8);
     static constexpr bool OPF = E < 16;
     // NXT: the NEXT tile's even-bin pieces are requested during the odd-bin transform and stay in flight across the
-    // epilogue (always with OPF; without it only where registers remain: the 512-thread fp64 tiles have 256)
-#ifndef PFB_INV_NXT64
-#define PFB_INV_NXT64 1          // 2 x 8192^2 fp64: 1.376 -> 1.195 ms (239 VGPRs, no scratch).  It had measured a tie (1.612 / 1.618)
-#endif                           // while one XCD set the pace of every variant (PFB_INV_ROT)
-    static constexpr bool NXT = OPF || (PFB_INV_NXT64 && sizeof(T) == 8);
+    // epilogue (always with OPF; without it only where registers remain: the 512-thread fp64 tiles have 256).
+    // 2 x 8192^2 fp64: 1.376 -> 1.195 ms (239 VGPRs, no scratch).  It had measured a tie (1.612 / 1.618) while one XCD set
+    // the pace of every variant (INV_ROT)
+    static constexpr bool NXT = OPF || sizeof(T) == 8;
     // NXE: neither -- but the next tile's even-bin pieces are requested at the START of the epilogue (the transforms are
     // over, their temporaries gone) instead of at the top of the next trip, where they were waited for right away
-    // (profiles/r03_q_phase_stamps_8192x2_*: 8.4 us of a 45 us trip)
-#ifndef PFB_INV_HOIST_B
-#define PFB_INV_HOIST_B 8
-#endif
-#ifndef PFB_INV_NXE
-#define PFB_INV_NXE 0           // measured: 1.955 vs 1.639 ms per 2 x 8192^2 fp64 (the pieces queue behind the epilogue's own loads): off
-#endif
-    // HOIST32 (default): the fp32 16-element tiles (4096-point rows) read their operand rows in two batches of 8 samples and
-    // request the next tile's even-bin pieces behind the second batch: 2 x 8192^2 fp32 0.682 -> 0.665 ms (no change with beam)
-#ifndef PFB_INV_HOIST32
-#define PFB_INV_HOIST32 1
-#endif
-    static constexpr bool NXE = !NXT && ((PFB_INV_NXE && (sizeof(T) == 8 || PFB_INV_NXE > 1)) || (PFB_INV_HOIST32 && sizeof(T) == 4));
+    // (profiles/r03_q_phase_stamps_8192x2_*: 8.4 us of a 45 us trip).  Only for fp32: fp64 measured 1.955 vs 1.639 ms per
+    // 2 x 8192^2 (the pieces queue behind the epilogue's own loads).  The fp32 16-element tiles (4096-point rows) read their
+    // operand rows in batches of INV_HOIST_B samples and request the next tile's even-bin pieces behind the last batch:
+    // 2 x 8192^2 fp32 0.682 -> 0.665 ms (no change with beam)
+    static constexpr bool NXE = !NXT && sizeof(T) == 4;
     // HOIST (fp32 NXE): all operand rows of the tile requested at once behind the combine loop (the even-bin result is dead
     // by then), the next tile's even-bin pieces half way through the loop that consumes them, in the registers it has freed
     static constexpr bool HOIST = NXE && sizeof(T) == 4;
@@ -1860,11 +1489,11 @@ struct InvP {
     // transform instead of at the top of the next trip (8 x 4096^2 fp32 0.6293 -> 0.6229 ms, 2 x 8192^2 fp64 1.673 -> 1.643); not
     // for the fp32 tiles that request a tile's pieces at the top of its own trip -- there the barrier was the only thing
     // those loads were in flight across (0.706 -> 0.732)
-    static constexpr bool BARUP = PFB_INV_BARUP && (NXT || sizeof(T) == 8 || (HOIST && PFB_INV_HOIST32 > 1));
+    static constexpr bool BARUP = NXT || sizeof(T) == 8;
     static constexpr int NTM = SMT ? F::TPB : L;
     static constexpr size_t LDS = 384 + sizeof(cplx<T>) * ((size_t)PTWP + NTM + (size_t)G * STRIDE + (PARK ? (size_t)G * L : 0));
     static constexpr bool OK = LDS <= (size_t)160 * 1024 && !C::WAVE && (!SMT || 32 * F::TPB == 2 * L) &&
-                               (sizeof(T) == 4 ? (NT == (HALF ? 512 : 1024) && G >= 4 && G <= 16) : (NT == 512 && (G == 2 || G == 4) && L >= 1024));
+                               (sizeof(T) == 4 ? (NT == 1024 && G >= 4 && G <= 16) : (NT == 512 && (G == 2 || G == 4) && L >= 1024));
     __device__ __forceinline__ static cplx<T> tw_row(const cplx<T>* ltm, int t, int j) {     // w_M^(t + TPB j)
         if constexpr (SMT) return j == 0 ? ltm[t] : ltm[t] * root32<T>(j);
         else return ltm[t + F::TPB * j];
@@ -1875,34 +1504,11 @@ struct InvP {
 // plain kernel is a 2-row, 1024-thread, 8-elements tile under the 128-VGPR cap, the persistent one a 2-row, 512-thread,
 // 16-elements tile (174-199 VGPRs, no scratch; small tables, operands read in place): 2.30 -> 1.61 ms per 2 x 8192^2.
 // (The plain kernel at 16 elements spills 648 B and takes 3.0 ms: the two kernels keep separate pass tables.)
-#ifndef PFB_INVPE64_MINL       // smallest fp64 row length that takes the 16-element persistent tile
-#define PFB_INVPE64_MINL 4096
-#endif
 template <typename T, int L> struct InvPE {
-    static constexpr int E = (sizeof(T) == 8 && L >= PFB_INVPE64_MINL) ? 16 : RowCfg<T, L, true>::E;
+    static constexpr int MINL64 = 4096;       // smallest fp64 row length that takes the 16-element persistent tile
+    static constexpr int E = (sizeof(T) == 8 && L >= MINL64) ? 16 : RowCfg<T, L, true>::E;
 };
 
-#ifndef PFB_INV_LIN
-#define PFB_INV_LIN 1
-#endif
-// PFB_INV_EARLY bit 0: the first pass's slice of loads (odd-bin pieces / dot_with2 rows) is requested right behind the scatter
-// instead, so that something is in flight across the barrier and inv_build: 0.6075 -> 0.5999 ms per 8 x 4096^2 fp32, 0.7415 ->
-// 0.7216 per 4 x 4096^2 fp64.  Bits 1-3 (all odd-bin pieces there / x rows behind the even transform / next tile's pieces in the
-// last pass only) measured no better (profiles/r03_ab_inv_ablation.md).
-#ifndef PFB_INV_EARLY
-#define PFB_INV_EARLY 1
-#endif
-#ifndef PFB_INV_ABL             // ablation builds of k_row_inv_pow2p (timing only, results are wrong): 1 no strided pieces,
-#define PFB_INV_ABL 0           // 2 no operand rows, 4 no result stores, 8 no transforms
-#endif
-template <int NP, typename H> __device__ __forceinline__ void abl_hooks(H&& h) {
-    if constexpr (NP > 0) { abl_hooks<NP - 1>(h); h(std::integral_constant<int, NP - 1>{}); }
-}
-template <typename F, typename V, typename C, typename H>
-__device__ __forceinline__ void inv_run(V& vv, C* lds, int t, const C* ltw, H&& h) {
-    if constexpr ((PFB_INV_ABL & 8) != 0) abl_hooks<F::NPASS>(h);
-    else F::template run<true>(vv, lds, t, ltw, h);
-}
 // strength-reduced addressing of the strided pieces (see fwdp_post_lin): the blocks of a thread are BSTEP apart, so the
 // load address is a workgroup-uniform base (band, parity, step) + a 32-bit per-thread offset that never changes, and
 // the padded LDS index of the scatter is one base + compile-time offsets.  Regular whenever BSTEP divides the odd-bin
@@ -1912,7 +1518,7 @@ constexpr bool inv_lin_ok() {
     using P = InvP<T, L, E>;
     // (fp32 only: 1902 instead of 2147 instructions per thread and tile, 0.613 vs 0.616 ms -- the inverse kernel is not
     // issue bound the way the forward sweep was; the fp64 tiles measured 1 % slower with it)
-    return PFB_INV_LIN && sizeof(T) == 4 && P::NBO % P::BSTEP == 0 && P::NBE == P::NBO + 1 && P::NITO * P::BSTEP == P::NBO &&
+    return sizeof(T) == 4 && P::NBO % P::BSTEP == 0 && P::NBE == P::NBO + 1 && P::NITO * P::BSTEP == P::NBO &&
            P::NITE == P::NITO + 1 && (P::NVB * P::BSTEP) % 16 == 0 && P::F::TPB % 16 == 0;
 }
 template <typename T, int L, int E, int PAR, int K0, int K1>
@@ -1923,12 +1529,6 @@ __device__ __forceinline__ void inv_issue(const cplx<T>* __restrict__ Tb, int nx
                                           Blk<T, FastCfg<T>::NVB> (&y)[InvP<T, L, E>::NITE]) {
     using P = InvP<T, L, E>;
     constexpr int NBP = PAR ? P::NBO : P::NBE, NIT = PAR ? P::NITO : P::NITE;
-    if constexpr ((PFB_INV_ABL & 1) != 0) {
-#pragma unroll
-        for (int k = 0; k < NIT; ++k)
-            for (int c = 0; c < P::NVB; ++c) y[k].c[c] = cplx<T>((T)(bi + k), (T)rr);
-        return;
-    }
     if constexpr (inv_lin_ok<T, L, E>()) {
         inv_issue_slice<T, L, E, PAR, 0, NIT>(Tb, nx, i0, rr, bi, y);
         return;
@@ -1948,12 +1548,6 @@ __device__ __forceinline__ void inv_issue_slice(const cplx<T>* __restrict__ Tb, 
                                                 Blk<T, FastCfg<T>::NVB> (&y)[InvP<T, L, E>::NITE]) {
     using P = InvP<T, L, E>;
     constexpr int NBP = PAR ? P::NBO : P::NBE;
-    if constexpr ((PFB_INV_ABL & 1) != 0) {
-#pragma unroll
-        for (int k = K0; k < K1; ++k)
-            for (int c = 0; c < P::NVB; ++c) y[k].c[c] = cplx<T>((T)(bi + k), (T)rr);
-        return;
-    }
     if constexpr (inv_lin_ok<T, L, E>()) {
         const cplx<T>* ub = Tb + (size_t)(PAR ? P::NBE : 0) * nx * P::NVB;                    // workgroup-uniform
         const size_t ustep = (size_t)P::BSTEP * nx * P::NVB;
@@ -2037,27 +1631,28 @@ __device__ __forceinline__ void inv_build(const cplx<T>* lds, const cplx<T>* ltm
 }
 
 // MODE 0: no inner products; 1: <x, out>, <out, out>; 2: also <dot_with2, out> (the PCG call)
-// SPR: the strided pieces and the epilogue operands are requested a few per FFT PASS (RegFft pass hook) instead of
+// The strided pieces and the epilogue operands are requested a few per FFT PASS (RegFft pass hook) instead of
 // in two bursts behind the scatters: a burst of 21 loads per thread parks all 16 waves at issue for 7.6 us of a
 // 22.6 us trip (profiles/r02_a_phase_stamps_*).  Per trip, in issue order (vmcnt retires in order):
 //     IFFT (even)  <- y(odd bins of this tile), then x [, beam]   of this tile's rows
 //     IFFT (odd)   <- dot_with2 rows, then y(even bins of the NEXT tile)
-template <typename T, int L, int E, int MODE, bool BEAM, bool SPR = false>
+// The first pass's slice of each (odd-bin pieces / dot_with2 rows) is requested right behind the scatter instead, so that
+// something is in flight across the barrier and inv_build: 0.6075 -> 0.5999 ms per 8 x 4096^2 fp32, 0.7415 -> 0.7216 per
+// 4 x 4096^2 fp64 (requesting more there measured no better: profiles/r03_ab_inv_ablation.md).
+template <typename T, int L, int E, int MODE, bool BEAM>
 __global__ void __launch_bounds__((InvP<T, L, E>::NT), (InvP<T, L, E>::NT / 256 * InvP<T, L, E>::WG_PER_CU))
 k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 const cplx<T>* __restrict__ ptw, const T* __restrict__ x, const T* __restrict__ beam,
                 const T* __restrict__ dot_with2, T* __restrict__ out,
                 double* __restrict__ partials, FastDims d, int band0, int tiles_per_band, int ntiles,
-                T scale, T sigmainv, cplx<T> wq1, int defer_stores, PcgTail tail) {
+                T scale, T sigmainv, cplx<T> wq1) {
     using P = InvP<T, L, E>;
     using F = typename P::F;
     constexpr int TPB = F::TPB, G = P::G, NT = P::NT;
     // (the batched-operand variant of the fp32 16-element tiles keeps 12 B of scratch with beam + two inner products: that
     // instantiation stays on the plain order -- a tile's pieces requested at the top of its own trip)
     constexpr bool NXEK = P::NXE && !(P::HOIST && BEAM && MODE == 2), HOISTK = P::HOIST && NXEK;
-    // (likewise the fp64 16-element tiles without the per-pass request schedule -- PFB_SPREAD=0, an A/B fallback -- keep 12 B
-    // of scratch with the next tile's pieces prefetched: that instantiation requests them at the top of the trip)
-    constexpr bool NXTK = P::NXT && (P::OPF || SPR);
+    constexpr bool NXTK = P::NXT;
     constexpr int NP = F::NPASS, NPA = NP / 2 > 0 ? NP / 2 : 1, NPB = NP - NPA > 0 ? NP - NPA : 1;
     using V2 = typename vec2<T>::type;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2089,23 +1684,17 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
     if constexpr (NXTK || NXEK)
         inv_issue<T, L, E, 0>(Tw + (size_t)(band0 + bl) * d.T_band, d.nx, i0, threadIdx.x % G, threadIdx.x / G, y);
     double acc[3] = {0.0, 0.0, 0.0};
-    // deferred stores (SPR, fp32): a tile's output rows stay in registers and are written two per pass of the NEXT
+    // deferred stores (fp32): a tile's output rows stay in registers and are written two per pass of the NEXT
     // tile's even-bin transform instead of in one burst behind the epilogue
-    const bool dst = SPR && P::PARK && defer_stores;
-    V2 ov[(SPR && P::PARK) ? E : 1];
+    V2 ov[P::PARK ? E : 1];
     V2* oprev = nullptr;
     for (int sit = 0;; ++sit) {
         STAMP(2, sit, 0);
-        int vbn;
-        if constexpr (PFB_INV_ROT != 0) {
-            // the workgroup -> tile map rotates by PFB_INV_ROT workgroups per trip: over its trips a workgroup sees the row
-            // groups of every XCD, not always the same 128 bytes of each 1-KB stretch of a column block
-            const int s1 = sit + 1;
-            const int cand = (int)(((unsigned)blockIdx.x + (unsigned)s1 * (unsigned)PFB_INV_ROT) % gridDim.x) + s1 * (int)gridDim.x;
-            vbn = cand < ntiles ? cand : vb;
-        } else {
-            vbn = vb + (int)gridDim.x < ntiles ? vb + (int)gridDim.x : vb;   // last tile: harmless repeat
-        }
+        // the workgroup -> tile map rotates by INV_ROT workgroups per trip: over its trips a workgroup sees the row
+        // groups of every XCD, not always the same 128 bytes of each 1-KB stretch of a column block
+        const int s1 = sit + 1;
+        const int cand = (int)(((unsigned)blockIdx.x + (unsigned)s1 * (unsigned)INV_ROT) % gridDim.x) + s1 * (int)gridDim.x;
+        const int vbn = cand < ntiles ? cand : vb;   // last tile: harmless repeat
         int bln, i0n;
         tile(vbn, bln, i0n);
         const cplx<T>* Tb = Tw + (size_t)(band0 + bl) * d.T_band;
@@ -2125,51 +1714,37 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             STAMP(2, sit, 1);
             inv_scatter<T, L, E, 0>(y, lds0 + (size_t)rr * P::STRIDE, bi);
             STAMP(2, sit, 2);
-            if constexpr (!SPR) inv_issue<T, L, E, 1>(Tb, d.nx, i0, rr, bi, y);
-            else if constexpr ((PFB_INV_EARLY & 2) != 0) inv_issue<T, L, E, 1>(Tb, d.nx, i0, rr, bi, y);
-            else if constexpr ((PFB_INV_EARLY & 1) != 0) inv_issue_slice<T, L, E, 1, 0, P::NITO / NPA>(Tb, d.nx, i0, rr, bi, y);   // pass 0's slice: in flight across the barrier and inv_build
+            inv_issue_slice<T, L, E, 1, 0, P::NITO / NPA>(Tb, d.nx, i0, rr, bi, y);   // pass 0's slice: in flight across the barrier and inv_build
             __syncthreads();
             STAMP(2, sit, 3);
             inv_build<T, L, E, 0>(lds, ltm, wq1, t, vv);
             STAMP(2, sit, 4);
-            if constexpr (SPR) {
+            {
                 const size_t rowoff = ((size_t)bl * d.nx + (i0 + g)) * d.ny;
                 const V2* xr = reinterpret_cast<const V2*>(x + rowoff) + t;
                 const V2* br = BEAM ? reinterpret_cast<const V2*>(beam + rowoff) + t : nullptr;
-                inv_run<F>(vv, lds, t, ltw, [&](auto k) {
+                F::template run<true>(vv, lds, t, ltw, [&](auto k) {
                     constexpr int K = decltype(k)::value;
                     if constexpr (P::PARK) {
-                        if (dst && oprev) {
+                        if (oprev) {
 #pragma unroll
-                            for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) { if (!(PFB_INV_ABL & 4) || scale == (T)123456) oprev[TPB * j] = ov[j]; }
+                            for (int j = (K * E) / NP; j < ((K + 1) * E) / NP; ++j) oprev[TPB * j] = ov[j];
                         }
                     }
-                    if constexpr (K < NPA) {            // first passes: the odd-bin pieces (needed first)
-                        if constexpr (!((PFB_INV_EARLY & 1) && K == 0) && !(PFB_INV_EARLY & 2))
+                    if constexpr (K < NPA) {            // first passes: the odd-bin pieces (needed first; pass 0's slice is out)
+                        if constexpr (K != 0)
                         inv_issue_slice<T, L, E, 1, (K * P::NITO) / NPA, ((K + 1) * P::NITO) / NPA>(Tb, d.nx, i0, rr, bi, y);
-                    } else if constexpr (OPF && !(PFB_INV_EARLY & 4)) {         // then this tile's x (and beam) rows for the epilogue
+                    } else if constexpr (OPF) {         // then this tile's x (and beam) rows for the epilogue
                         constexpr int KK = K - NPA;
 #pragma unroll
                         for (int j = (KK * E) / NPB; j < ((KK + 1) * E) / NPB; ++j) {
-                            if constexpr ((PFB_INV_ABL & 2) == 0) xq[j] = xr[TPB * j]; else { xq[j].x = (T)(t + j); xq[j].y = (T)1; }
+                            xq[j] = xr[TPB * j];
                             if constexpr (BEAM) bq[j] = br[TPB * j];
                         }
                     }
                 });
-            } else {
-                F::template run<true>(vv, lds, t, ltw);
             }
             STAMP(2, sit, 5);
-            if constexpr (SPR && OPF && (PFB_INV_EARLY & 4) != 0) {      // x rows requested here: in flight across park, scatter, build
-                const size_t rowoff = ((size_t)bl * d.nx + (i0 + g)) * d.ny;
-                const V2* xr = reinterpret_cast<const V2*>(x + rowoff) + t;
-#pragma unroll
-                for (int j = 0; j < E; ++j) {
-                    xq[j] = xr[TPB * j];
-                    if constexpr (BEAM) bq[j] = reinterpret_cast<const V2*>(beam + rowoff)[t + TPB * j];
-                }
-            }
-            if constexpr (P::BARUP && (PFB_INV_BARUP & 2) != 0) __syncthreads();   // (the even transform's readers are done: before the park, not behind it)
 #pragma unroll
             for (int j = 0; j < E; ++j) {
                 if constexpr (P::PARK) park[j * NT + tid] = vv[j]; else ev[j] = vv[j];
@@ -2180,29 +1755,14 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             const int tid = launder((int)threadIdx.x);
             const int g = tid / TPB, t = tid % TPB, rr = tid % G, bi = tid / G;
             cplx<T>* lds = lds0 + (size_t)g * P::STRIDE;
-            if constexpr (!(P::BARUP && (PFB_INV_BARUP & 2) != 0)) __syncthreads();
+            __syncthreads();
             STAMP(2, sit, 6);
             inv_scatter<T, L, E, 1>(y, lds0 + (size_t)rr * P::STRIDE, bi);
             STAMP(2, sit, 7);
             const size_t rowoff = ((size_t)bl * d.nx + (i0 + g)) * d.ny;
             const V2* dr2 = reinterpret_cast<const V2*>(dot_with2 + rowoff) + t;
             const cplx<T>* Tbn = Tw + (size_t)(band0 + bln) * d.T_band;
-            if constexpr (!SPR) {
-                if constexpr (OPF) {
-                    const V2* xr = reinterpret_cast<const V2*>(x + rowoff) + t;
-#pragma unroll
-                    for (int j = 0; j < E; ++j) {
-                        xq[j] = xr[TPB * j];
-                        if constexpr (MODE == 2) rq[j] = dr2[TPB * j];
-                    }
-                    if constexpr (BEAM) {
-                        const V2* br = reinterpret_cast<const V2*>(beam + rowoff) + t;
-#pragma unroll
-                        for (int j = 0; j < E; ++j) bq[j] = br[TPB * j];
-                    }
-                }
-                if constexpr (NXTK) inv_issue<T, L, E, 0>(Tbn, d.nx, i0n, rr, bi, y);
-            } else if constexpr ((PFB_INV_EARLY & 1) != 0 && MODE == 2 && OPF) {
+            if constexpr (MODE == 2 && OPF) {           // pass 0's slice of the dot_with2 rows: in flight across the barrier
 #pragma unroll
                 for (int j = 0; j < E / NPA; ++j) rq[j] = dr2[TPB * j];
             }
@@ -2210,27 +1770,21 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             STAMP(2, sit, 8);
             inv_build<T, L, E, 1>(lds, ltm, wq1, t, vv);
             STAMP(2, sit, 9);
-            if constexpr (SPR) {
-                inv_run<F>(vv, lds, t, ltw, [&](auto k) {
-                    constexpr int K = decltype(k)::value;
-                    if constexpr (MODE == 2 && OPF) {
-                        if constexpr (K < NPA) {        // dot_with2 rows first: the epilogue waits for them
-                            if constexpr (!((PFB_INV_EARLY & 1) && K == 0))
+            F::template run<true>(vv, lds, t, ltw, [&](auto k) {
+                constexpr int K = decltype(k)::value;
+                if constexpr (MODE == 2 && OPF) {
+                    if constexpr (K < NPA) {        // dot_with2 rows first: the epilogue waits for them
+                        if constexpr (K != 0)
 #pragma unroll
-                            for (int j = (K * E) / NPA; j < ((K + 1) * E) / NPA; ++j) { if constexpr ((PFB_INV_ABL & 2) == 0) rq[j] = dr2[TPB * j]; else { rq[j].x = (T)(t - j); rq[j].y = (T)2; } }
-                        } else {                        // the next tile's even-bin pieces stay in flight past the epilogue
-                            constexpr int KK = K - NPA;
-                            if constexpr ((PFB_INV_EARLY & 8) != 0) { if constexpr (K == NP - 1) inv_issue<T, L, E, 0>(Tbn, d.nx, i0n, rr, bi, y); }
-                            else
-                            inv_issue_slice<T, L, E, 0, (KK * P::NITE) / NPB, ((KK + 1) * P::NITE) / NPB>(Tbn, d.nx, i0n, rr, bi, y);
-                        }
-                    } else if constexpr (NXTK) {
-                        inv_issue_slice<T, L, E, 0, (K * P::NITE) / NP, ((K + 1) * P::NITE) / NP>(Tbn, d.nx, i0n, rr, bi, y);
+                        for (int j = (K * E) / NPA; j < ((K + 1) * E) / NPA; ++j) rq[j] = dr2[TPB * j];
+                    } else {                        // the next tile's even-bin pieces stay in flight past the epilogue
+                        constexpr int KK = K - NPA;
+                        inv_issue_slice<T, L, E, 0, (KK * P::NITE) / NPB, ((KK + 1) * P::NITE) / NPB>(Tbn, d.nx, i0n, rr, bi, y);
                     }
-                });
-            } else {
-                F::template run<true>(vv, lds, t, ltw);
-            }
+                } else if constexpr (NXTK) {
+                    inv_issue_slice<T, L, E, 0, (K * P::NITE) / NP, ((K + 1) * P::NITE) / NP>(Tbn, d.nx, i0n, rr, bi, y);
+                }
+            });
             STAMP(2, sit, 10);
             // the last exchange's readers are done BEFORE the epilogue instead of at the top of the next trip: the waves are
             // still in step here (cheap), and a wave that is through with its epilogue scatters the next tile's pieces while
@@ -2276,7 +1830,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 if constexpr (HOISTK) {
                     // operand rows in batches of HB samples; behind the LAST batch the next tile's even-bin pieces (in order:
                     // nothing the epilogue still waits for is queued behind them)
-                    constexpr int HB = PFB_INV_HOIST_B;
+                    constexpr int HB = INV_HOIST_B;
                     if (j % HB == 0) {
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -2295,7 +1849,6 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 [[maybe_unused]] V2 bb;
                 if constexpr (OPF) { xx = xq[j]; if constexpr (BEAM) bb = bq[j]; }
                 else if constexpr (HOISTK) { xx = xh[j]; if constexpr (BEAM) bb = bh[j]; }
-                else if constexpr ((PFB_INV_ABL & 2) != 0) { xx.x = (T)(t + j); xx.y = (T)1; if constexpr (BEAM) bb = br_e[TPB * j]; }
                 else { xx = xr_e[TPB * j]; if constexpr (BEAM) bb = br_e[TPB * j]; }
                 if constexpr (BEAM) {
                     val.x = zz.x * scale * bb.x + sigmainv * xx.x;
@@ -2304,9 +1857,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                     val.x = zz.x * scale + sigmainv * xx.x;
                     val.y = zz.y * scale + sigmainv * xx.y;
                 }
-                if constexpr (SPR && P::PARK) { if (dst) ov[j] = val; else orow[TPB * j] = val; }
-                else if constexpr ((PFB_INV_ABL & 4) != 0 && MODE >= 1) { }          // (the inner products keep val alive)
-                else orow[TPB * j] = val;
+                if constexpr (P::PARK) ov[j] = val; else orow[TPB * j] = val;
                 // operands read in place (!OPF): a few samples at a time, or every x / dot_with2 load of the tile is
                 // hoisted to the top of the loop and spills
                 if constexpr (!OPF && !HOISTK) { if (sizeof(T) == 4 && (j & 3) == 3) __builtin_amdgcn_sched_barrier(0); }
@@ -2315,7 +1866,6 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                     if constexpr (MODE == 2) {
                         V2 d2;
                         if constexpr (OPF) d2 = rq[j]; else if constexpr (HOISTK) d2 = rh[j];
-                        else if constexpr ((PFB_INV_ABL & 2) != 0) { d2.x = (T)(t - j); d2.y = (T)2; }
                         else d2 = dr_e[TPB * j];
                         acc[1] += (double)d2.x * (double)val.x + (double)d2.y * (double)val.y;
                     }
@@ -2324,7 +1874,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             }
         }
         STAMP(2, sit, 11);
-        if constexpr (SPR && P::PARK) {
+        if constexpr (P::PARK) {
             const int tid = launder((int)threadIdx.x);
             const int g = tid / TPB, t = tid % TPB;
             oprev = reinterpret_cast<V2*>(out + ((size_t)bl * d.nx + (i0 + g)) * d.ny) + t;
@@ -2332,8 +1882,8 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
         if (vbn == vb) break;
         vb = vbn; bl = bln; i0 = i0n;
     }
-    if constexpr (SPR && P::PARK) {
-        if (dst && oprev) {
+    if constexpr (P::PARK) {
+        if (oprev) {
 #pragma unroll
             for (int j = 0; j < E; ++j) oprev[TPB * j] = ov[j];
         }
@@ -2343,12 +1893,8 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
         block_sum<3>(acc, red);
         if (threadIdx.x == 0) {           // one slot per WORKGROUP (launcher: last_npartials = grid)
             const size_t np = gridDim.x;
-            bool coh = false;
-            if constexpr (MODE == 2) coh = tail.S != nullptr;
-            if (coh) { pcg_partial_store(partials + blockIdx.x, acc[0]); pcg_partial_store(partials + np + blockIdx.x, acc[1]); pcg_partial_store(partials + 2 * np + blockIdx.x, acc[2]); }
-            else { partials[blockIdx.x] = acc[0]; partials[np + blockIdx.x] = acc[1]; partials[2 * np + blockIdx.x] = acc[2]; }
+            partials[blockIdx.x] = acc[0]; partials[np + blockIdx.x] = acc[1]; partials[2 * np + blockIdx.x] = acc[2];
         }
-        if constexpr (MODE == 2) pcg_tail(tail, partials, (int)gridDim.x, gridDim.x, red);
     }
 }
 
@@ -2361,12 +1907,6 @@ int pow2_col_set_stamp(unsigned long long* buf) {
 }
 #endif
 #if PFB_POW2_REST
-int pow2_set_xtra(const void* src_, double* sink) {
-    const float* src = (const float*)src_;
-    PFB_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_xtra_src), &src, sizeof(src)));
-    PFB_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_xtra_sink), &sink, sizeof(sink)));
-    return PFB_OK;
-}
 int pow2_col_set_stamp(unsigned long long* buf);
 int pow2_set_stamp(unsigned long long* buf) {
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &buf, sizeof(buf)) != hipSuccess) return PFB_ERR_HIP;
@@ -2384,11 +1924,9 @@ int pow2_set_stamp(unsigned long long* buf) {
 // of workgroups runs at their latency while the rest of the chip idles -- the same work on slightly fewer workgroups is
 // bandwidth bound to the end: col 0.816 -> 0.800 ms at 8 x 4096^2 fp32 (253 instead of 256 workgroups), 45.5 -> 42.6 us
 // at 1 x 2048^2 (342 instead of 512), 129.3 -> 126.5 us at 1 x 4096^2 (228), 0.889 -> 0.861 ms at 4 x 4096^2 fp64.  Only for
-// that kernel (the row kernels' grids divide evenly at the usual sizes, the two-level column kernel loses).  PFB_GRID_BALANCE=0: off.
+// that kernel (the row kernels' grids divide evenly at the usual sizes, the two-level column kernel loses).
 static inline int balanced_grid(int need, int maxgrid) {
     if (need <= maxgrid) return need;
-    static const bool on = [] { const char* e = getenv("PFB_GRID_BALANCE"); return !e || atoi(e); }();
-    if (!on) return maxgrid;
     const int trips = (need + maxgrid - 1) / maxgrid;
     return (need + trips - 1) / trips;
 }
@@ -2400,13 +1938,10 @@ struct FastTables {            // device tables owned by the plan (stored behind
     void* ptw_row_inv;         // inverse row kernel (E = 8): COMPACT table, copied to LDS
     void* ptw_row_inv_p;       // the persistent inverse kernel's, where its elements per thread differ (InvPE); else == ptw_row_inv
     void* twM;                 // exp(-2 pi i n / M), n < L
-    int col_persistent;        // PFB_COL_PERSIST (default: auto by size): persistent prefetching column kernel
     void* ptwc_row_fwd;        // compact pass table of the persistent forward row kernel (its own E)
-    int fwd_persistent;        // PFB_FWD_PERSIST (default 1): persistent pipelined forward row kernel where it fits
-    int inv_persistent;        // PFB_INV_PERSIST (default 1): persistent pipelined inverse row kernel where it fits
     int num_cu;
     void* ptwc_col_x;          // compact pass table of its HS = nx / 2 point sub-transform
-    int col_x;                 // two-level column kernel k_col_pow2x + class-major psf_l (default: nx = 8192; PFB_COL_X=0/1 forces)
+    int col_x;                 // two-level column kernel k_col_pow2x + class-major psf_l (nx = 8192)
 };
 // the column object's entry points (defined under PFB_POW2_COL below)
 int pow2_col_set_attr(int dtype, int H);
@@ -2442,9 +1977,7 @@ static int set_invp_attr() {
     constexpr int E = InvPE<T, L>::E;
     if constexpr (InvP<T, L, E>::OK) {
 #define PFB_INVATTR(MODE, BM)                                                                           \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, MODE, BM, false>),      \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, MODE, BM, true>),       \
+        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, MODE, BM>),             \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
         PFB_INVATTR(0, false); PFB_INVATTR(1, false); PFB_INVATTR(2, false);
         PFB_INVATTR(0, true);  PFB_INVATTR(1, true);  PFB_INVATTR(2, true);
@@ -2458,17 +1991,12 @@ static int prep_fwdp(void** table) {
     if constexpr (FwdP<T, L>::OK) {
         int rc = prep_ptw_compact<T, L, FwdP<T, L>::EOK>(table);
         if (rc != PFB_OK) return rc;
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2p<T, L, false, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2p<T, L, true, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2p<T, L, false, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2p<T, L, true, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2q<T, L, false>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2q<T, L, true>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    } else {
+        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_row_fwd_pow2<T, L, RowCfg<T, L, false>::E>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     return PFB_OK;
@@ -2483,7 +2011,7 @@ static int prep_tables(pfb_conv_plan* p, FastTables* ft) {
     switch (H) {
 #define X(NN) case NN: rc = prep_ptw<T, NN, ecol<T, NN>()>(&ft->ptw_col);                          \
         if (rc == PFB_OK) rc = prep_ptw_compact<T, NN, ecol<T, NN>()>(&ft->ptwc_col);             \
-        if (rc == PFB_OK && NN >= 2048) rc = prep_ptw_compact<T, (NN >= 2048 ? NN / 2 : 1024), ECOLX>(&ft->ptwc_col_x); \
+        if (rc == PFB_OK && NN == 8192) rc = prep_ptw_compact<T, 4096, ECOLX>(&ft->ptwc_col_x);         \
         if (rc == PFB_OK) rc = pow2_col_set_attr(p->dtype, NN); break;
         PFB_POW2_SIZES(X)
 #undef X
@@ -2496,8 +2024,6 @@ static int prep_tables(pfb_conv_plan* p, FastTables* ft) {
         if (rc == PFB_OK) rc = prep_ptw_compact<T, NN, RowCfg<T, NN, true>::E>(&ft->ptw_row_inv);    \
         if (rc == PFB_OK) { if (InvPE<T, NN>::E != RowCfg<T, NN, true>::E) rc = prep_ptw_compact<T, NN, InvPE<T, NN>::E>(&ft->ptw_row_inv_p); \
                             else ft->ptw_row_inv_p = ft->ptw_row_inv; }                            \
-        if (rc == PFB_OK) PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_row_fwd_pow2<T, NN, RowCfg<T, NN, false>::E>, \
-            hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));                                   \
         if (rc == PFB_OK) PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_row_inv_pow2<T, NN, RowCfg<T, NN, true>::E>, \
             hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));                                   \
         if (rc == PFB_OK) rc = set_invp_attr<T, NN>();                                               \
@@ -2553,22 +2079,12 @@ int pow2_prepare(pfb_conv_plan* p) {
     FastTables* ft = (FastTables*)calloc(1, sizeof(FastTables));
     PFB_REQUIRE(ft != nullptr, PFB_ERR_ALLOC, "pow2_prepare: host alloc failed");
     p->fast_tables = ft;
-    // -1 = auto: the persistent prefetching kernel wins up to nx = 2048 (0.27 vs 0.33 ms at
-    // 2048^2 x 8), the plain 2-workgroup/CU kernel at 4096 (1.17 vs 1.22 ms); 0 / 1 force one
-    ft->col_persistent = -1;
-    if (const char* e = getenv("PFB_COL_PERSIST")) ft->col_persistent = atoi(e) ? 1 : 0;
-    ft->fwd_persistent = 1;
-    if (const char* e = getenv("PFB_FWD_PERSIST")) ft->fwd_persistent = atoi(e) ? 1 : 0;
-    ft->inv_persistent = 1;
-    if (const char* e = getenv("PFB_INV_PERSIST")) ft->inv_persistent = atoi(e) ? 1 : 0;
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
         ft->num_cu = prop.multiProcessorCount;
     if (ft->num_cu <= 0) ft->num_cu = 256;
     ft->col_x = p->nx >= 8192 ? 1 : 0;
-    if (const char* e = getenv("PFB_COL_X")) ft->col_x = (atoi(e) && p->nx >= 2048) ? 1 : 0;
-    if (const char* e = getenv("PFB_CU_LIMIT")) { int v = atoi(e); if (v >= 16 && v < ft->num_cu) ft->num_cu = v; }   // experiments: leave CUs to a concurrent kernel
     return p->dtype == PFB_F32 ? prep_tables<float>(p, ft) : prep_tables<double>(p, ft);
 }
 
@@ -2663,16 +2179,20 @@ static void launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb
     using F = RegFft<T, H, E>;
     constexpr int GC = col_groups<H, E>();
     const int nblk = fast_nblocks(p->ny / 2, FastCfg<T>::NVB);
-    if constexpr (H >= 2048) {
+    // bands in DESCENDING order (persistent kernels): the row pass before and after run ascending, so each pass starts on
+    // the band whose T the previous one touched last (part of it still in the 256 MiB Infinity Cache):
+    // col 0.995 -> 0.987 ms, row_inv 0.666 -> 0.660 ms at 8 x 4096^2 fp32
+    const int band_first = band0 + nb - 1;
+    // psf read with non-temporal loads (see loadb_nt) only when this launch's share of the PSF spectrum is itself of the
+    // Infinity Cache's size or larger: a smaller one is RE-READ from that cache by the next apply and must stay allocatable
+    const bool psf_nt = sizeof(cplx<T>) * p->psf_elems_per_band * (size_t)nb >= ((size_t)200 << 20);
+    if constexpr (H == 8192) {
         if (ft->col_x) {
             // two-level kernel: HS = H / 2 point sub-transforms, one resident workgroup set (2 waves per SIMD)
             using CX = ColX<T, H, ECOLX>;
             using FX = typename CX::F;
             constexpr int GX = CX::GC;
             const int nitems = nblk * nb;
-            static const bool rev = [] { const char* e = getenv("PFB_COL_REV"); return !e || atoi(e); }();
-            static const bool psf_nt_on = [] { const char* e = getenv("PFB_PSF_NT"); return !e || atoi(e); }();
-            const bool psf_nt = psf_nt_on && sizeof(cplx<T>) * p->psf_elems_per_band * (size_t)nb >= ((size_t)200 << 20);
             const int wg_lds = (int)(((size_t)160 * 1024) / CX::LDS);
             int wg_per_cu = (8 * 64) / (GX * FX::TPB) > 0 ? (8 * 64) / (GX * FX::TPB) : 1;
             if (wg_per_cu > wg_lds) wg_per_cu = wg_lds > 0 ? wg_lds : 1;
@@ -2685,54 +2205,33 @@ static void launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb
             hipLaunchKernelGGL((k_col_pow2x<T, H, ECOLX, NTV>), dim3(grid), dim3(GX * FX::TPB), ldsx, st,      \
                                (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,               \
                                (const cplx<T>*)ft->ptwc_col_x, nblk, nitems, p->T_elems_per_band,              \
-                               p->psf_elems_per_band, rev ? band0 + nb - 1 : band0, rev ? -1 : 1)
+                               p->psf_elems_per_band, band_first, -1)
             if (psf_nt) PFB_COLX(true); else PFB_COLX(false);
 #undef PFB_COLX
             return;
         }
     }
-    const size_t lds = sizeof(cplx<T>) * (size_t)GC * FastCfg<T>::NVB * F::LDS_ELEMS;
+    constexpr size_t lds = sizeof(cplx<T>) * (size_t)GC * FastCfg<T>::NVB * F::LDS_ELEMS;
     // persistent kernel: needs its LDS (exchange buffers + twiddle table) to fit; measured faster
     // for H >= 2048 (fp32, packed arithmetic: 1.07 vs 1.32 ms at 4096^2 x 8, 0.276 vs 0.347 at 2048^2 x 8;
     // fp64: 1.19 vs 1.41 and 0.266 vs 0.333 at x 4; a tie or a small loss at H <= 1024)
-    const size_t lds_p = lds + sizeof(cplx<T>) * (size_t)((F::PTWC + 1) & ~1);
-    const bool fits_p = lds_p <= (size_t)160 * 1024;
-    if (fits_p && (ft->col_persistent == 1 || (ft->col_persistent < 0 && H >= 2048))) {
+    constexpr size_t tab = sizeof(cplx<T>) * (size_t)((F::PTWC + 1) & ~1);
+    if constexpr (H >= 2048 && lds + tab <= (size_t)160 * 1024) {
         // one resident workgroup set: 8 waves per CU at 256 VGPRs
         const int nitems = nblk * nb;
-        // bands in DESCENDING order: the row pass before and after run ascending, so each pass starts on
-        // the band whose T the previous one touched last (part of it still in the 256 MiB Infinity Cache):
-        // col 0.995 -> 0.987 ms, row_inv 0.666 -> 0.660 ms at 8 x 4096^2 fp32.  PFB_COL_REV=0 turns it off.
-        static const bool rev = [] { const char* e = getenv("PFB_COL_REV"); return !e || atoi(e); }();
-        const int wg_per_cu = (8 * 64) / (GC * F::TPB) > 0 ? (8 * 64) / (GC * F::TPB) : 1;
+        constexpr int wg_per_cu = (8 * 64) / (GC * F::TPB) > 0 ? (8 * 64) / (GC * F::TPB) : 1;
         const int need = (nitems + GC - 1) / GC;
         const int grid = balanced_grid(need, ft->num_cu * wg_per_cu);
         // second exchange buffer set when ONE workgroup per CU is resident anyway and it fits: col 0.98 ->
         // 0.96 ms at 8 x 4096^2 fp32, 1.16 -> 1.10 ms at 4 x 4096^2 fp64; with two workgroups per CU (H = 2048)
-        // the doubled LDS costs residency (fp64 0.245 -> 0.304 ms).  PFB_COL_DB=0 turns it off.
-        static const bool db_on = [] { const char* e = getenv("PFB_COL_DB"); return !e || atoi(e); }();
-        // loads spread over the FFT passes (see the kernel); PFB_SPREAD=0 keeps the two-burst schedule (A/B)
-        static const bool spread = [] { const char* e = getenv("PFB_SPREAD"); return !e || atoi(e); }();
-        const size_t tab = sizeof(cplx<T>) * (size_t)((F::PTWC + 1) & ~1);
-        const bool db = db_on && wg_per_cu == 1 && 2 * lds + tab <= (size_t)160 * 1024;
-        // psf read with non-temporal loads (see loadb_nt); PFB_PSF_NT=0: A/B
-        // ... only when this launch's share of the PSF spectrum is itself of the Infinity Cache's size or larger: a
-        // smaller one is RE-READ from that cache by the next apply and must stay allocatable
-        static const bool psf_nt_on = [] { const char* e = getenv("PFB_PSF_NT"); return !e || atoi(e); }();
-        const bool psf_nt = psf_nt_on && sizeof(cplx<T>) * p->psf_elems_per_band * (size_t)nb >= ((size_t)200 << 20);
-#define PFB_COLP(DBV, SPV)                                                                                     \
-        if (SPV && psf_nt)                                                                                     \
-        hipLaunchKernelGGL((k_col_pow2p<T, H, E, DBV, SPV, SPV>), dim3(grid), dim3(GC * F::TPB), (DBV ? 2 : 1) * lds + tab, st, \
+        // the doubled LDS costs residency (fp64 0.245 -> 0.304 ms)
+        constexpr bool db = wg_per_cu == 1 && 2 * lds + tab <= (size_t)160 * 1024;
+#define PFB_COLP(NTV)                                                                                          \
+        hipLaunchKernelGGL((k_col_pow2p<T, H, E, db, NTV>), dim3(grid), dim3(GC * F::TPB), (db ? 2 : 1) * lds + tab, st, \
                            (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,                   \
                            (const cplx<T>*)ft->ptwc_col, nblk, nitems, p->T_elems_per_band,                    \
-                           p->psf_elems_per_band, rev ? band0 + nb - 1 : band0, rev ? -1 : 1);                 \
-        else                                                                                                   \
-        hipLaunchKernelGGL((k_col_pow2p<T, H, E, DBV, SPV, false>), dim3(grid), dim3(GC * F::TPB), (DBV ? 2 : 1) * lds + tab, st, \
-                           (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,                   \
-                           (const cplx<T>*)ft->ptwc_col, nblk, nitems, p->T_elems_per_band,                    \
-                           p->psf_elems_per_band, rev ? band0 + nb - 1 : band0, rev ? -1 : 1)
-        if (db) { if (spread) PFB_COLP(true, true); else PFB_COLP(true, false); }
-        else    { if (spread) PFB_COLP(false, true); else PFB_COLP(false, false); }
+                           p->psf_elems_per_band, band_first, -1)
+        if (psf_nt) PFB_COLP(true); else PFB_COLP(false);
 #undef PFB_COLP
         return;
     }
@@ -2741,39 +2240,39 @@ static void launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb
                        (const cplx<T>*)ft->ptw_col, nblk, p->T_elems_per_band, p->psf_elems_per_band, band0);
 }
 
+template <typename T, int H>
+static int col_set_attr() {
+    constexpr int lds_max = 160 * 1024;
+    constexpr int E = ecol<T, H>();
+    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2<T, H, E>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_fwd_pow2<T, H, E>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    using F = RegFft<T, H, E>;
+    constexpr int GC = col_groups<H, E>();
+    constexpr size_t lds = sizeof(cplx<T>) * (size_t)GC * FastCfg<T>::NVB * F::LDS_ELEMS;
+    constexpr size_t tab = sizeof(cplx<T>) * (size_t)((F::PTWC + 1) & ~1);
+    if constexpr (H >= 2048 && lds + tab <= (size_t)160 * 1024) {      // as in launch_col
+        constexpr int wg_per_cu = (8 * 64) / (GC * F::TPB) > 0 ? (8 * 64) / (GC * F::TPB) : 1;
+        constexpr bool db = wg_per_cu == 1 && 2 * lds + tab <= (size_t)160 * 1024;
+        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, H, E, db, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, H, E, db, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    }
+    // (k_col_pow2x<double, 4096> is never launched -- the one-level kernel serves 4096-point columns -- but it shares the
+    // 2048-point RegFft with k_col_pow2p<double, 2048>: without it the compiler contracts some products of that kernel
+    // differently and 2048^2 fp64 results change in the last bits)
+    if constexpr (H == 8192 || (H == 4096 && sizeof(T) == 8)) {
+        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2x<T, H, ECOLX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2x<T, H, ECOLX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    }
+    return PFB_OK;
+}
 template <typename T>
 static int col_set_attr_t(int H) {
-    constexpr int lds_max = 160 * 1024;
     switch (H) {
-#define X(NN) case NN:                                                                                        \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2<T, NN, ecol<T, NN>()>),                    \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, NN, ecol<T, NN>(), false, false>),     \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, NN, ecol<T, NN>(), true, false>),      \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, NN, ecol<T, NN>(), false, true>),      \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, NN, ecol<T, NN>(), true, true>),       \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, NN, ecol<T, NN>(), false, true, true>), \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, NN, ecol<T, NN>(), true, true, true>), \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_fwd_pow2<T, NN, ecol<T, NN>()>),                \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));              \
-        if constexpr (NN >= 2048) {                                                                           \
-            PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2x<T, NN, ECOLX, false>),                \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));          \
-            PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2x<T, NN, ECOLX, true>),                 \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));          \
-        }                                                                                                     \
-        break;
+#define X(NN) case NN: return col_set_attr<T, NN>();
         PFB_POW2_SIZES(X)
 #undef X
         default: set_error("pow2: unsupported nx"); return PFB_ERR_UNSUPPORTED;
     }
-    return PFB_OK;
 }
 int pow2_col_set_attr(int dtype, int H) {
     return dtype == PFB_F32 ? col_set_attr_t<float>(H) : col_set_attr_t<double>(H);
@@ -2827,45 +2326,29 @@ int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, 
 template <typename T, int L>
 static void launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
                            const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
-    constexpr int E = RowCfg<T, L, false>::E;
-    using F = RegFft<T, L, E, RowCfg<T, L, false>::WAVE>;
-    constexpr int G = row_groups<T, L, E, RowCfg<T, L, false>::GMAX>();
     FastDims d{p->nx, p->ny, p->M, p->T_elems_per_band, p->psf_elems_per_band, xpitch, xband};
     if constexpr (FwdP<T, L>::OK) {
-        if (ft->fwd_persistent) {
-            using FP = FwdP<T, L>;
-            const int tiles_per_band = p->nx / FP::G, ntiles = tiles_per_band * nb;
-            const int grid = ntiles < ft->num_cu * FP::WG_PER_CU ? ntiles : ft->num_cu * FP::WG_PER_CU;
-            const long double a = 6.283185307179586476925286766559005768L / (2.0L * (long double)p->ny);
-            const cplx<T> wq1((T)cosl(a), (T)(-sinl(a)));
-            // spreading the next tile's row requests over the even-bin sweep measured SLOWER here (0.389 -> 0.411 ms at
-            // 8 x 4096^2 fp32: the sweep's stores and the loads then queue behind each other): off unless PFB_SPREAD_FWD=1
-            // parities in sequence, next rows requested inside the second transform (k_row_fwd_pow2q); PFB_FWD_SEQ=0: A/B
-            static const bool seq = [] { const char* e = getenv("PFB_FWD_SEQ"); return !e || atoi(e); }();
-            if (seq) {
+        // persistent kernel: parities in sequence, next rows requested inside the second transform
+        using FP = FwdP<T, L>;
+        const int tiles_per_band = p->nx / FP::G, ntiles = tiles_per_band * nb;
+        const int grid = ntiles < ft->num_cu * FP::WG_PER_CU ? ntiles : ft->num_cu * FP::WG_PER_CU;
+        const long double a = 6.283185307179586476925286766559005768L / (2.0L * (long double)p->ny);
+        const cplx<T> wq1((T)cosl(a), (T)(-sinl(a)));
 #define PFB_FWDQ(BM)                                                                                              \
-                hipLaunchKernelGGL((k_row_fwd_pow2q<T, L, BM>), dim3(grid), dim3(FP::NT), FP::LDS, st, (const T*)x, \
-                                   (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)ft->twM,                      \
-                                   (const cplx<T>*)ft->ptwc_row_fwd, d, band0, tiles_per_band, ntiles, wq1)
-                if (beam) PFB_FWDQ(true); else PFB_FWDQ(false);
+        hipLaunchKernelGGL((k_row_fwd_pow2q<T, L, BM>), dim3(grid), dim3(FP::NT), FP::LDS, st, (const T*)x,      \
+                           (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)ft->twM,                              \
+                           (const cplx<T>*)ft->ptwc_row_fwd, d, band0, tiles_per_band, ntiles, wq1)
+        if (beam) PFB_FWDQ(true); else PFB_FWDQ(false);
 #undef PFB_FWDQ
-                return;
-            }
-            static const bool spread = [] { const char* e = getenv("PFB_SPREAD_FWD"); return e && atoi(e); }();
-#define PFB_FWDP(BM, SP)                                                                                          \
-            hipLaunchKernelGGL((k_row_fwd_pow2p<T, L, BM, SP>), dim3(grid), dim3(FP::NT), FP::LDS, st, (const T*)x, \
-                               (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)ft->twM,                          \
-                               (const cplx<T>*)ft->ptwc_row_fwd, d, band0, tiles_per_band, ntiles, wq1)
-            if (beam) { if (spread) PFB_FWDP(true, true); else PFB_FWDP(true, false); }
-            else      { if (spread) PFB_FWDP(false, true); else PFB_FWDP(false, false); }
-#undef PFB_FWDP
-            return;
-        }
+    } else {
+        constexpr int E = RowCfg<T, L, false>::E;
+        using F = RegFft<T, L, E, RowCfg<T, L, false>::WAVE>;
+        constexpr int G = row_groups<T, L, E, RowCfg<T, L, false>::GMAX>();
+        const size_t lds = sizeof(cplx<T>) * (size_t)G * (F::LDS_ELEMS + 4);
+        hipLaunchKernelGGL((k_row_fwd_pow2<T, L, E>), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
+                           (const T*)x, (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)p->twQ,
+                           (const cplx<T>*)ft->twM, (const cplx<T>*)ft->ptw_row, d, band0);
     }
-    const size_t lds = sizeof(cplx<T>) * (size_t)G * (F::LDS_ELEMS + 4);
-    hipLaunchKernelGGL((k_row_fwd_pow2<T, L, E>), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
-                       (const T*)x, (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)p->twQ,
-                       (const cplx<T>*)ft->twM, (const cplx<T>*)ft->ptw_row, d, band0);
 }
 
 template <typename T, int L>
@@ -2880,45 +2363,33 @@ static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, in
     if constexpr (InvP<T, L, EP>::OK) {
         // pipelined persistent kernel: no beam, inner products only against x itself (+ dot_with2)
         const bool plain_dots = !dot_with || (dot_with == x);
-        if (ft->inv_persistent && plain_dots && !(dot_with2 && !dot_with)) {
+        if (plain_dots && !(dot_with2 && !dot_with)) {
             using IP = InvP<T, L, EP>;
             const int tiles_per_band = p->nx / IP::G, ntiles = tiles_per_band * nb;
             const int grid = ntiles < IP::WG_PER_CU * ft->num_cu ? ntiles : IP::WG_PER_CU * ft->num_cu;
             const long double a = 6.283185307179586476925286766559005768L / (2.0L * (long double)p->ny);
             const cplx<T> wq1((T)cosl(a), (T)(-sinl(a)));
-            static const bool spread = [] { const char* e = getenv("PFB_SPREAD"); return !e || atoi(e); }();
-            static const int defer = [] { const char* e = getenv("PFB_INV_DEFER"); return e ? atoi(e) : 1; }();   // A/B
-#define PFB_INVP3(MODE, BM, SP)                                                                         \
-            hipLaunchKernelGGL((k_row_inv_pow2p<T, L, EP, MODE, BM, SP>), dim3(grid), dim3(IP::NT), IP::LDS, st, \
+#define PFB_INVP2(MODE, BM)                                                                             \
+            hipLaunchKernelGGL((k_row_inv_pow2p<T, L, EP, MODE, BM>), dim3(grid), dim3(IP::NT), IP::LDS, st, \
                                (const cplx<T>*)p->T, (const cplx<T>*)ft->twM,                           \
                                (const cplx<T>*)ft->ptw_row_inv_p, (const T*)x, (const T*)beam,          \
                                (const T*)dot_with2, (T*)out, p->partials, d, band0, tiles_per_band,     \
-                               ntiles, (T)scale, (T)sigmainv, wq1, defer, tail)
-#define PFB_INVP2(MODE, BM) do { if (spread) PFB_INVP3(MODE, BM, true); else PFB_INVP3(MODE, BM, false); } while (0)
+                               ntiles, (T)scale, (T)sigmainv, wq1)
 #define PFB_INVP(MODE) do { if (beam) PFB_INVP2(MODE, true); else PFB_INVP2(MODE, false); } while (0)
             p->last_npartials = grid;
-            // the PCG driver's bookkeeping rides in the tail of the MODE 2 kernel (pcg_state.hpp)
-            PcgTail tail = p->tail;
-            if (!(dot_with && dot_with2) || IP::NT < 256 || grid > 1024) tail.S = nullptr;
-            if (tail.S) p->tail_done = 1;
             if (!dot_with) PFB_INVP(0);
             else if (!dot_with2) PFB_INVP(1);
             else PFB_INVP(2);
 #undef PFB_INVP
 #undef PFB_INVP2
-#undef PFB_INVP3
             return;
         }
     }
     const size_t lds = 384 + sizeof(cplx<T>) * ((size_t)((F::PTWC + 1) & ~1) + (size_t)G * (F::LDS_ELEMS + 4) * (InvDb<T, L>::ON ? 2 : 1));
-    PcgTail tail = p->tail;
-    if (!(dot_with && dot_with2) || G * F::TPB < 256 || (size_t)(p->nx / G) * nb != (size_t)p->last_npartials ||
-        (size_t)(p->nx / G) * nb > 1024) tail.S = nullptr;
-    if (tail.S) p->tail_done = 1;
     hipLaunchKernelGGL((k_row_inv_pow2<T, L, E>), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
                        (const cplx<T>*)p->T, (const cplx<T>*)p->twQ, (const cplx<T>*)ft->twM,
                        (const cplx<T>*)ft->ptw_row_inv, (const T*)x, (const T*)beam, (const T*)dot_with,
-                       (const T*)dot_with2, (T*)out, p->partials, d, band0, (T)scale, (T)sigmainv, tail);
+                       (const T*)dot_with2, (T*)out, p->partials, d, band0, (T)scale, (T)sigmainv);
 }
 
 template <typename T>
@@ -2959,6 +2430,4 @@ int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* b
 #if PFB_STAMP && PFB_POW2_REST
 // diagnostic build only: buf = 3 * 1024 * PFB_STAMP_ITS * 16 device uint64 (NULL switches the stamps off)
 extern "C" int pfb_debug_set_stamps(void* buf) { return pfb::pow2_set_stamp((unsigned long long*)buf); }
-// diagnostic build only: src = an array shaped like the image cube that k_row_fwd_pow2q streams in addition (NULL: off)
-extern "C" int pfb_debug_set_extra_stream(const void* src, double* sink) { return pfb::pow2_set_xtra(src, sink); }
 #endif

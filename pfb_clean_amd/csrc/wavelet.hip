@@ -50,7 +50,7 @@ struct pfb_psi_plan {
     pfb::BasisInfo* bases;
     void* scratch[2];           // per band ping-pong approx / partial-image buffers
     size_t scratch_band;        // elements per band in each scratch buffer
-    // fused finest synthesis level (k_idwt_finest_fused): per-basis parameter table on the device
+    // fused finest synthesis level (k_idwt_finest_fused2): per-basis parameter table on the device
     // and one level-1 partial image per basis and band (all alive when the fused kernel runs)
     void* fin_prm;
     void* fin_scratch;
@@ -77,9 +77,8 @@ static inline int signal_size(int c, int F) { return 2 * c - F + 2; }
 // fetches) its own partial copy of the shared line.  Within every run of 64 consecutive workgroups the 8 that share an
 // XCD (ids j, j + 8, .. j + 56) are given 8 CONSECUTIVE tiles instead (speed only: any bijection is correct).
 struct TileId { int x, y, z; };
-__device__ __forceinline__ TileId xcd_tile(bool on) {
-    TileId t{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
-    if (!on) return t;
+__device__ __forceinline__ TileId xcd_tile() {
+    TileId t;
     const unsigned gx = gridDim.x, gy = gridDim.y;
     const unsigned total = gx * gy * gridDim.z;
     unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
@@ -152,7 +151,7 @@ template <typename T, int F, int TA>
 __device__ __forceinline__ void dwt_tile(T* smem, const T* __restrict__ flo, const T* __restrict__ fhi,
                                          const T* __restrict__ src, int ldin, int nxin, int nyin,
                                          T* __restrict__ dst, int ldc, int Cx, int Cy, T* __restrict__ approx,
-                                         int ox0, int oy0, bool allow_fast = true);
+                                         int ox0, int oy0);
 
 template <typename T, int F, int TA>
 __global__ void __launch_bounds__(256)
@@ -162,8 +161,7 @@ k_dwt_level(const T* __restrict__ in, size_t in_band, int ldin, int nxin, int ny
     extern __shared__ __attribute__((aligned(16))) char smem[];
     dwt_tile<T, F, TA>(reinterpret_cast<T*>(smem), f.lo, f.hi, in + (size_t)blockIdx.z * in_band, ldin, nxin, nyin,
                        coeffs + (size_t)blockIdx.z * c_band, ldc, Cx, Cy,
-                       approx ? approx + (size_t)blockIdx.z * a_band : nullptr, blockIdx.x * TA, blockIdx.y * TA,
-                       f.F > 0);                    // F < 0 (launch_dwt, PFB_DWT_FAST=0): plain tiles only
+                       approx ? approx + (size_t)blockIdx.z * a_band : nullptr, blockIdx.x * TA, blockIdx.y * TA);
 }
 
 // Register-blocked tile for 16-byte aligned input rows (the finest level of an image whose width is a multiple of
@@ -405,17 +403,15 @@ template <typename T, int F, int TA>
 __device__ __forceinline__ void dwt_tile(T* smem, const T* __restrict__ flo, const T* __restrict__ fhi,
                                          const T* __restrict__ src, int ldin, int nxin, int nyin,
                                          T* __restrict__ dst, int ldc, int Cx, int Cy, T* __restrict__ approx,
-                                         int ox0, int oy0, bool allow_fast) {
+                                         int ox0, int oy0) {
     constexpr int VW0 = 16 / (int)sizeof(T);
-    if (allow_fast && ldin % VW0 == 0 && nyin % VW0 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && TA % (2 * VW0) == 0) {
+    if (ldin % VW0 == 0 && nyin % VW0 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && TA % (2 * VW0) == 0) {
         dwt_tile_fast<T, F, TA, true>(smem, flo, fhi, src, ldin, nxin, nyin, dst, ldc, Cx, Cy, approx, ox0, oy0);
         return;
     }
     if constexpr (TA % (2 * VW0) == 0 && (2 * TA + F - 2) / 2 <= 64) {
-        if (allow_fast) {
-            dwt_tile_fast<T, F, TA, false>(smem, flo, fhi, src, ldin, nxin, nyin, dst, ldc, Cx, Cy, approx, ox0, oy0);
-            return;
-        }
+        dwt_tile_fast<T, F, TA, false>(smem, flo, fhi, src, ldin, nxin, nyin, dst, ldc, Cx, Cy, approx, ox0, oy0);
+        return;
     }
     constexpr int NI = 2 * TA + F - 2;        // input samples per tile edge
     // Both passes decimate by two (index 2q + d): with a plain row the 32 lanes of a half-wave touch only 16
@@ -540,9 +536,7 @@ __global__ void __launch_bounds__(256)
 k_dwt_batched(const T* __restrict__ in_base, size_t in_band, T* __restrict__ alpha, size_t aband, int ldc,
               T* __restrict__ scr_out, size_t sband, const AnaPrm<T>* __restrict__ prm, int nwb) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const bool allow_fast = !(nwb & (1 << 30));     // PFB_DWT_FAST=0 (A/B): plain tiles only
-    const TileId tl = xcd_tile(!(nwb & (1 << 29))); // PFB_PSI_XCD=0 (A/B): launch order
-    nwb &= ~(3 << 29);
+    const TileId tl = xcd_tile();
     const int j = tl.z % nwb, band = tl.z / nwb;
     const AnaPrm<T>& P = prm[j];
     const int ox0 = tl.x * TA, oy0 = tl.y * TA;
@@ -551,7 +545,7 @@ k_dwt_batched(const T* __restrict__ in_base, size_t in_band, T* __restrict__ alp
     T* dst = alpha + (size_t)band * aband + P.coeff_off;
     T* approx = P.has_approx ? scr_out + P.approx_off + (size_t)band * sband : nullptr;
     switch (P.F) {
-#define X(FF) case FF: if constexpr (FF <= FMAX) dwt_tile<T, FF, TA>(reinterpret_cast<T*>(smem_raw), P.lo, P.hi, src, P.ldin, P.nxin, P.nyin, dst, ldc, P.Cx, P.Cy, approx, ox0, oy0, allow_fast); break;
+#define X(FF) case FF: if constexpr (FF <= FMAX) dwt_tile<T, FF, TA>(reinterpret_cast<T*>(smem_raw), P.lo, P.hi, src, P.ldin, P.nxin, P.nyin, dst, ldc, P.Cx, P.Cy, approx, ox0, oy0); break;
         X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18)
 #undef X
         default: break;
@@ -573,8 +567,7 @@ k_dwt_l1_fused(const T* __restrict__ x, size_t xband, int ldin, int nxin, int ny
     T* A = reinterpret_cast<T*>(smem_raw);
     constexpr int NIS = D::ni(TA, FS), SA = D::sa(TA, FS), AO = NIS * SA, OFFS = D::off(FS, true);
     T* B = A + 2 * AO;
-    const TileId tl = xcd_tile(!(nwb & (1 << 29)));
-    nwb &= ~(1 << 29);
+    const TileId tl = xcd_tile();
     const int band = tl.z;
     const int ox0 = tl.x * TA, oy0 = tl.y * TA;
     dwt_fast_stage<T, FS, TA, true>(A, x + (size_t)band * xband, ldin, nxin, nyin, ox0, oy0);
@@ -861,28 +854,6 @@ __device__ __forceinline__ void idwt_tile_store(T* smem, const T* __restrict__ f
             if (gy < nyw)     { q[0] = sl0 + sh0; }
             if (gy + 1 < nyw) { q[1] = sl1 + sh1; }
         }
-    }
-}
-
-template <typename T, int TS, int FMAX>
-__global__ void __launch_bounds__(256)
-k_idwt_batched(const T* __restrict__ alpha, size_t aband, int ldc, const T* __restrict__ scr_prev, size_t sband,
-               T* __restrict__ out_base, size_t oband, const SynPrm<T>* __restrict__ prm, int nwb) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const TileId tl = xcd_tile(!(nwb & (1 << 29)));
-    nwb &= ~(1 << 29);
-    const int j = tl.z % nwb, band = tl.z / nwb;
-    const SynPrm<T>& P = prm[j];
-    const int ix0 = tl.x * TS, iy0 = tl.y * TS;
-    if (ix0 >= P.nxw || iy0 >= P.nyw) return;
-    const T* src = alpha + (size_t)band * aband + P.coeff_off;
-    const T* pv = P.has_prev ? scr_prev + P.prev_off + (size_t)band * sband : nullptr;
-    T* dst = out_base + P.out_off + (size_t)band * oband;
-    switch (P.F) {
-#define X(FF) case FF: if constexpr (FF <= FMAX) idwt_tile_store<T, FF, TS>(reinterpret_cast<T*>(smem_raw), P.lo, P.hi, src, ldc, P.nax, P.nay, pv, P.ldp, dst, P.ldo, P.nxw, P.nyw, ix0, iy0); break;
-        X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18)
-#undef X
-        default: break;
     }
 }
 
@@ -1205,145 +1176,9 @@ template <typename T> struct FinBasis {
     T lo[MAXF], hi[MAXF];       // rec_lo, rec_hi
 };
 
-// one basis' contribution to the thread's output pairs (same staging / passes as k_idwt_level)
-template <typename T, int F, int TS>
-__device__ __forceinline__ void idwt_tile_acc(T* smem, const FinBasis<T>& B, const T* __restrict__ src, int ldc,
-                                              const T* __restrict__ pv, int ix0, int iy0, int tid,
-                                              T (&acc)[TS * (TS / 2) / 256][2]) {
-    constexpr int h = F / 2;
-    constexpr int NC = TS / 2 + h - 1;
-    constexpr int SC = 2 * NC + 1;
-    constexpr int ST = TS + 1;
-    T* C = smem;
-    T* Tm = C + 2 * NC * SC;
-    const int nax = B.nax, nay = B.nay, ldp = B.ldp;
-    const int mx0 = ix0 / 2, my0 = iy0 / 2;
-    T lo[F], hi[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) { lo[j] = B.lo[j]; hi[j] = B.hi[j]; }
-    T stage[StageCfg<NC>::NLD];
-    coef_load<T, NC>(stage, src, ldc, nax, nay, mx0, my0, pv != nullptr, tid);
-    constexpr int NLP = (NC * NC + 255) / 256;
-    T stagep[NLP];
-    if (pv) {
-#pragma unroll
-        for (int k = 0; k < NLP; ++k) {
-            const int e = tid + 256 * k;
-            const int cx = e / NC, ry = e - cx * NC;
-            const int gy = my0 + ry, gx = mx0 + cx;
-            T v = 0;
-            if (e < NC * NC && gy < nay && gx < nax) v = pv[(size_t)gx * ldp + gy];
-            stagep[k] = v;
-        }
-    }
-    __syncthreads();                                   // the previous basis is done with the LDS
-    coef_store<T, NC, SC>(C, stage, pv != nullptr, tid);
-    if (pv) {
-#pragma unroll
-        for (int k = 0; k < NLP; ++k) {
-            const int e = tid + 256 * k;
-            const int cx = e / NC, ry = e - cx * NC;
-            if (e < NC * NC) C[ry * SC + cx] = stagep[k];
-        }
-    }
-    __syncthreads();
-    for (int e = tid; e < 2 * NC * (TS / 2); e += 256) {
-        const int ry = e / (TS / 2), m = e - ry * (TS / 2);
-        const T* c = C + ry * SC + m + h - 1;
-        T sl0 = 0, sh0 = 0, sl1 = 0, sh1 = 0;
-#pragma unroll
-        for (int j = 0; j < h; ++j) {
-            const T a = c[-j], d = c[NC - j];
-            sl0 += lo[2 * j] * a;     sh0 += hi[2 * j] * d;
-            sl1 += lo[2 * j + 1] * a; sh1 += hi[2 * j + 1] * d;
-        }
-        Tm[ry * ST + 2 * m] = sl0 + sh0;
-        Tm[ry * ST + 2 * m + 1] = sl1 + sh1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < TS * (TS / 2) / 256; ++k) {
-        const int e = tid + 256 * k;
-        const int ox = e / (TS / 2), m = e - ox * (TS / 2);
-        const T* t = Tm + (m + h - 1) * ST + ox;
-        T sl0 = 0, sh0 = 0, sl1 = 0, sh1 = 0;
-#pragma unroll
-        for (int j = 0; j < h; ++j) {
-            const T a = t[-j * ST], d = t[(NC - j) * ST];
-            sl0 += lo[2 * j] * a;     sh0 += hi[2 * j] * d;
-            sl1 += lo[2 * j + 1] * a; sh1 += hi[2 * j + 1] * d;
-        }
-        acc[k][0] += sl0 + sh0;
-        acc[k][1] += sl1 + sh1;
-    }
-}
-
-template <typename T, int TS, int FMAX>
-__global__ void __launch_bounds__(256)
-k_idwt_finest_fused(const T* __restrict__ alpha, size_t aband, int ldc, const FinBasis<T>* __restrict__ prm,
-                    int nbasis, const T* __restrict__ fin, size_t fin_band,
-                    T* __restrict__ xo, size_t xband, int ldo, int nxw, int nyw) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    T* smem = reinterpret_cast<T*>(smem_raw);
-    constexpr int NP = TS * (TS / 2) / 256;
-    T acc[NP][2];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) { acc[k][0] = 0; acc[k][1] = 0; }
-    const TileId tl = xcd_tile(!(nbasis & (1 << 29)));
-    nbasis &= ~(1 << 29);
-    const int ix0 = tl.x * TS, iy0 = tl.y * TS;
-    const T* ab = alpha + (size_t)tl.z * aband;
-    for (int ib = 0; ib < nbasis; ++ib) {
-        const FinBasis<T>& B = prm[ib];
-        const T* src = ab + B.coeff_off;
-        // the per-thread index arithmetic of every basis body is loop invariant: without this the
-        // compiler hoists all of it out of the basis loop (256 VGPRs, occupancy 2; with it 8x less)
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        if (B.K == 0) {
-            // 'self': x[gx][gy] += alpha[gy][gx]  (psi.py:229-232) through an LDS transpose
-            constexpr int SS = TS + 1;
-            __syncthreads();
-            for (int e = tid; e < TS * TS; e += 256) {
-                const int ly = e / TS, lx = e - ly * TS;                  // lx fastest: rows of alpha
-                T v = 0;
-                if (iy0 + ly < nyw && ix0 + lx < nxw) v = src[(size_t)(iy0 + ly) * ldc + ix0 + lx];
-                smem[ly * SS + lx] = v;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int e = tid + 256 * k;
-                const int ox = e / (TS / 2), m = e - ox * (TS / 2);
-                acc[k][0] += smem[(2 * m) * SS + ox];
-                acc[k][1] += smem[(2 * m + 1) * SS + ox];
-            }
-            continue;
-        }
-        const T* pv = B.has_prev ? fin + B.prev_off + (size_t)tl.z * fin_band : nullptr;
-        switch (B.F) {
-#define X(FF) case FF: if constexpr (FF <= FMAX) idwt_tile_acc<T, FF, TS>(smem, B, src, ldc, pv, ix0, iy0, tid, acc); break;
-            X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18)
-#undef X
-            default: break;
-        }
-    }
-    T* dst = xo + (size_t)tl.z * xband;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        const int e = threadIdx.x + 256 * k;
-        const int ox = e / (TS / 2), m = e - ox * (TS / 2);
-        const int gx = ix0 + ox, gy = iy0 + 2 * m;
-        if (gx < nxw) {
-            T* q = dst + (size_t)gx * ldo + gy;
-            if (gy < nyw) q[0] = acc[k][0];
-            if (gy + 1 < nyw) q[1] = acc[k][1];
-        }
-    }
-}
-
-// ------------------------------------------------ lean fused finest level (second generation)
-// rocprofv3 + the ISA of the kernel above: ~4500 instructions per thread and tile, of which the arithmetic is a
+// ------------------------------------------------ lean fused finest level
+// rocprofv3 + the ISA of the first-generation kernel (staging and passes as in k_idwt_level; removed, the code is at
+// commit e9a762c): ~4500 instructions per thread and tile, of which the arithmetic is a
 // fifth -- the staging spends ~45 SCALAR instructions per wave-row on quadrant selects, 64-bit row addresses and
 // exec-mask juggling (the CU has ONE scalar unit: 117 of the kernel's 185 us), the passes one LDS read and a few index
 // instructions per tap.  Same mathematics here, organised around instruction count:
@@ -1522,8 +1357,7 @@ k_idwt_finest_fused2(const T* __restrict__ alpha, size_t aband, int ldc, const F
     T acc[2 * MBY];
 #pragma unroll
     for (int k = 0; k < 2 * MBY; ++k) acc[k] = 0;
-    const TileId tl = xcd_tile(!(nbasis & (1 << 29)));
-    nbasis &= ~(1 << 29);
+    const TileId tl = xcd_tile();
     const int ix0 = tl.x * TS, iy0 = tl.y * TS;
     const T* ab = alpha + (size_t)tl.z * aband;
     for (int ib = 0; ib < nbasis; ++ib) {
@@ -1563,8 +1397,7 @@ __global__ void __launch_bounds__(256)
 k_idwt_batched2(const T* __restrict__ alpha, size_t aband, int ldc, const T* __restrict__ scr_prev, size_t sband,
                 T* __restrict__ out_base, size_t oband, const SynPrm<T>* __restrict__ prm, int nwb) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const TileId tl = xcd_tile(!(nwb & (1 << 29)));
-    nwb &= ~(1 << 29);
+    const TileId tl = xcd_tile();
     const int j = tl.z % nwb, band = tl.z / nwb;
     const SynPrm<T>& P = prm[j];
     const int ix0 = tl.x * TS, iy0 = tl.y * TS;
@@ -1614,10 +1447,7 @@ static size_t idwt_lds(int F) {
 template <typename T>
 static void launch_dwt(int F, dim3 grid, size_t lds, hipStream_t st, const T* in, size_t in_band, int ldin,
                        int nxin, int nyin, T* blk, size_t c_band, int ldc, int Cx, int Cy, T* approx,
-                       size_t a_band, const Filt<T>& f_in) {
-    static const bool fast = [] { const char* e = getenv("PFB_DWT_FAST"); return !e || atoi(e); }();
-    Filt<T> f = f_in;
-    if (!fast) f.F = -f.F;
+                       size_t a_band, const Filt<T>& f) {
     switch (F) {
 #define X(FF) case FF: hipLaunchKernelGGL((k_dwt_level<T, FF, Tile<T>::TA>), grid, dim3(256), lds, st, in, in_band, \
                                           ldin, nxin, nyin, blk, c_band, ldc, Cx, Cy, approx, a_band, f); break;
@@ -1731,10 +1561,6 @@ static int psi_fin_prepare(pfb_psi_plan* p) {
     PFB_HIP_CHECK(hipMalloc(&p->fin_scratch, sizeof(T) * p->fin_basis * p->nbasis));
     constexpr int TS = Tile<T>::TS;
     constexpr int TA = Tile<T>::TA;
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_finest_fused<T, TS, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_finest_fused<T, TS, 18>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_batched2<T, TS, 8>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_batched2<T, TS, 18>),
@@ -1750,10 +1576,6 @@ static int psi_fin_prepare(pfb_psi_plan* p) {
     PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_dwt_batched<T, TA, 8>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_dwt_batched<T, TA, 18>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_batched<T, TS, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_batched<T, TS, 18>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // ---- batched level tables: [level][wavelet basis]
     std::vector<int> wb;
@@ -1819,9 +1641,7 @@ static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t 
     constexpr int TA = Tile<T>::TA;
     // finest level of all bases (and the first 'self' plane) in one kernel when the image rows are 16-byte aligned
     constexpr int VW = 16 / (int)sizeof(T);
-    static const bool l1f_on = [] { const char* e = getenv("PFB_DWT_L1FUSED"); const char* f = getenv("PFB_DWT_FAST");
-                                    return (!e || atoi(e)) && (!f || atoi(f)); }();     // built from the fast tile's passes
-    const bool l1_fused = l1f_on && p->nwb > 0 && p->ny % VW == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+    const bool l1_fused = p->nwb > 0 && p->ny % VW == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
                           TA % (2 * VW) == 0;
     long long self_off = -1;
     for (int ib = 0; ib < p->nbasis; ++ib) {
@@ -1833,33 +1653,29 @@ static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t 
     }
     if (p->nwb > 0) {
         const size_t lds = dwt_lds<T>(p->fin_fmax);
-        static const int xoffa = [] { const char* e = getenv("PFB_PSI_XCD"); return (!e || atoi(e)) ? 0 : (1 << 29); }();
         if (l1_fused) {
             dim3 grid(p->gx_ana[0], p->gy_ana[0], p->nband);
             const AnaPrm<T>* prm = (const AnaPrm<T>*)p->ana_prm;
             if (p->fin_fmax <= 8)
                 hipLaunchKernelGGL((k_dwt_l1_fused<T, TA, 8>), grid, dim3(256), sizeof(T) * DwtFast<T>::elems(TA, 8), st, x, xband,
                                    p->ny, p->nx, p->ny, alpha, aband, p->Nxmax, (T*)p->bscr[0], p->scratch_band, prm,
-                                   p->nwb | xoffa, self_off);
+                                   p->nwb, self_off);
             else
                 hipLaunchKernelGGL((k_dwt_l1_fused<T, TA, 18>), grid, dim3(256), sizeof(T) * DwtFast<T>::elems(TA, 18), st, x, xband,
                                    p->ny, p->nx, p->ny, alpha, aband, p->Nxmax, (T*)p->bscr[0], p->scratch_band, prm,
-                                   p->nwb | xoffa, self_off);
+                                   p->nwb, self_off);
         }
         for (int l = l1_fused ? 1 : 0; l < p->nlevel; ++l) {
             dim3 grid(p->gx_ana[l], p->gy_ana[l], p->nband * p->nwb);
             const T* in = l == 0 ? x : (const T*)p->bscr[(l - 1) & 1];
             const size_t in_band = l == 0 ? xband : p->scratch_band;
             const AnaPrm<T>* prm = (const AnaPrm<T>*)p->ana_prm + (size_t)l * p->nwb;
-            static const bool fast = [] { const char* e = getenv("PFB_DWT_FAST"); return !e || atoi(e); }();
-            static const bool xcd = [] { const char* e = getenv("PFB_PSI_XCD"); return !e || atoi(e); }();
-            const int nwb_arg = p->nwb | (fast ? 0 : (1 << 30)) | (xcd ? 0 : (1 << 29));
             if (p->fin_fmax <= 8)
                 hipLaunchKernelGGL((k_dwt_batched<T, TA, 8>), grid, dim3(256), lds, st, in, in_band, alpha, aband,
-                                   p->Nxmax, (T*)p->bscr[l & 1], p->scratch_band, prm, nwb_arg);
+                                   p->Nxmax, (T*)p->bscr[l & 1], p->scratch_band, prm, p->nwb);
             else
                 hipLaunchKernelGGL((k_dwt_batched<T, TA, 18>), grid, dim3(256), lds, st, in, in_band, alpha, aband,
-                                   p->Nxmax, (T*)p->bscr[l & 1], p->scratch_band, prm, nwb_arg);
+                                   p->Nxmax, (T*)p->bscr[l & 1], p->scratch_band, prm, p->nwb);
         }
     }
     PFB_HIP_CHECK(hipGetLastError());
@@ -1875,54 +1691,31 @@ static int psi_hdot_fused_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t 
     const size_t aband = plane * p->nbasis;
     const size_t xband = (size_t)p->nx * p->ny;
     constexpr int TS = Tile<T>::TS;
-    static const int xoff = [] { const char* e = getenv("PFB_PSI_XCD"); return (!e || atoi(e)) ? 0 : (1 << 29); }();
     if (p->nwb > 0) {
-        const size_t ldsb = idwt_lds<T>(p->fin_fmax);
+        const size_t lds2 = sizeof(T) * SynFast<T, TS>::elems(p->fin_fmax);
         for (int l = p->nlevel - 1; l >= 1; --l) {       // coarse levels: one launch per level, all bases
             dim3 g(p->gx_syn[l], p->gy_syn[l], p->nband * p->nwb);
             const SynPrm<T>* prm = (const SynPrm<T>*)p->syn_prm + (size_t)l * p->nwb;
             T* out = l == 1 ? (T*)p->fin_scratch : (T*)p->bscr[l & 1];
             const size_t oband = l == 1 ? p->fin_band : p->scratch_band;
-            static const bool lean = [] { const char* e = getenv("PFB_PSI_FIN2"); return !e || atoi(e); }();
-            if (lean && SynFast<T, TS>::ok) {
-                const size_t lds2 = sizeof(T) * SynFast<T, TS>::elems(p->fin_fmax);
-                if (p->fin_fmax <= 8)
-                    hipLaunchKernelGGL((k_idwt_batched2<T, TS, 8>), g, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                                       (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb | xoff);
-                else
-                    hipLaunchKernelGGL((k_idwt_batched2<T, TS, 18>), g, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                                       (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb | xoff);
-            } else if (p->fin_fmax <= 8)
-                hipLaunchKernelGGL((k_idwt_batched<T, TS, 8>), g, dim3(256), ldsb, st, alpha, aband, p->Nxmax,
-                                   (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb | xoff);
+            if (p->fin_fmax <= 8)
+                hipLaunchKernelGGL((k_idwt_batched2<T, TS, 8>), g, dim3(256), lds2, st, alpha, aband, p->Nxmax,
+                                   (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb);
             else
-                hipLaunchKernelGGL((k_idwt_batched<T, TS, 18>), g, dim3(256), ldsb, st, alpha, aband, p->Nxmax,
-                                   (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb | xoff);
+                hipLaunchKernelGGL((k_idwt_batched2<T, TS, 18>), g, dim3(256), lds2, st, alpha, aband, p->Nxmax,
+                                   (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb);
         }
     }
     dim3 grid((p->nx + TS - 1) / TS, (p->ny + TS - 1) / TS, p->nband);
-    size_t lds = idwt_lds<T>(p->fin_fmax);
-    const size_t lds_self = sizeof(T) * (size_t)TS * (TS + 1);
-    if (lds < lds_self) lds = lds_self;
-    static const bool fin2 = [] { const char* e = getenv("PFB_PSI_FIN2"); return !e || atoi(e); }();
-    if (fin2 && SynFast<T, TS>::ok) {
-        static_assert(SynFast<T, TS>::ok, "tile shape of the lean fused kernel");
-        const size_t lds2 = sizeof(T) * SynFast<T, TS>::elems(p->fin_fmax);
-        if (p->fin_fmax <= 8)
-            hipLaunchKernelGGL((k_idwt_finest_fused2<T, TS, 8>), grid, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                               (const FinBasis<T>*)p->fin_prm, p->nbasis | xoff, (const T*)p->fin_scratch, p->fin_band,
-                               xo, xband, p->ny, p->nx, p->ny);
-        else
-            hipLaunchKernelGGL((k_idwt_finest_fused2<T, TS, 18>), grid, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                               (const FinBasis<T>*)p->fin_prm, p->nbasis | xoff, (const T*)p->fin_scratch, p->fin_band,
-                               xo, xband, p->ny, p->nx, p->ny);
-    } else if (p->fin_fmax <= 8)
-        hipLaunchKernelGGL((k_idwt_finest_fused<T, TS, 8>), grid, dim3(256), lds, st, alpha, aband, p->Nxmax,
-                           (const FinBasis<T>*)p->fin_prm, p->nbasis | xoff, (const T*)p->fin_scratch, p->fin_band,
+    static_assert(SynFast<T, TS>::ok, "tile shape of the lean fused kernel");
+    const size_t lds2 = sizeof(T) * SynFast<T, TS>::elems(p->fin_fmax);
+    if (p->fin_fmax <= 8)
+        hipLaunchKernelGGL((k_idwt_finest_fused2<T, TS, 8>), grid, dim3(256), lds2, st, alpha, aband, p->Nxmax,
+                           (const FinBasis<T>*)p->fin_prm, p->nbasis, (const T*)p->fin_scratch, p->fin_band,
                            xo, xband, p->ny, p->nx, p->ny);
     else
-        hipLaunchKernelGGL((k_idwt_finest_fused<T, TS, 18>), grid, dim3(256), lds, st, alpha, aband, p->Nxmax,
-                           (const FinBasis<T>*)p->fin_prm, p->nbasis | xoff, (const T*)p->fin_scratch, p->fin_band,
+        hipLaunchKernelGGL((k_idwt_finest_fused2<T, TS, 18>), grid, dim3(256), lds2, st, alpha, aband, p->Nxmax,
+                           (const FinBasis<T>*)p->fin_prm, p->nbasis, (const T*)p->fin_scratch, p->fin_band,
                            xo, xband, p->ny, p->nx, p->ny);
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;
@@ -1988,7 +1781,7 @@ static int psi_hdot_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t st) {
 
 // grid for the streaming elementwise kernels that WRITE as much as they read: a few workgroups per
 // CU (tools/micro/hbm_stream.hip: the write-heavy mixes lose 10-25 % when the chip is oversubscribed)
-static inline int stream_grid(size_t nvec, int per_cu) {
+static inline int stream_grid(size_t nvec) {
     static const int ncu = [] {
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
@@ -1996,7 +1789,7 @@ static inline int stream_grid(size_t nvec, int per_cu) {
         return v;
     }();
     size_t g = (nvec + 255) / 256;
-    if (g > (size_t)ncu * per_cu) g = (size_t)ncu * per_cu;
+    if (g > (size_t)ncu) g = ncu;
     if (g < 1) g = 1;
     return (int)g;
 }
@@ -2012,8 +1805,6 @@ template <typename T>
 static void dual_update_launch(const T* vp, T* v, const T* w, T lam, T sigma, int nband, size_t nper, T* vp_out,
                                hipStream_t st) {
     constexpr int V = 16 / sizeof(T);
-    static const int per_cu = [] { const char* e = getenv("PFB_DUAL_PER_CU"); const int o = e ? atoi(e) : 0;
-                                   return o > 0 && o <= 16 ? o : 1; }();
     auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
     const bool vec = nband <= 8 && nper % V == 0 && al(vp) && al(v) && al(w) && (!vp_out || al(vp_out));
     if (!vec) {
@@ -2021,10 +1812,9 @@ static void dual_update_launch(const T* vp, T* v, const T* w, T lam, T sigma, in
                            nper, vp_out);
         return;
     }
-    const dim3 grid(stream_grid(nper / V, per_cu));
+    const dim3 grid(stream_grid(nper / V));
     // non-temporal reads of vp / psi^H(x) once the cube is far beyond the caches (+0.8 % on the config #4 iteration)
-    static const int ntl_env = [] { const char* e = getenv("PFB_DUAL_NT"); return e ? atoi(e) : -1; }();
-    const bool ntl = ntl_env >= 0 ? ntl_env != 0 : (size_t)nband * nper * sizeof(T) >= ((size_t)64 << 20);
+    const bool ntl = (size_t)nband * nper * sizeof(T) >= ((size_t)64 << 20);
 #define PFB_DU_CASE(NB) case NB: if (ntl) hipLaunchKernelGGL((k_dual_update_vec<T, NB, true>), grid, dim3(256), 0, st, vp, v, w, \
                                                     lam, sigma, nper, vp_out); \
                                  else hipLaunchKernelGGL((k_dual_update_vec<T, NB, false>), grid, dim3(256), 0, st, vp, v, w, \
@@ -2256,8 +2046,7 @@ static int pd_primal_launch(int dtype, const void* xp, const void* xout, const v
     int G = ew_grid(npix) > 1024 ? 1024 : ew_grid(npix);
     const uintptr_t al = (uintptr_t)xp | (uintptr_t)xout | (uintptr_t)xprev | (uintptr_t)g | (uintptr_t)gsub | (uintptr_t)x;
     const size_t V = dtype == PFB_F32 ? 4 : 2;
-    static const bool vec_on = [] { const char* e = getenv("PFB_PD_VEC"); return !e || atoi(e); }();
-    if (vec_on && (al & 15) == 0 && npix % V == 0) {          // band offsets (npix elements) stay 16-byte aligned
+    if ((al & 15) == 0 && npix % V == 0) {          // band offsets (npix elements) stay 16-byte aligned
         const size_t nvec = npix / V;
         G = ew_grid(nvec) > 1024 ? 1024 : ew_grid(nvec);
         if (dtype == PFB_F32)

@@ -151,7 +151,7 @@ def test_conv_tensor_path_and_fused_dot(amd, shape):
 @pmp('ny', [4096, 2048])
 @pmp('mode', [0, 1, 2])
 def test_persistent_row_kernels_multi_tile(amd, mode, ny, with_beam):
-    """ny = 4096 / 2048 fp32 take the persistent pipelined row kernels (k_row_fwd_pow2p for ny = 4096,
+    """ny = 4096 / 2048 fp32 take the persistent pipelined row kernels (k_row_fwd_pow2q for ny = 4096,
     k_row_inv_pow2p for both; with and without a beam); with 3 bands every workgroup walks several row
     tiles and crosses band boundaries.  mode 0: no inner products, 1: <x, out>, <out, out>, 2: + <w, out>
     (pfb_psfconv_apply_dots, the call the fused PCG makes)."""

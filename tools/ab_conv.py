@@ -1,9 +1,10 @@
 """A/B of convolution-kernel variants on ONE device (guide rule 24: never rank builds across boxes).
-Variants are environment settings the library reads once per process, so each measurement is a child process;
-the variants are interleaved over several rounds and the median stage times reported.
+Variants are environment settings the library reads once per process -- another build of the library
+(PFB_HIP_LIB) or a path switch -- so each measurement is a child process; the variants are interleaved over
+several rounds and the median stage times reported.
 
     python tools/ab_conv.py [--size 4096] [--bands 8] [--dtype f32] [--rounds 3] NAME:ENV=V,ENV=V ...
-e.g. python tools/ab_conv.py base: seq0:PFB_FWD_SEQ=0 spread0:PFB_SPREAD=0
+e.g. python tools/ab_conv.py base: base2:PFB_HIP_LIB=../pfb-base/pfb_clean_amd/libpfb_hip.so generic:PFB_FORCE_GENERIC=1
 """
 import argparse
 import json

@@ -23,9 +23,7 @@ dt = torch.float64 if (len(sys.argv) > 3 and sys.argv[3] == 'f64') else torch.fl
 cdt = torch.complex128 if dt == torch.float64 else torch.complex64
 ITS, NWG, NSLOT = 4, 1024, 16
 NAMES = {
-    # default forward kernel k_row_fwd_pow2q (parities in sequence); PFB_FWD_SEQ=0 runs k_row_fwd_pow2p, whose seven
-    # intervals are: pack + w_M multiply | both transforms | LDS write even + issue next x | even sweep | LDS write odd |
-    # odd sweep | final barrier
+    # the persistent forward kernel k_row_fwd_pow2q (parities in sequence)
     0: ('k_row_fwd_pow2q', ['top -> pack (x * beam)', 'FFT (even bins)', 'LDS write even + barriers',
                              'post-process + store even bins', 'z w_M, FFT (odd bins) with the next rows requested per pass',
                              'LDS write odd + post-process + store odd bins', 'final barrier']),
@@ -36,7 +34,7 @@ NAMES = {
                             'build (odd)', 'IFFT (odd)', 'wait x, r; epilogue + stores issued']),
 }
 
-if n >= 8192 or os.environ.get('PFB_COL_X', '0') not in ('', '0'):
+if n >= 8192:
     # two-level column kernel (k_col_pow2x): four rounds (classes 0, 2, 1, 3) of FFT | multiply + IFFT | accumulate + next input
     NAMES[1] = ('k_col_pow2x', ['r0: a_lo + a_hi, FFT', 'r0: wait psf, multiply, IFFT (psf class 2 requested)',
                                 'r0 -> r2: keep c0, form (a_lo - a_hi) w^2n', 'r2: FFT', 'r2: multiply, IFFT (class 1 requested)',
