@@ -29,13 +29,14 @@ def to_dev(a, dtype=None):
     needed)."""
     if a is None:
         return None
-    dev = require_device()
-    if isinstance(a, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=False)
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        t = a
+    elif isinstance(a, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(require_device(), non_blocking=False)
     elif isinstance(a, torch.Tensor):
-        t = a if a.is_cuda else a.to(dev)
+        t = a.to(require_device())
     else:
-        t = torch.as_tensor(a, device=dev)
+        t = torch.as_tensor(a, device=require_device())
     if dtype is not None and t.dtype != dtype:
         t = t.to(dtype)
     return t.contiguous()
@@ -71,15 +72,60 @@ def scratch():
     return cache[key]
 
 
-def give_back(t, like, out=None):
-    """Return a result the way the caller handed data in: numpy in -> numpy out
-    (written into `out` when given), tensor in -> tensor out."""
-    if isinstance(like, np.ndarray):
-        if out is not None and isinstance(out, np.ndarray):
-            out[...] = t.cpu().numpy()
-            return out
-        return t.cpu().numpy()
-    if out is not None and isinstance(out, torch.Tensor) and out is not t:
-        out.copy_(t)
+def dot_into(u, v, out, slot=0):
+    """out[slot] = <u, v> in fp64 (out: the fp64 device vector of scratch()); no host synchronisation."""
+    ws = scratch()[0]
+    _lib.check(_lib.load().pfb_dot(code(u.dtype), ptr(u), ptr(v), u.numel(), ptr(out) + 8 * slot, ptr(ws), stream()))
+
+
+def dot(u, v):
+    out = scratch()[1]
+    dot_into(u, v, out)
+    return out[0].item()
+
+
+def any_nonzero(u):
+    ws, out = scratch()
+    _lib.check(_lib.load().pfb_any_nonzero(code(u.dtype), ptr(u), u.numel(), ptr(out), ptr(ws), stream()))
+    return out[0].item() != 0.0
+
+
+def axpby(a, u, b, v):
+    """v = a*u + b*v, in place on v."""
+    _lib.check(_lib.load().pfb_axpby(code(v.dtype), float(a), ptr(u), float(b), ptr(v), v.numel(), stream()))
+
+
+def norm_diff_sums(x, xp):
+    """Device fp64 pair (sum (x-xp)^2, sum x^2) -- a 2-element view of scratch()'s output vector, overwritten by the
+    next reduction on this thread and stream."""
+    ws, out = scratch()
+    _lib.check(_lib.load().pfb_norm_diff_sums(code(x.dtype), ptr(x), ptr(xp), x.numel(), ptr(out), ptr(ws), stream()))
+    return out[:2]
+
+
+# ---- the array boundary: results go back in the kind of array the caller handed in
+def host_like(t, like):
+    """Device tensor t as the caller's kind: a numpy copy when `like` is numpy, else t itself."""
+    return t.cpu().numpy() if isinstance(like, np.ndarray) else t
+
+
+def out_buffer(out, like, alias=True, shape=None):
+    """The tensor a kernel writes a fresh result into: the caller's `out` itself when it is a contiguous GPU tensor
+    with `like`'s dtype and shape (`shape` instead, when given) -- and, with alias=False, not at `like`'s address --
+    else a new device tensor.  Hand the result back with deliver(buf, out)."""
+    if (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == like.dtype
+            and out.shape == (like.shape if shape is None else shape) and (alias or out.data_ptr() != like.data_ptr())):
         return out
-    return t
+    return torch.empty(like.shape if shape is None else shape, dtype=like.dtype, device=like.device)
+
+
+def deliver(t, out=None, like=None):
+    """Write device result t into the caller's `out` (a numpy array by assignment, a tensor by copy unless it is t
+    itself) and return `out`; without `out`, return host_like(t, like)."""
+    if out is None:
+        return host_like(t, like)
+    if isinstance(out, np.ndarray):
+        out[...] = t.cpu().numpy()
+    elif out is not t:
+        out.copy_(t)
+    return out

@@ -29,13 +29,12 @@ from ..operators.psf import psf_convolve_cube
 def clark(ID, PSF, PSFHAT, wsums, threshold=0, gamma=0.05, pf=0.05, maxit=50, subpf=0.5,
           submaxit=1000, report_freq=1, verbosity=1, psfopts=None, sigmathreshold=2, nthreads=1):
     lib = _lib.load()
-    as_numpy = _dev.is_numpy(ID)
-    IDd = _dev.to_dev(ID).contiguous()
+    IDd = _dev.to_dev(ID)
     dt = IDd.dtype
     code = _dev.code(dt)
-    psf = _dev.to_dev(PSF, dt).contiguous()
+    psf = _dev.to_dev(PSF, dt)
     psfhat = _dev.to_dev(PSFHAT)
-    w = _dev.to_dev(wsums, dt).contiguous()
+    w = _dev.to_dev(wsums, dt)
     nband, nx, ny = IDd.shape
     _, nx_psf, ny_psf = psf.shape
     if not np.allclose(float(w.sum().item()), 1.0):
@@ -82,4 +81,4 @@ def clark(ID, PSF, PSFHAT, wsums, threshold=0, gamma=0.05, pf=0.05, maxit=50, su
         msg = ("Max iters reached. " if k >= maxit else "Stalled. " if stall_count >= 5
                else f"Success, converged after {k} iterations. ")
         print(f"{msg}Max resid = {IRmax:.3e}, rms = {rms:.3e}", file=sys.stderr)
-    return (model.cpu().numpy() if as_numpy else model), status
+    return _dev.host_like(model, ID), status

@@ -14,10 +14,9 @@ from .. import _lib, _dev
 
 def hogbom(ID, PSF, threshold=0, gamma=0.1, pf=0.1, maxit=10000, report_freq=1000, verbosity=1):
     lib = _lib.load()
-    as_numpy = _dev.is_numpy(ID)
-    IR = _dev.to_dev(ID).contiguous().clone()
+    IR = _dev.to_dev(ID).clone()
     dt = IR.dtype
-    psf = _dev.to_dev(PSF, dt).contiguous()
+    psf = _dev.to_dev(PSF, dt)
     nband, nx, ny = IR.shape
     _, nx_psf, ny_psf = psf.shape
     wsums = psf.amax(dim=(1, 2)).contiguous()                       # hogbom.py:27
@@ -35,4 +34,4 @@ def hogbom(ID, PSF, threshold=0, gamma=0.1, pf=0.1, maxit=10000, report_freq=100
         rms = float(IR.sum(dim=0)[quiet].std(unbiased=False).item()) if bool(quiet.any().item()) else float('nan')
         msg = "Max iters reached. " if status else f"Success, converged after {k.value} iterations. "
         print(f"{msg}Max resid = {irmax.value:.3e}, rms = {rms:.3e}", file=sys.stderr)
-    return (model.cpu().numpy() if as_numpy else model), status
+    return _dev.host_like(model, ID), status

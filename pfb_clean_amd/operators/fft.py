@@ -61,4 +61,4 @@ def psfhat_from_psf(psf):
         out = torch.fft.rfft2(torch.fft.ifftshift(p, dim=(-2, -1)), dim=(-2, -1))
     if squeeze:
         out = out[0]
-    return out.cpu().numpy() if _dev.is_numpy(psf) else out
+    return _dev.host_like(out, psf)

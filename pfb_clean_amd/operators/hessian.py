@@ -56,7 +56,7 @@ class HessianPsf:
             raise ValueError("2-D input to a multi-band HessianPsf")
         res = self.plan.apply(xd, out=out, beam=self.beam, wsum=self.wsum,
                               sigmainv=self.sigmainv, band0=self.band0)
-        return res.cpu().numpy() if _dev.is_numpy(x) else res
+        return _dev.host_like(res, x)
 
 
 class hessian_psf_slice:
@@ -75,20 +75,20 @@ class hessian_psf_slice:
         self.cell, self.do_wgridding, self.epsilon, self.double_accum = cell, do_wgridding, epsilon, double_accum
         self.lastsize = ds.PSF.shape[-1]
         self.bandid = ds.bandid
-        self.dirty = _dev.to_dev(ds.DIRTY.values).contiguous()
+        self.dirty = _dev.to_dev(ds.DIRTY.values)
         rdt = self.dirty.dtype
-        self.psfhat = _dev.to_dev(ds.PSFHAT.values).contiguous()
-        self.psf = _dev.to_dev(ds.PSF.values, rdt).contiguous()
-        self.beam = _dev.to_dev(ds.BEAM.values, rdt).contiguous()
+        self.psfhat = _dev.to_dev(ds.PSFHAT.values)
+        self.psf = _dev.to_dev(ds.PSF.values, rdt)
+        self.beam = _dev.to_dev(ds.BEAM.values, rdt)
         self.wsumb = ds.WSUM.values[0]
-        self.model = (_dev.to_dev(ds.MODEL.values, rdt).contiguous() if 'MODEL' in ds
+        self.model = (_dev.to_dev(ds.MODEL.values, rdt) if 'MODEL' in ds
                       else torch.zeros_like(self.dirty))
         if 'DUAL' in ds:
-            self.dual = _dev.to_dev(ds.DUAL.values, rdt).contiguous()
+            self.dual = _dev.to_dev(ds.DUAL.values, rdt)
             assert tuple(self.dual.shape) == (nbasis, nmax)
         else:
             self.dual = torch.zeros((nbasis, nmax), dtype=rdt, device=self.dirty.device)
-        self.residual = (_dev.to_dev(ds.RESIDUAL.values, rdt).contiguous() if 'RESIDUAL' in ds
+        self.residual = (_dev.to_dev(ds.RESIDUAL.values, rdt) if 'RESIDUAL' in ds
                          else self.dirty.clone())
         nx, ny = self.dirty.shape
         self._op = HessianPsf(self.psfhat, nx, ny, self.lastsize, beam=self.beam, sigmainv=sigmainv)
@@ -119,11 +119,8 @@ def _hess(psfhat, beam, lastsize, x, xout, sigmainv, wsum):
             raise ValueError('Beam has incorrect shape')
     res = plan.apply(xd, beam=bd, wsum=wsum, sigmainv=sigmainv)
     if xout is not None:
-        if _dev.is_numpy(xout):
-            xout[...] = res.cpu().numpy()
-        elif isinstance(xout, torch.Tensor):
-            xout.copy_(res)
-    return res.cpu().numpy() if _dev.is_numpy(x) else res
+        _dev.deliver(res, xout)
+    return _dev.host_like(res, x)
 
 
 def _hessian_psf_slice(xpad, xhat, xout, psfhat, beam, lastsize, x,

@@ -17,12 +17,12 @@ with functools.partial (workers/spotless.py:175-183).
 """
 import ctypes as C
 import threading
-from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from .. import _lib, _dev
+from .._plan import NativePlan, PlanCache
 
 
 def _pow2ceil(n):
@@ -61,57 +61,66 @@ def _embed_grid(nx, ny, nx_psf, ny_psf, rdtype):
     return nx2, ny2
 
 
-class PsfConvPlan:
+class PsfConvPlan(NativePlan):
     """Owns the device plan (twiddles, re-laid-out psfhat, spectrum workspace) for one
     psfhat cube.  psfhat: (nband, nx_psf, nyo2) or (nx_psf, nyo2) complex.
 
-    A plan is single-owner in the C-ABI (one stream and one host thread at a time: its spectrum
-    workspace, fused-dot partials and profiling slots are per plan).  plan_for() hands the SAME plan to
-    every host thread that presents the same psfhat (the reference's dask threads do, pcg.py:346-356), so
-    the Python layer serialises: `lock` is held for the enqueue of an apply and for a whole fused solve,
-    and a caller on a different stream than the previous user first waits for that stream's work."""
+    plan_for() hands the SAME plan to every host thread that presents the same psfhat (the reference's dask threads
+    do, pcg.py:346-356), so `lock` is held for the enqueue of an apply and for a whole fused solve, and a caller on a
+    different stream than the previous user first waits for that stream's work (NativePlan._enter_stream).
 
-    def __init__(self, psfhat, nx, ny, lastsize):
-        lib = _lib.load()
-        ph = _dev.to_dev(psfhat)
-        if ph.dtype not in _dev.REAL_OF:
-            raise TypeError(f"psfhat must be complex64/complex128, got {ph.dtype}")
-        if ph.ndim == 2:
-            ph = ph[None]
-        if ph.ndim != 3:
-            raise ValueError("psfhat must be (nx_psf, nyo2) or (nband, nx_psf, nyo2)")
-        self.nband, self.nx_psf, self.nyo2 = ph.shape
+    `psf` (keyword, what from_psf passes instead of psfhat): the real PSF cube as a contiguous device tensor of a
+    fast-path size; the library transforms it itself, into `psfhat_out` as well when that is given."""
+    _destroy = 'pfb_psfconv_plan_destroy'
+
+    def __init__(self, psfhat, nx, ny, lastsize, *, psf=None, psfhat_out=None):
+        super().__init__()
         self.nx, self.ny, self.lastsize = int(nx), int(ny), int(lastsize)
-        if self.nyo2 != self.lastsize // 2 + 1:
-            raise ValueError(f"psfhat last axis {self.nyo2} != lastsize//2+1 "
-                             f"({self.lastsize // 2 + 1})")
-        self.rdtype = _dev.REAL_OF[ph.dtype]
-        self.code = _dev.code(self.rdtype)
-        self.device = ph.device
-        self._lib = lib
-        self._h = C.c_void_p()
-        self.lock = threading.RLock()
-        # Arbitrary sizes on the power-of-two kernels: the same image-space PSF is re-gridded
-        # (pfb_psfhat_regrid) onto nx_psf2 = 2 nx2, ny_psf2 = 2 ny2 with nx2, ny2 the next powers
-        # of two, images are zero-padded into (nx2, ny2) buffers and results cropped.  Identical
-        # results to rounding, 3-6x faster than the line-per-workgroup coverage kernels
-        # (measured: 3600^2 x 2 bands 3.2 ms generic vs 0.55 ms for two 4096^2 bands).
         self.embed = None
-        grid2 = _embed_grid(self.nx, self.ny, self.nx_psf, self.lastsize, self.rdtype)
+        if psf is None:
+            ph = _dev.to_dev(psfhat)
+            if ph.dtype not in _dev.REAL_OF:
+                raise TypeError(f"psfhat must be complex64/complex128, got {ph.dtype}")
+            if ph.ndim == 2:
+                ph = ph[None]
+            if ph.ndim != 3:
+                raise ValueError("psfhat must be (nx_psf, nyo2) or (nband, nx_psf, nyo2)")
+            self.nband, self.nx_psf, self.nyo2 = ph.shape
+            if self.nyo2 != self.lastsize // 2 + 1:
+                raise ValueError(f"psfhat last axis {self.nyo2} != lastsize//2+1 "
+                                 f"({self.lastsize // 2 + 1})")
+            self.rdtype, self.device = _dev.REAL_OF[ph.dtype], ph.device
+        else:
+            self.nband, self.nx_psf = (int(v) for v in psf.shape[:2])
+            self.nyo2 = self.lastsize // 2 + 1
+            self.rdtype, self.device = psf.dtype, psf.device
+        self.code = _dev.code(self.rdtype)
         cnx, cny, cpx, cpy = self.nx, self.ny, self.nx_psf, self.lastsize
-        if grid2 is not None:
-            ph2 = self._regrid(ph.contiguous(), grid2)
-            if ph2 is not None:
-                self.embed = grid2
-                ph = ph2
-                cnx, cny, cpx, cpy = grid2[0], grid2[1], 2 * grid2[0], 2 * grid2[1]
-        h = C.c_void_p()
-        _lib.check(lib.pfb_psfconv_plan_create(cnx, cny, cpx, cpy, self.nband, self.code, C.byref(h)))
-        self._h = h
-        _lib.check(lib.pfb_psfconv_set_psfhat(h, _dev.ptr(ph.contiguous()), _dev.stream()))
-        torch.cuda.current_stream().synchronize()      # ph may be a temporary
+        if psf is None:
+            # Arbitrary sizes on the power-of-two kernels: the same image-space PSF is re-gridded
+            # (pfb_psfhat_regrid) onto nx_psf2 = 2 nx2, ny_psf2 = 2 ny2 with nx2, ny2 the next powers
+            # of two, images are zero-padded into (nx2, ny2) buffers and results cropped.  Identical
+            # results to rounding, 3-6x faster than the line-per-workgroup coverage kernels
+            # (measured: 3600^2 x 2 bands 3.2 ms generic vs 0.55 ms for two 4096^2 bands).
+            grid2 = _embed_grid(self.nx, self.ny, self.nx_psf, self.lastsize, self.rdtype)
+            if grid2 is not None:
+                ph2 = self._regrid(ph.contiguous(), grid2)
+                if ph2 is not None:
+                    self.embed = grid2
+                    ph = ph2
+                    cnx, cny, cpx, cpy = grid2[0], grid2[1], 2 * grid2[0], 2 * grid2[1]
+        _lib.check(self._lib.pfb_psfconv_plan_create(cnx, cny, cpx, cpy, self.nband, self.code, C.byref(self._h)))
+        try:
+            if psf is None:
+                _lib.check(self._lib.pfb_psfconv_set_psfhat(self._h, _dev.ptr(ph.contiguous()), _dev.stream()))
+            else:
+                _lib.check(self._lib.pfb_psfconv_set_psf(self._h, _dev.ptr(psf), _dev.ptr(psfhat_out), _dev.stream()))
+        except Exception:
+            self.close()
+            raise
+        torch.cuda.current_stream().synchronize()      # psfhat / psf may be a temporary
         fast, vb, wsb = C.c_int(), C.c_int(), C.c_size_t()
-        lib.pfb_psfconv_plan_info(h, C.byref(fast), C.byref(vb), C.byref(wsb))
+        self._lib.pfb_psfconv_plan_info(self._h, C.byref(fast), C.byref(vb), C.byref(wsb))
         self.fast_path, self.vb, self.workspace_bytes = bool(fast.value), vb.value, wsb.value
 
     def _regrid(self, ph, grid2):
@@ -149,56 +158,29 @@ class PsfConvPlan:
         z[:, :self.nx, :self.ny] = t
         return z
 
-    @property
-    def handle(self):
-        return self._h
-
     @classmethod
     def from_psf(cls, psf, nx, ny, want_psfhat=False):
         """Build the plan straight from the real PSF cube (nband, nx_psf, ny_psf) | (nx_psf, ny_psf):
         psfhat = r2c(ifftshift(psf)) is produced by the library's own kernels
         (pfb_psfconv_set_psf; gridder.py:712-714) and never leaves the device.  With
         want_psfhat=True also returns it in the reference's layout."""
-        lib = _lib.load()
         p = _dev.to_dev(psf)
         if p.ndim == 2:
             p = p[None]
         if p.ndim != 3 or p.dtype not in (torch.float32, torch.float64):
             raise ValueError("psf must be a real (nband, nx_psf, ny_psf) or (nx_psf, ny_psf) array")
-        p = p.contiguous()
-        if _embed_grid(int(nx), int(ny), int(p.shape[1]), int(p.shape[2]), p.dtype) is not None:
+        nband, nx_psf, ny_psf = (int(v) for v in p.shape)
+        if _embed_grid(int(nx), int(ny), nx_psf, ny_psf, p.dtype) is not None:
             # not a fast-path size: transform on the PSF's own grid first, then let the constructor
             # re-grid it onto the power-of-two plan (operators/fft.py picks the native producer)
             from .fft import psfhat_from_psf
             ph = psfhat_from_psf(p)
-            plan = cls(ph, nx, ny, int(p.shape[2]))
+            plan = cls(ph, nx, ny, ny_psf)
             return (plan, ph) if want_psfhat else plan
-        self = cls.__new__(cls)
-        self.embed = None
-        self.lock = threading.RLock()
-        self.nband, self.nx_psf, self.lastsize = (int(v) for v in p.shape)
-        self.nyo2 = self.lastsize // 2 + 1
-        self.nx, self.ny = int(nx), int(ny)
-        self.rdtype = p.dtype
-        self.code = _dev.code(self.rdtype)
-        self.device = p.device
-        h = C.c_void_p()
-        _lib.check(lib.pfb_psfconv_plan_create(self.nx, self.ny, self.nx_psf, self.lastsize,
-                                               self.nband, self.code, C.byref(h)))
-        self._h = h
-        self._lib = lib
-        cdt = torch.complex64 if self.rdtype == torch.float32 else torch.complex128
-        ph = torch.empty((self.nband, self.nx_psf, self.nyo2), dtype=cdt, device=p.device) if want_psfhat else None
-        try:
-            _lib.check(lib.pfb_psfconv_set_psf(h, _dev.ptr(p), _dev.ptr(ph), _dev.stream()))
-        except Exception:
-            self.close()
-            raise
-        torch.cuda.current_stream().synchronize()      # p may be a temporary
-        fast, vb, wsb = C.c_int(), C.c_int(), C.c_size_t()
-        lib.pfb_psfconv_plan_info(h, C.byref(fast), C.byref(vb), C.byref(wsb))
-        self.fast_path, self.vb, self.workspace_bytes = bool(fast.value), vb.value, wsb.value
-        return (self, ph) if want_psfhat else self
+        ph = torch.empty((nband, nx_psf, ny_psf // 2 + 1), dtype=_dev.CPLX_OF[p.dtype],
+                         device=p.device) if want_psfhat else None
+        plan = cls(None, nx, ny, ny_psf, psf=p, psfhat_out=ph)
+        return (plan, ph) if want_psfhat else plan
 
     def apply(self, x, out=None, beam=None, wsum=None, sigmainv=0.0, band0=0,
               dot_with=None, dot_out=None):
@@ -254,21 +236,6 @@ class PsfConvPlan:
                 _dev.ptr(ds), _dev.ptr(dot_out), _dev.stream()))
         return out3[0] if squeeze else out3
 
-    def _enter_stream(self):
-        """Call with `lock` held, BEFORE enqueueing on the current stream: the plan's workspace is about to be used
-        there.  If the previous user enqueued on a DIFFERENT stream its work must finish first -- as a DEVICE-side
-        dependency (an event recorded behind the previous user's enqueue, waited for by the current stream), never a
-        host wait: with the reference's dask-thread pattern (several threads, one plan, a stream per thread,
-        pcg.py:346-356) a host synchronize here would stall every thread queued on the lock until the previous thread's
-        whole stream had drained.  Same stream: stream order already serialises the kernels."""
-        cur = torch.cuda.current_stream()
-        last = self.__dict__.get('_last_stream')
-        if last is not None and last != cur:
-            ev = torch.cuda.Event()
-            ev.record(last)               # behind everything the previous user has enqueued so far (it holds no lock now)
-            cur.wait_event(ev)
-        self._last_stream = cur
-
     def set_profiling(self, on):
         """on: False/0 off, True/1 every apply, N > 1 every N-th apply (each timed apply puts
         four event records = ~20 us on the stream)."""
@@ -281,23 +248,9 @@ class PsfConvPlan:
         _lib.check(self._lib.pfb_psfconv_get_profile(self._h, ms, C.byref(n)))
         return tuple(ms), n.value
 
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            torch.cuda.synchronize()
-            self._lib.pfb_psfconv_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ------------------------------------------------------------------- plan cache
-_cache = OrderedDict()
-_cache_lock = threading.Lock()
-_CACHE_MAX = 8
+_cache = PlanCache(8)
 
 
 def _fingerprint(psfhat):
@@ -318,22 +271,12 @@ def plan_for(psfhat, nx, ny, lastsize):
     tensor so that its memory cannot be freed and re-used by a DIFFERENT psfhat at the same
     address while the entry lives (clear_plan_cache() releases plans and references)."""
     key = (_fingerprint(psfhat), int(nx), int(ny), int(lastsize))
-    with _cache_lock:
-        hit = _cache.get(key)
-        if hit is not None:
-            _cache.move_to_end(key)
-            return hit[0]
-    plan = PsfConvPlan(psfhat, nx, ny, lastsize)
-    with _cache_lock:
-        _cache[key] = (plan, psfhat if isinstance(psfhat, torch.Tensor) else None)
-        while len(_cache) > _CACHE_MAX:
-            _cache.popitem(last=False)
-    return plan
+    return _cache.get(key, lambda: (PsfConvPlan(psfhat, nx, ny, lastsize),
+                                    psfhat if isinstance(psfhat, torch.Tensor) else None))[0]
 
 
 def clear_plan_cache():
-    with _cache_lock:
-        _cache.clear()
+    _cache.clear()
 
 
 # ---------------------------------------------------------------- reference API
@@ -344,19 +287,9 @@ def _run(psfhat, lastsize, x, xout, beam=None, wsum=None, sigmainv=0.0):
     if xd.dtype != plan.rdtype:
         raise TypeError(f"x is {xd.dtype} but psfhat is {psfhat.dtype}")
     bd = _dev.to_dev(beam, plan.rdtype) if beam is not None else None
-    direct = isinstance(xout, torch.Tensor) and xout.is_cuda and xout.is_contiguous() \
-        and xout.dtype == plan.rdtype and tuple(xout.shape) == tuple(xd.shape) \
-        and xout.data_ptr() != xd.data_ptr()
-    res = plan.apply(xd, out=xout if direct else None, beam=bd, wsum=wsum, sigmainv=sigmainv)
-    if direct:
-        return xout
-    if xout is None:
-        return res.cpu().numpy() if _dev.is_numpy(x) else res
-    if _dev.is_numpy(xout):
-        xout[...] = res.cpu().numpy()
-    else:
-        xout.copy_(res)
-    return xout
+    buf = _dev.out_buffer(xout, xd, alias=False)          # never overwrite x: stage when xout aliases it
+    plan.apply(xd, out=buf, beam=bd, wsum=wsum, sigmainv=sigmainv)
+    return _dev.deliver(buf, xout, like=x)
 
 
 def psf_convolve_slice(xpad, xhat, xout, psfhat, lastsize, x, nthreads=1):

@@ -15,12 +15,11 @@ per (basis, level) covering all bands (pfb_psi_dot / pfb_psi_hdot, csrc/wavelet.
 The reference's psi buffers are float64 only (psi.py:130-133); here the dtype follows
 the arrays (float64 or float32).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from .. import _lib, _dev
+from .._plan import PsiPlan
 from ..wavelets import filters as _filters
 
 
@@ -46,27 +45,18 @@ class Psi(object):
             ks.append(K)
             for q in range(4):
                 filt[i, q, :2 * K] = fb[q]
-        self._ks = (C.c_int * self.nbasis)(*ks)
+        self._ks = ks
         self._filt = filt
         self._plans = {}
         self._lib = _lib.load()
         # dims do not depend on dtype: build the default plan now (also validates sizes)
-        self._default = torch.float64 if dtype is None else dtype
-        p = self._plan(self._default)
-        ny_, nx_ = C.c_int(), C.c_int()
-        _lib.check(self._lib.pfb_psi_plan_dims(p, C.byref(ny_), C.byref(nx_)))
-        self.Nymax, self.Nxmax = ny_.value, nx_.value
+        p = self._plan(torch.float64 if dtype is None else dtype)
+        self.Nymax, self.Nxmax = p.Nymax, p.Nxmax
 
     def _plan(self, dtype):
         p = self._plans.get(dtype)
         if p is None:
-            _dev.require_device()
-            h = C.c_void_p()
-            _lib.check(self._lib.pfb_psi_plan_create(
-                self.nband, self.nx, self.ny, self.nbasis, self._ks,
-                self._filt.ctypes.data_as(C.POINTER(C.c_double)), self.nlevel, _dev.code(dtype),
-                C.byref(h)))
-            p = self._plans[dtype] = h
+            p = self._plans[dtype] = PsiPlan(self.nband, self.nx, self.ny, self._ks, self._filt, self.nlevel, dtype)
         return p
 
     def _check(self, x, alpha):
@@ -80,45 +70,23 @@ class Psi(object):
     def dot(self, x, alphao):
         """image to coeffs (psi.py:284-295), in place on alphao."""
         self._check(x, alphao)
-        xd = _dev.to_dev(x).contiguous()
-        direct = isinstance(alphao, torch.Tensor) and alphao.is_cuda and alphao.is_contiguous() \
-            and alphao.dtype == xd.dtype
-        ad = alphao if direct else _dev.to_dev(alphao, xd.dtype).contiguous()
-        _lib.check(self._lib.pfb_psi_dot(self._plan(xd.dtype), _dev.ptr(xd), _dev.ptr(ad), _dev.stream()))
-        if not direct:
-            if _dev.is_numpy(alphao):
-                alphao[...] = ad.cpu().numpy()
-            else:
-                alphao.copy_(ad)
-        return alphao
+        xd = _dev.to_dev(x)
+        ad = _dev.to_dev(alphao, xd.dtype)      # alphao itself when it is a contiguous GPU tensor of x's dtype
+        _lib.check(self._lib.pfb_psi_dot(self._plan(xd.dtype).handle, _dev.ptr(xd), _dev.ptr(ad), _dev.stream()))
+        return _dev.deliver(ad, alphao)
 
     def hdot(self, alpha, xo):
         """coeffs to image (psi.py:297-310), in place on xo."""
         self._check(xo, alpha)
-        ad = _dev.to_dev(alpha).contiguous()
-        direct = isinstance(xo, torch.Tensor) and xo.is_cuda and xo.is_contiguous() \
-            and xo.dtype == ad.dtype
-        xd = xo if direct else torch.empty((self.nband, self.nx, self.ny), dtype=ad.dtype, device=ad.device)
-        _lib.check(self._lib.pfb_psi_hdot(self._plan(ad.dtype), _dev.ptr(ad), _dev.ptr(xd), _dev.stream()))
-        if not direct:
-            if _dev.is_numpy(xo):
-                xo[...] = xd.cpu().numpy()
-            else:
-                xo.copy_(xd)
-        return xo
+        ad = _dev.to_dev(alpha)
+        xd = _dev.out_buffer(xo, ad, shape=(self.nband, self.nx, self.ny))
+        _lib.check(self._lib.pfb_psi_hdot(self._plan(ad.dtype).handle, _dev.ptr(ad), _dev.ptr(xd), _dev.stream()))
+        return _dev.deliver(xd, xo)
 
     def close(self):
-        if self._plans:
-            torch.cuda.synchronize()
-            for h in self._plans.values():
-                self._lib.pfb_psi_plan_destroy(h)
-            self._plans = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        for p in self._plans.values():
+            p.close()
+        self._plans = {}
 
 
 class psi_band(object):

@@ -51,8 +51,7 @@ def _detect_div_precond(M, b):
     entries, an operator, something non-linear) fails the elementwise test and keeps the generic path."""
     try:
         bd = _dev.to_dev(b)
-        host = (lambda t: t.cpu().numpy()) if _dev.is_numpy(b) else (lambda t: t)
-        y1 = _dev.to_dev(M(host(bd)), bd.dtype)
+        y1 = _dev.to_dev(M(_dev.host_like(bd, b)), bd.dtype)
         if y1.shape != bd.shape:
             return None
         flat_b, flat_y = bd.reshape(-1), y1.reshape(-1)
@@ -64,7 +63,7 @@ def _detect_div_precond(M, b):
         scale = flat_b.abs().max().item() / abs(c)
         if (flat_y - flat_b / c).abs().max().item() > eps * scale:
             return None
-        y2 = _dev.to_dev(M(host(-2.0 * bd)), bd.dtype).reshape(-1)
+        y2 = _dev.to_dev(M(_dev.host_like(-2.0 * bd, b)), bd.dtype).reshape(-1)
         if (y2 + 2.0 * flat_b / c).abs().max().item() > 2 * eps * scale:
             return None
         return DivPrecond(c)
@@ -214,7 +213,6 @@ def pcg(A, b, x0=None, M=None, tol=1e-5, maxit=500, minit=100, verbosity=1,
     if H is not None and M is not None and not isinstance(M, DivPrecond):
         M = _detect_div_precond(M, b) or M
     fusable_M = M is None or isinstance(M, DivPrecond)
-    as_numpy = _dev.is_numpy(b)
     if H is not None and fusable_M:
         bd = _dev.to_dev(b)
         x0d = None if x0 is None else _dev.to_dev(x0, bd.dtype)
@@ -225,32 +223,24 @@ def pcg(A, b, x0=None, M=None, tol=1e-5, maxit=500, minit=100, verbosity=1,
         if status == 'zero-residual':
             _log("Initial residual is zero", verbosity)
             # the reference returns x0 itself, and ONLY x0, even with return_resid
-            return x0 if x0 is not None else (x.cpu().numpy() if as_numpy else x)
+            return x0 if x0 is not None else _dev.host_like(x, b)
         _report(status, res.iters, res.eps, verbosity)
-        if as_numpy:
-            x = x.cpu().numpy()
-            r = None if r is None else r.cpu().numpy()
-        return (x, r) if return_resid else x
+        return (_dev.host_like(x, b), _dev.host_like(r, b)) if return_resid else _dev.host_like(x, b)
     return _pcg_generic(A, b, x0, M, tol, maxit, minit, verbosity, report_freq, backtrack,
                         return_resid)
 
 
 def _pcg_generic(A, b, x0, M, tol, maxit, minit, verbosity, report_freq, backtrack,
                  return_resid):
-    lib = _lib.load()
     as_numpy = _dev.is_numpy(b)
-    bd = _dev.to_dev(b).contiguous()
+    bd = _dev.to_dev(b)
     dt = bd.dtype
-    code = _dev.code(dt)
-    n = bd.numel()
-    st = _dev.stream
-    ws, out = _dev.scratch()
 
     def host(t):
-        return t.cpu().numpy() if as_numpy else t
+        return _dev.host_like(t, b)
 
     def dev(a):
-        return _dev.to_dev(a, dt).contiguous()
+        return _dev.to_dev(a, dt)
 
     def callA(v):
         return dev(A(host(v))).clone() if not as_numpy else dev(A(host(v)))
@@ -258,23 +248,13 @@ def _pcg_generic(A, b, x0, M, tol, maxit, minit, verbosity, report_freq, backtra
     def callM(v):
         return v if M is None else dev(M(host(v)))
 
-    def dot(u, v):
-        _lib.check(lib.pfb_dot(code, _dev.ptr(u), _dev.ptr(v), n, _dev.ptr(out), _dev.ptr(ws), st()))
-        return out[0].item()
-
-    def anynz(u):
-        _lib.check(lib.pfb_any_nonzero(code, _dev.ptr(u), n, _dev.ptr(out), _dev.ptr(ws), st()))
-        return out[0].item() != 0.0
-
-    def axpby(a, u, bb, v):       # v = a*u + bb*v
-        _lib.check(lib.pfb_axpby(code, float(a), _dev.ptr(u), float(bb), _dev.ptr(v), n, st()))
-
+    dot, axpby = _dev.dot, _dev.axpby
     x0_in = x0
     x = torch.zeros_like(bd) if x0 is None else dev(x0).clone()
     r = callA(x)
     axpby(-1.0, bd, 1.0, r)                          # r = A(x0) - b
     y = callM(r)
-    if not anynz(y):
+    if not _dev.any_nonzero(y):
         _log("Initial residual is zero", verbosity)
         return x0_in if x0_in is not None else host(x)
     p = y.clone()
@@ -302,13 +282,11 @@ def _pcg_generic(A, b, x0, M, tol, maxit, minit, verbosity, report_freq, backtra
             rnorm_next = dot(r, y)
         beta = rnorm_next / rnorm
         axpby(-1.0, y, beta, p)                      # p = beta*p - y
-        if not anynz(p):
+        if not _dev.any_nonzero(p):
             broke = True
             break
         k += 1
-        _lib.check(lib.pfb_norm_diff_sums(code, _dev.ptr(x), _dev.ptr(xp), n, _dev.ptr(out),
-                                          _dev.ptr(ws), st()))
-        num, den = out[:2].tolist()
+        num, den = _dev.norm_diff_sums(x, xp).tolist()
         eps = math.sqrt(num / (1e-12 + den))
         if not k % report_freq and verbosity > 1:
             _log(f"At iteration {k} epsx = {eps:.3e}", verbosity, 2)
@@ -325,40 +303,25 @@ def cg_dct(A, b, x, tol=1e-5, maxit=500, verbosity=1, report_freq=10):
     `eps > tol and k < maxit`.  Leaves live on the GPU for the whole solve; `A` is called with a
     dict of GPU tensors when the caller's leaves are tensors, of numpy arrays otherwise, and like
     the reference the caller's `x` leaves are updated in place.  Returns (x, r)."""
-    lib = _lib.load()
-    as_numpy = _dev.is_numpy(next(iter(next(iter(b.values())).values())))
-    ws, out = _dev.scratch()
-    st = _dev.stream
+    leaf = next(iter(next(iter(b.values())).values()))
 
     def todev(d):
-        return {f: {i: _dev.to_dev(d[f][i]).contiguous() for i in d[f]} for f in d}
+        return {f: {i: _dev.to_dev(d[f][i]) for i in d[f]} for f in d}
 
     def callA(d):
-        if not as_numpy:
+        if not _dev.is_numpy(leaf):
             return todev(A(d))
-        return todev(A({f: {i: d[f][i].cpu().numpy() for i in d[f]} for f in d}))
+        return todev(A({f: {i: _dev.host_like(d[f][i], leaf) for i in d[f]} for f in d}))
 
     def vdot(u, v):
-        acc = 0.0
-        for f in u:
-            for i in u[f]:
-                t = u[f][i]
-                _lib.check(lib.pfb_dot(_dev.code(t.dtype), _dev.ptr(t), _dev.ptr(v[f][i]), t.numel(),
-                                       _dev.ptr(out), _dev.ptr(ws), st()))
-                acc += out[0].item()
-        return acc
+        return sum(_dev.dot(u[f][i], v[f][i]) for f in u for i in u[f])
 
     def axpby(a, u, bb, v):       # v = a*u + bb*v, leaf by leaf
         for f in v:
             for i in v[f]:
-                t = v[f][i]
-                _lib.check(lib.pfb_axpby(_dev.code(t.dtype), float(a), _dev.ptr(u[f][i]), float(bb),
-                                         _dev.ptr(t), t.numel(), st()))
+                _dev.axpby(a, u[f][i], bb, v[f][i])
 
-    xd = todev(x)
-    if not as_numpy:                 # tensors already on the device are updated in place
-        xd = {f: {i: (x[f][i] if (x[f][i].is_cuda and x[f][i].is_contiguous()) else xd[f][i]) for i in x[f]}
-              for f in x}
+    xd = todev(x)                    # a caller's contiguous device tensors are the leaves themselves: updated in place
     bd = todev(b)
     r = callA(xd)
     r = {f: {i: r[f][i].clone() for i in r[f]} for f in r}
@@ -384,13 +347,8 @@ def cg_dct(A, b, x, tol=1e-5, maxit=500, verbosity=1, report_freq=10):
              else f"Success, converged after {k} iterations", verbosity)
     for f in x:                                               # in-place semantics of the reference
         for i in x[f]:
-            if as_numpy:
-                x[f][i][...] = xd[f][i].cpu().numpy()
-            elif x[f][i] is not xd[f][i]:
-                x[f][i].copy_(xd[f][i])
-    if as_numpy:
-        r = {f: {i: r[f][i].cpu().numpy() for i in r[f]} for f in r}
-    return x, r
+            _dev.deliver(xd[f][i], x[f][i])
+    return x, {f: {i: _dev.host_like(r[f][i], leaf) for i in r[f]} for f in r}
 
 
 def pcg_dist(A, maxit, minit, tol, sigmainv):
@@ -401,29 +359,13 @@ def pcg_dist(A, maxit, minit, tol, sigmainv):
     stay on the GPU; the matvec is the fused convolution, the recurrences are pfb_axpby /
     pfb_dot / pfb_any_nonzero; the scalars the while-conditions need come back per iteration
     (this path keeps the reference's exact backtracking loop)."""
-    lib = _lib.load()
     src = A.residual if hasattr(A, 'residual') else A.dirty
-    as_numpy = _dev.is_numpy(src)
-    b = _dev.to_dev(src).contiguous() / float(A.wsum)
+    b = _dev.to_dev(src) / float(A.wsum)
     dt = b.dtype
-    code = _dev.code(dt)
-    n = b.numel()
-    st = _dev.stream
-    ws, out = _dev.scratch()
-
-    def dot(u, v):
-        _lib.check(lib.pfb_dot(code, _dev.ptr(u), _dev.ptr(v), n, _dev.ptr(out), _dev.ptr(ws), st()))
-        return out[0].item()
-
-    def anynz(u):
-        _lib.check(lib.pfb_any_nonzero(code, _dev.ptr(u), n, _dev.ptr(out), _dev.ptr(ws), st()))
-        return out[0].item() != 0.0
-
-    def axpby(a, u, bb, v):       # v = a*u + bb*v
-        _lib.check(lib.pfb_axpby(code, float(a), _dev.ptr(u), float(bb), _dev.ptr(v), n, st()))
+    dot, axpby = _dev.dot, _dev.axpby
 
     def callA(v):
-        return _dev.to_dev(A(v), dt).contiguous().clone()
+        return _dev.to_dev(A(v), dt).clone()
 
     x = torch.zeros_like(b)
     r = callA(x)
@@ -451,7 +393,7 @@ def pcg_dist(A, maxit, minit, tol, sigmainv):
             alpha *= 0.75
         beta = rnorm_next / rnorm
         axpby(-1.0, y, beta, p)                      # p = beta*p - y
-        if not anynz(p):
+        if not _dev.any_nonzero(p):
             break
         rnorm = rnorm_next
         k += 1
@@ -459,39 +401,29 @@ def pcg_dist(A, maxit, minit, tol, sigmainv):
         if abs(eps - epsp) < 1e-3 * tol:
             stall += 1
     print(f'Band={getattr(A, "bandid", "?")}, iters{k}, eps={eps}', file=sys.stderr)
-    return x.cpu().numpy() if as_numpy else x
+    return _dev.host_like(x, src)
 
 
 def cg(A, b, x0=None, tol=1e-5, maxit=500, verbosity=1, report_freq=10):
     """pfb/opt/pcg.py:12-50 -- the plain CG variant (no preconditioner, no backtracking,
     stopping rule `eps = <r,r> > tol`, unused by the live workers).  Vector work and
     reductions in the HIP kernels; A is called with the array kind of `b`."""
-    lib = _lib.load()
-    as_numpy = _dev.is_numpy(b)
-    bd = _dev.to_dev(b).contiguous()
-    dt, n = bd.dtype, bd.numel()
-    code = _dev.code(dt)
-    ws, out = _dev.scratch()
+    bd = _dev.to_dev(b)
+    dt = bd.dtype
+    dot, axpby = _dev.dot, _dev.axpby
 
     def host(t):
-        return t.cpu().numpy() if as_numpy else t
+        return _dev.host_like(t, b)
 
-    def dot(u, v):
-        _lib.check(lib.pfb_dot(code, _dev.ptr(u), _dev.ptr(v), n, _dev.ptr(out), _dev.ptr(ws), _dev.stream()))
-        return out[0].item()
-
-    def axpby(a, u, bb, v):
-        _lib.check(lib.pfb_axpby(code, float(a), _dev.ptr(u), float(bb), _dev.ptr(v), n, _dev.stream()))
-
-    x = torch.zeros_like(bd) if x0 is None else _dev.to_dev(x0, dt).contiguous().clone()
-    r = _dev.to_dev(A(host(x)), dt).contiguous().clone()
+    x = torch.zeros_like(bd) if x0 is None else _dev.to_dev(x0, dt).clone()
+    r = _dev.to_dev(A(host(x)), dt).clone()
     axpby(-1.0, bd, 1.0, r)                          # r = A(x) - b
     p = r.clone()
     axpby(0.0, r, -1.0, p)                           # p = -r
     rnorm = dot(r, r)
     eps, k = rnorm, 0
     while eps > tol and k < maxit:
-        Ap = _dev.to_dev(A(host(p)), dt).contiguous()
+        Ap = _dev.to_dev(A(host(p)), dt)
         alpha = rnorm / dot(p, Ap)
         axpby(alpha, p, 1.0, x)
         axpby(alpha, Ap, 1.0, r)
@@ -512,7 +444,6 @@ def pcg_psf(psfhat, b, x0, beam, lastsize, nthreads, sigmainv, cgopts, compute=T
     sigmainv > 0.  The reference's dask blockwise-over-bands becomes a loop of fused
     device solves on one plan (bands are independent: shard them over GPUs with
     pfb_clean_amd.dist.shard_bands for multi-GPU)."""
-    as_numpy = _dev.is_numpy(b)
     bd = _dev.to_dev(b)
     nband, nx, ny = bd.shape
     if psfhat.shape[0] != nband:
@@ -545,4 +476,4 @@ def pcg_psf(psfhat, b, x0, beam, lastsize, nthreads, sigmainv, cgopts, compute=T
         else:
             _report(status, res.iters, res.eps, verbosity)
             model[k] = x[0]
-    return model.cpu().numpy() if as_numpy else model
+    return _dev.host_like(model, b)

@@ -40,29 +40,15 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
     if b0 is None:
         b0 = np.random.randn(*imsize)
         if isinstance(dtype, torch.dtype):
-            as_numpy = False
-            bd = _dev.to_dev(b0, dtype).contiguous()
-        else:
-            as_numpy = True
-            bd = _dev.to_dev(b0 if dtype is None else b0.astype(dtype)).contiguous()
-    else:
-        as_numpy = _dev.is_numpy(b0)
-        bd = _dev.to_dev(b0).contiguous().clone()
-    code = _dev.code(bd.dtype)
-    n = bd.numel()
-    ws, out = _dev.scratch()
-
-    def dot_into(u, v, slot):           # out[slot] = <u, v>, no host synchronisation
-        _lib.check(lib.pfb_dot(code, _dev.ptr(u), _dev.ptr(v), n, _dev.ptr(out) + 8 * slot, _dev.ptr(ws),
-                               _dev.stream()))
-
-    def dot(u, v):
-        dot_into(u, v, 0)
-        return out[0].item()
+            b0 = _dev.to_dev(b0, dtype)         # device tensors throughout
+        elif dtype is not None:
+            b0 = b0.astype(dtype)
+    bd = _dev.to_dev(b0).clone()
+    out = _dev.scratch()[1]
 
     # the fused path: A as the library's own operator on device tensors
     H = None
-    if not as_numpy:
+    if not _dev.is_numpy(b0):
         from .pcg import _as_hessian
         H = _as_hessian(A, bd)
         if H is not None and (H.plan.rdtype != bd.dtype or H.plan.embed is not None or
@@ -71,10 +57,7 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
             H = None
     bout = torch.empty_like(bd) if H is not None else None
 
-    def scale(v, s):
-        _lib.check(lib.pfb_axpby(code, 0.0, _dev.ptr(v), float(s), _dev.ptr(v), n, _dev.stream()))
-
-    scale(bd, 1.0 / math.sqrt(allsum([dot(bd, bd)])[0]))
+    _dev.axpby(0.0, bd, 1.0 / math.sqrt(allsum([_dev.dot(bd, bd)])[0]), bd)
     bp = bd.clone()
     b = bd
     beta, eps, k = 1.0, 1.0, 0
@@ -88,20 +71,19 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
                     H.wsum if H.wsum is not None else 0.0, H.sigmainv, _dev.ptr(bout), _dev.ptr(b3), None,
                     _dev.ptr(out), _dev.stream()))                 # out[0] = <bp, b>, out[2] = <b, b>
             b = bout
-            dot_into(bp, bp, 1)
+            _dev.dot_into(bp, bp, out, 1)
             pb, pp, bb = allsum(out[:3].tolist())
         else:
-            res = A(bp.cpu().numpy()) if as_numpy else A(bp)
-            b = _dev.to_dev(res, bp.dtype).contiguous()
-            dot_into(bp, b, 0)
-            dot_into(bp, bp, 1)
-            dot_into(b, b, 2)
+            b = _dev.to_dev(A(_dev.host_like(bp, b0)), bp.dtype)
+            _dev.dot_into(bp, b, out, 0)
+            _dev.dot_into(bp, bp, out, 1)
+            _dev.dot_into(b, b, out, 2)
             pb, pp, bb = allsum(out[:3].tolist())                  # ONE host look per iteration
         bnorm = math.sqrt(bb)
         betap = beta
         beta = pb / pp
         bp.copy_(b)
-        scale(bp, 1.0 / bnorm)                   # b /= bnorm ; bp[...] = b
+        _dev.axpby(0.0, bp, 1.0 / bnorm, bp)     # b /= bnorm ; bp[...] = b
         eps = abs(beta - betap) / betap
         k += 1
         if not k % report_freq and verbosity > 1:
@@ -111,6 +93,4 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
             print(f"Maximum iterations reached. eps = {eps:.3e}, beta = {beta:.3e}", file=sys.stderr)
         else:
             print(f"Success, converged after {k} iterations. beta = {beta:.3e}", file=sys.stderr)
-    if as_numpy:
-        return beta, bp.cpu().numpy()
-    return beta, bp
+    return beta, _dev.host_like(bp, b0)

@@ -33,6 +33,7 @@ import sys
 import torch
 
 from .. import _lib, _dev
+from ..operators.psi import Psi
 from ..prox.prox_21m import dual_update_numba
 
 
@@ -44,16 +45,14 @@ class PsfGradient:
 
     def __init__(self, plan, data):
         self.plan = plan
-        self.data = _dev.to_dev(data, plan.rdtype).contiguous()
+        self.data = _dev.to_dev(data, plan.rdtype)
         self._out = torch.empty_like(self.data)
 
     def conv(self, x):
         return self.plan.apply(x, out=self._out)
 
     def __call__(self, x):
-        xd = _dev.to_dev(x, self.plan.rdtype)
-        res = self.conv(xd) - self.data
-        return res.cpu().numpy() if _dev.is_numpy(x) else res
+        return _dev.host_like(self.conv(_dev.to_dev(x, self.plan.rdtype)) - self.data, x)
 
 
 def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, grad,
@@ -64,8 +63,8 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
         import torch.distributed as dist
         pg = None if group is True else group
     as_numpy = _dev.is_numpy(x)
-    xd = _dev.to_dev(x).contiguous()
-    vd = _dev.to_dev(v, xd.dtype).contiguous()
+    xd = _dev.to_dev(x)
+    vd = _dev.to_dev(v, xd.dtype)
     dt = xd.dtype
     code = _dev.code(dt)
     nband = xd.shape[0]
@@ -76,8 +75,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
     # only taken when `psiH` is this package's Psi.hdot, which is exactly linear and overwrites its output.  Any other
     # callable -- a masked, clipped or otherwise affine synthesis is legal in this signature -- gets the reference's
     # statement order verbatim: vp = 2 v - vp; psiH(vp, xout) (primal_dual.py:137-138).
-    linear_syn = getattr(psiH, '__self__', None).__class__.__name__ == 'Psi' and getattr(psiH, '__name__', '') == 'hdot' \
-        and getattr(psiH, '__module__', '').startswith('pfb_clean_amd')
+    linear_syn = isinstance(getattr(psiH, '__self__', None), Psi) and psiH.__name__ == 'hdot'
     # s_new = psi^H(v) of this iteration, s_old = psi^H(vp) = psi^H(v) of the previous one (linear synthesis)
     s_new = torch.zeros_like(xd)
     s_old = torch.zeros_like(xd)
@@ -85,7 +83,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
         psiH(vp, s_old)
     fused_grad = linear_syn and isinstance(grad, PsfGradient) and not as_numpy and grad.data.shape == xd.shape \
         and grad.data.dtype == dt
-    w = _dev.to_dev(l1weight, dt).contiguous()
+    w = _dev.to_dev(l1weight, dt)
     ws, out = _dev.scratch()
 
     if sigma is None:
@@ -93,7 +91,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
     tau = 0.9 / (L / (2.0 * gamma) + sigma * nu ** 2)
 
     def host(t):
-        return t.cpu().numpy() if as_numpy else t
+        return _dev.host_like(t, x)
 
     # Buffer rotation instead of the reference's end-of-iteration copies `xp = x.copy()`,
     # `vp = v.copy()` (primal_dual.py:176-177): the freshly written x / v simply become the next
@@ -101,7 +99,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
     # support (ours does) and (b) the margins of the packed layout, which psi never writes, are zero
     # in the caller's v (then they stay zero in both buffers); otherwise the copy is kept.
     rotate_v = False
-    if getattr(psi, '__self__', None).__class__.__name__ == 'Psi' and getattr(psi, '__name__', '') == 'dot':
+    if isinstance(getattr(psi, '__self__', None), Psi) and psi.__name__ == 'dot':
         mark = torch.full_like(vd, float('nan'))
         psi(xp, mark)
         rotate_v = not bool(torch.any(vd[torch.isnan(mark)] != 0).item())
@@ -140,7 +138,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
             if fused_grad:
                 gd, gsub = grad.conv(xp), grad.data                      # :139, `- data` inside the update
             else:
-                gd, gsub = _dev.to_dev(grad(host(xp)), dt).contiguous(), None
+                gd, gsub = _dev.to_dev(grad(host(xp)), dt), None
             _lib.check(lib.pfb_pd_primal_update2(code, _dev.ptr(xp), _dev.ptr(s_new), _dev.ptr(s_old), _dev.ptr(gd),
                                                  _dev.ptr(gsub), float(tau), pos_arg, nband, npix,
                                                  _dev.ptr(xn), _dev.ptr(out), _dev.ptr(ws),
@@ -148,14 +146,12 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
         else:
             # the reference's own statements: vp = 2 v - vp (vp is dead afterwards: re-set at the top of the next
             # iteration), psiH(vp, xout) with whatever the caller's synthesis does to its arguments, xout += grad(xp)
-            _lib.check(lib.pfb_axpby(code, 2.0, _dev.ptr(vn), -1.0, _dev.ptr(vp), vp.numel(), _dev.stream()))   # :137
-            if as_numpy:
-                sh = s_new.cpu().numpy()
-                psiH(host(vp), sh)
+            _dev.axpby(2.0, vn, -1.0, vp)                                # :137
+            sh = host(s_new)
+            psiH(host(vp), sh)                                           # :138
+            if sh is not s_new:
                 s_new.copy_(torch.from_numpy(sh))
-            else:
-                psiH(vp, s_new)                                          # :138
-            gd = _dev.to_dev(grad(host(xp)), dt).contiguous()            # :139
+            gd = _dev.to_dev(grad(host(xp)), dt)                         # :139
             _lib.check(lib.pfb_pd_primal_update(code, _dev.ptr(xp), _dev.ptr(s_new), _dev.ptr(gd), float(tau), pos_arg,
                                                 nband, npix, _dev.ptr(xn), _dev.ptr(out), _dev.ptr(ws),
                                                 _dev.stream()))          # :140-146
@@ -164,8 +160,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
                 bad = (xn <= 0).any(dim=0).to(torch.uint8)
                 dist.all_reduce(bad, op=dist.ReduceOp.MAX, group=pg)
                 xn.mul_((1 - bad).to(dt)[None])
-                _lib.check(lib.pfb_norm_diff_sums(code, _dev.ptr(xn), _dev.ptr(xp), xn.numel(),
-                                                  _dev.ptr(out), _dev.ptr(ws), _dev.stream()))
+                _dev.norm_diff_sums(xn, xp)                              # into out[:2]
                 out[2] = (xn != 0).any().to(out.dtype)
             dist.all_reduce(out[:3], op=dist.ReduceOp.SUM, group=pg)
         if lookahead:
@@ -186,7 +181,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
             eps = 1.0
         if eps < tol:
             if reweighter is not None and numreweight < maxreweight:
-                w = _dev.to_dev(reweighter(host(xn)), dt).contiguous()
+                w = _dev.to_dev(reweighter(host(xn)), dt)
                 numreweight += 1
             else:
                 if numreweight >= maxreweight and verbosity:
@@ -204,15 +199,7 @@ def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, g
         else:
             print(f"Success, converged after {k} iterations", file=sys.stderr)
 
-    if as_numpy:
-        x[...] = xn.cpu().numpy()
-        v[...] = vn.cpu().numpy()
-        return x, v
-    if xn is not x:
-        x.copy_(xn)
-    if vn is not v:
-        v.copy_(vn)
-    return x, v
+    return _dev.deliver(xn, x), _dev.deliver(vn, v)
 
 
 def primal_dual(x, v, lam, psi, psiH, L, prox, grad, nu=1.0, sigma=None, mask=None, tol=1e-5, maxit=1000,
@@ -226,11 +213,10 @@ def primal_dual(x, v, lam, psi, psiH, L, prox, grad, nu=1.0, sigma=None, mask=No
     with positivity and the two norms in pfb_pd_primal_update; the callables see GPU tensors when x is a tensor, numpy
     arrays when x is numpy (drop-in: every call then crosses PCIe).  Returns NEW x, v like the reference."""
     lib = _lib.load()
-    as_numpy = _dev.is_numpy(x)
-    xd = _dev.to_dev(x).contiguous()
+    xd = _dev.to_dev(x)
     dt = xd.dtype
     code = _dev.code(dt)
-    vd = _dev.to_dev(v, dt).contiguous()
+    vd = _dev.to_dev(v, dt)
     nband, npix = xd.shape[0], xd[0].numel()
     ws, out = _dev.scratch()
     if sigma is None:
@@ -238,14 +224,13 @@ def primal_dual(x, v, lam, psi, psiH, L, prox, grad, nu=1.0, sigma=None, mask=No
     tau = 0.9 / (L / (2.0 * gamma) + sigma * nu ** 2)
 
     def host(t):
-        return t.cpu().numpy() if as_numpy else t
+        return _dev.host_like(t, x)
 
     def dev(a, private=False):                    # result of a caller's operator -> contiguous device tensor
-        t = _dev.to_dev(a, dt).contiguous()       # private: we write into it -- never into a buffer the caller may own
+        t = _dev.to_dev(a, dt)                    # private: we write into it -- never into a buffer the caller may own
         return t.clone() if (private and isinstance(a, torch.Tensor)) or t.data_ptr() in keep else t
 
-    def axpby(a, u, b, w):                        # w = a*u + b*w
-        _lib.check(lib.pfb_axpby(code, float(a), _dev.ptr(u), float(b), _dev.ptr(w), w.numel(), _dev.stream()))
+    axpby = _dev.axpby                            # w = a*u + b*w
 
     xp = xd.clone()
     vp = vd.clone()
@@ -283,6 +268,6 @@ def primal_dual(x, v, lam, psi, psiH, L, prox, grad, nu=1.0, sigma=None, mask=No
             print(f"Max iters reached. eps = {eps:.3e}", file=sys.stderr)
         else:
             print(f"Success, converged after {k} iterations", file=sys.stderr)
-    if as_numpy:
-        return xp.cpu().numpy(), vcur.cpu().numpy()
+    if _dev.is_numpy(x):
+        return host(xp), host(vcur)
     return xp.clone(), vcur

@@ -16,18 +16,16 @@ import numpy as np
 import torch
 
 from .. import _lib, _dev
-from .prox_21m import _prep, _writeback
+from .prox_21m import _prep
 
 
 def prox_21_numba(v, result, lam, sigma=1.0, weight=None):
     lib = _lib.load()
     vd, wd, nband, nper = _prep(v, weight)
-    direct = isinstance(result, torch.Tensor) and result.is_cuda and result.is_contiguous() \
-        and result.dtype == vd.dtype and result.shape == vd.shape
-    rd = result if direct else torch.empty_like(vd)
+    rd = _dev.out_buffer(result, vd)
     _lib.check(lib.pfb_prox_21(_dev.code(vd.dtype), _dev.ptr(vd), _dev.ptr(rd), _dev.ptr(wd), float(lam), float(sigma),
                                nband, nper, _dev.stream()))
-    return _writeback(result, rd)
+    return _dev.deliver(rd, result)
 
 
 def prox_21(v, sigma, weight=None, axis=0):
@@ -40,21 +38,18 @@ def prox_21(v, sigma, weight=None, axis=0):
         if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
     res = torch.empty_like(vd)
     prox_21_numba(vd, res, sigma, sigma=1.0, weight=w)    # v max(||v|| - sigma w, 0) / ||v||
-    return res.cpu().numpy() if _dev.is_numpy(v) else res
+    return _dev.host_like(res, v)
 
 
 def dual_update_numba(vp, v, lam, sigma=1.0, weight=None):
     lib = _lib.load()
-    direct = isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()
-    vd, wd, nband, nper = _prep(v, weight)
-    vpd = _dev.to_dev(vp, vd.dtype).contiguous()
+    vd, wd, nband, nper = _prep(v, weight)          # vd: v itself when it is a contiguous GPU tensor, else a copy
+    vpd = _dev.to_dev(vp, vd.dtype)
     if vpd.shape != vd.shape:
         raise ValueError("vp and v must have the same shape")
-    if not direct and isinstance(v, torch.Tensor):
-        vd = vd.clone()
     _lib.check(lib.pfb_dual_update_l2(_dev.code(vd.dtype), _dev.ptr(vpd), _dev.ptr(vd), _dev.ptr(wd), float(lam),
                                       float(sigma), nband, nper, _dev.stream()))
-    return _writeback(v, vd)
+    return _dev.deliver(vd, v)
 
 
 def dual_update(v, x, psiH, lam, sigma=1.0, weight=1.0):
@@ -64,4 +59,4 @@ def dual_update(v, x, psiH, lam, sigma=1.0, weight=1.0):
     w = torch.as_tensor(weight, dtype=vd.dtype, device=vd.device).expand(vd.shape[1:]).contiguous() \
         if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
     dual_update_numba(vd, vout, lam, sigma=sigma, weight=w)
-    return vout.cpu().numpy() if _dev.is_numpy(v) else vout
+    return _dev.host_like(vout, v)

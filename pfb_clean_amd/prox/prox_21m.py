@@ -19,7 +19,7 @@ from .. import _lib, _dev
 
 
 def _prep(v, weight):
-    vd = _dev.to_dev(v).contiguous()
+    vd = _dev.to_dev(v)
     if vd.ndim < 2:
         raise ValueError("expected (nband, ...) coefficient cube")
     nband = vd.shape[0]
@@ -35,25 +35,13 @@ def _prep(v, weight):
     return vd, wd, nband, nper
 
 
-def _writeback(dst, src):
-    if dst is src:
-        return dst
-    if _dev.is_numpy(dst):
-        dst[...] = src.cpu().numpy()
-    else:
-        dst.copy_(src)
-    return dst
-
-
 def prox_21m_numba(v, result, lam, sigma=1.0, weight=None):
     lib = _lib.load()
     vd, wd, nband, nper = _prep(v, weight)
-    direct = isinstance(result, torch.Tensor) and result.is_cuda and result.is_contiguous() \
-        and result.dtype == vd.dtype and result.shape == vd.shape
-    rd = result if direct else torch.empty_like(vd)
+    rd = _dev.out_buffer(result, vd)
     _lib.check(lib.pfb_prox_21m(_dev.code(vd.dtype), _dev.ptr(vd), _dev.ptr(rd), _dev.ptr(wd),
                                 float(lam), float(sigma), nband, nper, _dev.stream()))
-    return _writeback(result, rd)
+    return _dev.deliver(rd, result)
 
 
 def dual_update_numba(vp, v, lam, sigma=1.0, weight=None, vp_out=None, group=None):
@@ -65,17 +53,14 @@ def dual_update_numba(vp, v, lam, sigma=1.0, weight=None, vp_out=None, group=Non
     if group is not None:
         return _dual_update_sharded(vp, v, lam, sigma, weight, vp_out, group)
     lib = _lib.load()
-    direct = isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()
-    vd, wd, nband, nper = _prep(v, weight)
-    vpd = _dev.to_dev(vp, vd.dtype).contiguous()
+    vd, wd, nband, nper = _prep(v, weight)          # vd: v itself when it is a contiguous GPU tensor, else a copy
+    vpd = _dev.to_dev(vp, vd.dtype)
     if vpd.shape != vd.shape:
         raise ValueError("vp and v must have the same shape")
-    if not direct and isinstance(v, torch.Tensor):
-        vd = vd.clone()
     _lib.check(lib.pfb_dual_update(_dev.code(vd.dtype), _dev.ptr(vpd), _dev.ptr(vd), _dev.ptr(wd),
                                    float(lam), float(sigma), nband, nper,
                                    _dev.ptr(vp_out) if vp_out is not None else None, _dev.stream()))
-    return _writeback(v, vd)
+    return _dev.deliver(vd, v)
 
 
 def _dual_update_sharded(vp, v, lam, sigma, weight, vp_out, group):
@@ -87,7 +72,7 @@ def _dual_update_sharded(vp, v, lam, sigma, weight, vp_out, group):
     if not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
         raise TypeError("band-sharded dual update works on contiguous GPU tensors")
     vd, wd, nband, nper = _prep(v, weight)
-    vpd = _dev.to_dev(vp, vd.dtype).contiguous()
+    vpd = _dev.to_dev(vp, vd.dtype)
     if vp_out is not None and not (vp_out.is_contiguous() and vp_out.shape == vd.shape and vp_out.dtype == vd.dtype):
         raise ValueError("vp_out must be a contiguous tensor shaped like v")
     plane = torch.empty(nper, dtype=vd.dtype, device=vd.device)
@@ -116,7 +101,7 @@ def prox_21m(v, sigma, weight=1.0, axis=0):
         if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
     res = torch.empty_like(vd)
     prox_21m_numba(vd, res, sigma, sigma=1.0, weight=w)
-    return res.cpu().numpy() if _dev.is_numpy(v) else res
+    return _dev.host_like(res, v)
 
 
 def dual_update(v, x, psiH, lam, sigma=1.0, weight=1.0):
@@ -126,4 +111,4 @@ def dual_update(v, x, psiH, lam, sigma=1.0, weight=1.0):
     w = torch.as_tensor(weight, dtype=vd.dtype, device=vd.device).expand(vd.shape[1:]).contiguous() \
         if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
     dual_update_numba(vd, vout, lam, sigma=sigma, weight=w)
-    return vout.cpu().numpy() if _dev.is_numpy(v) else vout
+    return _dev.host_like(vout, v)

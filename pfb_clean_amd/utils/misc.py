@@ -12,16 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib, _dev
-
-
-def norm_diff_sums(x, xp):
-    """Device fp64 pair (sum (x-xp)^2, sum x^2) -- a 2-element GPU tensor view that is
-    overwritten by the next reduction on this thread/stream."""
-    lib = _lib.load()
-    ws, out = _dev.scratch()
-    _lib.check(lib.pfb_norm_diff_sums(_dev.code(x.dtype), _dev.ptr(x), _dev.ptr(xp), x.numel(),
-                                      _dev.ptr(out), _dev.ptr(ws), _dev.stream()))
-    return out[:2]
+from .._dev import norm_diff_sums
 
 
 def norm_diff(x, xp):
@@ -32,7 +23,7 @@ def norm_diff(x, xp):
     xd, xpd = _dev.to_dev(x), _dev.to_dev(xp)
     if xd.dtype != xpd.dtype or xd.shape != xpd.shape:
         raise ValueError("norm_diff: x and xp must have the same shape and dtype")
-    num, den = norm_diff_sums(xd.contiguous(), xpd.contiguous()).tolist()
+    num, den = norm_diff_sums(xd, xpd).tolist()
     return math.sqrt(num / (1e-12 + den))
 
 
@@ -118,8 +109,8 @@ def dds2cubes(dds, nband, apparent=False, dual=True, modelname='MODEL'):
 
 def _freqmul(A, x, pre=None, post=None):
     lib = _lib.load()
-    xd = _dev.to_dev(x).contiguous()
-    Ad = _dev.to_dev(A, xd.dtype).contiguous()
+    xd = _dev.to_dev(x)
+    Ad = _dev.to_dev(A, xd.dtype)
     out = torch.empty_like(xd)
     nband = xd.shape[0]
     if tuple(Ad.shape) != (nband, nband):
@@ -131,8 +122,7 @@ def _freqmul(A, x, pre=None, post=None):
 
 def freqmul(A, x):
     """misc.py:1366-1375: out[k] = sum_l A[k, l] x[l] for an (nband, nx, ny) cube, on the GPU."""
-    out = _freqmul(A, x)
-    return out.cpu().numpy() if _dev.is_numpy(x) else out
+    return _dev.host_like(_freqmul(A, x), x)
 
 
 def setup_parametrisation(mode='id', minval=1e-5, sigma=1.0, freq=None, lscale=1.0):
@@ -148,36 +138,33 @@ def setup_parametrisation(mode='id', minval=1e-5, sigma=1.0, freq=None, lscale=1
     LH = np.ascontiguousarray(L.T)
     Linv = np.linalg.solve(L, np.eye(nband))
 
-    def back(t, like):
-        return t.cpu().numpy() if _dev.is_numpy(like) else t
-
     if mode == 'id':
         def func(x):
-            return back(_freqmul(L, x), x)
+            return _dev.host_like(_freqmul(L, x), x)
 
         def finv(x):
-            return back(_freqmul(Linv, x), x)
+            return _dev.host_like(_freqmul(Linv, x), x)
 
         def dfunc(x0, v):
-            return back(_freqmul(L, v), v)
+            return _dev.host_like(_freqmul(L, v), v)
 
         def dhfunc(x0, v):
-            return back(_freqmul(LH, v), v)
+            return _dev.host_like(_freqmul(LH, v), v)
     elif mode == 'exp':
         def func(x):
-            return back(torch.exp(_freqmul(L, x)), x)
+            return _dev.host_like(torch.exp(_freqmul(L, x)), x)
 
         def finv(x):
             t = _freqmul(Linv, x)
-            return back(torch.log(torch.clamp(torch.abs(t), min=minval)), x)
+            return _dev.host_like(torch.log(torch.clamp(torch.abs(t), min=minval)), x)
 
         def dfunc(x0, v):
             e = torch.exp(_freqmul(L, x0))
-            return back(_freqmul(L, v, post=e), v)                 # exp(L x0) * (L v)
+            return _dev.host_like(_freqmul(L, v, post=e), v)         # exp(L x0) * (L v)
 
         def dhfunc(x0, v):
             e = torch.exp(_freqmul(L, x0))
-            return back(_freqmul(LH, v, pre=e), v)                 # L^T (v * exp(L x0))
+            return _dev.host_like(_freqmul(LH, v, pre=e), v)         # L^T (v * exp(L x0))
     else:
         raise ValueError(f"Unknown mode - {mode}")
     return func, finv, dfunc, dhfunc

@@ -13,14 +13,13 @@ CHECKED against the sizes the filter length implies (psi.py:60-94) instead of be
 ValueError rather than writing somewhere else than the reference would.
 
 The transforms run through a single-band, single-basis plan of the same kernels operators.psi.Psi uses
-(pfb_psi_dot / pfb_psi_hdot), cached per (shape, filter, level count, dtype); numpy arguments are staged through the
-GPU, torch-ROCm tensors stay resident.
+(pfb_psi_dot / pfb_psi_hdot), cached per (shape, filter, level count, dtype) and shared by every thread and stream
+that asks for the same one; numpy arguments are staged through the GPU, torch-ROCm tensors stay resident.
 """
-import ctypes as C
-import threading
-
 import numpy as np
 
+from .. import _lib, _dev
+from .._plan import PlanCache, PsiPlan
 from .filters import filter_bank, dwt_max_level  # noqa: F401
 
 
@@ -56,42 +55,27 @@ def level_sizes(nx, ny, nfilter, nlevel):
     return tuple(sx), tuple(sy), tuple(spx), tuple(spy), ix, iy, hx, hy
 
 
-_plans = {}
-_plans_lock = threading.Lock()
+_plans = PlanCache(32)                           # a handful of shapes is the use case; never grow without bound
 
 
 def _single_basis_plan(nx, ny, f_lo, f_hi, analysis, nlevel, dtype):
-    """pfb_psi plan for ONE band and ONE basis whose four filters follow from the pair handed in (orthogonal banks:
-    the synthesis pair is the analysis pair reversed, psi.py:38-41)."""
-    from .. import _lib, _dev
+    """Shared PsiPlan for ONE band and ONE basis whose four filters follow from the pair handed in (orthogonal banks:
+    the synthesis pair is the analysis pair reversed, psi.py:38-41).  Enqueue on it under its lock, after
+    _enter_stream()."""
     lo = np.ascontiguousarray(f_lo, dtype=np.float64)
     hi = np.ascontiguousarray(f_hi, dtype=np.float64)
     F = lo.size
     if hi.size != F or F % 2 or not (2 <= F <= 18):
         raise ValueError(f"filter pair of lengths ({lo.size}, {hi.size}): need two even-length filters of 2..18 taps")
-    key = (int(nx), int(ny), int(nlevel), dtype, bool(analysis), lo.tobytes(), hi.tobytes())
-    with _plans_lock:
-        hit = _plans.get(key)
-        if hit is not None:
-            return hit
-        _dev.require_device()
-        lib = _lib.load()
+
+    def make():
         filt = np.zeros((1, 4, 18), dtype=np.float64)
         if analysis:
             filt[0, 0, :F], filt[0, 1, :F], filt[0, 2, :F], filt[0, 3, :F] = lo, hi, lo[::-1], hi[::-1]
         else:
             filt[0, 0, :F], filt[0, 1, :F], filt[0, 2, :F], filt[0, 3, :F] = lo[::-1], hi[::-1], lo, hi
-        ks = (C.c_int * 1)(F // 2)
-        h = C.c_void_p()
-        _lib.check(lib.pfb_psi_plan_create(1, int(nx), int(ny), 1, ks, filt.ctypes.data_as(C.POINTER(C.c_double)),
-                                           int(nlevel), _dev.code(dtype), C.byref(h)))
-        nym, nxm = C.c_int(), C.c_int()
-        _lib.check(lib.pfb_psi_plan_dims(h, C.byref(nym), C.byref(nxm)))
-        if len(_plans) >= 32:                    # a handful of shapes is the use case; never grow without bound
-            _, (old, _, _) = _plans.popitem()
-            lib.pfb_psi_plan_destroy(old)
-        _plans[key] = (h, nym.value, nxm.value)
-        return _plans[key]
+        return PsiPlan(1, nx, ny, [F // 2], filt, nlevel, dtype)
+    return _plans.get((int(nx), int(ny), int(nlevel), dtype, bool(analysis), lo.tobytes(), hi.tobytes()), make)
 
 
 def _check_bookkeeping(nx, ny, F, nlevel, coeffs_shape, ix, iy, sx, sy, spx=None, spy=None):
@@ -112,57 +96,38 @@ def _check_bookkeeping(nx, ny, F, nlevel, coeffs_shape, ix, iy, sx, sy, spx=None
 def dwt2d(image, coeffs, cbuff, cbuffT, ix, iy, sx, sy, dec_lo, dec_hi, nlevel):
     """Multi-level 2-D image -> coeffs (wavelets.py:175-213); `coeffs` (Ntoty, Ntotx) is written in place (cells of
     the packed layout that belong to no level block are left untouched, as in the reference) and returned."""
-    import torch
-    from .. import _lib, _dev
     if image.ndim != 2 or coeffs.ndim != 2:
         raise ValueError("dwt2d expects a 2-D image and a 2-D coefficient array")
     nx, ny = (int(v) for v in image.shape)
     F = int(np.asarray(dec_lo).size)
     _check_bookkeeping(nx, ny, F, int(nlevel), coeffs.shape, ix, iy, sx, sy)
-    xd = _dev.to_dev(image).contiguous()
-    h, nym, nxm = _single_basis_plan(nx, ny, dec_lo, dec_hi, True, nlevel, xd.dtype)
-    direct = isinstance(coeffs, torch.Tensor) and coeffs.is_cuda and coeffs.is_contiguous() and coeffs.dtype == xd.dtype
-    cd = coeffs if direct else _dev.to_dev(coeffs, xd.dtype).contiguous()
-    _lib.check(_lib.load().pfb_psi_dot(h, _dev.ptr(xd), _dev.ptr(cd), _dev.stream()))
-    if not direct:
-        if _dev.is_numpy(coeffs):
-            coeffs[...] = cd.cpu().numpy()
-        else:
-            coeffs.copy_(cd)
-    return coeffs
+    xd = _dev.to_dev(image)
+    plan = _single_basis_plan(nx, ny, dec_lo, dec_hi, True, nlevel, xd.dtype)
+    cd = _dev.to_dev(coeffs, xd.dtype)          # coeffs itself when it is a contiguous GPU tensor of the image's dtype
+    with plan.lock:
+        plan._enter_stream()
+        _lib.check(plan._lib.pfb_psi_dot(plan.handle, _dev.ptr(xd), _dev.ptr(cd), _dev.stream()))
+    return _dev.deliver(cd, coeffs)
 
 
 def idwt2d(coeffs, image, alpha, cbuff, cbuffT, ix, iy, sx, sy, spx, spy, rec_lo, rec_hi, nlevel):
     """Multi-level 2-D coeffs -> image (wavelets.py:261-315); `image` (nx, ny) is overwritten and returned, `coeffs`
     is not modified (the reference copies it into `alpha` for that; here nothing writes to it)."""
-    import torch
-    from .. import _lib, _dev
     if image.ndim != 2 or coeffs.ndim != 2:
         raise ValueError("idwt2d expects a 2-D coefficient array and a 2-D image")
     nx, ny = (int(v) for v in image.shape)
     F = int(np.asarray(rec_lo).size)
     _check_bookkeeping(nx, ny, F, int(nlevel), coeffs.shape, ix, iy, sx, sy, spx, spy)
-    cd = _dev.to_dev(coeffs).contiguous()
-    h, nym, nxm = _single_basis_plan(nx, ny, rec_lo, rec_hi, False, nlevel, cd.dtype)
-    direct = isinstance(image, torch.Tensor) and image.is_cuda and image.is_contiguous() and image.dtype == cd.dtype
-    xd = image if direct else torch.empty((nx, ny), dtype=cd.dtype, device=cd.device)
-    _lib.check(_lib.load().pfb_psi_hdot(h, _dev.ptr(cd), _dev.ptr(xd), _dev.stream()))
-    if not direct:
-        if _dev.is_numpy(image):
-            image[...] = xd.cpu().numpy()
-        else:
-            image.copy_(xd)
-    return image
+    cd = _dev.to_dev(coeffs)
+    plan = _single_basis_plan(nx, ny, rec_lo, rec_hi, False, nlevel, cd.dtype)
+    xd = _dev.out_buffer(image, cd, shape=(nx, ny))
+    with plan.lock:
+        plan._enter_stream()
+        _lib.check(plan._lib.pfb_psi_hdot(plan.handle, _dev.ptr(cd), _dev.ptr(xd), _dev.stream()))
+    return _dev.deliver(xd, image)
 
 
 def clear_plans():
-    """Destroy the cached single-basis plans (tests; a long-lived process that cycles through many shapes)."""
-    from .. import _lib
-    with _plans_lock:
-        if _plans:
-            import torch
-            torch.cuda.synchronize()
-            lib = _lib.load()
-            for h, _, _ in _plans.values():
-                lib.pfb_psi_plan_destroy(h)
-            _plans.clear()
+    """Drop the cached single-basis plans (tests; a long-lived process that cycles through many shapes).  A plan is
+    destroyed once no caller holds it any more."""
+    _plans.clear()

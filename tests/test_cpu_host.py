@@ -130,6 +130,49 @@ def test_plan_cache_fingerprint_distinguishes_content():
     assert _fingerprint(a[0]) != _fingerprint(a[1]) or a[0].__array_interface__['data'][0] != a[1].__array_interface__['data'][0]
 
 
+def test_plan_cache_evicts_the_oldest_and_never_destroys_a_plan_still_held():
+    """The shared LRU behind plan_for and the stand-alone wavelet transforms: least recently used out first, and
+    dropping an entry only releases the cache's reference -- a plan is closed when its last holder lets go."""
+    import gc
+    from pfb_clean_amd._plan import PlanCache
+    closed = []
+
+    class Plan:
+        def __init__(self, name):
+            self.name = name
+
+        def close(self):
+            closed.append(self.name)
+
+        def __del__(self):
+            self.close()
+
+    def make(name):
+        return lambda: Plan(name)
+
+    def fail():
+        raise AssertionError("cache miss")
+
+    cache = PlanCache(2)
+    held = cache.get('a', make('a'))
+    cache.get('b', make('b'))
+    assert cache.get('a', fail) is held               # a hit makes 'a' the most recent
+    cache.get('c', make('c'))                         # evicts 'b', the oldest
+    gc.collect()
+    assert closed == ['b']
+    assert cache.get('a', fail) is held and cache.get('c', fail).name == 'c'
+    cache.get('d', make('d'))                         # evicts 'a', which the caller still holds
+    gc.collect()
+    assert closed == ['b'] and held.name == 'a'
+    del held
+    gc.collect()
+    assert closed == ['b', 'a']
+    cache.clear()
+    gc.collect()
+    assert sorted(closed) == ['a', 'b', 'c', 'd']
+    assert cache.get('c', make('c2')).name == 'c2'    # cleared: made afresh
+
+
 # ------------------------------------------------------------------ gloo, world_size 2
 def _free_port():
     s = socket.socket()

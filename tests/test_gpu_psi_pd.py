@@ -163,6 +163,54 @@ def test_standalone_dwt2d_idwt2d_with_the_reference_argument_lists(amd, wavelet,
         dwt2d(data, alpha2, cbuff, cbuffT, ix, iy, tuple(v + 1 for v in sx), sy, dec_lo, dec_hi, nlevel)
 
 
+def test_standalone_dwt2d_idwt2d_share_one_plan_across_threads_and_streams(amd):
+    """Two host threads, each on its own stream, run dwt2d then idwt2d repeatedly on the same shape and filter pair,
+    so both use the same cached plans, each with its own images: every result matches the oracle in fp64."""
+    import threading
+    from pfb_clean_amd.wavelets import dwt2d, idwt2d, level_sizes, filter_bank, clear_plans
+    nx, ny, nlevel, nrep = 256, 192, 3, 6
+    dec_lo, dec_hi, rec_lo, rec_hi = filter_bank('db4')
+    sx, sy, spx, spy, ix, iy, ntx, nty = level_sizes(nx, ny, dec_lo.size, nlevel)
+    bk = owv.Bookkeeping(nx, ny, dec_lo.size, nlevel)
+    images = np.random.default_rng(31).standard_normal((2, nrep, nx, ny))
+    got, errors = [None, None], []
+
+    def run(t):
+        try:
+            stream = torch.cuda.Stream()
+            with torch.cuda.stream(stream):
+                res = []
+                for k in range(nrep):
+                    img = torch.from_numpy(images[t, k]).cuda()
+                    co = torch.zeros((nty, ntx), dtype=torch.float64, device='cuda')
+                    rec = torch.empty_like(img)
+                    dwt2d(img, co, None, None, ix, iy, sx, sy, dec_lo, dec_hi, nlevel)
+                    idwt2d(co, rec, None, None, None, ix, iy, sx, sy, spx, spy, rec_lo, rec_hi, nlevel)
+                    res.append((co, rec))
+                stream.synchronize()
+                got[t] = [(co.cpu().numpy(), rec.cpu().numpy()) for co, rec in res]
+        except Exception as e:          # re-raised below, in the test's own thread
+            errors.append(e)
+
+    clear_plans()
+    threads = [threading.Thread(target=run, args=(t,)) for t in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    if errors:
+        raise errors[0]
+    for t in range(2):
+        for k in range(nrep):
+            co, rec = got[t][k]
+            want = np.zeros((nty, ntx))
+            owv.dwt2d(images[t, k], want, bk, dec_lo, dec_hi)
+            assert maxerr(co, want) < 1e-12
+            want_rec = np.zeros((nx, ny))
+            owv.idwt2d(want, want_rec, bk, rec_lo, rec_hi)
+            assert maxerr(rec, want_rec) < 1e-12
+
+
 def test_primal_dual_with_a_callers_own_affine_synthesis(amd):
     """`psiH` is an arbitrary callable in primal_dual_optimised's signature (primal_dual.py:91-101).  The linear-synthesis
     shortcut (2 psi^H(v) - psi^H(vp)) is only valid for a LINEAR synthesis that overwrites its output, so it is taken
