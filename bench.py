@@ -2,7 +2,7 @@
 """
 bench.py -- the BASELINE workloads on MI355X, one JSON line on stdout (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--workload pcg|pd] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--workload pcg|pd] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 --workload pcg (default, the headline metric): PCG matvecs/sec on the 4096 x 4096 x 8-band cube
@@ -27,17 +27,22 @@ DIR/<name>.npy, so that two builds can be compared output for output; large outp
 child `torch.distributed.run` before anything touches the GPU and relays rank 0's line;
 --gpus that disagrees with WORLD_SIZE is an error.
 
+A plain run does only what the headline figure needs: set-up, warm-up, the timed regions, --dump-outputs, the JSON
+line.  --full adds what takes time of its own: the CPU oracle baseline with its parity check (cpu_baseline, parity;
+--no-cpu leaves them out) and, on the one-GPU headline run, the other BASELINE configs (configs; see --configs).
+
 Extra objects on the JSON line:
   roofline     pcg: the FFT-convolution kernel group (row-fwd, column, row-inv = one band matvec),
                algorithmic bytes B_alg = s (2 nx ny + 2 nx_psf (ny_psf/2+1)) per band-matvec
                 over its HIP-event-measured duration inside the timed solves (events
                recorded by the library on the solver's stream); per-stage times alongside.
                pd: the whole iteration's algorithmic bytes over its duration.
-  cpu_baseline the numpy/scipy.fft oracle ("port" of the reference's CPU path; ducc0 is not
+  configs      (--full) the other BASELINE configs timed in the same run (extra_configs).
+  cpu_baseline (--full) the numpy/scipy.fft oracle ("port" of the reference's CPU path; ducc0 is not
                installable) on this host: ALL bands of the same cube solved concurrently, one
                process per band (the reference runs bands concurrently too, pcg.py:320-356), a
                bounded number of iterations; the cube rate is measured, not extrapolated.
-  parity       max relative difference GPU vs CPU oracle of one band-matvec on the same input.
+  parity       (--full) max relative difference GPU vs CPU oracle of one band-matvec on the same input.
 """
 import argparse
 import json
@@ -79,13 +84,16 @@ def parse_args(argv=None):
     ap.add_argument('--size', type=int, default=None)
     ap.add_argument('--bands', type=int, default=None)
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f64'])
-    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline / parity leg')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the cpu_baseline / parity leg and, with '
+                         '--configs auto, the other BASELINE configs')
+    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline / parity leg of a --full run')
     ap.add_argument('--cpu-seconds', type=float, default=20.0)
     ap.add_argument('--cpu-cores', type=int, default=0,
                     help='host cores for the cpu_baseline leg (0 = min(usable cores, 64): the fastest setting measured)')
     ap.add_argument('--configs', default='auto', choices=['auto', 'all', 'none'],
                     help="the other BASELINE configs (C1, C2, C4, C5 shard) timed in the same run and reported under "
-                         "'configs' on the JSON line; auto = all for the default one-GPU headline run")
+                         "'configs' on the JSON line; auto = all for a --full one-GPU headline run, none otherwise")
     ap.add_argument('--force-dist', action='store_true',
                     help='run the band-sharded code path (all-reduce hook) even at world size 1')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -306,7 +314,7 @@ def main():
     ctx = dict(args=args, world=world, rank=rank, device=device, use_pg=use_pg)
     out = bench_pd(ctx) if args.workload == 'pd' else bench_pcg(ctx)
     headline = args.workload == 'pcg' and args.size is None and args.bands is None and args.dtype == 'f32'
-    if args.configs == 'all' or (args.configs == 'auto' and headline and world == 1 and not args.force_dist):
+    if args.configs == 'all' or (args.configs == 'auto' and args.full and headline and world == 1 and not args.force_dist):
         out["configs"] = extra_configs(ctx)
     if rank == 0:
         print(json.dumps(out))
@@ -470,7 +478,7 @@ def bench_pcg(ctx):
         }
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu, parity = cpu_baseline(plan, psfhat, b, sigmainv, n, nband, args)
 
     out = {
@@ -724,7 +732,7 @@ def bench_pd(ctx):
         "repeats": len(times), "value_min": round(args.steps / max(times), 3), "value_max": round(args.steps / min(times), 3),
         "roofline": roofline, "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_pd(psfhat, dirty, lam, L, n, nband, bases, nlevel, args)
         if out["cpu_baseline"]:
             out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)

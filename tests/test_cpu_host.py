@@ -483,3 +483,12 @@ def test_bench_dump_sample_is_fixed_and_steps_are_checked():
     for bad in (['--steps', '0'], ['--warmup', '-1']):
         with pytest.raises(SystemExit):
             bench.parse_args(bad)
+
+
+def test_bench_full_is_opt_in():
+    """The CPU oracle leg and the other BASELINE configs run only under --full; a plain run keeps the defaults."""
+    import bench
+    a = bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert not a.full and not a.no_cpu and a.configs == 'auto'
+    assert (a.steps, a.warmup, a.repeats, a.workload, a.dtype) == (20, 5, 5, 'pcg', 'f32')
+    assert bench.parse_args(['--full']).full

@@ -839,6 +839,45 @@ def test_bench_dump_outputs_pcg(tmp_path):
         assert np.allclose(got['pcg_result'][4:], [res.eps, res.rnorm], rtol=1e-6, atol=0)
 
 
+def test_bench_plain_run_is_headline_only():
+    """A plain headline run (no --full) times its steps and prints the line, and runs nothing else: no CPU oracle leg,
+    no other BASELINE configs."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = _run_bench(root, ['--gpus', '1', '--steps', '2', '--warmup', '1', '--repeats', '1'])
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['matvecs'] == 3 and d['value'] > 0 and d['ms_per_step'] > 0
+    assert d['cpu_baseline'] is None and d['parity'] is None and 'configs' not in d and 'gpu_over_cpu' not in d
+    assert d['roofline'] is not None
+
+
+def test_bench_full_adds_cpu_leg(tmp_path):
+    """--full adds the CPU oracle leg and its parity check to the same JSON line; the timed steps and the dumped
+    outputs are those of the plain run."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ['--size', '256', '--bands', '2', '--steps', '3', '--warmup', '1', '--repeats', '1']
+    lines = {}
+    for mode, extra in (('plain', []), ('full', ['--full', '--cpu-seconds', '1', '--cpu-cores', '2'])):
+        out = _run_bench(root, args + extra + ['--dump-outputs', str(tmp_path / mode)])
+        lines[mode] = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+    plain, full = lines['plain'], lines['full']
+    assert plain['cpu_baseline'] is None and plain['parity'] is None
+    assert full['cpu_baseline']['value'] > 0 and full['cpu_baseline']['unit'] == 'cube-matvecs/s'
+    assert full['parity']['ok'] and full['gpu_over_cpu'] > 0
+    assert 'configs' not in plain and 'configs' not in full            # not the headline size: configs auto = none
+    for k in ('metric', 'unit', 'steps', 'warmup', 'matvecs', 'dtype', 'higher_is_better'):
+        assert plain[k] == full[k], k
+    for name in ('x', 'pcg_result'):
+        assert np.array_equal(np.load(tmp_path / 'plain' / f'{name}.npy'), np.load(tmp_path / 'full' / f'{name}.npy'))
+
+
 def test_bench_dump_outputs_pd(tmp_path):
     """--workload pd --dump-outputs: x and v as primal_dual_optimised returns them (full shape below DUMP_MAX)."""
     if not torch.cuda.is_available():

@@ -1,10 +1,10 @@
-"""Markdown table of the BASELINE configs from ONE default `bench.py` run (its "configs" object; round 3).
+"""Markdown table of the BASELINE configs from ONE `bench.py --full` run (its "configs" object; round 3).
     python tools/make_configs_table.py BENCH_JSON [TITLE]"""
 import json
 import sys
 
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
-title = sys.argv[2] if len(sys.argv) > 2 else "the BASELINE configs from one default `python bench.py` run"
+title = sys.argv[2] if len(sys.argv) > 2 else "the BASELINE configs from one `python bench.py --full` run"
 print(f"# {title}\n")
 print("| config | value | ms per step (K+1 matvecs / K steps) | row_fwd / col / row_inv ms per launch | roofline.frac (algorithmic) |")
 print("|---|---|---|---|---|")
