@@ -136,6 +136,14 @@ int pfb_psfconv_apply_dots(pfb_conv_plan* plan, int band0, int nb,
                            void* out, const void* dot_with, const void* dot_with2,
                            double* dots_out, void* stream);
 
+/* Same apply, with the three sums PER BAND: dots_out is [nb][3] device doubles, dots_out[3 bl + 0] =
+ * <dot_with, out>, [3 bl + 1] = <dot_with2, out> (0 if dot_with2 is NULL), [3 bl + 2] = <out, out> over band
+ * band0 + bl alone, each summed in fp64 in a fixed order (the per-band products pfb_pcg_solve_bands needs). */
+int pfb_psfconv_apply_dots_bands(pfb_conv_plan* plan, int band0, int nb,
+                                 const void* x, const void* beam, double wsum, double sigmainv,
+                                 void* out, const void* dot_with, const void* dot_with2,
+                                 double* dots_out, void* stream);
+
 /* Introspection for benchmarks / tests */
 int    pfb_psfconv_plan_info(const pfb_conv_plan* plan, int* fast_path, int* vb,
                              size_t* workspace_bytes);
@@ -174,7 +182,8 @@ int pfb_axpby(int dtype, double a, const void* x, double b, void* y, size_t n,
  * and the preconditioner M(r) = r / mdiv (mdiv = sigmainv as pcg.py:264-267;
  * mdiv <= 0 means M = identity).  NaN/Inf propagate silently exactly as in the reference.
  * Works on bands [band0, band0+nb) as ONE system (np.vdot over the whole cube, the
- * fluxmop semantics fluxmop.py:193-199); call once per band for pcg_psf semantics.
+ * fluxmop semantics fluxmop.py:193-199); for pcg_psf semantics call it once per band, or solve all
+ * bands at once with pfb_pcg_solve_bands below.
  *
  * backtrack: 0 = off; 1 = the reference's loop verbatim (every rejected step re-runs the
  * vector update); 2 = predictive: the same decisions from the quadratic
@@ -221,6 +230,34 @@ int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb,
                   double tol, int maxit, int minit, int backtrack,
                   void* work, pfb_allreduce_fn allreduce, void* allreduce_ctx,
                   pfb_pcg_result* result, void* stream);
+
+/* ------------------------------------------------------------ batched per-band PCG
+ * pcg_psf (pfb/opt/pcg.py:243-360): every band of [band0, band0+nb) is its OWN system, solved as in
+ * pfb_pcg_solve with nb = 1 -- its own step lengths, backtracking, stopping rule and exit status -- but all
+ * bands in one solve: one convolution launch group per iteration over the bands still active, per-band
+ * scalars on the device, and the host looks only once some band can stop (k >= minit), and then only at
+ * whether any band is still active.  Band bl's result equals pfb_pcg_solve's on that band alone up to the
+ * order of the fp64 reductions (every band's convolution output is bit-identical to that solve's, except on the
+ * plain-kernel paths, which both share).
+ *   - a band whose initial residual is zero keeps x = x0 and gets PFB_PCG_ZERO_RESIDUAL; the others solve;
+ *   - breakdown (all-zero direction) ends that band before k += 1, as pcg.py:106-107;
+ *   - once a band has stopped, its x and r are never written again (iterations the host enqueued ahead of
+ *     its look change nothing there).
+ * backtrack: 0 or 2 (predictive); 1 (the exact loop) returns PFB_ERR_UNSUPPORTED -- solve band by band with
+ * pfb_pcg_solve for it.  No all-reduce hook: the bands are independent; shard them over GPUs and run one
+ * batched solve per rank.
+ * Convolution: at every host look the convolved range narrows to the span of bands still live; a stopped band
+ * between two live ones is still convolved (its result is discarded), so bands that need very different
+ * iteration counts can cost more convolution work than a band-by-band loop.
+ * Memory: work holds r, p and Ap of ALL nb bands at once (3 nb nx ny elements + per-band state), where a
+ * band-by-band loop of pfb_pcg_solve holds 5 vectors of one band; x is updated in place.
+ * results: nb entries.  Synchronises `stream`. */
+size_t pfb_pcg_bands_work_bytes(const pfb_conv_plan* plan, int nb);
+int pfb_pcg_solve_bands(pfb_conv_plan* plan, int band0, int nb,
+                        const void* b, void* x, void* r_out,
+                        const void* beam, double wsum, double sigmainv, double mdiv,
+                        double tol, int maxit, int minit, int backtrack,
+                        void* work, pfb_pcg_result* results, void* stream);
 
 /* ------------------------------------------------ band-shard exchange (RCCL, called from C)
  * The reference sums the CG inner products over ALL bands inside one process

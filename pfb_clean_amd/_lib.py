@@ -56,6 +56,7 @@ SIGNATURES = {
     'pfb_psfhat_regrid': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'pfb_psfhat_from_psf': (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     'pfb_psfconv_apply_dots': (_i, [_vp, _i, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    'pfb_psfconv_apply_dots_bands': (_i, [_vp, _i, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     'pfb_psfconv_plan_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
     'pfb_psfconv_set_profiling': (_i, [_vp, _i]),
     'pfb_psfconv_get_profile': (_i, [_vp, C.POINTER(_d), C.POINTER(_i)]),
@@ -66,6 +67,9 @@ SIGNATURES = {
     'pfb_pcg_work_bytes': (_sz, [_vp, _i]),
     'pfb_pcg_solve': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i,
                            _vp, ALLREDUCE_FN, _vp, C.POINTER(PcgResult), _vp]),
+    'pfb_pcg_bands_work_bytes': (_sz, [_vp, _i]),
+    'pfb_pcg_solve_bands': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i,
+                                 _vp, C.POINTER(PcgResult), _vp]),
     'pfb_comm_bind': (_i, [C.c_char_p]),
     'pfb_comm_unique_id': (_i, [_vp]),
     'pfb_comm_init': (_i, [_i, _i, _vp, C.POINTER(_vp)]),

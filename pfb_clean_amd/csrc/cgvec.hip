@@ -15,6 +15,7 @@
 #include <unistd.h>
 #include <cstring>
 #include <cstdlib>
+#include <vector>
 
 namespace pfb {
 
@@ -411,6 +412,184 @@ __global__ void k_init_state(double* S, double tol, double minit, double maxit) 
     S[S_EPS] = 1.0; S[S_EPSP] = 1.0;
 }
 
+// ------------------------------------------------------------------ batched per-band PCG (pfb_pcg_solve_bands)
+// Every band is its own system with its own state block S + bl * SB.  The vector kernels give each band `gpb`
+// workgroups of its own (workgroup w works on band w / gpb only), so every partial sum belongs to one band:
+// ws[q * (nb gpb) + bl * gpb + g].  The bookkeeping kernels run one workgroup per band and sum that band's partials in
+// a fixed order.  A band that has stopped (S_STOP) or broken down (S_DEAD) is neither read nor written, and its state
+// is left as the iteration that stopped it left it.
+constexpr int SB = 32;                     // doubles per band state block
+constexpr int SB_ZERO = S_NSCALAR;         // the band's initial residual was zero (it never iterates)
+static_assert(SB_ZERO < SB, "band state block too small");
+
+__device__ __forceinline__ bool band_live(const double* Sb) { return Sb[S_DEAD] == 0.0 && Sb[S_STOP] == 0.0; }
+
+// r holds A(x0) on entry.  r = r - b ; p = -M r ; per band: <r,y>, count(y != 0)
+template <typename T, int V>
+__global__ void __launch_bounds__(RED_BLOCK)
+k_pcg_init_bands(T* __restrict__ r, const T* __restrict__ b, T* __restrict__ p, T mdiv, size_t nvb, int gpb,
+                 double* __restrict__ ws) {
+    const int bl = blockIdx.x / gpb, g = blockIdx.x - bl * gpb;
+    const size_t off = (size_t)bl * nvb;
+    double acc[2] = {0.0, 0.0};
+    for (size_t i = (size_t)g * blockDim.x + threadIdx.x; i < nvb; i += (size_t)gpb * blockDim.x) {
+        Pack<T, V> pr = ld<T, V>(r, off + i), pb = ld<T, V>(b, off + i), pp;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const T rr = pr.e[e] - pb.e[e];
+            const T y = mdiv > T(0) ? rr / mdiv : rr;
+            pr.e[e] = rr;
+            pp.e[e] = -y;
+            acc[0] += (double)rr * (double)y;
+            acc[1] += (y != T(0)) ? 1.0 : 0.0;
+        }
+        st<T, V>(r, off + i, pr);
+        st<T, V>(p, off + i, pp);
+    }
+    emit_partials<2>(acc, ws);
+}
+
+// per band: S_RHO = <r,y>, S_ANY = count(y != 0) and the rule's parameters (k_init_state); a band with a zero initial
+// residual is marked SB_ZERO + S_STOP, so that no later kernel touches it
+__global__ void __launch_bounds__(128)
+k_init_bands(const double* __restrict__ ws, int gpb, double* __restrict__ S, double tol, double minit, double maxit) {
+    __shared__ double vals[2];
+    const int bl = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t G = (size_t)gridDim.x * gpb;
+    double acc = 0.0;
+    for (int g = lane; g < gpb; g += 64) acc += ws[w * G + (size_t)bl * gpb + g];
+    acc = wave_sum(acc);
+    if (lane == 0) vals[w] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* Sb = S + (size_t)bl * SB;
+        Sb[S_TOL] = tol; Sb[S_MINIT] = minit; Sb[S_MAXIT] = maxit;
+        Sb[S_RHON] = vals[0]; Sb[S_NUM] = vals[1];
+        Sb[S_RHO] = vals[0];
+        Sb[S_ANY] = vals[1];
+        Sb[S_EPS] = 1.0; Sb[S_EPSP] = 1.0;
+        if (vals[1] == 0.0) { Sb[SB_ZERO] = 1.0; Sb[S_STOP] = 1.0; }
+    }
+}
+
+// k_pcg_update_dir on one band per workgroup, in place (the predictive modes need no old x): x' = x + a p,
+// r' = r + a Ap, p' = beta p - M r' with the band's own alpha / beta; sums <r',y'>, |x'-x|^2, |x'|^2, count(p' != 0).
+// XNT / REV as in k_pcg_update_dir (x non-temporal, each band walked from its end), for vectors far beyond the caches
+template <typename T, int V, int U, bool XNT, bool REV>
+__global__ void __launch_bounds__(RED_BLOCK)
+k_pcg_update_dir_bands(T* __restrict__ x, T* __restrict__ r, T* __restrict__ p, const T* __restrict__ Ap,
+                       const double* __restrict__ S, T mdiv, size_t nvb, int gpb, double* __restrict__ ws) {
+    const int bl = blockIdx.x / gpb, g = blockIdx.x - bl * gpb;
+    const double* Sb = S + (size_t)bl * SB;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (band_live(Sb)) {
+        const T alpha = (T)Sb[S_ALPHA];
+        const T beta = (T)Sb[S_BETA];
+        const size_t off = (size_t)bl * nvb;
+        const size_t stride = (size_t)gpb * blockDim.x;
+        for (size_t i0 = (size_t)g * blockDim.x + threadIdx.x; i0 < nvb; i0 += U * stride) {
+            Pack<T, V> px[U], pr[U], pp[U], pa[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {          // all loads of the U strips in flight together
+                const size_t ii = i0 + u * stride;
+                const size_t i = off + (REV ? nvb - 1 - ii : ii);
+                if (ii < nvb) {
+                    px[u] = XNT ? ld_nt<T, V>(x, i) : ld<T, V>(x, i);
+                    pr[u] = ld<T, V>(r, i); pp[u] = ld<T, V>(p, i); pa[u] = ld<T, V>(Ap, i);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const size_t ii = i0 + u * stride;
+                const size_t i = off + (REV ? nvb - 1 - ii : ii);
+                if (ii >= nvb) break;
+                Pack<T, V> ox, orr;
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    const T xnew = px[u].e[e] + alpha * pp[u].e[e];
+                    const T rnew = pr[u].e[e] + alpha * pa[u].e[e];
+                    const T y = mdiv > T(0) ? rnew / mdiv : rnew;
+                    ox.e[e] = xnew;
+                    orr.e[e] = rnew;
+                    const double d = (double)xnew - (double)px[u].e[e];
+                    acc[0] += (double)rnew * (double)y;
+                    acc[1] += d * d;
+                    acc[2] += (double)xnew * (double)xnew;
+                    const T pn = beta * pp[u].e[e] - y;
+                    pp[u].e[e] = pn;
+                    acc[3] += (pn != T(0)) ? 1.0 : 0.0;
+                }
+                if constexpr (XNT) st_nt<T, V>(x, i, ox); else st<T, V>(x, i, ox);
+                st<T, V>(r, i, orr);
+                st<T, V>(p, i, pp[u]);
+            }
+        }
+    }
+    emit_partials<4>(acc, ws);
+}
+
+// one workgroup per band, once per iteration: the band's three convolution dots (cp: band bl's `bs` partials of
+// quantity q at q * qs + bl * bst), the four sums of its previous update (when `have_upd`; ws: [4][nb gpb]), then the
+// end of that iteration and the begin of this one
+__global__ void __launch_bounds__(256)
+k_iter_sums_bands(const double* __restrict__ cp, int bs, int qs, int bst, const double* __restrict__ ws, int gpb,
+                  int have_upd, double* __restrict__ S, double mdiv, int predict) {
+    __shared__ double vals[8];
+    const int bl = blockIdx.x, nb = gridDim.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (w < 3) {
+        const double* src = cp + (size_t)w * qs + (size_t)bl * bst;
+        double acc = 0.0;
+        for (int k = lane; k < bs; k += 64) acc += src[k];
+        acc = wave_sum(acc);
+        if (lane == 0) vals[w] = acc;
+    }
+    if (have_upd && w < 4) {
+        const double* src = ws + (size_t)w * nb * gpb + (size_t)bl * gpb;
+        double acc = 0.0;
+        for (int g = lane; g < gpb; g += 64) acc += src[g];
+        acc = wave_sum(acc);
+        if (lane == 0) vals[3 + w] = acc;
+    }
+    __syncthreads();
+    double* Sb = S + (size_t)bl * SB;
+    if (threadIdx.x == 0 && band_live(Sb)) {
+        Sb[S_PAP] = vals[0]; Sb[S_RAP] = vals[1]; Sb[S_APAP] = vals[2];
+        if (have_upd) {
+            Sb[S_RHON] = vals[3]; Sb[S_NUM] = vals[4]; Sb[S_DEN] = vals[5]; Sb[S_ANY] = vals[6];
+            iter_end_dev(Sb, 1);
+        }
+        iter_begin_dev(Sb, mdiv, predict);
+    }
+}
+
+// one workgroup per band: the update's four sums and the end of the iteration (past minit, where the host may look)
+__global__ void __launch_bounds__(256)
+k_iter_end_bands(const double* __restrict__ ws, int gpb, double* __restrict__ S) {
+    __shared__ double vals[4];
+    const int bl = blockIdx.x, nb = gridDim.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double* src = ws + (size_t)w * nb * gpb + (size_t)bl * gpb;
+    double acc = 0.0;
+    for (int g = lane; g < gpb; g += 64) acc += src[g];
+    acc = wave_sum(acc);
+    if (lane == 0) vals[w] = acc;
+    __syncthreads();
+    double* Sb = S + (size_t)bl * SB;
+    if (threadIdx.x == 0 && band_live(Sb)) {
+        Sb[S_RHON] = vals[0]; Sb[S_NUM] = vals[1]; Sb[S_DEN] = vals[2]; Sb[S_ANY] = vals[3];
+        iter_end_dev(Sb, 1);
+    }
+}
+
+// k_final_check per band: the direction the band's last iteration built has not been looked at yet
+__global__ void k_final_check_bands(double* S, int nb) {
+    for (int bl = threadIdx.x; bl < nb; bl += blockDim.x) {
+        double* Sb = S + (size_t)bl * SB;
+        if (Sb[SB_ZERO] == 0.0 && Sb[S_DEAD] == 0.0 && Sb[S_ANY] == 0.0) {
+            Sb[S_DEAD] = 1.0; Sb[S_K] -= 1.0; Sb[S_EPS] = Sb[S_EPSP];
+        }
+    }
+}
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <typename T>
@@ -798,6 +977,172 @@ static int pcg_impl(pfb_conv_plan* plan, int band0, int nb, const void* b, void*
     return PFB_OK;
 }
 
+// ------------------------------------------------------------------ batched per-band driver
+// workgroups per band of the per-band vector kernels: the whole grid stays near one 256-thread workgroup per CU
+// (stream_grid), split evenly over the bands; nb * gpb <= max(nb, RED_MAX_GRID) bounds the partials
+static int band_grid(size_t nvb, int nb) {
+    int g = stream_grid(nvb);
+    const int share = stream_grid((size_t)1 << 40) / nb;
+    if (g > share) g = share;
+    if (g > RED_MAX_GRID / nb) g = RED_MAX_GRID / nb;
+    return g < 1 ? 1 : g;
+}
+static size_t bands_state_bytes(int nb) { return ((size_t)nb * SB * sizeof(double) + 255) & ~(size_t)255; }
+static size_t bands_ws_doubles(int nb) { return 4 * (size_t)(nb > RED_MAX_GRID ? nb : RED_MAX_GRID); }
+
+template <typename T>
+static int pcg_bands_impl(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
+                          const void* beam, double wsum, double sigmainv, double mdiv_d, double tol,
+                          int maxit, int minit, int backtrack, void* work, pfb_pcg_result* res, hipStream_t st) {
+    const size_t nband = (size_t)plan->nx * plan->ny, n = (size_t)nb * nband;
+    const size_t vb = vec_bytes(plan, nb);
+    char* w = (char*)work;
+    T* r = (T*)w;
+    T* p = (T*)(w + vb);
+    T* Ap = (T*)(w + 2 * vb);
+    double* S = (double*)(w + 3 * vb);
+    double* ws = (double*)(w + 3 * vb + bands_state_bytes(nb));
+    T* xs = (T*)x;
+    const T mdiv = (T)mdiv_d;
+    const size_t nS = (size_t)nb * SB;
+    std::vector<double> h(nS);
+    int err;
+
+    memset(res, 0, sizeof(*res) * nb);
+    PFB_HIP_CHECK(hipMemsetAsync(S, 0, sizeof(double) * nS, st));
+    auto fetch = [&]() -> int {
+        PFB_HIP_CHECK(hipMemcpyAsync(h.data(), S, sizeof(double) * nS, hipMemcpyDeviceToHost, st));
+        PFB_HIP_CHECK(hipStreamSynchronize(st));
+        return PFB_OK;
+    };
+    auto any_live = [&](const double* hs) {
+        for (int bl = 0; bl < nb; ++bl)
+            if (hs[(size_t)bl * SB + S_STOP] == 0.0 && hs[(size_t)bl * SB + S_DEAD] == 0.0) return true;
+        return false;
+    };
+
+    // per-band vector geometry: every band starts on a vector boundary when its length is a multiple of V
+    using PL = std::initializer_list<const void*>;
+    const bool vec = can_vec<T>(nband, PL{x, b, r, p, Ap});
+    const int V = vec ? V16<T>::N : 1;
+    const size_t nvb = nband / V;
+    const int gpb = band_grid(nvb, nb);
+
+    // r = A(x0) - b ; y = M r ; p = -y                       pcg.py:71-76, per band
+    err = pfb_psfconv_apply(plan, band0, nb, x, beam, wsum, sigmainv, r, nullptr, nullptr, (void*)st);
+    if (err != PFB_OK) return err;
+    if (vec)
+        hipLaunchKernelGGL((k_pcg_init_bands<T, V16<T>::N>), dim3(nb * gpb), dim3(RED_BLOCK), 0, st, r, (const T*)b, p,
+                           mdiv, nvb, gpb, ws);
+    else
+        hipLaunchKernelGGL((k_pcg_init_bands<T, 1>), dim3(nb * gpb), dim3(RED_BLOCK), 0, st, r, (const T*)b, p, mdiv,
+                           nvb, gpb, ws);
+    hipLaunchKernelGGL(k_init_bands, dim3(nb), dim3(128), 0, st, (const double*)ws, gpb, S, tol, (double)minit,
+                       (double)maxit);
+    PFB_HIP_CHECK(hipGetLastError());
+    if ((err = fetch()) != PFB_OK) return err;
+
+    // the loop of pcg_impl's sync-free driver, with a state block per band: the host only has to look once some band
+    // can stop (k >= minit), and then only at whether any band is still live
+    const bool xnt = n * sizeof(T) >= ((size_t)32 << 20);
+    bool go = (1.0 > tol || 0 < minit) && 0 < maxit && any_live(h.data());
+    bool lookahead = n <= ((size_t)16 << 20);
+    if (const char* la = getenv("PFB_PCG_LOOKAHEAD")) lookahead = atoi(la) != 0;
+    if (lookahead) {
+        if (!plan->pcg_pin) {
+            PFB_HIP_CHECK(hipHostMalloc((void**)&plan->pcg_pin, sizeof(double) * 2 * S_NSCALAR, hipHostMallocDefault));
+            PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[0], hipEventDisableTiming));
+            PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[1], hipEventDisableTiming));
+        }
+        if (plan->pcg_pin_bands_n < nb) {
+            if (plan->pcg_pin_bands) { PFB_HIP_CHECK(hipStreamSynchronize(st)); (void)hipHostFree(plan->pcg_pin_bands); }
+            plan->pcg_pin_bands = nullptr;
+            plan->pcg_pin_bands_n = 0;
+            PFB_HIP_CHECK(hipHostMalloc((void**)&plan->pcg_pin_bands, sizeof(double) * 2 * nS, hipHostMallocDefault));
+            plan->pcg_pin_bands_n = nb;
+        }
+    }
+    const int predict = backtrack == 2 ? 2 : 3;   // beta always comes from rho(alpha)
+    int khost = 0, slot = 0;
+    bool pending_end = false, have_prev = false;
+    // the span [lo, lo + nl) of bands that may still be live: narrowed at every host look, so that bands which have
+    // stopped at either end are no longer convolved (a stopped band between two live ones still is)
+    int lo = 0, nl = nb, gpl = gpb;
+    auto narrow = [&](const double* hs) {
+        int a = 0, z = nb;
+        while (a < z && !(hs[(size_t)a * SB + S_STOP] == 0.0 && hs[(size_t)a * SB + S_DEAD] == 0.0)) ++a;
+        while (z > a && !(hs[(size_t)(z - 1) * SB + S_STOP] == 0.0 && hs[(size_t)(z - 1) * SB + S_DEAD] == 0.0)) --z;
+        if (z > a && (a != lo || z - a != nl)) { lo = a; nl = z - a; gpl = band_grid(nvb, nl); }
+    };
+    while (go) {
+        const size_t off = (size_t)lo * nband;
+        double* Sl = S + (size_t)lo * SB;
+        err = psfconv_apply_partials_bands(plan, band0 + lo, nl, p + off, beam ? (const T*)beam + off : nullptr, wsum,
+                                           sigmainv, Ap + off, p + off, r + off, (void*)st);
+        if (err != PFB_OK) return err;
+        hipLaunchKernelGGL(k_iter_sums_bands, dim3(nl), dim3(256), 0, st, (const double*)plan->partials,
+                           plan->last_band_slots, plan->last_q_stride, plan->last_band_stride, (const double*)ws, gpl,
+                           pending_end ? 1 : 0, Sl, mdiv_d, predict);
+        pending_end = false;
+#define PFB_UPD_BANDS(VV, XN)                                                                                      \
+        hipLaunchKernelGGL((k_pcg_update_dir_bands<T, VV, 2, XN, XN>), dim3(nl * gpl), dim3(RED_BLOCK), 0, st,     \
+                           xs + off, r + off, p + off, (const T*)Ap + off, (const double*)Sl, mdiv, nvb, gpl, ws)
+        if (vec && xnt) PFB_UPD_BANDS(V16<T>::N, true);
+        else if (vec) PFB_UPD_BANDS(V16<T>::N, false);
+        else PFB_UPD_BANDS(1, false);
+#undef PFB_UPD_BANDS
+        if (khost + 1 < minit && khost + 1 < maxit)
+            pending_end = true;        // summed by the next iteration's k_iter_sums_bands (no look, so no narrowing, between)
+        else
+            hipLaunchKernelGGL(k_iter_end_bands, dim3(nl), dim3(256), 0, st, (const double*)ws, gpl, Sl);
+        PFB_HIP_CHECK(hipGetLastError());
+        ++khost;
+        if (khost < minit && khost < maxit) continue;          // no band can stop yet: no need to look
+        if (lookahead && khost < maxit) {
+            // one iteration ahead (pcg_impl): every band evaluates its rule on the device, so the iteration enqueued
+            // behind a band's stop changes nothing in it
+            double* snap = plan->pcg_pin_bands + (size_t)slot * nS;
+            PFB_HIP_CHECK(hipMemcpyAsync(snap, S, sizeof(double) * nS, hipMemcpyDeviceToHost, st));
+            PFB_HIP_CHECK(hipEventRecord(plan->pcg_ev[slot], st));
+            if (have_prev) {
+                PFB_HIP_CHECK(hipEventSynchronize(plan->pcg_ev[slot ^ 1]));
+                const double* hp = plan->pcg_pin_bands + (size_t)(slot ^ 1) * nS;
+                if (!any_live(hp)) go = false;
+                else narrow(hp);          // an older snapshot: a band stopped there is stopped now as well
+            }
+            have_prev = true;
+            slot ^= 1;
+            continue;
+        }
+        if ((err = fetch()) != PFB_OK) return err;
+        go = khost < maxit && any_live(h.data());
+        if (go) narrow(h.data());
+    }
+    hipLaunchKernelGGL(k_final_check_bands, dim3(1), dim3(64), 0, st, S, nb);
+    PFB_HIP_CHECK(hipGetLastError());
+    if (r_out) PFB_HIP_CHECK(hipMemcpyAsync(r_out, r, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    if ((err = fetch()) != PFB_OK) return err;
+    for (int bl = 0; bl < nb; ++bl) {
+        const double* Sb = h.data() + (size_t)bl * SB;
+        pfb_pcg_result& o = res[bl];
+        o.rnorm = Sb[S_RHO];
+        if (Sb[SB_ZERO] != 0.0) {          // "Initial residual is zero": x untouched
+            o.status = PFB_PCG_ZERO_RESIDUAL;
+            o.matvecs = 1;
+            o.eps = 1.0;
+            continue;
+        }
+        const int k = (int)Sb[S_K];
+        const bool dead = Sb[S_DEAD] != 0.0;
+        o.status = dead ? PFB_PCG_BREAKDOWN : (k >= maxit ? PFB_PCG_MAXIT : PFB_PCG_CONVERGED);
+        o.iters = k;
+        o.eps = Sb[S_EPS];
+        o.backtracks = (int)Sb[S_NBTSUM];
+        o.matvecs = 1 + k + (dead ? 1 : 0);
+    }
+    return PFB_OK;
+}
+
 }  // namespace pfb
 
 using namespace pfb;
@@ -850,6 +1195,29 @@ int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x
     return pcg_impl<double>(plan, band0, nb, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit,
                             minit, backtrack, work, allreduce, allreduce_ctx, result,
                             as_stream(stream));
+}
+
+size_t pfb_pcg_bands_work_bytes(const pfb_conv_plan* plan, int nb) {
+    if (!plan || nb <= 0) return 0;
+    return 3 * vec_bytes(plan, nb) + bands_state_bytes(nb) + sizeof(double) * bands_ws_doubles(nb);
+}
+
+int pfb_pcg_solve_bands(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
+                        const void* beam, double wsum, double sigmainv, double mdiv, double tol,
+                        int maxit, int minit, int backtrack, void* work, pfb_pcg_result* results, void* stream) {
+    PFB_REQUIRE(plan && b && x && work && results, PFB_ERR_INVALID, "pcg_solve_bands: null argument");
+    PFB_REQUIRE(band0 >= 0 && nb > 0 && band0 + nb <= plan->nband, PFB_ERR_INVALID,
+                "pcg_solve_bands: band range [%d,%d) outside plan", band0, band0 + nb);
+    PFB_REQUIRE((reinterpret_cast<uintptr_t>(work) & 255u) == 0, PFB_ERR_INVALID,
+                "pcg_solve_bands: work must be 256-byte aligned");
+    PFB_REQUIRE(backtrack != 1, PFB_ERR_UNSUPPORTED,
+                "pcg_solve_bands: backtrack=1 (the exact loop) is not batched; solve band by band with pfb_pcg_solve");
+    PFB_REQUIRE(backtrack == 0 || backtrack == 2, PFB_ERR_INVALID, "pcg_solve_bands: backtrack must be 0 or 2");
+    if (plan->dtype == PFB_F32)
+        return pcg_bands_impl<float>(plan, band0, nb, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
+                                     backtrack, work, results, as_stream(stream));
+    return pcg_bands_impl<double>(plan, band0, nb, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
+                                  backtrack, work, results, as_stream(stream));
 }
 
 }  // extern "C"

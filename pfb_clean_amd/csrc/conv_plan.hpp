@@ -37,6 +37,9 @@ struct pfb_conv_plan {
     int have_psf;
     int partials_per_band;     // fused-dot partial sums emitted per band by row_inv
     int last_npartials;        // slots per quantity the LAST row-inverse launch wrote (k_sum_partials reads these)
+    int last_band_slots;       // per band: band bl's `last_band_slots` partials of quantity q start at
+    int last_q_stride;         //   q * last_q_stride + bl * last_band_stride
+    int last_band_stride;      // (last_band_slots 0: the launch summed across bands -- the whole-cube persistent kernel)
     void* fast_tables;         // pow2 path: per-pass twiddle tables (fftconv_pow2.hip)
     // optional per-stage timing (bench.py roofline): 4 events per apply, up to PROF_MAX applies
     int prof_on, prof_n, prof_tick;   // prof_on = sampling period (every prof_on-th apply is timed)
@@ -45,6 +48,9 @@ struct pfb_conv_plan {
     // iteration j-1 while iteration j is already enqueued (created on first use)
     double* pcg_pin;
     hipEvent_t pcg_ev[2];
+    // batched per-band driver (pfb_pcg_solve_bands): the same snapshots for nb state blocks (grown on demand)
+    double* pcg_pin_bands;
+    int pcg_pin_bands_n;
 };
 
 namespace pfb {
@@ -63,4 +69,8 @@ inline void prof_mark(pfb_conv_plan* p, hipStream_t st, int k) {
 int psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                            double wsum, double sigmainv, void* out, const void* dot_with,
                            const void* dot_with2, void* stream);
+// the same with partials that each belong to ONE band (layout: plan->last_band_slots / _q_stride / _band_stride)
+int psfconv_apply_partials_bands(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
+                                 double wsum, double sigmainv, void* out, const void* dot_with,
+                                 const void* dot_with2, void* stream);
 }  // namespace pfb

@@ -32,7 +32,7 @@ void set_error(const char* fmt, ...) {
 bool pow2_supported(const pfb_conv_plan* p);
 int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
-               hipStream_t st);
+               bool per_band, hipStream_t st);
 int pow2_prepare(pfb_conv_plan* p);
 void pow2_release(pfb_conv_plan* p);
 int pow2_rows_per_wg(const pfb_conv_plan* p);
@@ -266,6 +266,21 @@ k_sum_partials(const double* __restrict__ partials, int n, int nq, double* __res
         for (int k = threadIdx.x; k < n; k += blockDim.x) acc[0] += partials[(size_t)q * n + k];
         block_sum<1>(acc, red);
         if (threadIdx.x == 0) out[q] = acc[0];
+    }
+}
+
+// per band: out[bl * 3 + q] = sum of band bl's `bs` partials of quantity q (at q * qs + bl * bst), one workgroup per
+// band, fixed order => deterministic
+__global__ void __launch_bounds__(256)
+k_sum_partials_bands(const double* __restrict__ partials, int bs, int qs, int bst, double* __restrict__ out) {
+    __shared__ double red[4];
+    const int bl = blockIdx.x;
+    for (int q = 0; q < 3; ++q) {
+        const double* src = partials + (size_t)q * qs + (size_t)bl * bst;
+        double acc[1] = {0.0};
+        for (int k = threadIdx.x; k < bs; k += blockDim.x) acc[0] += src[k];
+        block_sum<1>(acc, red);
+        if (threadIdx.x == 0) out[(size_t)bl * 3 + q] = acc[0];
     }
 }
 
@@ -532,6 +547,7 @@ int pfb_psfconv_plan_destroy(pfb_conv_plan* p) {
         for (int k = 0; k < 4 * PROF_MAX; ++k) (void)hipEventDestroy(p->prof_ev[k]);
         free(p->prof_ev);
     }
+    if (p->pcg_pin_bands) (void)hipHostFree(p->pcg_pin_bands);
     if (p->pcg_pin) {
         (void)hipHostFree(p->pcg_pin);
         (void)hipEventDestroy(p->pcg_ev[0]);
@@ -646,7 +662,7 @@ int pfb_psfhat_regrid(int dtype, const void* psfhat, int nband, int nx, int ny, 
 
 static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                         double wsum, double sigmainv, void* out, const void* dot_with,
-                        const void* dot_with2, double* dots_out, int ndots, void* stream) {
+                        const void* dot_with2, double* dots_out, int ndots, void* stream, bool per_band = false) {
     PFB_REQUIRE(p && x && out, PFB_ERR_INVALID, "apply: null argument");
     PFB_REQUIRE(p->have_psf, PFB_ERR_INVALID, "apply: pfb_psfconv_set_psfhat was never called");
     PFB_REQUIRE(band0 >= 0 && nb > 0 && band0 + nb <= p->nband, PFB_ERR_INVALID,
@@ -659,8 +675,11 @@ static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, cons
     if (wsum > 0) scale /= wsum;
     int rc;
     p->last_npartials = p->partials_per_band * nb;        // the persistent row-inverse kernel lowers it
+    p->last_band_slots = p->partials_per_band;            // slot k of the plain / coverage kernels is band k / ppb's
+    p->last_q_stride = p->partials_per_band * nb;
+    p->last_band_stride = p->partials_per_band;
     if (p->fast)
-        rc = pow2_apply(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st);
+        rc = pow2_apply(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
     else if (p->long_lines) {
         const size_t need = p->dtype == PFB_F32 ? long_apply_ws_bytes<float>(nb, p->nx, p->M, p->P)
                                                 : long_apply_ws_bytes<double>(nb, p->nx, p->M, p->P);
@@ -693,7 +712,11 @@ static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, cons
     else
         rc = apply_generic<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st);
     if (rc != PFB_OK) return rc;
-    if (dot_with && ndots > 0) {           // ndots == 0: the caller sums p->partials itself (PCG driver)
+    if (dot_with && ndots > 0 && per_band) {
+        hipLaunchKernelGGL(k_sum_partials_bands, dim3(nb), dim3(256), 0, st, p->partials, p->last_band_slots,
+                           p->last_q_stride, p->last_band_stride, dots_out);
+        PFB_HIP_CHECK(hipGetLastError());
+    } else if (dot_with && ndots > 0) {    // ndots == 0: the caller sums p->partials itself (PCG driver)
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, p->partials,
                            p->last_npartials, ndots, dots_out);
         PFB_HIP_CHECK(hipGetLastError());
@@ -714,6 +737,13 @@ int pfb_psfconv_apply_dots(pfb_conv_plan* p, int band0, int nb, const void* x, c
     return apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, dots_out, 3, stream);
 }
 
+int pfb_psfconv_apply_dots_bands(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
+                                 double wsum, double sigmainv, void* out, const void* dot_with,
+                                 const void* dot_with2, double* dots_out, void* stream) {
+    PFB_REQUIRE(dot_with && dots_out, PFB_ERR_INVALID, "apply_dots_bands: dot_with and dots_out are required");
+    return apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, dots_out, 3, stream, true);
+}
+
 }  // extern "C"
 
 // internal (cgvec.hip): the convolution with its three fused dots left as per-workgroup partials in
@@ -724,4 +754,11 @@ int pfb::psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void*
                                 const void* dot_with2, void* stream) {
     PFB_REQUIRE(dot_with, PFB_ERR_INVALID, "apply_partials: dot_with is required");
     return apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, nullptr, 0, stream);
+}
+
+int pfb::psfconv_apply_partials_bands(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
+                                      double wsum, double sigmainv, void* out, const void* dot_with,
+                                      const void* dot_with2, void* stream) {
+    PFB_REQUIRE(dot_with, PFB_ERR_INVALID, "apply_partials_bands: dot_with is required");
+    return apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, nullptr, 0, stream, true);
 }

@@ -1509,6 +1509,12 @@ template <typename T, int L> struct InvPE {
     static constexpr int E = (sizeof(T) == 8 && L >= MINL64) ? 16 : RowCfg<T, L, true>::E;
 };
 
+// the per-band variant (PB) of k_row_inv_pow2p exists for every persistent tile but the 4096-point fp32 one (SMT, 16
+// elements per thread): that tile is at the 128-VGPR cap already, and its per-band flush kept 20-136 B of scratch however
+// it was written.  There the launcher runs the whole-cube kernel once per band instead (launch_row_inv).
+template <typename T, int L, int E>
+constexpr bool inv_pb_ok() { return !(sizeof(T) == 4 && InvP<T, L, E>::SMT); }
+
 // strength-reduced addressing of the strided pieces (see fwdp_post_lin): the blocks of a thread are BSTEP apart, so the
 // load address is a workgroup-uniform base (band, parity, step) + a 32-bit per-thread offset that never changes, and
 // the padded LDS index of the scatter is one base + compile-time offsets.  Regular whenever BSTEP divides the odd-bin
@@ -1639,7 +1645,11 @@ __device__ __forceinline__ void inv_build(const cplx<T>* lds, const cplx<T>* ltm
 // The first pass's slice of each (odd-bin pieces / dot_with2 rows) is requested right behind the scatter instead, so that
 // something is in flight across the barrier and inv_build: 0.6075 -> 0.5999 ms per 8 x 4096^2 fp32, 0.7415 -> 0.7216 per
 // 4 x 4096^2 fp64 (requesting more there measured no better: profiles/r03_ab_inv_ablation.md).
-template <typename T, int L, int E, int MODE, bool BEAM>
+// PB (per band, MODE >= 1): the inner products are flushed whenever the next tile lies in another band, so that every
+// partial belongs to one band: partials[(q * nbands + band) * grid + workgroup], zero for a band the workgroup never
+// visits.  The tiles of trip s are [s grid, (s + 1) grid) under the rotated map, so a workgroup's band never decreases
+// along its trips: one flush per band boundary it crosses.  PB = false compiles to the whole-cube kernel unchanged.
+template <typename T, int L, int E, int MODE, bool BEAM, bool PB = false>
 __global__ void __launch_bounds__((InvP<T, L, E>::NT), (InvP<T, L, E>::NT / 256 * InvP<T, L, E>::WG_PER_CU))
 k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 const cplx<T>* __restrict__ ptw, const T* __restrict__ x, const T* __restrict__ beam,
@@ -1684,6 +1694,12 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
     if constexpr (NXTK || NXEK)
         inv_issue<T, L, E, 0>(Tw + (size_t)(band0 + bl) * d.T_band, d.nx, i0, threadIdx.x % G, threadIdx.x / G, y);
     double acc[3] = {0.0, 0.0, 0.0};
+    if constexpr (PB && MODE >= 1) {      // every slot of this workgroup starts at zero: a band it never visits reads 0
+        if (threadIdx.x == 0) {           // (the same thread writes the visited bands' sums later: program order)
+            const int n = 3 * (ntiles / tiles_per_band);
+            for (int k = 0; k < n; ++k) partials[(size_t)k * gridDim.x + blockIdx.x] = 0.0;
+        }
+    }
     // deferred stores (fp32): a tile's output rows stay in registers and are written two per pass of the NEXT
     // tile's even-bin transform instead of in one burst behind the epilogue
     V2 ov[P::PARK ? E : 1];
@@ -1879,6 +1895,16 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             const int g = tid / TPB, t = tid % TPB;
             oprev = reinterpret_cast<V2*>(out + ((size_t)bl * d.nx + (i0 + g)) * d.ny) + t;
         }
+        if constexpr (PB && MODE >= 1) {
+            if (vbn == vb || bln != bl) {     // band bl is done for this workgroup (the last tile is not repeated)
+                block_sum<3>(acc, red);
+                if (threadIdx.x == 0) {
+                    const size_t np = (size_t)(ntiles / tiles_per_band) * gridDim.x, k = (size_t)bl * gridDim.x + blockIdx.x;
+                    partials[k] = acc[0]; partials[np + k] = acc[1]; partials[2 * np + k] = acc[2];
+                }
+                acc[0] = 0.0; acc[1] = 0.0; acc[2] = 0.0;
+            }
+        }
         if (vbn == vb) break;
         vb = vbn; bl = bln; i0 = i0n;
     }
@@ -1888,7 +1914,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             for (int j = 0; j < E; ++j) oprev[TPB * j] = ov[j];
         }
     }
-    if constexpr (MODE >= 1) {
+    if constexpr (!PB && MODE >= 1) {
         __syncthreads();
         block_sum<3>(acc, red);
         if (threadIdx.x == 0) {           // one slot per WORKGROUP (launcher: last_npartials = grid)
@@ -1981,6 +2007,12 @@ static int set_invp_attr() {
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
         PFB_INVATTR(0, false); PFB_INVATTR(1, false); PFB_INVATTR(2, false);
         PFB_INVATTR(0, true);  PFB_INVATTR(1, true);  PFB_INVATTR(2, true);
+        if constexpr (inv_pb_ok<T, L, E>()) {
+            PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, 2, false, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, 2, true, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        }
 #undef PFB_INVATTR
     }
     return PFB_OK;
@@ -2354,7 +2386,7 @@ static void launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, i
 template <typename T, int L>
 static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x,
                            const void* beam, double scale, double sigmainv, void* out,
-                           const void* dot_with, const void* dot_with2, hipStream_t st) {
+                           const void* dot_with, const void* dot_with2, bool per_band, hipStream_t st) {
     constexpr int E = RowCfg<T, L, true>::E;
     using F = RegFft<T, L, E, RowCfg<T, L, true>::WAVE>;
     constexpr int G = row_groups<T, L, E, RowCfg<T, L, true>::GMAX>();
@@ -2365,23 +2397,62 @@ static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, in
         const bool plain_dots = !dot_with || (dot_with == x);
         if (plain_dots && !(dot_with2 && !dot_with)) {
             using IP = InvP<T, L, EP>;
-            const int tiles_per_band = p->nx / IP::G, ntiles = tiles_per_band * nb;
-            const int grid = ntiles < IP::WG_PER_CU * ft->num_cu ? ntiles : IP::WG_PER_CU * ft->num_cu;
             const long double a = 6.283185307179586476925286766559005768L / (2.0L * (long double)p->ny);
             const cplx<T> wq1((T)cosl(a), (T)(-sinl(a)));
-#define PFB_INVP2(MODE, BM)                                                                             \
-            hipLaunchKernelGGL((k_row_inv_pow2p<T, L, EP, MODE, BM>), dim3(grid), dim3(IP::NT), IP::LDS, st, \
-                               (const cplx<T>*)p->T, (const cplx<T>*)ft->twM,                           \
-                               (const cplx<T>*)ft->ptw_row_inv_p, (const T*)x, (const T*)beam,          \
-                               (const T*)dot_with2, (T*)out, p->partials, d, band0, tiles_per_band,     \
-                               ntiles, (T)scale, (T)sigmainv, wq1)
+#define PFB_INVP3(MODE, BM, PBV, B0, NB, GRID, OFF, PART)                                                        \
+            hipLaunchKernelGGL((k_row_inv_pow2p<T, L, EP, MODE, BM, PBV>), dim3(GRID), dim3(IP::NT), IP::LDS, st,  \
+                               (const cplx<T>*)p->T, (const cplx<T>*)ft->twM,                                    \
+                               (const cplx<T>*)ft->ptw_row_inv_p, (const T*)x + (OFF),                           \
+                               beam ? (const T*)beam + (OFF) : nullptr,                                          \
+                               dot_with2 ? (const T*)dot_with2 + (OFF) : nullptr, (T*)out + (OFF), (PART), d,    \
+                               (B0), p->nx / IP::G, p->nx / IP::G * (NB), (T)scale, (T)sigmainv, wq1)
+#define PFB_INVP2(MODE, BM) PFB_INVP3(MODE, BM, false, band0, nb, grid, 0, p->partials)
 #define PFB_INVP(MODE) do { if (beam) PFB_INVP2(MODE, true); else PFB_INVP2(MODE, false); } while (0)
+            const int tiles_per_band = p->nx / IP::G, ntiles = tiles_per_band * nb;
+            int grid = ntiles < IP::WG_PER_CU * ft->num_cu ? ntiles : IP::WG_PER_CU * ft->num_cu;
+            if (per_band && dot_with) {
+                if constexpr (inv_pb_ok<T, L, EP>()) {
+                    if (dot_with2) {              // one launch, partials [3][nb][grid]
+                        if ((size_t)grid * nb > (size_t)p->nx * p->nband) grid = p->nx * p->nband / nb;   // partials: nx x nband
+                        if (beam) PFB_INVP3(2, true, true, band0, nb, grid, 0, p->partials);
+                        else PFB_INVP3(2, false, true, band0, nb, grid, 0, p->partials);
+                        p->last_npartials = grid * nb;
+                        p->last_band_slots = grid;
+                        p->last_q_stride = grid * nb;
+                        p->last_band_stride = grid;
+                        return;
+                    }
+                }
+                // the whole-cube kernel once per band (the same launches a band-by-band solve makes): band bl's
+                // partials land at [bl][3][grid1]
+                const int grid1 = tiles_per_band < IP::WG_PER_CU * ft->num_cu ? tiles_per_band : IP::WG_PER_CU * ft->num_cu;
+                const size_t bandel = (size_t)p->nx * p->ny;
+                for (int bl = 0; bl < nb; ++bl) {
+                    double* part = p->partials + (size_t)bl * 3 * grid1;
+                    if (dot_with2) {
+                        if (beam) PFB_INVP3(2, true, false, band0 + bl, 1, grid1, bl * bandel, part);
+                        else PFB_INVP3(2, false, false, band0 + bl, 1, grid1, bl * bandel, part);
+                    } else {
+                        if (beam) PFB_INVP3(1, true, false, band0 + bl, 1, grid1, bl * bandel, part);
+                        else PFB_INVP3(1, false, false, band0 + bl, 1, grid1, bl * bandel, part);
+                    }
+                }
+                p->last_npartials = grid1 * nb;
+                p->last_band_slots = grid1;
+                p->last_q_stride = grid1;
+                p->last_band_stride = 3 * grid1;
+                return;
+            }
             p->last_npartials = grid;
+            p->last_band_slots = nb == 1 ? grid : 0;
+            p->last_q_stride = grid;
+            p->last_band_stride = grid;
             if (!dot_with) PFB_INVP(0);
             else if (!dot_with2) PFB_INVP(1);
             else PFB_INVP(2);
 #undef PFB_INVP
 #undef PFB_INVP2
+#undef PFB_INVP3
             return;
         }
     }
@@ -2394,7 +2465,8 @@ static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, in
 
 template <typename T>
 static int apply_t(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam, double scale,
-                   double sigmainv, void* out, const void* dot_with, const void* dot_with2, hipStream_t st) {
+                   double sigmainv, void* out, const void* dot_with, const void* dot_with2, bool per_band,
+                   hipStream_t st) {
     const FastTables* ft = (const FastTables*)p->fast_tables;
     const int H = p->nx, L = p->ny / 2;
     prof_mark(p, st, 0);
@@ -2408,7 +2480,7 @@ static int apply_t(pfb_conv_plan* p, int band0, int nb, const void* x, const voi
     if (int rc = pow2_col_launch(p, ft, band0, nb, st); rc != PFB_OK) return rc;
     prof_mark(p, st, 2);
     switch (L) {
-#define X(NN) case NN: launch_row_inv<T, NN>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st); break;
+#define X(NN) case NN: launch_row_inv<T, NN>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st); break;
         PFB_POW2_SIZES(X)
 #undef X
         default: break;
@@ -2419,9 +2491,10 @@ static int apply_t(pfb_conv_plan* p, int band0, int nb, const void* x, const voi
 }
 
 int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam, double scale,
-               double sigmainv, void* out, const void* dot_with, const void* dot_with2, hipStream_t st) {
-    return p->dtype == PFB_F32 ? apply_t<float>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st)
-                               : apply_t<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st);
+               double sigmainv, void* out, const void* dot_with, const void* dot_with2, bool per_band, hipStream_t st) {
+    return p->dtype == PFB_F32
+        ? apply_t<float>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st)
+        : apply_t<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
 }
 #endif  // PFB_POW2_REST
 

@@ -5,6 +5,8 @@ Preconditioned conjugate gradients on MI355X -- drop-in for pfb/opt/pcg.py.
         report_freq=10, backtrack=True, return_resid=False)          pcg.py:53-136
     pcg_psf(psfhat, b, x0, beam, lastsize, nthreads, sigmainv, cgopts, compute=True)
                                                                       pcg.py:243-360
+    pcg_fused_bands(A, b, x0, mdiv, tol, maxit, minit, backtrack, return_resid)
+                                                       every band its own PCG, one batched solve
 
 Two execution paths with identical semantics (residual r = A x - b, stopping rule
 `(eps > tol or k < minit) and k < maxit`, backtracking without extra matvecs,
@@ -116,13 +118,15 @@ class _Work:
     _cache = {}
 
     @classmethod
-    def get(cls, plan, nb):
+    def get(cls, plan, nb, bands=False):
         # per host thread: the reference may drive per-band solves from several dask threads
         # (pcg.py:346-356).  Solves on ONE plan are serialised by plan.lock (the plan's spectrum workspace and
         # dot partials are single-owner); the vectors of a solve still live in a per-thread scratch so that a
-        # thread's result buffers are not overwritten by the next thread's solve
-        key = (id(plan), nb, _dev.stream(), threading.get_ident())
-        nbytes = _lib.load().pfb_pcg_work_bytes(plan.handle, nb)
+        # thread's result buffers are not overwritten by the next thread's solve.  bands: the batched solver's
+        # layout (pfb_pcg_bands_work_bytes)
+        key = (id(plan), nb, bands, _dev.stream(), threading.get_ident())
+        lib = _lib.load()
+        nbytes = (lib.pfb_pcg_bands_work_bytes if bands else lib.pfb_pcg_work_bytes)(plan.handle, nb)
         w = cls._cache.get(key)
         if w is None or w.numel() != nbytes or w.device != plan.device:
             if len(cls._cache) > 16:
@@ -197,6 +201,52 @@ def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack
         x = x[0]
         r = None if r is None else r[0]
     return x, r, res
+
+
+def pcg_fused_bands(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack=True,
+                    return_resid=False):
+    """Run pfb_pcg_solve_bands: every band of A (a HessianPsf over nb bands) is its own PCG, all bands in one
+    batched device solve -- pcg_psf's semantics (pcg.py:243-360).  b, x0: GPU tensors (nb, nx, ny).  Returns
+    (x, r|None, [PcgResult] * nb); a band with PFB_PCG_ZERO_RESIDUAL keeps x = x0.  backtrack='exact' (or
+    PFB_PCG_EXACT_BACKTRACK=1) has no batched form: the library raises PfbHipError (unsupported)."""
+    lib = _lib.load()
+    plan = A.plan
+    b3 = b.contiguous()
+    if b3.ndim != 3:
+        raise ValueError("pcg_fused_bands expects (nb, nx, ny) arrays")
+    nb = b3.shape[0]
+    if nb != A.nb:
+        raise ValueError(f"b has {nb} bands, operator has {A.nb}")
+    if b3.dtype != plan.rdtype:
+        raise TypeError(f"b is {b3.dtype}, operator is {plan.rdtype}")
+    x = torch.zeros_like(b3) if x0 is None else x0.contiguous().clone()
+    beam = A.beam
+    if plan.embed is not None:       # zero-padded domain with a beam that is zero outside the image (pcg_fused)
+        b3, x = plan._pad(b3, nb), plan._pad(x, nb)
+        beam = plan._pad(torch.ones((nb, plan.nx, plan.ny), dtype=plan.rdtype, device=b3.device)
+                         if beam is None else beam, nb)
+    r = torch.empty_like(b3) if return_resid else None
+    work = _Work.get(plan, nb, bands=True)
+    res = (_lib.PcgResult * nb)()
+    with plan.lock:
+        plan._enter_stream()
+        _lib.check(lib.pfb_pcg_solve_bands(plan.handle, A.band0, nb, _dev.ptr(b3), _dev.ptr(x), _dev.ptr(r),
+                                           _dev.ptr(beam), A.wsum if A.wsum is not None else 0.0, A.sigmainv,
+                                           float(mdiv), float(tol), int(maxit), int(minit),
+                                           _backtrack_mode(backtrack), _dev.ptr(work), res, _dev.stream()))
+    if plan.embed is not None:
+        x = x[:, :plan.nx, :plan.ny].contiguous()
+        r = None if r is None else r[:, :plan.nx, :plan.ny].contiguous()
+    return x, r, list(res)
+
+
+def _bands_batched(plan):
+    """Whether pcg_psf runs its bands as one batched solve on this plan.  Not on the 4096-point fp32 rows (plan ny = 8192:
+    8192-pixel images and, embedded, every fp32 image of 4100-8192 pixels): that row tile has no per-band persistent
+    inverse kernel, the batched solve launches the whole-cube one once per band there, and measured 2-3 % slower than
+    the band loop (2 x 8192^2: 153.2 vs 148.8 ms, 2 x 6000^2: 162.5 vs 159.2 ms for 50 iterations)."""
+    ny = plan.embed[1] if plan.embed is not None else plan.ny
+    return not (plan.fast_path and plan.rdtype == torch.float32 and ny == 8192)
 
 
 def _report(res_status, k, eps, verbosity):
@@ -441,9 +491,12 @@ def cg(A, b, x0=None, tol=1e-5, maxit=500, verbosity=1, report_freq=10):
 def pcg_psf(psfhat, b, x0, beam, lastsize, nthreads, sigmainv, cgopts, compute=True):
     """pfb/opt/pcg.py:310-360 (+ _pcg_psf_impl :243-291): independent PCG per band with
     A = _hessian_psf_slice(psfhat[k], beam[k], sigmainv) and M = x/sigmainv when
-    sigmainv > 0.  The reference's dask blockwise-over-bands becomes a loop of fused
-    device solves on one plan (bands are independent: shard them over GPUs with
-    pfb_clean_amd.dist.shard_bands for multi-GPU)."""
+    sigmainv > 0.  The reference's dask blockwise-over-bands becomes ONE batched device solve
+    on one plan (pcg_fused_bands: every band keeps its own step lengths and stopping rule);
+    backtrack='exact' (or PFB_PCG_EXACT_BACKTRACK=1) has no batched form, and fp32 plans of
+    8192-pixel rows are faster band by band (_bands_batched): both run the bands one after
+    another through pcg_fused.  Bands are independent: shard them over GPUs with
+    pfb_clean_amd.dist.shard_bands for multi-GPU."""
     bd = _dev.to_dev(b)
     nband, nx, ny = bd.shape
     if psfhat.shape[0] != nband:
@@ -465,6 +518,18 @@ def pcg_psf(psfhat, b, x0, beam, lastsize, nthreads, sigmainv, cgopts, compute=T
     verbosity = opts.pop('verbosity', 1)
     opts.pop('report_freq', None)
     mdiv = sigmainv if sigmainv > 0 else 0.0
+    if _backtrack_mode(opts.get('backtrack', True)) != 1 and _bands_batched(plan):
+        A = HessianPsf(plan, nx, ny, lastsize, beam=beamd, sigmainv=sigmainv, band0=0, nb=nband)
+        x, _, results = pcg_fused_bands(A, bd, x0d, mdiv=mdiv, **opts)
+        for k, res in enumerate(results):
+            status = _lib.PCG_STATUS[res.status]
+            if status == 'zero-residual':
+                _log("Initial residual is zero", verbosity)
+                model[k] = x0d[k]
+            else:
+                _report(status, res.iters, res.eps, verbosity)
+                model[k] = x[k]
+        return _dev.host_like(model, b)
     for k in range(nband):
         A = HessianPsf(plan, nx, ny, lastsize, beam=None if beamd is None else beamd[k:k + 1],
                        sigmainv=sigmainv, band0=k, nb=1)
