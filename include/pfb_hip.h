@@ -389,6 +389,47 @@ int pfb_hogbom(int dtype, void* IR, const void* psf, void* model, const void* ws
 int pfb_freqmul(int dtype, const void* A, const void* x, void* out, int nband, size_t npix,
                 const void* pre, const void* post, void* stream);
 
+/* ------------------------------------------------------- Gaussian restoring beam
+ * What pfb/utils/misc.py:186-238 (convolve2gaussres) and pfb/utils/restoration.py:6-57 (restore_image) need besides
+ * the PSF convolution above: the convolution kernel.  Plan-time work, all of it in fp64 whatever the image dtype
+ * (Gaussian2D returns float64, the kernel spectra are complex128); the truncation test and the quadratic form are
+ * evaluated without FMA contraction, so the zero pattern is numpy's.  Asynchronous on `stream`.
+ *
+ * A parameter set is 4 doubles [a00, a01, a11, extent]: the entries of R^T A R (misc.py:114-120) and
+ * (nsigma * Smaj)^2 (misc.py:123); `pars` is a DEVICE array of nset of them.  The value at (x, y) is
+ * exp(-2 sqrt(2 ln 2) (a00 x^2 + 2 a01 x y + a11 y^2)) where x^2 + y^2 <= extent, else 0. */
+
+/* Gaussian2D, misc.py:109-138, for nset parameter sets on the same npix coordinates xx, yy in one launch group.
+ * out: (nset, npix) doubles, or NULL when only the sums are wanted; sums: nset device doubles (or NULL) that receive
+ * the sum of the UNnormalised values, accumulated in a fixed order; normalise != 0 divides out[s] by sums[s]
+ * (misc.py:135-136; needs out and sums).  ws: PFB_REDUCE_WS_DOUBLES doubles of scratch. */
+int pfb_gauss2d(const double* xx, const double* yy, size_t npix, const double* pars, int nset, int normalise,
+                double* out, double* sums, double* ws, void* stream);
+
+/* The zero-padded kernel of misc.py:210-211, np.pad(Gaussian2D(xx, yy, .), ((npad_xl, .), (npad_yl, .))) on the
+ * (nx_pad, ny_pad) grid, evaluated straight onto the grid a convolution plan wants, without ever being stored:
+ *   out[s, nx_out/2 + dx, ny_out/2 + dy] = kpad_s[(nx_pad/2 + dx) mod nx_pad, (ny_pad/2 + dy) mod ny_pad]
+ * xx, yy: (nx, ny) coordinates.  norm: NULL, or nset doubles the values are divided by (the sums of pfb_gauss2d).
+ *   clip != 0: only |dx| < nx, |dy| < ny are kept, the offsets a convolution of an (nx, ny) image touches, zero
+ *              elsewhere; needs nx_out >= 2 nx - 1, ny_out >= 2 ny - 1.  The circular convolution of misc.py:212-236
+ *              on (nx_pad, ny_pad), wrap-around included, then equals the top-left convolution psf.py:11-56 with
+ *              this kernel on (nx_out, ny_out) -- the image-space twin of pfb_psfhat_regrid;
+ *   clip == 0: (nx_out, ny_out) = (nx_pad, ny_pad): the padded kernel itself.
+ * out: (nset, nx_out, ny_out) reals of `dtype`, peak at (nx_out/2, ny_out/2) as pfb_psfconv_set_psf expects. */
+int pfb_gauss_kernel_grid(int dtype, const double* xx, const double* yy, int nx, int ny, int npad_xl, int npad_yl,
+                          int nx_pad, int ny_pad, const double* pars, const double* norm, int nset, int clip,
+                          int nx_out, int ny_out, void* out, void* stream);
+
+/* The same gather (clipped) from an array: kern is (nband, nx_pad, ny_pad) doubles, periodic, its centre at index
+ * (cx, cy) -- (0, 0) for the c2r of a kernel spectrum, (nx_pad/2, ny_pad/2) for a padded kernel. */
+int pfb_kernel_gather(int dtype, const double* kern, int nband, int nx, int ny, int nx_pad, int ny_pad, int cx, int cy,
+                      int nx_out, int ny_out, void* out, void* stream);
+
+/* misc.py:229-231: out[b, i] = |den[b, i]| > 0 ? num[i] / den[b, i] : 0 over n complex128 values per band, num
+ * shared by the bands.  The test is exactly |den| > 0, not a threshold: where the initial kernel's spectrum has
+ * decayed to rounding noise the quotient is noise over noise, in the reference as here. */
+int pfb_kernhat_ratio(const void* num, const void* den, int nband, size_t n, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,10 @@ SIGNATURES = {
     'pfb_prox_21m': (_i, [_i, _vp, _vp, _vp, _d, _d, _i, _sz, _vp]),
     'pfb_pd_primal_update': (_i, [_i, _vp, _vp, _vp, _d, _i, _i, _sz, _vp, _vp, _vp, _vp]),
     'pfb_pd_primal_update2': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _d, _i, _i, _sz, _vp, _vp, _vp, _vp]),
+    'pfb_gauss2d': (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'pfb_gauss_kernel_grid': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'pfb_kernel_gather': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'pfb_kernhat_ratio': (_i, [_vp, _vp, _i, _sz, _vp, _vp]),
 }
 
 _lib = None
