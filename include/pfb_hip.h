@@ -222,7 +222,12 @@ typedef struct {
  * PFB_PCG_ZERO_RESIDUAL it is left untouched = x0, as the reference returns x0).
  * r_out: optional (nb,nx,ny) residual A x - b on exit (return_resid=True).
  * work: device scratch of pfb_pcg_work_bytes() bytes.
- * Synchronises `stream` (reads scalars back once per iteration). */
+ * pfb_pcg_solve and pfb_pcg_solve_bands below are ONE driver and one set of kernels: a solve works on systems --
+ * contiguous runs of bands that share a block of device-resident scalars -- and this entry point is the solve with a
+ * single system that spans all nb bands (and, alone, the all-reduce hook and backtrack = 1).  backtrack 0 and 2 read
+ * scalars back only once the stopping rule can fire (k >= minit); backtrack = 1 keeps the host-driven loop (scalars
+ * read back every iteration).  x and r alternate between the caller's arrays and two copies in `work`.
+ * Synchronises `stream` before it returns. */
 size_t pfb_pcg_work_bytes(const pfb_conv_plan* plan, int nb);
 int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb,
                   const void* b, void* x, void* r_out,
@@ -234,11 +239,11 @@ int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb,
 /* ------------------------------------------------------------ batched per-band PCG
  * pcg_psf (pfb/opt/pcg.py:243-360): every band of [band0, band0+nb) is its OWN system, solved as in
  * pfb_pcg_solve with nb = 1 -- its own step lengths, backtracking, stopping rule and exit status -- but all
- * bands in one solve: one convolution launch group per iteration over the bands still active, per-band
- * scalars on the device, and the host looks only once some band can stop (k >= minit), and then only at
- * whether any band is still active.  Band bl's result equals pfb_pcg_solve's on that band alone up to the
- * order of the fp64 reductions (every band's convolution output is bit-identical to that solve's, except on the
- * plain-kernel paths, which both share).
+ * bands in one solve (pfb_pcg_solve's driver with nb systems instead of one): one convolution launch group per
+ * iteration over the bands still active, per-band scalars on the device, and the host looks only once some band
+ * can stop (k >= minit), and then only at whether any band is still active.  Band bl's result equals
+ * pfb_pcg_solve's on that band alone up to the order of the fp64 reductions (every band's convolution output is
+ * bit-identical to that solve's, except on the plain-kernel paths, which both share).
  *   - a band whose initial residual is zero keeps x = x0 and gets PFB_PCG_ZERO_RESIDUAL; the others solve;
  *   - breakdown (all-zero direction) ends that band before k += 1, as pcg.py:106-107;
  *   - once a band has stopped, its x and r are never written again (iterations the host enqueued ahead of
@@ -250,7 +255,7 @@ int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb,
  * between two live ones is still convolved (its result is discarded), so bands that need very different
  * iteration counts can cost more convolution work than a band-by-band loop.
  * Memory: work holds r, p and Ap of ALL nb bands at once (3 nb nx ny elements + per-band state), where a
- * band-by-band loop of pfb_pcg_solve holds 5 vectors of one band; x is updated in place.
+ * band-by-band loop of pfb_pcg_solve holds 5 vectors of one band; here x and r are updated in place.
  * results: nb entries.  Synchronises `stream`. */
 size_t pfb_pcg_bands_work_bytes(const pfb_conv_plan* plan, int nb);
 int pfb_pcg_solve_bands(pfb_conv_plan* plan, int band0, int nb,

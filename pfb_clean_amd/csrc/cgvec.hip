@@ -2,9 +2,10 @@
 //
 // Replaces the ~12 numpy passes per iteration of pfb/opt/pcg.py:86-122 and the
 // serial numba norm_diff (pfb/utils/misc.py:1316-1351) by three HBM-bound kernels:
-//   k_pcg_init    r = A x0 - b ; y = M r ; p = -y           + <r,y>, any(y)
-//   k_pcg_update  x' = x + a p ; r' = r + a Ap ; y' = M r'   + <r',y'>, |x'-x|^2, |x'|^2
-//   k_pcg_dir     p = beta p - M r'                          + any(p)
+//   k_pcg_init        r = A x0 - b ; y = M r ; p = -y           + <r,y>, any(y)
+//   k_pcg_update      x' = x + a p ; r' = r + a Ap ; y' = M r'   + <r',y'>, |x'-x|^2, |x'|^2
+//   k_pcg_dir         p = beta p - M r'                          + any(p)
+//   k_pcg_update_dir  the last two in one pass (the sync-free driver; the two above: the exact backtracking loop)
 // All inner products accumulate in fp64 (wave64 __shfl_down -> LDS -> one partial per
 // workgroup -> single-workgroup final sum in a fixed order), scalars stay in device
 // memory (alpha, beta are read by the kernels from there), the p.Ap product comes
@@ -15,6 +16,7 @@
 #include <unistd.h>
 #include <cstring>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 namespace pfb {
@@ -111,19 +113,6 @@ k_final_sum(const double* __restrict__ ws, int G, int nq, double* __restrict__ o
     }
 }
 
-// the fused update's four sums in one launch: wave q sums quantity q (fixed order ->
-// deterministic) and writes out[dst[q]] -- [r'.y', |x'-x|^2, |x'|^2] go to S_RHON.., count(p') to S_ANY
-struct Dst4 { int d[4]; };
-__global__ void __launch_bounds__(256)
-k_final_sum_waves(const double* __restrict__ ws, int G, int nq, double* __restrict__ out, Dst4 dst) {
-    const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (q >= nq) return;
-    double acc = 0.0;
-    for (int g = lane; g < G; g += 64) acc += ws[(size_t)q * G + g];
-    acc = wave_sum(acc);
-    if (lane == 0) out[dst.d[q]] = acc;
-}
-
 template <typename T, int V>
 __global__ void __launch_bounds__(RED_BLOCK)
 k_dot(const T* __restrict__ a, const T* __restrict__ b, size_t nvec, double* __restrict__ ws) {
@@ -180,16 +169,24 @@ k_axpby(T a, const T* __restrict__ x, T b, T* __restrict__ y, size_t nvec) {
     }
 }
 
+// ------------------------------------------------------------------ the fused solver's kernels, by SYSTEM
+// A system (pcg_state.hpp) is a contiguous run of bands solved as one PCG: the whole cube (pfb_pcg_solve, one system) or
+// one band (pfb_pcg_solve_bands, a system per band).  System s has `nvs` vectors at offset s * nvs, its state block
+// S + s * SB and `gps` workgroups of its own in the vector kernels (workgroup w works on system w / gps only), so every
+// partial sum belongs to one system: ws[q * (nsys gps) + s * gps + g].  The bookkeeping kernels run one workgroup per
+// system and sum that system's partials in a fixed order.
+
 // M(r) = r / mdiv when mdiv > 0 (pcg.py:264-267: M = x / sigmainv), identity otherwise.
-// r holds A(x0) on entry.  r = r - b ; y = M r ; p = -y ; sums: <r,y>, count(y != 0)
+// r holds A(x0) on entry.  r = r - b ; y = M r ; p = -y ; sums per system: <r,y>, count(y != 0)
 template <typename T, int V>
 __global__ void __launch_bounds__(RED_BLOCK)
-k_pcg_init(T* __restrict__ r, const T* __restrict__ b, T* __restrict__ p, T mdiv, size_t nvec,
+k_pcg_init(T* __restrict__ r, const T* __restrict__ b, T* __restrict__ p, T mdiv, size_t nvs, int gps,
            double* __restrict__ ws) {
+    const int s = blockIdx.x / gps, g = blockIdx.x - s * gps;
+    const size_t off = (size_t)s * nvs;
     double acc[2] = {0.0, 0.0};
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-         i += (size_t)gridDim.x * blockDim.x) {
-        Pack<T, V> pr = ld<T, V>(r, i), pb = ld<T, V>(b, i), pp;
+    for (size_t i = (size_t)g * blockDim.x + threadIdx.x; i < nvs; i += (size_t)gps * blockDim.x) {
+        Pack<T, V> pr = ld<T, V>(r, off + i), pb = ld<T, V>(b, off + i), pp;
 #pragma unroll
         for (int e = 0; e < V; ++e) {
             const T rr = pr.e[e] - pb.e[e];
@@ -199,10 +196,34 @@ k_pcg_init(T* __restrict__ r, const T* __restrict__ b, T* __restrict__ p, T mdiv
             acc[0] += (double)rr * (double)y;
             acc[1] += (y != T(0)) ? 1.0 : 0.0;
         }
-        st<T, V>(r, i, pr);
-        st<T, V>(p, i, pp);
+        st<T, V>(r, off + i, pr);
+        st<T, V>(p, off + i, pp);
     }
     emit_partials<2>(acc, ws);
+}
+
+// one workgroup per system.  `sum`: S_RHON = <r,y>, S_NUM = count(y != 0) from k_pcg_init's partials (k_final_sum's
+// order).  `place` (after the all-reduce of those two, when there is one): the rule's parameters and the start values;
+// a system with a zero initial residual is marked S_ZERO + S_STOP, so that no later kernel touches it
+__global__ void __launch_bounds__(RED_BLOCK)
+k_init_state(const double* __restrict__ ws, int gps, double* __restrict__ S, double tol, double minit, double maxit,
+             int sum, int place) {
+    __shared__ double red[RED_BLOCK / 64];
+    double* Sb = S + (size_t)blockIdx.x * SB;
+    for (int q = 0; sum && q < 2; ++q) {
+        const double* src = ws + ((size_t)q * gridDim.x + blockIdx.x) * gps;
+        double acc[1] = {0.0};
+        for (int g = threadIdx.x; g < gps; g += blockDim.x) acc[0] += src[g];
+        block_sum<1>(acc, red);
+        if (threadIdx.x == 0) Sb[S_RHON + q] = acc[0];
+    }
+    if (place && threadIdx.x == 0) {
+        Sb[S_TOL] = tol; Sb[S_MINIT] = minit; Sb[S_MAXIT] = maxit;
+        Sb[S_RHO] = Sb[S_RHON];
+        Sb[S_ANY] = Sb[S_NUM];                 // count(y != 0) = count(p != 0) for p = -y
+        Sb[S_EPS] = 1.0; Sb[S_EPSP] = 1.0;
+        if (Sb[S_NUM] == 0.0) { Sb[S_ZERO] = 1.0; Sb[S_STOP] = 1.0; }
+    }
 }
 
 // x' = x + a p ; r' = r + a Ap ; y' = M r' ; sums: <r',y'>, |x'-x|^2, |x'|^2
@@ -266,234 +287,40 @@ k_pcg_dir(T* __restrict__ p, const T* __restrict__ r, const double* __restrict__
     emit_partials<1>(acc, ws);
 }
 
-// update + direction in ONE pass (7 instead of 6 + 3 vector streams): possible because the
+// update + direction in ONE pass (7 vector streams instead of 6 + 3): possible because the
 // predictive line search already knows rnorm_next = rho(alpha) before the vectors are touched,
 // so beta = rho(alpha)/rho is available up front (the reference forms beta from the recomputed
 // <r',y'>; the two differ by rounding only -- the recomputed value is still what the NEXT
-// iteration uses as rnorm).  sums: <r',y'>, |x'-x|^2, |x'|^2, count(p' != 0)
+// iteration uses as rnorm).  x' = x + a p, r' = r + a Ap, p' = beta p - M r' with the system's own alpha / beta;
+// sums per system: <r',y'>, |x'-x|^2, |x'|^2, count(p' != 0).  x' and r' go to xn and rn, which may be x and r
+// themselves (hence no __restrict__ on the four): in place costs nothing where the vectors stream from HBM, but on
+// vectors that live in the caches writing a line just read measured 10.1 instead of 8.9 us at 1024^2 fp32, so a solve
+// whose work buffer has the room alternates between two copies.  A system that is not live changes nothing: in place it
+// is skipped, with separate destinations its x and r are carried over.
 // XNT: x is read and x' written non-temporally (x is not touched again until the next update, ~20 N bytes later)
-// REV: walk the vectors from the END.  The inverse row kernel before this one finishes on the last band (its Ap, p, r
+// REV: walk each system from its END.  The inverse row kernel before this one finishes on the last band (its Ap, p, r
 // rows are the freshest lines of the Infinity Cache) and the forward row kernel after it starts on the first band,
 // whose p' this kernel then has written last: one band's worth of each stream is served from that cache at both
 // boundaries instead of none.
-template <typename T, int V, int U = 1, bool XNT = false, bool REV = false>
-__global__ void __launch_bounds__(RED_BLOCK)
-k_pcg_update_dir(const T* __restrict__ x, const T* __restrict__ r, T* __restrict__ p,
-                 const T* __restrict__ Ap, T* __restrict__ xn, T* __restrict__ rn,
-                 const double* __restrict__ alpha_dev, T mdiv, size_t nvec, double* __restrict__ ws) {
-    const bool dead = alpha_dev[S_DEAD - S_ALPHA] != 0.0 || alpha_dev[S_STOP - S_ALPHA] != 0.0;
-    const T alpha = dead ? T(0) : (T)alpha_dev[0];
-    const T beta = (T)alpha_dev[S_BETA - S_ALPHA];
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nvec; i0 += U * stride) {
-        Pack<T, V> px[U], pr[U], pp[U], pa[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {              // all loads of the U strips in flight together
-            const size_t ii = i0 + u * stride;
-            const size_t i = REV ? nvec - 1 - ii : ii;
-            if (ii < nvec) { px[u] = XNT ? ld_nt<T, V>(x, i) : ld<T, V>(x, i); pr[u] = ld<T, V>(r, i); pp[u] = ld<T, V>(p, i); pa[u] = ld<T, V>(Ap, i); }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t ii = i0 + u * stride;
-            const size_t i = REV ? nvec - 1 - ii : ii;
-            if (ii >= nvec) break;
-            Pack<T, V> ox, orr;
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const T xnew = px[u].e[e] + alpha * pp[u].e[e];
-                const T rnew = pr[u].e[e] + alpha * pa[u].e[e];
-                const T y = mdiv > T(0) ? rnew / mdiv : rnew;
-                ox.e[e] = xnew;
-                orr.e[e] = rnew;
-                const double d = (double)xnew - (double)px[u].e[e];
-                acc[0] += (double)rnew * (double)y;
-                acc[1] += d * d;
-                acc[2] += (double)xnew * (double)xnew;
-                if (!dead) {
-                    const T pn = beta * pp[u].e[e] - y;
-                    pp[u].e[e] = pn;
-                }
-                acc[3] += (pp[u].e[e] != T(0)) ? 1.0 : 0.0;
-            }
-            if constexpr (XNT) st_nt<T, V>(xn, i, ox); else st<T, V>(xn, i, ox);
-            st<T, V>(rn, i, orr);
-            if (!dead) st<T, V>(p, i, pp[u]);
-        }
-    }
-    emit_partials<4>(acc, ws);
-}
-
-// tiny scalar kernels on the device state
-__global__ void k_set_alpha(double* S) { S[S_ALPHA] = S[S_RHO] / S[S_PAP]; S[S_NBT] = 0.0; }
-// Predictive backtracking.  With M(r) = r/d linear, <r',M r'> along r' = r + a Ap is the
-// quadratic  rho(a) = rho + (2 a <r,Ap> + a^2 <Ap,Ap>) / d,  so the reference's loop
-// "while rnorm_next > rnorm: alpha *= 0.75" (pcg.py:96-101) is evaluated on three scalars
-// instead of three more passes over the vectors; the accepted step is then applied ONCE and
-// rnorm_next is recomputed from the actual r' exactly as the reference does.
-__global__ void k_alpha_predict(double* S, double mdiv) {
-    const double d = mdiv > 0.0 ? mdiv : 1.0;
-    const double rho = S[S_RHO], s1 = S[S_RAP] / d, s2 = S[S_APAP] / d;
-    double alpha = rho / S[S_PAP];
-    int nbt = 0;
-    while (rho + (2.0 * alpha * s1 + alpha * alpha * s2) > rho && nbt < 200) { alpha *= 0.75; ++nbt; }
-    S[S_ALPHA] = alpha;
-    S[S_NBT] = (double)nbt;
-}
-__global__ void k_scale_alpha(double* S) { S[S_ALPHA] *= 0.75; }
-__global__ void k_set_beta(double* S) { S[S_BETA] = S[S_RHON] / S[S_RHO]; }
-__global__ void k_accept_rho(double* S) { S[S_RHO] = S[S_RHON]; }
-
-// the fused update's four sums AND the end-of-iteration bookkeeping in one launch (no all-reduce between)
-__global__ void __launch_bounds__(256)
-k_final_sum_waves_end(const double* __restrict__ ws, int G, double* __restrict__ S) {
-    const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int dst[4] = {S_RHON, S_NUM, S_DEN, S_ANY};
-    double acc = 0.0;
-    for (int g = lane; g < G; g += 64) acc += ws[(size_t)q * G + g];
-    acc = wave_sum(acc);
-    if (lane == 0) S[dst[q]] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) iter_end_dev(S, 1);
-}
-__global__ void k_iter_begin(double* S, double mdiv, int predict) { iter_begin_dev(S, mdiv, predict); }
-__global__ void k_iter_end(double* S, int fused) { iter_end_dev(S, fused); }
-// end of iteration k and begin of iteration k+1 in one launch (the merged all-reduce path)
-__global__ void k_iter_end_begin(double* S, double mdiv, int predict) {
-    iter_end_dev(S, 1);
-    iter_begin_dev(S, mdiv, predict);
-}
-// One launch per iteration for every scalar the sync-free driver needs: the three fused dots of the
-// convolution (per-workgroup partials `cp`), the four sums the
-// previous iteration's fused update left in `ws` (when `have_upd`), then -- unless an all-reduce has
-// to come first (`logic` == 0) -- the end of that iteration and the begin of this one.
-// Seven independent sums, each by ONE wave in a fixed lane-strided order (deterministic): wave w takes conv quantity w
-// (w < 3) and update quantity w (w < 4); `vals`: 8 doubles of LDS.
-__device__ __forceinline__ void iter_sums(const double* __restrict__ cp, int ncp, const double* __restrict__ ws, int G,
-                                          int have_upd, double* __restrict__ S, double mdiv, int predict, int logic,
-                                          double* vals) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (w < 3) {
-        double acc = 0.0;
-        for (int k = lane; k < ncp; k += 64) acc += cp[(size_t)w * ncp + k];
-        acc = wave_sum(acc);
-        if (lane == 0) vals[w] = acc;
-    }
-    if (have_upd && w < 4) {
-        double acc = 0.0;
-        for (int g = lane; g < G; g += 64) acc += ws[(size_t)w * G + g];
-        acc = wave_sum(acc);
-        if (lane == 0) vals[3 + w] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        S[S_PAP] = vals[0]; S[S_RAP] = vals[1]; S[S_APAP] = vals[2];
-        if (have_upd) { S[S_RHON] = vals[3]; S[S_NUM] = vals[4]; S[S_DEN] = vals[5]; S[S_ANY] = vals[6]; }
-        if (logic) {
-            if (have_upd) iter_end_dev(S, 1);
-            iter_begin_dev(S, mdiv, predict);
-        }
-    }
-}
-__global__ void __launch_bounds__(256)
-k_iter_sums(const double* __restrict__ cp, int ncp, const double* __restrict__ ws, int G, int have_upd,
-            double* __restrict__ S, double mdiv, int predict, int logic) {
-    __shared__ double vals[8];
-    iter_sums(cp, ncp, ws, G, have_upd, S, mdiv, predict, logic, vals);
-}
-__global__ void k_final_check(double* S) {
-    if (S[S_DEAD] == 0.0 && S[S_ANY] == 0.0) { S[S_DEAD] = 1.0; S[S_K] -= 1.0; S[S_EPS] = S[S_EPSP]; }
-}
-__global__ void k_init_state(double* S, double tol, double minit, double maxit) {
-    S[S_TOL] = tol; S[S_MINIT] = minit; S[S_MAXIT] = maxit;
-    S[S_RHO] = S[S_RHON];
-    S[S_ANY] = S[S_NUM];                   // count(y != 0) = count(p != 0) for p = -y
-    S[S_EPS] = 1.0; S[S_EPSP] = 1.0;
-}
-
-// ------------------------------------------------------------------ batched per-band PCG (pfb_pcg_solve_bands)
-// Every band is its own system with its own state block S + bl * SB.  The vector kernels give each band `gpb`
-// workgroups of its own (workgroup w works on band w / gpb only), so every partial sum belongs to one band:
-// ws[q * (nb gpb) + bl * gpb + g].  The bookkeeping kernels run one workgroup per band and sum that band's partials in
-// a fixed order.  A band that has stopped (S_STOP) or broken down (S_DEAD) is neither read nor written, and its state
-// is left as the iteration that stopped it left it.
-constexpr int SB = 32;                     // doubles per band state block
-constexpr int SB_ZERO = S_NSCALAR;         // the band's initial residual was zero (it never iterates)
-static_assert(SB_ZERO < SB, "band state block too small");
-
-__device__ __forceinline__ bool band_live(const double* Sb) { return Sb[S_DEAD] == 0.0 && Sb[S_STOP] == 0.0; }
-
-// r holds A(x0) on entry.  r = r - b ; p = -M r ; per band: <r,y>, count(y != 0)
-template <typename T, int V>
-__global__ void __launch_bounds__(RED_BLOCK)
-k_pcg_init_bands(T* __restrict__ r, const T* __restrict__ b, T* __restrict__ p, T mdiv, size_t nvb, int gpb,
-                 double* __restrict__ ws) {
-    const int bl = blockIdx.x / gpb, g = blockIdx.x - bl * gpb;
-    const size_t off = (size_t)bl * nvb;
-    double acc[2] = {0.0, 0.0};
-    for (size_t i = (size_t)g * blockDim.x + threadIdx.x; i < nvb; i += (size_t)gpb * blockDim.x) {
-        Pack<T, V> pr = ld<T, V>(r, off + i), pb = ld<T, V>(b, off + i), pp;
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const T rr = pr.e[e] - pb.e[e];
-            const T y = mdiv > T(0) ? rr / mdiv : rr;
-            pr.e[e] = rr;
-            pp.e[e] = -y;
-            acc[0] += (double)rr * (double)y;
-            acc[1] += (y != T(0)) ? 1.0 : 0.0;
-        }
-        st<T, V>(r, off + i, pr);
-        st<T, V>(p, off + i, pp);
-    }
-    emit_partials<2>(acc, ws);
-}
-
-// per band: S_RHO = <r,y>, S_ANY = count(y != 0) and the rule's parameters (k_init_state); a band with a zero initial
-// residual is marked SB_ZERO + S_STOP, so that no later kernel touches it
-__global__ void __launch_bounds__(128)
-k_init_bands(const double* __restrict__ ws, int gpb, double* __restrict__ S, double tol, double minit, double maxit) {
-    __shared__ double vals[2];
-    const int bl = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const size_t G = (size_t)gridDim.x * gpb;
-    double acc = 0.0;
-    for (int g = lane; g < gpb; g += 64) acc += ws[w * G + (size_t)bl * gpb + g];
-    acc = wave_sum(acc);
-    if (lane == 0) vals[w] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* Sb = S + (size_t)bl * SB;
-        Sb[S_TOL] = tol; Sb[S_MINIT] = minit; Sb[S_MAXIT] = maxit;
-        Sb[S_RHON] = vals[0]; Sb[S_NUM] = vals[1];
-        Sb[S_RHO] = vals[0];
-        Sb[S_ANY] = vals[1];
-        Sb[S_EPS] = 1.0; Sb[S_EPSP] = 1.0;
-        if (vals[1] == 0.0) { Sb[SB_ZERO] = 1.0; Sb[S_STOP] = 1.0; }
-    }
-}
-
-// k_pcg_update_dir on one band per workgroup, in place (the predictive modes need no old x): x' = x + a p,
-// r' = r + a Ap, p' = beta p - M r' with the band's own alpha / beta; sums <r',y'>, |x'-x|^2, |x'|^2, count(p' != 0).
-// XNT / REV as in k_pcg_update_dir (x non-temporal, each band walked from its end), for vectors far beyond the caches
 template <typename T, int V, int U, bool XNT, bool REV>
 __global__ void __launch_bounds__(RED_BLOCK)
-k_pcg_update_dir_bands(T* __restrict__ x, T* __restrict__ r, T* __restrict__ p, const T* __restrict__ Ap,
-                       const double* __restrict__ S, T mdiv, size_t nvb, int gpb, double* __restrict__ ws) {
-    const int bl = blockIdx.x / gpb, g = blockIdx.x - bl * gpb;
-    const double* Sb = S + (size_t)bl * SB;
+k_pcg_update_dir(const T* x, const T* r, T* __restrict__ p, const T* __restrict__ Ap, T* xn, T* rn,
+                 const double* __restrict__ S, T mdiv, size_t nvs, int gps, double* __restrict__ ws) {
+    const int s = blockIdx.x / gps, g = blockIdx.x - s * gps;
+    const double* Sb = S + (size_t)s * SB;
+    { const size_t off = (size_t)s * nvs * V; x += off; r += off; p += off; Ap += off; xn += off; rn += off; }
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    if (band_live(Sb)) {
+    if (sys_live(Sb)) {
         const T alpha = (T)Sb[S_ALPHA];
         const T beta = (T)Sb[S_BETA];
-        const size_t off = (size_t)bl * nvb;
-        const size_t stride = (size_t)gpb * blockDim.x;
-        for (size_t i0 = (size_t)g * blockDim.x + threadIdx.x; i0 < nvb; i0 += U * stride) {
+        const size_t stride = (size_t)gps * blockDim.x;
+        for (size_t i0 = (size_t)g * blockDim.x + threadIdx.x; i0 < nvs; i0 += U * stride) {
             Pack<T, V> px[U], pr[U], pp[U], pa[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {          // all loads of the U strips in flight together
                 const size_t ii = i0 + u * stride;
-                const size_t i = off + (REV ? nvb - 1 - ii : ii);
-                if (ii < nvb) {
+                const size_t i = REV ? nvs - 1 - ii : ii;
+                if (ii < nvs) {
                     px[u] = XNT ? ld_nt<T, V>(x, i) : ld<T, V>(x, i);
                     pr[u] = ld<T, V>(r, i); pp[u] = ld<T, V>(p, i); pa[u] = ld<T, V>(Ap, i);
                 }
@@ -501,8 +328,8 @@ k_pcg_update_dir_bands(T* __restrict__ x, T* __restrict__ r, T* __restrict__ p, 
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const size_t ii = i0 + u * stride;
-                const size_t i = off + (REV ? nvb - 1 - ii : ii);
-                if (ii >= nvb) break;
+                const size_t i = REV ? nvs - 1 - ii : ii;
+                if (ii >= nvs) break;
                 Pack<T, V> ox, orr;
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
@@ -519,72 +346,98 @@ k_pcg_update_dir_bands(T* __restrict__ x, T* __restrict__ r, T* __restrict__ p, 
                     pp[u].e[e] = pn;
                     acc[3] += (pn != T(0)) ? 1.0 : 0.0;
                 }
-                if constexpr (XNT) st_nt<T, V>(x, i, ox); else st<T, V>(x, i, ox);
-                st<T, V>(r, i, orr);
+                if constexpr (XNT) st_nt<T, V>(xn, i, ox); else st<T, V>(xn, i, ox);
+                st<T, V>(rn, i, orr);
                 st<T, V>(p, i, pp[u]);
             }
+        }
+    } else if (xn != x) {
+        for (size_t i = (size_t)g * blockDim.x + threadIdx.x; i < nvs; i += (size_t)gps * blockDim.x) {
+            st<T, V>(xn, i, ld<T, V>(x, i));
+            st<T, V>(rn, i, ld<T, V>(r, i));
         }
     }
     emit_partials<4>(acc, ws);
 }
 
-// one workgroup per band, once per iteration: the band's three convolution dots (cp: band bl's `bs` partials of
-// quantity q at q * qs + bl * bst), the four sums of its previous update (when `have_upd`; ws: [4][nb gpb]), then the
-// end of that iteration and the begin of this one
+// tiny scalar kernels of the exact backtracking loop
+__global__ void k_set_alpha(double* S) { S[S_ALPHA] = S[S_RHO] / S[S_PAP]; S[S_NBT] = 0.0; }
+__global__ void k_scale_alpha(double* S) { S[S_ALPHA] *= 0.75; }
+__global__ void k_set_beta(double* S) { S[S_BETA] = S[S_RHON] / S[S_RHO]; }
+__global__ void k_accept_rho(double* S) { S[S_RHO] = S[S_RHON]; }
+
+// One launch per iteration, one workgroup per system, for every scalar the sync-free driver needs: the three fused
+// dots of the convolution (`cp`: the system's `bs` per-workgroup partials of quantity q at q * qs + s * bst; null: none
+// to sum), the four sums the previous iteration's fused update left in `ws` (when `have_upd`), then -- unless an
+// all-reduce has to come first (`logic` == 0) -- the end of that iteration and the begin of this one.
+// Seven independent sums, each by ONE wave in a fixed lane-strided order (deterministic): wave w takes conv quantity w
+// (w < 3) and update quantity w (w < 4).
+// Predictive backtracking (iter_begin_dev).  With M(r) = r/d linear, <r',M r'> along r' = r + a Ap is the
+// quadratic  rho(a) = rho + (2 a <r,Ap> + a^2 <Ap,Ap>) / d,  so the reference's loop
+// "while rnorm_next > rnorm: alpha *= 0.75" (pcg.py:96-101) is evaluated on three scalars
+// instead of three more passes over the vectors; the accepted step is then applied ONCE and
+// rnorm_next is recomputed from the actual r' exactly as the reference does.
 __global__ void __launch_bounds__(256)
-k_iter_sums_bands(const double* __restrict__ cp, int bs, int qs, int bst, const double* __restrict__ ws, int gpb,
-                  int have_upd, double* __restrict__ S, double mdiv, int predict) {
+k_iter_sums(const double* __restrict__ cp, int bs, int qs, int bst, const double* __restrict__ ws, int gps,
+            int have_upd, double* __restrict__ S, double mdiv, int predict, int logic) {
     __shared__ double vals[8];
-    const int bl = blockIdx.x, nb = gridDim.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (w < 3) {
-        const double* src = cp + (size_t)w * qs + (size_t)bl * bst;
+    const int s = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (cp && w < 3) {
+        const double* src = cp + (size_t)w * qs + (size_t)s * bst;
         double acc = 0.0;
         for (int k = lane; k < bs; k += 64) acc += src[k];
         acc = wave_sum(acc);
         if (lane == 0) vals[w] = acc;
     }
     if (have_upd && w < 4) {
-        const double* src = ws + (size_t)w * nb * gpb + (size_t)bl * gpb;
+        const double* src = ws + ((size_t)w * gridDim.x + s) * gps;
         double acc = 0.0;
-        for (int g = lane; g < gpb; g += 64) acc += src[g];
+        for (int g = lane; g < gps; g += 64) acc += src[g];
         acc = wave_sum(acc);
         if (lane == 0) vals[3 + w] = acc;
     }
     __syncthreads();
-    double* Sb = S + (size_t)bl * SB;
-    if (threadIdx.x == 0 && band_live(Sb)) {
-        Sb[S_PAP] = vals[0]; Sb[S_RAP] = vals[1]; Sb[S_APAP] = vals[2];
-        if (have_upd) {
-            Sb[S_RHON] = vals[3]; Sb[S_NUM] = vals[4]; Sb[S_DEN] = vals[5]; Sb[S_ANY] = vals[6];
-            iter_end_dev(Sb, 1);
+    double* Sb = S + (size_t)s * SB;
+    if (threadIdx.x == 0 && sys_live(Sb)) {
+        if (cp) { Sb[S_PAP] = vals[0]; Sb[S_RAP] = vals[1]; Sb[S_APAP] = vals[2]; }
+        if (have_upd) { Sb[S_RHON] = vals[3]; Sb[S_NUM] = vals[4]; Sb[S_DEN] = vals[5]; Sb[S_ANY] = vals[6]; }
+        if (logic) {
+            if (have_upd) iter_end_dev(Sb);
+            iter_begin_dev(Sb, mdiv, predict);
         }
-        iter_begin_dev(Sb, mdiv, predict);
     }
 }
-
-// one workgroup per band: the update's four sums and the end of the iteration (past minit, where the host may look)
+// the update's four sums (unless an all-reduce stood between: `ws` null) and the end of the iteration, past minit,
+// where the host may look
 __global__ void __launch_bounds__(256)
-k_iter_end_bands(const double* __restrict__ ws, int gpb, double* __restrict__ S) {
+k_iter_end(const double* __restrict__ ws, int gps, double* __restrict__ S) {
     __shared__ double vals[4];
-    const int bl = blockIdx.x, nb = gridDim.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const double* src = ws + (size_t)w * nb * gpb + (size_t)bl * gpb;
-    double acc = 0.0;
-    for (int g = lane; g < gpb; g += 64) acc += src[g];
-    acc = wave_sum(acc);
-    if (lane == 0) vals[w] = acc;
-    __syncthreads();
-    double* Sb = S + (size_t)bl * SB;
-    if (threadIdx.x == 0 && band_live(Sb)) {
-        Sb[S_RHON] = vals[0]; Sb[S_NUM] = vals[1]; Sb[S_DEN] = vals[2]; Sb[S_ANY] = vals[3];
-        iter_end_dev(Sb, 1);
+    const int s = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (ws) {
+        const double* src = ws + ((size_t)w * gridDim.x + s) * gps;
+        double acc = 0.0;
+        for (int g = lane; g < gps; g += 64) acc += src[g];
+        acc = wave_sum(acc);
+        if (lane == 0) vals[w] = acc;
+        __syncthreads();
+    }
+    double* Sb = S + (size_t)s * SB;
+    if (threadIdx.x == 0 && sys_live(Sb)) {
+        if (ws) { Sb[S_RHON] = vals[0]; Sb[S_NUM] = vals[1]; Sb[S_DEN] = vals[2]; Sb[S_ANY] = vals[3]; }
+        iter_end_dev(Sb);
     }
 }
-
-// k_final_check per band: the direction the band's last iteration built has not been looked at yet
-__global__ void k_final_check_bands(double* S, int nb) {
-    for (int bl = threadIdx.x; bl < nb; bl += blockDim.x) {
-        double* Sb = S + (size_t)bl * SB;
-        if (Sb[SB_ZERO] == 0.0 && Sb[S_DEAD] == 0.0 && Sb[S_ANY] == 0.0) {
+// the all-reduce path (one system): what k_iter_sums left out, after the exchange
+__global__ void k_iter_begin(double* S, double mdiv, int predict) { iter_begin_dev(S, mdiv, predict); }
+__global__ void k_iter_end_begin(double* S, double mdiv, int predict) {
+    iter_end_dev(S);
+    iter_begin_dev(S, mdiv, predict);
+}
+// the direction a system's last iteration built has not been looked at yet
+__global__ void k_final_check(double* S, int nsys) {
+    for (int s = threadIdx.x; s < nsys; s += blockDim.x) {
+        double* Sb = S + (size_t)s * SB;
+        if (Sb[S_ZERO] == 0.0 && Sb[S_DEAD] == 0.0 && Sb[S_ANY] == 0.0) {
             Sb[S_DEAD] = 1.0; Sb[S_K] -= 1.0; Sb[S_EPS] = Sb[S_EPSP];
         }
     }
@@ -658,6 +511,7 @@ static int axpby_impl(double a, const void* x, double b, void* y, size_t n, hipS
     return PFB_OK;
 }
 
+// ------------------------------------------------------------------------ PCG driver
 // The fused update streams 4 reads + 3 writes; measured on MI355X (tools/micro/hbm_stream.hip and
 // the bench) that mix runs fastest with ONE 256-thread workgroup per CU -- few concurrent streams
 // per HBM channel -- not with the chip oversubscribed: 256 workgroups 0.60 ms, 1024 0.78 ms at
@@ -675,100 +529,64 @@ static int stream_grid(size_t nvec) {
     if (g > (size_t)ncu) g = ncu;
     return (int)g;
 }
-template <typename T>
-static int launch_update_dir(size_t n, const T* x, const T* r, T* p, const T* Ap, T* xn, T* rn,
-                             const double* alpha_dev, T mdiv, double* ws, hipStream_t st) {
-    // two strips per trip (all eight loads in flight before the first use): fp64 0.79 -> 0.71 ms at 4 x 4096^2,
-    // fp32 0.64 -> 0.62 ms at 8 x 4096^2 (rocprofv3)
-    using PL = std::initializer_list<const void*>;
-    constexpr int V = V16<T>::N;
-    if (can_vec<T>(n, PL{x, r, p, Ap, xn, rn})) {
-        const size_t nvec = n / V;
-        const int G = stream_grid(nvec);
-        // x non-temporal (and the walk from the end) only when the vectors are far beyond the caches anyway (>= 32 MB
-        // each): small problems live in L2 / the Infinity Cache between iterations and nt would send x to HBM
-        // (1024^2: 0.060 -> 0.066 ms per iteration)
-        if (n * sizeof(T) >= ((size_t)32 << 20))
-            hipLaunchKernelGGL((k_pcg_update_dir<T, V, 2, true, true>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, nvec, ws);
-        else
-            hipLaunchKernelGGL((k_pcg_update_dir<T, V, 2>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, nvec, ws);
-        return G;
-    }
-    const int G = stream_grid(n);
-    hipLaunchKernelGGL((k_pcg_update_dir<T, 1, 1>), dim3(G), dim3(RED_BLOCK), 0, st, x, r, p, Ap, xn, rn, alpha_dev, mdiv, n, ws);
-    return G;
+// workgroups per system of the fused update: the whole grid stays near one workgroup per CU, split evenly over the
+// systems; of k_pcg_init: red_grid's rule.  nsys * gps <= max(nsys, RED_MAX_GRID) bounds the partials of both.
+static int update_grid(size_t nvs, int nsys) {
+    int g = stream_grid(nvs);
+    const int share = stream_grid((size_t)1 << 40) / nsys;
+    if (g > share) g = share;
+    if (g > RED_MAX_GRID / nsys) g = RED_MAX_GRID / nsys;
+    return g < 1 ? 1 : g;
+}
+static int init_grid(size_t nvs, int nsys) {
+    int g = red_grid(nvs);
+    if (g > RED_MAX_GRID / nsys) g = RED_MAX_GRID / nsys;
+    return g < 1 ? 1 : g;
 }
 
-// ------------------------------------------------------------------------ PCG driver
-struct PcgWork {
-    char* r; char* p; char* Ap; char* xalt; char* ralt;
-    double* S; double* ws;
-};
-
+// work: r, p, Ap, the state blocks, the partial sums; then the exact loop's alternates of x and r
 static size_t vec_bytes(const pfb_conv_plan* plan, int nb) {
     const size_t esz = plan->dtype == PFB_F32 ? 4 : 8;
     size_t b = (size_t)nb * plan->nx * plan->ny * esz;
     return (b + 255) & ~(size_t)255;
 }
+static size_t state_bytes(int nsys) { return ((size_t)nsys * SB * sizeof(double) + 255) & ~(size_t)255; }
+static size_t ws_bytes(int nsys) { return sizeof(double) * 4 * (size_t)(nsys > RED_MAX_GRID ? nsys : RED_MAX_GRID); }
 
-template <typename T>
-static int pcg_impl(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
-                    const void* beam, double wsum, double sigmainv, double mdiv_d, double tol,
-                    int maxit, int minit, int backtrack, void* work, pfb_allreduce_fn allreduce,
-                    void* actx, pfb_pcg_result* res, hipStream_t st) {
-    const size_t n = (size_t)nb * plan->nx * plan->ny;
-    const size_t vb = vec_bytes(plan, nb);
-    char* w = (char*)work;
-    T* r = (T*)w;
-    T* p = (T*)(w + vb);
-    T* Ap = (T*)(w + 2 * vb);
-    T* xalt = (T*)(w + 3 * vb);
-    T* ralt = (T*)(w + 4 * vb);
-    double* S = (double*)(w + 5 * vb);
-    double* ws = S + 64;
-    const T mdiv = (T)mdiv_d;
-    double h[S_NSCALAR];
-    int G_used = 0;
-    using PL = std::initializer_list<const void*>;
-    T* xcur = (T*)x;    // current iterate lives alternately in x / xalt
-    T* rcur = r;
-    T* xnew = xalt;
-    T* rnew = ralt;
-
-    memset(res, 0, sizeof(*res));
-    if (allreduce) set_error("%s", "");        // comm_fail() quotes the hook's message: no stale text from an earlier call
-    PFB_HIP_CHECK(hipMemsetAsync(S, 0, sizeof(double) * 64, st));
-
-    // ---- the exchange can lose a participant (include/pfb_hip.h, "Failure protocol"): with a hook the solver never
-    // waits for the device unboundedly -- it polls an event, probes the exchange (count = 0) and gives up after
-    // PFB_COMM_TIMEOUT_S seconds, aborting the exchange (count < 0) so that no rank stays blocked in a collective
-    struct WaitEvent {
-        hipEvent_t ev = nullptr;
-        ~WaitEvent() { if (ev) (void)hipEventDestroy(ev); }
-    } wev;
+// The exchange can lose a participant (include/pfb_hip.h, "Failure protocol"): with a hook the solver never waits for
+// the device unboundedly -- it polls an event, probes the exchange (count = 0) and gives up after PFB_COMM_TIMEOUT_S
+// seconds, aborting the exchange (count < 0) so that no rank stays blocked in a collective.  Without a hook every wait
+// is a plain synchronise.
+struct PcgSync {
+    pfb_allreduce_fn allreduce;
+    void* actx;
+    hipStream_t st;
+    hipEvent_t ev = nullptr;
     double comm_timeout = 600.0;
-    if (allreduce) {
+    ~PcgSync() { if (ev) (void)hipEventDestroy(ev); }
+    int open() {
+        if (!allreduce) return PFB_OK;
+        set_error("%s", "");                   // comm_fail() quotes the hook's message: no stale text from an earlier call
         if (const char* e = getenv("PFB_COMM_TIMEOUT_S")) { const double v = atof(e); if (v > 0) comm_timeout = v; }
-        PFB_HIP_CHECK(hipEventCreateWithFlags(&wev.ev, hipEventDisableTiming));
+        PFB_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return PFB_OK;
     }
-    auto comm_fail = [&](const char* what) -> int {
+    int comm_fail(const char* what) {
         char msg[384];
         snprintf(msg, sizeof(msg), "%s", pfb_last_error());      // the hook's own message, if it left one
         (void)allreduce(actx, nullptr, -1, (void*)st);            // abort: peers blocked in the collective are released
         set_error("pcg: %s%s%s -- exchange aborted, this rank's result is void", what, msg[0] ? ": " : "", msg);
         return PFB_ERR_COMM;
-    };
-    auto reduce_hook = [&](int first, int count) -> int {
-        if (!allreduce) return PFB_OK;
-        if (allreduce(actx, S + first, count, (void*)st) != 0) return comm_fail("the all-reduce hook failed");
+    }
+    int reduce(double* buf, int count) {
+        if (allreduce && allreduce(actx, buf, count, (void*)st) != 0) return comm_fail("the all-reduce hook failed");
         return PFB_OK;
-    };
-    auto wait_stream = [&]() -> int {
-        if (!allreduce) { PFB_HIP_CHECK(hipStreamSynchronize(st)); return PFB_OK; }
-        PFB_HIP_CHECK(hipEventRecord(wev.ev, st));
+    }
+    int wait_event(hipEvent_t e) {
+        if (!allreduce) { PFB_HIP_CHECK(hipEventSynchronize(e)); return PFB_OK; }
         const auto t0 = std::chrono::steady_clock::now();
         for (long spins = 0;; ++spins) {
-            const hipError_t q = hipEventQuery(wev.ev);
+            const hipError_t q = hipEventQuery(e);
             if (q == hipSuccess) return PFB_OK;
             if (q != hipErrorNotReady) { set_error("pcg: hipEventQuery -> %s", hipGetErrorString(q)); return PFB_ERR_HIP; }
             if (spins < 4096) continue;                           // a look normally returns within tens of microseconds
@@ -782,365 +600,303 @@ static int pcg_impl(pfb_conv_plan* plan, int band0, int nb, const void* b, void*
             }
             usleep(el < 0.01 ? 20 : 500);
         }
-    };
-    auto fetch = [&]() -> int {
-        PFB_HIP_CHECK(hipMemcpyAsync(h, S, sizeof(double) * S_NSCALAR, hipMemcpyDeviceToHost, st));
-        return wait_stream();
-    };
-    int err;
-
-    // r = A(x0) - b ; y = M r ; p = -y                       pcg.py:71-76
-    err = pfb_psfconv_apply(plan, band0, nb, xcur, beam, wsum, sigmainv, rcur, nullptr, nullptr, (void*)st);
-    if (err != PFB_OK) return err;
-    res->matvecs = 1;
-    PFB_LAUNCH_VEC(T, k_pcg_init, n, (PL{rcur, b, p}), rcur, (const T*)b, p, mdiv);
-    hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 2, S + S_RHON);
-    // S_RHON = <r,y>, S_NUM = count(y != 0): move into place after the hook
-    if ((err = reduce_hook(S_RHON, 2)) != PFB_OK) return err;
-    hipLaunchKernelGGL(k_init_state, dim3(1), dim3(1), 0, st, S, tol, (double)minit, (double)maxit);
-    if ((err = fetch()) != PFB_OK) return err;
-    if (h[S_NUM] == 0.0) {                               // "Initial residual is zero"
-        res->status = PFB_PCG_ZERO_RESIDUAL;
-        res->eps = 1.0;
-        res->rnorm = h[S_RHO];
-        if (r_out) PFB_HIP_CHECK(hipMemcpyAsync(r_out, rcur, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    }
+    int wait_stream() {
+        if (!allreduce) { PFB_HIP_CHECK(hipStreamSynchronize(st)); return PFB_OK; }
+        PFB_HIP_CHECK(hipEventRecord(ev, st));
+        return wait_event(ev);
+    }
+    int fetch(double* h, const double* S, size_t count) {
+        PFB_HIP_CHECK(hipMemcpyAsync(h, S, sizeof(double) * count, hipMemcpyDeviceToHost, st));
         return wait_stream();
     }
+};
 
-    int k = 0;
-    double eps = 1.0;
-    double rho = h[S_RHO];
-    int status = -1;
-    if (backtrack != 1) {
-        // ---- sync-free driver (backtrack off or predictive).  Everything an iteration
-        // needs to decide lives in S on the device; the host only has to look when the
-        // stopping rule `(eps > tol or k < minit) and k < maxit` can actually fire, i.e.
-        // never while k < minit.  Two reduction points per iteration:
-        //   [p.Ap, r.Ap, Ap.Ap, any(p)]  and  [r'.y', |x'-x|^2, |x'|^2]
-        // -- with sharded bands one all-reduce each, merged into ONE per iteration while k < minit.
-        int khost = 0;
-        bool pending_end = false;
-        bool go = (1.0 > tol || 0 < minit) && 0 < maxit;
+// One solve: bands [band0, band0 + nb) as one system (the cube: inner products over all bands) or, `per_band`, every
+// band its own.  init(), then run() or run_exact(), then report().
+template <typename T>
+struct Pcg {
+    pfb_conv_plan* plan;
+    int band0, nb;
+    bool per_band;
+    const T* b; T* x; T* r_out; const T* beam;
+    double wsum, sigmainv, mdiv_d, tol;
+    int maxit, minit;
+    PcgSync sync;
+    hipStream_t st;
+    int nsys;
+    size_t n, ns, nvs;         // elements of the solve and of a system; vectors of a system
+    bool vec;                  // every system starts on a 16-byte boundary and is a whole number of them
+    T *r, *p, *Ap, *xalt, *ralt;
+    double *S, *ws;
+    T mdiv;
+    std::vector<double> h;     // the host's copy of the state blocks
+
+    Pcg(pfb_conv_plan* plan_, int band0_, int nb_, bool per_band_, const void* b_, void* x_, void* r_out_,
+        const void* beam_, double wsum_, double sigmainv_, double mdiv_, double tol_, int maxit_, int minit_, void* work,
+        pfb_allreduce_fn allreduce, void* actx, hipStream_t st_)
+        : plan(plan_), band0(band0_), nb(nb_), per_band(per_band_), b((const T*)b_), x((T*)x_), r_out((T*)r_out_),
+          beam((const T*)beam_), wsum(wsum_), sigmainv(sigmainv_), mdiv_d(mdiv_), tol(tol_), maxit(maxit_),
+          minit(minit_), sync{allreduce, actx, st_}, st(st_), nsys(per_band_ ? nb_ : 1), mdiv((T)mdiv_),
+          h((size_t)nsys * SB) {
+        n = (size_t)nb * plan->nx * plan->ny;
+        ns = n / nsys;
+        const size_t vb = vec_bytes(plan, nb);
+        char* w = (char*)work;
+        r = (T*)w; p = (T*)(w + vb); Ap = (T*)(w + 2 * vb);
+        S = (double*)(w + 3 * vb);
+        ws = (double*)(w + 3 * vb + state_bytes(nsys));
+        // alternates of x and r: only in the cube solve's work buffer (pfb_pcg_work_bytes); without them x and r are
+        // updated in place
+        xalt = per_band ? nullptr : (T*)(w + 3 * vb + state_bytes(nsys) + ws_bytes(nsys));
+        ralt = per_band ? nullptr : (T*)((char*)xalt + vb);
+        using PL = std::initializer_list<const void*>;
+        // decided once for every vector kernel of the solve (r, p, Ap and the alternates are 256-byte aligned parts of
+        // `work`).  A caller whose x or b is not 16-byte aligned gets the scalar kernels throughout, init included
+        vec = can_vec<T>(ns, PL{x, b, r, p, Ap});
+        nvs = vec ? ns / V16<T>::N : ns;
+    }
+
+    // r = A(x0) - b ; y = M r ; p = -y ; the state blocks, on the device and in h          pcg.py:71-76
+    int init() {
+        int err;
+        if ((err = sync.open()) != PFB_OK) return err;
+        PFB_HIP_CHECK(hipMemsetAsync(S, 0, sizeof(double) * h.size(), st));
+        err = pfb_psfconv_apply(plan, band0, nb, x, beam, wsum, sigmainv, r, nullptr, nullptr, (void*)st);
+        if (err != PFB_OK) return err;
+        const int gps = init_grid(nvs, nsys);
+        if (vec)
+            hipLaunchKernelGGL((k_pcg_init<T, V16<T>::N>), dim3(nsys * gps), dim3(RED_BLOCK), 0, st, r, b, p, mdiv, nvs,
+                               gps, ws);
+        else
+            hipLaunchKernelGGL((k_pcg_init<T, 1>), dim3(nsys * gps), dim3(RED_BLOCK), 0, st, r, b, p, mdiv, nvs, gps, ws);
+        // S_RHON = <r,y>, S_NUM = count(y != 0): moved into place after the hook
+        const int hook = sync.allreduce ? 1 : 0;
+        hipLaunchKernelGGL(k_init_state, dim3(nsys), dim3(RED_BLOCK), 0, st, (const double*)ws, gps, S, tol,
+                           (double)minit, (double)maxit, 1, 1 - hook);
+        if (hook) {
+            if ((err = sync.reduce(S + S_RHON, 2)) != PFB_OK) return err;
+            hipLaunchKernelGGL(k_init_state, dim3(nsys), dim3(RED_BLOCK), 0, st, (const double*)ws, gps, S, tol,
+                               (double)minit, (double)maxit, 0, 1);
+        }
+        PFB_HIP_CHECK(hipGetLastError());
+        return sync.fetch(h.data(), S, h.size());
+    }
+
+    // Sync-free driver (backtrack off or predictive).  Everything an iteration needs to decide lives in the state
+    // blocks on the device; the host only has to look when the stopping rule `(eps > tol or k < minit) and k < maxit`
+    // can actually fire, i.e. never while k < minit, and then only at whether any system is still live.  Two reduction
+    // points per iteration:  [p.Ap, r.Ap, Ap.Ap, any(p)]  and  [r'.y', |x'-x|^2, |x'|^2]
+    // -- with sharded bands one all-reduce each, merged into ONE per iteration while k < minit.
+    int run(int predict, size_t lookahead_max) {
+        const size_t nS = h.size();
+        const int bps = nb / nsys;                 // bands per system
+        const bool hook = sync.allreduce != nullptr;
+        auto any_live = [&](const double* hs) {
+            for (int s = 0; s < nsys; ++s) if (sys_live(hs + (size_t)s * SB)) return true;
+            return false;
+        };
+        int err;
         // Past minit the stopping rule needs eps after every iteration.  Looking costs a copy + stream sync
         // (13-24 us, tools/exp_sync_cost.py): a third of an iteration at 1024^2, 1 % at 8 x 4096^2.  Small
         // problems therefore run ONE iteration ahead: iteration j is enqueued, then the pinned snapshot taken
-        // after iteration j-1 is read; the device evaluates the rule itself (S_STOP) so that the speculative
+        // after iteration j-1 is read; every system evaluates the rule itself (S_STOP) so that the speculative
         // iteration is a no-op once it fired.  Price: one wasted iteration per solve -- large problems keep
         // the synchronous look.  PFB_PCG_LOOKAHEAD=0/1 overrides the size rule.
-        bool lookahead = n <= ((size_t)4 << 20);
+        bool lookahead = n <= lookahead_max;
         if (const char* la = getenv("PFB_PCG_LOOKAHEAD")) lookahead = atoi(la) != 0;
-        if (lookahead && !plan->pcg_pin) {
-            PFB_HIP_CHECK(hipHostMalloc((void**)&plan->pcg_pin, sizeof(double) * 2 * S_NSCALAR, hipHostMallocDefault));
-            PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[0], hipEventDisableTiming));
-            PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[1], hipEventDisableTiming));
+        if (lookahead && plan->pcg_pin_n < nsys) {     // two snapshots of the state blocks, grown on demand
+            if (plan->pcg_pin) { PFB_HIP_CHECK(hipStreamSynchronize(st)); (void)hipHostFree(plan->pcg_pin); }
+            plan->pcg_pin = nullptr;
+            plan->pcg_pin_n = 0;
+            PFB_HIP_CHECK(hipHostMalloc((void**)&plan->pcg_pin, sizeof(double) * 2 * nS, hipHostMallocDefault));
+            plan->pcg_pin_n = nsys;
+            for (int e = 0; e < 2; ++e)
+                if (!plan->pcg_ev[e]) PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[e], hipEventDisableTiming));
         }
-        int slot = 0;
-        bool have_prev = false, stale_h = false;
+        // x non-temporal (and the walk from the end) only when the vectors are far beyond the caches anyway (>= 32 MB
+        // each): small problems live in L2 / the Infinity Cache between iterations and nt would send x to HBM
+        // (1024^2: 0.060 -> 0.066 ms per iteration)
+        const bool xnt = vec && n * sizeof(T) >= ((size_t)32 << 20);
+        const double* seen = h.data();             // the newest state the host has looked at
+        bool go = (1.0 > tol || 0 < minit) && 0 < maxit && any_live(seen);
+        int khost = 0, slot = 0;
+        bool pending_end = false, have_prev = false;
+        // the span [lo, lo + nl) of systems that may still be live: narrowed at every host look, so that bands which
+        // have stopped at either end are no longer convolved (a stopped band between two live ones still is)
+        int lo = 0, nl = nsys, gpl = update_grid(nvs, nsys);
+        // the iterate, and where the next update writes it (k_pcg_update_dir): the alternates, or in place
+        T *xc = x, *rc = r, *xn = xalt ? xalt : x, *rn = ralt ? ralt : r;
+        auto narrow = [&](const double* hs) {
+            int a = 0, z = nsys;
+            while (a < z && !sys_live(hs + (size_t)a * SB)) ++a;
+            while (z > a && !sys_live(hs + (size_t)(z - 1) * SB)) --z;
+            if (z > a && (a != lo || z - a != nl)) { lo = a; nl = z - a; gpl = update_grid(nvs, nl); }
+        };
         while (go) {
-            err = psfconv_apply_partials(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, rcur, (void*)st);
+            const size_t off = (size_t)lo * ns;
+            double* Sl = S + (size_t)lo * SB;
+            int bs, qs, bst;                       // where the convolution left system s's partials: k_iter_sums
+            err = psfconv_apply_partials(plan, band0 + lo * bps, nl * bps, p + off, beam ? beam + off : nullptr, wsum,
+                                         sigmainv, Ap + off, p + off, rc + off, per_band, &bs, &qs, &bst, (void*)st);
             if (err != PFB_OK) return err;
             // ONE scalar launch per iteration: the convolution's dots, the previous update's sums
             // (left pending while nobody can look at k / eps, i.e. while k < minit) and the
             // bookkeeping; with sharded bands the all-reduce of those 7 (or 4) scalars sits between
             // the sums and the bookkeeping -- one RCCL call per iteration instead of two.
-            const int predict = backtrack == 2 ? 2 : 3;   // beta always comes from rho(alpha)
-            hipLaunchKernelGGL(k_iter_sums, dim3(1), dim3(256), 0, st, (const double*)plan->partials,
-                               plan->last_npartials, (const double*)ws, G_used, pending_end ? 1 : 0, S,
-                               mdiv_d, predict, allreduce ? 0 : 1);
-            if (allreduce) {
-                if ((err = reduce_hook(S_PAP, pending_end ? 7 : 4)) != PFB_OK) return err;
-                if (pending_end)
-                    hipLaunchKernelGGL(k_iter_end_begin, dim3(1), dim3(1), 0, st, S, mdiv_d, predict);
-                else
-                    hipLaunchKernelGGL(k_iter_begin, dim3(1), dim3(1), 0, st, S, mdiv_d, predict);
+            hipLaunchKernelGGL(k_iter_sums, dim3(nl), dim3(256), 0, st, (const double*)plan->partials, bs, qs, bst,
+                               (const double*)ws, gpl, pending_end ? 1 : 0, Sl, mdiv_d, predict, hook ? 0 : 1);
+            // Behind a stop (the look-ahead's one speculative iteration) k_iter_sums writes nothing, so these exchanges
+            // sum S_PAP .. S_ANY over the ranks a second time.  Every rank stops on the same reduced scalars, so all
+            // still take part; nothing reads S_PAP .. S_DEN of a stopped system again, and S_ANY, which k_final_check
+            // compares with zero, is a sum of counts >= 0: zero stays zero, non-zero stays non-zero.
+            if (hook) {
+                if ((err = sync.reduce(Sl + S_PAP, pending_end ? 7 : 4)) != PFB_OK) return err;
+                if (pending_end) hipLaunchKernelGGL(k_iter_end_begin, dim3(1), dim3(1), 0, st, Sl, mdiv_d, predict);
+                else hipLaunchKernelGGL(k_iter_begin, dim3(1), dim3(1), 0, st, Sl, mdiv_d, predict);
             }
             pending_end = false;
-            G_used = launch_update_dir<T>(n, xcur, rcur, p, Ap, xnew, rnew, S + S_ALPHA, mdiv, ws, st);
+            // two strips per trip (all eight loads in flight before the first use): fp64 0.79 -> 0.71 ms at
+            // 4 x 4096^2, fp32 0.64 -> 0.62 ms at 8 x 4096^2 (rocprofv3)
+#define PFB_UPDATE(VV, XN)                                                                                     \
+            hipLaunchKernelGGL((k_pcg_update_dir<T, VV, 2, XN, XN>), dim3(nl * gpl), dim3(RED_BLOCK), 0, st,   \
+                               (const T*)xc + off, (const T*)rc + off, p + off, (const T*)Ap + off, xn + off,    \
+                               rn + off, (const double*)Sl, mdiv, nvs, gpl, ws)
+            if (xnt) PFB_UPDATE(V16<T>::N, true);
+            else if (vec) PFB_UPDATE(V16<T>::N, false);
+            else PFB_UPDATE(1, false);
+#undef PFB_UPDATE
+            std::swap(xc, xn);
+            std::swap(rc, rn);
             if (khost + 1 < minit && khost + 1 < maxit) {
-                pending_end = true;        // summed by the next iteration's k_iter_sums
-            } else if (!allreduce) {
-                hipLaunchKernelGGL(k_final_sum_waves_end, dim3(1), dim3(256), 0, st, ws, G_used, S);
+                pending_end = true;        // summed by the next iteration's k_iter_sums (no look, so no narrowing, between)
             } else {
-                hipLaunchKernelGGL(k_final_sum_waves, dim3(1), dim3(256), 0, st, ws, G_used, 4, S,
-                                   (Dst4{{S_RHON, S_NUM, S_DEN, S_ANY}}));
-                if ((err = reduce_hook(S_RHON, 3)) != PFB_OK) return err;
-                hipLaunchKernelGGL(k_iter_end, dim3(1), dim3(1), 0, st, S, 1);
+                if (hook) {
+                    hipLaunchKernelGGL(k_iter_sums, dim3(nl), dim3(256), 0, st, (const double*)nullptr, 0, 0, 0,
+                                       (const double*)ws, gpl, 1, Sl, mdiv_d, predict, 0);
+                    if ((err = sync.reduce(Sl + S_RHON, 3)) != PFB_OK) return err;
+                }
+                hipLaunchKernelGGL(k_iter_end, dim3(nl), dim3(256), 0, st, hook ? nullptr : (const double*)ws, gpl, Sl);
             }
-            { T* t = xcur; xcur = xnew; xnew = t; t = rcur; rcur = rnew; rnew = t; }
+            PFB_HIP_CHECK(hipGetLastError());
             ++khost;
-            if (khost < minit && khost < maxit) continue;          // cannot stop yet: no need to look
+            if (khost < minit && khost < maxit) continue;          // no system can stop yet: no need to look
             if (lookahead && khost < maxit) {
-                double* snap = plan->pcg_pin + (size_t)slot * S_NSCALAR;
-                PFB_HIP_CHECK(hipMemcpyAsync(snap, S, sizeof(double) * S_NSCALAR, hipMemcpyDeviceToHost, st));
+                double* snap = plan->pcg_pin + (size_t)slot * nS;
+                PFB_HIP_CHECK(hipMemcpyAsync(snap, S, sizeof(double) * nS, hipMemcpyDeviceToHost, st));
                 PFB_HIP_CHECK(hipEventRecord(plan->pcg_ev[slot], st));
-                stale_h = true;
                 if (have_prev) {
-                    if (allreduce) {            // bounded: the same poll / probe / timeout as every other look
-                        const auto t0 = std::chrono::steady_clock::now();
-                        for (long spins = 0;; ++spins) {
-                            const hipError_t q = hipEventQuery(plan->pcg_ev[slot ^ 1]);
-                            if (q == hipSuccess) break;
-                            if (q != hipErrorNotReady) { set_error("pcg: hipEventQuery -> %s", hipGetErrorString(q)); return PFB_ERR_HIP; }
-                            if (spins < 4096) continue;
-                            if (allreduce(actx, nullptr, 0, (void*)st) != 0) return comm_fail("the exchange reported a failure");
-                            const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                            if (el > comm_timeout) { set_error("%s", ""); return comm_fail("no progress on the solver's stream (PFB_COMM_TIMEOUT_S)"); }
-                            usleep(el < 0.01 ? 20 : 500);
-                        }
-                    } else
-                    PFB_HIP_CHECK(hipEventSynchronize(plan->pcg_ev[slot ^ 1]));
-                    const double* hp = plan->pcg_pin + (size_t)(slot ^ 1) * S_NSCALAR;
-                    if (hp[S_DEAD] != 0.0) { status = PFB_PCG_BREAKDOWN; break; }
-                    if (hp[S_STOP] != 0.0) go = false;             // the iteration just enqueued changes nothing
+                    if ((err = sync.wait_event(plan->pcg_ev[slot ^ 1])) != PFB_OK) return err;
+                    seen = plan->pcg_pin + (size_t)(slot ^ 1) * nS;
+                    go = any_live(seen);       // if not, the iteration just enqueued changes nothing
+                    if (go) narrow(seen);      // an older snapshot: a system stopped there is stopped now as well
                 }
                 have_prev = true;
                 slot ^= 1;
                 continue;
             }
-            if ((err = fetch()) != PFB_OK) return err;
-            stale_h = false;
-            k = (int)h[S_K];
-            eps = h[S_EPS];
-            if (h[S_DEAD] != 0.0) { status = PFB_PCG_BREAKDOWN; break; }
-            go = (eps > tol || k < minit) && k < maxit;
+            if ((err = sync.fetch(h.data(), S, nS)) != PFB_OK) return err;
+            seen = h.data();
+            go = khost < maxit && any_live(seen);
+            if (go) narrow(seen);
         }
-        if (status >= 0 && stale_h && (err = fetch()) != PFB_OK) return err;
-        if (status < 0) {
-            // the direction built by the last iteration has not been looked at yet
-            if ((err = reduce_hook(S_ANY, 1)) != PFB_OK) return err;
-            hipLaunchKernelGGL(k_final_check, dim3(1), dim3(1), 0, st, S);
-            if ((err = fetch()) != PFB_OK) return err;
-            if (h[S_DEAD] != 0.0) status = PFB_PCG_BREAKDOWN;
+        // the direction a system's last iteration built has not been looked at yet (a system seen dead has none)
+        bool check = false;
+        for (int s = 0; s < nsys; ++s) check |= seen[(size_t)s * SB + S_DEAD] == 0.0 && seen[(size_t)s * SB + S_ZERO] == 0.0;
+        if (check) {
+            if ((err = sync.reduce(S + S_ANY, 1)) != PFB_OK) return err;
+            hipLaunchKernelGGL(k_final_check, dim3(1), dim3(64), 0, st, S, nsys);
+            PFB_HIP_CHECK(hipGetLastError());
         }
-        k = (int)h[S_K];
-        eps = h[S_EPS];
-        rho = h[S_RHO];
-        res->backtracks = (int)h[S_NBTSUM];
-        res->matvecs = 1 + k + (status == PFB_PCG_BREAKDOWN ? 1 : 0);
+        if (xc != x) PFB_HIP_CHECK(hipMemcpyAsync(x, xc, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (r_out) PFB_HIP_CHECK(hipMemcpyAsync(r_out, rc, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        return sync.fetch(h.data(), S, nS);
     }
-    while (backtrack == 1 && (eps > tol || k < minit) && k < maxit) {
-        // Ap = A(p); S_PAP = <p,Ap> (+ <r,Ap>, <Ap,Ap> for the predictive line search)  pcg.py:89-91
-        if (backtrack == 2)
-            err = pfb_psfconv_apply_dots(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, rcur, S + S_PAP, (void*)st);
-        else
+
+    // Exact backtracking: the reference's loop verbatim, driven from the host (one system; it needs the old x and r:
+    // the iterate lives alternately in x / xalt, r / ralt).  Leaves its outcome in h for report().
+    int run_exact() {
+        using PL = std::initializer_list<const void*>;
+        T *xcur = x, *rcur = r, *xnew = xalt, *rnew = ralt;
+        int err, G_used = 0, k = 0, nbt = 0;
+        double eps = 1.0, rho = h[S_RHO];
+        bool broke = false;
+        while (h[S_ZERO] == 0.0 && (eps > tol || k < minit) && k < maxit) {
+            // Ap = A(p); S_PAP = <p,Ap>                                                     pcg.py:89-91
             err = pfb_psfconv_apply(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, S + S_PAP, (void*)st);
-        if (err != PFB_OK) return err;
-        res->matvecs++;
-        if ((err = reduce_hook(S_PAP, backtrack == 2 ? 3 : 1)) != PFB_OK) return err;
-        if (backtrack == 2)
-            hipLaunchKernelGGL(k_alpha_predict, dim3(1), dim3(1), 0, st, S, mdiv_d);
-        else
+            if (err != PFB_OK) return err;
+            if ((err = sync.reduce(S + S_PAP, 1)) != PFB_OK) return err;
             hipLaunchKernelGGL(k_set_alpha, dim3(1), dim3(1), 0, st, S);
-        for (;;) {
-            PFB_LAUNCH_VEC(T, k_pcg_update, n, (PL{xcur, rcur, p, Ap, xnew, rnew}), (const T*)xcur,
-                           (const T*)rcur, (const T*)p, (const T*)Ap, xnew, rnew,
-                           (const double*)(S + S_ALPHA), mdiv);
-            hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 3, S + S_RHON);
-            if ((err = reduce_hook(S_RHON, 3)) != PFB_OK) return err;
-            if ((err = fetch()) != PFB_OK) return err;
-            if (backtrack == 2) { res->backtracks += (int)h[S_NBT]; break; }
-            if (backtrack && h[S_RHON] > rho) {          // pcg.py:96-101
+            for (;;) {
+                PFB_LAUNCH_VEC(T, k_pcg_update, n, (PL{xcur, rcur, p, Ap, xnew, rnew}), (const T*)xcur,
+                               (const T*)rcur, (const T*)p, (const T*)Ap, xnew, rnew,
+                               (const double*)(S + S_ALPHA), mdiv);
+                hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 3, S + S_RHON);
+                if ((err = sync.reduce(S + S_RHON, 3)) != PFB_OK) return err;
+                if ((err = sync.fetch(h.data(), S, S_NSCALAR)) != PFB_OK) return err;
+                if (!(h[S_RHON] > rho)) break;          // pcg.py:96-101
                 hipLaunchKernelGGL(k_scale_alpha, dim3(1), dim3(1), 0, st, S);
-                res->backtracks++;
+                ++nbt;
+            }
+            // accept x', r'
+            { T* t = xcur; xcur = xnew; xnew = t; t = rcur; rcur = rnew; rnew = t; }
+            // beta = rnorm_next / rnorm ; p = beta p - y      pcg.py:103-107
+            hipLaunchKernelGGL(k_set_beta, dim3(1), dim3(1), 0, st, S);
+            PFB_LAUNCH_VEC(T, k_pcg_dir, n, (PL{p, rcur}), p, (const T*)rcur, (const double*)(S + S_BETA), mdiv);
+            hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, S + S_ANY);
+            if ((err = sync.reduce(S + S_ANY, 1)) != PFB_OK) return err;
+            hipLaunchKernelGGL(k_accept_rho, dim3(1), dim3(1), 0, st, S);
+            rho = h[S_RHON];
+            const double num = h[S_NUM], den = h[S_DEN];
+            if ((err = sync.fetch(h.data(), S, S_NSCALAR)) != PFB_OK) return err;
+            if (h[S_ANY] == 0.0) { broke = true; break; }    // break BEFORE k += 1
+            k += 1;
+            eps = sqrt(num / (1e-12 + den));                 // norm_diff, misc.py:1326-1351
+        }
+        h[S_K] = k; h[S_EPS] = eps; h[S_RHO] = rho; h[S_NBTSUM] = nbt; h[S_DEAD] = broke ? 1.0 : 0.0;
+        if (xcur != x) PFB_HIP_CHECK(hipMemcpyAsync(x, xcur, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (r_out) PFB_HIP_CHECK(hipMemcpyAsync(r_out, rcur, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if ((err = sync.wait_stream()) != PFB_OK) return err;
+        PFB_HIP_CHECK(hipGetLastError());
+        return PFB_OK;
+    }
+
+    void report(pfb_pcg_result* res) const {
+        for (int s = 0; s < nsys; ++s) {
+            const double* Sb = h.data() + (size_t)s * SB;
+            pfb_pcg_result& o = res[s];
+            o.rnorm = Sb[S_RHO];
+            if (Sb[S_ZERO] != 0.0) {           // "Initial residual is zero": x untouched
+                o.status = PFB_PCG_ZERO_RESIDUAL;
+                o.matvecs = 1;
+                o.eps = 1.0;
                 continue;
             }
-            break;
+            const int k = (int)Sb[S_K];
+            const bool dead = Sb[S_DEAD] != 0.0;
+            o.status = dead ? PFB_PCG_BREAKDOWN : (k >= maxit ? PFB_PCG_MAXIT : PFB_PCG_CONVERGED);
+            o.iters = k;
+            o.eps = Sb[S_EPS];
+            o.backtracks = (int)Sb[S_NBTSUM];
+            o.matvecs = 1 + k + (dead ? 1 : 0);
         }
-        // accept x', r'
-        { T* t = xcur; xcur = xnew; xnew = t; t = rcur; rcur = rnew; rnew = t; }
-        // beta = rnorm_next / rnorm ; p = beta p - y      pcg.py:103-107
-        hipLaunchKernelGGL(k_set_beta, dim3(1), dim3(1), 0, st, S);
-        PFB_LAUNCH_VEC(T, k_pcg_dir, n, (PL{p, rcur}), p, (const T*)rcur, (const double*)(S + S_BETA), mdiv);
-        hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, S + S_ANY);
-        if ((err = reduce_hook(S_ANY, 1)) != PFB_OK) return err;
-        hipLaunchKernelGGL(k_accept_rho, dim3(1), dim3(1), 0, st, S);
-        const double rho_next = h[S_RHON], num = h[S_NUM], den = h[S_DEN];
-        if ((err = fetch()) != PFB_OK) return err;
-        if (h[S_ANY] == 0.0) {                           // break BEFORE k += 1
-            status = PFB_PCG_BREAKDOWN;
-            rho = rho_next;
-            break;
-        }
-        rho = rho_next;
-        k += 1;
-        eps = sqrt(num / (1e-12 + den));                 // norm_diff, misc.py:1326-1351
     }
-    if (status < 0) status = (k >= maxit) ? PFB_PCG_MAXIT : PFB_PCG_CONVERGED;
-    res->status = status;
-    res->iters = k;
-    res->eps = eps;
-    res->rnorm = rho;
-    if (xcur != (T*)x) PFB_HIP_CHECK(hipMemcpyAsync(x, xcur, n * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (r_out) PFB_HIP_CHECK(hipMemcpyAsync(r_out, rcur, n * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if ((err = wait_stream()) != PFB_OK) return err;
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
-
-// ------------------------------------------------------------------ batched per-band driver
-// workgroups per band of the per-band vector kernels: the whole grid stays near one 256-thread workgroup per CU
-// (stream_grid), split evenly over the bands; nb * gpb <= max(nb, RED_MAX_GRID) bounds the partials
-static int band_grid(size_t nvb, int nb) {
-    int g = stream_grid(nvb);
-    const int share = stream_grid((size_t)1 << 40) / nb;
-    if (g > share) g = share;
-    if (g > RED_MAX_GRID / nb) g = RED_MAX_GRID / nb;
-    return g < 1 ? 1 : g;
-}
-static size_t bands_state_bytes(int nb) { return ((size_t)nb * SB * sizeof(double) + 255) & ~(size_t)255; }
-static size_t bands_ws_doubles(int nb) { return 4 * (size_t)(nb > RED_MAX_GRID ? nb : RED_MAX_GRID); }
+};
 
 template <typename T>
-static int pcg_bands_impl(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
-                          const void* beam, double wsum, double sigmainv, double mdiv_d, double tol,
-                          int maxit, int minit, int backtrack, void* work, pfb_pcg_result* res, hipStream_t st) {
-    const size_t nband = (size_t)plan->nx * plan->ny, n = (size_t)nb * nband;
-    const size_t vb = vec_bytes(plan, nb);
-    char* w = (char*)work;
-    T* r = (T*)w;
-    T* p = (T*)(w + vb);
-    T* Ap = (T*)(w + 2 * vb);
-    double* S = (double*)(w + 3 * vb);
-    double* ws = (double*)(w + 3 * vb + bands_state_bytes(nb));
-    T* xs = (T*)x;
-    const T mdiv = (T)mdiv_d;
-    const size_t nS = (size_t)nb * SB;
-    std::vector<double> h(nS);
-    int err;
-
-    memset(res, 0, sizeof(*res) * nb);
-    PFB_HIP_CHECK(hipMemsetAsync(S, 0, sizeof(double) * nS, st));
-    auto fetch = [&]() -> int {
-        PFB_HIP_CHECK(hipMemcpyAsync(h.data(), S, sizeof(double) * nS, hipMemcpyDeviceToHost, st));
-        PFB_HIP_CHECK(hipStreamSynchronize(st));
-        return PFB_OK;
-    };
-    auto any_live = [&](const double* hs) {
-        for (int bl = 0; bl < nb; ++bl)
-            if (hs[(size_t)bl * SB + S_STOP] == 0.0 && hs[(size_t)bl * SB + S_DEAD] == 0.0) return true;
-        return false;
-    };
-
-    // per-band vector geometry: every band starts on a vector boundary when its length is a multiple of V
-    using PL = std::initializer_list<const void*>;
-    const bool vec = can_vec<T>(nband, PL{x, b, r, p, Ap});
-    const int V = vec ? V16<T>::N : 1;
-    const size_t nvb = nband / V;
-    const int gpb = band_grid(nvb, nb);
-
-    // r = A(x0) - b ; y = M r ; p = -y                       pcg.py:71-76, per band
-    err = pfb_psfconv_apply(plan, band0, nb, x, beam, wsum, sigmainv, r, nullptr, nullptr, (void*)st);
-    if (err != PFB_OK) return err;
-    if (vec)
-        hipLaunchKernelGGL((k_pcg_init_bands<T, V16<T>::N>), dim3(nb * gpb), dim3(RED_BLOCK), 0, st, r, (const T*)b, p,
-                           mdiv, nvb, gpb, ws);
-    else
-        hipLaunchKernelGGL((k_pcg_init_bands<T, 1>), dim3(nb * gpb), dim3(RED_BLOCK), 0, st, r, (const T*)b, p, mdiv,
-                           nvb, gpb, ws);
-    hipLaunchKernelGGL(k_init_bands, dim3(nb), dim3(128), 0, st, (const double*)ws, gpb, S, tol, (double)minit,
-                       (double)maxit);
-    PFB_HIP_CHECK(hipGetLastError());
-    if ((err = fetch()) != PFB_OK) return err;
-
-    // the loop of pcg_impl's sync-free driver, with a state block per band: the host only has to look once some band
-    // can stop (k >= minit), and then only at whether any band is still live
-    const bool xnt = n * sizeof(T) >= ((size_t)32 << 20);
-    bool go = (1.0 > tol || 0 < minit) && 0 < maxit && any_live(h.data());
-    bool lookahead = n <= ((size_t)16 << 20);
-    if (const char* la = getenv("PFB_PCG_LOOKAHEAD")) lookahead = atoi(la) != 0;
-    if (lookahead) {
-        if (!plan->pcg_pin) {
-            PFB_HIP_CHECK(hipHostMalloc((void**)&plan->pcg_pin, sizeof(double) * 2 * S_NSCALAR, hipHostMallocDefault));
-            PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[0], hipEventDisableTiming));
-            PFB_HIP_CHECK(hipEventCreateWithFlags(&plan->pcg_ev[1], hipEventDisableTiming));
-        }
-        if (plan->pcg_pin_bands_n < nb) {
-            if (plan->pcg_pin_bands) { PFB_HIP_CHECK(hipStreamSynchronize(st)); (void)hipHostFree(plan->pcg_pin_bands); }
-            plan->pcg_pin_bands = nullptr;
-            plan->pcg_pin_bands_n = 0;
-            PFB_HIP_CHECK(hipHostMalloc((void**)&plan->pcg_pin_bands, sizeof(double) * 2 * nS, hipHostMallocDefault));
-            plan->pcg_pin_bands_n = nb;
-        }
-    }
-    const int predict = backtrack == 2 ? 2 : 3;   // beta always comes from rho(alpha)
-    int khost = 0, slot = 0;
-    bool pending_end = false, have_prev = false;
-    // the span [lo, lo + nl) of bands that may still be live: narrowed at every host look, so that bands which have
-    // stopped at either end are no longer convolved (a stopped band between two live ones still is)
-    int lo = 0, nl = nb, gpl = gpb;
-    auto narrow = [&](const double* hs) {
-        int a = 0, z = nb;
-        while (a < z && !(hs[(size_t)a * SB + S_STOP] == 0.0 && hs[(size_t)a * SB + S_DEAD] == 0.0)) ++a;
-        while (z > a && !(hs[(size_t)(z - 1) * SB + S_STOP] == 0.0 && hs[(size_t)(z - 1) * SB + S_DEAD] == 0.0)) --z;
-        if (z > a && (a != lo || z - a != nl)) { lo = a; nl = z - a; gpl = band_grid(nvb, nl); }
-    };
-    while (go) {
-        const size_t off = (size_t)lo * nband;
-        double* Sl = S + (size_t)lo * SB;
-        err = psfconv_apply_partials_bands(plan, band0 + lo, nl, p + off, beam ? (const T*)beam + off : nullptr, wsum,
-                                           sigmainv, Ap + off, p + off, r + off, (void*)st);
-        if (err != PFB_OK) return err;
-        hipLaunchKernelGGL(k_iter_sums_bands, dim3(nl), dim3(256), 0, st, (const double*)plan->partials,
-                           plan->last_band_slots, plan->last_q_stride, plan->last_band_stride, (const double*)ws, gpl,
-                           pending_end ? 1 : 0, Sl, mdiv_d, predict);
-        pending_end = false;
-#define PFB_UPD_BANDS(VV, XN)                                                                                      \
-        hipLaunchKernelGGL((k_pcg_update_dir_bands<T, VV, 2, XN, XN>), dim3(nl * gpl), dim3(RED_BLOCK), 0, st,     \
-                           xs + off, r + off, p + off, (const T*)Ap + off, (const double*)Sl, mdiv, nvb, gpl, ws)
-        if (vec && xnt) PFB_UPD_BANDS(V16<T>::N, true);
-        else if (vec) PFB_UPD_BANDS(V16<T>::N, false);
-        else PFB_UPD_BANDS(1, false);
-#undef PFB_UPD_BANDS
-        if (khost + 1 < minit && khost + 1 < maxit)
-            pending_end = true;        // summed by the next iteration's k_iter_sums_bands (no look, so no narrowing, between)
-        else
-            hipLaunchKernelGGL(k_iter_end_bands, dim3(nl), dim3(256), 0, st, (const double*)ws, gpl, Sl);
-        PFB_HIP_CHECK(hipGetLastError());
-        ++khost;
-        if (khost < minit && khost < maxit) continue;          // no band can stop yet: no need to look
-        if (lookahead && khost < maxit) {
-            // one iteration ahead (pcg_impl): every band evaluates its rule on the device, so the iteration enqueued
-            // behind a band's stop changes nothing in it
-            double* snap = plan->pcg_pin_bands + (size_t)slot * nS;
-            PFB_HIP_CHECK(hipMemcpyAsync(snap, S, sizeof(double) * nS, hipMemcpyDeviceToHost, st));
-            PFB_HIP_CHECK(hipEventRecord(plan->pcg_ev[slot], st));
-            if (have_prev) {
-                PFB_HIP_CHECK(hipEventSynchronize(plan->pcg_ev[slot ^ 1]));
-                const double* hp = plan->pcg_pin_bands + (size_t)(slot ^ 1) * nS;
-                if (!any_live(hp)) go = false;
-                else narrow(hp);          // an older snapshot: a band stopped there is stopped now as well
-            }
-            have_prev = true;
-            slot ^= 1;
-            continue;
-        }
-        if ((err = fetch()) != PFB_OK) return err;
-        go = khost < maxit && any_live(h.data());
-        if (go) narrow(h.data());
-    }
-    hipLaunchKernelGGL(k_final_check_bands, dim3(1), dim3(64), 0, st, S, nb);
-    PFB_HIP_CHECK(hipGetLastError());
-    if (r_out) PFB_HIP_CHECK(hipMemcpyAsync(r_out, r, n * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if ((err = fetch()) != PFB_OK) return err;
-    for (int bl = 0; bl < nb; ++bl) {
-        const double* Sb = h.data() + (size_t)bl * SB;
-        pfb_pcg_result& o = res[bl];
-        o.rnorm = Sb[S_RHO];
-        if (Sb[SB_ZERO] != 0.0) {          // "Initial residual is zero": x untouched
-            o.status = PFB_PCG_ZERO_RESIDUAL;
-            o.matvecs = 1;
-            o.eps = 1.0;
-            continue;
-        }
-        const int k = (int)Sb[S_K];
-        const bool dead = Sb[S_DEAD] != 0.0;
-        o.status = dead ? PFB_PCG_BREAKDOWN : (k >= maxit ? PFB_PCG_MAXIT : PFB_PCG_CONVERGED);
-        o.iters = k;
-        o.eps = Sb[S_EPS];
-        o.backtracks = (int)Sb[S_NBTSUM];
-        o.matvecs = 1 + k + (dead ? 1 : 0);
-    }
-    return PFB_OK;
+static int pcg_solve(pfb_conv_plan* plan, int band0, int nb, bool per_band, const void* b, void* x, void* r_out,
+                     const void* beam, double wsum, double sigmainv, double mdiv, double tol, int maxit, int minit,
+                     int backtrack, size_t lookahead_max, void* work, pfb_allreduce_fn allreduce, void* actx,
+                     pfb_pcg_result* res, hipStream_t st) {
+    Pcg<T> s(plan, band0, nb, per_band, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit, work, allreduce,
+             actx, st);
+    PFB_REQUIRE(!allreduce || s.nsys == 1, PFB_ERR_INVALID, "pcg: an all-reduce hook needs the bands to be one system");
+    memset(res, 0, sizeof(*res) * s.nsys);
+    int err = s.init();
+    // beta always comes from rho(alpha) in the sync-free driver: predict 2 with, 3 without the line search
+    if (err == PFB_OK) err = backtrack == 1 ? s.run_exact() : s.run(backtrack == 2 ? 2 : 3, lookahead_max);
+    if (err == PFB_OK) s.report(res);
+    return err;
 }
 
 }  // namespace pfb
@@ -1173,10 +929,9 @@ int pfb_axpby(int dtype, double a, const void* x, double b, void* y, size_t n, v
     return dtype == PFB_F32 ? axpby_impl<float>(a, x, b, y, n, as_stream(stream))
                             : axpby_impl<double>(a, x, b, y, n, as_stream(stream));
 }
-
 size_t pfb_pcg_work_bytes(const pfb_conv_plan* plan, int nb) {
     if (!plan || nb <= 0) return 0;
-    return 5 * vec_bytes(plan, nb) + sizeof(double) * (64 + PFB_REDUCE_WS_DOUBLES);
+    return 5 * vec_bytes(plan, nb) + state_bytes(1) + ws_bytes(1);
 }
 
 int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
@@ -1188,18 +943,17 @@ int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x
                 "pcg_solve: band range [%d,%d) outside plan", band0, band0 + nb);
     PFB_REQUIRE((reinterpret_cast<uintptr_t>(work) & 255u) == 0, PFB_ERR_INVALID,
                 "pcg_solve: work must be 256-byte aligned");
+    const size_t la = (size_t)4 << 20;         // elements up to which the host looks one iteration late
     if (plan->dtype == PFB_F32)
-        return pcg_impl<float>(plan, band0, nb, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit,
-                               minit, backtrack, work, allreduce, allreduce_ctx, result,
-                               as_stream(stream));
-    return pcg_impl<double>(plan, band0, nb, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit,
-                            minit, backtrack, work, allreduce, allreduce_ctx, result,
-                            as_stream(stream));
+        return pcg_solve<float>(plan, band0, nb, false, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
+                                backtrack, la, work, allreduce, allreduce_ctx, result, as_stream(stream));
+    return pcg_solve<double>(plan, band0, nb, false, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
+                             backtrack, la, work, allreduce, allreduce_ctx, result, as_stream(stream));
 }
 
 size_t pfb_pcg_bands_work_bytes(const pfb_conv_plan* plan, int nb) {
     if (!plan || nb <= 0) return 0;
-    return 3 * vec_bytes(plan, nb) + bands_state_bytes(nb) + sizeof(double) * bands_ws_doubles(nb);
+    return 3 * vec_bytes(plan, nb) + state_bytes(nb) + ws_bytes(nb);
 }
 
 int pfb_pcg_solve_bands(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
@@ -1213,11 +967,12 @@ int pfb_pcg_solve_bands(pfb_conv_plan* plan, int band0, int nb, const void* b, v
     PFB_REQUIRE(backtrack != 1, PFB_ERR_UNSUPPORTED,
                 "pcg_solve_bands: backtrack=1 (the exact loop) is not batched; solve band by band with pfb_pcg_solve");
     PFB_REQUIRE(backtrack == 0 || backtrack == 2, PFB_ERR_INVALID, "pcg_solve_bands: backtrack must be 0 or 2");
+    const size_t la = (size_t)16 << 20;
     if (plan->dtype == PFB_F32)
-        return pcg_bands_impl<float>(plan, band0, nb, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
-                                     backtrack, work, results, as_stream(stream));
-    return pcg_bands_impl<double>(plan, band0, nb, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
-                                  backtrack, work, results, as_stream(stream));
+        return pcg_solve<float>(plan, band0, nb, true, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
+                                backtrack, la, work, nullptr, nullptr, results, as_stream(stream));
+    return pcg_solve<double>(plan, band0, nb, true, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
+                             backtrack, la, work, nullptr, nullptr, results, as_stream(stream));
 }
 
 }  // extern "C"

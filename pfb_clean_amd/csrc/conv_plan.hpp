@@ -44,13 +44,11 @@ struct pfb_conv_plan {
     // optional per-stage timing (bench.py roofline): 4 events per apply, up to PROF_MAX applies
     int prof_on, prof_n, prof_tick;   // prof_on = sampling period (every prof_on-th apply is timed)
     hipEvent_t* prof_ev;
-    // PCG driver (cgvec.hip): pinned snapshots of the solver's state block + their events, for looking at
-    // iteration j-1 while iteration j is already enqueued (created on first use)
+    // PCG driver (cgvec.hip): two pinned snapshots of the solver's `pcg_pin_n` state blocks + their events, for looking
+    // at iteration j-1 while iteration j is already enqueued (created on first use, grown on demand)
     double* pcg_pin;
+    int pcg_pin_n;
     hipEvent_t pcg_ev[2];
-    // batched per-band driver (pfb_pcg_solve_bands): the same snapshots for nb state blocks (grown on demand)
-    double* pcg_pin_bands;
-    int pcg_pin_bands_n;
 };
 
 namespace pfb {
@@ -65,12 +63,9 @@ inline void prof_mark(pfb_conv_plan* p, hipStream_t st, int k) {
         p->prof_tick++;
     }
 }
-// fftconv.hip: convolution + fused dots left un-summed in plan->partials (see there)
+// fftconv.hip: convolution + fused dots left un-summed in plan->partials (see there).  The PCG's systems are the bands
+// (`per_band`) or the whole range is one; system s's `bs` partials of quantity q start at q * qs + s * bst
 int psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                            double wsum, double sigmainv, void* out, const void* dot_with,
-                           const void* dot_with2, void* stream);
-// the same with partials that each belong to ONE band (layout: plan->last_band_slots / _q_stride / _band_stride)
-int psfconv_apply_partials_bands(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
-                                 double wsum, double sigmainv, void* out, const void* dot_with,
-                                 const void* dot_with2, void* stream);
+                           const void* dot_with2, bool per_band, int* bs, int* qs, int* bst, void* stream);
 }  // namespace pfb

@@ -547,12 +547,8 @@ int pfb_psfconv_plan_destroy(pfb_conv_plan* p) {
         for (int k = 0; k < 4 * PROF_MAX; ++k) (void)hipEventDestroy(p->prof_ev[k]);
         free(p->prof_ev);
     }
-    if (p->pcg_pin_bands) (void)hipHostFree(p->pcg_pin_bands);
-    if (p->pcg_pin) {
-        (void)hipHostFree(p->pcg_pin);
-        (void)hipEventDestroy(p->pcg_ev[0]);
-        (void)hipEventDestroy(p->pcg_ev[1]);
-    }
+    if (p->pcg_pin) (void)hipHostFree(p->pcg_pin);
+    for (int e = 0; e < 2; ++e) if (p->pcg_ev[e]) (void)hipEventDestroy(p->pcg_ev[e]);
     free(p);
     return PFB_OK;
 }
@@ -747,18 +743,18 @@ int pfb_psfconv_apply_dots_bands(pfb_conv_plan* p, int band0, int nb, const void
 }  // extern "C"
 
 // internal (cgvec.hip): the convolution with its three fused dots left as per-workgroup partials in
-// plan->partials ([3][plan->last_npartials]) -- the PCG driver sums them in the same launch that does
-// its per-iteration scalar bookkeeping
+// plan->partials -- the PCG driver sums them in the same launch that does its per-iteration scalar
+// bookkeeping.  per_band: every partial belongs to ONE band (a system per band); otherwise the range is one system and
+// all plan->last_npartials slots of a quantity are its partials
 int pfb::psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                                 double wsum, double sigmainv, void* out, const void* dot_with,
-                                const void* dot_with2, void* stream) {
+                                const void* dot_with2, bool per_band, int* bs, int* qs, int* bst, void* stream) {
     PFB_REQUIRE(dot_with, PFB_ERR_INVALID, "apply_partials: dot_with is required");
-    return apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, nullptr, 0, stream);
-}
-
-int pfb::psfconv_apply_partials_bands(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
-                                      double wsum, double sigmainv, void* out, const void* dot_with,
-                                      const void* dot_with2, void* stream) {
-    PFB_REQUIRE(dot_with, PFB_ERR_INVALID, "apply_partials_bands: dot_with is required");
-    return apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, nullptr, 0, stream, true);
+    const int rc = apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, nullptr, 0, stream,
+                                per_band);
+    if (rc != PFB_OK) return rc;
+    *bs = per_band ? p->last_band_slots : p->last_npartials;
+    *qs = per_band ? p->last_q_stride : p->last_npartials;
+    *bst = per_band ? p->last_band_stride : 0;
+    return PFB_OK;
 }

@@ -1,5 +1,6 @@
-// pcg_state.hpp -- the device-resident scalar state of pfb_pcg_solve (cgvec.hip) and the per-iteration bookkeeping on
-// it.
+// pcg_state.hpp -- the device-resident scalar state of the PCG driver (cgvec.hip) and the per-iteration bookkeeping on
+// it.  A SYSTEM is a contiguous run of bands that is solved as one PCG -- the whole cube (pfb_pcg_solve) or one band
+// (pfb_pcg_solve_bands) -- and owns one state block of SB doubles, S + s * SB.
 #pragma once
 #include "common.hpp"
 
@@ -14,8 +15,14 @@ enum { S_PAP = 0, S_RAP = 1, S_APAP = 2,          // <p,Ap>, <r,Ap>, <Ap,Ap>   (
        S_K = 12, S_EPS = 13, S_EPSP = 14, S_NBTSUM = 15,
        S_STOP = 16,                               // the stopping rule fired on the device: later work is a no-op
        S_TOL = 17, S_MINIT = 18, S_MAXIT = 19,    // the rule's parameters (set once per solve)
-       S_NSCALAR = 20 };
+       S_ZERO = 20,                               // the initial residual was zero: the system never iterates
+       S_NSCALAR = 21 };
+constexpr int SB = 32;                            // doubles per state block
+static_assert(S_NSCALAR <= SB, "state block too small");
 
+// a system that has stopped (S_STOP) or broken down (S_DEAD) is neither read nor written, and its state is left as the
+// iteration that stopped it left it
+__device__ __host__ __forceinline__ bool sys_live(const double* Sb) { return Sb[S_DEAD] == 0.0 && Sb[S_STOP] == 0.0; }
 
 // ---- device-side loop bookkeeping of the sync-free driver
 __device__ __forceinline__ void iter_begin_dev(double* S, double mdiv, int predict) {
@@ -41,9 +48,8 @@ __device__ __forceinline__ void iter_begin_dev(double* S, double mdiv, int predi
         S[S_BETA] = (rho + (2.0 * alpha * S[S_RAP] + alpha * alpha * S[S_APAP]) / d) / rho;
     }
 }
-__device__ __forceinline__ void iter_end_dev(double* S, int fused) {
+__device__ __forceinline__ void iter_end_dev(double* S) {
     if (S[S_DEAD] != 0.0 || S[S_STOP] != 0.0) return;
-    if (!fused) S[S_BETA] = S[S_RHON] / S[S_RHO];
     S[S_RHO] = S[S_RHON];
     const double k = S[S_K] + 1.0;
     const double eps = sqrt(S[S_NUM] / (1e-12 + S[S_DEN]));

@@ -135,6 +135,46 @@ class _Work:
         return w
 
 
+class _Staged:
+    """What pcg_fused and pcg_fused_bands share around the native call: the checks on b, the contiguous copies, the
+    embedded plan's padding, the work buffer, and the way back (crop)."""
+
+    def __init__(self, A, b3, x0, return_resid, bands=False):
+        self.plan = plan = A.plan
+        b3 = b3.contiguous()
+        if bands and b3.ndim != 3:
+            raise ValueError("pcg_fused_bands expects (nb, nx, ny) arrays")
+        self.nb = nb = b3.shape[0]
+        if nb != A.nb:
+            raise ValueError(f"b has {nb} bands, operator has {A.nb}")
+        if b3.dtype != plan.rdtype:
+            raise TypeError(f"b is {b3.dtype}, operator is {plan.rdtype}")
+        x = torch.zeros_like(b3) if x0 is None else x0.contiguous().clone()
+        beam = A.beam
+        if plan.embed is not None:
+            # Embedded plan (arbitrary size on the power-of-two kernels, operators/psf.py): solve in the
+            # zero-padded domain with a beam that is ZERO outside the image.  There A' x' = sigmainv x',
+            # b' = 0 and x0' = 0, so r, y, p stay exactly zero outside and every inner product, step
+            # length and stopping decision equals the un-padded solve's.
+            b3, x = plan._pad(b3, nb), plan._pad(x, nb)
+            beam = plan._pad(torch.ones((nb, plan.nx, plan.ny), dtype=plan.rdtype, device=b3.device)
+                             if beam is None else beam, nb)
+        self.b, self.x, self.beam = b3, x, beam
+        self.r = torch.empty_like(b3) if return_resid else None
+        self.work = _Work.get(plan, nb, bands=bands)
+        # band0, nb, b, x, r_out, beam, wsum, sigmainv: the arguments both entry points start with
+        self.args = (A.band0, nb, _dev.ptr(b3), _dev.ptr(x), _dev.ptr(self.r), _dev.ptr(beam),
+                     A.wsum if A.wsum is not None else 0.0, A.sigmainv)
+
+    def result(self):
+        """(x, r|None) in the caller's domain."""
+        x, r, plan = self.x, self.r, self.plan
+        if plan.embed is not None:
+            x = x[:, :plan.nx, :plan.ny].contiguous()
+            r = None if r is None else r[:, :plan.nx, :plan.ny].contiguous()
+        return x, r
+
+
 def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack=True,
               return_resid=False, group=None, distributed=False):
     """Run pfb_pcg_solve.  b, x0: GPU tensors (nb, nx, ny) | (nx, ny).  Returns
@@ -144,36 +184,19 @@ def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack
     lib = _lib.load()
     plan = A.plan
     squeeze = b.ndim == 2
-    b3 = (b[None] if squeeze else b).contiguous()
-    nb = b3.shape[0]
-    if nb != A.nb:
-        raise ValueError(f"b has {nb} bands, operator has {A.nb}")
-    if b3.dtype != plan.rdtype:
-        raise TypeError(f"b is {b3.dtype}, operator is {plan.rdtype}")
-    x = torch.zeros_like(b3) if x0 is None else (x0[None] if squeeze else x0).contiguous().clone()
-    beam = A.beam
-    if plan.embed is not None:
-        # Embedded plan (arbitrary size on the power-of-two kernels, operators/psf.py): solve in the
-        # zero-padded domain with a beam that is ZERO outside the image.  There A' x' = sigmainv x',
-        # b' = 0 and x0' = 0, so r, y, p stay exactly zero outside and every inner product, step
-        # length and stopping decision equals the un-padded solve's.
-        b3, x = plan._pad(b3, nb), plan._pad(x, nb)
-        beam = plan._pad(torch.ones((nb, plan.nx, plan.ny), dtype=plan.rdtype, device=b3.device)
-                         if beam is None else beam, nb)
-    r = torch.empty_like(b3) if return_resid else None
-    work = _Work.get(plan, nb)
+    s = _Staged(A, b[None] if squeeze else b, x0[None] if squeeze and x0 is not None else x0, return_resid)
     res = _lib.PcgResult()
     cb_ctx = None
     native = None
     if distributed:
         from ..dist import AllReduceHook, native_comm
-        native = native_comm(group, b3.device) if b3.is_cuda else None
+        native = native_comm(group, s.b.device) if s.b.is_cuda else None
     if not distributed:
         cb = _lib.ALLREDUCE_FN(0)
     elif native is not None:             # RCCL from C on the solver's stream: nothing on the host per iteration
         cb, cb_ctx = native.fn, native.ctx
     else:
-        allreduce = AllReduceHook(work, group)
+        allreduce = AllReduceHook(s.work, group)
 
         def _hook(ctx, buf, count, stream):
             try:
@@ -186,17 +209,13 @@ def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack
         cb = _lib.ALLREDUCE_FN(_hook)
     with plan.lock:            # a plan is single-owner (include/pfb_hip.h): one solve at a time per plan
         plan._enter_stream()
-        _lib.check(lib.pfb_pcg_solve(plan.handle, A.band0, nb, _dev.ptr(b3), _dev.ptr(x), _dev.ptr(r),
-                                     _dev.ptr(beam), A.wsum if A.wsum is not None else 0.0,
-                                     A.sigmainv, float(mdiv), float(tol), int(maxit), int(minit),
-                                     _backtrack_mode(backtrack), _dev.ptr(work), cb, cb_ctx, C.byref(res),
+        _lib.check(lib.pfb_pcg_solve(plan.handle, *s.args, float(mdiv), float(tol), int(maxit), int(minit),
+                                     _backtrack_mode(backtrack), _dev.ptr(s.work), cb, cb_ctx, C.byref(res),
                                      _dev.stream()))
     if distributed:                  # bench.py reports which exchange ran and what the hook costs the host
         res.exchange = 'rccl-native' if native is not None else 'torch-hook'
         res.hook_calls, res.hook_host_s = (0, 0.0) if native is not None else (allreduce.calls, allreduce.host_s)
-    if plan.embed is not None:
-        x = x[:, :plan.nx, :plan.ny].contiguous()
-        r = None if r is None else r[:, :plan.nx, :plan.ny].contiguous()
+    x, r = s.result()
     if squeeze:
         x = x[0]
         r = None if r is None else r[0]
@@ -211,32 +230,13 @@ def pcg_fused_bands(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, bac
     PFB_PCG_EXACT_BACKTRACK=1) has no batched form: the library raises PfbHipError (unsupported)."""
     lib = _lib.load()
     plan = A.plan
-    b3 = b.contiguous()
-    if b3.ndim != 3:
-        raise ValueError("pcg_fused_bands expects (nb, nx, ny) arrays")
-    nb = b3.shape[0]
-    if nb != A.nb:
-        raise ValueError(f"b has {nb} bands, operator has {A.nb}")
-    if b3.dtype != plan.rdtype:
-        raise TypeError(f"b is {b3.dtype}, operator is {plan.rdtype}")
-    x = torch.zeros_like(b3) if x0 is None else x0.contiguous().clone()
-    beam = A.beam
-    if plan.embed is not None:       # zero-padded domain with a beam that is zero outside the image (pcg_fused)
-        b3, x = plan._pad(b3, nb), plan._pad(x, nb)
-        beam = plan._pad(torch.ones((nb, plan.nx, plan.ny), dtype=plan.rdtype, device=b3.device)
-                         if beam is None else beam, nb)
-    r = torch.empty_like(b3) if return_resid else None
-    work = _Work.get(plan, nb, bands=True)
-    res = (_lib.PcgResult * nb)()
+    s = _Staged(A, b, x0, return_resid, bands=True)
+    res = (_lib.PcgResult * s.nb)()
     with plan.lock:
         plan._enter_stream()
-        _lib.check(lib.pfb_pcg_solve_bands(plan.handle, A.band0, nb, _dev.ptr(b3), _dev.ptr(x), _dev.ptr(r),
-                                           _dev.ptr(beam), A.wsum if A.wsum is not None else 0.0, A.sigmainv,
-                                           float(mdiv), float(tol), int(maxit), int(minit),
-                                           _backtrack_mode(backtrack), _dev.ptr(work), res, _dev.stream()))
-    if plan.embed is not None:
-        x = x[:, :plan.nx, :plan.ny].contiguous()
-        r = None if r is None else r[:, :plan.nx, :plan.ny].contiguous()
+        _lib.check(lib.pfb_pcg_solve_bands(plan.handle, *s.args, float(mdiv), float(tol), int(maxit), int(minit),
+                                           _backtrack_mode(backtrack), _dev.ptr(s.work), res, _dev.stream()))
+    x, r = s.result()
     return x, r, list(res)
 
 
@@ -518,27 +518,25 @@ def pcg_psf(psfhat, b, x0, beam, lastsize, nthreads, sigmainv, cgopts, compute=T
     verbosity = opts.pop('verbosity', 1)
     opts.pop('report_freq', None)
     mdiv = sigmainv if sigmainv > 0 else 0.0
-    if _backtrack_mode(opts.get('backtrack', True)) != 1 and _bands_batched(plan):
-        A = HessianPsf(plan, nx, ny, lastsize, beam=beamd, sigmainv=sigmainv, band0=0, nb=nband)
-        x, _, results = pcg_fused_bands(A, bd, x0d, mdiv=mdiv, **opts)
-        for k, res in enumerate(results):
-            status = _lib.PCG_STATUS[res.status]
-            if status == 'zero-residual':
-                _log("Initial residual is zero", verbosity)
-                model[k] = x0d[k]
-            else:
-                _report(status, res.iters, res.eps, verbosity)
-                model[k] = x[k]
-        return _dev.host_like(model, b)
-    for k in range(nband):
-        A = HessianPsf(plan, nx, ny, lastsize, beam=None if beamd is None else beamd[k:k + 1],
-                       sigmainv=sigmainv, band0=k, nb=1)
-        x, _, res = pcg_fused(A, bd[k:k + 1], x0d[k:k + 1], mdiv=mdiv, **opts)
+
+    def deliver(k, res, xk):
         status = _lib.PCG_STATUS[res.status]
         if status == 'zero-residual':
             _log("Initial residual is zero", verbosity)
             model[k] = x0d[k]
         else:
             _report(status, res.iters, res.eps, verbosity)
-            model[k] = x[0]
+            model[k] = xk
+
+    if _backtrack_mode(opts.get('backtrack', True)) != 1 and _bands_batched(plan):
+        A = HessianPsf(plan, nx, ny, lastsize, beam=beamd, sigmainv=sigmainv, band0=0, nb=nband)
+        x, _, results = pcg_fused_bands(A, bd, x0d, mdiv=mdiv, **opts)
+        for k, res in enumerate(results):
+            deliver(k, res, x[k])
+        return _dev.host_like(model, b)
+    for k in range(nband):
+        A = HessianPsf(plan, nx, ny, lastsize, beam=None if beamd is None else beamd[k:k + 1],
+                       sigmainv=sigmainv, band0=k, nb=1)
+        x, _, res = pcg_fused(A, bd[k:k + 1], x0d[k:k + 1], mdiv=mdiv, **opts)
+        deliver(k, res, x[0])
     return _dev.host_like(model, b)
