@@ -10,6 +10,8 @@
 // workgroup -> single-workgroup final sum in a fixed order), scalars stay in device
 // memory (alpha, beta are read by the kernels from there), the p.Ap product comes
 // fused out of the convolution epilogue (fftconv*.hip).
+// The 16-byte packs (V16, Pack, ld / st and their non-temporal forms), can_vec, emit_partials and k_final_sum live in
+// common.hpp, shared with the prox / primal-dual kernels of wavelet.hip.
 #include "conv_plan.hpp"
 #include "pcg_state.hpp"
 #include <chrono>
@@ -21,7 +23,6 @@
 
 namespace pfb {
 
-constexpr int RED_BLOCK = 256;
 constexpr int RED_MAX_GRID = 1024;
 
 static inline int red_grid(size_t nvec) {
@@ -30,87 +31,6 @@ static inline int red_grid(size_t nvec) {
     if (g < 1) g = 1;
     if (g > (size_t)RED_MAX_GRID) g = RED_MAX_GRID;   // 4 sums x grid <= PFB_REDUCE_WS_DOUBLES
     return (int)g;
-}
-
-// 16-byte vector view of T
-template <typename T> struct V16;
-template <> struct V16<float>  { using type = float4;  static constexpr int N = 4; };
-template <> struct V16<double> { using type = double2; static constexpr int N = 2; };
-
-template <typename T, int V> struct Pack { T e[V]; };
-
-template <typename T, int V>
-__device__ __forceinline__ Pack<T, V> ld(const T* p, size_t i) {
-    Pack<T, V> r;
-    if constexpr (V == 1) {
-        r.e[0] = p[i];
-    } else {
-        using VT = typename V16<T>::type;
-        VT v = reinterpret_cast<const VT*>(p)[i];
-        memcpy(&r, &v, sizeof(VT));
-    }
-    return r;
-}
-template <typename T, int V>
-__device__ __forceinline__ void st(T* p, size_t i, const Pack<T, V>& r) {
-    if constexpr (V == 1) {
-        p[i] = r.e[0];
-    } else {
-        using VT = typename V16<T>::type;
-        VT v;
-        memcpy(&v, &r, sizeof(VT));
-        reinterpret_cast<VT*>(p)[i] = v;
-    }
-}
-
-// non-temporal forms (global_load / global_store ... nt) for streams that are touched once per iteration and are not
-// re-read before ~256 MiB of other traffic has passed: they should not displace what IS re-read soon (at one band per
-// GPU the half spectrum T, p and A p live in the Infinity Cache between kernels)
-template <typename T, int V>
-__device__ __forceinline__ Pack<T, V> ld_nt(const T* p, size_t i) {
-    Pack<T, V> r;
-    if constexpr (V == 1) {
-        r.e[0] = __builtin_nontemporal_load(p + i);
-    } else {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p) + i);
-        memcpy(&r, &v, 16);
-    }
-    return r;
-}
-template <typename T, int V>
-__device__ __forceinline__ void st_nt(T* p, size_t i, const Pack<T, V>& r) {
-    if constexpr (V == 1) {
-        __builtin_nontemporal_store(r.e[0], p + i);
-    } else {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        v4f v;
-        memcpy(&v, &r, 16);
-        __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(p) + i);
-    }
-}
-
-// write NQ block results to ws[q * gridDim.x + blockIdx.x]
-template <int NQ>
-__device__ __forceinline__ void emit_partials(double (&acc)[NQ], double* __restrict__ ws) {
-    __shared__ double red[NQ * (RED_BLOCK / 64)];
-    block_sum<NQ>(acc, red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) ws[(size_t)q * gridDim.x + blockIdx.x] = acc[q];
-    }
-}
-
-// final stage: out[q] = sum_g ws[q*G + g], q < nq, fixed order
-__global__ void __launch_bounds__(RED_BLOCK)
-k_final_sum(const double* __restrict__ ws, int G, int nq, double* __restrict__ out) {
-    __shared__ double red[RED_BLOCK / 64];
-    for (int q = 0; q < nq; ++q) {
-        double acc[1] = {0.0};
-        for (int g = threadIdx.x; g < G; g += blockDim.x) acc[0] += ws[(size_t)q * G + g];
-        block_sum<1>(acc, red);
-        if (threadIdx.x == 0) out[q] = acc[0];
-    }
 }
 
 template <typename T, int V>
@@ -443,15 +363,6 @@ __global__ void k_final_check(double* S, int nsys) {
     }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-template <typename T>
-static inline bool can_vec(size_t n, std::initializer_list<const void*> ptrs) {
-    if (n % V16<T>::N) return false;
-    for (const void* p : ptrs) if (p && !aligned16(p)) return false;
-    return true;
-}
-
 // ------------------------------------------------------------------ launch helpers
 #define PFB_LAUNCH_VEC(T, kern, n, ptrs, ...)                                              \
     do {                                                                                   \
@@ -474,7 +385,7 @@ static int dot_impl(const void* a, const void* b, size_t n, double* out, double*
     int G_used = 0;
     using PL = std::initializer_list<const void*>;
     PFB_LAUNCH_VEC(T, k_dot, n, (PL{a, b}), (const T*)a, (const T*)b);
-    hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, out);
+    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, out);
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;
 }
@@ -483,7 +394,7 @@ static int nd_impl(const void* x, const void* xp, size_t n, double* out, double*
     int G_used = 0;
     using PL = std::initializer_list<const void*>;
     PFB_LAUNCH_VEC(T, k_norm_diff, n, (PL{x, xp}), (const T*)x, (const T*)xp);
-    hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 2, out);
+    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 2, out);
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;
 }
@@ -492,7 +403,7 @@ static int any_impl(const void* a, size_t n, double* out, double* ws, hipStream_
     int G_used = 0;
     using PL = std::initializer_list<const void*>;
     PFB_LAUNCH_VEC(T, k_any, n, (PL{a}), (const T*)a);
-    hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, out);
+    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, out);
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;
 }
@@ -517,12 +428,7 @@ static int axpby_impl(double a, const void* x, double b, void* y, size_t n, hipS
 // per HBM channel -- not with the chip oversubscribed: 256 workgroups 0.60 ms, 1024 0.78 ms at
 // 8 x 4096^2 fp32.  Returns the grid (= number of partial sums per quantity).
 static int stream_grid(size_t nvec) {
-    static const int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
+    const int ncu = device_cu_count();
     size_t g = (nvec + RED_BLOCK - 1) / RED_BLOCK;
     g = (g + 3) / 4;
     if (g < 1) g = 1;
@@ -831,7 +737,7 @@ struct Pcg {
                 PFB_LAUNCH_VEC(T, k_pcg_update, n, (PL{xcur, rcur, p, Ap, xnew, rnew}), (const T*)xcur,
                                (const T*)rcur, (const T*)p, (const T*)Ap, xnew, rnew,
                                (const double*)(S + S_ALPHA), mdiv);
-                hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 3, S + S_RHON);
+                hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 3, S + S_RHON);
                 if ((err = sync.reduce(S + S_RHON, 3)) != PFB_OK) return err;
                 if ((err = sync.fetch(h.data(), S, S_NSCALAR)) != PFB_OK) return err;
                 if (!(h[S_RHON] > rho)) break;          // pcg.py:96-101
@@ -843,7 +749,7 @@ struct Pcg {
             // beta = rnorm_next / rnorm ; p = beta p - y      pcg.py:103-107
             hipLaunchKernelGGL(k_set_beta, dim3(1), dim3(1), 0, st, S);
             PFB_LAUNCH_VEC(T, k_pcg_dir, n, (PL{p, rcur}), p, (const T*)rcur, (const double*)(S + S_BETA), mdiv);
-            hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, S + S_ANY);
+            hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, S + S_ANY);
             if ((err = sync.reduce(S + S_ANY, 1)) != PFB_OK) return err;
             hipLaunchKernelGGL(k_accept_rho, dim3(1), dim3(1), 0, st, S);
             rho = h[S_RHON];

@@ -5,6 +5,8 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cmath>
+#include <cstring>
+#include <initializer_list>
 #include "../../include/pfb_hip.h"
 
 namespace pfb {
@@ -165,6 +167,118 @@ __device__ __forceinline__ void block_sum(double (&v)[NQ], double* red) {
         }
     }
     __syncthreads();
+}
+
+// ------------------------------------------- streaming elementwise kernels with fp64 partial sums
+// The layer under the PCG vector kernels (cgvec.hip) and the prox / primal-dual kernels (wavelet.hip): 16-byte packs,
+// one partial sum per workgroup and quantity, a single-workgroup final sum in a fixed order.  Templates and inline
+// functions only: a translation unit that does not use them compiles as if they were not here.
+constexpr int RED_BLOCK = 256;          // threads per workgroup of every kernel that ends in emit_partials
+
+// 16-byte vector view of T
+template <typename T> struct V16;
+template <> struct V16<float>  { using type = float4;  static constexpr int N = 4; };
+template <> struct V16<double> { using type = double2; static constexpr int N = 2; };
+
+template <typename T, int V> struct Pack { T e[V]; };
+
+template <typename T, int V>
+__device__ __forceinline__ Pack<T, V> ld(const T* p, size_t i) {
+    Pack<T, V> r;
+    if constexpr (V == 1) {
+        r.e[0] = p[i];
+    } else {
+        using VT = typename V16<T>::type;
+        VT v = reinterpret_cast<const VT*>(p)[i];
+        memcpy(&r, &v, sizeof(VT));
+    }
+    return r;
+}
+template <typename T, int V>
+__device__ __forceinline__ void st(T* p, size_t i, const Pack<T, V>& r) {
+    if constexpr (V == 1) {
+        p[i] = r.e[0];
+    } else {
+        using VT = typename V16<T>::type;
+        VT v;
+        memcpy(&v, &r, sizeof(VT));
+        reinterpret_cast<VT*>(p)[i] = v;
+    }
+}
+
+// non-temporal forms (global_load / global_store ... nt) for streams that are touched once per iteration and are not
+// re-read before ~256 MiB of other traffic has passed: they should not displace what IS re-read soon (at one band per
+// GPU the half spectrum T, p and A p live in the Infinity Cache between kernels)
+template <typename T, int V>
+__device__ __forceinline__ Pack<T, V> ld_nt(const T* p, size_t i) {
+    Pack<T, V> r;
+    if constexpr (V == 1) {
+        r.e[0] = __builtin_nontemporal_load(p + i);
+    } else {
+        typedef float v4f __attribute__((ext_vector_type(4)));
+        const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p) + i);
+        memcpy(&r, &v, 16);
+    }
+    return r;
+}
+template <typename T, int V>
+__device__ __forceinline__ void st_nt(T* p, size_t i, const Pack<T, V>& r) {
+    if constexpr (V == 1) {
+        __builtin_nontemporal_store(r.e[0], p + i);
+    } else {
+        typedef float v4f __attribute__((ext_vector_type(4)));
+        v4f v;
+        memcpy(&v, &r, 16);
+        __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(p) + i);
+    }
+}
+
+// write NQ block results to ws[q * gridDim.x + blockIdx.x]
+template <int NQ>
+__device__ __forceinline__ void emit_partials(double (&acc)[NQ], double* __restrict__ ws) {
+    __shared__ double red[NQ * (RED_BLOCK / 64)];
+    block_sum<NQ>(acc, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) ws[(size_t)q * gridDim.x + blockIdx.x] = acc[q];
+    }
+}
+
+// final stage: out[q] = sum_g ws[q*G + g], q < nq, fixed order; one workgroup of BLOCK threads.  A template, so that
+// only the translation units that launch it emit it
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK)
+k_final_sum(const double* __restrict__ ws, int G, int nq, double* __restrict__ out) {
+    __shared__ double red[BLOCK / 64];
+    for (int q = 0; q < nq; ++q) {
+        double acc[1] = {0.0};
+        for (int g = threadIdx.x; g < G; g += blockDim.x) acc[0] += ws[(size_t)q * G + g];
+        block_sum<1>(acc, red);
+        if (threadIdx.x == 0) out[q] = acc[0];
+    }
+}
+
+// host side: which launches may use the 16-byte form
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// n a multiple of the vector width and every (non-null) pointer 16-byte aligned
+template <typename T>
+inline bool can_vec(size_t n, std::initializer_list<const void*> ptrs) {
+    if (n % V16<T>::N) return false;
+    for (const void* p : ptrs) if (p && !aligned16(p)) return false;
+    return true;
+}
+
+// compute units of the current device (looked up once; 256 when the query fails): the grid rules of the streaming
+// kernels are stated in workgroups per CU
+inline int device_cu_count() {
+    static const int ncu = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        return v;
+    }();
+    return ncu;
 }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

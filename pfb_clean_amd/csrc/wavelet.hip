@@ -11,6 +11,10 @@
 // separate row pass, copyT transpose and column pass (3 sweeps over HBM) become one.
 // All memory-bound: coalesced row reads, LDS-staged taps, no MFMA (no contraction).
 //
+// The prox / PD section streams elementwise with fp64 partial sums on the layer of common.hpp that cgvec.hip uses
+// too (V16 / can_vec for the 16-byte forms, k_final_sum, device_cu_count); each C entry point validates and hands
+// over to a typed host function (dual_update_t<T>, pd_primal_t<T>, ...).
+//
 //   analysis 1-D :  out[o]   = sum_{j<F} filt[j] in[2o+1-j]          (zero outside)
 //   synthesis 1-D:  out[2m+p] = sum_{j<F/2} lo[2j+p] a[m+h-1-j] + sum_j hi[2j+p] d[m+h-1-j]
 //                   m = 0 .. N-h,  h = F/2                           (wavelets.py:99-123)
@@ -866,25 +870,38 @@ __global__ void __launch_bounds__(256) k_fill(T* p, size_t n, T v) {
 // --------------------------------------------------------------------- prox / PD
 // dual_update_numba (prox_21m.py:76-103): vt = vp + sigma v; a = |sum_band vt / sigma|;
 // v = vt * (a != 0 ? 1 - max(a - lam w / sigma, 0)/a : 1);  optionally vp_out = 2 v - vp
+// The threshold of that band sum: the factor, and in nz whether a != 0 (where it is not, v = vt exactly)
 template <typename T>
+__device__ __forceinline__ T band_sum_factor(T sum, T w, T lam, T sigma, bool& nz) {
+    const T a = fabs(sum / sigma);
+    nz = a != T(0);
+    if (!nz) return T(1);
+    const T soft = fmax(a - lam * w / sigma, T(0));
+    return T(1) - soft / a;
+}
+
+// Any band count and alignment.  GIVEN = false: the whole update, the band sum formed here.  GIVEN = true: the sum is
+// read from sum_in -- the second phase of the band-sharded update (bands split over GPUs), where k_dual_bandsum forms
+// the LOCAL sum of vtilde = vp + sigma v per coefficient and an all-reduce(sum) of that plane over the ranks comes
+// in between (prox_21m.py:95-103).
+// bstride: elements between the bands of vp / v (= nper for the whole plane; a CHUNK of the plane is the same call on
+// shifted pointers with the chunk's length as nper)
+template <typename T, bool GIVEN>
 __global__ void __launch_bounds__(256)
-k_dual_update(const T* vp, T* __restrict__ v, const T* __restrict__ w, T lam, T sigma,
-              int nband, size_t nper, T* vp_out) {        // vp_out may alias vp
+k_dual_apply(const T* vp, T* __restrict__ v, const T* __restrict__ w, const T* __restrict__ sum_in,
+             T lam, T sigma, int nband, size_t nper, size_t bstride, T* vp_out) {        // vp_out may alias vp
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nper;
          i += (size_t)gridDim.x * blockDim.x) {
         T sum = 0;
-        for (int b = 0; b < nband; ++b) sum += vp[(size_t)b * nper + i] + sigma * v[(size_t)b * nper + i];
-        const T a = fabs(sum / sigma);
-        T fac = 1;
-        if (a != T(0)) {
-            const T soft = fmax(a - lam * w[i] / sigma, T(0));
-            fac = T(1) - soft / a;
-        }
+        if (GIVEN) sum = sum_in[i];
+        else for (int b = 0; b < nband; ++b) sum += vp[(size_t)b * bstride + i] + sigma * v[(size_t)b * bstride + i];
+        bool nz;
+        const T fac = band_sum_factor(sum, w[i], lam, sigma, nz);
         for (int b = 0; b < nband; ++b) {
-            const size_t k = (size_t)b * nper + i;
+            const size_t k = (size_t)b * bstride + i;
             const T vpk = vp[k];
             const T vt = vpk + sigma * v[k];
-            const T vn = (a != T(0)) ? vt * fac : vt;
+            const T vn = nz ? vt * fac : vt;
             v[k] = vn;
             if (vp_out) vp_out[k] = T(2) * vn - vpk;
         }
@@ -921,7 +938,7 @@ k_dual_update_vec(const T* vp, T* __restrict__ v, const T* __restrict__ w, T lam
             T sum = 0;
 #pragma unroll
             for (int b = 0; b < NB; ++b) sum += a_vp[b][e] + sigma * a_v[b][e];
-            const T a = fabs(sum / sigma);
+            const T a = fabs(sum / sigma);         // band_sum_factor, spelled out: calling it regroups this kernel's code
             nz[e] = a != T(0);
             fac[e] = 1;
             if (nz[e]) {
@@ -944,42 +961,16 @@ k_dual_update_vec(const T* vp, T* __restrict__ v, const T* __restrict__ w, T lam
     }
 }
 
-// Band-sharded dual update (bands split over GPUs): phase 1 forms the LOCAL band sum of
-// vtilde = vp + sigma v per coefficient; after an all-reduce(sum) of that plane over the
-// ranks, phase 2 applies the same soft threshold with the GLOBAL sum (prox_21m.py:95-103).
+// phase 1 of the band-sharded dual update (k_dual_apply<T, true> is phase 2)
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_dual_bandsum(const T* __restrict__ vp, const T* __restrict__ v, T sigma, int nband, size_t nper,
                size_t bstride, T* __restrict__ sum_out) {
-    // bstride: elements between the bands of vp / v (= nper for the whole plane; a CHUNK of the plane is the same
-    // call on shifted pointers with the chunk's length as nper)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nper;
          i += (size_t)gridDim.x * blockDim.x) {
         T sum = 0;
         for (int b = 0; b < nband; ++b) sum += vp[(size_t)b * bstride + i] + sigma * v[(size_t)b * bstride + i];
         sum_out[i] = sum;
-    }
-}
-template <typename T>
-__global__ void __launch_bounds__(256)
-k_dual_apply(const T* vp, T* __restrict__ v, const T* __restrict__ w, const T* __restrict__ sum_in,
-             T lam, T sigma, int nband, size_t nper, size_t bstride, T* vp_out) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nper;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const T a = fabs(sum_in[i] / sigma);
-        T fac = 1;
-        if (a != T(0)) {
-            const T soft = fmax(a - lam * w[i] / sigma, T(0));
-            fac = T(1) - soft / a;
-        }
-        for (int b = 0; b < nband; ++b) {
-            const size_t k = (size_t)b * bstride + i;
-            const T vpk = vp[k];
-            const T vt = vpk + sigma * v[k];
-            const T vn = (a != T(0)) ? vt * fac : vt;
-            v[k] = vn;
-            if (vp_out) vp_out[k] = T(2) * vn - vpk;
-        }
     }
 }
 
@@ -1052,54 +1043,15 @@ k_dual_update_l2(const T* __restrict__ vp, T* __restrict__ v, const T* __restric
 // 2 psi^H(v) - psi^H(vp), and psi^H(vp) is the previous iteration's psi^H(v): the coefficient cube 2 v - vp
 // (primal_dual.py:137) is then never written nor read.  gsub (optional): g - gsub is the gradient (the data term of
 // grad(x) = conv(x) - dirty, workers/spotless.py:259-260, subtracted here instead of in a pass of its own).
-template <typename T>
-__global__ void __launch_bounds__(256)
-k_pd_primal(const T* __restrict__ xp, const T* __restrict__ xout, const T* __restrict__ xprev,
-            const T* __restrict__ g, const T* __restrict__ gsub, T tau,
-            int positivity, int nband, size_t npix, T* __restrict__ x, double* __restrict__ ws) {
-    __shared__ double red[3 * 4];
-    double acc[3] = {0.0, 0.0, 0.0};
-    auto value = [&](size_t k) -> T {
-        T gk = g ? g[k] : T(0);
-        if (gsub) gk -= gsub[k];
-        T xo = xout[k];
-        if (xprev) xo = T(2) * xo - xprev[k];
-        return xp[k] - tau * (xo + gk);
-    };
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix;
-         i += (size_t)gridDim.x * blockDim.x) {
-        bool kill = false;
-        if (positivity == 2) {
-            for (int b = 0; b < nband; ++b)
-                if (value((size_t)b * npix + i) <= T(0)) kill = true;
-        }
-        for (int b = 0; b < nband; ++b) {
-            const size_t k = (size_t)b * npix + i;
-            T val = value(k);
-            if (positivity == 1 && val < T(0)) val = 0;
-            if (kill) val = 0;
-            x[k] = val;
-            const double d = (double)val - (double)xp[k];
-            acc[0] += d * d;
-            acc[1] += (double)val * (double)val;
-            acc[2] += (val != T(0)) ? 1.0 : 0.0;
-        }
-    }
-    block_sum<3>(acc, red);
-    if (threadIdx.x == 0) {
-        for (int q = 0; q < 3; ++q) ws[(size_t)q * gridDim.x + blockIdx.x] = acc[q];
-    }
-}
-
-// the same with V pixels per thread and step (16-byte accesses; npix a multiple of V, 16-byte aligned arrays): the
-// scalar kernel above moved 402 MB in 119 us at config #4, 3.4 TB/s
+// V pixels per thread and step: V = 16 / sizeof(T) (16-byte accesses; npix a multiple of V, 16-byte aligned arrays; the
+// scalar form moved 402 MB in 119 us at config #4, 3.4 TB/s), V = 1 for any npix and alignment.  nvec = npix / V.
 template <typename T, int V>
 __global__ void __launch_bounds__(256)
 k_pd_primal_vec(const T* __restrict__ xp, const T* __restrict__ xout, const T* __restrict__ xprev,
                 const T* __restrict__ g, const T* __restrict__ gsub, T tau,
                 int positivity, int nband, size_t nvec, T* __restrict__ x, double* __restrict__ ws) {
     struct alignas(V * sizeof(T)) Vec { T e[V]; };
-    __shared__ double red[3 * 4];
+    __shared__ double red[3 * (RED_BLOCK / 64)];
     double acc[3] = {0.0, 0.0, 0.0};
     auto ldv = [](const T* p, size_t k) { return reinterpret_cast<const Vec*>(p)[k]; };
     auto value = [&](size_t k, Vec& xpv) -> Vec {
@@ -1146,20 +1098,11 @@ k_pd_primal_vec(const T* __restrict__ xp, const T* __restrict__ xout, const T* _
             reinterpret_cast<Vec*>(x)[k] = val;
         }
     }
+    // emit_partials<3>, spelled out: through the call block_sum's blockDim.x is not folded into the loop's (one more
+    // load, other registers in the 16-byte kernels)
     block_sum<3>(acc, red);
     if (threadIdx.x == 0) {
         for (int q = 0; q < 3; ++q) ws[(size_t)q * gridDim.x + blockIdx.x] = acc[q];
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_final_sum3(const double* __restrict__ ws, int G, int nq, double* __restrict__ out) {
-    __shared__ double red[4];
-    for (int q = 0; q < nq; ++q) {
-        double acc[1] = {0.0};
-        for (int g = threadIdx.x; g < G; g += blockDim.x) acc[0] += ws[(size_t)q * G + g];
-        block_sum<1>(acc, red);
-        if (threadIdx.x == 0) out[q] = acc[0];
     }
 }
 
@@ -1482,12 +1425,24 @@ static int set_wavelet_lds_limits() {
 
 template <typename T> static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t st);
 
+// the batched / fused drivers unless PFB_PSI_FUSED=0 asks for the per-basis path; read on EVERY call (the tests
+// switch it within one process)
+static bool psi_fused(const pfb_psi_plan* p) {
+    const char* e = getenv("PFB_PSI_FUSED");
+    return !(e && !atoi(e)) && p->nbasis > 0;
+}
+
+// the batched kernels exist for FMAX = 8 and 18 (longest filter they hold): launch the one the plan `p` needs, block
+// 256, on stream `st`
+#define PFB_FMAX_LAUNCH(KERN, TILE, grid, lds, ...)                                                          \
+    do {                                                                                                     \
+        if (p->fin_fmax <= 8) hipLaunchKernelGGL((KERN<T, TILE, 8>), grid, dim3(256), lds, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERN<T, TILE, 18>), grid, dim3(256), lds, st, __VA_ARGS__);                 \
+    } while (0)
+
 template <typename T>
 static int psi_dot_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t st) {
-    {
-        const char* e = getenv("PFB_PSI_FUSED");
-        if (!(e && !atoi(e)) && p->nbasis > 0) return psi_dot_batched_t<T>(p, x, alpha, st);
-    }
+    if (psi_fused(p)) return psi_dot_batched_t<T>(p, x, alpha, st);
     const size_t plane = (size_t)p->Nymax * p->Nxmax;
     const size_t aband = plane * p->nbasis;
     const size_t xband = (size_t)p->nx * p->ny;
@@ -1561,22 +1516,12 @@ static int psi_fin_prepare(pfb_psi_plan* p) {
     PFB_HIP_CHECK(hipMalloc(&p->fin_scratch, sizeof(T) * p->fin_basis * p->nbasis));
     constexpr int TS = Tile<T>::TS;
     constexpr int TA = Tile<T>::TA;
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_batched2<T, TS, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_batched2<T, TS, 18>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_finest_fused2<T, TS, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_idwt_finest_fused2<T, TS, 18>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_dwt_l1_fused<T, TA, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_dwt_l1_fused<T, TA, 18>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_dwt_batched<T, TA, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_dwt_batched<T, TA, 18>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define PFB_FMAX_LDS(KERN, TILE)                                                                                         \
+    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(KERN<T, TILE, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(KERN<T, TILE, 18>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PFB_FMAX_LDS(k_idwt_batched2, TS) PFB_FMAX_LDS(k_idwt_finest_fused2, TS)
+    PFB_FMAX_LDS(k_dwt_l1_fused, TA) PFB_FMAX_LDS(k_dwt_batched, TA)
+#undef PFB_FMAX_LDS
     // ---- batched level tables: [level][wavelet basis]
     std::vector<int> wb;
     for (int ib = 0; ib < p->nbasis; ++ib) if (p->bases[ib].K != 0) wb.push_back(ib);
@@ -1656,26 +1601,17 @@ static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t 
         if (l1_fused) {
             dim3 grid(p->gx_ana[0], p->gy_ana[0], p->nband);
             const AnaPrm<T>* prm = (const AnaPrm<T>*)p->ana_prm;
-            if (p->fin_fmax <= 8)
-                hipLaunchKernelGGL((k_dwt_l1_fused<T, TA, 8>), grid, dim3(256), sizeof(T) * DwtFast<T>::elems(TA, 8), st, x, xband,
-                                   p->ny, p->nx, p->ny, alpha, aband, p->Nxmax, (T*)p->bscr[0], p->scratch_band, prm,
-                                   p->nwb, self_off);
-            else
-                hipLaunchKernelGGL((k_dwt_l1_fused<T, TA, 18>), grid, dim3(256), sizeof(T) * DwtFast<T>::elems(TA, 18), st, x, xband,
-                                   p->ny, p->nx, p->ny, alpha, aband, p->Nxmax, (T*)p->bscr[0], p->scratch_band, prm,
-                                   p->nwb, self_off);
+            PFB_FMAX_LAUNCH(k_dwt_l1_fused, TA, grid, sizeof(T) * DwtFast<T>::elems(TA, p->fin_fmax <= 8 ? 8 : 18), x, xband,
+                            p->ny, p->nx, p->ny, alpha, aband, p->Nxmax, (T*)p->bscr[0], p->scratch_band, prm, p->nwb,
+                            self_off);
         }
         for (int l = l1_fused ? 1 : 0; l < p->nlevel; ++l) {
             dim3 grid(p->gx_ana[l], p->gy_ana[l], p->nband * p->nwb);
             const T* in = l == 0 ? x : (const T*)p->bscr[(l - 1) & 1];
             const size_t in_band = l == 0 ? xband : p->scratch_band;
             const AnaPrm<T>* prm = (const AnaPrm<T>*)p->ana_prm + (size_t)l * p->nwb;
-            if (p->fin_fmax <= 8)
-                hipLaunchKernelGGL((k_dwt_batched<T, TA, 8>), grid, dim3(256), lds, st, in, in_band, alpha, aband,
-                                   p->Nxmax, (T*)p->bscr[l & 1], p->scratch_band, prm, p->nwb);
-            else
-                hipLaunchKernelGGL((k_dwt_batched<T, TA, 18>), grid, dim3(256), lds, st, in, in_band, alpha, aband,
-                                   p->Nxmax, (T*)p->bscr[l & 1], p->scratch_band, prm, p->nwb);
+            PFB_FMAX_LAUNCH(k_dwt_batched, TA, grid, lds, in, in_band, alpha, aband, p->Nxmax, (T*)p->bscr[l & 1],
+                            p->scratch_band, prm, p->nwb);
         }
     }
     PFB_HIP_CHECK(hipGetLastError());
@@ -1698,35 +1634,23 @@ static int psi_hdot_fused_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t 
             const SynPrm<T>* prm = (const SynPrm<T>*)p->syn_prm + (size_t)l * p->nwb;
             T* out = l == 1 ? (T*)p->fin_scratch : (T*)p->bscr[l & 1];
             const size_t oband = l == 1 ? p->fin_band : p->scratch_band;
-            if (p->fin_fmax <= 8)
-                hipLaunchKernelGGL((k_idwt_batched2<T, TS, 8>), g, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                                   (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb);
-            else
-                hipLaunchKernelGGL((k_idwt_batched2<T, TS, 18>), g, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                                   (const T*)p->bscr[(l + 1) & 1], p->scratch_band, out, oband, prm, p->nwb);
+            PFB_FMAX_LAUNCH(k_idwt_batched2, TS, g, lds2, alpha, aband, p->Nxmax, (const T*)p->bscr[(l + 1) & 1],
+                            p->scratch_band, out, oband, prm, p->nwb);
         }
     }
     dim3 grid((p->nx + TS - 1) / TS, (p->ny + TS - 1) / TS, p->nband);
     static_assert(SynFast<T, TS>::ok, "tile shape of the lean fused kernel");
     const size_t lds2 = sizeof(T) * SynFast<T, TS>::elems(p->fin_fmax);
-    if (p->fin_fmax <= 8)
-        hipLaunchKernelGGL((k_idwt_finest_fused2<T, TS, 8>), grid, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                           (const FinBasis<T>*)p->fin_prm, p->nbasis, (const T*)p->fin_scratch, p->fin_band,
-                           xo, xband, p->ny, p->nx, p->ny);
-    else
-        hipLaunchKernelGGL((k_idwt_finest_fused2<T, TS, 18>), grid, dim3(256), lds2, st, alpha, aband, p->Nxmax,
-                           (const FinBasis<T>*)p->fin_prm, p->nbasis, (const T*)p->fin_scratch, p->fin_band,
-                           xo, xband, p->ny, p->nx, p->ny);
+    PFB_FMAX_LAUNCH(k_idwt_finest_fused2, TS, grid, lds2, alpha, aband, p->Nxmax, (const FinBasis<T>*)p->fin_prm,
+                    p->nbasis, (const T*)p->fin_scratch, p->fin_band, xo, xband, p->ny, p->nx, p->ny);
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;
 }
+#undef PFB_FMAX_LAUNCH
 
 template <typename T>
 static int psi_hdot_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t st) {
-    {
-        const char* e = getenv("PFB_PSI_FUSED");
-        if (!(e && !atoi(e)) && p->nbasis > 0) return psi_hdot_fused_t<T>(p, alpha, xo, st);
-    }
+    if (psi_fused(p)) return psi_hdot_fused_t<T>(p, alpha, xo, st);
     const size_t plane = (size_t)p->Nymax * p->Nxmax;
     const size_t aband = plane * p->nbasis;
     const size_t xband = (size_t)p->nx * p->ny;
@@ -1782,12 +1706,7 @@ static int psi_hdot_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t st) {
 // grid for the streaming elementwise kernels that WRITE as much as they read: a few workgroups per
 // CU (tools/micro/hbm_stream.hip: the write-heavy mixes lose 10-25 % when the chip is oversubscribed)
 static inline int stream_grid(size_t nvec) {
-    static const int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
+    const int ncu = device_cu_count();
     size_t g = (nvec + 255) / 256;
     if (g > (size_t)ncu) g = ncu;
     if (g < 1) g = 1;
@@ -1801,27 +1720,78 @@ static inline int ew_grid(size_t n) {
     return (int)g;
 }
 
+// The typed halves of the C entry points below (which validate, then dispatch on dtype in one line).
+using PtrList = std::initializer_list<const void*>;
+
 template <typename T>
-static void dual_update_launch(const T* vp, T* v, const T* w, T lam, T sigma, int nband, size_t nper, T* vp_out,
-                               hipStream_t st) {
-    constexpr int V = 16 / sizeof(T);
-    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    const bool vec = nband <= 8 && nper % V == 0 && al(vp) && al(v) && al(w) && (!vp_out || al(vp_out));
-    if (!vec) {
-        hipLaunchKernelGGL((k_dual_update<T>), dim3(ew_grid(nper)), dim3(256), 0, st, vp, v, w, lam, sigma, nband,
-                           nper, vp_out);
-        return;
-    }
-    const dim3 grid(stream_grid(nper / V));
-    // non-temporal reads of vp / psi^H(x) once the cube is far beyond the caches (+0.8 % on the config #4 iteration)
-    const bool ntl = (size_t)nband * nper * sizeof(T) >= ((size_t)64 << 20);
+static int dual_update_t(const void* vp_, void* v_, const void* w_, double lam_, double sigma_, int nband, size_t nper,
+                         void* vp_out_, hipStream_t st) {
+    const T *vp = (const T*)vp_, *w = (const T*)w_;
+    T *v = (T*)v_, *vp_out = (T*)vp_out_;
+    const T lam = (T)lam_, sigma = (T)sigma_;
+    if (nband <= 8 && can_vec<T>(nper, PtrList{vp, v, w, vp_out})) {
+        const dim3 grid(stream_grid(nper / V16<T>::N));
+        // non-temporal reads of vp / psi^H(x) once the cube is far beyond the caches (+0.8 % on the config #4 iteration)
+        const bool ntl = (size_t)nband * nper * sizeof(T) >= ((size_t)64 << 20);
 #define PFB_DU_CASE(NB) case NB: if (ntl) hipLaunchKernelGGL((k_dual_update_vec<T, NB, true>), grid, dim3(256), 0, st, vp, v, w, \
                                                     lam, sigma, nper, vp_out); \
                                  else hipLaunchKernelGGL((k_dual_update_vec<T, NB, false>), grid, dim3(256), 0, st, vp, v, w, \
                                                     lam, sigma, nper, vp_out); break;
-    switch (nband) { PFB_DU_CASE(1) PFB_DU_CASE(2) PFB_DU_CASE(3) PFB_DU_CASE(4) PFB_DU_CASE(5) PFB_DU_CASE(6)
-                     PFB_DU_CASE(7) PFB_DU_CASE(8) }
+        switch (nband) { PFB_DU_CASE(1) PFB_DU_CASE(2) PFB_DU_CASE(3) PFB_DU_CASE(4) PFB_DU_CASE(5) PFB_DU_CASE(6)
+                         PFB_DU_CASE(7) PFB_DU_CASE(8) }
 #undef PFB_DU_CASE
+    } else {
+        hipLaunchKernelGGL((k_dual_apply<T, false>), dim3(ew_grid(nper)), dim3(256), 0, st, vp, v, w, (const T*)nullptr,
+                           lam, sigma, nband, nper, nper, vp_out);
+    }
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+template <typename T>
+static int dual_bandsum_t(const void* vp, const void* v, double sigma, int nband, size_t count, size_t band_stride,
+                          void* sum_out, hipStream_t st) {
+    hipLaunchKernelGGL((k_dual_bandsum<T>), dim3(ew_grid(count)), dim3(256), 0, st, (const T*)vp, (const T*)v, (T)sigma,
+                       nband, count, band_stride, (T*)sum_out);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+template <typename T>
+static int dual_apply_t(const void* vp, void* v, const void* w, const void* sum_in, double lam, double sigma, int nband,
+                        size_t count, size_t band_stride, void* vp_out, hipStream_t st) {
+    hipLaunchKernelGGL((k_dual_apply<T, true>), dim3(ew_grid(count)), dim3(256), 0, st, (const T*)vp, (T*)v, (const T*)w,
+                       (const T*)sum_in, (T)lam, (T)sigma, nband, count, band_stride, (T*)vp_out);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+// the three whole-plane kernels with one signature: k_prox_21m, k_prox_21_l2 (in = v, out = result) and k_dual_update_l2
+// (in = vp, out = v)
+template <typename T, typename K>
+static int prox_plane_t(K kern, const void* in, void* out, const void* w, double lam, double sigma, int nband, size_t nper,
+                        hipStream_t st) {
+    hipLaunchKernelGGL(kern, dim3(ew_grid(nper)), dim3(256), 0, st, (const T*)in, (T*)out, (const T*)w, (T)lam, (T)sigma,
+                       nband, nper);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+template <typename T>
+static int pd_primal_t(const void* xp, const void* xout, const void* xprev, const void* g, const void* gsub, double tau,
+                       int positivity, int nband, size_t npix, void* x, double* sums, double* ws, hipStream_t st) {
+    // 16-byte form: the band offsets (npix elements) stay 16-byte aligned
+    const bool vec = can_vec<T>(npix, PtrList{xp, xout, xprev, g, gsub, x});
+    const size_t n = vec ? npix / V16<T>::N : npix;
+    const int G = ew_grid(n) > 1024 ? 1024 : ew_grid(n);
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(G), dim3(RED_BLOCK), 0, st, (const T*)xp, (const T*)xout, (const T*)xprev,
+                           (const T*)g, (const T*)gsub, (T)tau, positivity, nband, n, (T*)x, ws);
+    };
+    if (vec) launch(k_pd_primal_vec<T, V16<T>::N>); else launch(k_pd_primal_vec<T, 1>);
+    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G, 3, sums);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
 }
 
 }  // namespace pfb
@@ -1947,12 +1917,8 @@ int pfb_dual_update(int dtype, const void* vp, void* v, const void* weight, doub
                     int nband, size_t nper, void* vp_out, void* stream) {
     PFB_REQUIRE(vp && v && weight && nband > 0, PFB_ERR_INVALID, "dual_update: bad argument");
     hipStream_t st = as_stream(stream);
-    if (dtype == PFB_F32) dual_update_launch<float>((const float*)vp, (float*)v, (const float*)weight, (float)lam,
-                                                    (float)sigma, nband, nper, (float*)vp_out, st);
-    else dual_update_launch<double>((const double*)vp, (double*)v, (const double*)weight, lam, sigma, nband, nper,
-                                    (double*)vp_out, st);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return dtype == PFB_F32 ? dual_update_t<float>(vp, v, weight, lam, sigma, nband, nper, vp_out, st)
+                            : dual_update_t<double>(vp, v, weight, lam, sigma, nband, nper, vp_out, st);
 }
 
 int pfb_dual_bandsum_chunk(int dtype, const void* vp, const void* v, double sigma, int nband, size_t count,
@@ -1960,14 +1926,8 @@ int pfb_dual_bandsum_chunk(int dtype, const void* vp, const void* v, double sigm
     PFB_REQUIRE(vp && v && sum_out && nband > 0 && band_stride >= count, PFB_ERR_INVALID, "dual_bandsum: bad argument");
     if (count == 0) return PFB_OK;
     hipStream_t st = as_stream(stream);
-    if (dtype == PFB_F32)
-        hipLaunchKernelGGL((k_dual_bandsum<float>), dim3(ew_grid(count)), dim3(256), 0, st, (const float*)vp,
-                           (const float*)v, (float)sigma, nband, count, band_stride, (float*)sum_out);
-    else
-        hipLaunchKernelGGL((k_dual_bandsum<double>), dim3(ew_grid(count)), dim3(256), 0, st, (const double*)vp,
-                           (const double*)v, sigma, nband, count, band_stride, (double*)sum_out);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return dtype == PFB_F32 ? dual_bandsum_t<float>(vp, v, sigma, nband, count, band_stride, sum_out, st)
+                            : dual_bandsum_t<double>(vp, v, sigma, nband, count, band_stride, sum_out, st);
 }
 int pfb_dual_bandsum(int dtype, const void* vp, const void* v, double sigma, int nband, size_t nper,
                      void* sum_out, void* stream) {
@@ -1979,16 +1939,9 @@ int pfb_dual_apply_chunk(int dtype, const void* vp, void* v, const void* weight,
     PFB_REQUIRE(vp && v && weight && sum_in && nband > 0 && band_stride >= count, PFB_ERR_INVALID, "dual_apply: bad argument");
     if (count == 0) return PFB_OK;
     hipStream_t st = as_stream(stream);
-    if (dtype == PFB_F32)
-        hipLaunchKernelGGL((k_dual_apply<float>), dim3(ew_grid(count)), dim3(256), 0, st, (const float*)vp,
-                           (float*)v, (const float*)weight, (const float*)sum_in, (float)lam, (float)sigma,
-                           nband, count, band_stride, (float*)vp_out);
-    else
-        hipLaunchKernelGGL((k_dual_apply<double>), dim3(ew_grid(count)), dim3(256), 0, st, (const double*)vp,
-                           (double*)v, (const double*)weight, (const double*)sum_in, lam, sigma, nband, count,
-                           band_stride, (double*)vp_out);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return dtype == PFB_F32
+        ? dual_apply_t<float>(vp, v, weight, sum_in, lam, sigma, nband, count, band_stride, vp_out, st)
+        : dual_apply_t<double>(vp, v, weight, sum_in, lam, sigma, nband, count, band_stride, vp_out, st);
 }
 int pfb_dual_apply(int dtype, const void* vp, void* v, const void* weight, const void* sum_in, double lam,
                    double sigma, int nband, size_t nper, void* vp_out, void* stream) {
@@ -1999,42 +1952,24 @@ int pfb_prox_21(int dtype, const void* v, void* result, const void* weight, doub
                 int nband, size_t nper, void* stream) {
     PFB_REQUIRE(v && result && weight && nband > 0 && sigma != 0.0, PFB_ERR_INVALID, "prox_21: bad argument");
     hipStream_t st = as_stream(stream);
-    if (dtype == PFB_F32)
-        hipLaunchKernelGGL((k_prox_21_l2<float>), dim3(ew_grid(nper)), dim3(256), 0, st, (const float*)v, (float*)result,
-                           (const float*)weight, (float)lam, (float)sigma, nband, nper);
-    else
-        hipLaunchKernelGGL((k_prox_21_l2<double>), dim3(ew_grid(nper)), dim3(256), 0, st, (const double*)v, (double*)result,
-                           (const double*)weight, lam, sigma, nband, nper);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return dtype == PFB_F32 ? prox_plane_t<float>(k_prox_21_l2<float>, v, result, weight, lam, sigma, nband, nper, st)
+                            : prox_plane_t<double>(k_prox_21_l2<double>, v, result, weight, lam, sigma, nband, nper, st);
 }
 
 int pfb_dual_update_l2(int dtype, const void* vp, void* v, const void* weight, double lam, double sigma,
                        int nband, size_t nper, void* stream) {
     PFB_REQUIRE(vp && v && weight && nband > 0 && sigma != 0.0, PFB_ERR_INVALID, "dual_update_l2: bad argument");
     hipStream_t st = as_stream(stream);
-    if (dtype == PFB_F32)
-        hipLaunchKernelGGL((k_dual_update_l2<float>), dim3(ew_grid(nper)), dim3(256), 0, st, (const float*)vp, (float*)v,
-                           (const float*)weight, (float)lam, (float)sigma, nband, nper);
-    else
-        hipLaunchKernelGGL((k_dual_update_l2<double>), dim3(ew_grid(nper)), dim3(256), 0, st, (const double*)vp, (double*)v,
-                           (const double*)weight, lam, sigma, nband, nper);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return dtype == PFB_F32 ? prox_plane_t<float>(k_dual_update_l2<float>, vp, v, weight, lam, sigma, nband, nper, st)
+                            : prox_plane_t<double>(k_dual_update_l2<double>, vp, v, weight, lam, sigma, nband, nper, st);
 }
 
 int pfb_prox_21m(int dtype, const void* v, void* result, const void* weight, double lam, double sigma,
                  int nband, size_t nper, void* stream) {
     PFB_REQUIRE(v && result && weight && nband > 0, PFB_ERR_INVALID, "prox_21m: bad argument");
     hipStream_t st = as_stream(stream);
-    if (dtype == PFB_F32)
-        hipLaunchKernelGGL((k_prox_21m<float>), dim3(ew_grid(nper)), dim3(256), 0, st, (const float*)v,
-                           (float*)result, (const float*)weight, (float)lam, (float)sigma, nband, nper);
-    else
-        hipLaunchKernelGGL((k_prox_21m<double>), dim3(ew_grid(nper)), dim3(256), 0, st, (const double*)v,
-                           (double*)result, (const double*)weight, lam, sigma, nband, nper);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return dtype == PFB_F32 ? prox_plane_t<float>(k_prox_21m<float>, v, result, weight, lam, sigma, nband, nper, st)
+                            : prox_plane_t<double>(k_prox_21m<double>, v, result, weight, lam, sigma, nband, nper, st);
 }
 
 static int pd_primal_launch(int dtype, const void* xp, const void* xout, const void* xprev, const void* g,
@@ -2043,31 +1978,9 @@ static int pd_primal_launch(int dtype, const void* xp, const void* xout, const v
     PFB_REQUIRE(xp && xout && x && sums && ws && nband > 0, PFB_ERR_INVALID, "pd_primal_update: bad argument");
     PFB_REQUIRE(!gsub || g, PFB_ERR_INVALID, "pd_primal_update: gsub given without g");
     hipStream_t st = as_stream(stream);
-    int G = ew_grid(npix) > 1024 ? 1024 : ew_grid(npix);
-    const uintptr_t al = (uintptr_t)xp | (uintptr_t)xout | (uintptr_t)xprev | (uintptr_t)g | (uintptr_t)gsub | (uintptr_t)x;
-    const size_t V = dtype == PFB_F32 ? 4 : 2;
-    if ((al & 15) == 0 && npix % V == 0) {          // band offsets (npix elements) stay 16-byte aligned
-        const size_t nvec = npix / V;
-        G = ew_grid(nvec) > 1024 ? 1024 : ew_grid(nvec);
-        if (dtype == PFB_F32)
-            hipLaunchKernelGGL((k_pd_primal_vec<float, 4>), dim3(G), dim3(256), 0, st, (const float*)xp, (const float*)xout,
-                               (const float*)xprev, (const float*)g, (const float*)gsub, (float)tau, positivity, nband,
-                               nvec, (float*)x, ws);
-        else
-            hipLaunchKernelGGL((k_pd_primal_vec<double, 2>), dim3(G), dim3(256), 0, st, (const double*)xp,
-                               (const double*)xout, (const double*)xprev, (const double*)g, (const double*)gsub, tau,
-                               positivity, nband, nvec, (double*)x, ws);
-    } else if (dtype == PFB_F32)
-        hipLaunchKernelGGL((k_pd_primal<float>), dim3(G), dim3(256), 0, st, (const float*)xp, (const float*)xout,
-                           (const float*)xprev, (const float*)g, (const float*)gsub, (float)tau, positivity, nband,
-                           npix, (float*)x, ws);
-    else
-        hipLaunchKernelGGL((k_pd_primal<double>), dim3(G), dim3(256), 0, st, (const double*)xp,
-                           (const double*)xout, (const double*)xprev, (const double*)g, (const double*)gsub, tau,
-                           positivity, nband, npix, (double*)x, ws);
-    hipLaunchKernelGGL(k_final_sum3, dim3(1), dim3(256), 0, st, ws, G, 3, sums);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return dtype == PFB_F32
+        ? pd_primal_t<float>(xp, xout, xprev, g, gsub, tau, positivity, nband, npix, x, sums, ws, st)
+        : pd_primal_t<double>(xp, xout, xprev, g, gsub, tau, positivity, nband, npix, x, sums, ws, st);
 }
 
 int pfb_pd_primal_update(int dtype, const void* xp, const void* xout, const void* g, double tau,

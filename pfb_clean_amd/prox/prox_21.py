@@ -12,11 +12,10 @@ v.shape[1:].  Elementwise HIP kernels with the band loop inside (pfb_prox_21 / p
 The live spotless worker hands prox_21 to primal_dual_optimised, which never calls it (primal_dual.py:98): these are
 not on the hot path, they complete the module.
 """
-import numpy as np
 import torch
 
 from .. import _lib, _dev
-from .prox_21m import _prep
+from .prox_21m import _prep, _weight_like, _dual_update_array
 
 
 def prox_21_numba(v, result, lam, sigma=1.0, weight=None):
@@ -34,10 +33,8 @@ def prox_21(v, sigma, weight=None, axis=0):
     vd = _dev.to_dev(v)
     if weight is None:
         raise ValueError("weight is required")            # the reference multiplies by it unconditionally (:15)
-    w = torch.as_tensor(weight, dtype=vd.dtype, device=vd.device).expand(vd.shape[1:]).contiguous() \
-        if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
     res = torch.empty_like(vd)
-    prox_21_numba(vd, res, sigma, sigma=1.0, weight=w)    # v max(||v|| - sigma w, 0) / ||v||
+    prox_21_numba(vd, res, sigma, sigma=1.0, weight=_weight_like(weight, vd))    # v max(||v|| - sigma w, 0) / ||v||
     return _dev.host_like(res, v)
 
 
@@ -53,10 +50,4 @@ def dual_update_numba(vp, v, lam, sigma=1.0, weight=None):
 
 
 def dual_update(v, x, psiH, lam, sigma=1.0, weight=1.0):
-    vd = _dev.to_dev(v)
-    vout = torch.zeros_like(vd)
-    psiH(_dev.to_dev(x), vout)
-    w = torch.as_tensor(weight, dtype=vd.dtype, device=vd.device).expand(vd.shape[1:]).contiguous() \
-        if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
-    dual_update_numba(vd, vout, lam, sigma=sigma, weight=w)
-    return _dev.host_like(vout, v)
+    return _dual_update_array(dual_update_numba, v, x, psiH, lam, sigma, weight)

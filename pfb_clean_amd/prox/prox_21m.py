@@ -35,6 +35,22 @@ def _prep(v, weight):
     return vd, wd, nband, nper
 
 
+def _weight_like(weight, vd):
+    """The array forms' weight: an array as it is, a scalar spread over vd.shape[1:]."""
+    if isinstance(weight, (np.ndarray, torch.Tensor)):
+        return weight
+    return torch.as_tensor(weight, dtype=vd.dtype, device=vd.device).expand(vd.shape[1:]).contiguous()
+
+
+def _dual_update_array(update_numba, v, x, psiH, lam, sigma, weight):
+    """The array-form dual_update of prox_21m.py:64-71 and prox_21.py:51-58 around the in-place kernel `update_numba`."""
+    vd = _dev.to_dev(v)
+    vout = torch.zeros_like(vd)
+    psiH(_dev.to_dev(x), vout)
+    update_numba(vd, vout, lam, sigma=sigma, weight=_weight_like(weight, vd))
+    return _dev.host_like(vout, v)
+
+
 def prox_21m_numba(v, result, lam, sigma=1.0, weight=None):
     lib = _lib.load()
     vd, wd, nband, nper = _prep(v, weight)
@@ -97,18 +113,10 @@ def prox_21m(v, sigma, weight=1.0, axis=0):
     if axis != 0:
         raise ValueError("band axis must be 0")
     vd = _dev.to_dev(v)
-    w = torch.as_tensor(weight, dtype=vd.dtype, device=vd.device).expand(vd.shape[1:]).contiguous() \
-        if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
     res = torch.empty_like(vd)
-    prox_21m_numba(vd, res, sigma, sigma=1.0, weight=w)
+    prox_21m_numba(vd, res, sigma, sigma=1.0, weight=_weight_like(weight, vd))
     return _dev.host_like(res, v)
 
 
 def dual_update(v, x, psiH, lam, sigma=1.0, weight=1.0):
-    vd = _dev.to_dev(v)
-    vout = torch.zeros_like(vd)
-    psiH(_dev.to_dev(x), vout)
-    w = torch.as_tensor(weight, dtype=vd.dtype, device=vd.device).expand(vd.shape[1:]).contiguous() \
-        if not isinstance(weight, (np.ndarray, torch.Tensor)) else weight
-    dual_update_numba(vd, vout, lam, sigma=sigma, weight=w)
-    return _dev.host_like(vout, v)
+    return _dual_update_array(dual_update_numba, v, x, psiH, lam, sigma, weight)
