@@ -317,7 +317,9 @@ int pfb_psi_hdot(pfb_psi_plan* plan, const void* alpha, void* xo, void* stream);
 
 /* pfb/prox/prox_21m.py:76-103 dual_update_numba, in place on v.
  * vp, v: (nband, nbasis, nymax, nxmax); weight: (nbasis, nymax, nxmax).
- * If vp_out != NULL it additionally receives 2*v_new - vp (primal_dual.py:137). */
+ * If vp_out != NULL it additionally receives 2*v_new - vp (primal_dual.py:137); vp_out may alias vp (here and in
+ * pfb_dual_apply[_chunk]).  No other two arrays may overlap.  Pointers of any element alignment and any nper are
+ * accepted; 16-byte aligned arrays with nper a multiple of 16 / sizeof(T) and nband <= 8 take the 16-byte kernels. */
 int pfb_dual_update(int dtype, const void* vp, void* v, const void* weight,
                     double lam, double sigma, int nband, size_t nper,
                     void* vp_out, void* stream);
@@ -348,8 +350,10 @@ int pfb_dual_update_l2(int dtype, const void* vp, void* v, const void* weight,
 /* pfb/prox/prox_21m.py:31-61 prox_21m_numba */
 int pfb_prox_21m(int dtype, const void* v, void* result, const void* weight,
                  double lam, double sigma, int nband, size_t nper, void* stream);
-/* primal_dual.py:140-146: x = xp - tau*(xout + g); positivity 0|1|2 over nband;
- * sums[0..1] receive the norm_diff partial sums of (x, xp), sums[2] = any(x). */
+/* primal_dual.py:140-146: x = xp - tau*(xout + g); positivity 0|1|2 over nband; g may be NULL (no gradient term).
+ * sums[0..1] receive the norm_diff partial sums of (x, xp); sums[2] is zero if and only if x is identically zero (it
+ * counts the non-zero elements, a NaN included: test it against 0, like np.any).  ws: PFB_REDUCE_WS_DOUBLES doubles.
+ * x must not alias xp, xout, xout_prev, g or gsub (the kernel reads them as non-overlapping with what it writes). */
 int pfb_pd_primal_update(int dtype, const void* xp, const void* xout, const void* g,
                          double tau, int positivity, int nband, size_t npix,
                          void* x, double* sums, double* ws, void* stream);

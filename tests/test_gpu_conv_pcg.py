@@ -332,6 +332,42 @@ def test_vector_kernels(amd, n, rdt):
     d1 = out[0].item()
     _lib.check(lib.pfb_dot(code, ta.data_ptr(), ta.data_ptr(), n, out.data_ptr(), ws.data_ptr(), _dev.stream()))
     assert out[0].item() == d1
+    # each operand in turn one element off the 16-byte boundary (fp32 also two: 8-byte aligned): the V = 1 kernels,
+    # the same tolerances; axpby's y lies between sentinels that must survive
+    SENT, PAD = -1234.5, 64
+
+    def off16(arr, k):
+        full = torch.full((PAD + k + n + PAD,), SENT, dtype=ta.dtype, device='cuda')
+        full[PAD + k:PAD + k + n] = torch.from_numpy(arr).cuda()
+        view = full[PAD + k:PAD + k + n]
+        assert (view.data_ptr() % 16 == 0) == (k * arr.itemsize % 16 == 0)
+        return full, view
+    for k in ((1, 2) if rdt == np.float32 else (1,)):
+        for ka, kb in ((k, 0), (0, k), (k, k)):
+            (fa, va), (fb, vb) = off16(a, ka), off16(b, kb)
+            _lib.check(lib.pfb_dot(code, va.data_ptr(), vb.data_ptr(), n, out.data_ptr(), ws.data_ptr(), _dev.stream()))
+            assert abs(out[0].item() - ref) <= 1e-12 * max(1.0, np.abs(a64 * b).sum())
+            _lib.check(lib.pfb_norm_diff_sums(code, va.data_ptr(), vb.data_ptr(), n, out.data_ptr(), ws.data_ptr(),
+                                              _dev.stream()))
+            num, den = out[:2].tolist()
+            assert abs(num - np.sum((a64 - b64) ** 2)) <= 1e-12 * np.sum((a64 - b64) ** 2) + 1e-300
+            assert abs(den - np.sum(a64 ** 2)) <= 1e-12 * np.sum(a64 ** 2)
+            _lib.check(lib.pfb_axpby(code, 0.5, va.data_ptr(), -2.0, vb.data_ptr(), n, _dev.stream()))
+            np.testing.assert_allclose(vb.cpu().numpy(), rdt(0.5) * a + rdt(-2.0) * b,
+                                       rtol=1e-6 if rdt == np.float32 else 1e-14)
+            assert torch.equal(va, ta)
+            for f, kk in ((fa, ka), (fb, kb)):
+                assert bool((f[:PAD + kk] == SENT).all()) and bool((f[PAD + kk + n:] == SENT).all())
+        fz, vz = off16(np.zeros(n, rdt), k)
+        _lib.check(lib.pfb_any_nonzero(code, vz.data_ptr(), n, out.data_ptr(), ws.data_ptr(), _dev.stream()))
+        assert out[0].item() == 0
+        vz[n - 1] = 1e-30
+        _lib.check(lib.pfb_any_nonzero(code, vz.data_ptr(), n, out.data_ptr(), ws.data_ptr(), _dev.stream()))
+        assert out[0].item() > 0
+    if n in (4099, (1 << 20) + 3):          # a single non-zero element, the last one, behind the last full pack
+        z[n - 1] = -1e-30
+        _lib.check(lib.pfb_any_nonzero(code, z.data_ptr(), n, out.data_ptr(), ws.data_ptr(), _dev.stream()))
+        assert out[0].item() > 0
 
 
 def test_norm_diff_api(amd):
