@@ -439,6 +439,56 @@ int pfb_kernel_gather(int dtype, const double* kern, int nband, int nx, int ny, 
  * decayed to rounding noise the quotient is noise over noise, in the reference as here. */
 int pfb_kernhat_ratio(const void* num, const void* den, int nband, size_t n, void* out, void* stream);
 
+/* ----------------------------------------------------------------- component model
+ * What pfb/utils/misc.py:1084-1313 (fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice) do on image-sized
+ * arrays.  The host keeps what is tiny: the design matrix Xfit and its strings (misc.py:1146-1202), the LU factors of
+ * Xfit^T diag(w) Xfit (misc.py:1206-1211), the basis values of the parsed expression (misc.py:1223-1233) and the 1-D
+ * coordinate arrays of the regrid (misc.py:1254-1294).  All arithmetic is fp64 whatever the image dtype; nothing is
+ * allocated, there is no plan and no global state; asynchronous on `stream`.
+ *
+ * The fit is three calls.  `work` is device scratch of pfb_comps_work_bytes(npix) bytes, 8-byte aligned: the bit mask
+ * (one 64-bit word per 64 pixels), the scanned per-workgroup counts and, in its LAST 8 bytes, the number of
+ * components as an int64.  The caller reads that one number between pfb_comps_mask and pfb_comps_compact to size
+ * Ix / Iy / coeffs -- the only synchronisation of the fit (the output shape depends on the data). */
+
+/* Bytes of `work` for a cube of npix pixels per plane; 0 when npix is out of range. */
+size_t pfb_comps_work_bytes(size_t npix);
+
+/* misc.py:1131: np.any(image, axis=(0, 1)) of an (nplane, npix) cube of `dtype` as a bit mask -- a pixel is set iff
+ * any plane value != 0, so a NaN counts and -0.0 does not -- then the scan of the counts.  One pass over the cube,
+ * 16-byte loads; planes that do not start on a 16-byte boundary (odd npix in fp32) are read from their first aligned
+ * vector on, with a peel of up to 3 pixels. */
+int pfb_comps_mask(int dtype, const void* image, int nplane, size_t npix, void* work, void* stream);
+
+/* misc.py:1132: Ix, Iy = np.where(mask) for the (npix / ny, ny) mask in `work`, in np.where's row-major order.
+ * Ix, Iy: device int64 arrays of (at least) the component count. */
+int pfb_comps_compact(size_t npix, int ny, const void* work, long long* Ix, long long* Iy, void* stream);
+
+/* misc.py:1136, 1206-1211: coeffs[:, c] = solve(H, (Xfit^T diag(w)) image[:, Ix[c], Iy[c]]), one component per lane.
+ * sys: device doubles [A (nparam, nrow) | LU (nparam, nparam) | piv (nparam)], A = Xfit^T diag(w), LU / piv the getrf
+ * factors of H (scipy.linalg.lu_factor; piv stored as doubles).  image: (nrow, npix) of `dtype`; coeffs:
+ * (nparam, ncomps) doubles.  A NaN in a component's pixel gives NaN coefficients for that component only.
+ * nrow <= 64 and nparam <= 32, else PFB_ERR_UNSUPPORTED. */
+int pfb_comps_fit(int dtype, const void* image, int nrow, size_t npix, int ny, const long long* Ix, const long long* Iy,
+                  long long ncomps, const double* sys, int nparam, double* coeffs, void* stream);
+
+/* misc.py:1222-1233 / :1243-1252: out (nplane, nx, ny) of `dtype` is zero-filled, then
+ * out[plane, Ix[c], Iy[c]] = sum_p E[plane, p] coeffs[p, c], accumulated in fp64.  E: (nplane, nparam) device doubles,
+ * the value of expr's factor of parameter p at plane's (t, f).  The (Ix, Iy) pairs must be UNIQUE (numpy's
+ * last-one-wins for duplicates is not reproduced); a pair outside the plane is skipped.  nplane <= 65535. */
+int pfb_comps_eval(int dtype, const double* E, int nplane, int nparam, const double* coeffs, const long long* Ix,
+                   const long long* Iy, long long ncomps, int nx, int ny, void* out, void* stream);
+
+/* misc.py:1302-1306: RegularGridInterpolator((xin, yin), np.pad(image, ...), method='linear') at meshgrid(xo, yo).
+ * image: (nxi, nyi) device doubles; the padded plane is virtual: padded index (a, b) is image[a - npad_xl, b - npad_yl]
+ * and 0 outside it.  xin (nx_pad), yin (ny_pad), xo (nxo), yo (nyo): device doubles, computed by the caller with the
+ * reference's expressions and used as they are (the kernel never recomputes index * cell + x0); xin, yin ascending.
+ * Interval np.searchsorted(grid, x) - 1 clipped to [0, n - 2], distance (x - grid[i]) / (grid[i+1] - grid[i]), sum of
+ * the four corner products; no bounds check (the caller's, misc.py:1304).  out: (nxo, nyo) of `dtype`. */
+int pfb_comps_interp(int dtype, const double* image, int nxi, int nyi, int npad_xl, int npad_yl, const double* xin,
+                     int nx_pad, const double* yin, int ny_pad, const double* xo, int nxo, const double* yo, int nyo,
+                     void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,12 @@ SIGNATURES = {
     'pfb_gauss_kernel_grid': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'pfb_kernel_gather': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'pfb_kernhat_ratio': (_i, [_vp, _vp, _i, _sz, _vp, _vp]),
+    'pfb_comps_work_bytes': (_sz, [_sz]),
+    'pfb_comps_mask': (_i, [_i, _vp, _i, _sz, _vp, _vp]),
+    'pfb_comps_compact': (_i, [_sz, _i, _vp, _vp, _vp, _vp]),
+    'pfb_comps_fit': (_i, [_i, _vp, _i, _sz, _i, _vp, _vp, C.c_longlong, _vp, _i, _vp, _vp]),
+    'pfb_comps_eval': (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp]),
+    'pfb_comps_interp': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

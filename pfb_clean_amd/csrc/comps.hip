@@ -1,0 +1,482 @@
+// comps.hip -- the component model: what pfb/utils/misc.py:1084-1313 (fit_image_cube, eval_coeffs_to_cube,
+// eval_coeffs_to_slice) do on image-sized arrays.  The design matrix, its LU factors, the basis values and the
+// coordinate arrays are tiny and come from the host (utils/comps.py); these kernels do the rest:
+//   k_comps_mask     one pass over the (nplane, npix) cube: np.any over the planes as a bit mask (one 64-bit word per
+//                    64 pixels) and the number of set bits per workgroup (k_comps_mask_peel: planes off 16 bytes)
+//   k_comps_scan     exclusive scan of the workgroup counts, the total behind them (one workgroup)
+//   k_comps_compact  Ix, Iy in row-major order (np.where) from the mask, the scanned offsets and a popcount
+//   k_comps_fit      one component per lane: gather, rhs = (Xfit^T diag(w)) beta, LU substitution, all fp64
+//   k_comps_eval     scatter of sum_p E[plane][p] coeffs[p][c] to (Ix[c], Iy[c])
+//   k_comps_interp   RegularGridInterpolator(method='linear') of a rendered plane, np.pad read as zeros
+//
+// No FMA contraction in this file: the interpolation must take scipy's weights on grid-aligned points (a distance of
+// exactly 0 or 1 returns the corner value itself), and the dot products round like numpy's multiply-then-add.
+#pragma clang fp contract(off)
+#include "common.hpp"
+
+namespace pfb {
+
+typedef unsigned long long u64;
+typedef long long i64;
+
+constexpr int CP_BLOCK = 256;
+constexpr int CP_WAVES = CP_BLOCK / 64;
+// mask words (of 64 pixels) per wave.  Measured on 4096^2 x 8 fp32 with non-temporal loads (the cube is read once
+// and is larger than the Infinity Cache): 4 / 8 / 16 / 32 words stream 4.7 / 5.4 / 5.7 / 5.3 TB/s; with plain loads
+// 4.1 / 4.8 / 4.9 / 4.6
+constexpr int CP_WAVE_WORDS = 16;
+constexpr int CP_WORDS = CP_WAVES * CP_WAVE_WORDS;          // ... and per workgroup: 4096 pixels
+constexpr int CP_SCAN_BLOCK = 256;
+constexpr int CP_FIT_BLOCK = 64;
+constexpr int CP_MAX_ROWS = 64;
+constexpr int CP_MAX_PARAMS = 32;
+
+// bit i of x -> bit 4 i (16 bits in) / bit 2 i (32 bits in)
+__device__ __forceinline__ u64 spread4(u64 x) {
+    x &= 0xFFFFull;
+    x = (x | (x << 24)) & 0x000000FF000000FFull;
+    x = (x | (x << 12)) & 0x000F000F000F000Full;
+    x = (x | (x << 6)) & 0x0303030303030303ull;
+    x = (x | (x << 3)) & 0x1111111111111111ull;
+    return x;
+}
+__device__ __forceinline__ u64 spread2(u64 x) {
+    x &= 0xFFFFFFFFull;
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+
+// Word j < V of the 64 V pixels whose flags the V ballots hold (ballot k: element k of every lane): bit V i + k of the
+// word is bit 64 j / V + i of ballot k
+template <int V>
+__device__ __forceinline__ u64 mask_word(const u64 (&b)[V], int j) {
+    static_assert(V == 2 || V == 4, "16-byte packs of double or float");
+    if constexpr (V == 2) {
+        return spread2(b[0] >> (32 * j)) | (spread2(b[1] >> (32 * j)) << 1);
+    } else {
+        return spread4(b[0] >> (16 * j)) | (spread4(b[1] >> (16 * j)) << 1) | (spread4(b[2] >> (16 * j)) << 2) |
+               (spread4(b[3] >> (16 * j)) << 3);
+    }
+}
+
+// Workgroup g owns mask words [64 g, 64 g + 64), wave w of it the 16 words from 64 g + 16 w.  A lane holds V consecutive
+// pixels (V = 16 bytes of T), so one iteration of a wave covers V words.  A pixel is set iff any plane value != 0: NaN
+// counts, -0.0 does not.  This form needs every plane on a 16-byte boundary (then npix % V == 0 and no vector
+// straddles npix); k_comps_mask_peel takes the rest.  counts[g] = set bits of the workgroup's words.
+template <typename T, int V>
+__global__ void __launch_bounds__(CP_BLOCK)
+k_comps_mask(const T* __restrict__ img, int nplane, size_t npix, size_t nwords, u64* __restrict__ mask,
+             i64* __restrict__ counts) {
+    __shared__ int cnt[CP_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t w0 = (size_t)blockIdx.x * CP_WORDS + (size_t)wave * CP_WAVE_WORDS;
+    int c = 0;
+#pragma unroll
+    for (int it = 0; it < CP_WAVE_WORDS / V; ++it) {
+        const size_t wbase = w0 + (size_t)it * V;
+        const size_t pix = wbase * 64 + (size_t)lane * V;
+        bool flag[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) flag[k] = false;
+        if (pix < npix) {
+#pragma unroll 8
+            for (int p = 0; p < nplane; ++p) {
+                const Pack<T, V> v = ld_nt<T, V>(img + (size_t)p * npix, pix / V);
+#pragma unroll
+                for (int k = 0; k < V; ++k) flag[k] |= (v.e[k] != (T)0);
+            }
+        }
+        u64 b[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            b[k] = __ballot(flag[k]);
+            c += __popcll(b[k]);
+        }
+        if (lane < V && wbase + lane < nwords) mask[wbase + lane] = mask_word<V>(b, lane);
+    }
+    if (lane == 0) cnt[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < CP_WAVES; ++w) s += cnt[w];
+        counts[blockIdx.x] = s;
+    }
+}
+
+// The same for planes that do not all start on a 16-byte boundary (odd npix in fp32, say).  Plane p starts a_p
+// elements past a boundary, so its aligned vectors begin at pixel h_p = (V - a_p) mod V, its head: a lane then loads the
+// vector h_p pixels AFTER its own V pixels, and the flags of the planes of one head h form the iteration's 64 V-bit
+// mask shifted up by h bits.  The h pixels that the shift leaves open at the bottom are read one per lane; the h bits
+// pushed out at the top belong to the next iteration, which reads them as ITS bottom.  A vector that would straddle
+// npix is read element by element.
+template <typename T>
+__global__ void __launch_bounds__(CP_BLOCK)
+k_comps_mask_peel(const T* __restrict__ img, int nplane, size_t npix, size_t nwords, u64* __restrict__ mask,
+                  i64* __restrict__ counts) {
+    constexpr int V = V16<T>::N;
+    __shared__ int cnt[CP_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t w0 = (size_t)blockIdx.x * CP_WORDS + (size_t)wave * CP_WAVE_WORDS;
+    const unsigned a0 = (unsigned)((reinterpret_cast<uintptr_t>(img) / sizeof(T)) % V);
+    const unsigned step = (unsigned)(npix % V);
+    const int j = lane & (V - 1);
+    int c = 0;
+#pragma unroll 1
+    for (int it = 0; it < CP_WAVE_WORDS / V; ++it) {
+        const size_t wbase = w0 + (size_t)it * V;
+        const size_t pix0 = wbase * 64;
+        u64 word = 0;                                    // word j of the iteration, in lanes j < V
+#pragma unroll
+        for (int h = 0; h < V; ++h) {
+            const size_t pix = pix0 + (size_t)lane * V + h;
+            bool flag[V], low = false;
+#pragma unroll
+            for (int k = 0; k < V; ++k) flag[k] = false;
+            for (int p = 0; p < nplane; ++p) {
+                if ((V - (a0 + p * step) % V) % V != (unsigned)h) continue;          // wave-uniform
+                const T* plane = img + (size_t)p * npix;
+                if (pix + V <= npix) {
+                    const Pack<T, V> v = ld_nt<T, V>(plane + h, (pix - h) / V);
+#pragma unroll
+                    for (int k = 0; k < V; ++k) flag[k] |= (v.e[k] != (T)0);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < V; ++k)
+                        if (pix + k < npix) flag[k] |= (plane[pix + k] != (T)0);
+                }
+                if (lane < h && pix0 + lane < npix) low |= (plane[pix0 + lane] != (T)0);
+            }
+            u64 b[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) b[k] = __ballot(flag[k]);
+            const u64 lowbits = __ballot(low);
+            if (lane < V) {
+                const u64 here = mask_word<V>(b, j);
+                if (h == 0) {
+                    word |= here;
+                } else {
+                    const u64 below = j > 0 ? mask_word<V>(b, j - 1) : lowbits << (64 - h);
+                    word |= (here << h) | (below >> (64 - h));
+                }
+            }
+        }
+        if (lane < V && wbase + lane < nwords) {
+            mask[wbase + lane] = word;
+            c += __popcll(word);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if (lane == 0) cnt[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < CP_WAVES; ++w) s += cnt[w];
+        counts[blockIdx.x] = s;
+    }
+}
+
+// one workgroup: offs[g] <- sum_{h < g} offs[h] in place, offs[n] <- the total
+__global__ void __launch_bounds__(CP_SCAN_BLOCK)
+k_comps_scan(i64* __restrict__ offs, int n) {
+    __shared__ i64 wsum[CP_SCAN_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    i64 carry = 0;
+    for (int base = 0; base < n; base += CP_SCAN_BLOCK) {
+        const int i = base + threadIdx.x;
+        const i64 c = i < n ? offs[i] : 0;
+        i64 inc = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const i64 t = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += t;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        i64 before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < CP_SCAN_BLOCK / 64; ++w) {
+            const i64 s = wsum[w];
+            if (w < wave) before += s;
+            total += s;
+        }
+        if (i < n) offs[i] = carry + before + inc - c;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) offs[n] = carry;
+}
+
+// same ownership of words as k_comps_mask; pixel q = 64 word + bit is component offs[g] + (set bits before it in the
+// workgroup's words), i.e. components are numbered in pixel order: the order of np.where on the (nx, ny) mask
+__global__ void __launch_bounds__(CP_BLOCK)
+k_comps_compact(const u64* __restrict__ mask, const i64* __restrict__ offs, size_t nwords, i64 ny,
+                i64* __restrict__ Ix, i64* __restrict__ Iy) {
+    __shared__ u64 words[CP_WORDS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t w0 = (size_t)blockIdx.x * CP_WORDS;
+    if (threadIdx.x < CP_WORDS) words[threadIdx.x] = w0 + threadIdx.x < nwords ? mask[w0 + threadIdx.x] : 0;
+    __syncthreads();
+    i64 base = offs[blockIdx.x];
+    for (int j = 0; j < wave * CP_WAVE_WORDS; ++j) base += __popcll(words[j]);
+#pragma unroll
+    for (int k = 0; k < CP_WAVE_WORDS; ++k) {
+        const int j = wave * CP_WAVE_WORDS + k;
+        const u64 bits = words[j];
+        if ((bits >> lane) & 1) {
+            const i64 pos = base + __popcll(bits & ((1ull << lane) - 1));
+            const i64 q = (i64)((w0 + j) * 64 + lane);
+            Ix[pos] = q / ny;
+            Iy[pos] = q % ny;
+        }
+        base += __popcll(bits);
+    }
+}
+
+// One component per lane, one wave per workgroup.  sys = [A (nparam, nrow) | LU (nparam, nparam) | piv (nparam)], all
+// doubles, is staged in LDS, followed by the lanes' vectors v[p][lane]: every dynamically indexed array lives in LDS.
+// LU / piv are LAPACK getrf's (unit lower triangle below the diagonal; row i was exchanged with row piv[i], in order).
+template <typename T>
+__global__ void __launch_bounds__(CP_FIT_BLOCK)
+k_comps_fit(const T* __restrict__ img, int nrow, size_t npix, i64 ny, const i64* __restrict__ Ix,
+            const i64* __restrict__ Iy, i64 ncomps, const double* __restrict__ sys, int nparam,
+            double* __restrict__ coeffs) {
+    extern __shared__ double cp_lds[];
+    const int nsys = nparam * nrow + nparam * nparam + nparam;
+    for (int i = threadIdx.x; i < nsys; i += CP_FIT_BLOCK) cp_lds[i] = sys[i];
+    __syncthreads();
+    const double* A = cp_lds;
+    const double* LU = A + nparam * nrow;
+    const double* piv = LU + nparam * nparam;
+    const int lane = threadIdx.x;
+    double* v = cp_lds + nsys + lane;                         // v[p * CP_FIT_BLOCK]
+    const i64 c = (i64)blockIdx.x * CP_FIT_BLOCK + lane;
+    if (c >= ncomps) return;
+    const size_t q = (size_t)(Ix[c] * ny + Iy[c]);
+    for (int p = 0; p < nparam; ++p) v[p * CP_FIT_BLOCK] = 0.0;
+    for (int r = 0; r < nrow; ++r) {
+        const double b = (double)img[(size_t)r * npix + q];
+        for (int p = 0; p < nparam; ++p) v[p * CP_FIT_BLOCK] += A[p * nrow + r] * b;
+    }
+    for (int i = 0; i < nparam; ++i) {
+        const int pi = (int)piv[i];
+        if (pi != i) {
+            const double t = v[i * CP_FIT_BLOCK];
+            v[i * CP_FIT_BLOCK] = v[pi * CP_FIT_BLOCK];
+            v[pi * CP_FIT_BLOCK] = t;
+        }
+    }
+    for (int i = 1; i < nparam; ++i) {
+        double s = v[i * CP_FIT_BLOCK];
+        for (int j = 0; j < i; ++j) s -= LU[i * nparam + j] * v[j * CP_FIT_BLOCK];
+        v[i * CP_FIT_BLOCK] = s;
+    }
+    for (int i = nparam - 1; i >= 0; --i) {
+        double s = v[i * CP_FIT_BLOCK];
+        for (int j = i + 1; j < nparam; ++j) s -= LU[i * nparam + j] * v[j * CP_FIT_BLOCK];
+        v[i * CP_FIT_BLOCK] = s / LU[i * nparam + i];
+    }
+    for (int p = 0; p < nparam; ++p) coeffs[(size_t)p * ncomps + c] = v[p * CP_FIT_BLOCK];
+}
+
+// grid (ceil(ncomps / block), nplane): out[plane, Ix[c], Iy[c]] = sum_p E[plane, p] coeffs[p, c]; a component outside
+// the (nx, ny) plane is skipped
+template <typename TO>
+__global__ void __launch_bounds__(CP_BLOCK)
+k_comps_eval(const double* __restrict__ E, const double* __restrict__ coeffs, const i64* __restrict__ Ix,
+             const i64* __restrict__ Iy, i64 ncomps, int nparam, i64 nx, i64 ny, TO* __restrict__ out) {
+    const i64 c = (i64)blockIdx.x * CP_BLOCK + threadIdx.x;
+    if (c >= ncomps) return;
+    const int plane = blockIdx.y;
+    const i64 ix = Ix[c], iy = Iy[c];
+    if (ix < 0 || ix >= nx || iy < 0 || iy >= ny) return;
+    double acc = 0.0;
+    for (int p = 0; p < nparam; ++p) acc += E[(size_t)plane * nparam + p] * coeffs[(size_t)p * ncomps + c];
+    out[((size_t)plane * nx + ix) * ny + iy] = (TO)acc;
+}
+
+// np.searchsorted(grid, x) - 1 clipped to [0, n - 2]
+__device__ __forceinline__ int interval(const double* __restrict__ grid, int n, double x) {
+    int lo = 0, hi = n;                        // first index with grid[index] >= x
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (grid[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    int i = lo - 1;
+    if (i < 0) i = 0;
+    if (i > n - 2) i = n - 2;
+    return i;
+}
+
+struct InterpGeom {
+    int nxi, nyi;        // the stored plane
+    int padx, pady;      // zeros np.pad puts in front of it
+    int nxp, nyp;        // lengths of the (padded) coordinate arrays
+    int nxo, nyo;
+};
+
+// grid (ceil(nyo / block), min(nxo, 65535)): scipy's _evaluate_linear on the padded plane, which is never stored
+template <typename TO>
+__global__ void __launch_bounds__(CP_BLOCK)
+k_comps_interp(const double* __restrict__ img, InterpGeom g, const double* __restrict__ xin,
+               const double* __restrict__ yin, const double* __restrict__ xo, const double* __restrict__ yo,
+               TO* __restrict__ out) {
+    const int j = blockIdx.x * CP_BLOCK + threadIdx.x;
+    if (j >= g.nyo) return;
+    const double y = yo[j];
+    const int jj = interval(yin, g.nyp, y);
+    const double dy = (y - yin[jj]) / (yin[jj + 1] - yin[jj]);
+    for (int i = blockIdx.y; i < g.nxo; i += gridDim.y) {
+        const double x = xo[i];
+        const int ii = interval(xin, g.nxp, x);
+        const double dx = (x - xin[ii]) / (xin[ii + 1] - xin[ii]);
+        auto at = [&](int a, int b) -> double {
+            a -= g.padx;
+            b -= g.pady;
+            return (a >= 0 && a < g.nxi && b >= 0 && b < g.nyi) ? img[(size_t)a * g.nyi + b] : 0.0;
+        };
+        double val = 0.0;
+        val = val + at(ii, jj) * ((1.0 - dx) * (1.0 - dy));
+        val = val + at(ii, jj + 1) * ((1.0 - dx) * dy);
+        val = val + at(ii + 1, jj) * (dx * (1.0 - dy));
+        val = val + at(ii + 1, jj + 1) * (dx * dy);
+        out[(size_t)i * g.nyo + j] = (TO)val;
+    }
+}
+
+static inline size_t comps_nwords(size_t npix) { return (npix + 63) / 64; }
+static inline size_t comps_nblocks(size_t npix) { return (comps_nwords(npix) + CP_WORDS - 1) / CP_WORDS; }
+constexpr size_t CP_MAX_PIX = (size_t)1 << 40;              // 2^28 workgroups
+
+template <typename T>
+static void mask_launch(const void* img, int nplane, size_t npix, u64* mask, i64* counts, hipStream_t st) {
+    const size_t nwords = comps_nwords(npix);
+    const dim3 grid((unsigned)comps_nblocks(npix));
+    constexpr int V = V16<T>::N;
+    // every plane starts on a 16-byte boundary
+    if (aligned16(img) && (npix * sizeof(T)) % 16 == 0)
+        hipLaunchKernelGGL((k_comps_mask<T, V>), grid, dim3(CP_BLOCK), 0, st, (const T*)img, nplane, npix, nwords,
+                           mask, counts);
+    else
+        hipLaunchKernelGGL(k_comps_mask_peel<T>, grid, dim3(CP_BLOCK), 0, st, (const T*)img, nplane, npix, nwords, mask,
+                           counts);
+}
+
+}  // namespace pfb
+
+using namespace pfb;
+
+extern "C" {
+
+size_t pfb_comps_work_bytes(size_t npix) {
+    if (npix < 1 || npix > CP_MAX_PIX) return 0;
+    return 8 * (comps_nwords(npix) + comps_nblocks(npix) + 1);
+}
+
+int pfb_comps_mask(int dtype, const void* image, int nplane, size_t npix, void* work, void* stream) {
+    PFB_REQUIRE(image && work, PFB_ERR_INVALID, "comps_mask: null argument");
+    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "comps_mask: bad dtype %d", dtype);
+    PFB_REQUIRE(nplane >= 1 && npix >= 1 && npix <= CP_MAX_PIX, PFB_ERR_INVALID,
+                "comps_mask: nplane %d / npix %zu out of range", nplane, npix);
+    PFB_REQUIRE(((uintptr_t)work & 7u) == 0, PFB_ERR_INVALID, "comps_mask: work must be 8-byte aligned");
+    PFB_REQUIRE((uintptr_t)image % (dtype == PFB_F32 ? 4 : 8) == 0, PFB_ERR_INVALID,
+                "comps_mask: image is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    u64* mask = (u64*)work;
+    i64* offs = (i64*)work + comps_nwords(npix);
+    if (dtype == PFB_F32) mask_launch<float>(image, nplane, npix, mask, offs, st);
+    else                  mask_launch<double>(image, nplane, npix, mask, offs, st);
+    hipLaunchKernelGGL(k_comps_scan, dim3(1), dim3(CP_SCAN_BLOCK), 0, st, offs, (int)comps_nblocks(npix));
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_comps_compact(size_t npix, int ny, const void* work, long long* Ix, long long* Iy, void* stream) {
+    PFB_REQUIRE(work && Ix && Iy, PFB_ERR_INVALID, "comps_compact: null argument");
+    PFB_REQUIRE(npix >= 1 && npix <= CP_MAX_PIX && ny >= 1 && npix % (size_t)ny == 0, PFB_ERR_INVALID,
+                "comps_compact: npix %zu is not a multiple of ny %d", npix, ny);
+    const u64* mask = (const u64*)work;
+    const i64* offs = (const i64*)work + comps_nwords(npix);
+    hipLaunchKernelGGL(k_comps_compact, dim3((unsigned)comps_nblocks(npix)), dim3(CP_BLOCK), 0, as_stream(stream), mask,
+                       offs, comps_nwords(npix), (i64)ny, Ix, Iy);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_comps_fit(int dtype, const void* image, int nrow, size_t npix, int ny, const long long* Ix, const long long* Iy,
+                  long long ncomps, const double* sys, int nparam, double* coeffs, void* stream) {
+    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "comps_fit: bad dtype %d", dtype);
+    PFB_REQUIRE(nrow >= 1 && nparam >= 1 && ncomps >= 0 && ny >= 1 && npix >= 1, PFB_ERR_INVALID,
+                "comps_fit: nrow %d / nparam %d / ncomps %lld / npix %zu out of range", nrow, nparam, ncomps, npix);
+    PFB_REQUIRE(nrow <= CP_MAX_ROWS && nparam <= CP_MAX_PARAMS, PFB_ERR_UNSUPPORTED,
+                "comps_fit: nrow %d / nparam %d beyond the supported %d / %d", nrow, nparam, CP_MAX_ROWS, CP_MAX_PARAMS);
+    if (ncomps == 0) return PFB_OK;
+    PFB_REQUIRE(image && Ix && Iy && sys && coeffs, PFB_ERR_INVALID, "comps_fit: null argument");
+    PFB_REQUIRE(ncomps <= (long long)npix, PFB_ERR_INVALID, "comps_fit: %lld components in %zu pixels", ncomps, npix);
+    const size_t lds = sizeof(double) * ((size_t)nparam * nrow + (size_t)nparam * nparam + nparam +
+                                         (size_t)nparam * CP_FIT_BLOCK);
+    const dim3 grid((unsigned)((ncomps + CP_FIT_BLOCK - 1) / CP_FIT_BLOCK));
+    hipStream_t st = as_stream(stream);
+    if (dtype == PFB_F32)
+        hipLaunchKernelGGL(k_comps_fit<float>, grid, dim3(CP_FIT_BLOCK), lds, st, (const float*)image, nrow, npix,
+                           (i64)ny, Ix, Iy, ncomps, sys, nparam, coeffs);
+    else
+        hipLaunchKernelGGL(k_comps_fit<double>, grid, dim3(CP_FIT_BLOCK), lds, st, (const double*)image, nrow, npix,
+                           (i64)ny, Ix, Iy, ncomps, sys, nparam, coeffs);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_comps_eval(int dtype, const double* E, int nplane, int nparam, const double* coeffs, const long long* Ix,
+                   const long long* Iy, long long ncomps, int nx, int ny, void* out, void* stream) {
+    PFB_REQUIRE(out && E, PFB_ERR_INVALID, "comps_eval: null argument");
+    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "comps_eval: bad dtype %d", dtype);
+    PFB_REQUIRE(nplane >= 1 && nplane <= 65535 && nparam >= 1 && nx >= 1 && ny >= 1 && ncomps >= 0, PFB_ERR_INVALID,
+                "comps_eval: nplane %d / nparam %d / shape (%d,%d) / ncomps %lld out of range", nplane, nparam, nx, ny,
+                ncomps);
+    hipStream_t st = as_stream(stream);
+    const size_t n = (size_t)nplane * nx * ny;
+    PFB_HIP_CHECK(hipMemsetAsync(out, 0, n * (dtype == PFB_F32 ? 4 : 8), st));
+    if (ncomps == 0) return PFB_OK;
+    PFB_REQUIRE(coeffs && Ix && Iy, PFB_ERR_INVALID, "comps_eval: null argument");
+    const dim3 grid((unsigned)((ncomps + CP_BLOCK - 1) / CP_BLOCK), nplane);
+    if (dtype == PFB_F32)
+        hipLaunchKernelGGL(k_comps_eval<float>, grid, dim3(CP_BLOCK), 0, st, E, coeffs, Ix, Iy, ncomps, nparam, (i64)nx,
+                           (i64)ny, (float*)out);
+    else
+        hipLaunchKernelGGL(k_comps_eval<double>, grid, dim3(CP_BLOCK), 0, st, E, coeffs, Ix, Iy, ncomps, nparam, (i64)nx,
+                           (i64)ny, (double*)out);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_comps_interp(int dtype, const double* image, int nxi, int nyi, int npad_xl, int npad_yl, const double* xin,
+                     int nx_pad, const double* yin, int ny_pad, const double* xo, int nxo, const double* yo, int nyo,
+                     void* out, void* stream) {
+    PFB_REQUIRE(image && xin && yin && xo && yo && out, PFB_ERR_INVALID, "comps_interp: null argument");
+    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "comps_interp: bad dtype %d", dtype);
+    PFB_REQUIRE(nxi >= 1 && nyi >= 1 && npad_xl >= 0 && npad_yl >= 0 && nx_pad >= npad_xl + nxi &&
+                ny_pad >= npad_yl + nyi, PFB_ERR_INVALID,
+                "comps_interp: padding (%d,%d) puts the (%d,%d) plane outside the (%d,%d) grid", npad_xl, npad_yl, nxi,
+                nyi, nx_pad, ny_pad);
+    PFB_REQUIRE(nx_pad >= 2 && ny_pad >= 2 && nxo >= 1 && nyo >= 1, PFB_ERR_INVALID,
+                "comps_interp: grid (%d,%d) / output (%d,%d) out of range", nx_pad, ny_pad, nxo, nyo);
+    const InterpGeom g{nxi, nyi, npad_xl, npad_yl, nx_pad, ny_pad, nxo, nyo};
+    const dim3 grid((nyo + CP_BLOCK - 1) / CP_BLOCK, nxo < 65535 ? nxo : 65535);
+    hipStream_t st = as_stream(stream);
+    if (dtype == PFB_F32)
+        hipLaunchKernelGGL(k_comps_interp<float>, grid, dim3(CP_BLOCK), 0, st, image, g, xin, yin, xo, yo, (float*)out);
+    else
+        hipLaunchKernelGGL(k_comps_interp<double>, grid, dim3(CP_BLOCK), 0, st, image, g, xin, yin, xo, yo,
+                           (double*)out);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@ The three pfb/utils/misc.py helpers that sit on the hot path.
     dds2cubes(dds, nband, ...)            misc.py:664-739   (cube assembly, device resident)
     freqmul(A, x), setup_parametrisation  misc.py:1366-1423 (band coupling of the fwdbwd parametrisations)
     Gaussian2D, get_padding_info, convolve2gaussres   misc.py:109-238 (restoring-beam convolution)
+    fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice   misc.py:1084-1313 (component model, utils/comps.py)
 """
 import math
 import threading
@@ -17,6 +18,7 @@ from .. import _lib, _dev
 from .._dev import norm_diff_sums
 from .._plan import PlanCache
 from ..operators.psf import PsfConvPlan
+from .comps import fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice  # noqa: F401
 
 
 def norm_diff(x, xp):
