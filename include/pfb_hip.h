@@ -489,6 +489,55 @@ int pfb_comps_interp(int dtype, const double* image, int nxi, int nyi, int npad_
                      int nx_pad, const double* yin, int ny_pad, const double* xo, int nxo, const double* yo, int nyo,
                      void* out, void* stream);
 
+/* ----------------------------------------------------------------------- clean beam
+ * What pfb/utils/misc.py:506-584 (psf_errorsq, fitcleanbeam) do on image-sized arrays.  The host keeps the optimiser
+ * (scipy's fmin_l_bfgs_b, misc.py:577-581) and calls pfb_beamfit_objective from its callback.  All fit arithmetic is
+ * fp64 whatever the PSF dtype; nothing is allocated, there is no plan and no global state; asynchronous on `stream`.
+ *
+ * `work` is device scratch of pfb_beamfit_work_bytes(nband, npix) bytes, 8-byte aligned.  It BEGINS with one record of
+ * PFB_BEAMFIT_RECORD doubles per band, the only thing the host reads:
+ *   [0] max          psf[v].max(), NaN-propagating (misc.py:552)
+ *   [1] any          1.0 iff psf[v].any() (misc.py:549); everything behind it is 0 when it is 0
+ *   [2] centre_above 1.0 iff psf[v, nx//2, ny//2] / max > level; everything behind it is 0 when it is 0
+ *   [3..6]           x.min(), x.max(), y.min(), y.max() over the centre island (misc.py:561-564)
+ *   [7], [8]         np.abs(x).max(), np.abs(y).max() (misc.py:565)
+ *   [9]              pixels of the centre island
+ *   [10]             pixels of the fit region rrsq < extent * rsq (misc.py:566-567)
+ *   [11]             extent * rsq
+ * Behind the records: the partial maxima of the streaming pass and per band a visited bit mask, one 64-bit word per
+ * 64 pixels. */
+#define PFB_BEAMFIT_RECORD 16
+
+/* Bytes of `work`; 0 when nband (1 .. 65535) or npix (1 .. 2^40) is out of range. */
+size_t pfb_beamfit_work_bytes(int nband, size_t npix);
+
+/* misc.py:549, 552: per band of the (nband, npix) cube of `dtype` the maximum (a NaN anywhere gives NaN, like
+ * ndarray.max) and np.any (a NaN counts, -0.0 does not) into record [0], [1]; the rest of the record and the band's
+ * visited mask are cleared.  One pass over the cube, the only one of the fit; 16-byte loads, a plane that does not
+ * start on a 16-byte boundary (odd npix in fp32) is read from its first aligned vector on with a peel of up to 3
+ * elements at either end.  The partials are combined in a fixed order. */
+int pfb_beamfit_max(int dtype, const void* psf, int nband, size_t npix, void* work, void* stream);
+
+/* misc.py:552-567, all bands in one launch: the island of `psf[v] / max > level` that holds (nx // 2, ny // 2) under
+ * 8-connectivity (skimage.morphology.label's default in 2-D), grown from that pixel until a sweep adds nothing, and
+ * from it record [2..11].  The quotient is formed in `dtype` and compared in `dtype` with `level` rounded to it
+ * (NumPy 2), strictly.  Coordinates are x_i = -nx / 2 + i, y_j = -ny / 2 + j (misc.py:542-543).  The fit region is
+ * counted inside the square of half-side ceil(sqrt(extent * rsq)) around the centre, never over the plane.
+ * To follow pfb_beamfit_max on the same `work` (it needs the cleared mask), once. */
+int pfb_beamfit_lobe(int dtype, const void* psf, int nband, int nx, int ny, double level, double extent, void* work,
+                     void* stream);
+
+/* misc.py:506-526 and its gradient for band `band` of the cube at x = (emaj, emin, pa): out[0] = f =
+ * sum_i (d_i - exp(-2 sqrt(2 ln 2) Q_i))^2 over the fit region of the band's record, out[1..3] = df/d(emaj, emin, pa);
+ * out: 4 device doubles.  d_i = psf / max in `dtype`, then fp64; Q = xy^T R^T diag(1/Smin^2, 1/Smaj^2) R xy with
+ * Smin = min(emaj, emin), Smaj = max(emaj, emin) and R the rotation by deg2rad(-pa), whose cosine and sine are taken on
+ * the host.  The derivatives are analytic, through Smin and Smaj; at emaj == emin each of the two gets the mean of
+ * the Smin and the Smaj derivative, which is what jax's documentation states for minimum / maximum at a tie (taken
+ * from the documentation, not verified against jax).  emin = 0 gives non-finite values as in the reference.  Sums in a
+ * fixed order. */
+int pfb_beamfit_objective(int dtype, const void* psf, int band, int nx, int ny, double emaj, double emin, double pa,
+                          const void* work, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ wavelet hot path behind the reference's own Python entry points:
     pfb.opt.power_method   -> pfb_clean_amd.opt.power_method   power_method
     pfb.opt.primal_dual    -> pfb_clean_amd.opt.primal_dual    primal_dual_optimised
     pfb.prox.prox_21m      -> pfb_clean_amd.prox.prox_21m      prox_21m_numba, dual_update_numba
-    pfb.utils.misc         -> pfb_clean_amd.utils.misc         norm_diff, l1reweight_func
+    pfb.utils.misc         -> pfb_clean_amd.utils.misc         norm_diff, l1reweight_func, fitcleanbeam
 
 All arithmetic runs in hand-written HIP kernels (libpfb_hip.so, C-ABI in
 include/pfb_hip.h).  There is no CPU fallback: importing the operator modules without

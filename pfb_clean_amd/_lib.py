@@ -107,6 +107,10 @@ SIGNATURES = {
     'pfb_comps_fit': (_i, [_i, _vp, _i, _sz, _i, _vp, _vp, C.c_longlong, _vp, _i, _vp, _vp]),
     'pfb_comps_eval': (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp]),
     'pfb_comps_interp': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    'pfb_beamfit_work_bytes': (_sz, [_i, _sz]),
+    'pfb_beamfit_max': (_i, [_i, _vp, _i, _sz, _vp, _vp]),
+    'pfb_beamfit_lobe': (_i, [_i, _vp, _i, _i, _i, _d, _d, _vp, _vp]),
+    'pfb_beamfit_objective': (_i, [_i, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -7,6 +7,7 @@ The three pfb/utils/misc.py helpers that sit on the hot path.
     freqmul(A, x), setup_parametrisation  misc.py:1366-1423 (band coupling of the fwdbwd parametrisations)
     Gaussian2D, get_padding_info, convolve2gaussres   misc.py:109-238 (restoring-beam convolution)
     fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice   misc.py:1084-1313 (component model, utils/comps.py)
+    fitcleanbeam                          misc.py:506-584   (clean beam, utils/beamfit.py)
 """
 import math
 import threading
@@ -19,6 +20,7 @@ from .._dev import norm_diff_sums
 from .._plan import PlanCache
 from ..operators.psf import PsfConvPlan
 from .comps import fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice  # noqa: F401
+from .beamfit import fitcleanbeam  # noqa: F401
 
 
 def norm_diff(x, xp):
