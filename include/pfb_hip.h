@@ -538,6 +538,66 @@ int pfb_beamfit_lobe(int dtype, const void* psf, int nband, int nx, int ny, doub
 int pfb_beamfit_objective(int dtype, const void* psf, int band, int nx, int ny, double emaj, double emin, double pa,
                           const void* work, double* out, void* stream);
 
+/* ------------------------------------------------------------------ major-cycle statistics
+ * What the workers' major-cycle loops do inline between the solver calls (workers/klean.py:190-339, spotless.py:155-363,
+ * fluxmop.py:129-199, fwdbwd.py:233, 423): the band sum of a cube with its statistics, the mop mask and the masked
+ * system of the flux mop.  fp32 and fp64; nothing is allocated, there is no plan and no global state; asynchronous on
+ * `stream`.  16-byte loads when every plane starts on a 16-byte boundary (npix a multiple of 4 resp. 2 elements and
+ * aligned bases); otherwise (odd npix in fp32, a base offset by 1-3 elements) the same kernels run one element per
+ * lane.  Masks are unsigned char planes, 0 = out, anything else = in; the ones written here hold 0 or 1.  No output may
+ * overlap an input or another output (sum_out a band of x, b the residual, x0 the seed, ...): the kernels are not
+ * written for in-place use and nothing checks it beyond `out != mask` in pfb_mask_close. */
+
+/* Doubles per set of the record pfb_bandsum_stats writes: [count, mean, M2, absmax]. */
+#define PFB_CYCLE_RECORD 4
+
+/* Bytes of the `work` buffer of pfb_bandsum_stats (the workgroups' partial records) for nset sets; host only; 0 when
+ * nset (1 .. 65535) is out of range. */
+size_t pfb_cycle_work_bytes(int nset);
+
+/* np.sum(x, axis=0) with np.std and np.abs().max() of the result, in one pass.
+ * x: (nband, nset, npix) of `dtype` -- a residual cube has nset = 1, a coefficient cube nset = nbasis and npix =
+ *   Nymax * Nxmax.  Per pixel s = x[0] + x[1] + ... in `dtype`, in band order (numpy's order: the bits of np.sum).
+ * model: NULL, or (nband_m, npix) of `dtype`, allowed with nset == 1 only.  A pixel is quiet iff every model band is
+ *   == 0 there (a NaN makes it not quiet, -0.0 does not: ~np.any(model, axis=0)); without a model every pixel is quiet.
+ * sum_out: NULL, or (nset, npix) of `dtype`, receives s.
+ * work: device scratch of pfb_cycle_work_bytes(nset) bytes, 8-byte aligned.
+ * out: nset records of PFB_CYCLE_RECORD device doubles:
+ *   [0] count   quiet pixels of the set
+ *   [1] mean    of s over them, fp64 (0 when count == 0)
+ *   [2] M2      sum (s - mean)^2 over them, fp64: np.std = sqrt(M2 / count), nan for count == 0 as in numpy
+ *   [3] absmax  max |s| over ALL pixels of the set, a NaN anywhere gives NaN (ndarray.max)
+ * The moments are accumulated about a pivot from the data and merged pairwise (M2 = M2a + M2b + d^2 na nb / (na + nb)),
+ * never as sum x, sum x^2: |mean| >> std does not cancel.  Fixed combination order: identical bits from run to run.  No
+ * floating-point atomics; the merge of the workgroups' partials is a second, one-wave-per-set launch. */
+int pfb_bandsum_stats(int dtype, const void* x, int nband, int nset, size_t npix, const void* model, int nband_m,
+                      void* sum_out, void* work, double* out, void* stream);
+
+/* klean.py:301-305 / fluxmop.py:129: a support and its binary closing.
+ * Exactly one of `cube` and `mask` is non-NULL:
+ *   cube: (nband, nx, ny) of `dtype`; the support is any(v != 0) over the bands (a NaN counts, -0.0 does not), or
+ *         any(v > min_value) when has_min != 0, min_value rounded to `dtype` (NumPy 2 for a Python-float bound; a NaN
+ *         does not count);
+ *   mask: (nx, ny) unsigned char, the support is mask != 0 (`dtype`, nband, has_min, min_value are ignored).
+ * connectivity selects the structure of scipy.ndimage.generate_binary_structure(2, c): c <= 0: no closing, out is the
+ * support itself (the worker's `if opts.dirosion`); c == 1: the 5-point cross; c >= 2: the full 3 x 3.
+ * out: (nx, ny) unsigned char, 0 or 1, not the input mask: one binary_dilation followed by one binary_erosion, outside
+ * the image counting as 0 in BOTH (scipy's border_value=0).  A pixel whose structure reaches outside the image is
+ * therefore never set, whatever the support: the reference's mop mask loses its border pixels the same way. */
+int pfb_mask_close(int dtype, const void* cube, int nband, const unsigned char* mask, int nx, int ny, int has_min,
+                   double min_value, int connectivity, unsigned char* out, void* stream);
+
+/* klean.py:306-317 / fluxmop.py:166-199: the masked system in one pass.
+ * residual: (nband, npix) of `dtype` (may be NULL when b is); mask: (npix) unsigned char.
+ * beam: NULL, or (nband_beam, npix) of `dtype` with nband_beam == nband or 1; seed: NULL, or one (npix) plane.
+ * Outputs, each may be NULL:
+ *   beam_eff (nband_beam, npix), or (1, npix) without a beam: beam * mask resp. the mask as 0 / 1 of `dtype`;
+ *   b (nband, npix) = beam_eff * residual, the product formed in `dtype` in this order: a NaN residual outside the mask
+ *     stays NaN, as in numpy;
+ *   x0 (nband, npix) = mask ? seed : 0, zeros without a seed. */
+int pfb_masked_problem(int dtype, const void* residual, const unsigned char* mask, const void* beam, int nband_beam,
+                       const void* seed, int nband, size_t npix, void* b, void* x0, void* beam_eff, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

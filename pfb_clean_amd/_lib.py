@@ -111,6 +111,10 @@ SIGNATURES = {
     'pfb_beamfit_max': (_i, [_i, _vp, _i, _sz, _vp, _vp]),
     'pfb_beamfit_lobe': (_i, [_i, _vp, _i, _i, _i, _d, _d, _vp, _vp]),
     'pfb_beamfit_objective': (_i, [_i, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
+    'pfb_cycle_work_bytes': (_sz, [_i]),
+    'pfb_bandsum_stats': (_i, [_i, _vp, _i, _i, _sz, _vp, _i, _vp, _vp, _vp, _vp]),
+    'pfb_mask_close': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _d, _i, _vp, _vp]),
+    'pfb_masked_problem': (_i, [_i, _vp, _vp, _vp, _i, _vp, _i, _sz, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
