@@ -31,8 +31,6 @@ template <typename T> struct Tile;
 template <> struct Tile<float>  { static constexpr int TA = 32; static constexpr int TS = 64; };
 template <> struct Tile<double> { static constexpr int TA = 16; static constexpr int TS = 32; };
 
-template <typename T> struct Filt { T lo[MAXF]; T hi[MAXF]; int F; };
-
 struct LevelInfo {
     int nxin, nyin;     // analysis input (= approx of the previous level) shape
     int Cx, Cy;         // coefficients per half at this level (sx, sy)
@@ -52,8 +50,7 @@ struct pfb_psi_plan {
     int nband, nx, ny, nbasis, nlevel, dtype;
     int Nxmax, Nymax;
     pfb::BasisInfo* bases;
-    void* scratch[2];           // per band ping-pong approx / partial-image buffers
-    size_t scratch_band;        // elements per band in each scratch buffer
+    size_t scratch_band;        // elements per band and wavelet basis in each bscr buffer (the kernels' band stride)
     // fused finest synthesis level (k_idwt_finest_fused2): per-basis parameter table on the device
     // and one level-1 partial image per basis and band (all alive when the fused kernel runs)
     void* fin_prm;
@@ -95,8 +92,8 @@ __device__ __forceinline__ TileId xcd_tile() {
 }
 
 // ------------------------------------------------------------------ 'self' basis
-// dst[c][r] = src[r][c]   (src R x C, ld ls; dst ld ld); ACC adds instead of storing
-template <typename T, bool ACC>
+// dst[c][r] = src[r][c]   (src R x C, ld ls; dst ld ld)
+template <typename T>
 __global__ void __launch_bounds__(256)
 k_transpose(const T* __restrict__ src, size_t src_band, int ls, T* __restrict__ dst, size_t dst_band,
             int ld, int R, int C) {
@@ -109,20 +106,19 @@ k_transpose(const T* __restrict__ src, size_t src_band, int ls, T* __restrict__ 
         if (r0 + r < R && c0 + tx < C) tile[r][tx] = s[(size_t)(r0 + r) * ls + c0 + tx];
     __syncthreads();
     for (int c = ty; c < 32; c += 8)
-        if (c0 + c < C && r0 + tx < R) {
-            T* p = d + (size_t)(c0 + c) * ld + r0 + tx;
-            if (ACC) *p += tile[tx][c]; else *p = tile[tx][c];
-        }
+        if (c0 + c < C && r0 + tx < R) d[(size_t)(c0 + c) * ld + r0 + tx] = tile[tx][c];
 }
 
 // ------------------------------------------------------------------ analysis level
-// in    : (nxin, nyin) row-major, ld = ldin
-// coeffs: this level's block origin, ld = ldc; quadrants [0:Cy | Cy:2Cy] x [0:Cx | Cx:2Cx]
+// The tile functions (dwt_tile, dwt_tile_fast) take
+// src   : (nxin, nyin) row-major, ld = ldin
+// dst   : this level's block origin, ld = ldc; quadrants [0:Cy | Cy:2Cy] x [0:Cx | Cx:2Cx]
 // approx: optional (Cx, Cy) row-major copy of the LL quadrant transposed (next level input)
 // F (filter length) and TA (output tile edge per quadrant) are compile-time: the staging loop
 // is fully unrolled so that ALL global loads of a thread are in flight before the first LDS
 // store (a rolled load-wait-store loop pays the HBM latency once per trip: 104 us -> see
 // DESIGN.md), and the tap loops are unrolled FMA chains.
+//
 // layout of the register-blocked tile (dwt_tile_fast below), shared with the host's LDS sizing
 template <typename T> struct DwtFast {
     static constexpr int EV = 16 / (int)sizeof(T);          // elements per 16-byte access
@@ -150,23 +146,6 @@ template <typename T> struct DwtFast {
         return (size_t)2 * ni(TA, F) * sa(TA, F) + (size_t)bo(TA, F) + (size_t)(ni(TA, F) / 2) * sb(TA);
     }
 };
-
-template <typename T, int F, int TA>
-__device__ __forceinline__ void dwt_tile(T* smem, const T* __restrict__ flo, const T* __restrict__ fhi,
-                                         const T* __restrict__ src, int ldin, int nxin, int nyin,
-                                         T* __restrict__ dst, int ldc, int Cx, int Cy, T* __restrict__ approx,
-                                         int ox0, int oy0);
-
-template <typename T, int F, int TA>
-__global__ void __launch_bounds__(256)
-k_dwt_level(const T* __restrict__ in, size_t in_band, int ldin, int nxin, int nyin,
-            T* __restrict__ coeffs, size_t c_band, int ldc, int Cx, int Cy,
-            T* __restrict__ approx, size_t a_band, Filt<T> f) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    dwt_tile<T, F, TA>(reinterpret_cast<T*>(smem), f.lo, f.hi, in + (size_t)blockIdx.z * in_band, ldin, nxin, nyin,
-                       coeffs + (size_t)blockIdx.z * c_band, ldc, Cx, Cy,
-                       approx ? approx + (size_t)blockIdx.z * a_band : nullptr, blockIdx.x * TA, blockIdx.y * TA);
-}
 
 // Register-blocked tile for 16-byte aligned input rows (the finest level of an image whose width is a multiple of
 // the vector width -- the level that carries 3/4 of the work).  The plain tile below spends one LDS read and a few
@@ -402,7 +381,7 @@ template <typename T> struct SynPrm {           // synthesis, one per (level >= 
     T lo[MAXF], hi[MAXF];                       // rec_lo, rec_hi
 };
 
-// body of k_dwt_level for the tile (ox0, oy0); src / dst / approx already point at the band
+// one basis' tile (ox0, oy0) of k_dwt_batched; src / dst / approx already point at the band
 template <typename T, int F, int TA>
 __device__ __forceinline__ void dwt_tile(T* smem, const T* __restrict__ flo, const T* __restrict__ fhi,
                                          const T* __restrict__ src, int ldin, int nxin, int nyin,
@@ -603,268 +582,6 @@ k_dwt_l1_fused(const T* __restrict__ x, size_t xband, int ldin, int nxin, int ny
             default: break;
         }
     }
-}
-
-// ----------------------------------------------------------------- synthesis level
-// ---- staging of a synthesis tile's coefficients: C[ry][cx], ry, cx < 2NC (lo | hi halves in both)
-// When a C row is at least a wavefront wide (fp32 tiles: 2NC >= 64) a WAVE takes a row: the row index is
-// wave-uniform (scalar address / bounds arithmetic), the lane is the column, and only the 2NC - 64 columns
-// beyond the wavefront go through the flat per-element mapping.  The flat mapping cost ~22 VALU
-// instructions per element (division by 2NC, quadrant selects, 64-bit address) -- more than the synthesis
-// arithmetic itself (rocprofv3: 81.8 M VALU wave-instructions per finest-level launch against ~16 M of FMAs).
-template <int NC> struct StageCfg {
-    static constexpr bool ROWS = 2 * NC >= 64;
-    static constexpr int NR = ROWS ? (2 * NC + 3) / 4 : 0;           // rows per wave (4 waves)
-    static constexpr int NREM = ROWS ? 2 * NC - 64 : 0;              // columns beyond the 64 lanes
-    static constexpr int NLR = (NREM * 2 * NC + 255) / 256;
-    static constexpr int NLD = ROWS ? NR + NLR : (4 * NC * NC + 255) / 256;
-};
-template <typename T, int NC>
-__device__ __forceinline__ void coef_load(T (&stage)[StageCfg<NC>::NLD], const T* __restrict__ src, int ldc,
-                                          int nax, int nay, int mx0, int my0, bool skip_ll, int tid) {
-    using S = StageCfg<NC>;
-    if constexpr (S::ROWS) {
-        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-        const bool hx = lane >= NC;
-        const int gx = mx0 + (hx ? lane - NC : lane);
-        const int coloff = (hx ? nax : 0) + gx;
-        const bool okx = gx < nax;
-#pragma unroll
-        for (int k = 0; k < S::NR; ++k) {
-            const int ry = wv + 4 * k;                               // wave-uniform
-            const bool hy = ry >= NC;
-            const int gy = my0 + (hy ? ry - NC : ry);
-            T v = 0;
-            if (ry < 2 * NC && gy < nay && okx && !(skip_ll && !hy && !hx))
-                v = src[(size_t)((hy ? nay : 0) + gy) * ldc + coloff];
-            stage[k] = v;
-        }
-        if constexpr (S::NREM > 0) {
-#pragma unroll
-            for (int k = 0; k < S::NLR; ++k) {
-                const int e = tid + 256 * k;
-                const int ry = e / S::NREM, cx = 64 + (e - ry * S::NREM);   // cx >= 64 > NC: the hi-x half
-                const bool hy = ry >= NC;
-                const int gy = my0 + (hy ? ry - NC : ry), gx2 = mx0 + cx - NC;
-                T v = 0;
-                if (e < S::NREM * 2 * NC && gy < nay && gx2 < nax)
-                    v = src[(size_t)((hy ? nay : 0) + gy) * ldc + nax + gx2];
-                stage[S::NR + k] = v;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < S::NLD; ++k) {
-            const int e = tid + 256 * k;
-            const int ry = e / (2 * NC), cx = e - ry * (2 * NC);
-            const bool hy = ry >= NC, hx = cx >= NC;
-            const int gy = my0 + (hy ? ry - NC : ry), gx = mx0 + (hx ? cx - NC : cx);
-            T v = 0;
-            if (e < 4 * NC * NC && gy < nay && gx < nax && !(skip_ll && !hy && !hx))
-                v = src[(size_t)((hy ? nay : 0) + gy) * ldc + (hx ? nax : 0) + gx];
-            stage[k] = v;
-        }
-    }
-}
-template <typename T, int NC, int SC>
-__device__ __forceinline__ void coef_store(T* C, const T (&stage)[StageCfg<NC>::NLD], bool skip_ll, int tid) {
-    using S = StageCfg<NC>;
-    if constexpr (S::ROWS) {
-        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-#pragma unroll
-        for (int k = 0; k < S::NR; ++k) {
-            const int ry = wv + 4 * k;
-            if (ry < 2 * NC && !(skip_ll && ry < NC && lane < NC)) C[ry * SC + lane] = stage[k];
-        }
-        if constexpr (S::NREM > 0) {
-#pragma unroll
-            for (int k = 0; k < S::NLR; ++k) {
-                const int e = tid + 256 * k;
-                const int ry = e / S::NREM, cx = 64 + (e - ry * S::NREM);
-                if (e < S::NREM * 2 * NC) C[ry * SC + cx] = stage[S::NR + k];
-            }
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < S::NLD; ++k) {
-            const int e = tid + 256 * k;
-            const int ry = e / (2 * NC), cx = e - ry * (2 * NC);
-            if (e < 4 * NC * NC && !(skip_ll && ry < NC && cx < NC)) C[ry * SC + cx] = stage[k];
-        }
-    }
-}
-
-// coeffs : this level's (2 nay, 2 nax) block, ld = ldc (y-major)
-// prev   : if non-null, the approx quadrant is prev[c][r] (previous level's image,
-//          row-major ld = ldp) instead of coeffs[r][c]      (wavelets.py:303-309)
-// out    : image (nxw, nyw) row-major ld = ldo; ACC adds (sum over bases, psi.py:252)
-template <typename T, int F, int TS, bool ACC>
-__global__ void __launch_bounds__(256)
-k_idwt_level(const T* __restrict__ coeffs, size_t c_band, int ldc, int nax, int nay,
-             const T* __restrict__ prev, size_t p_band, int ldp,
-             T* __restrict__ out, size_t o_band, int ldo, int nxw, int nyw, Filt<T> f) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int h = F / 2;
-    constexpr int NC = TS / 2 + h - 1;        // coefficients needed per half and tile edge
-    constexpr int SC = 2 * NC + 1;
-    constexpr int ST = TS + 1;
-    T* C = reinterpret_cast<T*>(smem);        // [2NC][SC]  C[ry][cx]  (lo|hi in both)
-    T* Tm = C + 2 * NC * SC;                  // [2NC][ST]  after the x pass  Tm[ry][ox]
-    const T* src = coeffs + (size_t)blockIdx.z * c_band;
-    const T* pv = prev ? prev + (size_t)blockIdx.z * p_band : nullptr;
-    T* dst = out + (size_t)blockIdx.z * o_band;
-    const int ix0 = blockIdx.x * TS, iy0 = blockIdx.y * TS;
-    const int mx0 = ix0 / 2, my0 = iy0 / 2;
-    T lo[F], hi[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) { lo[j] = f.lo[j]; hi[j] = f.hi[j]; }
-    // 1. stage coefficients (all loads first); rows/cols beyond (nay, nax) are only used by
-    //    cropped outputs.  coeffs are read row-wise (cx fastest), prev column-wise (ry fastest).
-    T stage[StageCfg<NC>::NLD];
-    coef_load<T, NC>(stage, src, ldc, nax, nay, mx0, my0, pv != nullptr, (int)threadIdx.x);
-    constexpr int NLP = (NC * NC + 255) / 256;
-    T stagep[NLP];
-    if (pv) {
-#pragma unroll
-        for (int k = 0; k < NLP; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int cx = e / NC, ry = e - cx * NC;              // ry fastest: prev is read along y
-            const int gy = my0 + ry, gx = mx0 + cx;
-            T v = 0;
-            if (e < NC * NC && gy < nay && gx < nax) v = pv[(size_t)gx * ldp + gy];
-            stagep[k] = v;
-        }
-    }
-    coef_store<T, NC, SC>(C, stage, pv != nullptr, (int)threadIdx.x);
-    if (pv) {
-#pragma unroll
-        for (int k = 0; k < NLP; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int cx = e / NC, ry = e - cx * NC;
-            if (e < NC * NC) C[ry * SC + cx] = stagep[k];
-        }
-    }
-    __syncthreads();
-    // 2. x pass: Tm[ry][ox] = sum_j lo[2j+p] C[ry][m+h-1-j] + sum_j hi[2j+p] C[ry][NC+m+h-1-j]
-    //    (one thread makes the even/odd output pair from the same h taps)
-    for (int e = threadIdx.x; e < 2 * NC * (TS / 2); e += 256) {
-        const int ry = e / (TS / 2), m = e - ry * (TS / 2);
-        const T* c = C + ry * SC + m + h - 1;
-        T sl0 = 0, sh0 = 0, sl1 = 0, sh1 = 0;
-#pragma unroll
-        for (int j = 0; j < h; ++j) {
-            const T a = c[-j], d = c[NC - j];
-            sl0 += lo[2 * j] * a;     sh0 += hi[2 * j] * d;
-            sl1 += lo[2 * j + 1] * a; sh1 += hi[2 * j + 1] * d;
-        }
-        Tm[ry * ST + 2 * m] = sl0 + sh0;
-        Tm[ry * ST + 2 * m + 1] = sl1 + sh1;
-    }
-    __syncthreads();
-    // 3. y pass + store (iy fastest); a thread makes the pair (2m, 2m+1) of one image row
-    for (int e = threadIdx.x; e < TS * (TS / 2); e += 256) {
-        const int ox = e / (TS / 2), m = e - ox * (TS / 2);
-        const T* t = Tm + (m + h - 1) * ST + ox;
-        T sl0 = 0, sh0 = 0, sl1 = 0, sh1 = 0;
-#pragma unroll
-        for (int j = 0; j < h; ++j) {
-            const T a = t[-j * ST], d = t[(NC - j) * ST];
-            sl0 += lo[2 * j] * a;     sh0 += hi[2 * j] * d;
-            sl1 += lo[2 * j + 1] * a; sh1 += hi[2 * j + 1] * d;
-        }
-        const int gx = ix0 + ox, gy = iy0 + 2 * m;
-        if (gx < nxw) {
-            T* q = dst + (size_t)gx * ldo + gy;
-            if (gy < nyw)     { if (ACC) q[0] += sl0 + sh0; else q[0] = sl0 + sh0; }
-            if (gy + 1 < nyw) { if (ACC) q[1] += sl1 + sh1; else q[1] = sl1 + sh1; }
-        }
-    }
-}
-
-// body of k_idwt_level (store, no accumulate) for the output tile (ix0, iy0)
-template <typename T, int F, int TS>
-__device__ __forceinline__ void idwt_tile_store(T* smem, const T* __restrict__ flo, const T* __restrict__ fhi,
-                                                const T* __restrict__ src, int ldc, int nax, int nay,
-                                                const T* __restrict__ pv, int ldp, T* __restrict__ dst, int ldo,
-                                                int nxw, int nyw, int ix0, int iy0) {
-
-    constexpr int h = F / 2;
-    constexpr int NC = TS / 2 + h - 1;        // coefficients needed per half and tile edge
-    constexpr int SC = 2 * NC + 1;
-    constexpr int ST = TS + 1;
-    T* C = smem;                              // [2NC][SC]  C[ry][cx]  (lo|hi in both)
-    T* Tm = C + 2 * NC * SC;                  // [2NC][ST]  after the x pass  Tm[ry][ox]
-    const int mx0 = ix0 / 2, my0 = iy0 / 2;
-    T lo[F], hi[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) { lo[j] = flo[j]; hi[j] = fhi[j]; }
-    // 1. stage coefficients (all loads first); rows/cols beyond (nay, nax) are only used by
-    //    cropped outputs.  coeffs are read row-wise (cx fastest), prev column-wise (ry fastest).
-    T stage[StageCfg<NC>::NLD];
-    coef_load<T, NC>(stage, src, ldc, nax, nay, mx0, my0, pv != nullptr, (int)threadIdx.x);
-    constexpr int NLP = (NC * NC + 255) / 256;
-    T stagep[NLP];
-    if (pv) {
-#pragma unroll
-        for (int k = 0; k < NLP; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int cx = e / NC, ry = e - cx * NC;              // ry fastest: prev is read along y
-            const int gy = my0 + ry, gx = mx0 + cx;
-            T v = 0;
-            if (e < NC * NC && gy < nay && gx < nax) v = pv[(size_t)gx * ldp + gy];
-            stagep[k] = v;
-        }
-    }
-    coef_store<T, NC, SC>(C, stage, pv != nullptr, (int)threadIdx.x);
-    if (pv) {
-#pragma unroll
-        for (int k = 0; k < NLP; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int cx = e / NC, ry = e - cx * NC;
-            if (e < NC * NC) C[ry * SC + cx] = stagep[k];
-        }
-    }
-    __syncthreads();
-    // 2. x pass: Tm[ry][ox] = sum_j lo[2j+p] C[ry][m+h-1-j] + sum_j hi[2j+p] C[ry][NC+m+h-1-j]
-    //    (one thread makes the even/odd output pair from the same h taps)
-    for (int e = threadIdx.x; e < 2 * NC * (TS / 2); e += 256) {
-        const int ry = e / (TS / 2), m = e - ry * (TS / 2);
-        const T* c = C + ry * SC + m + h - 1;
-        T sl0 = 0, sh0 = 0, sl1 = 0, sh1 = 0;
-#pragma unroll
-        for (int j = 0; j < h; ++j) {
-            const T a = c[-j], d = c[NC - j];
-            sl0 += lo[2 * j] * a;     sh0 += hi[2 * j] * d;
-            sl1 += lo[2 * j + 1] * a; sh1 += hi[2 * j + 1] * d;
-        }
-        Tm[ry * ST + 2 * m] = sl0 + sh0;
-        Tm[ry * ST + 2 * m + 1] = sl1 + sh1;
-    }
-    __syncthreads();
-    // 3. y pass + store (iy fastest); a thread makes the pair (2m, 2m+1) of one image row
-    for (int e = threadIdx.x; e < TS * (TS / 2); e += 256) {
-        const int ox = e / (TS / 2), m = e - ox * (TS / 2);
-        const T* t = Tm + (m + h - 1) * ST + ox;
-        T sl0 = 0, sh0 = 0, sl1 = 0, sh1 = 0;
-#pragma unroll
-        for (int j = 0; j < h; ++j) {
-            const T a = t[-j * ST], d = t[(NC - j) * ST];
-            sl0 += lo[2 * j] * a;     sh0 += hi[2 * j] * d;
-            sl1 += lo[2 * j + 1] * a; sh1 += hi[2 * j + 1] * d;
-        }
-        const int gx = ix0 + ox, gy = iy0 + 2 * m;
-        if (gx < nxw) {
-            T* q = dst + (size_t)gx * ldo + gy;
-            if (gy < nyw)     { q[0] = sl0 + sh0; }
-            if (gy + 1 < nyw) { q[1] = sl1 + sh1; }
-        }
-    }
-}
-
-
-template <typename T>
-__global__ void __launch_bounds__(256) k_fill(T* p, size_t n, T v) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
 // --------------------------------------------------------------------- prox / PD
@@ -1120,7 +837,7 @@ template <typename T> struct FinBasis {
 };
 
 // ------------------------------------------------ lean fused finest level
-// rocprofv3 + the ISA of the first-generation kernel (staging and passes as in k_idwt_level; removed, the code is at
+// rocprofv3 + the ISA of the first-generation kernel (flat per-element staging, one LDS read per tap; removed, the code is at
 // commit e9a762c): ~4500 instructions per thread and tile, of which the arithmetic is a
 // fifth -- the staging spends ~45 SCALAR instructions per wave-row on quadrant selects, 64-bit row addresses and
 // exec-mask juggling (the CU has ONE scalar unit: 117 of the kernel's 185 us), the passes one LDS read and a few index
@@ -1362,74 +1079,12 @@ k_idwt_batched2(const T* __restrict__ alpha, size_t aband, int ldc, const T* __r
 }
 
 template <typename T>
-static Filt<T> make_filt(const BasisInfo& b, int lo_idx, int hi_idx) {
-    Filt<T> f;
-    memset(&f, 0, sizeof(f));
-    f.F = b.F;
-    for (int k = 0; k < b.F; ++k) { f.lo[k] = (T)b.filt[lo_idx][k]; f.hi[k] = (T)b.filt[hi_idx][k]; }
-    return f;
-}
-
-template <typename T>
 static size_t dwt_lds(int F) {
     constexpr int TA = Tile<T>::TA;
     const int NI = 2 * TA + F - 2;
-    const size_t plain = (size_t)NI * (NI + 1) + (size_t)NI * (2 * TA + 1);       // LL aliases A
-    const size_t fast = DwtFast<T>::elems(TA, F);                                // dwt_tile_fast (aligned input rows)
+    const size_t plain = (size_t)NI * (NI + 1) + (size_t)NI * (2 * TA + 1);       // dwt_tile's non-register-blocked tile (LL aliases A)
+    const size_t fast = DwtFast<T>::elems(TA, F);                                // dwt_tile_fast
     return sizeof(T) * (plain > fast ? plain : fast);
-}
-template <typename T>
-static size_t idwt_lds(int F) {
-    constexpr int TS = Tile<T>::TS;
-    const int NC = TS / 2 + F / 2 - 1;
-    return sizeof(T) * ((size_t)2 * NC * (2 * NC + 1) + (size_t)2 * NC * (TS + 1));
-}
-
-#define PFB_FOR_F(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18)
-
-template <typename T>
-static void launch_dwt(int F, dim3 grid, size_t lds, hipStream_t st, const T* in, size_t in_band, int ldin,
-                       int nxin, int nyin, T* blk, size_t c_band, int ldc, int Cx, int Cy, T* approx,
-                       size_t a_band, const Filt<T>& f) {
-    switch (F) {
-#define X(FF) case FF: hipLaunchKernelGGL((k_dwt_level<T, FF, Tile<T>::TA>), grid, dim3(256), lds, st, in, in_band, \
-                                          ldin, nxin, nyin, blk, c_band, ldc, Cx, Cy, approx, a_band, f); break;
-        PFB_FOR_F(X)
-#undef X
-        default: break;
-    }
-}
-template <typename T, bool ACC>
-static void launch_idwt(int F, dim3 grid, size_t lds, hipStream_t st, const T* blk, size_t c_band, int ldc,
-                        int nax, int nay, const T* prev, size_t p_band, int ldp, T* out, size_t o_band, int ldo,
-                        int nxw, int nyw, const Filt<T>& f) {
-    switch (F) {
-#define X(FF) case FF: hipLaunchKernelGGL((k_idwt_level<T, FF, Tile<T>::TS, ACC>), grid, dim3(256), lds, st, blk, \
-                                          c_band, ldc, nax, nay, prev, p_band, ldp, out, o_band, ldo, nxw, nyw, f); break;
-        PFB_FOR_F(X)
-#undef X
-        default: break;
-    }
-}
-template <typename T>
-static int set_wavelet_lds_limits() {
-    const int lds_max = 160 * 1024;
-#define X(FF) \
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_dwt_level<T, FF, Tile<T>::TA>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)); \
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_idwt_level<T, FF, Tile<T>::TS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)); \
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_idwt_level<T, FF, Tile<T>::TS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_FOR_F(X)
-#undef X
-    return PFB_OK;
-}
-
-template <typename T> static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t st);
-
-// the batched / fused drivers unless PFB_PSI_FUSED=0 asks for the per-basis path; read on EVERY call (the tests
-// switch it within one process)
-static bool psi_fused(const pfb_psi_plan* p) {
-    const char* e = getenv("PFB_PSI_FUSED");
-    return !(e && !atoi(e)) && p->nbasis > 0;
 }
 
 // the batched kernels exist for FMAX = 8 and 18 (longest filter they hold): launch the one the plan `p` needs, block
@@ -1440,47 +1095,20 @@ static bool psi_fused(const pfb_psi_plan* p) {
         else hipLaunchKernelGGL((KERN<T, TILE, 18>), grid, dim3(256), lds, st, __VA_ARGS__);                 \
     } while (0)
 
-template <typename T>
-static int psi_dot_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t st) {
-    if (psi_fused(p)) return psi_dot_batched_t<T>(p, x, alpha, st);
-    const size_t plane = (size_t)p->Nymax * p->Nxmax;
-    const size_t aband = plane * p->nbasis;
-    const size_t xband = (size_t)p->nx * p->ny;
-    for (int ib = 0; ib < p->nbasis; ++ib) {
-        const BasisInfo& b = p->bases[ib];
-        T* ab = alpha + (size_t)ib * plane;
-        if (b.K == 0) {        // 'self': alpha[b, ib, 0:ny, 0:nx] = x[b].T     (psi.py:196-199)
-            dim3 grid((p->ny + 31) / 32, (p->nx + 31) / 32, p->nband);
-            hipLaunchKernelGGL((k_transpose<T, false>), grid, dim3(256), 0, st, x, xband, p->ny, ab, aband,
-                               p->Nxmax, p->nx, p->ny);
-            continue;
-        }
-        const Filt<T> f = make_filt<T>(b, 0, 1);
-        const T* in = x;
-        size_t in_band = xband;
-        int ldin = p->ny;
-        for (int l = 0; l < p->nlevel; ++l) {
-            const LevelInfo& L = b.lev[l];
-            T* blk = ab + (size_t)L.lowy * p->Nxmax + L.lowx;
-            const bool last = l == p->nlevel - 1;
-            T* approx = last ? nullptr : (T*)p->scratch[l & 1];
-            constexpr int TA = Tile<T>::TA;
-            dim3 grid((L.Cx + TA - 1) / TA, (L.Cy + TA - 1) / TA, p->nband);
-            launch_dwt<T>(b.F, grid, dwt_lds<T>(b.F), st, in, in_band, ldin, L.nxin, L.nyin, blk, aband,
-                          p->Nxmax, L.Cx, L.Cy, approx, p->scratch_band, f);
-            in = approx;
-            in_band = p->scratch_band;
-            ldin = L.Cy;
-        }
-    }
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
+#define PFB_PLAN_MALLOC(ptr, bytes)                                                               \
+    do {                                                                                          \
+        if (hipMalloc(ptr, bytes) != hipSuccess) {                                                \
+            (void)hipGetLastError();                                                              \
+            set_error("psi_plan_create: device allocation failed (%zu B)", (size_t)(bytes));      \
+            return PFB_ERR_ALLOC;                                                                 \
+        }                                                                                         \
+    } while (0)
 
+// everything a plan holds on the device, built once by pfb_psi_plan_create (dot / hdot only read the plan): the
+// parameter tables, the scratch images and the kernels' LDS limits
 template <typename T>
-static int psi_fin_prepare(pfb_psi_plan* p) {
-    // parameter table + per-basis level-1 partial images of the fused finest level (once per plan)
-    if (p->fin_prm) return PFB_OK;
+static int psi_plan_device_setup(pfb_psi_plan* p) {
+    // parameter table + per-basis level-1 partial images of the fused finest level
     const size_t plane = (size_t)p->Nymax * p->Nxmax;
     std::vector<FinBasis<T>> h(p->nbasis);
     size_t fin_band = 1;
@@ -1511,9 +1139,9 @@ static int psi_fin_prepare(pfb_psi_plan* p) {
         q.prev_off = (long long)((size_t)ib * p->fin_basis);
         for (int k = 0; k < b.F; ++k) { q.lo[k] = (T)b.filt[2][k]; q.hi[k] = (T)b.filt[3][k]; }
     }
-    PFB_HIP_CHECK(hipMalloc(&p->fin_prm, sizeof(FinBasis<T>) * h.size()));
+    PFB_PLAN_MALLOC(&p->fin_prm, sizeof(FinBasis<T>) * h.size());
     PFB_HIP_CHECK(hipMemcpy(p->fin_prm, h.data(), sizeof(FinBasis<T>) * h.size(), hipMemcpyHostToDevice));
-    PFB_HIP_CHECK(hipMalloc(&p->fin_scratch, sizeof(T) * p->fin_basis * p->nbasis));
+    PFB_PLAN_MALLOC(&p->fin_scratch, sizeof(T) * p->fin_basis * p->nbasis);
     constexpr int TS = Tile<T>::TS;
     constexpr int TA = Tile<T>::TA;
 #define PFB_FMAX_LDS(KERN, TILE)                                                                                         \
@@ -1529,7 +1157,7 @@ static int psi_fin_prepare(pfb_psi_plan* p) {
     if (p->nwb == 0) return PFB_OK;
     p->bscr_basis = p->scratch_band * p->nband;
     for (int k = 0; k < 2; ++k)
-        PFB_HIP_CHECK(hipMalloc(&p->bscr[k], sizeof(T) * p->bscr_basis * p->nwb));
+        PFB_PLAN_MALLOC(&p->bscr[k], sizeof(T) * p->bscr_basis * p->nwb);
     std::vector<AnaPrm<T>> ha((size_t)p->nlevel * p->nwb);
     std::vector<SynPrm<T>> hs((size_t)p->nlevel * p->nwb);
     for (int l = 0; l < p->nlevel; ++l) {
@@ -1568,18 +1196,17 @@ static int psi_fin_prepare(pfb_psi_plan* p) {
             if (gd > p->gy_syn[l]) p->gy_syn[l] = gd;
         }
     }
-    PFB_HIP_CHECK(hipMalloc(&p->ana_prm, sizeof(AnaPrm<T>) * ha.size()));
+    PFB_PLAN_MALLOC(&p->ana_prm, sizeof(AnaPrm<T>) * ha.size());
     PFB_HIP_CHECK(hipMemcpy(p->ana_prm, ha.data(), sizeof(AnaPrm<T>) * ha.size(), hipMemcpyHostToDevice));
-    PFB_HIP_CHECK(hipMalloc(&p->syn_prm, sizeof(SynPrm<T>) * hs.size()));
+    PFB_PLAN_MALLOC(&p->syn_prm, sizeof(SynPrm<T>) * hs.size());
     PFB_HIP_CHECK(hipMemcpy(p->syn_prm, hs.data(), sizeof(SynPrm<T>) * hs.size(), hipMemcpyHostToDevice));
     return PFB_OK;
 }
+#undef PFB_PLAN_MALLOC
 
 // psi.dot with ONE launch per level for all wavelet bases (+ the 'self' transposes)
 template <typename T>
-static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t st) {
-    int rc = psi_fin_prepare<T>(p);
-    if (rc != PFB_OK) return rc;
+static int psi_dot_t(const pfb_psi_plan* p, const T* x, T* alpha, hipStream_t st) {
     const size_t plane = (size_t)p->Nymax * p->Nxmax;
     const size_t aband = plane * p->nbasis;
     const size_t xband = (size_t)p->nx * p->ny;
@@ -1593,7 +1220,7 @@ static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t 
         if (p->bases[ib].K != 0) continue;
         if (l1_fused && self_off < 0) { self_off = (long long)((size_t)ib * plane); continue; }
         dim3 grid((p->ny + 31) / 32, (p->nx + 31) / 32, p->nband);
-        hipLaunchKernelGGL((k_transpose<T, false>), grid, dim3(256), 0, st, x, xband, p->ny,
+        hipLaunchKernelGGL((k_transpose<T>), grid, dim3(256), 0, st, x, xband, p->ny,
                            alpha + (size_t)ib * plane, aband, p->Nxmax, p->nx, p->ny);
     }
     if (p->nwb > 0) {
@@ -1618,11 +1245,10 @@ static int psi_dot_batched_t(pfb_psi_plan* p, const T* x, T* alpha, hipStream_t 
     return PFB_OK;
 }
 
-// all bases' finest level in one kernel (image written once); coarser levels basis by basis
+// psi.hdot: the coarse levels with one launch per level for all wavelet bases, then all bases' finest level (and
+// 'self') in one kernel that writes the image once
 template <typename T>
-static int psi_hdot_fused_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t st) {
-    int rc = psi_fin_prepare<T>(p);
-    if (rc != PFB_OK) return rc;
+static int psi_hdot_t(const pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t st) {
     const size_t plane = (size_t)p->Nymax * p->Nxmax;
     const size_t aband = plane * p->nbasis;
     const size_t xband = (size_t)p->nx * p->ny;
@@ -1647,61 +1273,6 @@ static int psi_hdot_fused_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t 
     return PFB_OK;
 }
 #undef PFB_FMAX_LAUNCH
-
-template <typename T>
-static int psi_hdot_t(pfb_psi_plan* p, const T* alpha, T* xo, hipStream_t st) {
-    if (psi_fused(p)) return psi_hdot_fused_t<T>(p, alpha, xo, st);
-    const size_t plane = (size_t)p->Nymax * p->Nxmax;
-    const size_t aband = plane * p->nbasis;
-    const size_t xband = (size_t)p->nx * p->ny;
-    bool first = true;          // first basis stores, the others accumulate (xo zeroed implicitly)
-    for (int ib = 0; ib < p->nbasis; ++ib) {
-        const BasisInfo& b = p->bases[ib];
-        const T* ab = alpha + (size_t)ib * plane;
-        if (b.K == 0) {        // xo[b] (+)= alpha[b, ib, 0:ny, 0:nx].T          (psi.py:229-232)
-            dim3 grid((p->nx + 31) / 32, (p->ny + 31) / 32, p->nband);
-            if (first)
-                hipLaunchKernelGGL((k_transpose<T, false>), grid, dim3(256), 0, st, ab, aband, p->Nxmax, xo,
-                                   xband, p->ny, p->ny, p->nx);
-            else
-                hipLaunchKernelGGL((k_transpose<T, true>), grid, dim3(256), 0, st, ab, aband, p->Nxmax, xo,
-                                   xband, p->ny, p->ny, p->nx);
-            first = false;
-            continue;
-        }
-        const Filt<T> f = make_filt<T>(b, 2, 3);
-        const T* prev = nullptr;
-        int ldp = 0;
-        for (int l = p->nlevel - 1; l >= 0; --l) {
-            const LevelInfo& L = b.lev[l];
-            const T* blk = ab + (size_t)L.lowy * p->Nxmax + L.lowx;
-            const bool finest = l == 0;
-            T* out = finest ? xo : (T*)p->scratch[l & 1];
-            const size_t o_band = finest ? xband : p->scratch_band;
-            const int nxw = finest ? (L.nxo < p->nx ? L.nxo : p->nx) : L.nxo;
-            const int nyw = finest ? (L.nyo < p->ny ? L.nyo : p->ny) : L.nyo;
-            const int ldo = finest ? p->ny : L.nyo;
-            constexpr int TS = Tile<T>::TS;
-            dim3 grid((nxw + TS - 1) / TS, (nyw + TS - 1) / TS, p->nband);
-            if (finest && !first)
-                launch_idwt<T, true>(b.F, grid, idwt_lds<T>(b.F), st, blk, aband, p->Nxmax, L.Cx, L.Cy, prev,
-                                     p->scratch_band, ldp, out, o_band, ldo, nxw, nyw, f);
-            else
-                launch_idwt<T, false>(b.F, grid, idwt_lds<T>(b.F), st, blk, aband, p->Nxmax, L.Cx, L.Cy, prev,
-                                      p->scratch_band, ldp, out, o_band, ldo, nxw, nyw, f);
-            prev = out;
-            ldp = ldo;
-        }
-        // signal_size(Cx) can fall short of nx only if nx were odd and ... it cannot: the
-        // finest level always covers [0, nx) x [0, ny) (2 Cx - F + 2 >= nx)
-        first = false;
-    }
-    if (first) {               // no bases at all: xo = 0
-        hipLaunchKernelGGL((k_fill<T>), dim3(1024), dim3(256), 0, st, xo, xband * p->nband, (T)0);
-    }
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
 
 // grid for the streaming elementwise kernels that WRITE as much as they read: a few workgroups per
 // CU (tools/micro/hbm_stream.hip: the write-heavy mixes lose 10-25 % when the chip is oversubscribed)
@@ -1840,7 +1411,7 @@ int pfb_psi_plan_create(int nband, int nx, int ny, int nbasis, const int* basis_
             L.nxo = signal_size(L.Cx, b.F);
             L.nyo = signal_size(L.Cy, b.F);
             ainx = L.Cx; ainy = L.Cy;             // the approx passed on is (Cx, Cy), wavelets.py:171
-            // scratch holds the approx handed to the next analysis level (Cx*Cy, not for the
+            // a basis' slice of bscr holds the approx handed to the next analysis level (Cx*Cy, not for the
             // last level) and the partial images of the synthesis (nxo*nyo, not for level 0)
             if (l < nlevel - 1 && (size_t)L.Cx * L.Cy > scratch_elems) scratch_elems = (size_t)L.Cx * L.Cy;
             if (l > 0 && (size_t)L.nxo * L.nyo > scratch_elems) scratch_elems = (size_t)L.nxo * L.nyo;
@@ -1865,16 +1436,8 @@ int pfb_psi_plan_create(int nband, int nx, int ny, int nbasis, const int* basis_
     if (p->Nxmax < nx) p->Nxmax = nx;
     if (p->Nymax < ny) p->Nymax = ny;
     p->scratch_band = scratch_elems;
-    const size_t esz = dtype == PFB_F32 ? 4 : 8;
-    for (int k = 0; k < 2; ++k) {
-        if (hipMalloc(&p->scratch[k], esz * scratch_elems * nband) != hipSuccess) {
-            pfb_psi_plan_destroy(p);
-            set_error("psi_plan_create: device allocation failed");
-            return PFB_ERR_ALLOC;
-        }
-    }
     {
-        int rc = dtype == PFB_F32 ? set_wavelet_lds_limits<float>() : set_wavelet_lds_limits<double>();
+        const int rc = dtype == PFB_F32 ? psi_plan_device_setup<float>(p) : psi_plan_device_setup<double>(p);
         if (rc != PFB_OK) { pfb_psi_plan_destroy(p); return rc; }
     }
     *plan = p;
@@ -1883,7 +1446,6 @@ int pfb_psi_plan_create(int nband, int nx, int ny, int nbasis, const int* basis_
 
 int pfb_psi_plan_destroy(pfb_psi_plan* p) {
     if (!p) return PFB_OK;
-    for (int k = 0; k < 2; ++k) if (p->scratch[k]) (void)hipFree(p->scratch[k]);
     if (p->fin_prm) (void)hipFree(p->fin_prm);
     if (p->fin_scratch) (void)hipFree(p->fin_scratch);
     if (p->ana_prm) (void)hipFree(p->ana_prm);

@@ -10,8 +10,9 @@ Same attributes (nband, nx, ny, nbasis, nthreads, Nxmax, Nymax), same in-place c
 transposed coefficient layout with never-written margin cells, same un-normalised
 convention hdot(dot(x)) = nbasis * x.  bases: 'self' | 'db1'..'db9'.
 
-The reference's per-band ThreadPool + numba prange row loops become one fused HIP kernel
-per (basis, level) covering all bands (pfb_psi_dot / pfb_psi_hdot, csrc/wavelet.hip).
+The reference's per-band ThreadPool + numba prange row loops become one HIP launch per
+level covering all bases and all bands, with the finest level of all bases (and 'self')
+fused into one kernel in each direction (pfb_psi_dot / pfb_psi_hdot, csrc/wavelet.hip).
 The reference's psi buffers are float64 only (psi.py:130-133); here the dtype follows
 the arrays (float64 or float32).
 """

@@ -460,31 +460,91 @@ def test_primal_dual_nonzero_margins_keep_reference_semantics(amd, golden):
     assert maxerr(v, vo) < 1e-9 * np.abs(vo).max()
 
 
-@pytest.mark.parametrize('rdt', [np.float64, np.float32])
-def test_psi_batched_and_fused_kernels_match_per_basis_kernels(amd, rdt, monkeypatch):
-    """Default: one launch per level for all wavelet bases (k_dwt_batched / k_idwt_batched) and one
-    fused finest synthesis level (k_idwt_finest_fused).  PFB_PSI_FUSED=0 runs the per-basis kernels
-    instead; both must give the same coefficients / image (incl. db5+, the FMAX = 18 variants)."""
-    rng = np.random.default_rng(17)
-    nband, nx, ny = 3, 200, 168
-    for bases, nlevel in ((['self', 'db1', 'db2', 'db3', 'db4'], 3), (['db6', 'self', 'db2'], 2), (['db3'], 1)):
-        psi = amd.Psi(nband, nx, ny, bases, nlevel, 1, dtype=torch.float64 if rdt == np.float64 else torch.float32)
-        x = torch.from_numpy(rng.standard_normal((nband, nx, ny)).astype(rdt)).cuda()
-        shape = (nband, len(bases), psi.Nymax, psi.Nxmax)
-        a1 = torch.zeros(shape, dtype=x.dtype, device='cuda')
-        a0 = torch.zeros_like(a1)
-        psi.dot(x, a1)
-        c = torch.from_numpy(rng.standard_normal(shape).astype(rdt)).cuda()
-        y1 = torch.empty_like(x)
-        psi.hdot(c, y1)
-        monkeypatch.setenv('PFB_PSI_FUSED', '0')
-        psi.dot(x, a0)
-        y0 = torch.empty_like(x)
-        psi.hdot(c, y0)
-        monkeypatch.delenv('PFB_PSI_FUSED')
-        assert torch.equal(a0, a1)
-        tol = 1e-14 if rdt == np.float64 else 1e-6
-        assert (y0 - y1).abs().max().item() <= tol * y0.abs().max().item()
+# ---- the batched / fused level kernels against the oracle at every dispatch path of the psi drivers
+PSI_DICTS = ((['self', 'db1', 'db2', 'db3', 'db4'], 3), (['db6', 'self', 'db2'], 2), (['db3'], 1))
+PSI_NBAND, PSI_NX = 3, 200
+_psi_refs = {}
+
+
+def psi_oracle_case(ny, idict, rdt):
+    """Inputs rounded to rdt and the oracle's fp64 results for them, computed once per (ny, dictionary, dtype): x,
+    psi.dot(x) written into an array of NaN (cells that stay NaN are never written), coefficients c, psi.hdot(c)."""
+    key = (ny, idict, np.dtype(rdt).name)
+    if key not in _psi_refs:
+        bases, nlevel = PSI_DICTS[idict]
+        rng = np.random.default_rng(17 + ny + idict)
+        po = owv.Psi(PSI_NBAND, PSI_NX, ny, bases, nlevel, 1)
+        x = rng.standard_normal((PSI_NBAND, PSI_NX, ny)).astype(rdt)
+        a_ref = np.full((PSI_NBAND, po.nbasis, po.Nymax, po.Nxmax), np.nan)
+        po.dot(x.astype(np.float64), a_ref)
+        c = rng.standard_normal(a_ref.shape).astype(rdt)
+        xo_ref = np.zeros((PSI_NBAND, PSI_NX, ny))
+        po.hdot(c.astype(np.float64), xo_ref)
+        for arr in (x, a_ref, c, xo_ref):
+            arr.setflags(write=False)
+        _psi_refs[key] = (x, a_ref, c, xo_ref)
+    return _psi_refs[key]
+
+
+def one_past(t, fill=None):
+    """A contiguous device tensor with t's shape, dtype and values (`fill` instead, when given) that starts one element
+    into a larger buffer, so that its pointer is not 16-byte aligned."""
+    v = torch.empty(t.numel() + 1, dtype=t.dtype, device='cuda')[1:].view(t.shape)
+    assert v.is_contiguous() and v.data_ptr() % 16 != 0
+    if fill is None:
+        v.copy_(t)
+    else:
+        v.fill_(fill)
+    return v
+
+
+def check_psi_against_oracle(amd, ny, idict, rdt, unaligned_pointers):
+    bases, nlevel = PSI_DICTS[idict]
+    x, a_ref, c, xo_ref = psi_oracle_case(ny, idict, rdt)
+    tol = 1e-12 if rdt == np.float64 else 2e-5
+    written = ~np.isnan(a_ref)
+    a_scale, x_scale = np.abs(a_ref[written]).max(), np.abs(xo_ref).max()
+    psi = amd.Psi(PSI_NBAND, PSI_NX, ny, bases, nlevel, 1, dtype=torch.float64 if rdt == np.float64 else torch.float32)
+    assert (psi.Nymax, psi.Nxmax) == a_ref.shape[2:]
+    xd, cd = torch.tensor(x).cuda(), torch.tensor(c).cuda()
+
+    def run(xin, xout):
+        alpha = torch.full(a_ref.shape, 7.25, dtype=xd.dtype, device='cuda')     # sentinel: never-written cells keep it
+        assert psi.dot(xin, alpha) is alpha
+        assert psi.hdot(cd, xout) is xout                                        # xout arrives full of NaN
+        a, xo = alpha.cpu().numpy(), xout.cpu().numpy()
+        assert np.all(a[~written] == 7.25)
+        assert not np.isnan(xo).any()
+        ea, ex = maxerr(a[written], a_ref[written]) / a_scale, maxerr(xo, xo_ref) / x_scale
+        print(f"psi vs oracle ny={ny} dict={idict} {np.dtype(rdt).name} unaligned={xin is not xd}: dot {ea:.2e} hdot {ex:.2e}")
+        assert ea < tol and ex < tol
+        return a, xo
+    a, xo = run(xd, torch.full_like(xd, float('nan')))
+    if unaligned_pointers:
+        a1, xo1 = run(one_past(xd), one_past(xd, fill=float('nan')))
+        assert maxerr(a1[written], a[written]) < tol * a_scale
+        assert maxerr(xo1, xo) < tol * x_scale
+
+
+@pmp('idict', [0, 1, 2])
+@pmp('ny', [168, 166])
+@pmp('rdt', [np.float64, np.float32])
+def test_psi_batched_and_fused_kernels_match_oracle(amd, rdt, ny, idict):
+    """One launch per level for all wavelet bases (k_dwt_batched / k_idwt_batched2), the finest level of all bases fused
+    (k_dwt_l1_fused / k_idwt_finest_fused2), against the CPU oracle that tests/golden/psi.npz pins to the reference:
+    mixed dictionaries with 'self' first, in the middle and absent, FMAX = 8 and 18 (db6), 1 to 3 levels, both dtypes.
+    ny = 168: aligned image rows, level 0 of psi.dot runs in k_dwt_l1_fused.  ny = 166: in fp32 the rows are not 16-byte
+    aligned, so level 0 runs in k_dwt_batched with unaligned staging, every 'self' plane in k_transpose, and psi.hdot
+    stores the image through the scalar branch of tile_store_transposed."""
+    check_psi_against_oracle(amd, ny, idict, rdt, unaligned_pointers=False)
+
+
+@pmp('rdt', [np.float64, np.float32])
+def test_psi_with_unaligned_image_pointers_matches_oracle_and_aligned_call(amd, rdt):
+    """x of psi.dot and xo of psi.hdot as contiguous views that start one element into a larger buffer.  The oracle
+    takes no odd image size, so this is the only way fp64 reaches the unaligned level-0 path of psi.dot and the scalar
+    stores of psi.hdot.  The results equal the oracle's and the aligned call's within the same tolerance."""
+    check_psi_against_oracle(amd, 168, 0, rdt, unaligned_pointers=True)
 
 
 # ---- the reference's own prox tests (tests/test_psi_operator.py:50-148), same statements on the GPU
