@@ -14,6 +14,17 @@ namespace pfb {
 constexpr int CLK_T = 1024;
 constexpr int CLK_MAXBAND = 64;
 
+// The arg-max of all three searches is numpy's: the FIRST index of the maximum, and a NaN is a maximum (np.argmax
+// returns the first NaN).  The peak is then NaN, `NaN > threshold` is false and the loop stops there, as the
+// reference's does.  True when candidate (ov, oi) replaces (best, besti).  A slot that saw no pixel holds (-1, 0)
+// and loses to every pixel, whose value is a square or NaN.
+template <typename T>
+__device__ __forceinline__ bool argmax_takes(T ov, long long oi, T best, long long besti) {
+    const bool on = ov != ov, bn = best != best;
+    if (on || bn) return on && (!bn || oi < besti);
+    return ov > best || (ov == best && oi < besti);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(CLK_T)
 k_clark_subminor(T* __restrict__ A, size_t nact, int nband, const T* __restrict__ psf, int P, int Q,
@@ -29,7 +40,7 @@ k_clark_subminor(T* __restrict__ A, size_t nact, int nband, const T* __restrict_
     bool have_comp = false;             // iteration 0 only searches
     for (;;) {
         // ---- (subtract the component chosen last round and) search: max of (sum_b A[b,i])^2, first index wins
-        T best = T(-1);                  // NaN-safe: comparisons with NaN are false, index 0 stays valid
+        T best = T(-1);                  // below every square; a NaN takes over and stays (argmax_takes)
         long long besti = 0;
         for (size_t i = tid; i < nact; i += CLK_T) {
             T s = 0;
@@ -46,13 +57,13 @@ k_clark_subminor(T* __restrict__ A, size_t nact, int nband, const T* __restrict_
                 for (int b = 0; b < nband; ++b) s += A[(size_t)b * nact + i];
             }
             const T v = s * s;
-            if (v > best) { best = v; besti = (long long)i; }       // ascending i per thread: first max kept
+            if (v > best || (v != v && best == best)) { best = v; besti = (long long)i; }   // ascending i: first max / first NaN kept
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const T ov = __shfl_down(best, off, 64);
             const long long oi = __shfl_down(besti, off, 64);
-            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+            if (argmax_takes(ov, oi, best, besti)) { best = ov; besti = oi; }
         }
         if (lane == 0) { s_val[wave] = best; s_idx[wave] = besti; }
         __syncthreads();
@@ -60,8 +71,8 @@ k_clark_subminor(T* __restrict__ A, size_t nact, int nband, const T* __restrict_
             T bv = s_val[0];
             long long bi = s_idx[0];
             for (int w = 1; w < CLK_T / 64; ++w)
-                if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
-            const T amax = sqrt(bv);         // NaN (all-NaN input or empty maxima) compares false: stop
+                if (argmax_takes(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+            const T amax = sqrt(bv);         // a NaN anywhere in the band sums: amax is NaN, compares false, stop
             int go = (amax > th && k < maxit && bi >= 0 && (size_t)bi < nact) ? 1 : 0;
             int pn = 0, qn = 0;
             if (go) {
@@ -120,20 +131,20 @@ k_hogbom_step(T* __restrict__ IR, const T* __restrict__ psf, int nband, int nx, 
                 s += v;
             }
             const T val = s * s;
-            if (val > best) { best = val; besti = (long long)e; }
+            if (val > best || (val != val && best == best)) { best = val; besti = (long long)e; }
         }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const T ov = __shfl_down(best, off, 64);
         const long long oi = __shfl_down(besti, off, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        if (argmax_takes(ov, oi, best, besti)) { best = ov; besti = oi; }
     }
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = besti; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < besti)) { best = sv[w]; besti = si[w]; }
+            if (argmax_takes(sv[w], si[w], best, besti)) { best = sv[w]; besti = si[w]; }
         pval[blockIdx.x] = best;
         pidx[blockIdx.x] = besti;
     }
@@ -150,18 +161,18 @@ k_hogbom_select(const T* __restrict__ pval, const long long* __restrict__ pidx, 
     T best = T(-1);
     long long besti = 0;
     for (int g = threadIdx.x; g < nparts; g += blockDim.x)
-        if (pval[g] > best || (pval[g] == best && pidx[g] < besti)) { best = pval[g]; besti = pidx[g]; }
+        if (argmax_takes(pval[g], pidx[g], best, besti)) { best = pval[g]; besti = pidx[g]; }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const T ov = __shfl_down(best, off, 64);
         const long long oi = __shfl_down(besti, off, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        if (argmax_takes(ov, oi, best, besti)) { best = ov; besti = oi; }
     }
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = besti; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < besti)) { best = sv[w]; besti = si[w]; }
+            if (argmax_takes(sv[w], si[w], best, besti)) { best = sv[w]; besti = si[w]; }
         HogState st = *stt;
         const double irmax = sqrt((double)best);
         if (first) *tol_io = fmax(pf * irmax, threshold);         // hogbom.py:30
