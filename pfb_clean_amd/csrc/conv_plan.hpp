@@ -10,6 +10,7 @@
 //              place (reads column v of T, writes column v of T).
 //   psf_l      the caller's psfhat (P, M+1) re-laid out once into the same blocking:
 //                psf_l[b][v / VB][u][v % VB]  u in [0, P)
+//              Only the fast path blocks (VB > 1); the coverage paths keep VB = 1, T[b][v][i] and psf_l[b][v][u].
 //   twP, twQ   exp(-2 pi i n / P), exp(-2 pi i n / Q), computed in long double.
 #pragma once
 #include "common.hpp"
@@ -22,7 +23,7 @@ struct pfb_conv_plan {
     int fast;                  // 1: pow2 register-resident kernels are used
     int long_lines;            // 1: a line does not fit the LDS and the fast path cannot hold the grid: every transform
                                //    runs as multi-launch global-memory passes (fft_long.hpp) -- coverage, not speed
-    void* long_ws;             // its workspace (grown on demand, freed with the plan)
+    void* long_ws;             // the scratch of its stages (grown on demand, freed with the plan)
     size_t long_ws_bytes;
     pfb::FftFactors frow;      // length M  (row transform on packed reals)
     pfb::FftFactors fcol;      // length P

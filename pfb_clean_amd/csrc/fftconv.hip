@@ -1,19 +1,23 @@
-// fftconv.hip -- PSF convolution plan + the coverage ("generic") kernels + C-ABI.
+// fftconv.hip -- PSF convolution plan + the coverage ("generic") paths + C-ABI.
 //
 // out = [beam*] crop(irfft2(rfft2(pad([beam*] x)) * psfhat)) [/wsum] + sigmainv * x
 // (pfb/operators/psf.py:11-56, pfb/operators/hessian.py:129-158, 254-281)
 //
-// Three launches per apply, never materialising the zero-padded image:
-//   1. row_fwd : one image row -> packed real FFT of length Q -> M+1 bins into T
-//   2. col     : one frequency column of T -> FFT_P -> * psfhat -> IFFT_P -> first nx
-//                samples back into T (in place)
-//   3. row_inv : M+1 bins of one output row -> c2r of length Q -> crop, scale, beam,
-//                Tikhonov term, fused <dot_with, out> partial sum
-// The generic kernels here run one line per 256-thread workgroup with a runtime
-// mixed-radix Stockham FFT in LDS; fftconv_pow2.hip supplies the fast versions of the
-// same three stages on the same layouts.
+// Three stages per apply, never materialising the zero-padded image:
+//   1. rows_r2c : one image row -> packed real FFT of length Q -> M+1 bins into T
+//   2. columns  : one frequency column of T -> FFT_P -> * psfhat -> IFFT_P -> first nx
+//                 samples back into T (in place)
+//   3. rows_c2r : M+1 bins of one output row -> c2r of length Q -> crop, scale, beam,
+//                 Tikhonov term, fused <dot_with, out> partial sums
+// The same row stages, over other views (fft_generic.hpp), and the plain column transform `cols`
+// also make psfhat = r2c(ifftshift(psf)) and re-grid a psfhat (pfb_psfhat_regrid).  Every stage
+// entry runs either one line per 256-thread workgroup with a runtime mixed-radix Stockham FFT in
+// LDS (the kernels here) or, for lines beyond the LDS, as global-memory passes (fft_long.hpp);
+// the caller says which and brings the scratch.  fftconv_pow2.hip supplies the fast versions of
+// the three stages on the same layouts.
 #include "conv_plan.hpp"
 #include "fft_long.hpp"
+#include <algorithm>
 #include <vector>
 #include <cstring>
 #include <cstdlib>
@@ -41,63 +45,49 @@ int pow2_nvb(const pfb_conv_plan* p);
 int pow2_set_psfhat(pfb_conv_plan* p, const void* psfhat, hipStream_t st);
 int pow2_set_psf(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStream_t st);
 
+// the coverage layouts (VB = 1): T[band][v][i], psf_l[band][v][u]
 struct ConvDims {
-    int nx, ny, P, Q, M, VB, nvb;
+    int nx, ny, P, Q, M;
     size_t T_band, psf_band;
 };
 
 __device__ __forceinline__ size_t t_index(const ConvDims& d, int band, int i, int v) {
-    return (size_t)band * d.T_band + ((size_t)(v / d.VB) * d.nx + i) * d.VB + (v % d.VB);
+    return (size_t)band * d.T_band + (size_t)v * d.nx + i;
 }
 __device__ __forceinline__ size_t psf_index(const ConvDims& d, int band, int u, int v) {
-    return (size_t)band * d.psf_band + ((size_t)(v / d.VB) * d.P + u) * d.VB + (v % d.VB);
+    return (size_t)band * d.psf_band + (size_t)v * d.P + u;
 }
 
 // ---------------------------------------------------------------- psfhat re-layout
 template <typename T>
 __global__ void k_relayout_psfhat(const cplx<T>* __restrict__ psfhat, cplx<T>* __restrict__ psf_l,
                                   ConvDims d) {
-    // grid: (ceil(nvb*VB / 64), P, nband); thread -> v
+    // grid: (ceil((M+1) / 64), P, nband); thread -> v
     const int band = blockIdx.z;
     const int u = blockIdx.y;
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= d.nvb * d.VB) return;
-    cplx<T> val(0, 0);
-    if (v <= d.M) val = psfhat[((size_t)band * d.P + u) * (d.M + 1) + v];
-    psf_l[psf_index(d, band, u, v)] = val;
+    if (v > d.M) return;
+    psf_l[psf_index(d, band, u, v)] = psfhat[((size_t)band * d.P + u) * (d.M + 1) + v];
 }
 
-// ------------------------------------------------------------------- row forward
+// ------------------------------------------------------------------- rows, r2c
+// grid (P, nb): row r of band b of the real view -> its M+1 bins in the spectrum view
 template <typename T>
 __global__ void __launch_bounds__(256)
-k_row_fwd_generic(const T* __restrict__ x, const T* __restrict__ beam, cplx<T>* __restrict__ Tw,
-                  const cplx<T>* __restrict__ twQ, ConvDims d, FftFactors f, int band0) {
+k_rows_r2c(RealView<const T> in, const T* __restrict__ beam, SpecView<T> out, const cplx<T>* __restrict__ twQ,
+           FftFactors f) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int M = in.Q / 2;
     cplx<T>* bufA = reinterpret_cast<cplx<T>*>(smem);
-    cplx<T>* bufB = bufA + d.M;
-    const int i = blockIdx.x;
-    const int bl = blockIdx.y;                 // local band (x/beam index)
-    const int band = band0 + bl;               // plan band (T/psf index)
-    const T* xr = x + ((size_t)bl * d.nx + i) * d.ny;
-    const T* br = beam ? beam + ((size_t)bl * d.nx + i) * d.ny : nullptr;
-    // pack z[n] = x[2n] + i x[2n+1], zero beyond ny
-    for (int n = threadIdx.x; n < d.M; n += blockDim.x) {
-        const int j0 = 2 * n, j1 = 2 * n + 1;
-        T a = 0, b = 0;
-        if (j0 < d.ny) a = br ? xr[j0] * br[j0] : xr[j0];
-        if (j1 < d.ny) b = br ? xr[j1] * br[j1] : xr[j1];
-        bufA[n] = cplx<T>(a, b);
-    }
+    cplx<T>* bufB = bufA + M;
+    const int r = blockIdx.x, b = blockIdx.y;
+    const size_t off = in.row(b, r);
+    const T* xr = in.base + off;
+    const T* br = beam ? beam + off : nullptr;
+    for (int n = threadIdx.x; n < M; n += blockDim.x) bufA[n] = packed_pair(in, xr, br, n);
     cplx<T>* Z = fft_lds_generic<T, false>(bufA, bufB, f, twQ, 2);
-    // X[v] = 1/2 [ (Z[v] + conj Z[M-v]) - i w_Q^v (Z[v] - conj Z[M-v]) ],  v = 0..M
-    for (int v = threadIdx.x; v <= d.M; v += blockDim.x) {
-        const cplx<T> zv = Z[v == d.M ? 0 : v];
-        const cplx<T> zm = conj(Z[v == 0 ? 0 : d.M - v]);
-        const cplx<T> w = twQ[v];
-        const cplx<T> s = zv + zm;
-        const cplx<T> t = mul_mi(w * (zv - zm));
-        Tw[t_index(d, band, i, v)] = T(0.5) * (s + t);
-    }
+    cplx<T>* orow = out.line(b, r);
+    for (int v = threadIdx.x; v <= M; v += blockDim.x) orow[(size_t)v * out.bin] = r2c_bin(Z, M, v, twQ);
 }
 
 // ------------------------------------------------------------------------ column
@@ -121,122 +111,40 @@ k_col_generic(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         Tw[t_index(d, band, n, v)] = Y[n];
 }
 
-// ------------------------------------------------------------------- row inverse
-template <typename T>
-__global__ void __launch_bounds__(256)
-k_row_inv_generic(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
-                  const T* __restrict__ x, const T* __restrict__ beam,
-                  const T* __restrict__ dot_with, const T* __restrict__ dot_with2,
-                  T* __restrict__ out, double* __restrict__ partials, ConvDims d, FftFactors f,
-                  int band0, T scale, T sigmainv) {
-    // all LDS in the one dynamic array (a static __shared__ beside it would eat into
-    // the 160 KB limit and shift the 16-byte alignment of the dynamic base)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* red = reinterpret_cast<double*>(smem);              // 3 sums x 4 waves = 96 B
-    cplx<T>* bufA = reinterpret_cast<cplx<T>*>(smem + 128);
-    cplx<T>* bufB = bufA + d.M;
-    const int i = blockIdx.x;
-    const int bl = blockIdx.y;
-    const int band = band0 + bl;
-    // Z[v] = (Y[v] + conj Y[M-v]) + i conj(w_Q^v) (Y[v] - conj Y[M-v]),  v < M
-    // imaginary parts of the DC and Nyquist bins are ignored (ducc0/pocketfft c2r)
-    for (int v = threadIdx.x; v < d.M; v += blockDim.x) {
-        cplx<T> yv = Tw[t_index(d, band, i, v)];
-        cplx<T> ym = Tw[t_index(d, band, i, d.M - v)];
-        if (v == 0) { yv.y = 0; ym.y = 0; }
-        ym = conj(ym);
-        const cplx<T> w = twQ[v];
-        bufA[v] = (yv + ym) + mul_i(mulc(yv - ym, w));
-    }
-    cplx<T>* z = fft_lds_generic<T, true>(bufA, bufB, f, twQ, 2);
-    const size_t rowoff = ((size_t)bl * d.nx + i) * d.ny;
-    // fused sums: <dot_with, out>, <dot_with2, out>, <out, out>
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int j = threadIdx.x; j < d.ny; j += blockDim.x) {
-        const cplx<T> zz = z[j >> 1];
-        T val = ((j & 1) ? zz.y : zz.x) * scale;
-        if (beam) val *= beam[rowoff + j];
-        val += sigmainv * x[rowoff + j];
-        out[rowoff + j] = val;
-        if (dot_with) {
-            acc[0] += (double)dot_with[rowoff + j] * (double)val;
-            if (dot_with2) acc[1] += (double)dot_with2[rowoff + j] * (double)val;
-            acc[2] += (double)val * (double)val;
-        }
-    }
-    if (dot_with) {
-        block_sum<3>(acc, red);
-        if (threadIdx.x == 0) {
-            const size_t np = (size_t)gridDim.x * gridDim.y, k = (size_t)bl * d.nx + i;
-            partials[k] = acc[0]; partials[np + k] = acc[1]; partials[2 * np + k] = acc[2];
-        }
-    }
-}
-
-// ------------------------------------------------------------- PSFHAT producer
-// psfhat = r2c(ifftshift(psf), axes=(0,1), forward, unnormalised)   (gridder.py:712-714, fft.py:7-9)
-// ifftshift: y[i] = x[(i + n/2) % n] (n/2 rounded down).  One workgroup per line: rows as
-// packed-real transforms of length M = Q/2 (+ Hermitian unpacking), then columns of length P
-// in place -- once per gridding run, so the column pass simply takes the strided 8/16-byte
-// accesses of the caller's (P, M+1) row-major layout.
-template <typename T>
-__global__ void __launch_bounds__(256)
-k_psfhat_rows(const T* __restrict__ psf, cplx<T>* __restrict__ out, const cplx<T>* __restrict__ twQ,
-              int P, int Q, FftFactors f, int shift) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int M = Q / 2;
-    cplx<T>* bufA = reinterpret_cast<cplx<T>*>(smem);
-    cplx<T>* bufB = bufA + M;
-    const int u = blockIdx.x, band = blockIdx.y;
-    const int su = shift ? P / 2 : 0, sv = shift ? M : 0;                     // Q/2 = M
-    const T* row = psf + ((size_t)band * P + (u + su) % P) * Q;
-    for (int n = threadIdx.x; n < M; n += blockDim.x)
-        bufA[n] = cplx<T>(row[(2 * n + sv) % Q], row[(2 * n + 1 + sv) % Q]);
-    cplx<T>* Z = fft_lds_generic<T, false>(bufA, bufB, f, twQ, 2);
-    cplx<T>* orow = out + ((size_t)band * P + u) * (M + 1);
-    for (int v = threadIdx.x; v <= M; v += blockDim.x) {
-        const cplx<T> zv = Z[v == M ? 0 : v];
-        const cplx<T> zm = conj(Z[v == 0 ? 0 : M - v]);
-        orow[v] = T(0.5) * ((zv + zm) + mul_mi(twQ[v] * (zv - zm)));
-    }
-}
-
+// plain FFT of length P down every column of a spectrum view, in place: grid (bins, nb)
 template <typename T, bool INV>
 __global__ void __launch_bounds__(256)
-k_psfhat_cols(cplx<T>* __restrict__ out, const cplx<T>* __restrict__ twP, int P, int M1, FftFactors f) {
+k_psfhat_cols(SpecView<T> a, const cplx<T>* __restrict__ twP, FftFactors f) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int P = f.n;
     cplx<T>* bufA = reinterpret_cast<cplx<T>*>(smem);
     cplx<T>* bufB = bufA + P;
-    cplx<T>* col = out + (size_t)blockIdx.y * P * M1 + blockIdx.x;
-    for (int n = threadIdx.x; n < P; n += blockDim.x) bufA[n] = col[(size_t)n * M1];
+    cplx<T>* col = a.line(blockIdx.y, 0) + (size_t)blockIdx.x * a.bin;
+    for (int n = threadIdx.x; n < P; n += blockDim.x) bufA[n] = col[(size_t)n * a.row];
     cplx<T>* X = fft_lds_generic<T, INV>(bufA, bufB, f, twP, 1);
-    for (int n = threadIdx.x; n < P; n += blockDim.x) col[(size_t)n * M1] = X[n];
+    for (int n = threadIdx.x; n < P; n += blockDim.x) col[(size_t)n * a.row] = X[n];
 }
 
-// inverse of k_psfhat_rows (no shift): half spectrum row (M+1 bins, after the inverse column
-// pass) -> Q real samples, unnormalised; DC / Nyquist imaginary parts ignored like ducc's c2r
+// ------------------------------------------------------------------- rows, c2r
+// grid (P, nb): the M+1 bins of row r of band b -> c2r of length Q -> the row's first `valid` samples through the
+// epilogue.  LDS: the two line buffers, then (only with e.dot_with) 128 B for the block sums -- all in the one dynamic
+// array (a static __shared__ beside it would eat into the 160 KB limit)
 template <typename T>
 __global__ void __launch_bounds__(256)
-k_psf_rows_c2r(const cplx<T>* __restrict__ spec, T* __restrict__ psf, const cplx<T>* __restrict__ twQ,
-               int P, int Q, FftFactors f) {
+k_rows_c2r(SpecView<T> in, RealView<T> out, const cplx<T>* __restrict__ twQ, FftFactors f, Epilogue<T> e) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int M = Q / 2;
+    const int M = out.Q / 2;
     cplx<T>* bufA = reinterpret_cast<cplx<T>*>(smem);
     cplx<T>* bufB = bufA + M;
-    const int u = blockIdx.x, band = blockIdx.y;
-    const cplx<T>* srow = spec + ((size_t)band * P + u) * (M + 1);
-    for (int v = threadIdx.x; v < M; v += blockDim.x) {
-        cplx<T> yv = srow[v], ym = srow[M - v];
-        if (v == 0) { yv.y = 0; ym.y = 0; }
-        ym = conj(ym);
-        bufA[v] = (yv + ym) + mul_i(mulc(yv - ym, twQ[v]));
-    }
+    double* red = reinterpret_cast<double*>(bufB + M);          // 3 sums x 4 waves = 96 B
+    const int r = blockIdx.x, b = blockIdx.y;
+    const cplx<T>* srow = in.line(b, r);
+    for (int v = threadIdx.x; v < M; v += blockDim.x)
+        bufA[v] = c2r_bin(srow[(size_t)v * in.bin], srow[(size_t)(M - v) * in.bin], v, twQ[v]);
     cplx<T>* z = fft_lds_generic<T, true>(bufA, bufB, f, twQ, 2);
-    T* orow = psf + ((size_t)band * P + u) * Q;
-    for (int n = threadIdx.x; n < M; n += blockDim.x) {
-        orow[2 * n] = z[n].x;
-        orow[2 * n + 1] = z[n].y;
-    }
+    double acc[3] = {0.0, 0.0, 0.0};
+    finish_row(z, out.base, out.row(b, r), out.valid, (int)threadIdx.x, (int)blockDim.x, e, acc);
+    if (e.dot_with) store_row_partials(acc, red, e.partials, (size_t)b * out.P + r, (size_t)gridDim.x * gridDim.y);
 }
 
 // psf2[u2][v2] = scale * psf[(du mod P)][(dv mod Q)] for the offsets |du| < nx, |dv| < ny a
@@ -287,7 +195,6 @@ k_sum_partials_bands(const double* __restrict__ partials, int bs, int qs, int bs
 static ConvDims dims_of(const pfb_conv_plan* p) {
     ConvDims d;
     d.nx = p->nx; d.ny = p->ny; d.P = p->P; d.Q = p->Q; d.M = p->M;
-    d.VB = p->VB; d.nvb = p->nvb;
     d.T_band = p->T_elems_per_band; d.psf_band = p->psf_elems_per_band;
     return d;
 }
@@ -307,76 +214,157 @@ static int upload_twiddles(int n, void** dev) {
     return PFB_OK;
 }
 
-template <typename T>
-static int apply_generic(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
-                         double scale, double sigmainv, void* out, const void* dot_with,
-                         const void* dot_with2, hipStream_t st) {
-    const ConvDims d = dims_of(p);
-    const size_t lds_row = 128 + 2 * sizeof(cplx<T>) * (size_t)p->M;
-    const size_t lds_col = 2 * sizeof(cplx<T>) * (size_t)p->P;
-    prof_mark(p, st, 0);
-    hipLaunchKernelGGL((k_row_fwd_generic<T>), dim3(p->nx, nb), dim3(256), lds_row, st,
-                       (const T*)x, (const T*)beam, (cplx<T>*)p->T, (const cplx<T>*)p->twQ,
-                       d, p->frow, band0);
-    prof_mark(p, st, 1);
-    hipLaunchKernelGGL((k_col_generic<T>), dim3(p->M + 1, nb), dim3(256), lds_col, st,
-                       (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,
-                       d, p->fcol, band0);
-    prof_mark(p, st, 2);
-    hipLaunchKernelGGL((k_row_inv_generic<T>), dim3(p->nx, nb), dim3(256), lds_row, st,
-                       (const cplx<T>*)p->T, (const cplx<T>*)p->twQ, (const T*)x,
-                       (const T*)beam, (const T*)dot_with, (const T*)dot_with2, (T*)out, p->partials, d,
-                       p->frow, band0, (T)scale, (T)sigmainv);
-    prof_mark(p, st, 3);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
+// device memory owned by a scope: freed on every way out (hipFree waits for work that still uses it)
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    bool alloc(size_t bytes) { return bytes == 0 || hipMalloc(&p, bytes) == hipSuccess; }
+};
 
 template <typename T>
-static int set_lds_limits(const pfb_conv_plan*) {
+static int set_lds_limits() {
     // the attribute is per function, not per launch: always raise it to the whole
     // 160 KB of a gfx950 CU so plans of different sizes can coexist
     const int lds_max = 160 * 1024;
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_row_fwd_generic<T>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_row_inv_generic<T>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_col_generic<T>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_psfhat_rows<T>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_psfhat_cols<T, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_psfhat_cols<T, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_psf_rows_c2r<T>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    for (const void* k : {(const void*)k_rows_r2c<T>, (const void*)k_rows_c2r<T>, (const void*)k_col_generic<T>,
+                          (const void*)(k_psfhat_cols<T, false>), (const void*)(k_psfhat_cols<T, true>)})
+        PFB_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
     return PFB_OK;
 }
 
 // a line of n complex values fits the LDS ping-pong buffers of the one-workgroup-per-line kernels
 template <typename T> static inline bool line_fits_lds(int n) { return 2 * sizeof(cplx<T>) * (size_t)n <= (size_t)160 * 1024; }
 
-// psfhat_out (nband, P, M+1) = r2c(ifftshift(psf)) for ANY 13-smooth grid: rows, then columns in place; a line that
-// fits the LDS takes the one-workgroup-per-line kernels, a longer one the global-memory passes (fft_long.hpp).
-// twP / twQ: exp(-2 pi i n / P), exp(-2 pi i n / Q).  Synchronous.
+// ---------------------------------------------------------------------------------------------- stage entries
+// One host entry per stage.  lds: one line per workgroup in LDS (no scratch); otherwise global-memory passes in the
+// caller's scratch `ws` (rows_ws_elems / cols_ws_elems complex values).  Launches only: the caller checks
+// hipGetLastError and synchronises where it has to.
+static inline size_t rows_ws_elems(bool lds, int nb, int P, int M) { return lds ? 0 : 2 * (size_t)nb * P * M; }
+static inline size_t cols_ws_elems(bool lds, int P, int nbins) { return lds ? 0 : (size_t)P * nbins; }
+
+// r2c of every row of nb bands of a real view (f: length Q/2, twQ: exp(-2 pi i n / Q))
+template <typename T>
+static int rows_r2c(const RealView<const T>& in, const T* beam, const SpecView<T>& out, int nb, const FftFactors& f,
+                    const cplx<T>* twQ, bool lds, cplx<T>* ws, hipStream_t st) {
+    const int M = in.Q / 2;
+    if (lds) {
+        hipLaunchKernelGGL((k_rows_r2c<T>), dim3(in.P, nb), dim3(256), 2 * sizeof(cplx<T>) * (size_t)M, st, in, beam, out, twQ, f);
+        return PFB_OK;
+    }
+    const size_t n = (size_t)nb * in.P * M;
+    hipLaunchKernelGGL((k_long_pack<T>), long_grid(M, in.P, nb), dim3(256), 0, st, in, beam, ws);
+    if (int rc = long_fft<T, false>(ws, ws + n, n, f, twQ, 2, (size_t)nb * in.P, 1, (size_t)M, st); rc != PFB_OK) return rc;
+    hipLaunchKernelGGL((k_long_post<T>), long_grid(M + 1, in.P, nb), dim3(256), 0, st, (const cplx<T>*)ws, out, twQ, in.P, M);
+    return PFB_OK;
+}
+
+// unnormalised c2r of every row of nb bands of a spectrum view, through the epilogue, into a real view
+template <typename T>
+static int rows_c2r(const SpecView<T>& in, const RealView<T>& out, const Epilogue<T>& e, int nb, const FftFactors& f,
+                    const cplx<T>* twQ, bool lds, cplx<T>* ws, hipStream_t st) {
+    const int M = out.Q / 2;
+    if (lds) {
+        hipLaunchKernelGGL((k_rows_c2r<T>), dim3(out.P, nb), dim3(256), 2 * sizeof(cplx<T>) * (size_t)M + (e.dot_with ? 128 : 0),
+                           st, in, out, twQ, f, e);
+        return PFB_OK;
+    }
+    const size_t n = (size_t)nb * out.P * M;
+    hipLaunchKernelGGL((k_long_pre<T>), long_grid(M, out.P, nb), dim3(256), 0, st, in, ws, twQ, out.P, M);
+    if (int rc = long_fft<T, true>(ws, ws + n, n, f, twQ, 2, (size_t)nb * out.P, 1, (size_t)M, st); rc != PFB_OK) return rc;
+    hipLaunchKernelGGL((k_long_finish<T>), e.x ? dim3(1, out.P, nb) : long_grid(out.valid, out.P, nb), dim3(256), 0, st,
+                       (const cplx<T>*)ws, out, e);
+    return PFB_OK;
+}
+
+// FFT of length f.n down the `nbins` columns of nb bands of a spectrum view, in place (a band is contiguous)
+template <typename T, bool INV>
+static int cols(const SpecView<T>& a, int nb, int nbins, const FftFactors& f, const cplx<T>* twP, bool lds, cplx<T>* ws,
+                hipStream_t st) {
+    if (lds) {
+        hipLaunchKernelGGL((k_psfhat_cols<T, INV>), dim3(nbins, nb), dim3(256), 2 * sizeof(cplx<T>) * (size_t)f.n, st, a, twP, f);
+        return PFB_OK;
+    }
+    for (int b = 0; b < nb; ++b)
+        if (int rc = long_fft<T, INV>(a.line(b, 0), ws, (size_t)f.n * nbins, f, twP, 1, (size_t)nbins, a.row, a.bin, st);
+            rc != PFB_OK)
+            return rc;
+    return PFB_OK;
+}
+
+// the column stage of the convolution, in place in T: zero-pad to P, forward, multiply by psf_l, inverse, keep nx
+template <typename T>
+static int conv_cols(pfb_conv_plan* p, int band0, int nb, bool lds, cplx<T>* ws, hipStream_t st) {
+    if (lds) {
+        hipLaunchKernelGGL((k_col_generic<T>), dim3(p->M + 1, nb), dim3(256), 2 * sizeof(cplx<T>) * (size_t)p->P, st,
+                           (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP, dims_of(p), p->fcol, band0);
+        return PFB_OK;
+    }
+    // band by band through one contiguous zero-padded column per line: C[v][u]
+    const int nbins = p->M + 1;
+    const size_t ncol = (size_t)nbins * p->P;
+    const SpecView<T> C{ws, ncol, 1, (size_t)p->P};
+    for (int bl = 0; bl < nb; ++bl) {
+        cplx<T>* Tb = (cplx<T>*)p->T + (size_t)(band0 + bl) * p->T_elems_per_band;
+        const cplx<T>* psf_b = (const cplx<T>*)p->psf_l + (size_t)(band0 + bl) * p->psf_elems_per_band;
+        hipLaunchKernelGGL((k_long_col_load<T>), long_grid(p->P, nbins, 1), dim3(256), 0, st, (const cplx<T>*)Tb, ws, p->nx, p->P);
+        if (int rc = cols<T, false>(C, 1, nbins, p->fcol, (const cplx<T>*)p->twP, false, ws + ncol, st); rc != PFB_OK) return rc;
+        hipLaunchKernelGGL((k_long_col_mul<T>), dim3(4096), dim3(256), 0, st, ws, psf_b, ncol);
+        if (int rc = cols<T, true>(C, 1, nbins, p->fcol, (const cplx<T>*)p->twP, false, ws + ncol, st); rc != PFB_OK) return rc;
+        hipLaunchKernelGGL((k_long_col_store<T>), long_grid(p->nx, nbins, 1), dim3(256), 0, st, (const cplx<T>*)ws, Tb, p->nx, p->P);
+    }
+    return PFB_OK;
+}
+
+// scratch of apply_coverage on a long_lines plan for nb bands: the larger of the row stages' and the column stage's
+template <typename T>
+static size_t long_apply_ws_bytes(int nb, int nx, int M, int P) {
+    const size_t rows = rows_ws_elems(false, nb, nx, M), cols = 2 * (size_t)(M + 1) * P;
+    return sizeof(cplx<T>) * (rows > cols ? rows : cols);
+}
+
+// the convolution off the fast path: three stage calls, all in LDS or (long_lines plan) all as global passes
+template <typename T>
+static int apply_coverage(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
+                          double scale, double sigmainv, void* out, const void* dot_with,
+                          const void* dot_with2, hipStream_t st) {
+    const bool lds = !p->long_lines;
+    cplx<T>* ws = (cplx<T>*)p->long_ws;
+    const size_t img = (size_t)p->nx * p->ny;
+    const RealView<const T> xin{(const T*)x, img, p->ny, p->nx, p->Q, p->ny, 0, 0};
+    const RealView<T> xout{(T*)out, img, p->ny, p->nx, p->Q, p->ny, 0, 0};
+    const SpecView<T> Tv{(cplx<T>*)p->T + (size_t)band0 * p->T_elems_per_band, p->T_elems_per_band, 1, (size_t)p->nx};
+    const Epilogue<T> e{(const T*)x, (const T*)beam, (const T*)dot_with, (const T*)dot_with2, p->partials, (T)scale, (T)sigmainv};
+    prof_mark(p, st, 0);
+    int rc = rows_r2c<T>(xin, (const T*)beam, Tv, nb, p->frow, (const cplx<T>*)p->twQ, lds, ws, st);
+    prof_mark(p, st, 1);
+    if (rc == PFB_OK) rc = conv_cols<T>(p, band0, nb, lds, ws, st);
+    prof_mark(p, st, 2);
+    if (rc == PFB_OK) rc = rows_c2r<T>(Tv, xout, e, nb, p->frow, (const cplx<T>*)p->twQ, lds, ws, st);
+    prof_mark(p, st, 3);
+    if (rc != PFB_OK) return rc;
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+// psfhat_out (nband, P, M+1) = r2c(ifftshift(psf)) for ANY 13-smooth grid: rows, then columns in place; each of the two
+// transforms runs in LDS when its line fits, else as global passes.  twP / twQ: exp(-2 pi i n / P), exp(-2 pi i n / Q).
+// Synchronous.
 template <typename T>
 static int psfhat_from_psf_t(const void* psf, void* psfhat_out, int nband, int P, int Q, const FftFactors& frow,
                              const FftFactors& fcol, const void* twP, const void* twQ, hipStream_t st) {
     const int M = Q / 2;
-    const size_t lds_r = 2 * sizeof(cplx<T>) * (size_t)M, lds_c = 2 * sizeof(cplx<T>) * (size_t)P;
-    if (line_fits_lds<T>(M))
-        hipLaunchKernelGGL((k_psfhat_rows<T>), dim3(P, nband), dim3(256), lds_r, st, (const T*)psf,
-                           (cplx<T>*)psfhat_out, (const cplx<T>*)twQ, P, Q, frow, 1);
-    else if (int rc = long_rows_r2c<T>((const T*)psf, (cplx<T>*)psfhat_out, (const cplx<T>*)twQ, nband, P, Q, frow, 1, st);
-             rc != PFB_OK)
-        return rc;
-    if (line_fits_lds<T>(P))
-        hipLaunchKernelGGL((k_psfhat_cols<T, false>), dim3(M + 1, nband), dim3(256), lds_c, st,
-                           (cplx<T>*)psfhat_out, (const cplx<T>*)twP, P, M + 1, fcol);
-    else if (int rc = long_cols<T, false>((cplx<T>*)psfhat_out, (const cplx<T>*)twP, nband, P, M + 1, fcol, st);
-             rc != PFB_OK)
-        return rc;
+    const bool rl = line_fits_lds<T>(M), cl = line_fits_lds<T>(P);
+    const size_t need = sizeof(cplx<T>) * std::max(rows_ws_elems(rl, nband, P, M), cols_ws_elems(cl, P, M + 1));
+    DevBuf ws;
+    PFB_REQUIRE(ws.alloc(need), PFB_ERR_ALLOC, "psfhat_from_psf: device allocation failed (%zu B)", need);
+    const RealView<const T> in{(const T*)psf, (size_t)P * Q, Q, P, Q, Q, P / 2, M};
+    const SpecView<T> out{(cplx<T>*)psfhat_out, (size_t)P * (M + 1), (size_t)(M + 1), 1};
+    int rc = rows_r2c<T>(in, nullptr, out, nband, frow, (const cplx<T>*)twQ, rl, (cplx<T>*)ws.p, st);
+    if (rc == PFB_OK) rc = cols<T, false>(out, nband, M + 1, fcol, (const cplx<T>*)twP, cl, (cplx<T>*)ws.p, st);
+    if (rc != PFB_OK) return rc;
     PFB_HIP_CHECK(hipGetLastError());
     PFB_HIP_CHECK(hipStreamSynchronize(st));
     return PFB_OK;
@@ -388,13 +376,11 @@ static int psfhat_from_psf_grid(const void* psf, void* psfhat_out, int nband, in
     FftFactors fr, fc;
     PFB_REQUIRE(plan_factors(Q / 2, &fr) && plan_factors(P, &fc), PFB_ERR_UNSUPPORTED,
                 "psfhat_from_psf: (%d,%d) has a prime factor > 13", P, Q);
-    void *twP = nullptr, *twQ = nullptr;
-    int rc = upload_twiddles<T>(P, &twP);
-    if (rc == PFB_OK) rc = upload_twiddles<T>(Q, &twQ);
-    if (rc == PFB_OK) rc = set_lds_limits<T>(nullptr);
-    if (rc == PFB_OK) rc = psfhat_from_psf_t<T>(psf, psfhat_out, nband, P, Q, fr, fc, twP, twQ, st);
-    if (twP) (void)hipFree(twP);
-    if (twQ) (void)hipFree(twQ);
+    DevBuf twP, twQ;
+    int rc = upload_twiddles<T>(P, &twP.p);
+    if (rc == PFB_OK) rc = upload_twiddles<T>(Q, &twQ.p);
+    if (rc == PFB_OK) rc = set_lds_limits<T>();
+    if (rc == PFB_OK) rc = psfhat_from_psf_t<T>(psf, psfhat_out, nband, P, Q, fr, fc, twP.p, twQ.p, st);
     return rc;
 }
 
@@ -408,56 +394,40 @@ static int psfhat_regrid_t(const void* psfhat, int nband, int nx, int ny, int P,
     FftFactors fr, fc, fr2, fc2;
     PFB_REQUIRE(plan_factors(M, &fr) && plan_factors(P, &fc) && plan_factors(M2, &fr2) && plan_factors(P2, &fc2),
                 PFB_ERR_UNSUPPORTED, "psfhat_regrid: a grid length has a prime factor > 13");
-    void *twP = nullptr, *twQ = nullptr, *twP2 = nullptr, *twQ2 = nullptr, *spec = nullptr, *psf = nullptr, *psf2 = nullptr;
-    int rc = upload_twiddles<T>(P, &twP);
-    if (rc == PFB_OK) rc = upload_twiddles<T>(Q, &twQ);
-    if (rc == PFB_OK) rc = upload_twiddles<T>(P2, &twP2);
-    if (rc == PFB_OK) rc = upload_twiddles<T>(Q2, &twQ2);
+    DevBuf twP, twQ, twP2, twQ2, spec, psf, psf2, ws;
+    int rc = upload_twiddles<T>(P, &twP.p);
+    if (rc == PFB_OK) rc = upload_twiddles<T>(Q, &twQ.p);
+    if (rc == PFB_OK) rc = upload_twiddles<T>(P2, &twP2.p);
+    if (rc == PFB_OK) rc = upload_twiddles<T>(Q2, &twQ2.p);
+    if (rc != PFB_OK) return rc;
+    // every transform picks the one-workgroup-per-line LDS kernel when its line fits, else the global-memory passes
+    const bool rl = line_fits_lds<T>(M), cl = line_fits_lds<T>(P), rl2 = line_fits_lds<T>(M2), cl2 = line_fits_lds<T>(P2);
     const size_t nspec = (size_t)nband * P * (M + 1), npsf = (size_t)nband * P * Q, npsf2 = (size_t)nband * P2 * Q2;
-    if (rc == PFB_OK && (hipMalloc(&spec, nspec * sizeof(cplx<T>)) != hipSuccess ||
-                         hipMalloc(&psf, npsf * sizeof(T)) != hipSuccess ||
-                         hipMalloc(&psf2, npsf2 * sizeof(T)) != hipSuccess)) {
-        set_error("psfhat_regrid: device allocation failed");
-        rc = PFB_ERR_ALLOC;
-    }
+    const size_t nws = std::max(std::max(rows_ws_elems(rl, nband, P, M), cols_ws_elems(cl, P, M + 1)),
+                                std::max(rows_ws_elems(rl2, nband, P2, M2), cols_ws_elems(cl2, P2, M2 + 1)));
+    PFB_REQUIRE(spec.alloc(nspec * sizeof(cplx<T>)) && psf.alloc(npsf * sizeof(T)) && psf2.alloc(npsf2 * sizeof(T)) &&
+                    ws.alloc(nws * sizeof(cplx<T>)),
+                PFB_ERR_ALLOC, "psfhat_regrid: device allocation failed");
+    set_lds_limits<T>();
+    const SpecView<T> sv{(cplx<T>*)spec.p, (size_t)P * (M + 1), (size_t)(M + 1), 1};
+    const SpecView<T> sv2{(cplx<T>*)psfhat2, (size_t)P2 * (M2 + 1), (size_t)(M2 + 1), 1};
+    const RealView<T> pv{(T*)psf.p, (size_t)P * Q, Q, P, Q, Q, 0, 0};
+    const RealView<const T> pv2{(const T*)psf2.p, (size_t)P2 * Q2, Q2, P2, Q2, Q2, 0, 0};
+    const Epilogue<T> plain{nullptr, nullptr, nullptr, nullptr, nullptr, T(1), T(0)};
+    cplx<T>* w = (cplx<T>*)ws.p;
+    (void)hipMemcpyAsync(spec.p, psfhat, nspec * sizeof(cplx<T>), hipMemcpyDeviceToDevice, st);
+    rc = cols<T, true>(sv, nband, M + 1, fc, (const cplx<T>*)twP.p, cl, w, st);
+    if (rc == PFB_OK) rc = rows_c2r<T>(sv, pv, plain, nband, fr, (const cplx<T>*)twQ.p, rl, w, st);
     if (rc == PFB_OK) {
-        set_lds_limits<T>(nullptr);
-        // every transform picks the one-workgroup-per-line LDS kernel when its line fits, else the global-memory passes
-        (void)hipMemcpyAsync(spec, psfhat, nspec * sizeof(cplx<T>), hipMemcpyDeviceToDevice, st);
-        if (line_fits_lds<T>(P))
-            hipLaunchKernelGGL((k_psfhat_cols<T, true>), dim3(M + 1, nband), dim3(256), 2 * sizeof(cplx<T>) * (size_t)P, st,
-                               (cplx<T>*)spec, (const cplx<T>*)twP, P, M + 1, fc);
-        else
-            rc = long_cols<T, true>((cplx<T>*)spec, (const cplx<T>*)twP, nband, P, M + 1, fc, st);
-        if (rc == PFB_OK) {
-            if (line_fits_lds<T>(M))
-                hipLaunchKernelGGL((k_psf_rows_c2r<T>), dim3(P, nband), dim3(256), 2 * sizeof(cplx<T>) * (size_t)M, st,
-                                   (const cplx<T>*)spec, (T*)psf, (const cplx<T>*)twQ, P, Q, fr);
-            else
-                rc = long_rows_c2r<T>((const cplx<T>*)spec, (T*)psf, (const cplx<T>*)twQ, nband, P, Q, fr, st);
-        }
-        if (rc == PFB_OK) {
-            hipLaunchKernelGGL((k_psf_embed<T>), dim3((Q2 + 255) / 256, P2, nband), dim3(256), 0, st, (const T*)psf,
-                               (T*)psf2, nx, ny, P, Q, P2, Q2, (T)(1.0 / ((double)P * (double)Q)));
-            if (line_fits_lds<T>(M2))
-                hipLaunchKernelGGL((k_psfhat_rows<T>), dim3(P2, nband), dim3(256), 2 * sizeof(cplx<T>) * (size_t)M2, st,
-                                   (const T*)psf2, (cplx<T>*)psfhat2, (const cplx<T>*)twQ2, P2, Q2, fr2, 0);
-            else
-                rc = long_rows_r2c<T>((const T*)psf2, (cplx<T>*)psfhat2, (const cplx<T>*)twQ2, nband, P2, Q2, fr2, 0, st);
-        }
-        if (rc == PFB_OK) {
-            if (line_fits_lds<T>(P2))
-                hipLaunchKernelGGL((k_psfhat_cols<T, false>), dim3(M2 + 1, nband), dim3(256), 2 * sizeof(cplx<T>) * (size_t)P2,
-                                   st, (cplx<T>*)psfhat2, (const cplx<T>*)twP2, P2, M2 + 1, fc2);
-            else
-                rc = long_cols<T, false>((cplx<T>*)psfhat2, (const cplx<T>*)twP2, nband, P2, M2 + 1, fc2, st);
-        }
-        if (rc == PFB_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
-            set_error("psfhat_regrid: kernel launch failed");
-            rc = PFB_ERR_HIP;
-        }
+        hipLaunchKernelGGL((k_psf_embed<T>), dim3((Q2 + 255) / 256, P2, nband), dim3(256), 0, st, (const T*)psf.p,
+                           (T*)psf2.p, nx, ny, P, Q, P2, Q2, (T)(1.0 / ((double)P * (double)Q)));
+        rc = rows_r2c<T>(pv2, nullptr, sv2, nband, fr2, (const cplx<T>*)twQ2.p, rl2, w, st);
     }
-    for (void* q : {twP, twQ, twP2, twQ2, spec, psf, psf2}) if (q) (void)hipFree(q);
+    if (rc == PFB_OK) rc = cols<T, false>(sv2, nband, M2 + 1, fc2, (const cplx<T>*)twP2.p, cl2, w, st);
+    if (rc == PFB_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+        set_error("psfhat_regrid: kernel launch failed");
+        rc = PFB_ERR_HIP;
+    }
     return rc;
 }
 
@@ -522,7 +492,7 @@ int pfb_psfconv_plan_create(int nx, int ny, int nx_psf, int ny_psf, int nband, i
         rc = PFB_ERR_ALLOC;
     if (rc == PFB_OK) {
         p->workspace_bytes = tbytes + pbytes;
-        rc = (dtype == PFB_F32) ? set_lds_limits<float>(p) : set_lds_limits<double>(p);
+        rc = (dtype == PFB_F32) ? set_lds_limits<float>() : set_lds_limits<double>();
         if (p->fast && rc == PFB_OK) rc = pow2_prepare(p);
     }
     if (rc != PFB_OK) {
@@ -598,7 +568,7 @@ int pfb_psfconv_set_psfhat(pfb_conv_plan* p, const void* psfhat, void* stream) {
         return rc;
     }
     const ConvDims d = dims_of(p);
-    dim3 grid((p->nvb * p->VB + 63) / 64, p->P, p->nband);
+    dim3 grid((p->M + 1 + 63) / 64, p->P, p->nband);
     if (p->dtype == PFB_F32)
         hipLaunchKernelGGL((k_relayout_psfhat<float>), grid, dim3(64), 0, as_stream(stream),
                            (const cplx<float>*)psfhat, (cplx<float>*)p->psf_l, d);
@@ -619,20 +589,17 @@ int pfb_psfconv_set_psf(pfb_conv_plan* p, const void* psf, void* psfhat_out, voi
     }
     const size_t csz = p->dtype == PFB_F32 ? 8 : 16;
     hipStream_t st = as_stream(stream);
-    void* tmp = nullptr;
+    DevBuf tmp;
     void* dst = psfhat_out;
     if (!dst) {
-        PFB_HIP_CHECK(hipMalloc(&tmp, csz * (size_t)p->nband * p->P * (p->M + 1)));
-        dst = tmp;
+        PFB_HIP_CHECK(hipMalloc(&tmp.p, csz * (size_t)p->nband * p->P * (p->M + 1)));
+        dst = tmp.p;
     }
     int rc = p->dtype == PFB_F32
         ? psfhat_from_psf_t<float>(psf, dst, p->nband, p->P, p->Q, p->frow, p->fcol, p->twP, p->twQ, st)
         : psfhat_from_psf_t<double>(psf, dst, p->nband, p->P, p->Q, p->frow, p->fcol, p->twP, p->twQ, st);
     if (rc == PFB_OK) rc = pfb_psfconv_set_psfhat(p, dst, stream);
-    if (tmp) {
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(tmp);
-    }
+    if (tmp.p) (void)hipStreamSynchronize(st);
     return rc;
 }
 
@@ -676,37 +643,25 @@ static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, cons
     p->last_band_stride = p->partials_per_band;
     if (p->fast)
         rc = pow2_apply(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
-    else if (p->long_lines) {
-        const size_t need = p->dtype == PFB_F32 ? long_apply_ws_bytes<float>(nb, p->nx, p->M, p->P)
-                                                : long_apply_ws_bytes<double>(nb, p->nx, p->M, p->P);
-        if (need > p->long_ws_bytes) {
-            PFB_HIP_CHECK(hipStreamSynchronize(st));
-            if (p->long_ws) (void)hipFree(p->long_ws);
-            p->long_ws = nullptr; p->long_ws_bytes = 0;
-            if (hipMalloc(&p->long_ws, need) != hipSuccess) {
-                set_error("apply: workspace allocation of %zu B for the long-line path failed", need);
-                return PFB_ERR_ALLOC;
+    else {
+        if (p->long_lines) {                                  // the global passes' scratch: grown on demand, freed with the plan
+            const size_t need = p->dtype == PFB_F32 ? long_apply_ws_bytes<float>(nb, p->nx, p->M, p->P)
+                                                    : long_apply_ws_bytes<double>(nb, p->nx, p->M, p->P);
+            if (need > p->long_ws_bytes) {
+                PFB_HIP_CHECK(hipStreamSynchronize(st));
+                if (p->long_ws) (void)hipFree(p->long_ws);
+                p->long_ws = nullptr; p->long_ws_bytes = 0;
+                if (hipMalloc(&p->long_ws, need) != hipSuccess) {
+                    set_error("apply: workspace allocation of %zu B for the long-line path failed", need);
+                    return PFB_ERR_ALLOC;
+                }
+                p->long_ws_bytes = need;
             }
-            p->long_ws_bytes = need;
         }
-        prof_mark(p, st, 0); prof_mark(p, st, 1); prof_mark(p, st, 2);
-        if (p->dtype == PFB_F32)
-            rc = apply_long<float>((cplx<float>*)p->long_ws, (cplx<float>*)p->T, (const cplx<float>*)p->psf_l, p->partials,
-                                   (const cplx<float>*)p->twP, (const cplx<float>*)p->twQ, p->frow, p->fcol, p->nx, p->ny,
-                                   p->P, p->M, p->T_elems_per_band, p->psf_elems_per_band, band0, nb, (const float*)x,
-                                   (const float*)beam, scale, sigmainv, (float*)out, (const float*)dot_with,
-                                   (const float*)dot_with2, st);
-        else
-            rc = apply_long<double>((cplx<double>*)p->long_ws, (cplx<double>*)p->T, (const cplx<double>*)p->psf_l,
-                                    p->partials, (const cplx<double>*)p->twP, (const cplx<double>*)p->twQ, p->frow, p->fcol,
-                                    p->nx, p->ny, p->P, p->M, p->T_elems_per_band, p->psf_elems_per_band, band0, nb,
-                                    (const double*)x, (const double*)beam, scale, sigmainv, (double*)out,
-                                    (const double*)dot_with, (const double*)dot_with2, st);
-        prof_mark(p, st, 3);
-    } else if (p->dtype == PFB_F32)
-        rc = apply_generic<float>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st);
-    else
-        rc = apply_generic<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st);
+        rc = p->dtype == PFB_F32
+            ? apply_coverage<float>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st)
+            : apply_coverage<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st);
+    }
     if (rc != PFB_OK) return rc;
     if (dot_with && ndots > 0 && per_band) {
         hipLaunchKernelGGL(k_sum_partials_bands, dim3(nb), dim3(256), 0, st, p->partials, p->last_band_slots,

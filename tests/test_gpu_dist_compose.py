@@ -377,7 +377,9 @@ def test_cg_dct_nested_dict(kind):
                                    # power-of-two: the fast path's row / column kernels (largest column / row lines)
                                    (2, 2048, 1024), (1, 16384, 256), (1, 128, 16384),
                                    # lines beyond the LDS, not powers of two: global-memory Stockham passes
-                                   (1, 12000, 96), (1, 96, 12000), (1, 14400, 128)])
+                                   (1, 12000, 96), (1, 96, 12000), (1, 14400, 128),
+                                   # rows beyond the LDS in fp32 too (M = 10400 = 2^5 5^2 13 > 10240)
+                                   (1, 8, 20800)])
 def test_native_psfhat_producer(shape, rdt):
     """pfb_psfconv_set_psf (gridder.py:712-714: r2c(ifftshift(psf))) against the oracle, pow2 and
     mixed-radix grids, odd nx_psf; and a plan built straight from the PSF convolves like one built
@@ -619,6 +621,32 @@ def test_plan_from_psf_for_embedded_sizes():
     want = ofc.psf_convolve_cube(xpad, xhat, xout, ref_hat, Q, x)
     got = plan.apply(torch.from_numpy(x).cuda()).cpu().numpy()
     assert np.abs(got - want).max() < 1e-12 * np.abs(want).max()
+
+
+def test_psfhat_regrid_fp32_rows_beyond_the_lds():
+    """The fp32 instantiation of pfb_psfhat_regrid, called directly (the Python layer tries fp64 first): one band from
+    the (8, 20800) grid to (8, 21000), M = 10400 and M2 = 10500 = 2^2 3 5^3 7 both beyond the LDS, so the c2r and the r2c
+    rows run as global-memory passes and the columns in LDS.  Checked through the oracle: a (4, 10400) image convolved
+    with the returned spectrum on the new grid against the same image with the original spectrum on the old grid."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from pfb_clean_amd import _lib, _dev
+    lib = _lib.load()
+    rng = np.random.default_rng(20800)
+    nx, ny, P, Q, P2, Q2 = 4, 10400, 8, 20800, 8, 21000
+    ph = ofc.psfhat_from_psf(rng.standard_normal((1, P, Q))).astype(np.complex64)
+    src = torch.from_numpy(ph).cuda()
+    dst = torch.empty((1, P2, Q2 // 2 + 1), dtype=torch.complex64, device='cuda')
+    rc = lib.pfb_psfhat_regrid(_lib.PFB_F32, _dev.ptr(src), 1, nx, ny, P, Q, P2, Q2, _dev.ptr(dst), _dev.stream())
+    assert rc == _lib.PFB_OK, lib.pfb_last_error()
+    torch.cuda.synchronize()
+    x = rng.standard_normal((1, nx, ny))
+    ph64, ph2 = ph.astype(np.complex128), dst.cpu().numpy().astype(np.complex128)
+    want = ofc.psf_convolve_cube(*ofc.make_scratch(ph64, Q, x.shape, np.float64), ph64, Q, x).copy()
+    got = ofc.psf_convolve_cube(*ofc.make_scratch(ph2, Q2, x.shape, np.float64), ph2, Q2, x)
+    err = np.abs(got - want).max() / np.abs(want).max()
+    print(f"fp32 regrid (8,20800)->(8,21000): rel err {err:.3e}")
+    assert err < 1e-5
 
 
 def test_new_entry_points_reject_bad_arguments():
