@@ -264,6 +264,49 @@ int pfb_pcg_solve_bands(pfb_conv_plan* plan, int band0, int nb,
                         double tol, int maxit, int minit, int backtrack,
                         void* work, pfb_pcg_result* results, void* stream);
 
+/* ------------------------------------- band-coupled Hessian of the parametrised forward step
+ * pfb/workers/fwdbwd.py:246-252 with the parametrisations of pfb/utils/misc.py:1366-1423:
+ *
+ *   hesspsf(v) = 2 dhf(psf_convolve(df(v))) + sigmainv v,  df(v) = e * (L v),  dhf(w) = L^T (e * w),
+ *   e = exp(L x0) (mode 'exp') or 1 (mode 'id': e = NULL)
+ *              = L^T [ e * conv(e * (L v)) / wsum ] + sigmainv v      with wsum = 0.5 (the factor 2 is exact)
+ *
+ * i.e. a band mix, pfb_psfconv_apply(beam = e, wsum = 0.5, sigmainv = 0), and a second band mix that adds the
+ * Tikhonov term and, on request, emits the three fp64 sums of the PCG.
+ *
+ * pfb_bandmix_dots (fwdbwd.py:246-252, misc.py:1366-1423): out[k] = sum_l A[k, l] c[l] + sigmainv p[k] on (nband, npix)
+ * arrays, A a device nband x nband matrix, the sum in the arrays' dtype with l ascending (misc.py:1366-1375's order).
+ * dots3 (device, 3 doubles; needs p and the scratch ws of PFB_REDUCE_WS_DOUBLES): <p, out>, <r, out> (0 if r is
+ * NULL), <out, out>, fp64 in a fixed order.  With p, r and dots3 NULL and sigmainv = 0 it is the plain mix.  out may
+ * alias c (not p or r).  nband > 16: PFB_ERR_UNSUPPORTED (pfb_freqmul serves up to 64 bands). */
+int pfb_bandmix_dots(int dtype, const void* A, const void* c, int nband, size_t npix, double sigmainv,
+                     const void* p, const void* r, void* out, double* dots3, double* ws, void* stream);
+
+/* pfb_hessparam_apply (fwdbwd.py:246-252, misc.py:1366-1423): out = hesspsf(x) over ALL bands of the plan.  L, LH:
+ * device nband x nband arrays of the plan's real dtype (LH = L^T); e: NULL or an (nband, nx, ny) cube; x, out:
+ * (nband, nx, ny), distinct.  work: pfb_hessparam_work_bytes() bytes of device scratch, 256-byte aligned.
+ * nband > 16: PFB_ERR_UNSUPPORTED.  Asynchronous on `stream`.
+ * pfb_hessparam_apply_dots: the same with dots_out[0] = <dot_with, out>, [1] = <dot_with2, out> (0 if NULL),
+ * [2] = <out, out>; dot_with must be x itself (what the PCG and the power method form), else PFB_ERR_UNSUPPORTED. */
+size_t pfb_hessparam_work_bytes(const pfb_conv_plan* plan);
+int pfb_hessparam_apply(pfb_conv_plan* plan, const void* L, const void* LH, const void* e, double sigmainv,
+                        const void* x, void* out, void* work, void* stream);
+int pfb_hessparam_apply_dots(pfb_conv_plan* plan, const void* L, const void* LH, const void* e, double sigmainv,
+                             const void* x, void* out, const void* dot_with, const void* dot_with2,
+                             double* dots_out, void* work, void* stream);
+
+/* pfb_pcg_solve_param (fwdbwd.py:246-252 and :327-334, misc.py:1366-1423): pfb_pcg_solve's driver and kernels with
+ * A = hesspsf as the operator step: ONE system over all nb = plan nband bands (the mix couples every band, so there is
+ * no band range and no all-reduce hook: a band shard cannot apply it).  Per iteration: mix, the three convolution
+ * kernels, mix with the three sums, one scalar launch, the fused vector update.  b, x, r_out, mdiv, tol, maxit,
+ * minit, backtrack (0, 1, 2), result: as pfb_pcg_solve.  work: pfb_pcg_param_work_bytes() bytes (pfb_pcg_work_bytes
+ * plus one cube and the mix's partial sums).  Synchronises `stream`. */
+size_t pfb_pcg_param_work_bytes(const pfb_conv_plan* plan, int nb);
+int pfb_pcg_solve_param(pfb_conv_plan* plan, int nb, const void* L, const void* LH, const void* e,
+                        const void* b, void* x, void* r_out, double sigmainv, double mdiv,
+                        double tol, int maxit, int minit, int backtrack,
+                        void* work, pfb_pcg_result* result, void* stream);
+
 /* ------------------------------------------------ band-shard exchange (RCCL, called from C)
  * The reference sums the CG inner products over ALL bands inside one process
  * (pfb/opt/pcg.py:92-107 on (nband, nx, ny) arrays); with one process per GPU and the bands sharded

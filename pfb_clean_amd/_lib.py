@@ -70,6 +70,14 @@ SIGNATURES = {
     'pfb_pcg_bands_work_bytes': (_sz, [_vp, _i]),
     'pfb_pcg_solve_bands': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i,
                                  _vp, C.POINTER(PcgResult), _vp]),
+    # the band-coupled Hessian of the parametrised forward step (fwdbwd.py:246-252, misc.py:1366-1423)
+    'pfb_bandmix_dots': (_i, [_i, _vp, _vp, _i, _sz, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pfb_hessparam_work_bytes': (_sz, [_vp]),
+    'pfb_hessparam_apply': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pfb_hessparam_apply_dots': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pfb_pcg_param_work_bytes': (_sz, [_vp, _i]),
+    'pfb_pcg_solve_param': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _i, _i,
+                                 _vp, C.POINTER(PcgResult), _vp]),
     'pfb_comm_bind': (_i, [C.c_char_p]),
     'pfb_comm_unique_id': (_i, [_vp]),
     'pfb_comm_init': (_i, [_i, _i, _vp, C.POINTER(_vp)]),

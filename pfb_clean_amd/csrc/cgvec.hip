@@ -9,7 +9,8 @@
 // All inner products accumulate in fp64 (wave64 __shfl_down -> LDS -> one partial per
 // workgroup -> single-workgroup final sum in a fixed order), scalars stay in device
 // memory (alpha, beta are read by the kernels from there), the p.Ap product comes
-// fused out of the convolution epilogue (fftconv*.hip).
+// fused out of the convolution epilogue (fftconv*.hip) -- or, in the parametrised solve (pfb_pcg_solve_param), out of the
+// second band mix of hessparam.hip, the operator step Pcg::param_op at the driver's three call sites.
 // The 16-byte packs (V16, Pack, ld / st and their non-temporal forms), can_vec, emit_partials and k_final_sum live in
 // common.hpp, shared with the prox / primal-dual kernels of wavelet.hip.
 #include "conv_plan.hpp"
@@ -537,6 +538,11 @@ struct Pcg {
     double *S, *ws;
     T mdiv;
     std::vector<double> h;     // the host's copy of the state blocks
+    // the parametrised solve (pfb_pcg_solve_param): the operator step is param_op() instead of the convolution alone;
+    // `beam` is then e, and mixp holds the partials of the three dots that come out of the second band mix
+    const T *Lm = nullptr, *LHm = nullptr;
+    T* tmp = nullptr;
+    double* mixp = nullptr;
 
     Pcg(pfb_conv_plan* plan_, int band0_, int nb_, bool per_band_, const void* b_, void* x_, void* r_out_,
         const void* beam_, double wsum_, double sigmainv_, double mdiv_, double tol_, int maxit_, int minit_, void* work,
@@ -563,12 +569,19 @@ struct Pcg {
         nvs = vec ? ns / V16<T>::N : ns;
     }
 
+    // out = A(v) of the parametrised solve (hessparam.hip); `dots`: the partials of <v,out>, <rr,out>, <out,out> in mixp,
+    // *G of each
+    int param_op(const T* v, T* out, const T* rr, bool dots, int* G) {
+        return hessparam_apply_partials(plan, Lm, LHm, beam, sigmainv, v, out, rr, tmp, dots ? mixp : nullptr, G, st);
+    }
+
     // r = A(x0) - b ; y = M r ; p = -y ; the state blocks, on the device and in h          pcg.py:71-76
     int init() {
         int err;
         if ((err = sync.open()) != PFB_OK) return err;
         PFB_HIP_CHECK(hipMemsetAsync(S, 0, sizeof(double) * h.size(), st));
-        err = pfb_psfconv_apply(plan, band0, nb, x, beam, wsum, sigmainv, r, nullptr, nullptr, (void*)st);
+        err = Lm ? param_op(x, r, nullptr, false, nullptr)
+                 : pfb_psfconv_apply(plan, band0, nb, x, beam, wsum, sigmainv, r, nullptr, nullptr, (void*)st);
         if (err != PFB_OK) return err;
         const int gps = init_grid(nvs, nsys);
         if (vec)
@@ -642,15 +655,21 @@ struct Pcg {
         while (go) {
             const size_t off = (size_t)lo * ns;
             double* Sl = S + (size_t)lo * SB;
-            int bs, qs, bst;                       // where the convolution left system s's partials: k_iter_sums
-            err = psfconv_apply_partials(plan, band0 + lo * bps, nl * bps, p + off, beam ? beam + off : nullptr, wsum,
-                                         sigmainv, Ap + off, p + off, rc + off, per_band, &bs, &qs, &bst, (void*)st);
+            int bs, qs, bst;                       // where the operator step left system s's partials: k_iter_sums
+            const double* cp = plan->partials;
+            if (Lm) {                              // one system over all bands: the second mix's partials
+                err = param_op(p, Ap, rc, true, &bs);
+                qs = bs; bst = 0; cp = mixp;
+            } else
+                err = psfconv_apply_partials(plan, band0 + lo * bps, nl * bps, p + off, beam ? beam + off : nullptr,
+                                             wsum, sigmainv, Ap + off, p + off, rc + off, per_band, &bs, &qs, &bst,
+                                             (void*)st);
             if (err != PFB_OK) return err;
             // ONE scalar launch per iteration: the convolution's dots, the previous update's sums
             // (left pending while nobody can look at k / eps, i.e. while k < minit) and the
             // bookkeeping; with sharded bands the all-reduce of those 7 (or 4) scalars sits between
             // the sums and the bookkeeping -- one RCCL call per iteration instead of two.
-            hipLaunchKernelGGL(k_iter_sums, dim3(nl), dim3(256), 0, st, (const double*)plan->partials, bs, qs, bst,
+            hipLaunchKernelGGL(k_iter_sums, dim3(nl), dim3(256), 0, st, cp, bs, qs, bst,
                                (const double*)ws, gpl, pending_end ? 1 : 0, Sl, mdiv_d, predict, hook ? 0 : 1);
             // Behind a stop (the look-ahead's one speculative iteration) k_iter_sums writes nothing, so these exchanges
             // sum S_PAP .. S_ANY over the ranks a second time.  Every rank stops on the same reduced scalars, so all
@@ -729,7 +748,13 @@ struct Pcg {
         bool broke = false;
         while (h[S_ZERO] == 0.0 && (eps > tol || k < minit) && k < maxit) {
             // Ap = A(p); S_PAP = <p,Ap>                                                     pcg.py:89-91
-            err = pfb_psfconv_apply(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, S + S_PAP, (void*)st);
+            if (Lm) {
+                int Gm = 0;
+                if ((err = param_op(p, Ap, nullptr, true, &Gm)) == PFB_OK)
+                    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, (const double*)mixp, Gm, 1,
+                                       S + S_PAP);
+            } else
+                err = pfb_psfconv_apply(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, S + S_PAP, (void*)st);
             if (err != PFB_OK) return err;
             if ((err = sync.reduce(S + S_PAP, 1)) != PFB_OK) return err;
             hipLaunchKernelGGL(k_set_alpha, dim3(1), dim3(1), 0, st, S);
@@ -793,9 +818,15 @@ template <typename T>
 static int pcg_solve(pfb_conv_plan* plan, int band0, int nb, bool per_band, const void* b, void* x, void* r_out,
                      const void* beam, double wsum, double sigmainv, double mdiv, double tol, int maxit, int minit,
                      int backtrack, size_t lookahead_max, void* work, pfb_allreduce_fn allreduce, void* actx,
-                     pfb_pcg_result* res, hipStream_t st) {
+                     pfb_pcg_result* res, hipStream_t st, const void* L = nullptr, const void* LH = nullptr) {
     Pcg<T> s(plan, band0, nb, per_band, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit, work, allreduce,
              actx, st);
+    if (L) {       // the parametrised solve: one more cube and the mix's partials behind the cube solve's layout
+        char* w = (char*)work + 5 * vec_bytes(plan, nb) + state_bytes(1) + ws_bytes(1);
+        s.Lm = (const T*)L; s.LHm = (const T*)LH;
+        s.tmp = (T*)w;
+        s.mixp = (double*)(w + vec_bytes(plan, nb));
+    }
     PFB_REQUIRE(!allreduce || s.nsys == 1, PFB_ERR_INVALID, "pcg: an all-reduce hook needs the bands to be one system");
     memset(res, 0, sizeof(*res) * s.nsys);
     int err = s.init();
@@ -855,6 +886,29 @@ int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x
                                 backtrack, la, work, allreduce, allreduce_ctx, result, as_stream(stream));
     return pcg_solve<double>(plan, band0, nb, false, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
                              backtrack, la, work, allreduce, allreduce_ctx, result, as_stream(stream));
+}
+
+size_t pfb_pcg_param_work_bytes(const pfb_conv_plan* plan, int nb) {
+    if (!plan || nb != plan->nband) return 0;
+    return pfb_pcg_work_bytes(plan, nb) + vec_bytes(plan, nb) + sizeof(double) * 3 * MIX_MAX_GRID;
+}
+
+int pfb_pcg_solve_param(pfb_conv_plan* plan, int nb, const void* L, const void* LH, const void* e, const void* b,
+                        void* x, void* r_out, double sigmainv, double mdiv, double tol, int maxit, int minit,
+                        int backtrack, void* work, pfb_pcg_result* result, void* stream) {
+    PFB_REQUIRE(plan && L && LH && b && x && work && result, PFB_ERR_INVALID, "pcg_solve_param: null argument");
+    PFB_REQUIRE(nb == plan->nband, PFB_ERR_INVALID,
+                "pcg_solve_param: the band mix couples all %d bands of the plan, nb = %d", plan->nband, nb);
+    PFB_REQUIRE(nb <= 16, PFB_ERR_UNSUPPORTED, "pcg_solve_param: nband %d > 16", nb);
+    PFB_REQUIRE(backtrack >= 0 && backtrack <= 2, PFB_ERR_INVALID, "pcg_solve_param: backtrack must be 0, 1 or 2");
+    PFB_REQUIRE((reinterpret_cast<uintptr_t>(work) & 255u) == 0, PFB_ERR_INVALID,
+                "pcg_solve_param: work must be 256-byte aligned");
+    const size_t la = (size_t)4 << 20;
+    if (plan->dtype == PFB_F32)
+        return pcg_solve<float>(plan, 0, nb, false, b, x, r_out, e, 0.5, sigmainv, mdiv, tol, maxit, minit, backtrack, la,
+                                work, nullptr, nullptr, result, as_stream(stream), L, LH);
+    return pcg_solve<double>(plan, 0, nb, false, b, x, r_out, e, 0.5, sigmainv, mdiv, tol, maxit, minit, backtrack, la,
+                             work, nullptr, nullptr, result, as_stream(stream), L, LH);
 }
 
 size_t pfb_pcg_bands_work_bytes(const pfb_conv_plan* plan, int nb) {

@@ -62,4 +62,14 @@ __device__ __forceinline__ void iter_end_dev(double* S) {
     if (!((eps > S[S_TOL] || k < S[S_MINIT]) && k < S[S_MAXIT])) S[S_STOP] = 1.0;
 }
 
+// ---- the operator step of the parametrised solve (pfb_pcg_solve_param), hessparam.hip:
+// out = L^T [e conv(e (L x)) / 0.5] + sigmainv x over all the plan's bands (L, LH: device nband x nband; e: null or a
+// cube; tmp: one cube of scratch; x, out, tmp distinct).  partials non-null: the per-workgroup fp64 partials of <x,out>,
+// <r,out> (r may be null), <out,out>, quantity-major with *grid (<= MIX_MAX_GRID) per quantity -- what k_iter_sums
+// reads through (cp, bs = qs = *grid, bst = 0)
+constexpr int MIX_MAX_GRID = 1024;
+int hessparam_apply_partials(pfb_conv_plan* plan, const void* L, const void* LH, const void* e, double sigmainv,
+                             const void* x, void* out, const void* r, void* tmp, double* partials, int* grid,
+                             hipStream_t st);
+
 }  // namespace pfb

@@ -14,11 +14,19 @@ un-regularised convolution there, which no caller reads).
 HessianPsf is the object form used by the fused PCG (opt/pcg.py): it carries the plan
 and the operator parameters so that `pcg(A, b, ...)` can run the whole solve inside
 libpfb_hip.so when A is one of these.
+
+ParamHessian / hessian_psf are the band-coupled Hessian of the parametrised forward step
+(workers/fwdbwd.py:246-252):  2 dhf(psf_convolve(df(v))) + sigmainv v  with the closures of
+utils/misc.py::setup_parametrisation, as band mix -> convolution with the e sandwich -> band mix
+(csrc/hessparam.hip).
 """
+import functools
+
+import numpy as np
 import torch
 
-from .. import _dev
-from .psf import plan_for, PsfConvPlan
+from .. import _dev, _lib
+from .psf import plan_for, PsfConvPlan, psf_convolve_cube
 
 
 class HessianPsf:
@@ -137,3 +145,139 @@ def hessian_psf_cube(xpad, xhat, xout, beam, psfhat, lastsize, x,
     if x.ndim != 3:
         raise ValueError("hessian_psf_cube expects a (nband, nx, ny) cube")
     return _hess(psfhat, beam, lastsize, x, xout, sigmainv, wsum)
+
+
+# --------------------------------------------------- the parametrised forward step (workers/fwdbwd.py:246-252)
+MIX_MAXBAND = 16          # csrc/hessparam.hip: band counts the fused mix kernels are built for
+
+
+def _param_tags(dfunc, dhfunc):
+    """(mode, L) when dfunc / dhfunc are the tagged closures of ONE setup_parametrisation call, else None."""
+    try:
+        if dfunc.adjoint or not dhfunc.adjoint or dfunc.mode != dhfunc.mode or dfunc.L is not dhfunc.L:
+            return None
+        return dfunc.mode, dfunc.L
+    except AttributeError:
+        return None
+
+
+class ParamHessian:
+    """A(v) = 2 dhfunc(x0, psf_convolve_cube(dfunc(x0, v))) + sigmainv v over all bands of the plan
+    (workers/fwdbwd.py:246-252; dfunc, dhfunc from utils/misc.py::setup_parametrisation), evaluated as
+        L^T [ e * conv(e * (L v)) / 0.5 ] + sigmainv v,      e = exp(L x0) (mode 'exp') | 1 (mode 'id')
+    by pfb_hessparam_apply: two band mixes around the convolution, whose row kernels apply e and the exact factor 2.
+    e is built ONCE per x0 (the closures rebuild it on every call): the operator is bound to the value of x0 at
+    construction (x0 is copied); a new x0 needs a new ParamHessian, which is what pcg / power_method build per call from
+    the worker's partial.  psfhat: as HessianPsf, or a PsfConvPlan.
+    Callable on GPU tensors or numpy arrays of shape (nband, nx, ny); recognised by opt/pcg.py (pfb_pcg_solve_param),
+    opt/power_method.py and opt/primal_dual.py::ParamGradient.  More than 16 bands: `fused` is False and a call
+    evaluates the closure composition as it stands."""
+
+    def __init__(self, psfhat, nx, ny, lastsize, x0, sigmainv, dfunc, dhfunc):
+        tags = _param_tags(dfunc, dhfunc)
+        if tags is None:
+            raise TypeError("dfunc / dhfunc must be the pair one setup_parametrisation call returned")
+        self.mode, Lh = tags
+        self.plan = plan = psfhat if isinstance(psfhat, PsfConvPlan) else plan_for(psfhat, nx, ny, lastsize)
+        self.nx, self.ny = int(nx), int(ny)
+        self.nb = nb = plan.nband
+        self.sigmainv = float(sigmainv)
+        self.dfunc, self.dhfunc = dfunc, dhfunc
+        if Lh.shape != (nb, nb):
+            raise ValueError(f"the parametrisation has {Lh.shape[0]} bands, the plan {nb}")
+        # a private copy: e is formed from x0 once, so the operator is bound to the VALUE x0 has now, on the fused route
+        # and in the fallback alike, whatever the caller does to its array afterwards (the worker's xp lives on)
+        self.x0 = _dev.to_dev(x0, plan.rdtype).clone()
+        if tuple(self.x0.shape) != (nb, self.nx, self.ny):
+            raise ValueError(f"x0 has shape {tuple(self.x0.shape)}, operator is ({nb},{self.nx},{self.ny})")
+        self.fused = nb <= MIX_MAXBAND
+        self.e = None
+        if not self.fused:
+            return
+        self.L = _dev.to_dev(Lh, plan.rdtype)
+        self.LH = _dev.to_dev(np.ascontiguousarray(Lh.T), plan.rdtype)
+        if self.mode == 'exp':
+            from ..utils.misc import _freqmul
+            self.e = torch.exp(_freqmul(Lh, self.x0))           # the closures' own statement, once
+        if plan.embed is not None:
+            # embedded plan: the operator runs in the zero-padded domain with e ZERO outside the image ('id': a mask of
+            # ones inside).  There the convolution's output is exactly zero, and so are both mixes of zeros and the
+            # Tikhonov term of a zero-padded v: the same argument as opt/pcg.py::_Staged
+            self.e = plan._pad(torch.ones_like(self.x0) if self.e is None else self.e, nb)
+        nbytes = _lib.load().pfb_hessparam_work_bytes(plan.handle)
+        self._work = torch.empty(nbytes, dtype=torch.uint8, device=self.x0.device)
+
+    @property
+    def dtype(self):
+        return self.plan.rdtype
+
+    def __call__(self, x, out=None):
+        plan = self.plan
+        xd = _dev.to_dev(x, plan.rdtype if _dev.is_numpy(x) else None)
+        if xd.dtype != plan.rdtype:
+            raise TypeError(f"x is {xd.dtype}, operator is {plan.rdtype}")
+        if tuple(xd.shape) != (self.nb, self.nx, self.ny):
+            raise ValueError(f"x has shape {tuple(xd.shape)}, operator is ({self.nb},{self.nx},{self.ny})")
+        if not self.fused:           # the closure composition on the same plan: pfb_freqmul serves up to 64 bands
+            res = 2 * self.dhfunc(self.x0, plan.apply(self.dfunc(self.x0, xd))) + self.sigmainv * xd
+            if out is not None:
+                out.copy_(res)
+                res = out
+            return _dev.host_like(res, x)
+        xs = xd if plan.embed is None else plan._pad(xd, self.nb)
+        buf = _dev.out_buffer(out, xs, alias=False)
+        with plan.lock:
+            plan._enter_stream()
+            _lib.check(_lib.load().pfb_hessparam_apply(plan.handle, _dev.ptr(self.L), _dev.ptr(self.LH),
+                                                       _dev.ptr(self.e), self.sigmainv, _dev.ptr(xs), _dev.ptr(buf),
+                                                       _dev.ptr(self._work), _dev.stream()))
+        if plan.embed is not None:
+            buf = buf[:, :self.nx, :self.ny]
+            if out is not None:
+                out.copy_(buf)
+                buf = out
+            else:
+                buf = buf.contiguous()
+        elif out is not None and buf is not out:
+            out.copy_(buf)
+            buf = out
+        return _dev.host_like(buf, x)
+
+
+def hessian_psf(psfo, x0, sigmainv, df, dhf, v, _nofuse=False):
+    """workers/fwdbwd.py:246-252 with the worker's signature (its unused `dx0 = df(x0)` is not evaluated):
+        2 * dhf(psfo(df(v))) + v * sigmainv
+    so that the worker's `partial(hessian_psf, psf_convolve, xp, sigmainv, df, dhf)` can import it unchanged.  Called
+    directly it evaluates exactly that composition with whatever callables it is given; pcg and power_method look at
+    the partial and, when psfo is a partial of this package's psf_convolve_cube and df / dhf are partials of the
+    tagged closures of setup_parametrisation over the same x0, run the fused ParamHessian instead (as_param_hessian).
+    _nofuse=True (keyword of the partial) keeps the generic path."""
+    # _nofuse is deliberately unused here: only as_param_hessian reads it, from the partial's keywords
+    return 2 * dhf(psfo(df(v))) + v * sigmainv
+
+
+def as_param_hessian(A, b):
+    """The ParamHessian a `partial(hessian_psf, psfo, x0, sigmainv, df, dhf)` stands for, or None: psfo must be a
+    partial of this package's psf_convolve_cube binding (xpad, xhat, xout, psfhat, lastsize), df / dhf partials of the
+    two tagged closures of one setup_parametrisation call, both over the very x0 the partial carries, and x0 shaped
+    like b.  Anything else -- a foreign convolution, a wrapped closure, another x0 -- is not recognised."""
+    if not (isinstance(A, functools.partial) and A.func is hessian_psf and len(A.args) == 5):
+        return None
+    if any(A.keywords.values()) or set(A.keywords) - {'_nofuse'}:
+        return None
+    psfo, x0, sigmainv, df, dhf = A.args
+    if not (isinstance(psfo, functools.partial) and psfo.func is psf_convolve_cube and len(psfo.args) == 5
+            and not psfo.keywords):
+        return None
+    for f in (df, dhf):
+        if not (isinstance(f, functools.partial) and len(f.args) == 1 and not f.keywords and f.args[0] is x0):
+            return None
+    if _param_tags(df.func, dhf.func) is None:
+        return None
+    psfhat, lastsize = psfo.args[3], psfo.args[4]
+    if getattr(psfhat, 'ndim', 0) != 3 or tuple(getattr(x0, 'shape', ())) != tuple(b.shape) or b.ndim != 3:
+        return None
+    if psfhat.shape[0] != b.shape[0] or df.func.L.shape[0] != b.shape[0]:
+        return None
+    nx, ny = b.shape[-2:]
+    return ParamHessian(psfhat, nx, ny, lastsize, x0, float(sigmainv), df.func, dhf.func)

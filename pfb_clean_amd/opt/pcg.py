@@ -17,6 +17,10 @@ break-before-increment on an all-zero direction, "Initial residual is zero" retu
    build -- fluxmop.py:160-174, pcg.py:276-284) and `M` is None or a DivPrecond, the
    whole solve runs inside libpfb_hip.so (pfb_pcg_solve): 3 convolution kernels + 3
    fused vector kernels per iteration, device-resident scalars.
+ * FUSED, band-coupled: when `A` is a ParamHessian of at most 16 bands (or the fwdbwd worker's
+   `partial(hessian_psf, psf_convolve, xp, sigmainv, df, dhf)` built from this package's pieces,
+   fwdbwd.py:318) the same driver runs with the mix -> convolution -> mix operator step
+   (pfb_pcg_solve_param): one system over all bands.
  * GENERIC: any Python callables A, M.  Vector arithmetic and reductions still run in
    the HIP kernels (pfb_dot, pfb_axpby, pfb_norm_diff_sums, pfb_any_nonzero); A and M
    are called with the same array kind (numpy / tensor) the caller passed for `b`.
@@ -32,7 +36,7 @@ import torch
 
 from .. import _lib, _dev
 from ..operators import hessian as _hess
-from ..operators.hessian import HessianPsf
+from ..operators.hessian import HessianPsf, ParamHessian
 
 
 class DivPrecond:
@@ -82,6 +86,11 @@ def _as_hessian(A, b):
     """Recognise the operator objects / partials the fused driver can run."""
     if isinstance(A, HessianPsf):
         return A
+    if isinstance(A, ParamHessian):
+        return A if A.fused and tuple(b.shape) == (A.nb, A.nx, A.ny) else None
+    if isinstance(A, functools.partial) and A.func is _hess.hessian_psf:
+        H = _hess.as_param_hessian(A, b)        # None as well with _nofuse=True among the partial's keywords
+        return H if H is not None and H.fused else None
     if isinstance(A, functools.partial) and not A.keywords.get('_nofuse', False):
         kw = dict(A.keywords)
         args = A.args
@@ -118,15 +127,16 @@ class _Work:
     _cache = {}
 
     @classmethod
-    def get(cls, plan, nb, bands=False):
+    def get(cls, plan, nb, bands=False, param=False):
         # per host thread: the reference may drive per-band solves from several dask threads
         # (pcg.py:346-356).  Solves on ONE plan are serialised by plan.lock (the plan's spectrum workspace and
         # dot partials are single-owner); the vectors of a solve still live in a per-thread scratch so that a
         # thread's result buffers are not overwritten by the next thread's solve.  bands: the batched solver's
-        # layout (pfb_pcg_bands_work_bytes)
-        key = (id(plan), nb, bands, _dev.stream(), threading.get_ident())
+        # layout (pfb_pcg_bands_work_bytes); param: the parametrised solve's (pfb_pcg_param_work_bytes)
+        key = (id(plan), nb, bands, param, _dev.stream(), threading.get_ident())
         lib = _lib.load()
-        nbytes = (lib.pfb_pcg_bands_work_bytes if bands else lib.pfb_pcg_work_bytes)(plan.handle, nb)
+        nbytes = (lib.pfb_pcg_param_work_bytes if param else
+                  lib.pfb_pcg_bands_work_bytes if bands else lib.pfb_pcg_work_bytes)(plan.handle, nb)
         w = cls._cache.get(key)
         if w is None or w.numel() != nbytes or w.device != plan.device:
             if len(cls._cache) > 16:
@@ -150,7 +160,15 @@ class _Staged:
         if b3.dtype != plan.rdtype:
             raise TypeError(f"b is {b3.dtype}, operator is {plan.rdtype}")
         x = torch.zeros_like(b3) if x0 is None else x0.contiguous().clone()
-        beam = A.beam
+        param = isinstance(A, ParamHessian)
+        beam = A.e if param else A.beam         # a ParamHessian's e is padded already
+        if param:
+            self.work = _Work.get(plan, nb, param=True)
+            if plan.embed is not None:          # the same argument as below, with e in the beam's place
+                b3, x = plan._pad(b3, nb), plan._pad(x, nb)
+            self.b, self.x, self.beam = b3, x, beam
+            self.r = torch.empty_like(b3) if return_resid else None
+            return
         if plan.embed is not None:
             # Embedded plan (arbitrary size on the power-of-two kernels, operators/psf.py): solve in the
             # zero-padded domain with a beam that is ZERO outside the image.  There A' x' = sigmainv x',
@@ -183,6 +201,18 @@ def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack
     (pfb_clean_amd.dist.AllReduceHook, RCCL)."""
     lib = _lib.load()
     plan = A.plan
+    if isinstance(A, ParamHessian):
+        if distributed:
+            raise ValueError("a ParamHessian couples every band: it cannot be solved on a band shard")
+        s = _Staged(A, b, x0, return_resid)
+        res = _lib.PcgResult()
+        with plan.lock:
+            plan._enter_stream()
+            _lib.check(lib.pfb_pcg_solve_param(plan.handle, s.nb, _dev.ptr(A.L), _dev.ptr(A.LH), _dev.ptr(s.beam),
+                                               _dev.ptr(s.b), _dev.ptr(s.x), _dev.ptr(s.r), A.sigmainv, float(mdiv),
+                                               float(tol), int(maxit), int(minit), _backtrack_mode(backtrack),
+                                               _dev.ptr(s.work), C.byref(res), _dev.stream()))
+        return s.result() + (res,)
     squeeze = b.ndim == 2
     s = _Staged(A, b[None] if squeeze else b, x0[None] if squeeze and x0 is not None else x0, return_resid)
     res = _lib.PcgResult()

@@ -3,7 +3,10 @@ Power method for the spectral norm of the (PSF-approximated) Hessian -- drop-in 
 pfb/opt/power_method.py:11-49.  One matvec per iteration and ONE host look at the three inner products
 <b,b>, <bp,b>, <bp,bp> (they are left in device scalars and read back together); when `A` is this package's
 HessianPsf (or the functools.partial of hessian_psf_cube / _hessian_psf_slice the workers build) <bp,b> and
-<b,b> come fused out of the convolution's epilogue (pfb_psfconv_apply_dots) instead of two more passes.
+<b,b> come fused out of the convolution's epilogue (pfb_psfconv_apply_dots) instead of two more passes; for a
+ParamHessian (or the fwdbwd worker's partial of hessian_psf, fwdbwd.py:318-324) out of its second band mix
+(pfb_hessparam_apply_dots); on an embedded (non-power-of-two) plan the recognised ParamHessian is called as a whole --
+its fused apply, pfb_hessparam_apply, in the padded domain -- and the three products are separate passes.
 `A` may return an aliased buffer (it is normalised into `bp` straight away, power_method.py:29-36).  With b0=None the start vector is drawn with numpy's global
 RNG exactly like the reference (np.random.randn, fp64); `dtype` (numpy or torch dtype,
 an extension) casts it and, when a torch dtype, keeps the iteration on device tensors.
@@ -46,16 +49,24 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
     bd = _dev.to_dev(b0).clone()
     out = _dev.scratch()[1]
 
-    # the fused path: A as the library's own operator on device tensors
-    H = None
+    # the fused path: A as the library's own operator on device tensors (HP: the band-coupled ParamHessian)
+    H = HP = None
     if not _dev.is_numpy(b0):
         from .pcg import _as_hessian
+        from ..operators.hessian import ParamHessian
         H = _as_hessian(A, bd)
+        if isinstance(H, ParamHessian):
+            if H.plan.rdtype == bd.dtype:
+                if H.plan.embed is None:
+                    HP = H
+                else:
+                    A = H         # embedded plan: the operator as a whole (its fused apply pads and crops), plain dots
+            H = None
         if H is not None and (H.plan.rdtype != bd.dtype or H.plan.embed is not None or
                               tuple(bd.shape[-2:]) != (H.nx, H.ny) or (bd.ndim == 3 and bd.shape[0] != H.nb)
                               or (bd.ndim == 2 and H.nb != 1)):
             H = None
-    bout = torch.empty_like(bd) if H is not None else None
+    bout = torch.empty_like(bd) if H is not None or HP is not None else None
 
     _dev.axpby(0.0, bd, 1.0 / math.sqrt(allsum([_dev.dot(bd, bd)])[0]), bd)
     bp = bd.clone()
@@ -70,6 +81,16 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
                     H.plan.handle, H.band0, H.nb, _dev.ptr(b3), _dev.ptr(H.beam),
                     H.wsum if H.wsum is not None else 0.0, H.sigmainv, _dev.ptr(bout), _dev.ptr(b3), None,
                     _dev.ptr(out), _dev.stream()))                 # out[0] = <bp, b>, out[2] = <b, b>
+            b = bout
+            _dev.dot_into(bp, bp, out, 1)
+            pb, pp, bb = allsum(out[:3].tolist())
+        elif HP is not None:
+            with HP.plan.lock:
+                HP.plan._enter_stream()
+                _lib.check(lib.pfb_hessparam_apply_dots(
+                    HP.plan.handle, _dev.ptr(HP.L), _dev.ptr(HP.LH), _dev.ptr(HP.e), HP.sigmainv, _dev.ptr(bp),
+                    _dev.ptr(bout), _dev.ptr(bp), None, _dev.ptr(out), _dev.ptr(HP._work),
+                    _dev.stream()))                                # out[0] = <bp, b>, out[2] = <b, b>
             b = bout
             _dev.dot_into(bp, bp, out, 1)
             pb, pp, bb = allsum(out[:3].tolist())

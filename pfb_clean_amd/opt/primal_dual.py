@@ -55,6 +55,21 @@ class PsfGradient:
         return _dev.host_like(self.conv(_dev.to_dev(x, self.plan.rdtype)) - self.data, x)
 
 
+class ParamGradient(PsfGradient):
+    """grad(x) = H(x) - H(data) = H(x - data) for a ParamHessian H: the backward step's
+    `grad21 = lambda v: hesspsf(v - data)` (workers/fwdbwd.py:366) in PsfGradient's form -- conv(x) is the fused
+    operator, H(data) is formed once -- so that primal_dual_optimised subtracts inside its primal update."""
+
+    def __init__(self, H, data):
+        self.H = H
+        self.plan = H.plan
+        self.data = H(_dev.to_dev(data, H.plan.rdtype)).clone()
+        self._out = torch.empty_like(self.data)
+
+    def conv(self, x):
+        return self.H(x, out=self._out)
+
+
 def primal_dual_optimised(x, v, lam, psiH, psi, L, prox, l1weight, reweighter, grad,
                           nu=1.0, sigma=None, mask=None, tol=1e-5, maxit=1000, positivity=1,
                           report_freq=10, gamma=1.0, verbosity=1, maxreweight=50, group=None):

@@ -138,7 +138,8 @@ def setup_parametrisation(mode='id', minval=1e-5, sigma=1.0, freq=None, lscale=1
     (func, finv, dfunc, dhfunc) working on GPU tensors or numpy cubes; the nband x nband factor is
     built on the host (numpy Cholesky), every cube-sized operation is one pfb_freqmul launch (the
     exp / product factors of mode='exp' fused into it).  finv applies L^-1 through the same kernel
-    (the reference's scipy.solve_triangular on the cube)."""
+    (the reference's scipy.solve_triangular on the cube).  dfunc and dhfunc carry `mode`, the host factor `L` and
+    `adjoint` (False / True) as attributes."""
     nu = np.asarray(freq, dtype=np.float64) / np.mean(freq)
     nband = nu.size
     K = sigma ** 2 * np.exp(-(nu[:, None] - nu[None, :]) ** 2 / (2 * lscale ** 2))
@@ -175,6 +176,9 @@ def setup_parametrisation(mode='id', minval=1e-5, sigma=1.0, freq=None, lscale=1
             return _dev.host_like(_freqmul(LH, v, pre=e), v)         # L^T (v * exp(L x0))
     else:
         raise ValueError(f"Unknown mode - {mode}")
+    # what operators/hessian.py::ParamHessian (and through it the fused PCG) needs to know about the two closures
+    dfunc.mode, dfunc.L, dfunc.adjoint = mode, L, False
+    dhfunc.mode, dhfunc.L, dhfunc.adjoint = mode, L, True
     return func, finv, dfunc, dhfunc
 
 
