@@ -16,6 +16,13 @@
 #include "common.hpp"
 #include "fft_generic.hpp"
 
+// Where a row-inverse launch left its fused-dot partials in plan->partials: `slots` per quantity; band bl's `band_slots`
+// partials of quantity q start at q * q_stride + bl * band_stride (band_slots 0: the launch summed across bands -- the
+// whole-cube persistent kernel).  Read by k_sum_partials* and psfconv_apply_partials.
+struct pfb_partial_layout {
+    int slots, band_slots, q_stride, band_stride;
+};
+
 struct pfb_conv_plan {
     int nx, ny, P, Q, M;       // M = Q/2
     int nband, dtype;
@@ -37,10 +44,7 @@ struct pfb_conv_plan {
     size_t workspace_bytes;
     int have_psf;
     int partials_per_band;     // fused-dot partial sums emitted per band by row_inv
-    int last_npartials;        // slots per quantity the LAST row-inverse launch wrote (k_sum_partials reads these)
-    int last_band_slots;       // per band: band bl's `last_band_slots` partials of quantity q start at
-    int last_q_stride;         //   q * last_q_stride + bl * last_band_stride
-    int last_band_stride;      // (last_band_slots 0: the launch summed across bands -- the whole-cube persistent kernel)
+    pfb_partial_layout last;   // of the LAST row-inverse launch (apply_common sets the default, the pow2 launcher its own)
     void* fast_tables;         // pow2 path: per-pass twiddle tables (fftconv_pow2.hip)
     // optional per-stage timing (bench.py roofline): 4 events per apply, up to PROF_MAX applies
     int prof_on, prof_n, prof_tick;   // prof_on = sampling period (every prof_on-th apply is timed)
@@ -69,4 +73,16 @@ inline void prof_mark(pfb_conv_plan* p, hipStream_t st, int k) {
 int psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                            double wsum, double sigmainv, void* out, const void* dot_with,
                            const void* dot_with2, bool per_band, int* bs, int* qs, int* bst, void* stream);
+// fftconv_pow2.hip: the fast path's entry points
+bool pow2_supported(const pfb_conv_plan* p);
+int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
+               double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
+               bool per_band, hipStream_t st);
+int pow2_prepare(pfb_conv_plan* p);
+void pow2_release(pfb_conv_plan* p);
+int pow2_rows_per_wg(const pfb_conv_plan* p);
+int pow2_nblocks(const pfb_conv_plan* p);
+int pow2_nvb(const pfb_conv_plan* p);
+int pow2_set_psfhat(pfb_conv_plan* p, const void* psfhat, hipStream_t st);
+int pow2_set_psf(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStream_t st);
 }  // namespace pfb

@@ -32,19 +32,6 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// fast-path hooks (fftconv_pow2.hip)
-bool pow2_supported(const pfb_conv_plan* p);
-int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
-               double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
-               bool per_band, hipStream_t st);
-int pow2_prepare(pfb_conv_plan* p);
-void pow2_release(pfb_conv_plan* p);
-int pow2_rows_per_wg(const pfb_conv_plan* p);
-int pow2_nblocks(const pfb_conv_plan* p);
-int pow2_nvb(const pfb_conv_plan* p);
-int pow2_set_psfhat(pfb_conv_plan* p, const void* psfhat, hipStream_t st);
-int pow2_set_psf(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStream_t st);
-
 // the coverage layouts (VB = 1): T[band][v][i], psf_l[band][v][u]
 struct ConvDims {
     int nx, ny, P, Q, M;
@@ -637,10 +624,8 @@ static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, cons
     double scale = 1.0 / ((double)p->P * (double)p->Q);
     if (wsum > 0) scale /= wsum;
     int rc;
-    p->last_npartials = p->partials_per_band * nb;        // the persistent row-inverse kernel lowers it
-    p->last_band_slots = p->partials_per_band;            // slot k of the plain / coverage kernels is band k / ppb's
-    p->last_q_stride = p->partials_per_band * nb;
-    p->last_band_stride = p->partials_per_band;
+    // slot k of the plain / coverage kernels is band k / ppb's; the persistent row-inverse kernel writes fewer
+    p->last = {p->partials_per_band * nb, p->partials_per_band, p->partials_per_band * nb, p->partials_per_band};
     if (p->fast)
         rc = pow2_apply(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
     else {
@@ -664,12 +649,12 @@ static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, cons
     }
     if (rc != PFB_OK) return rc;
     if (dot_with && ndots > 0 && per_band) {
-        hipLaunchKernelGGL(k_sum_partials_bands, dim3(nb), dim3(256), 0, st, p->partials, p->last_band_slots,
-                           p->last_q_stride, p->last_band_stride, dots_out);
+        hipLaunchKernelGGL(k_sum_partials_bands, dim3(nb), dim3(256), 0, st, p->partials, p->last.band_slots,
+                           p->last.q_stride, p->last.band_stride, dots_out);
         PFB_HIP_CHECK(hipGetLastError());
     } else if (dot_with && ndots > 0) {    // ndots == 0: the caller sums p->partials itself (PCG driver)
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, p->partials,
-                           p->last_npartials, ndots, dots_out);
+                           p->last.slots, ndots, dots_out);
         PFB_HIP_CHECK(hipGetLastError());
     }
     return PFB_OK;
@@ -700,7 +685,7 @@ int pfb_psfconv_apply_dots_bands(pfb_conv_plan* p, int band0, int nb, const void
 // internal (cgvec.hip): the convolution with its three fused dots left as per-workgroup partials in
 // plan->partials -- the PCG driver sums them in the same launch that does its per-iteration scalar
 // bookkeeping.  per_band: every partial belongs to ONE band (a system per band); otherwise the range is one system and
-// all plan->last_npartials slots of a quantity are its partials
+// all plan->last.slots slots of a quantity are its partials
 int pfb::psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                                 double wsum, double sigmainv, void* out, const void* dot_with,
                                 const void* dot_with2, bool per_band, int* bs, int* qs, int* bst, void* stream) {
@@ -708,8 +693,8 @@ int pfb::psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void*
     const int rc = apply_common(p, band0, nb, x, beam, wsum, sigmainv, out, dot_with, dot_with2, nullptr, 0, stream,
                                 per_band);
     if (rc != PFB_OK) return rc;
-    *bs = per_band ? p->last_band_slots : p->last_npartials;
-    *qs = per_band ? p->last_q_stride : p->last_npartials;
-    *bst = per_band ? p->last_band_stride : 0;
+    *bs = per_band ? p->last.band_slots : p->last.slots;
+    *qs = per_band ? p->last.q_stride : p->last.slots;
+    *bst = per_band ? p->last.band_stride : 0;
     return PFB_OK;
 }

@@ -29,13 +29,17 @@
 //                   store in place; the two columns share barriers (RegFft NV = 2)
 //   k_row_inv_pow2  mirror image of row_fwd with the fused epilogue
 //                   (1/(PQ wsum), beam, + sigmainv x, <dot_with, out> partials)
+// Host side (below the kernels): which variant serves a class and what it needs is stated once -- ColCfg / ColKernels,
+// RowFwdK, RowInvK -- and read by the launchers, the LDS-attribute set-up and the table set-up.
 #include "conv_plan.hpp"
 #include "fft_pow2.hpp"
 #include <vector>
 #include <cstdlib>
+#include <type_traits>
 
-// This file is compiled into TWO objects (csrc/Makefile): PFB_POW2_PART=1 -- everything but the column
-// kernels -- and PFB_POW2_PART=2 -- the column kernels and their launcher, built with LLVM's max-ILP machine
+// This file is compiled into TWO objects (csrc/Makefile, FLAGS_fftconv_pow2 / FLAGS_fftconv_pow2_col): PFB_POW2_PART=1
+// -- everything but the column kernels -- and PFB_POW2_PART=2 -- the column kernels with their host description, table
+// set-up and launchers (pow2_col_*), built with LLVM's max-ILP machine
 // scheduler (-mllvm -amdgpu-sched-strategy=max-ilp).  Their occupancy is pinned by the launch bounds, so
 // the default occupancy-driven scheduling only costs them instruction-level parallelism: col 0.977 ->
 // 0.904 ms fp32 and 1.152 -> 1.078 ms fp64 at 4096^2; the row kernels LOSE 5-25 % under the same switch,
@@ -98,17 +102,18 @@ template <typename T, int L, bool INVK> struct RowCfg {
     static constexpr bool WAVE = TPB <= 64;
     static constexpr int GMAX = INVK ? 4 : 8;
 };
+constexpr int LDS_MAX = 160 * 1024;       // dynamic LDS a workgroup may ask for (hipFuncAttributeMaxDynamicSharedMemorySize)
+constexpr int LDS_BUDGET = 152 * 1024;    // what the row tiles are sized to
+
 // inverse row kernel: second exchange buffer (one barrier per exchange instead of two)
 // whenever 2 x G rows fit the LDS
 template <typename T, int L> struct InvDb {
     using C = RowCfg<T, L, true>;
     static constexpr int G = row_groups<T, L, C::E, C::GMAX>();
     static constexpr int STRIDE = RegFft<T, L, C::E>::LDS_ELEMS + 4;
-    static constexpr bool ON = (size_t)(2 * G * STRIDE + L) * sizeof(cplx<T>) + 384 <= (size_t)152 * 1024;
+    static constexpr bool ON = (size_t)(2 * G * STRIDE + L) * sizeof(cplx<T>) + 384 <= (size_t)LDS_BUDGET;
     static constexpr int OFF = ON ? G * STRIDE : 0;
 };
-
-constexpr int LDS_BUDGET = 152 * 1024;
 
 // elements per thread of the column transform: 8, but 16 for fp64 at H = 8192 -- with E = 8 that
 // size needs a 1024-thread workgroup (128-VGPR cap) and spilled ~200 bytes per lane: 4.32 -> 3.29 ms
@@ -1037,7 +1042,7 @@ struct FwdP {
     static constexpr int KR = (32 * NVB * BSTEP) / (2 * L);
     // fp64 rows of 4096 points as 2-row 512-thread persistent tiles: 1.87 against 1.21 ms per 2 x 8192^2 for the plain
     // kernel (profiles/r03_i_*; the same verdict as at 2048 points in round 1): not used
-    static constexpr bool OK = E == 16 && LDS <= (size_t)160 * 1024 && !(BIG && sizeof(T) == 8) &&
+    static constexpr bool OK = E == 16 && LDS <= (size_t)LDS_MAX && !(BIG && sizeof(T) == 8) &&
                                (!SMT || (EOK == 16 && 32 * TPR == 2 * L && KR * 2 * L == 32 * NVB * BSTEP && NTM >= TPR));
     // w_M^(t + TPR j) from the table in the LDS
     __device__ __forceinline__ static cplx<T> tw_row(const cplx<T>* ltm, int t, int j) {
@@ -1492,7 +1497,7 @@ struct InvP {
     static constexpr bool BARUP = NXT || sizeof(T) == 8;
     static constexpr int NTM = SMT ? F::TPB : L;
     static constexpr size_t LDS = 384 + sizeof(cplx<T>) * ((size_t)PTWP + NTM + (size_t)G * STRIDE + (PARK ? (size_t)G * L : 0));
-    static constexpr bool OK = LDS <= (size_t)160 * 1024 && !C::WAVE && (!SMT || 32 * F::TPB == 2 * L) &&
+    static constexpr bool OK = LDS <= (size_t)LDS_MAX && !C::WAVE && (!SMT || 32 * F::TPB == 2 * L) &&
                                (sizeof(T) == 4 ? (NT == 1024 && G >= 4 && G <= 16) : (NT == 512 && (G == 2 || G == 4) && L >= 1024));
     __device__ __forceinline__ static cplx<T> tw_row(const cplx<T>* ltm, int t, int j) {     // w_M^(t + TPB j)
         if constexpr (SMT) return j == 0 ? ltm[t] : ltm[t] * root32<T>(j);
@@ -1941,10 +1946,65 @@ int pow2_set_stamp(unsigned long long* buf) {
 #endif
 #endif
 
-// size switch helper
-#define PFB_POW2_SIZES(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
-
 // -------------------------------------------------------------------- host side
+// Every fact about which kernel variant serves a size / type class and what it needs is stated ONCE below: ColCfg /
+// ColKernels for the column pass (nx), RowFwdK / RowInvK for the row passes (ny / 2).  The launchers, the LDS-attribute
+// set-up and the table set-up all read those; a new or retuned variant is entered there and nowhere else.
+
+// f(std::integral_constant<int, N>) for the transform length N == n; false if the fast path has no such length
+template <typename Fn>
+static inline bool for_pow2_size(int n, Fn&& f) {
+    switch (n) {
+#define X(NN) case NN: f(std::integral_constant<int, NN>{}); return true;
+        X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
+#undef X
+        default: return false;
+    }
+}
+
+// the two-level column kernel k_col_pow2x and its class-major psf_l (the `four` of psf_off) serve nx >= 8192
+constexpr bool col_two_level(int nx) { return nx >= 8192; }
+
+enum Tab {                     // device tables owned by the plan
+    PTW_COL,                   // pass table of the one-level column transform (plain kernel, PSFHAT producer)
+    PTWC_COL,                  // compact (w only) table of the persistent / two-level column kernel, copied to LDS (ColCfg)
+    PTW_ROW,                   // plain forward row kernel
+    PTWC_ROW_FWD,              // compact pass table of the persistent forward row kernel (its own E)
+    PTWC_ROW_INV,              // inverse row kernel: COMPACT table, copied to LDS
+    PTWC_ROW_INV_P,            // the persistent inverse kernel's, where its elements per thread differ (InvPE); else an ALIAS of PTWC_ROW_INV
+    TW_M,                      // exp(-2 pi i n / M), n < L
+    NTAB
+};
+struct FastTables {            // stored behind p->fast_tables
+    void* tab[NTAB];
+    int num_cu;
+};
+// the column object's entry points (defined under PFB_POW2_COL below)
+int pow2_col_prepare(pfb_conv_plan* p, FastTables* ft);
+int pow2_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st);
+int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st);
+
+// n table entries written by fill(cplx<T>*) -> a new device array
+template <typename T, typename Fill>
+static int upload_table(void** dev, int n, Fill&& fill) {
+    std::vector<cplx<T>> h(n > 0 ? n : 1);
+    if (n > 0) fill(h.data());
+    PFB_HIP_CHECK(hipMalloc(dev, sizeof(cplx<T>) * h.size()));
+    PFB_HIP_CHECK(hipMemcpy(*dev, h.data(), sizeof(cplx<T>) * h.size(), hipMemcpyHostToDevice));
+    return PFB_OK;
+}
+template <typename T, int N, int E>
+static int upload_ptw(void** dev) { return upload_table<T>(dev, ptw_total<N, E>(), fill_ptw<T, N, E>); }
+template <typename T, int N, int E>
+static int upload_ptwc(void** dev) { return upload_table<T>(dev, ptw_total<N, E>() / 4, fill_ptw_compact<T, N, E>); }
+
+template <typename K>
+static int set_lds_max(K* kernel) {
+    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    return PFB_OK;
+}
+
+#if PFB_POW2_COL
 // Grid of the persistent column kernel k_col_pow2p: not all `maxgrid` resident workgroups but as many as give every one of them the same number
 // of trips.  `need` is rarely a multiple of the CU count (a band is 2^k + 1 column blocks), and a last trip with a handful
 // of workgroups runs at their latency while the rest of the chip idles -- the same work on slightly fewer workgroups is
@@ -1957,128 +2017,235 @@ static inline int balanced_grid(int need, int maxgrid) {
     return (need + trips - 1) / trips;
 }
 
-struct FastTables {            // device tables owned by the plan (stored behind p->fast_tables)
-    void* ptw_col;
-    void* ptwc_col;            // compact (w only) table of the column transform, copied to LDS
-    void* ptw_row;             // forward row kernel (E = 16)
-    void* ptw_row_inv;         // inverse row kernel (E = 8): COMPACT table, copied to LDS
-    void* ptw_row_inv_p;       // the persistent inverse kernel's, where its elements per thread differ (InvPE); else == ptw_row_inv
-    void* twM;                 // exp(-2 pi i n / M), n < L
-    void* ptwc_row_fwd;        // compact pass table of the persistent forward row kernel (its own E)
-    int num_cu;
-    void* ptwc_col_x;          // compact pass table of its HS = nx / 2 point sub-transform
-    int col_x;                 // two-level column kernel k_col_pow2x + class-major psf_l (nx = 8192)
+// The column pass of class (T, H = nx): which kernel serves it and what that kernel needs.
+enum class ColKind { Plain, Persistent, TwoLevel };
+// workgroups per CU of the persistent and the two-level kernel: one resident set, 8 waves per CU at 256 VGPRs
+constexpr int col_resident(int threads) { return (8 * 64) / threads > 0 ? (8 * 64) / threads : 1; }
+template <typename T, int H> struct ColCfg {
+    static constexpr int NVB = FastCfg<T>::NVB;
+    // the one-level transform (plain and persistent kernel, PSFHAT producer)
+    static constexpr int E1 = ecol<T, H>();
+    using F1 = RegFft<T, H, E1>;
+    static constexpr int GC1 = col_groups<H, E1>(), NT1 = GC1 * F1::TPB;
+    static constexpr size_t XB1 = sizeof(cplx<T>) * (size_t)GC1 * NVB * F1::LDS_ELEMS;   // one set of exchange buffers
+    static constexpr size_t TAB1 = sizeof(cplx<T>) * (size_t)((F1::PTWC + 1) & ~1);       // the compact table in the LDS
+    // persistent kernel: needs its LDS (exchange buffers + twiddle table) to fit; measured faster
+    // for H >= 2048 (fp32, packed arithmetic: 1.07 vs 1.32 ms at 4096^2 x 8, 0.276 vs 0.347 at 2048^2 x 8;
+    // fp64: 1.19 vs 1.41 and 0.266 vs 0.333 at x 4; a tie or a small loss at H <= 1024)
+    static constexpr ColKind KIND = col_two_level(H) ? ColKind::TwoLevel
+                                  : H >= 2048 && XB1 + TAB1 <= (size_t)LDS_MAX ? ColKind::Persistent : ColKind::Plain;
+    // second exchange buffer set when ONE workgroup per CU is resident anyway and it fits: col 0.98 ->
+    // 0.96 ms at 8 x 4096^2 fp32, 1.16 -> 1.10 ms at 4 x 4096^2 fp64; with two workgroups per CU (H = 2048)
+    // the doubled LDS costs residency (fp64 0.245 -> 0.304 ms)
+    static constexpr bool DB = KIND == ColKind::Persistent && col_resident(NT1) == 1 && 2 * XB1 + TAB1 <= (size_t)LDS_MAX;
+
+    // the serving kernel's launch shape; TAB_N, TAB_E: the transform whose pass table it reads (PTW_COL for the plain
+    // kernel, the compact PTWC_COL otherwise)
+    struct Shape { int gc, threads; size_t lds; int wg_per_cu, tab_n, tab_e; };
+    static constexpr Shape shape() {
+        if constexpr (KIND == ColKind::TwoLevel) {
+            // HS = H / 2 point sub-transforms, one resident workgroup set (2 waves per SIMD)
+            using CX = ColX<T, H, ECOLX>;
+            const int wg_lds = (int)((size_t)LDS_MAX / CX::LDS);
+            int wg_per_cu = col_resident(CX::NT);
+            if (wg_per_cu > wg_lds) wg_per_cu = wg_lds > 0 ? wg_lds : 1;
+            return {CX::GC, CX::NT, CX::LDS, wg_per_cu, CX::HS, ECOLX};
+        } else if constexpr (KIND == ColKind::Persistent) {
+            return {GC1, NT1, (DB ? 2 : 1) * XB1 + TAB1, col_resident(NT1), H, E1};
+        } else {
+            return {GC1, NT1, XB1, 0, H, E1};
+        }
+    }
 };
-// the column object's entry points (defined under PFB_POW2_COL below)
-int pow2_col_set_attr(int dtype, int H);
-int pow2_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st);
-int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st);
+
+// The column-kernel instantiations of class (T, H).
+template <typename T, int H> struct ColKernels {
+    using C = ColCfg<T, H>;
+    static constexpr auto plain() { return k_col_pow2<T, H, C::E1>; }
+    static constexpr auto fwd() { return k_col_fwd_pow2<T, H, C::E1>; }
+    // the serving persistent / two-level kernel: f(kernel, NT) for its plain and its non-temporal PSF reads
+    template <typename Fn> static void serving(Fn&& f) {
+        if constexpr (C::KIND == ColKind::Persistent) {
+            f(k_col_pow2p<T, H, C::E1, C::DB, false>, false);
+            f(k_col_pow2p<T, H, C::E1, C::DB, true>, true);
+        } else if constexpr (C::KIND == ColKind::TwoLevel) {
+            f(k_col_pow2x<T, H, ECOLX, false>, false);
+            f(k_col_pow2x<T, H, ECOLX, true>, true);
+        }
+    }
+    // all of them, f(kernel)
+    template <typename Fn> static void all(Fn&& f) {
+        // (the plain kernel is launched only where KIND is Plain; it stays instantiated for every H: the kernels of one
+        // object share their transforms' code, and the object's kernel set is the one all measurements were taken with)
+        f(plain());
+        f(fwd());
+        serving([&](auto* k, bool) { f(k); });
+        // KEPT INSTANTIATED, NEVER LAUNCHED: k_col_pow2x<double, 4096> -- the one-level kernel serves 4096-point columns -- shares
+        // the 2048-point RegFft with k_col_pow2p<double, 2048>: without it the compiler contracts some products of that kernel
+        // differently and 2048^2 fp64 results change in the last bits
+        if constexpr (H == 4096 && sizeof(T) == 8) {
+            f(k_col_pow2x<T, H, ECOLX, false>);
+            f(k_col_pow2x<T, H, ECOLX, true>);
+        }
+    }
+};
+
+template <typename T, int H>
+static void launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
+    using C = ColCfg<T, H>;
+    using CK = ColKernels<T, H>;
+    constexpr auto S = C::shape();
+    const int nblk = fast_nblocks(p->ny / 2, FastCfg<T>::NVB);
+    if constexpr (C::KIND == ColKind::Plain) {
+        hipLaunchKernelGGL(CK::plain(), dim3((nblk + S.gc - 1) / S.gc, nb), dim3(S.threads), S.lds, st,
+                           (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,
+                           (const cplx<T>*)ft->tab[PTW_COL], nblk, p->T_elems_per_band, p->psf_elems_per_band, band0);
+    } else {
+        // bands in DESCENDING order (persistent kernels): the row pass before and after run ascending, so each pass starts on
+        // the band whose T the previous one touched last (part of it still in the 256 MiB Infinity Cache):
+        // col 0.995 -> 0.987 ms, row_inv 0.666 -> 0.660 ms at 8 x 4096^2 fp32
+        const int band_first = band0 + nb - 1;
+        // psf read with non-temporal loads (see loadb_nt) only when this launch's share of the PSF spectrum is itself of the
+        // Infinity Cache's size or larger: a smaller one is RE-READ from that cache by the next apply and must stay allocatable
+        const bool psf_nt = sizeof(cplx<T>) * p->psf_elems_per_band * (size_t)nb >= ((size_t)200 << 20);
+        const int nitems = nblk * nb, need = (nitems + S.gc - 1) / S.gc, maxgrid = ft->num_cu * S.wg_per_cu;
+        // (the two-level kernel without balanced_grid: it is bound by the issue of its transforms, every workgroup counts --
+        // 2.003 -> 2.047 ms fp64, 1.110 -> 1.128 fp32 with 253 / 249 instead of 256)
+        const int grid = C::KIND == ColKind::Persistent ? balanced_grid(need, maxgrid) : (need < maxgrid ? need : maxgrid);
+        CK::serving([&](auto* k, bool nt) {
+            if (nt != psf_nt) return;
+            hipLaunchKernelGGL(k, dim3(grid), dim3(S.threads), S.lds, st,
+                               (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,
+                               (const cplx<T>*)ft->tab[PTWC_COL], nblk, nitems, p->T_elems_per_band,
+                               p->psf_elems_per_band, band_first, -1);
+        });
+    }
+}
+
+// PSFHAT producer: the four quadrant spectra in Tq (slots of T_elems_per_band) -> psf_l of `band`
+template <typename T, int H>
+static void launch_col_fwd(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
+    using C = ColCfg<T, H>;
+    using CK = ColKernels<T, H>;
+    const int L = p->ny / 2;
+    const int nblk = fast_nblocks(L, C::NVB), nbe = (L + C::NVB) / C::NVB;
+    hipLaunchKernelGGL(CK::fwd(), dim3((nblk + C::GC1 - 1) / C::GC1), dim3(C::NT1), C::XB1, st,
+                       (const cplx<T>*)Tq, (cplx<T>*)p->psf_l + (size_t)band * p->psf_elems_per_band,
+                       (const cplx<T>*)p->twP, (const cplx<T>*)ft->tab[PTW_COL], nblk, nbe, p->T_elems_per_band,
+                       col_two_level(H));
+}
+
+// tables and LDS attributes of class (T, H)
+template <typename T, int H>
+static int col_prepare(FastTables* ft) {
+    constexpr auto S = ColCfg<T, H>::shape();
+    int rc = upload_ptw<T, H, ColCfg<T, H>::E1>(&ft->tab[PTW_COL]);
+    if constexpr (ColCfg<T, H>::KIND != ColKind::Plain)
+        if (rc == PFB_OK) rc = upload_ptwc<T, S.tab_n, S.tab_e>(&ft->tab[PTWC_COL]);
+    ColKernels<T, H>::all([&](auto* k) { if (rc == PFB_OK) rc = set_lds_max(k); });
+    return rc;
+}
+
+// f(T{}, std::integral_constant<int, H>) for the plan's type and nx
+template <typename Fn>
+static int for_col_class(const pfb_conv_plan* p, Fn&& f) {
+    const bool ok = for_pow2_size(p->nx, [&](auto h) { if (p->dtype == PFB_F32) f(float{}, h); else f(double{}, h); });
+    if (!ok) set_error("pow2: unsupported nx");
+    return ok ? PFB_OK : PFB_ERR_UNSUPPORTED;
+}
+int pow2_col_prepare(pfb_conv_plan* p, FastTables* ft) {
+    int rc = PFB_OK;
+    const int rs = for_col_class(p, [&](auto t, auto h) { rc = col_prepare<decltype(t), h()>(ft); });
+    return rs != PFB_OK ? rs : rc;
+}
+int pow2_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
+    return for_col_class(p, [&](auto t, auto h) { launch_col<decltype(t), h()>(p, ft, band0, nb, st); });
+}
+int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
+    return for_col_class(p, [&](auto t, auto h) { launch_col_fwd<decltype(t), h()>(p, ft, Tq, band, st); });
+}
+#endif  // PFB_POW2_COL
 
 #if PFB_POW2_REST
-template <typename T, int N, int E>
-static int upload_ptw(void** dev) {
-    constexpr int n = ptw_total<N, E>();
-    std::vector<cplx<T>> h(n > 0 ? n : 1);
-    if (n > 0) fill_ptw<T, N, E>(h.data());
-    PFB_HIP_CHECK(hipMalloc(dev, sizeof(cplx<T>) * h.size()));
-    PFB_HIP_CHECK(hipMemcpy(*dev, h.data(), sizeof(cplx<T>) * h.size(), hipMemcpyHostToDevice));
-    return PFB_OK;
-}
-
-template <typename T, int N, int E>
-static int prep_ptw(void** dev) { return upload_ptw<T, N, E>(dev); }
-
-template <typename T, int N, int E>
-static int prep_ptw_compact(void** dev) {
-    constexpr int n = ptw_total<N, E>() / 4;
-    std::vector<cplx<T>> h(n > 0 ? n : 1);
-    if (n > 0) fill_ptw_compact<T, N, E>(h.data());
-    PFB_HIP_CHECK(hipMalloc(dev, sizeof(cplx<T>) * h.size()));
-    PFB_HIP_CHECK(hipMemcpy(*dev, h.data(), sizeof(cplx<T>) * h.size(), hipMemcpyHostToDevice));
-    return PFB_OK;
-}
-
-template <typename T, int L>
-static int set_invp_attr() {
-    constexpr int E = InvPE<T, L>::E;
-    if constexpr (InvP<T, L, E>::OK) {
-#define PFB_INVATTR(MODE, BM)                                                                           \
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, MODE, BM>),             \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-        PFB_INVATTR(0, false); PFB_INVATTR(1, false); PFB_INVATTR(2, false);
-        PFB_INVATTR(0, true);  PFB_INVATTR(1, true);  PFB_INVATTR(2, true);
-        if constexpr (inv_pb_ok<T, L, E>()) {
-            PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, 2, false, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_inv_pow2p<T, L, E, 2, true, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+// The forward row kernels of class (T, L = ny / 2): the persistent one where FwdP::OK, else the plain one.
+template <typename T, int L> struct RowFwdK {
+    using FP = FwdP<T, L>;
+    static constexpr bool PERSISTENT = FP::OK;
+    static constexpr int E = PERSISTENT ? FP::EOK : RowCfg<T, L, false>::E;
+    static constexpr auto plain() { return k_row_fwd_pow2<T, L, E>; }
+    // the instantiations launch_row_fwd can reach: f(kernel, beam) (the plain kernel takes `beam` at run time)
+    template <typename Fn> static void reachable(Fn&& f) {
+        if constexpr (PERSISTENT) {
+            f(k_row_fwd_pow2q<T, L, false>, false);
+            f(k_row_fwd_pow2q<T, L, true>, true);
+        } else {
+            f(plain(), false);
         }
-#undef PFB_INVATTR
     }
-    return PFB_OK;
-}
+};
 
+// The inverse row kernels of class (T, L): the plain one, and where InvP::OK the persistent one by mode (0: no inner
+// product, 1: <x, out>, 2: + <dot_with2, out>), beam and -- where inv_pb_ok -- its per-band form.
+template <typename T, int L> struct RowInvK {
+    static constexpr int E = RowCfg<T, L, true>::E, EP = InvPE<T, L>::E;
+    using IP = InvP<T, L, EP>;
+    static constexpr bool PERSISTENT = IP::OK;
+    static constexpr bool PER_BAND = PERSISTENT && inv_pb_ok<T, L, EP>();
+    static constexpr auto plain() { return k_row_inv_pow2<T, L, E>; }
+    template <int MODE, bool PB, typename Fn> static void beam_pair(Fn&& f) {
+        f(k_row_inv_pow2p<T, L, EP, MODE, false, PB>, MODE, false, PB);
+        f(k_row_inv_pow2p<T, L, EP, MODE, true, PB>, MODE, true, PB);
+    }
+    // the persistent instantiations launch_row_inv can reach: f(kernel, mode, beam, per_band)
+    template <typename Fn> static void persistent(Fn&& f) {
+        if constexpr (PERSISTENT) {
+            beam_pair<0, false>(f);
+            beam_pair<1, false>(f);
+            beam_pair<2, false>(f);
+            if constexpr (PER_BAND) beam_pair<2, true>(f);
+        }
+    }
+    template <typename Fn> static void reachable(Fn&& f) {       // all of them, f(kernel)
+        f(plain());
+        persistent([&](auto* k, int, bool, bool) { f(k); });
+    }
+};
+
+// tables and LDS attributes of the row class (T, L)
 template <typename T, int L>
-static int prep_fwdp(void** table) {
-    if constexpr (FwdP<T, L>::OK) {
-        int rc = prep_ptw_compact<T, L, FwdP<T, L>::EOK>(table);
-        if (rc != PFB_OK) return rc;
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2q<T, L, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_row_fwd_pow2q<T, L, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+static int row_prepare(FastTables* ft) {
+    using FK = RowFwdK<T, L>;
+    using IK = RowInvK<T, L>;
+    int rc;
+    if constexpr (FK::PERSISTENT) rc = upload_ptwc<T, L, FK::E>(&ft->tab[PTWC_ROW_FWD]);
+    else rc = upload_ptw<T, L, FK::E>(&ft->tab[PTW_ROW]);
+    if (rc == PFB_OK) rc = upload_ptwc<T, L, IK::E>(&ft->tab[PTWC_ROW_INV]);
+    if constexpr (IK::EP != IK::E) {
+        if (rc == PFB_OK) rc = upload_ptwc<T, L, IK::EP>(&ft->tab[PTWC_ROW_INV_P]);
     } else {
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_row_fwd_pow2<T, L, RowCfg<T, L, false>::E>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ft->tab[PTWC_ROW_INV_P] = ft->tab[PTWC_ROW_INV];
     }
-    return PFB_OK;
+    FK::reachable([&](auto* k, bool) { if (rc == PFB_OK) rc = set_lds_max(k); });
+    IK::reachable([&](auto* k) { if (rc == PFB_OK) rc = set_lds_max(k); });
+    return rc;
 }
-
 
 template <typename T>
 static int prep_tables(pfb_conv_plan* p, FastTables* ft) {
-    const int H = p->nx, L = p->ny / 2;
-    int rc = PFB_ERR_UNSUPPORTED;
-    constexpr int lds_max = 160 * 1024;
-    switch (H) {
-#define X(NN) case NN: rc = prep_ptw<T, NN, ecol<T, NN>()>(&ft->ptw_col);                          \
-        if (rc == PFB_OK) rc = prep_ptw_compact<T, NN, ecol<T, NN>()>(&ft->ptwc_col);             \
-        if (rc == PFB_OK && NN == 8192) rc = prep_ptw_compact<T, 4096, ECOLX>(&ft->ptwc_col_x);         \
-        if (rc == PFB_OK) rc = pow2_col_set_attr(p->dtype, NN); break;
-        PFB_POW2_SIZES(X)
-#undef X
-        default: break;
-    }
+    const int L = p->ny / 2;
+    int rc = pow2_col_prepare(p, ft);
     if (rc != PFB_OK) return rc;
-    rc = PFB_ERR_UNSUPPORTED;
-    switch (L) {
-#define X(NN) case NN: rc = prep_ptw<T, NN, RowCfg<T, NN, false>::E>(&ft->ptw_row);                   \
-        if (rc == PFB_OK) rc = prep_ptw_compact<T, NN, RowCfg<T, NN, true>::E>(&ft->ptw_row_inv);    \
-        if (rc == PFB_OK) { if (InvPE<T, NN>::E != RowCfg<T, NN, true>::E) rc = prep_ptw_compact<T, NN, InvPE<T, NN>::E>(&ft->ptw_row_inv_p); \
-                            else ft->ptw_row_inv_p = ft->ptw_row_inv; }                            \
-        if (rc == PFB_OK) PFB_HIP_CHECK(hipFuncSetAttribute((const void*)k_row_inv_pow2<T, NN, RowCfg<T, NN, true>::E>, \
-            hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));                                   \
-        if (rc == PFB_OK) rc = set_invp_attr<T, NN>();                                               \
-        if (rc == PFB_OK) rc = prep_fwdp<T, NN>(&ft->ptwc_row_fwd); break;
-        PFB_POW2_SIZES(X)
-#undef X
-        default: break;
-    }
+    if (!for_pow2_size(L, [&](auto l) { rc = row_prepare<T, l()>(ft); })) return PFB_ERR_UNSUPPORTED;
     if (rc != PFB_OK) return rc;
     // twM[n] = exp(-2 pi i n / M), n < L  (M = ny)
-    std::vector<cplx<T>> h(L);
-    const long double two_pi = 6.283185307179586476925286766559005768L;
-    for (int n = 0; n < L; ++n) {
-        long double a = two_pi * (long double)n / (long double)p->ny;
-        h[n] = cplx<T>((T)cosl(a), (T)(-sinl(a)));
-    }
-    PFB_HIP_CHECK(hipMalloc(&ft->twM, sizeof(cplx<T>) * L));
-    PFB_HIP_CHECK(hipMemcpy(ft->twM, h.data(), sizeof(cplx<T>) * L, hipMemcpyHostToDevice));
-    return PFB_OK;
+    return upload_table<T>(&ft->tab[TW_M], L, [&](cplx<T>* h) {
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        for (int n = 0; n < L; ++n) {
+            long double a = two_pi * (long double)n / (long double)p->ny;
+            h[n] = cplx<T>((T)cosl(a), (T)(-sinl(a)));
+        }
+    });
 }
-
-template <typename T, int L>
-static int rows_per_wg() { return row_groups<T, L, RowCfg<T, L, true>::E, RowCfg<T, L, true>::GMAX>(); }
 
 bool pow2_supported(const pfb_conv_plan* p) {
     if (!is_pow2(p->nx) || !is_pow2(p->ny)) return false;
@@ -2089,15 +2256,14 @@ bool pow2_supported(const pfb_conv_plan* p) {
     return true;
 }
 
+template <typename T, int L>
+static int rows_per_wg() { return row_groups<T, L, RowCfg<T, L, true>::E, RowCfg<T, L, true>::GMAX>(); }
+
 int pow2_rows_per_wg(const pfb_conv_plan* p) {
-    const int L = p->ny / 2;
     const bool f32 = p->dtype == PFB_F32;
-    switch (L) {
-#define X(NN) case NN: return f32 ? rows_per_wg<float, NN>() : rows_per_wg<double, NN>();
-        PFB_POW2_SIZES(X)
-#undef X
-        default: return 0;
-    }
+    int g = 0;
+    for_pow2_size(p->ny / 2, [&](auto l) { g = f32 ? rows_per_wg<float, l()>() : rows_per_wg<double, l()>(); });
+    return g;
 }
 
 int pow2_nblocks(const pfb_conv_plan* p) {
@@ -2116,21 +2282,15 @@ int pow2_prepare(pfb_conv_plan* p) {
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
         ft->num_cu = prop.multiProcessorCount;
     if (ft->num_cu <= 0) ft->num_cu = 256;
-    ft->col_x = p->nx >= 8192 ? 1 : 0;
     return p->dtype == PFB_F32 ? prep_tables<float>(p, ft) : prep_tables<double>(p, ft);
 }
 
 void pow2_release(pfb_conv_plan* p) {
     FastTables* ft = (FastTables*)p->fast_tables;
     if (!ft) return;
-    if (ft->ptw_col) (void)hipFree(ft->ptw_col);
-    if (ft->ptwc_col) (void)hipFree(ft->ptwc_col);
-    if (ft->ptwc_col_x) (void)hipFree(ft->ptwc_col_x);
-    if (ft->ptw_row) (void)hipFree(ft->ptw_row);
-    if (ft->ptw_row_inv_p && ft->ptw_row_inv_p != ft->ptw_row_inv) (void)hipFree(ft->ptw_row_inv_p);
-    if (ft->ptw_row_inv) (void)hipFree(ft->ptw_row_inv);
-    if (ft->twM) (void)hipFree(ft->twM);
-    if (ft->ptwc_row_fwd) (void)hipFree(ft->ptwc_row_fwd);
+    if (ft->tab[PTWC_ROW_INV_P] == ft->tab[PTWC_ROW_INV]) ft->tab[PTWC_ROW_INV_P] = nullptr;      // the alias
+    for (void* t : ft->tab)
+        if (t) (void)hipFree(t);
     free(ft);
     p->fast_tables = nullptr;
 }
@@ -2143,7 +2303,7 @@ static int set_psfhat_t(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
     dim3 grid((nv + 31) / 32, (p->P + 31) / 32, p->nband);
     hipLaunchKernelGGL((k_relayout_psf_pow2<T>), grid, dim3(256), 0, st, (const cplx<T>*)psfhat,
                        (cplx<T>*)p->psf_l, p->P, nv, p->ny / 2, FastCfg<T>::NVB, p->psf_elems_per_band,
-                       ((const FastTables*)p->fast_tables)->col_x);
+                       col_two_level(p->nx));
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;
 }
@@ -2152,9 +2312,45 @@ int pow2_set_psfhat(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
     return p->dtype == PFB_F32 ? set_psfhat_t<float>(p, psfhat, st) : set_psfhat_t<double>(p, psfhat, st);
 }
 
+static FastDims fast_dims(const pfb_conv_plan* p, size_t xpitch, size_t xband) {
+    return FastDims{p->nx, p->ny, p->M, p->T_elems_per_band, p->psf_elems_per_band, xpitch, xband};
+}
+// w_Q = exp(-2 pi i / Q), Q = 2 ny: the persistent row kernels' odd-bin twiddles are w_M^m w_Q
+template <typename T>
+static cplx<T> wq1_of(const pfb_conv_plan* p) {
+    const long double a = 6.283185307179586476925286766559005768L / (2.0L * (long double)p->ny);
+    return cplx<T>((T)cosl(a), (T)(-sinl(a)));
+}
+
+// Tbuf: the half-spectrum buffer to fill (the plan's T, or the PSFHAT producer's quadrant scratch: `band0`
+// is then the slot); xpitch / xband: elements between rows / bands of x (and beam)
 template <typename T, int L>
 static void launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
-                           const void* beam, size_t xpitch, size_t xband, hipStream_t st);
+                           const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
+    using K = RowFwdK<T, L>;
+    const FastDims d = fast_dims(p, xpitch, xband);
+    if constexpr (K::PERSISTENT) {
+        // persistent kernel: parities in sequence, next rows requested inside the second transform
+        using FP = typename K::FP;
+        const int tiles_per_band = p->nx / FP::G, ntiles = tiles_per_band * nb;
+        const int grid = ntiles < ft->num_cu * FP::WG_PER_CU ? ntiles : ft->num_cu * FP::WG_PER_CU;
+        const cplx<T> wq1 = wq1_of<T>(p);
+        K::reachable([&](auto* k, bool bm) {
+            if (bm != (beam != nullptr)) return;
+            hipLaunchKernelGGL(k, dim3(grid), dim3(FP::NT), FP::LDS, st, (const T*)x,
+                               (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)ft->tab[TW_M],
+                               (const cplx<T>*)ft->tab[PTWC_ROW_FWD], d, band0, tiles_per_band, ntiles, wq1);
+        });
+    } else {
+        constexpr int E = K::E;
+        using F = RegFft<T, L, E, RowCfg<T, L, false>::WAVE>;
+        constexpr int G = row_groups<T, L, E, RowCfg<T, L, false>::GMAX>();
+        const size_t lds = sizeof(cplx<T>) * (size_t)G * (F::LDS_ELEMS + 4);
+        hipLaunchKernelGGL(K::plain(), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
+                           (const T*)x, (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)p->twQ,
+                           (const cplx<T>*)ft->tab[TW_M], (const cplx<T>*)ft->tab[PTW_ROW], d, band0);
+    }
+}
 
 // psfhat = r2c(ifftshift(psf)) with the fast path's own kernels (see k_col_fwd_pow2), band by band:
 // four pruned row passes over the PSF quadrants (ifftshift = which quadrant goes where), one forward column pass
@@ -2175,11 +2371,9 @@ static int set_psf_t(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStr
             // quadrant (a, b) of the SHIFTED PSF = quadrant (1 - a, 1 - b) of the centred one
             const int a = q >> 1, b = q & 1;
             const T* src = pb + (size_t)((1 - a) * nx) * Q + (size_t)(1 - b) * ny;
-            switch (L) {
-#define X(NN) case NN: launch_row_fwd<T, NN>(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st); break;
-                PFB_POW2_SIZES(X)
-#undef X
-                default: set_error("pow2_set_psf: unsupported ny"); rc = PFB_ERR_UNSUPPORTED; break;
+            if (!for_pow2_size(L, [&](auto l) { launch_row_fwd<T, l()>(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st); })) {
+                set_error("pow2_set_psf: unsupported ny");
+                rc = PFB_ERR_UNSUPPORTED;
             }
         }
         if (rc == PFB_OK) rc = pow2_col_fwd_launch(p, ft, Tq, band, st);
@@ -2188,7 +2382,7 @@ static int set_psf_t(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStr
         const int nv = p->M + 1;
         dim3 grid((nv + 31) / 32, (P + 31) / 32, p->nband);
         hipLaunchKernelGGL((k_unrelayout_psf_pow2<T>), grid, dim3(256), 0, st, (const cplx<T>*)p->psf_l,
-                           (cplx<T>*)psfhat_out, P, nv, L, FastCfg<T>::NVB, p->psf_elems_per_band, ft->col_x);
+                           (cplx<T>*)psfhat_out, P, nv, L, FastCfg<T>::NVB, p->psf_elems_per_band, col_two_level(nx));
     }
     if (rc == PFB_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
         set_error("pow2_set_psf: kernel launch failed");
@@ -2202,224 +2396,40 @@ int pow2_set_psf(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStream_
     return p->dtype == PFB_F32 ? set_psf_t<float>(p, psf, psfhat_out, st) : set_psf_t<double>(p, psf, psfhat_out, st);
 }
 
-#endif  // PFB_POW2_REST
-
-#if PFB_POW2_COL
-template <typename T, int H>
-static void launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
-    constexpr int E = ecol<T, H>();
-    using F = RegFft<T, H, E>;
-    constexpr int GC = col_groups<H, E>();
-    const int nblk = fast_nblocks(p->ny / 2, FastCfg<T>::NVB);
-    // bands in DESCENDING order (persistent kernels): the row pass before and after run ascending, so each pass starts on
-    // the band whose T the previous one touched last (part of it still in the 256 MiB Infinity Cache):
-    // col 0.995 -> 0.987 ms, row_inv 0.666 -> 0.660 ms at 8 x 4096^2 fp32
-    const int band_first = band0 + nb - 1;
-    // psf read with non-temporal loads (see loadb_nt) only when this launch's share of the PSF spectrum is itself of the
-    // Infinity Cache's size or larger: a smaller one is RE-READ from that cache by the next apply and must stay allocatable
-    const bool psf_nt = sizeof(cplx<T>) * p->psf_elems_per_band * (size_t)nb >= ((size_t)200 << 20);
-    if constexpr (H == 8192) {
-        if (ft->col_x) {
-            // two-level kernel: HS = H / 2 point sub-transforms, one resident workgroup set (2 waves per SIMD)
-            using CX = ColX<T, H, ECOLX>;
-            using FX = typename CX::F;
-            constexpr int GX = CX::GC;
-            const int nitems = nblk * nb;
-            const int wg_lds = (int)(((size_t)160 * 1024) / CX::LDS);
-            int wg_per_cu = (8 * 64) / (GX * FX::TPB) > 0 ? (8 * 64) / (GX * FX::TPB) : 1;
-            if (wg_per_cu > wg_lds) wg_per_cu = wg_lds > 0 ? wg_lds : 1;
-            const int need = (nitems + GX - 1) / GX;
-            // (not balanced_grid: this kernel is bound by the issue of its transforms, every workgroup counts --
-            // 2.003 -> 2.047 ms fp64, 1.110 -> 1.128 fp32 with 253 / 249 instead of 256)
-            const int grid = need < ft->num_cu * wg_per_cu ? need : ft->num_cu * wg_per_cu;
-            const size_t ldsx = CX::LDS;
-#define PFB_COLX(NTV)                                                                                          \
-            hipLaunchKernelGGL((k_col_pow2x<T, H, ECOLX, NTV>), dim3(grid), dim3(GX * FX::TPB), ldsx, st,      \
-                               (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,               \
-                               (const cplx<T>*)ft->ptwc_col_x, nblk, nitems, p->T_elems_per_band,              \
-                               p->psf_elems_per_band, band_first, -1)
-            if (psf_nt) PFB_COLX(true); else PFB_COLX(false);
-#undef PFB_COLX
-            return;
-        }
-    }
-    constexpr size_t lds = sizeof(cplx<T>) * (size_t)GC * FastCfg<T>::NVB * F::LDS_ELEMS;
-    // persistent kernel: needs its LDS (exchange buffers + twiddle table) to fit; measured faster
-    // for H >= 2048 (fp32, packed arithmetic: 1.07 vs 1.32 ms at 4096^2 x 8, 0.276 vs 0.347 at 2048^2 x 8;
-    // fp64: 1.19 vs 1.41 and 0.266 vs 0.333 at x 4; a tie or a small loss at H <= 1024)
-    constexpr size_t tab = sizeof(cplx<T>) * (size_t)((F::PTWC + 1) & ~1);
-    if constexpr (H >= 2048 && lds + tab <= (size_t)160 * 1024) {
-        // one resident workgroup set: 8 waves per CU at 256 VGPRs
-        const int nitems = nblk * nb;
-        constexpr int wg_per_cu = (8 * 64) / (GC * F::TPB) > 0 ? (8 * 64) / (GC * F::TPB) : 1;
-        const int need = (nitems + GC - 1) / GC;
-        const int grid = balanced_grid(need, ft->num_cu * wg_per_cu);
-        // second exchange buffer set when ONE workgroup per CU is resident anyway and it fits: col 0.98 ->
-        // 0.96 ms at 8 x 4096^2 fp32, 1.16 -> 1.10 ms at 4 x 4096^2 fp64; with two workgroups per CU (H = 2048)
-        // the doubled LDS costs residency (fp64 0.245 -> 0.304 ms)
-        constexpr bool db = wg_per_cu == 1 && 2 * lds + tab <= (size_t)160 * 1024;
-#define PFB_COLP(NTV)                                                                                          \
-        hipLaunchKernelGGL((k_col_pow2p<T, H, E, db, NTV>), dim3(grid), dim3(GC * F::TPB), (db ? 2 : 1) * lds + tab, st, \
-                           (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,                   \
-                           (const cplx<T>*)ft->ptwc_col, nblk, nitems, p->T_elems_per_band,                    \
-                           p->psf_elems_per_band, band_first, -1)
-        if (psf_nt) PFB_COLP(true); else PFB_COLP(false);
-#undef PFB_COLP
-        return;
-    }
-    hipLaunchKernelGGL((k_col_pow2<T, H, E>), dim3((nblk + GC - 1) / GC, nb), dim3(GC * F::TPB), lds, st,
-                       (cplx<T>*)p->T, (const cplx<T>*)p->psf_l, (const cplx<T>*)p->twP,
-                       (const cplx<T>*)ft->ptw_col, nblk, p->T_elems_per_band, p->psf_elems_per_band, band0);
-}
-
-template <typename T, int H>
-static int col_set_attr() {
-    constexpr int lds_max = 160 * 1024;
-    constexpr int E = ecol<T, H>();
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2<T, H, E>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_fwd_pow2<T, H, E>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    using F = RegFft<T, H, E>;
-    constexpr int GC = col_groups<H, E>();
-    constexpr size_t lds = sizeof(cplx<T>) * (size_t)GC * FastCfg<T>::NVB * F::LDS_ELEMS;
-    constexpr size_t tab = sizeof(cplx<T>) * (size_t)((F::PTWC + 1) & ~1);
-    if constexpr (H >= 2048 && lds + tab <= (size_t)160 * 1024) {      // as in launch_col
-        constexpr int wg_per_cu = (8 * 64) / (GC * F::TPB) > 0 ? (8 * 64) / (GC * F::TPB) : 1;
-        constexpr bool db = wg_per_cu == 1 && 2 * lds + tab <= (size_t)160 * 1024;
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, H, E, db, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2p<T, H, E, db, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    }
-    // (k_col_pow2x<double, 4096> is never launched -- the one-level kernel serves 4096-point columns -- but it shares the
-    // 2048-point RegFft with k_col_pow2p<double, 2048>: without it the compiler contracts some products of that kernel
-    // differently and 2048^2 fp64 results change in the last bits)
-    if constexpr (H == 8192 || (H == 4096 && sizeof(T) == 8)) {
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2x<T, H, ECOLX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        PFB_HIP_CHECK(hipFuncSetAttribute((const void*)(k_col_pow2x<T, H, ECOLX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    }
-    return PFB_OK;
-}
-template <typename T>
-static int col_set_attr_t(int H) {
-    switch (H) {
-#define X(NN) case NN: return col_set_attr<T, NN>();
-        PFB_POW2_SIZES(X)
-#undef X
-        default: set_error("pow2: unsupported nx"); return PFB_ERR_UNSUPPORTED;
-    }
-}
-int pow2_col_set_attr(int dtype, int H) {
-    return dtype == PFB_F32 ? col_set_attr_t<float>(H) : col_set_attr_t<double>(H);
-}
-template <typename T>
-static int col_launch_t(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
-    switch (p->nx) {
-#define X(NN) case NN: launch_col<T, NN>(p, ft, band0, nb, st); break;
-        PFB_POW2_SIZES(X)
-#undef X
-        default: set_error("pow2_apply: unsupported nx"); return PFB_ERR_UNSUPPORTED;
-    }
-    return PFB_OK;
-}
-int pow2_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
-    return p->dtype == PFB_F32 ? col_launch_t<float>(p, ft, band0, nb, st) : col_launch_t<double>(p, ft, band0, nb, st);
-}
-// PSFHAT producer: the four quadrant spectra in Tq (slots of T_elems_per_band) -> psf_l of `band`
-template <typename T, int H>
-static void launch_col_fwd(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
-    constexpr int E = ecol<T, H>();
-    using F = RegFft<T, H, E>;
-    constexpr int GC = col_groups<H, E>();
-    constexpr int NVB = FastCfg<T>::NVB;
-    const int L = p->ny / 2;
-    const int nblk = fast_nblocks(L, NVB), nbe = (L + NVB) / NVB;
-    const size_t lds = sizeof(cplx<T>) * (size_t)GC * NVB * F::LDS_ELEMS;
-    hipLaunchKernelGGL((k_col_fwd_pow2<T, H, E>), dim3((nblk + GC - 1) / GC), dim3(GC * F::TPB), lds, st,
-                       (const cplx<T>*)Tq, (cplx<T>*)p->psf_l + (size_t)band * p->psf_elems_per_band,
-                       (const cplx<T>*)p->twP, (const cplx<T>*)ft->ptw_col, nblk, nbe, p->T_elems_per_band, ft->col_x);
-}
-template <typename T>
-static int col_fwd_launch_t(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
-    switch (p->nx) {
-#define X(NN) case NN: launch_col_fwd<T, NN>(p, ft, Tq, band, st); break;
-        PFB_POW2_SIZES(X)
-#undef X
-        default: set_error("pow2_set_psf: unsupported nx"); return PFB_ERR_UNSUPPORTED;
-    }
-    return PFB_OK;
-}
-int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
-    return p->dtype == PFB_F32 ? col_fwd_launch_t<float>(p, ft, Tq, band, st) : col_fwd_launch_t<double>(p, ft, Tq, band, st);
-}
-#endif  // PFB_POW2_COL
-
-#if PFB_POW2_REST
-
-// Tbuf: the half-spectrum buffer to fill (the plan's T, or the PSFHAT producer's quadrant scratch: `band0`
-// is then the slot); xpitch / xband: elements between rows / bands of x (and beam)
-template <typename T, int L>
-static void launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
-                           const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
-    FastDims d{p->nx, p->ny, p->M, p->T_elems_per_band, p->psf_elems_per_band, xpitch, xband};
-    if constexpr (FwdP<T, L>::OK) {
-        // persistent kernel: parities in sequence, next rows requested inside the second transform
-        using FP = FwdP<T, L>;
-        const int tiles_per_band = p->nx / FP::G, ntiles = tiles_per_band * nb;
-        const int grid = ntiles < ft->num_cu * FP::WG_PER_CU ? ntiles : ft->num_cu * FP::WG_PER_CU;
-        const long double a = 6.283185307179586476925286766559005768L / (2.0L * (long double)p->ny);
-        const cplx<T> wq1((T)cosl(a), (T)(-sinl(a)));
-#define PFB_FWDQ(BM)                                                                                              \
-        hipLaunchKernelGGL((k_row_fwd_pow2q<T, L, BM>), dim3(grid), dim3(FP::NT), FP::LDS, st, (const T*)x,      \
-                           (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)ft->twM,                              \
-                           (const cplx<T>*)ft->ptwc_row_fwd, d, band0, tiles_per_band, ntiles, wq1)
-        if (beam) PFB_FWDQ(true); else PFB_FWDQ(false);
-#undef PFB_FWDQ
-    } else {
-        constexpr int E = RowCfg<T, L, false>::E;
-        using F = RegFft<T, L, E, RowCfg<T, L, false>::WAVE>;
-        constexpr int G = row_groups<T, L, E, RowCfg<T, L, false>::GMAX>();
-        const size_t lds = sizeof(cplx<T>) * (size_t)G * (F::LDS_ELEMS + 4);
-        hipLaunchKernelGGL((k_row_fwd_pow2<T, L, E>), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
-                           (const T*)x, (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)p->twQ,
-                           (const cplx<T>*)ft->twM, (const cplx<T>*)ft->ptw_row, d, band0);
-    }
-}
-
 template <typename T, int L>
 static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x,
                            const void* beam, double scale, double sigmainv, void* out,
                            const void* dot_with, const void* dot_with2, bool per_band, hipStream_t st) {
-    constexpr int E = RowCfg<T, L, true>::E;
-    using F = RegFft<T, L, E, RowCfg<T, L, true>::WAVE>;
-    constexpr int G = row_groups<T, L, E, RowCfg<T, L, true>::GMAX>();
-    FastDims d{p->nx, p->ny, p->M, p->T_elems_per_band, p->psf_elems_per_band, (size_t)p->ny, (size_t)p->nx * p->ny};
-    constexpr int EP = InvPE<T, L>::E;
-    if constexpr (InvP<T, L, EP>::OK) {
-        // pipelined persistent kernel: no beam, inner products only against x itself (+ dot_with2)
+    using K = RowInvK<T, L>;
+    const FastDims d = fast_dims(p, (size_t)p->ny, (size_t)p->nx * p->ny);
+    if constexpr (K::PERSISTENT) {
+        // pipelined persistent kernel: inner products only against x itself (+ dot_with2)
         const bool plain_dots = !dot_with || (dot_with == x);
         if (plain_dots && !(dot_with2 && !dot_with)) {
-            using IP = InvP<T, L, EP>;
-            const long double a = 6.283185307179586476925286766559005768L / (2.0L * (long double)p->ny);
-            const cplx<T> wq1((T)cosl(a), (T)(-sinl(a)));
-#define PFB_INVP3(MODE, BM, PBV, B0, NB, GRID, OFF, PART)                                                        \
-            hipLaunchKernelGGL((k_row_inv_pow2p<T, L, EP, MODE, BM, PBV>), dim3(GRID), dim3(IP::NT), IP::LDS, st,  \
-                               (const cplx<T>*)p->T, (const cplx<T>*)ft->twM,                                    \
-                               (const cplx<T>*)ft->ptw_row_inv_p, (const T*)x + (OFF),                           \
-                               beam ? (const T*)beam + (OFF) : nullptr,                                          \
-                               dot_with2 ? (const T*)dot_with2 + (OFF) : nullptr, (T*)out + (OFF), (PART), d,    \
-                               (B0), p->nx / IP::G, p->nx / IP::G * (NB), (T)scale, (T)sigmainv, wq1)
-#define PFB_INVP2(MODE, BM) PFB_INVP3(MODE, BM, false, band0, nb, grid, 0, p->partials)
-#define PFB_INVP(MODE) do { if (beam) PFB_INVP2(MODE, true); else PFB_INVP2(MODE, false); } while (0)
+            using IP = typename K::IP;
+            const cplx<T> wq1 = wq1_of<T>(p);
+            // the (mode, beam given, pb) instantiation over bands [b0, b0 + nbl) on `grid` workgroups; the operands of
+            // band b0 lie `off` elements into x / beam / dot_with2 / out
+            auto launch = [&](int mode, bool pb, int b0, int nbl, int grid, size_t off, double* part) {
+                K::persistent([&](auto* k, int m, bool bm, bool pbv) {
+                    if (m != mode || bm != (beam != nullptr) || pbv != pb) return;
+                    hipLaunchKernelGGL(k, dim3(grid), dim3(IP::NT), IP::LDS, st,
+                                       (const cplx<T>*)p->T, (const cplx<T>*)ft->tab[TW_M],
+                                       (const cplx<T>*)ft->tab[PTWC_ROW_INV_P], (const T*)x + off,
+                                       beam ? (const T*)beam + off : nullptr,
+                                       dot_with2 ? (const T*)dot_with2 + off : nullptr, (T*)out + off, part, d,
+                                       b0, p->nx / IP::G, p->nx / IP::G * nbl, (T)scale, (T)sigmainv, wq1);
+                });
+            };
+            const int mode = !dot_with ? 0 : !dot_with2 ? 1 : 2;
             const int tiles_per_band = p->nx / IP::G, ntiles = tiles_per_band * nb;
             int grid = ntiles < IP::WG_PER_CU * ft->num_cu ? ntiles : IP::WG_PER_CU * ft->num_cu;
             if (per_band && dot_with) {
-                if constexpr (inv_pb_ok<T, L, EP>()) {
+                if constexpr (K::PER_BAND) {
                     if (dot_with2) {              // one launch, partials [3][nb][grid]
                         if ((size_t)grid * nb > (size_t)p->nx * p->nband) grid = p->nx * p->nband / nb;   // partials: nx x nband
-                        if (beam) PFB_INVP3(2, true, true, band0, nb, grid, 0, p->partials);
-                        else PFB_INVP3(2, false, true, band0, nb, grid, 0, p->partials);
-                        p->last_npartials = grid * nb;
-                        p->last_band_slots = grid;
-                        p->last_q_stride = grid * nb;
-                        p->last_band_stride = grid;
+                        launch(2, true, band0, nb, grid, 0, p->partials);
+                        p->last = {grid * nb, grid, grid * nb, grid};
                         return;
                     }
                 }
@@ -2427,39 +2437,23 @@ static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, in
                 // partials land at [bl][3][grid1]
                 const int grid1 = tiles_per_band < IP::WG_PER_CU * ft->num_cu ? tiles_per_band : IP::WG_PER_CU * ft->num_cu;
                 const size_t bandel = (size_t)p->nx * p->ny;
-                for (int bl = 0; bl < nb; ++bl) {
-                    double* part = p->partials + (size_t)bl * 3 * grid1;
-                    if (dot_with2) {
-                        if (beam) PFB_INVP3(2, true, false, band0 + bl, 1, grid1, bl * bandel, part);
-                        else PFB_INVP3(2, false, false, band0 + bl, 1, grid1, bl * bandel, part);
-                    } else {
-                        if (beam) PFB_INVP3(1, true, false, band0 + bl, 1, grid1, bl * bandel, part);
-                        else PFB_INVP3(1, false, false, band0 + bl, 1, grid1, bl * bandel, part);
-                    }
-                }
-                p->last_npartials = grid1 * nb;
-                p->last_band_slots = grid1;
-                p->last_q_stride = grid1;
-                p->last_band_stride = 3 * grid1;
+                for (int bl = 0; bl < nb; ++bl)
+                    launch(mode, false, band0 + bl, 1, grid1, bl * bandel, p->partials + (size_t)bl * 3 * grid1);
+                p->last = {grid1 * nb, grid1, grid1, 3 * grid1};
                 return;
             }
-            p->last_npartials = grid;
-            p->last_band_slots = nb == 1 ? grid : 0;
-            p->last_q_stride = grid;
-            p->last_band_stride = grid;
-            if (!dot_with) PFB_INVP(0);
-            else if (!dot_with2) PFB_INVP(1);
-            else PFB_INVP(2);
-#undef PFB_INVP
-#undef PFB_INVP2
-#undef PFB_INVP3
+            p->last = {grid, nb == 1 ? grid : 0, grid, grid};
+            launch(mode, false, band0, nb, grid, 0, p->partials);
             return;
         }
     }
+    constexpr int E = K::E;
+    using F = RegFft<T, L, E, RowCfg<T, L, true>::WAVE>;
+    constexpr int G = row_groups<T, L, E, RowCfg<T, L, true>::GMAX>();
     const size_t lds = 384 + sizeof(cplx<T>) * ((size_t)((F::PTWC + 1) & ~1) + (size_t)G * (F::LDS_ELEMS + 4) * (InvDb<T, L>::ON ? 2 : 1));
-    hipLaunchKernelGGL((k_row_inv_pow2<T, L, E>), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
-                       (const cplx<T>*)p->T, (const cplx<T>*)p->twQ, (const cplx<T>*)ft->twM,
-                       (const cplx<T>*)ft->ptw_row_inv, (const T*)x, (const T*)beam, (const T*)dot_with,
+    hipLaunchKernelGGL(K::plain(), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
+                       (const cplx<T>*)p->T, (const cplx<T>*)p->twQ, (const cplx<T>*)ft->tab[TW_M],
+                       (const cplx<T>*)ft->tab[PTWC_ROW_INV], (const T*)x, (const T*)beam, (const T*)dot_with,
                        (const T*)dot_with2, (T*)out, p->partials, d, band0, (T)scale, (T)sigmainv);
 }
 
@@ -2468,23 +2462,20 @@ static int apply_t(pfb_conv_plan* p, int band0, int nb, const void* x, const voi
                    double sigmainv, void* out, const void* dot_with, const void* dot_with2, bool per_band,
                    hipStream_t st) {
     const FastTables* ft = (const FastTables*)p->fast_tables;
-    const int H = p->nx, L = p->ny / 2;
+    const int L = p->ny / 2;
     prof_mark(p, st, 0);
-    switch (L) {
-#define X(NN) case NN: launch_row_fwd<T, NN>(p, ft, p->T, band0, nb, x, beam, (size_t)p->ny, (size_t)p->nx * p->ny, st); break;
-        PFB_POW2_SIZES(X)
-#undef X
-        default: set_error("pow2_apply: unsupported ny"); return PFB_ERR_UNSUPPORTED;
+    if (!for_pow2_size(L, [&](auto l) {
+            launch_row_fwd<T, l()>(p, ft, p->T, band0, nb, x, beam, (size_t)p->ny, (size_t)p->nx * p->ny, st);
+        })) {
+        set_error("pow2_apply: unsupported ny");
+        return PFB_ERR_UNSUPPORTED;
     }
     prof_mark(p, st, 1);
     if (int rc = pow2_col_launch(p, ft, band0, nb, st); rc != PFB_OK) return rc;
     prof_mark(p, st, 2);
-    switch (L) {
-#define X(NN) case NN: launch_row_inv<T, NN>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st); break;
-        PFB_POW2_SIZES(X)
-#undef X
-        default: break;
-    }
+    for_pow2_size(L, [&](auto l) {
+        launch_row_inv<T, l()>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
+    });
     prof_mark(p, st, 3);
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;

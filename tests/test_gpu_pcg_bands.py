@@ -75,6 +75,7 @@ def _dots_bands(amd, plan, x, w, beam, nb, w2=True):
     (2, 48, 40, np.float64, None),          # generic (line-per-workgroup) kernels
     (2, 100, 120, np.float64, 'embed'),     # embedded in a power-of-two plan
     (2, 9000, 24, np.float64, None),        # long-line coverage path
+    (3, 64, 2048, np.float64, None),        # fp64 1024-point rows (4-row 512-thread tiles): 16 tiles per band, boundaries inside a trip
 ])
 @pmp('with_beam', [False, True])
 def test_conv_dots_per_band(amd, case, with_beam):
