@@ -10,7 +10,7 @@
 // workgroup -> single-workgroup final sum in a fixed order), scalars stay in device
 // memory (alpha, beta are read by the kernels from there), the p.Ap product comes
 // fused out of the convolution epilogue (fftconv*.hip) -- or, in the parametrised solve (pfb_pcg_solve_param), out of the
-// second band mix of hessparam.hip, the operator step Pcg::param_op at the driver's three call sites.
+// second band mix of hessparam.hip: the two forms of the operator step PcgOp, the driver's whole view of A.
 // The 16-byte packs (V16, Pack, ld / st and their non-temporal forms), can_vec, emit_partials and k_final_sum live in
 // common.hpp, shared with the prox / primal-dual kernels of wavelet.hip.
 #include "conv_plan.hpp"
@@ -451,14 +451,27 @@ static int init_grid(size_t nvs, int nsys) {
     return g < 1 ? 1 : g;
 }
 
-// work: r, p, Ap, the state blocks, the partial sums; then the exact loop's alternates of x and r
-static size_t vec_bytes(const pfb_conv_plan* plan, int nb) {
-    const size_t esz = plan->dtype == PFB_F32 ? 4 : 8;
-    size_t b = (size_t)nb * plan->nx * plan->ny * esz;
-    return (b + 255) & ~(size_t)255;
-}
-static size_t state_bytes(int nsys) { return ((size_t)nsys * SB * sizeof(double) + 255) & ~(size_t)255; }
-static size_t ws_bytes(int nsys) { return sizeof(double) * 4 * (size_t)(nsys > RED_MAX_GRID ? nsys : RED_MAX_GRID); }
+// The work buffer of a solve, stated once: the byte offset of every region (each starts on a 256-byte boundary) and the
+// total, which is what the three pfb_pcg_*_work_bytes return.  NONE: the solve has no such region.
+//   r, p, Ap    nb bands each
+//   S           one state block per system
+//   ws          4 sums x max(nsys, RED_MAX_GRID) partials of the vector kernels
+//   xalt, ralt  `alternates` (the cube and the parametrised solve): second copies of x and r, nb bands each
+//   tmp, mixp   `param`: the operator step's own scratch (MixWork: one cube, the second mix's partials)
+struct PcgLayout {
+    static constexpr size_t NONE = ~(size_t)0;
+    size_t r, p, Ap, S, ws, xalt = NONE, ralt = NONE, tmp = NONE, mixp = NONE, total = 0;
+    PcgLayout(const pfb_conv_plan* plan, int nb, int nsys, bool alternates, bool param) {
+        auto take = [&](size_t bytes) { const size_t at = total; total += bytes; return at; };
+        const size_t vb = vec_bytes(plan, nb);
+        r = take(vb); p = take(vb); Ap = take(vb);
+        S = take(((size_t)nsys * SB * sizeof(double) + 255) & ~(size_t)255);
+        ws = take(sizeof(double) * 4 * (size_t)(nsys > RED_MAX_GRID ? nsys : RED_MAX_GRID));
+        if (alternates) { xalt = take(vb); ralt = take(vb); }
+        if (param) { const MixWork mw(plan); tmp = take(mw.total); mixp = tmp + mw.partials; }
+    }
+    template <typename U> U* at(void* work, size_t off) const { return off == NONE ? nullptr : (U*)((char*)work + off); }
+};
 
 // The exchange can lose a participant (include/pfb_hip.h, "Failure protocol"): with a hook the solver never waits for
 // the device unboundedly -- it polls an event, probes the exchange (count = 0) and gives up after PFB_COMM_TIMEOUT_S
@@ -519,15 +532,80 @@ struct PcgSync {
     }
 };
 
-// One solve: bands [band0, band0 + nb) as one system (the cube: inner products over all bands) or, `per_band`, every
-// band its own.  init(), then run() or run_exact(), then report().
-template <typename T>
-struct Pcg {
+// What an entry point asks for: bands [band0, band0 + nb) as one system (the cube: inner products over all bands) or,
+// `per_band`, every band its own; L, LH non-null: the parametrised solve (`beam` is then e).
+struct PcgSolve {
     pfb_conv_plan* plan;
     int band0, nb;
     bool per_band;
-    const T* b; T* x; T* r_out; const T* beam;
-    double wsum, sigmainv, mdiv_d, tol;
+    const void* b; void* x; void* r_out; const void* beam;
+    double wsum, sigmainv, mdiv, tol;
+    int maxit, minit, backtrack;
+    size_t lookahead_max;      // elements up to which the host looks one iteration late
+    void* work;
+    pfb_allreduce_fn allreduce; void* actx;
+    const void *L, *LH;
+    pfb_pcg_result* res;
+    hipStream_t st;
+};
+
+// The operator step: the driver's whole view of A, one operation per place it applies A.  Two forms: the convolution
+// of the solve's bands (Lm null), or mix -> convolution -> mix over all the plan's bands as one system (hessparam.hip),
+// whose three dots come out of the second mix into mixp.
+template <typename T>
+struct PcgOp {
+    pfb_conv_plan* plan;
+    int band0, nb, bps;        // the solve's bands [band0, band0 + nb); bands per system
+    size_t ns;                 // elements per system
+    bool per_band;
+    const T* beam;
+    double wsum, sigmainv;
+    const T *Lm, *LHm;
+    T* tmp;
+    double* mixp;
+    hipStream_t st;
+    // where apply_partials left system s's partials: k_iter_sums' (cp, bs, qs, bst)
+    struct Partials { const double* cp; int bs, qs, bst; };
+
+    int mix(const T* v, T* out, const T* rr, double* partials, int* G) const {
+        return hessparam_apply_partials(plan, Lm, LHm, beam, sigmainv, v, out, rr, tmp, partials, G, st);
+    }
+    // r = A x0 over all systems, no sums
+    int apply(const T* x0, T* r) const {
+        return Lm ? mix(x0, r, nullptr, nullptr, nullptr)
+                  : pfb_psfconv_apply(plan, band0, nb, x0, beam, wsum, sigmainv, r, nullptr, nullptr, (void*)st);
+    }
+    // Ap = A p on the systems [lo, lo + nl), with <p,Ap>, <rc,Ap>, <Ap,Ap> left as per-workgroup partials at *w
+    int apply_partials(const T* p, T* Ap, const T* rc, int lo, int nl, Partials* w) const {
+        if (Lm) {
+            int G = 0;
+            const int err = mix(p, Ap, rc, mixp, &G);
+            *w = {mixp, G, G, 0};
+            return err;
+        }
+        const size_t off = (size_t)lo * ns;
+        w->cp = plan->partials;
+        return psfconv_apply_partials(plan, band0 + lo * bps, nl * bps, p + off, beam ? beam + off : nullptr, wsum,
+                                      sigmainv, Ap + off, p + off, rc + off, per_band, &w->bs, &w->qs, &w->bst, (void*)st);
+    }
+    // Ap = A p over all systems, <p,Ap> summed into *pap (device)
+    int apply_dot(const T* p, T* Ap, double* pap) const {
+        if (!Lm) return pfb_psfconv_apply(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, pap, (void*)st);
+        int G = 0;
+        const int err = mix(p, Ap, nullptr, mixp, &G);
+        if (err == PFB_OK)
+            hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, (const double*)mixp, G, 1, pap);
+        return err;
+    }
+};
+
+// One solve.  init(), then run() or run_exact(), then report().
+template <typename T>
+struct Pcg {
+    pfb_conv_plan* plan;
+    int nb;
+    const T* b; T* x; T* r_out;
+    double mdiv_d, tol;
     int maxit, minit;
     PcgSync sync;
     hipStream_t st;
@@ -538,30 +616,21 @@ struct Pcg {
     double *S, *ws;
     T mdiv;
     std::vector<double> h;     // the host's copy of the state blocks
-    // the parametrised solve (pfb_pcg_solve_param): the operator step is param_op() instead of the convolution alone;
-    // `beam` is then e, and mixp holds the partials of the three dots that come out of the second band mix
-    const T *Lm = nullptr, *LHm = nullptr;
-    T* tmp = nullptr;
-    double* mixp = nullptr;
+    PcgOp<T> A;
 
-    Pcg(pfb_conv_plan* plan_, int band0_, int nb_, bool per_band_, const void* b_, void* x_, void* r_out_,
-        const void* beam_, double wsum_, double sigmainv_, double mdiv_, double tol_, int maxit_, int minit_, void* work,
-        pfb_allreduce_fn allreduce, void* actx, hipStream_t st_)
-        : plan(plan_), band0(band0_), nb(nb_), per_band(per_band_), b((const T*)b_), x((T*)x_), r_out((T*)r_out_),
-          beam((const T*)beam_), wsum(wsum_), sigmainv(sigmainv_), mdiv_d(mdiv_), tol(tol_), maxit(maxit_),
-          minit(minit_), sync{allreduce, actx, st_}, st(st_), nsys(per_band_ ? nb_ : 1), mdiv((T)mdiv_),
-          h((size_t)nsys * SB) {
+    explicit Pcg(const PcgSolve& q)
+        : plan(q.plan), nb(q.nb), b((const T*)q.b), x((T*)q.x), r_out((T*)q.r_out), mdiv_d(q.mdiv), tol(q.tol),
+          maxit(q.maxit), minit(q.minit), sync{q.allreduce, q.actx, q.st}, st(q.st), nsys(q.per_band ? q.nb : 1),
+          mdiv((T)q.mdiv), h((size_t)nsys * SB) {
         n = (size_t)nb * plan->nx * plan->ny;
         ns = n / nsys;
-        const size_t vb = vec_bytes(plan, nb);
-        char* w = (char*)work;
-        r = (T*)w; p = (T*)(w + vb); Ap = (T*)(w + 2 * vb);
-        S = (double*)(w + 3 * vb);
-        ws = (double*)(w + 3 * vb + state_bytes(nsys));
-        // alternates of x and r: only in the cube solve's work buffer (pfb_pcg_work_bytes); without them x and r are
-        // updated in place
-        xalt = per_band ? nullptr : (T*)(w + 3 * vb + state_bytes(nsys) + ws_bytes(nsys));
-        ralt = per_band ? nullptr : (T*)((char*)xalt + vb);
+        // alternates of x and r: not in the per-band solve's work buffer, where x and r are updated in place
+        const PcgLayout lay(plan, nb, nsys, !q.per_band, q.L != nullptr);
+        r = lay.at<T>(q.work, lay.r); p = lay.at<T>(q.work, lay.p); Ap = lay.at<T>(q.work, lay.Ap);
+        S = lay.at<double>(q.work, lay.S); ws = lay.at<double>(q.work, lay.ws);
+        xalt = lay.at<T>(q.work, lay.xalt); ralt = lay.at<T>(q.work, lay.ralt);
+        A = {plan, q.band0, nb, nb / nsys, ns, q.per_band, (const T*)q.beam, q.wsum, q.sigmainv, (const T*)q.L,
+             (const T*)q.LH, lay.at<T>(q.work, lay.tmp), lay.at<double>(q.work, lay.mixp), st};
         using PL = std::initializer_list<const void*>;
         // decided once for every vector kernel of the solve (r, p, Ap and the alternates are 256-byte aligned parts of
         // `work`).  A caller whose x or b is not 16-byte aligned gets the scalar kernels throughout, init included
@@ -569,20 +638,12 @@ struct Pcg {
         nvs = vec ? ns / V16<T>::N : ns;
     }
 
-    // out = A(v) of the parametrised solve (hessparam.hip); `dots`: the partials of <v,out>, <rr,out>, <out,out> in mixp,
-    // *G of each
-    int param_op(const T* v, T* out, const T* rr, bool dots, int* G) {
-        return hessparam_apply_partials(plan, Lm, LHm, beam, sigmainv, v, out, rr, tmp, dots ? mixp : nullptr, G, st);
-    }
-
     // r = A(x0) - b ; y = M r ; p = -y ; the state blocks, on the device and in h          pcg.py:71-76
     int init() {
         int err;
         if ((err = sync.open()) != PFB_OK) return err;
         PFB_HIP_CHECK(hipMemsetAsync(S, 0, sizeof(double) * h.size(), st));
-        err = Lm ? param_op(x, r, nullptr, false, nullptr)
-                 : pfb_psfconv_apply(plan, band0, nb, x, beam, wsum, sigmainv, r, nullptr, nullptr, (void*)st);
-        if (err != PFB_OK) return err;
+        if ((err = A.apply(x, r)) != PFB_OK) return err;
         const int gps = init_grid(nvs, nsys);
         if (vec)
             hipLaunchKernelGGL((k_pcg_init<T, V16<T>::N>), dim3(nsys * gps), dim3(RED_BLOCK), 0, st, r, b, p, mdiv, nvs,
@@ -609,7 +670,6 @@ struct Pcg {
     // -- with sharded bands one all-reduce each, merged into ONE per iteration while k < minit.
     int run(int predict, size_t lookahead_max) {
         const size_t nS = h.size();
-        const int bps = nb / nsys;                 // bands per system
         const bool hook = sync.allreduce != nullptr;
         auto any_live = [&](const double* hs) {
             for (int s = 0; s < nsys; ++s) if (sys_live(hs + (size_t)s * SB)) return true;
@@ -655,21 +715,13 @@ struct Pcg {
         while (go) {
             const size_t off = (size_t)lo * ns;
             double* Sl = S + (size_t)lo * SB;
-            int bs, qs, bst;                       // where the operator step left system s's partials: k_iter_sums
-            const double* cp = plan->partials;
-            if (Lm) {                              // one system over all bands: the second mix's partials
-                err = param_op(p, Ap, rc, true, &bs);
-                qs = bs; bst = 0; cp = mixp;
-            } else
-                err = psfconv_apply_partials(plan, band0 + lo * bps, nl * bps, p + off, beam ? beam + off : nullptr,
-                                             wsum, sigmainv, Ap + off, p + off, rc + off, per_band, &bs, &qs, &bst,
-                                             (void*)st);
-            if (err != PFB_OK) return err;
+            typename PcgOp<T>::Partials c;
+            if ((err = A.apply_partials(p, Ap, rc, lo, nl, &c)) != PFB_OK) return err;
             // ONE scalar launch per iteration: the convolution's dots, the previous update's sums
             // (left pending while nobody can look at k / eps, i.e. while k < minit) and the
             // bookkeeping; with sharded bands the all-reduce of those 7 (or 4) scalars sits between
             // the sums and the bookkeeping -- one RCCL call per iteration instead of two.
-            hipLaunchKernelGGL(k_iter_sums, dim3(nl), dim3(256), 0, st, cp, bs, qs, bst,
+            hipLaunchKernelGGL(k_iter_sums, dim3(nl), dim3(256), 0, st, c.cp, c.bs, c.qs, c.bst,
                                (const double*)ws, gpl, pending_end ? 1 : 0, Sl, mdiv_d, predict, hook ? 0 : 1);
             // Behind a stop (the look-ahead's one speculative iteration) k_iter_sums writes nothing, so these exchanges
             // sum S_PAP .. S_ANY over the ranks a second time.  Every rank stops on the same reduced scalars, so all
@@ -748,14 +800,7 @@ struct Pcg {
         bool broke = false;
         while (h[S_ZERO] == 0.0 && (eps > tol || k < minit) && k < maxit) {
             // Ap = A(p); S_PAP = <p,Ap>                                                     pcg.py:89-91
-            if (Lm) {
-                int Gm = 0;
-                if ((err = param_op(p, Ap, nullptr, true, &Gm)) == PFB_OK)
-                    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, (const double*)mixp, Gm, 1,
-                                       S + S_PAP);
-            } else
-                err = pfb_psfconv_apply(plan, band0, nb, p, beam, wsum, sigmainv, Ap, p, S + S_PAP, (void*)st);
-            if (err != PFB_OK) return err;
+            if ((err = A.apply_dot(p, Ap, S + S_PAP)) != PFB_OK) return err;
             if ((err = sync.reduce(S + S_PAP, 1)) != PFB_OK) return err;
             hipLaunchKernelGGL(k_set_alpha, dim3(1), dim3(1), 0, st, S);
             for (;;) {
@@ -815,25 +860,25 @@ struct Pcg {
 };
 
 template <typename T>
-static int pcg_solve(pfb_conv_plan* plan, int band0, int nb, bool per_band, const void* b, void* x, void* r_out,
-                     const void* beam, double wsum, double sigmainv, double mdiv, double tol, int maxit, int minit,
-                     int backtrack, size_t lookahead_max, void* work, pfb_allreduce_fn allreduce, void* actx,
-                     pfb_pcg_result* res, hipStream_t st, const void* L = nullptr, const void* LH = nullptr) {
-    Pcg<T> s(plan, band0, nb, per_band, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit, work, allreduce,
-             actx, st);
-    if (L) {       // the parametrised solve: one more cube and the mix's partials behind the cube solve's layout
-        char* w = (char*)work + 5 * vec_bytes(plan, nb) + state_bytes(1) + ws_bytes(1);
-        s.Lm = (const T*)L; s.LHm = (const T*)LH;
-        s.tmp = (T*)w;
-        s.mixp = (double*)(w + vec_bytes(plan, nb));
-    }
-    PFB_REQUIRE(!allreduce || s.nsys == 1, PFB_ERR_INVALID, "pcg: an all-reduce hook needs the bands to be one system");
-    memset(res, 0, sizeof(*res) * s.nsys);
+static int pcg_solve(const PcgSolve& q) {
+    Pcg<T> s(q);
+    PFB_REQUIRE(!q.allreduce || s.nsys == 1, PFB_ERR_INVALID, "pcg: an all-reduce hook needs the bands to be one system");
+    memset(q.res, 0, sizeof(*q.res) * s.nsys);
     int err = s.init();
     // beta always comes from rho(alpha) in the sync-free driver: predict 2 with, 3 without the line search
-    if (err == PFB_OK) err = backtrack == 1 ? s.run_exact() : s.run(backtrack == 2 ? 2 : 3, lookahead_max);
-    if (err == PFB_OK) s.report(res);
+    if (err == PFB_OK) err = q.backtrack == 1 ? s.run_exact() : s.run(q.backtrack == 2 ? 2 : 3, q.lookahead_max);
+    if (err == PFB_OK) s.report(q.res);
     return err;
+}
+
+// what the three entry points (`who`) check alike, and the one fork by dtype
+static int pcg_checked(const char* who, const PcgSolve& q) {
+    PFB_REQUIRE(q.plan && q.b && q.x && q.work && q.res, PFB_ERR_INVALID, "%s: null argument", who);
+    PFB_REQUIRE(q.band0 >= 0 && q.nb > 0 && q.band0 + q.nb <= q.plan->nband, PFB_ERR_INVALID,
+                "%s: band range [%d,%d) outside plan", who, q.band0, q.band0 + q.nb);
+    PFB_REQUIRE((reinterpret_cast<uintptr_t>(q.work) & 255u) == 0, PFB_ERR_INVALID,
+                "%s: work must be 256-byte aligned", who);
+    return q.plan->dtype == PFB_F32 ? pcg_solve<float>(q) : pcg_solve<double>(q);
 }
 
 }  // namespace pfb
@@ -868,71 +913,50 @@ int pfb_axpby(int dtype, double a, const void* x, double b, void* y, size_t n, v
 }
 size_t pfb_pcg_work_bytes(const pfb_conv_plan* plan, int nb) {
     if (!plan || nb <= 0) return 0;
-    return 5 * vec_bytes(plan, nb) + state_bytes(1) + ws_bytes(1);
+    return PcgLayout(plan, nb, 1, true, false).total;
 }
 
 int pfb_pcg_solve(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
                   const void* beam, double wsum, double sigmainv, double mdiv, double tol,
                   int maxit, int minit, int backtrack, void* work, pfb_allreduce_fn allreduce,
                   void* allreduce_ctx, pfb_pcg_result* result, void* stream) {
-    PFB_REQUIRE(plan && b && x && work && result, PFB_ERR_INVALID, "pcg_solve: null argument");
-    PFB_REQUIRE(band0 >= 0 && nb > 0 && band0 + nb <= plan->nband, PFB_ERR_INVALID,
-                "pcg_solve: band range [%d,%d) outside plan", band0, band0 + nb);
-    PFB_REQUIRE((reinterpret_cast<uintptr_t>(work) & 255u) == 0, PFB_ERR_INVALID,
-                "pcg_solve: work must be 256-byte aligned");
-    const size_t la = (size_t)4 << 20;         // elements up to which the host looks one iteration late
-    if (plan->dtype == PFB_F32)
-        return pcg_solve<float>(plan, band0, nb, false, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
-                                backtrack, la, work, allreduce, allreduce_ctx, result, as_stream(stream));
-    return pcg_solve<double>(plan, band0, nb, false, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
-                             backtrack, la, work, allreduce, allreduce_ctx, result, as_stream(stream));
+    return pcg_checked("pcg_solve", {plan, band0, nb, false, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
+                                     backtrack, (size_t)4 << 20, work, allreduce, allreduce_ctx, nullptr, nullptr, result,
+                                     as_stream(stream)});
 }
 
 size_t pfb_pcg_param_work_bytes(const pfb_conv_plan* plan, int nb) {
     if (!plan || nb != plan->nband) return 0;
-    return pfb_pcg_work_bytes(plan, nb) + vec_bytes(plan, nb) + sizeof(double) * 3 * MIX_MAX_GRID;
+    return PcgLayout(plan, nb, 1, true, true).total;
 }
 
 int pfb_pcg_solve_param(pfb_conv_plan* plan, int nb, const void* L, const void* LH, const void* e, const void* b,
                         void* x, void* r_out, double sigmainv, double mdiv, double tol, int maxit, int minit,
                         int backtrack, void* work, pfb_pcg_result* result, void* stream) {
-    PFB_REQUIRE(plan && L && LH && b && x && work && result, PFB_ERR_INVALID, "pcg_solve_param: null argument");
+    PFB_REQUIRE(plan && L && LH, PFB_ERR_INVALID, "pcg_solve_param: null argument");
     PFB_REQUIRE(nb == plan->nband, PFB_ERR_INVALID,
                 "pcg_solve_param: the band mix couples all %d bands of the plan, nb = %d", plan->nband, nb);
     PFB_REQUIRE(nb <= 16, PFB_ERR_UNSUPPORTED, "pcg_solve_param: nband %d > 16", nb);
     PFB_REQUIRE(backtrack >= 0 && backtrack <= 2, PFB_ERR_INVALID, "pcg_solve_param: backtrack must be 0, 1 or 2");
-    PFB_REQUIRE((reinterpret_cast<uintptr_t>(work) & 255u) == 0, PFB_ERR_INVALID,
-                "pcg_solve_param: work must be 256-byte aligned");
-    const size_t la = (size_t)4 << 20;
-    if (plan->dtype == PFB_F32)
-        return pcg_solve<float>(plan, 0, nb, false, b, x, r_out, e, 0.5, sigmainv, mdiv, tol, maxit, minit, backtrack, la,
-                                work, nullptr, nullptr, result, as_stream(stream), L, LH);
-    return pcg_solve<double>(plan, 0, nb, false, b, x, r_out, e, 0.5, sigmainv, mdiv, tol, maxit, minit, backtrack, la,
-                             work, nullptr, nullptr, result, as_stream(stream), L, LH);
+    return pcg_checked("pcg_solve_param", {plan, 0, nb, false, b, x, r_out, e, 0.5, sigmainv, mdiv, tol, maxit, minit,
+                                           backtrack, (size_t)4 << 20, work, nullptr, nullptr, L, LH, result,
+                                           as_stream(stream)});
 }
 
 size_t pfb_pcg_bands_work_bytes(const pfb_conv_plan* plan, int nb) {
     if (!plan || nb <= 0) return 0;
-    return 3 * vec_bytes(plan, nb) + state_bytes(nb) + ws_bytes(nb);
+    return PcgLayout(plan, nb, nb, false, false).total;
 }
 
 int pfb_pcg_solve_bands(pfb_conv_plan* plan, int band0, int nb, const void* b, void* x, void* r_out,
                         const void* beam, double wsum, double sigmainv, double mdiv, double tol,
                         int maxit, int minit, int backtrack, void* work, pfb_pcg_result* results, void* stream) {
-    PFB_REQUIRE(plan && b && x && work && results, PFB_ERR_INVALID, "pcg_solve_bands: null argument");
-    PFB_REQUIRE(band0 >= 0 && nb > 0 && band0 + nb <= plan->nband, PFB_ERR_INVALID,
-                "pcg_solve_bands: band range [%d,%d) outside plan", band0, band0 + nb);
-    PFB_REQUIRE((reinterpret_cast<uintptr_t>(work) & 255u) == 0, PFB_ERR_INVALID,
-                "pcg_solve_bands: work must be 256-byte aligned");
     PFB_REQUIRE(backtrack != 1, PFB_ERR_UNSUPPORTED,
                 "pcg_solve_bands: backtrack=1 (the exact loop) is not batched; solve band by band with pfb_pcg_solve");
     PFB_REQUIRE(backtrack == 0 || backtrack == 2, PFB_ERR_INVALID, "pcg_solve_bands: backtrack must be 0 or 2");
-    const size_t la = (size_t)16 << 20;
-    if (plan->dtype == PFB_F32)
-        return pcg_solve<float>(plan, band0, nb, true, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
-                                backtrack, la, work, nullptr, nullptr, results, as_stream(stream));
-    return pcg_solve<double>(plan, band0, nb, true, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit, minit,
-                             backtrack, la, work, nullptr, nullptr, results, as_stream(stream));
+    return pcg_checked("pcg_solve_bands", {plan, band0, nb, true, b, x, r_out, beam, wsum, sigmainv, mdiv, tol, maxit,
+                                           minit, backtrack, (size_t)16 << 20, work, nullptr, nullptr, nullptr, nullptr,
+                                           results, as_stream(stream)});
 }
 
 }  // extern "C"

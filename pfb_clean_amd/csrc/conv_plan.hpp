@@ -57,6 +57,11 @@ struct pfb_conv_plan {
 };
 
 namespace pfb {
+// bytes of `nb` bands of the plan's images, rounded up to the 256 bytes every region of a work buffer starts on
+inline size_t vec_bytes(const pfb_conv_plan* plan, int nb) {
+    const size_t b = (size_t)nb * plan->nx * plan->ny * (plan->dtype == PFB_F32 ? 4 : 8);
+    return (b + 255) & ~(size_t)255;
+}
 constexpr int PROF_MAX = 512;
 // record stage boundary `k` (0..3) of the current apply on `st` when profiling is on
 inline void prof_mark(pfb_conv_plan* p, hipStream_t st, int k) {

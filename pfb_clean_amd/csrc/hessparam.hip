@@ -120,11 +120,6 @@ static int bandmix_partials(int dtype, const void* A, const void* c, int nband, 
                             : bandmix_t<double>(A, c, nband, npix, sigmainv, p, r, out, partials, grid, st);
 }
 
-static size_t cube_bytes(const pfb_conv_plan* plan) {
-    const size_t b = (size_t)plan->nband * plan->nx * plan->ny * (plan->dtype == PFB_F32 ? 4 : 8);
-    return (b + 255) & ~(size_t)255;
-}
-
 // mix (L) -> convolution with the e sandwich and wsum = 0.5 -> mix (L^T) + sigmainv x [+ partials].  `out` holds L x
 // between the first two steps, `tmp` the convolution's output (which may not alias its input).
 int hessparam_apply_partials(pfb_conv_plan* plan, const void* L, const void* LH, const void* e, double sigmainv,
@@ -159,7 +154,7 @@ int pfb_bandmix_dots(int dtype, const void* A, const void* c, int nband, size_t 
 
 size_t pfb_hessparam_work_bytes(const pfb_conv_plan* plan) {
     if (!plan) return 0;
-    return cube_bytes(plan) + sizeof(double) * 3 * MIX_MAX_GRID;
+    return MixWork(plan).total;
 }
 
 static int hessparam_checked(pfb_conv_plan* plan, const void* L, const void* LH, const void* e, double sigmainv,
@@ -174,7 +169,7 @@ static int hessparam_checked(pfb_conv_plan* plan, const void* L, const void* LH,
     PFB_REQUIRE(!dots_out || dot_with == x, PFB_ERR_UNSUPPORTED,
                 "hessparam_apply_dots: dot_with must be x itself (the products the PCG and the power method form)");
     hipStream_t st = as_stream(stream);
-    double* partials = dots_out ? (double*)((char*)work + cube_bytes(plan)) : nullptr;
+    double* partials = dots_out ? (double*)((char*)work + MixWork(plan).partials) : nullptr;
     int G = 0;
     const int rc = hessparam_apply_partials(plan, L, LH, e, sigmainv, x, out, dot_with2, work, partials, &G, st);
     if (rc != PFB_OK || !dots_out) return rc;

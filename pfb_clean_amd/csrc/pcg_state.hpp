@@ -2,7 +2,7 @@
 // it.  A SYSTEM is a contiguous run of bands that is solved as one PCG -- the whole cube (pfb_pcg_solve) or one band
 // (pfb_pcg_solve_bands) -- and owns one state block of SB doubles, S + s * SB.
 #pragma once
-#include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace pfb {
 
@@ -71,5 +71,12 @@ constexpr int MIX_MAX_GRID = 1024;
 int hessparam_apply_partials(pfb_conv_plan* plan, const void* L, const void* LH, const void* e, double sigmainv,
                              const void* x, void* out, const void* r, void* tmp, double* partials, int* grid,
                              hipStream_t st);
+// its scratch, stated once: `tmp` at the start, the partials behind it (pfb_hessparam_work_bytes; the tail of the
+// parametrised solve's work buffer, cgvec.hip)
+struct MixWork {
+    size_t partials, total;
+    explicit MixWork(const pfb_conv_plan* plan)
+        : partials(vec_bytes(plan, plan->nband)), total(partials + sizeof(double) * 3 * MIX_MAX_GRID) {}
+};
 
 }  // namespace pfb

@@ -66,6 +66,17 @@ class HessianPsf:
                               sigmainv=self.sigmainv, band0=self.band0)
         return _dev.host_like(res, x)
 
+    def apply_dots(self, x, out, dots_out):
+        """out = A(x) for contiguous device cubes of the plan's own grid, with <x, A x> left in dots_out[0] and
+        <A x, A x> in dots_out[2] (device fp64) out of the convolution's epilogue."""
+        plan = self.plan
+        with plan.lock:
+            plan._enter_stream()
+            _lib.check(_lib.load().pfb_psfconv_apply_dots(
+                plan.handle, self.band0, self.nb, _dev.ptr(x), _dev.ptr(self.beam),
+                self.wsum if self.wsum is not None else 0.0, self.sigmainv, _dev.ptr(out), _dev.ptr(x), None,
+                _dev.ptr(dots_out), _dev.stream()))
+
 
 class hessian_psf_slice:
     """pfb/operators/hessian.py:161-251 -- the per-band stateful operator (only referenced
@@ -232,7 +243,7 @@ class ParamHessian:
                                                        _dev.ptr(self.e), self.sigmainv, _dev.ptr(xs), _dev.ptr(buf),
                                                        _dev.ptr(self._work), _dev.stream()))
         if plan.embed is not None:
-            buf = buf[:, :self.nx, :self.ny]
+            buf = plan._crop(buf)
             if out is not None:
                 out.copy_(buf)
                 buf = out
@@ -242,6 +253,15 @@ class ParamHessian:
             out.copy_(buf)
             buf = out
         return _dev.host_like(buf, x)
+
+    def apply_dots(self, x, out, dots_out):
+        """As HessianPsf.apply_dots, the sums out of the second band mix."""
+        plan = self.plan
+        with plan.lock:
+            plan._enter_stream()
+            _lib.check(_lib.load().pfb_hessparam_apply_dots(
+                plan.handle, _dev.ptr(self.L), _dev.ptr(self.LH), _dev.ptr(self.e), self.sigmainv, _dev.ptr(x),
+                _dev.ptr(out), _dev.ptr(x), None, _dev.ptr(dots_out), _dev.ptr(self._work), _dev.stream()))
 
 
 def hessian_psf(psfo, x0, sigmainv, df, dhf, v, _nofuse=False):

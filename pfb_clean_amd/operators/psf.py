@@ -158,6 +158,22 @@ class PsfConvPlan(NativePlan):
         z[:, :self.nx, :self.ny] = t
         return z
 
+    def _crop(self, t):
+        """The image part of a padded (nb, nx2, ny2) cube, as a view (embedded plans only)."""
+        return t[:, :self.nx, :self.ny]
+
+    def _solve_work(self, kind, nb):
+        """Device scratch of a fused solve (opt/pcg.py) in the layout `kind` ('' the cube solve's, 'bands_', 'param_':
+        pfb_pcg_<kind>work_bytes), kept on the plan like the padded buffers of apply() and freed with it.  Per stream and
+        per host thread: the reference may drive per-band solves from several dask threads (pcg.py:346-356); solves on
+        ONE plan are serialised by `lock`, but a thread's result must not be overwritten by the next thread's solve."""
+        cache = self.__dict__.setdefault('_work_cache', {})
+        key = (kind, nb, _dev.stream(), threading.get_ident())
+        if key not in cache:
+            nbytes = getattr(self._lib, f'pfb_pcg_{kind}work_bytes')(self._h, nb)
+            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return cache[key]
+
     @classmethod
     def from_psf(cls, psf, nx, ny, want_psfhat=False):
         """Build the plan straight from the real PSF cube (nband, nx_psf, ny_psf) | (nx_psf, ny_psf):

@@ -30,7 +30,6 @@ import functools
 import math
 import os
 import sys
-import threading
 
 import torch
 
@@ -120,39 +119,15 @@ def _backtrack_mode(backtrack):
     return 2
 
 
-class _Work:
-    """Device scratch for pfb_pcg_solve, cached per (plan, nb, stream).  id(plan) can be re-used
-    by a NEW plan object of a different size once the old one is garbage collected, so the cached
-    buffer is only handed out if it has exactly the size this plan asks for."""
-    _cache = {}
-
-    @classmethod
-    def get(cls, plan, nb, bands=False, param=False):
-        # per host thread: the reference may drive per-band solves from several dask threads
-        # (pcg.py:346-356).  Solves on ONE plan are serialised by plan.lock (the plan's spectrum workspace and
-        # dot partials are single-owner); the vectors of a solve still live in a per-thread scratch so that a
-        # thread's result buffers are not overwritten by the next thread's solve.  bands: the batched solver's
-        # layout (pfb_pcg_bands_work_bytes); param: the parametrised solve's (pfb_pcg_param_work_bytes)
-        key = (id(plan), nb, bands, param, _dev.stream(), threading.get_ident())
-        lib = _lib.load()
-        nbytes = (lib.pfb_pcg_param_work_bytes if param else
-                  lib.pfb_pcg_bands_work_bytes if bands else lib.pfb_pcg_work_bytes)(plan.handle, nb)
-        w = cls._cache.get(key)
-        if w is None or w.numel() != nbytes or w.device != plan.device:
-            if len(cls._cache) > 16:
-                cls._cache.clear()
-            w = cls._cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=plan.device)
-        return w
-
-
 class _Staged:
     """What pcg_fused and pcg_fused_bands share around the native call: the checks on b, the contiguous copies, the
-    embedded plan's padding, the work buffer, and the way back (crop)."""
+    embedded plan's padding, the work buffer (kept on the plan, PsfConvPlan._solve_work), the call itself and the way
+    back (crop).  `kind`: the work buffer's layout for a HessianPsf, '' (the cube solve's) or 'bands_'."""
 
-    def __init__(self, A, b3, x0, return_resid, bands=False):
+    def __init__(self, A, b3, x0, return_resid, kind=''):
         self.plan = plan = A.plan
         b3 = b3.contiguous()
-        if bands and b3.ndim != 3:
+        if kind == 'bands_' and b3.ndim != 3:
             raise ValueError("pcg_fused_bands expects (nb, nx, ny) arrays")
         self.nb = nb = b3.shape[0]
         if nb != A.nb:
@@ -161,59 +136,53 @@ class _Staged:
             raise TypeError(f"b is {b3.dtype}, operator is {plan.rdtype}")
         x = torch.zeros_like(b3) if x0 is None else x0.contiguous().clone()
         param = isinstance(A, ParamHessian)
-        beam = A.e if param else A.beam         # a ParamHessian's e is padded already
-        if param:
-            self.work = _Work.get(plan, nb, param=True)
-            if plan.embed is not None:          # the same argument as below, with e in the beam's place
-                b3, x = plan._pad(b3, nb), plan._pad(x, nb)
-            self.b, self.x, self.beam = b3, x, beam
-            self.r = torch.empty_like(b3) if return_resid else None
-            return
+        beam = A.e if param else A.beam
         if plan.embed is not None:
             # Embedded plan (arbitrary size on the power-of-two kernels, operators/psf.py): solve in the
             # zero-padded domain with a beam that is ZERO outside the image.  There A' x' = sigmainv x',
             # b' = 0 and x0' = 0, so r, y, p stay exactly zero outside and every inner product, step
-            # length and stopping decision equals the un-padded solve's.
+            # length and stopping decision equals the un-padded solve's.  A ParamHessian's e is padded already.
             b3, x = plan._pad(b3, nb), plan._pad(x, nb)
-            beam = plan._pad(torch.ones((nb, plan.nx, plan.ny), dtype=plan.rdtype, device=b3.device)
-                             if beam is None else beam, nb)
+            if not param:
+                beam = plan._pad(torch.ones((nb, plan.nx, plan.ny), dtype=plan.rdtype, device=b3.device)
+                                 if beam is None else beam, nb)
         self.b, self.x, self.beam = b3, x, beam
         self.r = torch.empty_like(b3) if return_resid else None
-        self.work = _Work.get(plan, nb, bands=bands)
-        # band0, nb, b, x, r_out, beam, wsum, sigmainv: the arguments both entry points start with
-        self.args = (A.band0, nb, _dev.ptr(b3), _dev.ptr(x), _dev.ptr(self.r), _dev.ptr(beam),
-                     A.wsum if A.wsum is not None else 0.0, A.sigmainv)
+        self.work = plan._solve_work('param_' if param else kind, nb)
+        # what the entry point's arguments start with, up to sigmainv
+        ptr = _dev.ptr
+        if param:
+            self.args = (nb, ptr(A.L), ptr(A.LH), ptr(beam), ptr(b3), ptr(x), ptr(self.r), A.sigmainv)
+        else:
+            self.args = (A.band0, nb, ptr(b3), ptr(x), ptr(self.r), ptr(beam),
+                         A.wsum if A.wsum is not None else 0.0, A.sigmainv)
 
-    def result(self):
-        """(x, r|None) in the caller's domain."""
-        x, r, plan = self.x, self.r, self.plan
+    def solve(self, fn, mdiv, tol, maxit, minit, backtrack, *tail):
+        """fn(plan, *args, mdiv .. backtrack, work, *tail, stream), one solve at a time per plan (a plan is single-owner,
+        include/pfb_hip.h).  Returns (x, r|None) in the caller's domain."""
+        plan = self.plan
+        with plan.lock:
+            plan._enter_stream()
+            _lib.check(fn(plan.handle, *self.args, float(mdiv), float(tol), int(maxit), int(minit),
+                          _backtrack_mode(backtrack), _dev.ptr(self.work), *tail, _dev.stream()))
+        x, r = self.x, self.r
         if plan.embed is not None:
-            x = x[:, :plan.nx, :plan.ny].contiguous()
-            r = None if r is None else r[:, :plan.nx, :plan.ny].contiguous()
+            x = plan._crop(x).contiguous()
+            r = None if r is None else plan._crop(r).contiguous()
         return x, r
 
 
 def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack=True,
               return_resid=False, group=None, distributed=False):
-    """Run pfb_pcg_solve.  b, x0: GPU tensors (nb, nx, ny) | (nx, ny).  Returns
+    """Run pfb_pcg_solve (A a ParamHessian: pfb_pcg_solve_param).  b, x0: GPU tensors (nb, nx, ny) | (nx, ny).  Returns
     (x, r|None, PcgResult).  distributed=True: the bands of this call are one rank's
     shard of a cube solve; every inner product is all-reduced over `group`
     (pfb_clean_amd.dist.AllReduceHook, RCCL)."""
     lib = _lib.load()
-    plan = A.plan
-    if isinstance(A, ParamHessian):
-        if distributed:
-            raise ValueError("a ParamHessian couples every band: it cannot be solved on a band shard")
-        s = _Staged(A, b, x0, return_resid)
-        res = _lib.PcgResult()
-        with plan.lock:
-            plan._enter_stream()
-            _lib.check(lib.pfb_pcg_solve_param(plan.handle, s.nb, _dev.ptr(A.L), _dev.ptr(A.LH), _dev.ptr(s.beam),
-                                               _dev.ptr(s.b), _dev.ptr(s.x), _dev.ptr(s.r), A.sigmainv, float(mdiv),
-                                               float(tol), int(maxit), int(minit), _backtrack_mode(backtrack),
-                                               _dev.ptr(s.work), C.byref(res), _dev.stream()))
-        return s.result() + (res,)
-    squeeze = b.ndim == 2
+    param = isinstance(A, ParamHessian)
+    if param and distributed:
+        raise ValueError("a ParamHessian couples every band: it cannot be solved on a band shard")
+    squeeze = b.ndim == 2 and not param
     s = _Staged(A, b[None] if squeeze else b, x0[None] if squeeze and x0 is not None else x0, return_resid)
     res = _lib.PcgResult()
     cb_ctx = None
@@ -237,15 +206,13 @@ def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack
                     print(f"pfb_clean_amd: allreduce hook failed: {e!r}", file=sys.stderr)
                 return 1
         cb = _lib.ALLREDUCE_FN(_hook)
-    with plan.lock:            # a plan is single-owner (include/pfb_hip.h): one solve at a time per plan
-        plan._enter_stream()
-        _lib.check(lib.pfb_pcg_solve(plan.handle, *s.args, float(mdiv), float(tol), int(maxit), int(minit),
-                                     _backtrack_mode(backtrack), _dev.ptr(s.work), cb, cb_ctx, C.byref(res),
-                                     _dev.stream()))
+    if param:                        # no hook argument: a band shard cannot apply the mix
+        x, r = s.solve(lib.pfb_pcg_solve_param, mdiv, tol, maxit, minit, backtrack, C.byref(res))
+    else:
+        x, r = s.solve(lib.pfb_pcg_solve, mdiv, tol, maxit, minit, backtrack, cb, cb_ctx, C.byref(res))
     if distributed:                  # bench.py reports which exchange ran and what the hook costs the host
         res.exchange = 'rccl-native' if native is not None else 'torch-hook'
         res.hook_calls, res.hook_host_s = (0, 0.0) if native is not None else (allreduce.calls, allreduce.host_s)
-    x, r = s.result()
     if squeeze:
         x = x[0]
         r = None if r is None else r[0]
@@ -258,15 +225,9 @@ def pcg_fused_bands(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, bac
     batched device solve -- pcg_psf's semantics (pcg.py:243-360).  b, x0: GPU tensors (nb, nx, ny).  Returns
     (x, r|None, [PcgResult] * nb); a band with PFB_PCG_ZERO_RESIDUAL keeps x = x0.  backtrack='exact' (or
     PFB_PCG_EXACT_BACKTRACK=1) has no batched form: the library raises PfbHipError (unsupported)."""
-    lib = _lib.load()
-    plan = A.plan
-    s = _Staged(A, b, x0, return_resid, bands=True)
+    s = _Staged(A, b, x0, return_resid, kind='bands_')
     res = (_lib.PcgResult * s.nb)()
-    with plan.lock:
-        plan._enter_stream()
-        _lib.check(lib.pfb_pcg_solve_bands(plan.handle, *s.args, float(mdiv), float(tol), int(maxit), int(minit),
-                                           _backtrack_mode(backtrack), _dev.ptr(s.work), res, _dev.stream()))
-    x, r = s.result()
+    x, r = s.solve(_lib.load().pfb_pcg_solve_bands, mdiv, tol, maxit, minit, backtrack, res)
     return x, r, list(res)
 
 

@@ -23,12 +23,11 @@ import sys
 import numpy as np
 import torch
 
-from .. import _lib, _dev
+from .. import _dev
 
 
 def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_freq=25,
                  dtype=None, group=None):
-    lib = _lib.load()
     if group is not None:
         import torch.distributed as dist
         pg = None if group is True else group
@@ -49,24 +48,22 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
     bd = _dev.to_dev(b0).clone()
     out = _dev.scratch()[1]
 
-    # the fused path: A as the library's own operator on device tensors (HP: the band-coupled ParamHessian)
-    H = HP = None
+    # the fused path: A as the library's own operator on device tensors (HessianPsf or the band-coupled ParamHessian)
+    H = None
     if not _dev.is_numpy(b0):
         from .pcg import _as_hessian
         from ..operators.hessian import ParamHessian
         H = _as_hessian(A, bd)
         if isinstance(H, ParamHessian):
-            if H.plan.rdtype == bd.dtype:
-                if H.plan.embed is None:
-                    HP = H
-                else:
-                    A = H         # embedded plan: the operator as a whole (its fused apply pads and crops), plain dots
+            if H.plan.rdtype != bd.dtype:
+                H = None
+            elif H.plan.embed is not None:
+                A, H = H, None    # embedded plan: the operator as a whole (its fused apply pads and crops), plain dots
+        elif H is not None and (H.plan.rdtype != bd.dtype or H.plan.embed is not None or
+                                tuple(bd.shape[-2:]) != (H.nx, H.ny) or (bd.ndim == 3 and bd.shape[0] != H.nb)
+                                or (bd.ndim == 2 and H.nb != 1)):
             H = None
-        if H is not None and (H.plan.rdtype != bd.dtype or H.plan.embed is not None or
-                              tuple(bd.shape[-2:]) != (H.nx, H.ny) or (bd.ndim == 3 and bd.shape[0] != H.nb)
-                              or (bd.ndim == 2 and H.nb != 1)):
-            H = None
-    bout = torch.empty_like(bd) if H is not None or HP is not None else None
+    bout = torch.empty_like(bd) if H is not None else None
 
     _dev.axpby(0.0, bd, 1.0 / math.sqrt(allsum([_dev.dot(bd, bd)])[0]), bd)
     bp = bd.clone()
@@ -74,23 +71,7 @@ def power_method(A, imsize, b0=None, tol=1e-5, maxit=250, verbosity=1, report_fr
     beta, eps, k = 1.0, 1.0, 0
     while eps > tol and k < maxit:
         if H is not None:
-            b3 = bp if bp.ndim == 3 else bp[None]
-            with H.plan.lock:
-                H.plan._enter_stream()
-                _lib.check(lib.pfb_psfconv_apply_dots(
-                    H.plan.handle, H.band0, H.nb, _dev.ptr(b3), _dev.ptr(H.beam),
-                    H.wsum if H.wsum is not None else 0.0, H.sigmainv, _dev.ptr(bout), _dev.ptr(b3), None,
-                    _dev.ptr(out), _dev.stream()))                 # out[0] = <bp, b>, out[2] = <b, b>
-            b = bout
-            _dev.dot_into(bp, bp, out, 1)
-            pb, pp, bb = allsum(out[:3].tolist())
-        elif HP is not None:
-            with HP.plan.lock:
-                HP.plan._enter_stream()
-                _lib.check(lib.pfb_hessparam_apply_dots(
-                    HP.plan.handle, _dev.ptr(HP.L), _dev.ptr(HP.LH), _dev.ptr(HP.e), HP.sigmainv, _dev.ptr(bp),
-                    _dev.ptr(bout), _dev.ptr(bp), None, _dev.ptr(out), _dev.ptr(HP._work),
-                    _dev.stream()))                                # out[0] = <bp, b>, out[2] = <b, b>
+            H.apply_dots(bp, bout, out)                            # out[0] = <bp, b>, out[2] = <b, b>
             b = bout
             _dev.dot_into(bp, bp, out, 1)
             pb, pp, bb = allsum(out[:3].tolist())

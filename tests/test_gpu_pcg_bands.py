@@ -328,3 +328,66 @@ def test_solve_bands_argument_errors(amd):
     assert call() == 0
     with pytest.raises(_lib.PfbHipError):
         amd.pcg.pcg_fused_bands(A, b, None, backtrack='exact')
+
+
+# ------------------------------------------------------------------------------------------ work buffer bounds
+GUARD, SENTINEL = 4096, 0xA5
+
+
+def _guarded_solve(amd, plan, solve, nb, bt, b, L, slack):
+    """One native solve (3 fixed iterations, x0 = 0) whose `work` is a slice of a larger buffer: exactly the entry
+    point's *_work_bytes (+ slack) usable bytes with GUARD bytes of SENTINEL on either side.  Returns (x, result
+    fields, the two guard regions after the solve)."""
+    lib, _dev, _lib = amd.lib, amd.dev, amd._lib
+    nbytes = {'cube': lib.pfb_pcg_work_bytes, 'bands': lib.pfb_pcg_bands_work_bytes,
+              'param': lib.pfb_pcg_param_work_bytes}[solve](plan.handle, nb) + slack
+    assert nbytes > slack
+    big = torch.full((GUARD + nbytes + GUARD,), SENTINEL, dtype=torch.uint8, device='cuda')
+    work = big.data_ptr() + GUARD
+    assert work % 256 == 0
+    x, LH = torch.zeros_like(b), L.T.contiguous()
+    res = (_lib.PcgResult * nb)()
+    tail = (1.0, 1.0, 0.0, 3, 3, bt, work)           # sigmainv, mdiv, tol, maxit, minit, backtrack, work
+    with plan.lock:
+        plan._enter_stream()
+        if solve == 'cube':
+            rc = lib.pfb_pcg_solve(plan.handle, 0, nb, _dev.ptr(b), _dev.ptr(x), None, None, 0.0, *tail,
+                                   _lib.ALLREDUCE_FN(0), None, res, _dev.stream())
+        elif solve == 'bands':
+            rc = lib.pfb_pcg_solve_bands(plan.handle, 0, nb, _dev.ptr(b), _dev.ptr(x), None, None, 0.0, *tail, res,
+                                         _dev.stream())
+        else:
+            rc = lib.pfb_pcg_solve_param(plan.handle, nb, _dev.ptr(L), _dev.ptr(LH), None, _dev.ptr(b),
+                                         _dev.ptr(x), None, *tail, res, _dev.stream())
+    _lib.check(rc)
+    torch.cuda.synchronize()
+    nres = nb if solve == 'bands' else 1
+    fields = [tuple(getattr(r, f) for f, _ in _lib.PcgResult._fields_) for r in res[:nres]]
+    return x.cpu().numpy(), fields, (big[:GUARD].cpu().numpy(), big[GUARD + nbytes:].cpu().numpy())
+
+
+@pmp('rdt', [np.float32, np.float64])
+@pmp('solve,nb,bt', [('cube', 2, 2), ('cube', 2, 1), ('bands', 2, 2), ('param', 3, 2)])
+def test_solves_stay_inside_their_work_bytes(amd, solve, nb, bt, rdt):
+    """Every native solve writes inside the *_work_bytes it asks for: with exactly that many usable bytes between two
+    guard regions the guards stay untouched, and x and the results equal those of a solve with 64 KB to spare.
+    64 x 128 is the smallest fast-path image (the persistent kernels' partial layout); backtrack 1 is the one mode that
+    reaches the alternates through the exact loop; the layout does not depend on the plan class."""
+    nx, ny = 64, 128
+    u = np.fft.fftfreq(2 * nx)[:, None]
+    v = np.fft.rfftfreq(2 * ny)[None, :]
+    psfhat = np.stack([(1 + k) * np.exp(-(u ** 2 + v ** 2) / (2 * (0.1 + 0.05 * k) ** 2)) for k in range(nb)])
+    plan = amd.psf.PsfConvPlan(psfhat.astype(cdt(rdt)), nx, ny, 2 * ny)
+    assert plan.fast_path and plan.embed is None
+    rng = np.random.default_rng(5)
+    b = torch.from_numpy(rng.standard_normal((nb, nx, ny)).astype(rdt)).cuda()
+    L = torch.from_numpy(np.tril(0.5 + rng.random((nb, nb))).astype(rdt)).cuda()
+    x, res, guards = _guarded_solve(amd, plan, solve, nb, bt, b, L, 0)
+    for g in guards:
+        assert g.size == GUARD and (g == SENTINEL).all()
+    assert all(r[1] == 3 for r in res) and x.any(), res
+    x2, res2, guards2 = _guarded_solve(amd, plan, solve, nb, bt, b, L, 65536)
+    for g in guards2:
+        assert g.size == GUARD and (g == SENTINEL).all()
+    assert np.array_equal(x, x2)
+    assert res == res2
