@@ -1,5 +1,9 @@
-// fft_pow2.hpp -- register-resident power-of-two complex FFT shared by a group of
+// fft_pow2.hpp -- register-resident complex FFT of length 2^k, 3 2^k or 5 2^k shared by a group of
 // TPB = N/E threads (wave64-agnostic: groups may be a fraction of a wave or several).
+//
+// Lengths N = m 2^k with m = 3 or 5 carry the odd factor in E (E = m 2^a, so that TPB stays a power of two) and run it as
+// ONE radix-m pass, the LAST: every earlier predecessor product P is then a power of two (k = i & (P - 1)), in the last
+// pass P = N / m > i, and nothing is exchanged after it.  Everything below that speaks of "the radix" holds for it.
 //
 // Thread t of the group holds element t + TPB*j in register j (j < E) on entry AND on
 // exit (natural order both ways -> coalesced global access with no reordering pass).
@@ -24,37 +28,39 @@ namespace pfb {
 constexpr int ilog2(int n) { return n <= 1 ? 0 : 1 + ilog2(n >> 1); }
 constexpr int imin(int a, int b) { return a < b ? a : b; }
 
-// largest radix done in registers: min(E, 16); a thread with E > 16 elements runs E/16
-// radix-16 butterflies per pass
-constexpr int rmax_of(int E) { return E < 16 ? E : 16; }
+constexpr int odd_part(int n) { while (n > 1 && (n & 1) == 0) n >>= 1; return n; }
+constexpr int pow2_part(int n) { return n & -n; }
 
-// radix of the pass that starts with P elements already combined
-template <int N, int E, int P> struct PassRadix { static constexpr int R = imin(rmax_of(E), N / P); };
+// largest power-of-two radix done in registers: min(power-of-two part of E, 16); a thread with more elements runs
+// several butterflies per pass
+constexpr int rmax_of(int E) { return pow2_part(E) < 16 ? pow2_part(E) : 16; }
 
-// offset (in elements) of pass-with-product-P's twiddle block inside the ptw table
-template <int N, int E, int P>
-struct PtwOffset {
-    // passes before this one: products 1 (no twiddles), E, E^2, ...
-    static constexpr int RM = rmax_of(E);
-    static constexpr int prev = P / RM;         // product at the previous pass (P = prev * RM)
-    static constexpr int value = (P <= RM) ? 0 : PtwOffset<N, E, (P / RM < 1 ? 1 : P / RM)>::value + 4 * prev;
-};
-template <int N, int E> struct PtwOffset<N, E, 1> { static constexpr int value = 0; };
+// radix of the pass that starts with P elements already combined: the power-of-two passes first, the odd factor last
+constexpr int pass_radix(int N, int E, int P) {
+    const int N2 = N / odd_part(N);
+    return P < N2 ? imin(rmax_of(E), N2 / P) : odd_part(N);
+}
+template <int N, int E, int P> struct PassRadix { static constexpr int R = pass_radix(N, E, P); };
+
+// offset (in elements) of pass-with-product-P's twiddle block inside the ptw table: 4 P' elements for every earlier
+// pass with product P' > 1
+constexpr int ptw_offset(int N, int E, int P) {
+    int off = 0;
+    for (int p = pass_radix(N, E, 1); p < P; p *= pass_radix(N, E, p)) off += 4 * p;
+    return off;
+}
+template <int N, int E, int P> struct PtwOffset { static constexpr int value = ptw_offset(N, E, P); };
 
 template <int N, int E>
-constexpr int ptw_total() {
-    int tot = 0;
-    for (int P = rmax_of(E); P < N; P *= rmax_of(E)) tot += 4 * P;
-    return tot;
-}
+constexpr int ptw_total() { return ptw_offset(N, E, N); }
 
 // host: fill the table (long double accuracy, rounded once)
 template <typename T, int N, int E>
 void fill_ptw(cplx<T>* out) {
     const long double two_pi = 6.283185307179586476925286766559005768L;
     int off = 0;
-    for (int P = rmax_of(E); P < N; P *= rmax_of(E)) {
-        const int R = imin(rmax_of(E), N / P);
+    for (int P = pass_radix(N, E, 1); P < N; P *= pass_radix(N, E, P)) {
+        const int R = pass_radix(N, E, P);
         for (int m = 0; m < 4; ++m)
             for (int k = 0; k < P; ++k) {
                 long double a = two_pi * (long double)((long long)(1 << m) * k) / (long double)((long long)P * R);
@@ -69,8 +75,8 @@ template <typename T, int N, int E>
 void fill_ptw_compact(cplx<T>* out) {
     const long double two_pi = 6.283185307179586476925286766559005768L;
     int off = 0;
-    for (int P = rmax_of(E); P < N; P *= rmax_of(E)) {
-        const int R = imin(rmax_of(E), N / P);
+    for (int P = pass_radix(N, E, 1); P < N; P *= pass_radix(N, E, P)) {
+        const int R = pass_radix(N, E, P);
         for (int k = 0; k < P; ++k) {
             long double a = two_pi * (long double)k / (long double)((long long)P * R);
             out[off + k] = cplx<T>((T)cosl(a), (T)(-sinl(a)));
@@ -193,6 +199,34 @@ template <typename T, bool INV> struct Dft<T, INV, 16> {
     }
 };
 
+// the odd radices: X[k] = sum_n u[n] w_R^(nk), the conjugate pairs n, R - n folded (sums t, differences d)
+template <typename T, bool INV> struct Dft<T, INV, 3> {
+    __device__ __forceinline__ static void run(cplx<T> (&u)[3]) {
+        constexpr T S = T(0.86602540378443864676372317075293618347L);      // sin(2 pi / 3)
+        const cplx<T> t = u[1] + u[2], d = S * (u[1] - u[2]);
+        const cplx<T> m = u[0] - T(0.5) * t;
+        u[0] = u[0] + t;
+        u[1] = addrot<INV>(m, d);        // m -+ i d
+        u[2] = addrot<!INV>(m, d);
+    }
+};
+template <typename T, bool INV> struct Dft<T, INV, 5> {
+    __device__ __forceinline__ static void run(cplx<T> (&u)[5]) {
+        constexpr T C1 = T(0.30901699437494742410229341718281905886L);     // cos(2 pi / 5)
+        constexpr T C2 = T(-0.80901699437494742410229341718281905886L);    // cos(4 pi / 5)
+        constexpr T S1 = T(0.95105651629515357211643933337938214340L);     // sin(2 pi / 5)
+        constexpr T S2 = T(0.58778525229247312916870595463907276860L);     // sin(4 pi / 5)
+        const cplx<T> t1 = u[1] + u[4], t2 = u[2] + u[3], d1 = u[1] - u[4], d2 = u[2] - u[3];
+        const cplx<T> m1 = u[0] + (C1 * t1 + C2 * t2), m2 = u[0] + (C2 * t1 + C1 * t2);
+        const cplx<T> n1 = S1 * d1 + S2 * d2, n2 = S2 * d1 - S1 * d2;
+        u[0] = u[0] + (t1 + t2);
+        u[1] = addrot<INV>(m1, n1);      // m1 -+ i n1
+        u[4] = addrot<!INV>(m1, n1);
+        u[2] = addrot<INV>(m2, n2);
+        u[3] = addrot<!INV>(m2, n2);
+    }
+};
+
 // ------------------------------------------------------------------- the group FFT
 // WAVE: the TPB threads of a group sit inside ONE wavefront (TPB <= 64): the LDS exchanges
 // then need no s_barrier at all -- a wave's DS instructions execute in order, so its reads
@@ -219,9 +253,33 @@ struct NoPassHook {
 };
 template <int K> using PassIdx = std::integral_constant<int, K>;
 
+// padded index of the exchange after pass (P, R), CB bytes per element (RegFft::cxpad as a plain function)
+constexpr int fft_xpad(int P, int R, int c, int CB) {
+    const int slots = 128 / CB;
+    return P == 1 ? c + c / slots : P >= slots ? c : c + (c / (P * R)) * P;
+}
+// LDS elements of one transform's exchange buffer: room for every padding RegFft uses
+constexpr int fft_lds_elems(int N, int E, int CB) {
+    const int RM = rmax_of(E);
+    if (odd_part(N) == 1) return N + N / (RM < 128 / CB ? RM : 128 / CB);
+    // the last power-of-two pass may have a smaller radix than the others AND is followed by an exchange: take the
+    // largest padded index of any exchange, and of pad(N) (the row kernels park a transform under pad())
+    int need = N + (N >> 4) + 1;
+    for (int P = 1; P * pass_radix(N, E, P) < N; P *= pass_radix(N, E, P)) {
+        const int e = fft_xpad(P, pass_radix(N, E, P), N - 1, CB) + 1;
+        if (e > need) need = e;
+    }
+    return (need + 1) & ~1;
+}
+
 template <typename T, int N, int E, bool WAVE = false, int DBOFF = 0, bool SQTW = false, bool SEQX = false>
 struct RegFft {
-    static_assert((N & (N - 1)) == 0 && (E & (E - 1)) == 0 && N >= E, "power-of-two sizes");
+    static constexpr int ODD = odd_part(N);     // 1, or the radix of the last pass
+    static_assert((ODD == 1 || ODD == 3 || ODD == 5) && odd_part(E) == ODD && N >= E, "sizes 2^k, 3 2^k, 5 2^k; E carries the odd factor");
+    static_assert(ODD == 1 || pow2_part(E) >= 2, "the power-of-two passes need a radix");
+    // What the odd lengths run with: WAVE, SEQX (forward rows), SQTW and DBOFF (plain inverse rows: compact table in the
+    // LDS, second exchange buffer) -- all of them index by pass product and radix only.  The pass hook belongs to the
+    // persistent kernels, which do not take these lengths: pass() asserts against it.
     static_assert(!WAVE || N / E <= 64, "wave-local exchange needs the group inside one wave");
     __device__ __forceinline__ static void sync() {
         if constexpr (WAVE) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -229,7 +287,7 @@ struct RegFft {
     }
     static constexpr int TPB = N / E;
     static constexpr int RM = rmax_of(E);
-    static constexpr int LDS_ELEMS = N + N / (RM < (128 / (int)sizeof(cplx<T>)) ? RM : (128 / (int)sizeof(cplx<T>)));   // room for every padding below
+    static constexpr int LDS_ELEMS = fft_lds_elems(N, E, (int)sizeof(cplx<T>));   // room for every padding below
     static constexpr int PTW = ptw_total<N, E>();
     static constexpr int PTWC = ptw_total<N, E>() / 4;          // compact (w only) table size
 
@@ -273,6 +331,23 @@ struct RegFft {
             cplx<T> u[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) u[r] = v[q + r * NB];
+            if constexpr (R == 3 || R == 5) {
+                // the odd pass (the last one: P = N / R > i, so k = i): w, w^2 [, w^4] from the table, w^3 = w w^2
+                const int k = (t + TPB * q) & (P - 1);
+                const cplx<T>* tb = ptw + (SQTW ? PtwOffset<N, E, P>::value / 4 : PtwOffset<N, E, P>::value) + k;
+                auto tw = [](cplx<T> a, cplx<T> w) { return INV ? mulc(a, w) : a * w; };
+                const cplx<T> w1 = tb[0];
+                cplx<T> w2;
+                if constexpr (SQTW) w2 = w1 * w1; else w2 = tb[P];
+                u[1] = tw(u[1], w1);
+                u[2] = tw(u[2], w2);
+                if constexpr (R == 5) {
+                    cplx<T> w4;
+                    if constexpr (SQTW) w4 = w2 * w2; else w4 = tb[2 * P];
+                    u[3] = tw(u[3], w1 * w2);
+                    u[4] = tw(u[4], w4);
+                }
+            } else
             if constexpr (P > 1) {
                 const int k = (t + TPB * q) & (P - 1);
                 const cplx<T>* tb = ptw + (SQTW ? PtwOffset<N, E, P>::value / 4 : PtwOffset<N, E, P>::value) + k;
@@ -329,6 +404,7 @@ struct RegFft {
                                                 const cplx<T>* __restrict__ ptw, const Hook& hook = Hook()) {
         constexpr int R = PassRadix<N, E, P>::R;
         constexpr int NB = E / R;
+        static_assert(ODD == 1 || std::is_same<Hook, NoPassHook>::value, "pass hooks: power-of-two lengths only");
         hook(PassIdx<K>{});
 #pragma unroll
         for (int n = 0; n < NV; ++n) butterflies<INV, P>(v[n], t, ptw);

@@ -1,6 +1,11 @@
-// fftconv_pow2.hip -- the fast PSF-convolution path: power-of-two images with the
+// fftconv_pow2.hip -- the fast PSF-convolution path: images whose axes are 2^k, 3 2^k or 5 2^k long with the
 // standard 2x PSF oversampling (nx_psf = 2 nx, ny_psf = 2 ny; pfb's default
 // psf-oversize 2.0, parser/grid.yaml:65-67).  All BASELINE configs take this path.
+//
+// Lengths.  Columns (nx): 64 .. 8192 (2^k), 96 .. 6144 (3 2^k), 160 .. 5120 (5 2^k).  Rows (ny / 2): 64 .. 8192 (fp64:
+// 4096), 96 .. 6144 (fp64: 3072), 80 .. 5120 (fp64: 2560).  The axes mix freely.  The persistent kernels serve
+// power-of-two lengths only; a 3 2^k or 5 2^k axis runs the plain kernel of its pass (k_col_pow2, k_col_fwd_pow2,
+// k_row_fwd_pow2, k_row_inv_pow2) on a RegFft whose last pass has radix 3 or 5 (fft_pow2.hpp).
 //
 // Pruned transforms.  A length-2H FFT whose input is zero beyond H splits exactly into
 //     A_e = FFT_H(a)            (even output bins)
@@ -37,8 +42,10 @@
 #include <cstdlib>
 #include <type_traits>
 
-// This file is compiled into TWO objects (csrc/Makefile, FLAGS_fftconv_pow2 / FLAGS_fftconv_pow2_col): PFB_POW2_PART=1
-// -- everything but the column kernels -- and PFB_POW2_PART=2 -- the column kernels with their host description, table
+// This file is compiled into THREE objects (csrc/Makefile, FLAGS_fftconv_pow2 / _col / _mix): PFB_POW2_PART=1
+// -- everything but the column kernels -- PFB_POW2_PART=3 -- the plain kernels of the 3 2^k and 5 2^k lengths with their
+// launchers (pow2_mix_*; an object of their own: see ColKernels::all on what a new instantiation does to its object's other
+// kernels) -- and PFB_POW2_PART=2 -- the power-of-two column kernels with their host description, table
 // set-up and launchers (pow2_col_*), built with LLVM's max-ILP machine
 // scheduler (-mllvm -amdgpu-sched-strategy=max-ilp).  Their occupancy is pinned by the launch bounds, so
 // the default occupancy-driven scheduling only costs them instruction-level parallelism: col 0.977 ->
@@ -47,8 +54,11 @@
 #ifndef PFB_POW2_PART
 #define PFB_POW2_PART 0
 #endif
-#define PFB_POW2_COL  (PFB_POW2_PART != 1)
-#define PFB_POW2_REST (PFB_POW2_PART != 2)
+#define PFB_POW2_COL  (PFB_POW2_PART == 0 || PFB_POW2_PART == 2)    // the objects' host entry points ...
+#define PFB_POW2_REST (PFB_POW2_PART == 0 || PFB_POW2_PART == 1)
+#define PFB_POW2_MIX  (PFB_POW2_PART == 0 || PFB_POW2_PART == 3)
+#define PFB_POW2_COLK  (PFB_POW2_COL || PFB_POW2_MIX)               // ... and the kernel / launcher templates they instantiate
+#define PFB_POW2_RESTK (PFB_POW2_REST || PFB_POW2_MIX)
 
 namespace pfb {
 
@@ -91,13 +101,18 @@ template <> struct FastCfg<double> { static constexpr int ECOL = 8; static const
 // -> occupancy beats piece size for the latency-bound inverse kernel; the forward kernel
 // keeps 8 rows per workgroup (its strided side is the WRITE, full 128-byte lines).
 template <typename T, int L, int E, int GMAX> constexpr int row_groups();
+// Elements per thread at the lengths 3 2^k and 5 2^k: the odd factor times the radix of the power-of-two passes, so that a
+// row is at least 8 threads (the row tiles then have at most 32 rows, which divides every supported nx).
+//   3 2^k: 12 (radix-4 passes)      5 2^k: 20 (radix 4), 10 at L = 80 (radix 2)
+// Register counts of the alternatives: profiles/mixed_kernel_resources.md.
+constexpr int mix_row_e(int L) { return L % 3 == 0 ? 12 : (L >= 160 ? 20 : 10); }
 template <typename T, int L, bool INVK> struct RowCfg {
     // fp32 inverse rows: 8 elements per thread, except 16 at L = 4096: 4 rows / 64-byte pieces instead of 2 / 32, operands
     // read in the epilogue (no registers left to prefetch them): 1.054 against 1.188 ms per 2 x 8192^2.  (16 at L = 2048,
     // 8-row tiles with 128-byte pieces: 128 VGPRs + 232 B of scratch, 0.792 against 0.609 ms per 8-band launch.)
     // fp64: 8 elements per thread (the persistent inverse kernel has its own: InvPE)
     static constexpr int EMAX = sizeof(T) == 4 ? (INVK ? (L == 4096 ? 16 : 8) : 16) : 8;
-    static constexpr int E = (L / 64 < 8) ? 8 : (L / 64 > EMAX ? EMAX : L / 64);
+    static constexpr int E = odd_part(L) > 1 ? mix_row_e(L) : (L / 64 < 8) ? 8 : (L / 64 > EMAX ? EMAX : L / 64);
     static constexpr int TPB = L / E;
     static constexpr bool WAVE = TPB <= 64;
     static constexpr int GMAX = INVK ? 4 : 8;
@@ -123,7 +138,13 @@ template <typename T, int L> struct InvDb {
 // serial chain of four transforms; twice the threads per column halve the chain (1024^2 x 8 fp32: col 93.8 -> 73.2 us,
 // 1024^2 x 1: 23.6 -> 18.1, fp64 27.6 -> 24.1; profiles/r03_ab_col_e4_small.md)
 constexpr int COL_E4_MAXH = 1024;
-template <typename T, int H> constexpr int ecol() { return (H >= 8192 && sizeof(T) == 8) ? 16 : (H <= COL_E4_MAXH && H >= 64 ? 4 : FastCfg<T>::ECOL); }
+// ... and at the lengths 3 2^k / 5 2^k (plain kernel): 12 (radix-4 passes) / 10 (radix 2).  vv, aw and ev are 3 NVB E complex
+// registers whatever the type (144 / 120), which is why these run under the two-waves-per-SIMD launch bound
+// (col_waves); 24 / 20 elements do not fit 256 registers (profiles/mixed_kernel_resources.md)
+constexpr int mix_col_e(int H) { return H % 3 == 0 ? 12 : 10; }
+template <typename T, int H> constexpr int ecol() { return odd_part(H) > 1 ? mix_col_e(H) : (H >= 8192 && sizeof(T) == 8) ? 16 : (H <= COL_E4_MAXH && H >= 64 ? 4 : FastCfg<T>::ECOL); }
+// waves per SIMD the plain column kernels are bounded to
+template <typename T> constexpr int col_waves(int E) { return (E >= 16 || odd_part(E) > 1) ? 2 : FastCfg<T>::WCOL; }
 
 // rows per workgroup for the row kernels
 template <typename T, int L, int E, int GMAX>
@@ -233,7 +254,7 @@ __host__ __device__ inline size_t psf_off(int blk, int u, int c, int H, int nvb,
                 : (((size_t)blk * 2 + (u & 1)) * (size_t)H + (u >> 1)) * nvb + c;
 }
 
-#if PFB_POW2_REST
+#if PFB_POW2_RESTK
 // psf_l[band][blk][pu][mu][c] = psfhat[band][2 mu + pu][v]
 template <typename T>
 __global__ void k_relayout_psf_pow2(const cplx<T>* __restrict__ psfhat, cplx<T>* __restrict__ psf_l,
@@ -283,12 +304,12 @@ __global__ void k_unrelayout_psf_pow2(const cplx<T>* __restrict__ psf_l, cplx<T>
     }
 }
 
-#endif  // PFB_POW2_REST
+#endif  // PFB_POW2_RESTK
 
-#if PFB_POW2_COL
+#if PFB_POW2_COLK
 // ------------------------------------------------------------------------ column
 template <typename T, int H, int E>
-__global__ void __launch_bounds__((col_groups<H, E>() * (H / E)), (E >= 16 ? 2 : FastCfg<T>::WCOL))
+__global__ void __launch_bounds__((col_groups<H, E>() * (H / E)), (col_waves<T>(E)))
 k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
            const cplx<T>* __restrict__ twP, const cplx<T>* __restrict__ ptw,
            int nblk, size_t T_band, size_t psf_band, int band0) {
@@ -335,6 +356,12 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
     // (Requesting psf_e before the first transform and psf_o before the second in the 8192-point fp64 columns: vv + aw + q
     // are 192 registers before the radix-16 butterfly's own 64, 84 -> 556 bytes of scratch per lane.)
     constexpr int NPQ = F::NPASS;
+    // MIXL: the 3 2^k / 5 2^k columns launder the thread index per transform (LAUNDER_EARLY): with up to ten passes per
+    // transform the LDS addresses of all of them, computed once and kept across the four transforms, cost 130 registers
+    // (5120-point fp32 columns: 256 VGPRs + 132 B of scratch -> 132 VGPRs).  (Spelled as a branch per call: behind a
+    // helper -- a lambda or launder_if<MIXL>(t), both tried -- the power-of-two instantiations of this object compile to a
+    // different register allocation and schedule than the one all its measurements were taken with.)
+    constexpr bool MIXL = odd_part(H) > 1;
     Blk<T, NVB> q[PREQ2 ? E : 1];
     // ---- even bins of the column transform
     if constexpr (PREQ2) {
@@ -343,7 +370,8 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
             for (int j = (K * E) / NPQ; j < ((K + 1) * E) / NPQ; ++j) q[j] = loadb<T, NVB>(pe + NVB * TPB * j);
         });
-    } else
+    } else if constexpr (MIXL) F::template runN<false, NVB>(vv, lds, launder(t), ptw);
+    else
     F::template runN<false, NVB>(vv, lds, t, ptw);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
@@ -358,7 +386,8 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
             for (int j = (K * E) / NPQ; j < ((K + 1) * E) / NPQ; ++j) q[j] = loadb<T, NVB>(po + NVB * TPB * j);
         });
-    } else
+    } else if constexpr (MIXL) F::template runN<true, NVB>(vv, lds, launder(t), ptw);
+    else
     F::template runN<true, NVB>(vv, lds, t, ptw);
     cplx<T> ev[NVB][E];
 #pragma unroll
@@ -380,6 +409,8 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
         }
     }
     // ---- odd bins
+    if constexpr (MIXL) F::template runN<false, NVB>(vv, lds, launder(t), ptw);
+    else
     F::template runN<false, NVB>(vv, lds, t, ptw);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
@@ -388,6 +419,8 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 #pragma unroll
         for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * p.c[c];
     }
+    if constexpr (MIXL) F::template runN<true, NVB>(vv, lds, launder(t), ptw);
+    else
     F::template runN<true, NVB>(vv, lds, t, ptw);
     if (active) {
         const cplx<T>* tw3 = opaque(twP + t);
@@ -804,7 +837,7 @@ k_col_pow2x(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
 //     psfhat[2k+1] = FFT_nx((R_top - R_bot) .* w_P^n)[k]                 (un-pruned column transform of length P)
 // written straight into the plan's psf_l[blk][pu][mu][c] layout.
 template <typename T, int H, int E>
-__global__ void __launch_bounds__((col_groups<H, E>() * (H / E)), (E >= 16 ? 2 : FastCfg<T>::WCOL))
+__global__ void __launch_bounds__((col_groups<H, E>() * (H / E)), (col_waves<T>(E)))
 k_col_fwd_pow2(const cplx<T>* __restrict__ Tq, cplx<T>* __restrict__ psf_b,
                const cplx<T>* __restrict__ twP, const cplx<T>* __restrict__ ptw,
                int nblk, int nbe, size_t T_band, int four) {
@@ -838,6 +871,10 @@ k_col_fwd_pow2(const cplx<T>* __restrict__ Tq, cplx<T>* __restrict__ psf_b,
         }
     }
     // psfhat[2 k + pu] of this block: parity-major or class-major (psf_off), k = t + TPB j
+    // (MIXL: the 3 2^k / 5 2^k columns launder the thread index per transform, as k_col_pow2 does)
+    constexpr bool MIXL = odd_part(H) > 1;
+    if constexpr (MIXL) F::template runN<false, NVB>(ve, lds, launder(t), ptw);
+    else
     F::template runN<false, NVB>(ve, lds, t, ptw);
     if (active) {
 #pragma unroll
@@ -848,6 +885,8 @@ k_col_fwd_pow2(const cplx<T>* __restrict__ Tq, cplx<T>* __restrict__ psf_b,
             storeb<T, NVB>(psf_b + psf_off((int)b, 2 * (t + TPB * j), 0, H, NVB, four), o);
         }
     }
+    if constexpr (MIXL) F::template runN<false, NVB>(vo, lds, launder(t), ptw);
+    else
     F::template runN<false, NVB>(vo, lds, t, ptw);
     if (active) {
 #pragma unroll
@@ -860,9 +899,9 @@ k_col_fwd_pow2(const cplx<T>* __restrict__ Tq, cplx<T>* __restrict__ psf_b,
     }
 }
 
-#endif  // PFB_POW2_COL
+#endif  // PFB_POW2_COLK
 
-#if PFB_POW2_REST
+#if PFB_POW2_RESTK
 // ------------------------------------------------------------------- row forward
 // Hermitian post-processing of one parity: the group's transform Z (registers, natural order)
 // goes to LDS, then every lane produces the NVB bins of one block for one row and the G lanes
@@ -1380,7 +1419,9 @@ k_row_inv_pow2(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
     // a 1024-thread workgroup (it spilled 80-94 registers); they are read in the epilogue instead.  The same for fp32 at
     // 16 elements per thread (L >= 4096): x / x and r prefetched there cost 188 / 492 B of scratch, 1.29 / 1.63 ms
     constexpr bool BIG32 = sizeof(T) == 4 && E >= 16 && L >= 4096;
-    constexpr bool PREF = !BIG32 && (sizeof(T) == 4 || NT < 1024);
+    // ... and the 3 2^k / 5 2^k rows at 1024 threads or 16+ elements (profiles/mixed_kernel_resources.md)
+    constexpr bool MIXBIG = odd_part(L) > 1 && (NT >= 1024 || E >= 16 || (sizeof(T) == 8 && NT >= 512));
+    constexpr bool PREF = !BIG32 && !MIXBIG && (sizeof(T) == 4 || NT < 1024);
     V2 xq[PREF ? E : 1], rq[PREF ? E : 1];
     row_inv_phase<T, L, E, 1>([&] {
         if constexpr (PREF) {
@@ -1497,7 +1538,7 @@ struct InvP {
     static constexpr bool BARUP = NXT || sizeof(T) == 8;
     static constexpr int NTM = SMT ? F::TPB : L;
     static constexpr size_t LDS = 384 + sizeof(cplx<T>) * ((size_t)PTWP + NTM + (size_t)G * STRIDE + (PARK ? (size_t)G * L : 0));
-    static constexpr bool OK = LDS <= (size_t)LDS_MAX && !C::WAVE && (!SMT || 32 * F::TPB == 2 * L) &&
+    static constexpr bool OK = odd_part(L) == 1 && LDS <= (size_t)LDS_MAX && !C::WAVE && (!SMT || 32 * F::TPB == 2 * L) &&
                                (sizeof(T) == 4 ? (NT == 1024 && G >= 4 && G <= 16) : (NT == 512 && (G == 2 || G == 4) && L >= 1024));
     __device__ __forceinline__ static cplx<T> tw_row(const cplx<T>* ltm, int t, int j) {     // w_M^(t + TPB j)
         if constexpr (SMT) return j == 0 ? ltm[t] : ltm[t] * root32<T>(j);
@@ -1518,7 +1559,7 @@ template <typename T, int L> struct InvPE {
 // elements per thread): that tile is at the 128-VGPR cap already, and its per-band flush kept 20-136 B of scratch however
 // it was written.  There the launcher runs the whole-cube kernel once per band instead (launch_row_inv).
 template <typename T, int L, int E>
-constexpr bool inv_pb_ok() { return !(sizeof(T) == 4 && InvP<T, L, E>::SMT); }
+constexpr bool inv_pb_ok() { return odd_part(L) == 1 && !(sizeof(T) == 4 && InvP<T, L, E>::SMT); }
 
 // strength-reduced addressing of the strided pieces (see fwdp_post_lin): the blocks of a thread are BSTEP apart, so the
 // load address is a workgroup-uniform base (band, parity, step) + a 32-bit per-thread offset that never changes, and
@@ -1929,7 +1970,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
     }
 }
 
-#endif  // PFB_POW2_REST
+#endif  // PFB_POW2_RESTK
 
 #if PFB_STAMP
 #if PFB_POW2_COL
@@ -1962,8 +2003,29 @@ static inline bool for_pow2_size(int n, Fn&& f) {
     }
 }
 
+// the same for the lengths 3 2^k (96 .. 6144) and 5 2^k (80 .. 5120) of the third object
+template <typename Fn>
+static inline bool for_mix_size(int n, Fn&& f) {
+    switch (n) {
+#define X(NN) case NN: f(std::integral_constant<int, NN>{}); return true;
+        X(96) X(192) X(384) X(768) X(1536) X(3072) X(6144)
+        X(80) X(160) X(320) X(640) X(1280) X(2560) X(5120)
+#undef X
+        default: return false;
+    }
+}
+// which of them an axis may have: columns (H = nx) from 96, rows (L = ny / 2) from 80 and, like the power-of-two rows, up
+// to what one row's transform of that type takes in the LDS
+constexpr int MIX_COL_MIN = 96, MIX_ROW_MIN = 80;
+constexpr int mix_row_max(bool f32) { return f32 ? 6144 : 3072; }
+inline bool mix_len(int n, int lo, int hi) { return (odd_part(n) == 3 || odd_part(n) == 5) && n >= lo && n <= hi; }
+inline bool mix_col_len(int nx) { return mix_len(nx, MIX_COL_MIN, 6144); }
+inline bool mix_row_len(int L, bool f32) { return mix_len(L, MIX_ROW_MIN, mix_row_max(f32)); }
+// rows per workgroup of every row kernel divide this, and it divides every supported nx
+constexpr int ROW_TILE_MAX = 32;
+
 // the two-level column kernel k_col_pow2x and its class-major psf_l (the `four` of psf_off) serve nx >= 8192
-constexpr bool col_two_level(int nx) { return nx >= 8192; }
+constexpr bool col_two_level(int nx) { return odd_part(nx) == 1 && nx >= 8192; }
 
 enum Tab {                     // device tables owned by the plan
     PTW_COL,                   // pass table of the one-level column transform (plain kernel, PSFHAT producer)
@@ -1983,6 +2045,17 @@ struct FastTables {            // stored behind p->fast_tables
 int pow2_col_prepare(pfb_conv_plan* p, FastTables* ft);
 int pow2_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st);
 int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st);
+// the third object's (PFB_POW2_MIX): the same for an nx, and the row passes for an ny / 2, of 3 2^k or 5 2^k
+int pow2_mix_col_prepare(pfb_conv_plan* p, FastTables* ft);
+int pow2_mix_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st);
+int pow2_mix_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st);
+int pow2_mix_row_prepare(pfb_conv_plan* p, FastTables* ft);
+int pow2_mix_rows_per_wg(const pfb_conv_plan* p);
+int pow2_mix_row_fwd_launch(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
+                            const void* beam, size_t xpitch, size_t xband, hipStream_t st);
+int pow2_mix_row_inv_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x, const void* beam,
+                            double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
+                            bool per_band, hipStream_t st);
 
 // n table entries written by fill(cplx<T>*) -> a new device array
 template <typename T, typename Fill>
@@ -2004,7 +2077,7 @@ static int set_lds_max(K* kernel) {
     return PFB_OK;
 }
 
-#if PFB_POW2_COL
+#if PFB_POW2_COLK
 // Grid of the persistent column kernel k_col_pow2p: not all `maxgrid` resident workgroups but as many as give every one of them the same number
 // of trips.  `need` is rarely a multiple of the CU count (a band is 2^k + 1 column blocks), and a last trip with a handful
 // of workgroups runs at their latency while the rest of the chip idles -- the same work on slightly fewer workgroups is
@@ -2032,7 +2105,8 @@ template <typename T, int H> struct ColCfg {
     // persistent kernel: needs its LDS (exchange buffers + twiddle table) to fit; measured faster
     // for H >= 2048 (fp32, packed arithmetic: 1.07 vs 1.32 ms at 4096^2 x 8, 0.276 vs 0.347 at 2048^2 x 8;
     // fp64: 1.19 vs 1.41 and 0.266 vs 0.333 at x 4; a tie or a small loss at H <= 1024)
-    static constexpr ColKind KIND = col_two_level(H) ? ColKind::TwoLevel
+    // (the lengths 3 2^k and 5 2^k: the plain kernel, whatever their size)
+    static constexpr ColKind KIND = odd_part(H) > 1 ? ColKind::Plain : col_two_level(H) ? ColKind::TwoLevel
                                   : H >= 2048 && XB1 + TAB1 <= (size_t)LDS_MAX ? ColKind::Persistent : ColKind::Plain;
     // second exchange buffer set when ONE workgroup per CU is resident anyway and it fits: col 0.98 ->
     // 0.96 ms at 8 x 4096^2 fp32, 1.16 -> 1.10 ms at 4 x 4096^2 fp64; with two workgroups per CU (H = 2048)
@@ -2146,6 +2220,9 @@ static int col_prepare(FastTables* ft) {
     return rc;
 }
 
+#endif  // PFB_POW2_COLK
+
+#if PFB_POW2_COL
 // f(T{}, std::integral_constant<int, H>) for the plan's type and nx
 template <typename Fn>
 static int for_col_class(const pfb_conv_plan* p, Fn&& f) {
@@ -2166,12 +2243,17 @@ int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, 
 }
 #endif  // PFB_POW2_COL
 
-#if PFB_POW2_REST
+#if PFB_POW2_RESTK
 // The forward row kernels of class (T, L = ny / 2): the persistent one where FwdP::OK, else the plain one.
+// (FwdP is written for power-of-two rows and is not even instantiated for the others)
+template <typename T, int L> constexpr bool fwdp_ok() {
+    if constexpr (odd_part(L) > 1) return false;
+    else return FwdP<T, L>::OK;
+}
 template <typename T, int L> struct RowFwdK {
     using FP = FwdP<T, L>;
-    static constexpr bool PERSISTENT = FP::OK;
-    static constexpr int E = PERSISTENT ? FP::EOK : RowCfg<T, L, false>::E;
+    static constexpr bool PERSISTENT = fwdp_ok<T, L>();
+    static constexpr int E = [] { if constexpr (PERSISTENT) return FP::EOK; else return RowCfg<T, L, false>::E; }();
     static constexpr auto plain() { return k_row_fwd_pow2<T, L, E>; }
     // the instantiations launch_row_fwd can reach: f(kernel, beam) (the plain kernel takes `beam` at run time)
     template <typename Fn> static void reachable(Fn&& f) {
@@ -2233,9 +2315,10 @@ static int row_prepare(FastTables* ft) {
 template <typename T>
 static int prep_tables(pfb_conv_plan* p, FastTables* ft) {
     const int L = p->ny / 2;
-    int rc = pow2_col_prepare(p, ft);
+    int rc = is_pow2(p->nx) ? pow2_col_prepare(p, ft) : pow2_mix_col_prepare(p, ft);
     if (rc != PFB_OK) return rc;
-    if (!for_pow2_size(L, [&](auto l) { rc = row_prepare<T, l()>(ft); })) return PFB_ERR_UNSUPPORTED;
+    if (!is_pow2(L)) rc = pow2_mix_row_prepare(p, ft);
+    else if (!for_pow2_size(L, [&](auto l) { rc = row_prepare<T, l()>(ft); })) return PFB_ERR_UNSUPPORTED;
     if (rc != PFB_OK) return rc;
     // twM[n] = exp(-2 pi i n / M), n < L  (M = ny)
     return upload_table<T>(&ft->tab[TW_M], L, [&](cplx<T>* h) {
@@ -2247,21 +2330,27 @@ static int prep_tables(pfb_conv_plan* p, FastTables* ft) {
     });
 }
 
+#if PFB_POW2_REST
 bool pow2_supported(const pfb_conv_plan* p) {
-    if (!is_pow2(p->nx) || !is_pow2(p->ny)) return false;
-    if (p->P != 2 * p->nx || p->Q != 2 * p->ny) return false;
-    if (p->nx < 64 || p->nx > 8192) return false;
+    const bool f32 = p->dtype == PFB_F32;
+    if (p->P != 2 * p->nx || p->Q != 2 * p->ny || p->ny % 2) return false;
+    if (!(is_pow2(p->nx) && p->nx >= 64 && p->nx <= 8192) && !mix_col_len(p->nx)) return false;
     // rows: one length-ny/2 complex transform per image row in LDS: 8192 complex64 (ny = 16384) fit, complex128 do not
-    if (p->ny < 128 || p->ny > (p->dtype == PFB_F32 ? 16384 : 8192)) return false;
-    return true;
+    if (!(is_pow2(p->ny) && p->ny >= 128 && p->ny <= (f32 ? 16384 : 8192)) && !mix_row_len(p->ny / 2, f32)) return false;
+    // the row launchers run nx / G workgroups of G rows, G <= ROW_TILE_MAX a power of two: G must divide nx (this is what
+    // keeps nx = 80 out: the shortest rows are tiled 32 to a workgroup)
+    return p->nx % ROW_TILE_MAX == 0;
 }
+#endif
 
 template <typename T, int L>
 static int rows_per_wg() { return row_groups<T, L, RowCfg<T, L, true>::E, RowCfg<T, L, true>::GMAX>(); }
 
+#if PFB_POW2_REST
 int pow2_rows_per_wg(const pfb_conv_plan* p) {
     const bool f32 = p->dtype == PFB_F32;
     int g = 0;
+    if (!is_pow2(p->ny / 2)) return pow2_mix_rows_per_wg(p);
     for_pow2_size(p->ny / 2, [&](auto l) { g = f32 ? rows_per_wg<float, l()>() : rows_per_wg<double, l()>(); });
     return g;
 }
@@ -2294,6 +2383,7 @@ void pow2_release(pfb_conv_plan* p) {
     free(ft);
     p->fast_tables = nullptr;
 }
+#endif  // PFB_POW2_REST
 
 template <typename T>
 static int set_psfhat_t(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
@@ -2308,9 +2398,11 @@ static int set_psfhat_t(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
     return PFB_OK;
 }
 
+#if PFB_POW2_REST
 int pow2_set_psfhat(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
     return p->dtype == PFB_F32 ? set_psfhat_t<float>(p, psfhat, st) : set_psfhat_t<double>(p, psfhat, st);
 }
+#endif
 
 static FastDims fast_dims(const pfb_conv_plan* p, size_t xpitch, size_t xband) {
     return FastDims{p->nx, p->ny, p->M, p->T_elems_per_band, p->psf_elems_per_band, xpitch, xband};
@@ -2345,6 +2437,7 @@ static void launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, i
         constexpr int E = K::E;
         using F = RegFft<T, L, E, RowCfg<T, L, false>::WAVE>;
         constexpr int G = row_groups<T, L, E, RowCfg<T, L, false>::GMAX>();
+        static_assert(ROW_TILE_MAX % G == 0, "pow2_supported: the row tile divides nx");
         const size_t lds = sizeof(cplx<T>) * (size_t)G * (F::LDS_ELEMS + 4);
         hipLaunchKernelGGL(K::plain(), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
                            (const T*)x, (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)p->twQ,
@@ -2371,12 +2464,14 @@ static int set_psf_t(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStr
             // quadrant (a, b) of the SHIFTED PSF = quadrant (1 - a, 1 - b) of the centred one
             const int a = q >> 1, b = q & 1;
             const T* src = pb + (size_t)((1 - a) * nx) * Q + (size_t)(1 - b) * ny;
-            if (!for_pow2_size(L, [&](auto l) { launch_row_fwd<T, l()>(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st); })) {
+            if (!is_pow2(L)) {
+                if (rc == PFB_OK) rc = pow2_mix_row_fwd_launch(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st);
+            } else if (!for_pow2_size(L, [&](auto l) { launch_row_fwd<T, l()>(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st); })) {
                 set_error("pow2_set_psf: unsupported ny");
                 rc = PFB_ERR_UNSUPPORTED;
             }
         }
-        if (rc == PFB_OK) rc = pow2_col_fwd_launch(p, ft, Tq, band, st);
+        if (rc == PFB_OK) rc = is_pow2(nx) ? pow2_col_fwd_launch(p, ft, Tq, band, st) : pow2_mix_col_fwd_launch(p, ft, Tq, band, st);
     }
     if (rc == PFB_OK && psfhat_out) {
         const int nv = p->M + 1;
@@ -2392,9 +2487,11 @@ static int set_psf_t(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStr
     return rc;
 }
 
+#if PFB_POW2_REST
 int pow2_set_psf(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStream_t st) {
     return p->dtype == PFB_F32 ? set_psf_t<float>(p, psf, psfhat_out, st) : set_psf_t<double>(p, psf, psfhat_out, st);
 }
+#endif
 
 template <typename T, int L>
 static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x,
@@ -2450,6 +2547,7 @@ static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, in
     constexpr int E = K::E;
     using F = RegFft<T, L, E, RowCfg<T, L, true>::WAVE>;
     constexpr int G = row_groups<T, L, E, RowCfg<T, L, true>::GMAX>();
+    static_assert(ROW_TILE_MAX % G == 0, "pow2_supported: the row tile divides nx");
     const size_t lds = 384 + sizeof(cplx<T>) * ((size_t)((F::PTWC + 1) & ~1) + (size_t)G * (F::LDS_ELEMS + 4) * (InvDb<T, L>::ON ? 2 : 1));
     hipLaunchKernelGGL(K::plain(), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
                        (const cplx<T>*)p->T, (const cplx<T>*)p->twQ, (const cplx<T>*)ft->tab[TW_M],
@@ -2463,16 +2561,26 @@ static int apply_t(pfb_conv_plan* p, int band0, int nb, const void* x, const voi
                    hipStream_t st) {
     const FastTables* ft = (const FastTables*)p->fast_tables;
     const int L = p->ny / 2;
+    const bool rows_mix = !is_pow2(L);         // each axis on its own: 2^k -> this object's / the column object's launchers
     prof_mark(p, st, 0);
-    if (!for_pow2_size(L, [&](auto l) {
+    if (rows_mix) {
+        if (int rc = pow2_mix_row_fwd_launch(p, ft, p->T, band0, nb, x, beam, (size_t)p->ny, (size_t)p->nx * p->ny, st); rc != PFB_OK)
+            return rc;
+    } else if (!for_pow2_size(L, [&](auto l) {
             launch_row_fwd<T, l()>(p, ft, p->T, band0, nb, x, beam, (size_t)p->ny, (size_t)p->nx * p->ny, st);
         })) {
         set_error("pow2_apply: unsupported ny");
         return PFB_ERR_UNSUPPORTED;
     }
     prof_mark(p, st, 1);
-    if (int rc = pow2_col_launch(p, ft, band0, nb, st); rc != PFB_OK) return rc;
+    if (int rc = is_pow2(p->nx) ? pow2_col_launch(p, ft, band0, nb, st) : pow2_mix_col_launch(p, ft, band0, nb, st); rc != PFB_OK)
+        return rc;
     prof_mark(p, st, 2);
+    if (rows_mix) {
+        if (int rc = pow2_mix_row_inv_launch(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
+            rc != PFB_OK)
+            return rc;
+    } else
     for_pow2_size(L, [&](auto l) {
         launch_row_inv<T, l()>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
     });
@@ -2481,13 +2589,79 @@ static int apply_t(pfb_conv_plan* p, int band0, int nb, const void* x, const voi
     return PFB_OK;
 }
 
+#if PFB_POW2_REST
 int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam, double scale,
                double sigmainv, void* out, const void* dot_with, const void* dot_with2, bool per_band, hipStream_t st) {
     return p->dtype == PFB_F32
         ? apply_t<float>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st)
         : apply_t<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
 }
-#endif  // PFB_POW2_REST
+#endif
+#endif  // PFB_POW2_RESTK
+
+#if PFB_POW2_MIX
+// ------------------------------------------------- the lengths 3 2^k and 5 2^k (third object)
+// The classes are those of for_mix_size; a class is described by the same ColCfg / ColKernels / RowFwdK / RowInvK as a
+// power-of-two one (every one of them Plain / not PERSISTENT by construction) and launched by the same templates.
+// f(T{}, std::integral_constant<int, N>) for the plan's type and the length n; rows: only what mix_row_len allows
+template <bool ROWS, typename Fn>
+static int for_mix_class(const pfb_conv_plan* p, int n, Fn&& f) {
+    const bool f32 = p->dtype == PFB_F32;
+    bool ok = ROWS ? mix_row_len(n, f32) : mix_col_len(n);
+    ok = ok && for_mix_size(n, [&](auto c) {
+        constexpr int N = decltype(c)::value;
+        if constexpr (ROWS) {
+            if (f32) f(float{}, c);
+            else if constexpr (N <= mix_row_max(false)) f(double{}, c);
+        } else if constexpr (N >= MIX_COL_MIN) {
+            if (f32) f(float{}, c); else f(double{}, c);
+        }
+    });
+    if (!ok) set_error("pow2: unsupported %s %d", ROWS ? "ny / 2" : "nx", n);
+    return ok ? PFB_OK : PFB_ERR_UNSUPPORTED;
+}
+int pow2_mix_col_prepare(pfb_conv_plan* p, FastTables* ft) {
+    int rc = PFB_OK;
+    const int rs = for_mix_class<false>(p, p->nx, [&](auto t, auto h) {
+        static_assert(ColCfg<decltype(t), h()>::KIND == ColKind::Plain && !col_two_level(h()), "plain column kernel");
+        rc = col_prepare<decltype(t), h()>(ft);
+    });
+    return rs != PFB_OK ? rs : rc;
+}
+int pow2_mix_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
+    return for_mix_class<false>(p, p->nx, [&](auto t, auto h) { launch_col<decltype(t), h()>(p, ft, band0, nb, st); });
+}
+int pow2_mix_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
+    return for_mix_class<false>(p, p->nx, [&](auto t, auto h) { launch_col_fwd<decltype(t), h()>(p, ft, Tq, band, st); });
+}
+int pow2_mix_row_prepare(pfb_conv_plan* p, FastTables* ft) {
+    int rc = PFB_OK;
+    const int rs = for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) {
+        using T = decltype(t);
+        static_assert(!RowFwdK<T, l()>::PERSISTENT && !RowInvK<T, l()>::PERSISTENT && !RowInvK<T, l()>::PER_BAND, "plain row kernels");
+        rc = row_prepare<T, l()>(ft);
+    });
+    return rs != PFB_OK ? rs : rc;
+}
+int pow2_mix_rows_per_wg(const pfb_conv_plan* p) {
+    int g = 0;
+    for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) { g = rows_per_wg<decltype(t), l()>(); });
+    return g;
+}
+int pow2_mix_row_fwd_launch(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
+                            const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
+    return for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) {
+        launch_row_fwd<decltype(t), l()>(p, ft, Tbuf, band0, nb, x, beam, xpitch, xband, st);
+    });
+}
+int pow2_mix_row_inv_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x, const void* beam,
+                            double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
+                            bool per_band, hipStream_t st) {
+    return for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) {
+        launch_row_inv<decltype(t), l()>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
+    });
+}
+#endif  // PFB_POW2_MIX
 
 }  // namespace pfb
 

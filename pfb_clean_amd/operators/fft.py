@@ -6,8 +6,9 @@ PSFHAT production -- pfb/operators/gridder.py:712-714 with pfb/operators/fft.py:
 This runs ONCE per gridding run (plan time), not inside the PCG / PD loops.  It is produced by the library's own
 kernels for every grid whose lengths are 13-smooth with an even ny_psf (what pfb's grid worker makes, grid.py:276-285):
 
-  * power-of-two grids in the fast path's range (nx_psf <= 16384, ny_psf <= 32768 fp32 / 16384 fp64: every BASELINE
-    size) on the register-FFT row / column kernels of the convolution itself (pfb_psfconv_set_psf on a fast plan);
+  * grids that oversample a fast-path image size by 2 and that size is not itself embedded (operators/psf.py: the
+    powers of two up to nx_psf = 16384, ny_psf = 32768 fp32 / 16384 fp64 -- every BASELINE size -- and the offered
+    3 2^k / 5 2^k lengths) on the register-FFT row / column kernels of the convolution itself (pfb_psfconv_set_psf on a fast plan);
   * any other grid through pfb_psfhat_from_psf: one workgroup per line in LDS while a line fits, multi-launch
     Stockham passes in global memory beyond that -- no length limit.
 
@@ -20,11 +21,7 @@ import ctypes as C
 import torch
 
 from .. import _dev, _lib
-from .psf import PsfConvPlan, NX_FAST_MAX, NY_FAST_MAX
-
-
-def _is_pow2(n):
-    return n > 0 and (n & (n - 1)) == 0
+from .psf import PsfConvPlan, is_fast_size, _embed_grid
 
 
 def psfhat_from_psf(psf):
@@ -45,7 +42,8 @@ def psfhat_from_psf(psf):
         # to torch.fft on the same device tensor instead of failing; every other error is a real one and propagates.
         soft = (_lib.PFB_ERR_UNSUPPORTED, _lib.PFB_ERR_ALLOC)
         try:
-            if (_is_pow2(P) and _is_pow2(Q) and 128 <= P <= 2 * NX_FAST_MAX and 256 <= Q <= 2 * NY_FAST_MAX[p.dtype]):
+            if (P % 2 == 0 and is_fast_size(P // 2, Q // 2, p.dtype)
+                    and _embed_grid(P // 2, Q // 2, P, Q, p.dtype) is None):
                 # a fast plan for the (P/2, Q/2) image this grid oversamples by 2: its row / column kernels do the work
                 plan, out = PsfConvPlan.from_psf(p, P // 2, Q // 2, want_psfhat=True)
                 plan.close()

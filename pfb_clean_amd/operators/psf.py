@@ -32,15 +32,64 @@ def _pow2ceil(n):
     return p
 
 
-# what the kernels take (csrc): the fast path serves power-of-two images 64 <= nx <= 8192, 128 <= ny <= NY_FAST_MAX
-# with nx_psf = 2 nx, ny_psf = 2 ny; the coverage ("generic") kernels hold one line in two LDS buffers
+# what the kernels take (csrc): the fast path serves images whose axes are 2^k, 3 2^k or 5 2^k long -- 64 <= nx <= 8192
+# (96 .. 6144, 160 .. 5120), 128 <= ny <= NY_FAST_MAX (160 .. 12288, fp64 6144) -- with nx_psf = 2 nx, ny_psf = 2 ny; the
+# coverage ("generic") kernels hold one line in two LDS buffers
 NX_FAST_MAX = 8192
 NY_FAST_MAX = {torch.float32: 16384, torch.float64: 8192}
 LINE_MAX = {torch.float32: 10240, torch.float64: 5120}
+# Every 3 2^k / 5 2^k length the library takes (csrc/fftconv_pow2.hip): a plan created for such a size runs natively.
+MIX_ALL = {
+    'nx': {torch.float32: (96, 6144), torch.float64: (96, 6144)},
+    'ny': {torch.float32: (160, 12288), torch.float64: (160, 6144)},
+}
+# The ones _embed_grid OFFERS, per axis: those that measured faster per plan.apply than the power-of-two grid the
+# problem had before, by more than the run-to-run spread (profiles/mixed_conv_sweep.md).  The plain kernels these
+# lengths run are about 2 x slower per pixel than the persistent power-of-two kernels.  The row kernels still win where
+# the next power of two is 8192: fp32 rows of 5120 / 6144 pixels on power-of-two columns, 0.88-0.91 of the time.  The
+# plain column kernel loses to the persistent ones (5120 x 8192 +8 % against 8192^2, 6144 x 4096 +15 %), 3072^2 fp32
+# (+9 % against 4096^2) and 1536^2 fp64 (+2 % against 2048^2) lost, the shorter lengths and fp64 above 1536 were not
+# timed: none of them is offered, and an image that IS such a size is embedded in the next power of two as before.
+MIX_OFFERED = {
+    'nx': {torch.float32: (), torch.float64: ()},
+    'ny': {torch.float32: (5120, 6144), torch.float64: ()},
+}
+
+
+def _mix_lengths(lo, hi):
+    """Ascending: the lengths 3 2^k and 5 2^k in [lo, hi]."""
+    out, p = [], 1
+    while p <= hi:
+        out += [n for n in (3 * p, 5 * p) if lo <= n <= hi]
+        p *= 2
+    return sorted(out)
+
+
+def _fast_lengths(lo, hi, mix):
+    """Ascending: the powers of two in [lo, hi] and the lengths `mix`."""
+    out, p = list(mix), 1
+    while p <= hi:
+        if p >= lo:
+            out.append(p)
+        p *= 2
+    return sorted(out)
+
+
+def is_fast_size(nx, ny, rdtype):
+    """Whether an (nx, ny) image with a (2 nx, 2 ny) PSF is a size the fast kernels take natively."""
+    xs = _fast_lengths(64, NX_FAST_MAX, _mix_lengths(*MIX_ALL['nx'][rdtype]))
+    ys = _fast_lengths(128, NY_FAST_MAX[rdtype], _mix_lengths(*MIX_ALL['ny'][rdtype]))
+    return nx in xs and ny in ys and nx % 32 == 0
+
+
+def _fast_ceil(n, lengths):
+    """The smallest of `lengths` that holds n, or None."""
+    return next((m for m in lengths if m >= n), None)
 
 
 def _embed_grid(nx, ny, nx_psf, ny_psf, rdtype):
-    """(nx2, ny2) of the power-of-two plan an (nx, ny | nx_psf, ny_psf) problem is embedded in, or None: already
+    """(nx2, ny2) of the fast-path plan an (nx, ny | nx_psf, ny_psf) problem is embedded in -- per axis the smallest
+    length among the powers of two and the offered 3 2^k / 5 2^k lengths (MIX_OFFERED) -- or None: already
     a fast-path size, switched off (PFB_NO_EMBED / PFB_FORCE_GENERIC), odd ny_psf, or beyond the fast kernels.
     Problems the coverage kernels can run (every line fits the LDS) are only embedded when the padded problem has
     at most 3x the pixels; problems they cannot run (nx_psf > 10240 fp32 / 5120 fp64: 6000^2, 7200^2 ... images
@@ -50,10 +99,11 @@ def _embed_grid(nx, ny, nx_psf, ny_psf, rdtype):
         return None
     if ny_psf % 2:
         return None
-    nx2, ny2 = max(64, _pow2ceil(nx)), max(128, _pow2ceil(ny))
-    if (nx2, ny2) == (nx, ny) and (nx_psf, ny_psf) == (2 * nx, 2 * ny):
+    nx2 = _fast_ceil(nx, _fast_lengths(64, NX_FAST_MAX, MIX_OFFERED['nx'][rdtype]))
+    ny2 = _fast_ceil(ny, _fast_lengths(128, NY_FAST_MAX[rdtype], MIX_OFFERED['ny'][rdtype]))
+    if nx2 is None or ny2 is None:
         return None
-    if nx2 > NX_FAST_MAX or ny2 > NY_FAST_MAX[rdtype]:
+    if (nx2, ny2) == (nx, ny) and (nx_psf, ny_psf) == (2 * nx, 2 * ny):
         return None
     generic_ok = max(nx_psf, ny_psf // 2) <= LINE_MAX[rdtype]
     if generic_ok and nx2 * ny2 > 3 * nx * ny:
@@ -97,9 +147,9 @@ class PsfConvPlan(NativePlan):
         self.code = _dev.code(self.rdtype)
         cnx, cny, cpx, cpy = self.nx, self.ny, self.nx_psf, self.lastsize
         if psf is None:
-            # Arbitrary sizes on the power-of-two kernels: the same image-space PSF is re-gridded
-            # (pfb_psfhat_regrid) onto nx_psf2 = 2 nx2, ny_psf2 = 2 ny2 with nx2, ny2 the next powers
-            # of two, images are zero-padded into (nx2, ny2) buffers and results cropped.  Identical
+            # Arbitrary sizes on the fast kernels: the same image-space PSF is re-gridded
+            # (pfb_psfhat_regrid) onto nx_psf2 = 2 nx2, ny_psf2 = 2 ny2 with nx2, ny2 the next lengths
+            # 2^k, 3 2^k or 5 2^k, images are zero-padded into (nx2, ny2) buffers and results cropped.  Identical
             # results to rounding, 3-6x faster than the line-per-workgroup coverage kernels
             # (measured: 3600^2 x 2 bands 3.2 ms generic vs 0.55 ms for two 4096^2 bands).
             grid2 = _embed_grid(self.nx, self.ny, self.nx_psf, self.lastsize, self.rdtype)
@@ -188,7 +238,7 @@ class PsfConvPlan(NativePlan):
         nband, nx_psf, ny_psf = (int(v) for v in p.shape)
         if _embed_grid(int(nx), int(ny), nx_psf, ny_psf, p.dtype) is not None:
             # not a fast-path size: transform on the PSF's own grid first, then let the constructor
-            # re-grid it onto the power-of-two plan (operators/fft.py picks the native producer)
+            # re-grid it onto the fast-path plan (operators/fft.py picks the native producer)
             from .fft import psfhat_from_psf
             ph = psfhat_from_psf(p)
             plan = cls(ph, nx, ny, ny_psf)

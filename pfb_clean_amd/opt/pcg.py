@@ -233,11 +233,15 @@ def pcg_fused_bands(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, bac
 
 def _bands_batched(plan):
     """Whether pcg_psf runs its bands as one batched solve on this plan.  Not on the 4096-point fp32 rows (plan ny = 8192:
-    8192-pixel images and, embedded, every fp32 image of 4100-8192 pixels): that row tile has no per-band persistent
+    8192-pixel images and, embedded, fp32 images of 6145-8192 pixels): that row tile has no per-band persistent
     inverse kernel, the batched solve launches the whole-cube one once per band there, and measured 2-3 % slower than
-    the band loop (2 x 8192^2: 153.2 vs 148.8 ms, 2 x 6000^2: 162.5 vs 159.2 ms for 50 iterations)."""
+    the band loop (2 x 8192^2: 153.2 vs 148.8 ms, 2 x 6000^2: 162.5 vs 159.2 ms for 50 iterations).  fp32 images with rows of
+    4097-6144 pixels, which that plan held before the 5 2^k / 3 2^k rows (plan ny = 5120, 6144) took them, keep the band
+    loop they had: on the plain inverse-row kernel of those rows the two are 1.3 % apart the other way (2 x 6000^2 on
+    6144^2, 50 iterations, three alternating runs: loop 142.1 / 141.1 / 141.0 ms, batched 139.4 / 139.7 / 139.3 ms), which
+    was not taken as reason enough to change what pcg_psf does for these images."""
     ny = plan.embed[1] if plan.embed is not None else plan.ny
-    return not (plan.fast_path and plan.rdtype == torch.float32 and ny == 8192)
+    return not (plan.fast_path and plan.rdtype == torch.float32 and 4096 < ny <= 8192)
 
 
 def _report(res_status, k, eps, verbosity):
