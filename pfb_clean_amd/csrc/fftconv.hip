@@ -261,7 +261,7 @@ static int rows_c2r(const SpecView<T>& in, const RealView<T>& out, const Epilogu
     const size_t n = (size_t)nb * out.P * M;
     hipLaunchKernelGGL((k_long_pre<T>), long_grid(M, out.P, nb), dim3(256), 0, st, in, ws, twQ, out.P, M);
     if (int rc = long_fft<T, true>(ws, ws + n, n, f, twQ, 2, (size_t)nb * out.P, 1, (size_t)M, st); rc != PFB_OK) return rc;
-    hipLaunchKernelGGL((k_long_finish<T>), e.x ? dim3(1, out.P, nb) : long_grid(out.valid, out.P, nb), dim3(256), 0, st,
+    hipLaunchKernelGGL((k_long_finish<T>), e.dot_with ? dim3(1, out.P, nb) : long_grid(out.valid, out.P, nb), dim3(256), 0, st,
                        (const cplx<T>*)ws, out, e);
     return PFB_OK;
 }
