@@ -78,11 +78,21 @@ inline void prof_mark(pfb_conv_plan* p, hipStream_t st, int k) {
 int psfconv_apply_partials(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
                            double wsum, double sigmainv, void* out, const void* dot_with,
                            const void* dot_with2, bool per_band, int* bs, int* qs, int* bst, void* stream);
+// One apply: bands [band0, band0 + nb) of x (times beam, if given) convolved into out on `st`; the epilogue's scale
+// (1 / (P Q wsum)) and sigmainv, and the operands of the fused dots (per band, or over the whole range).  Built once by
+// apply_common (fftconv.hip) and handed down by reference to the coverage path and to the fast path's launchers.
+struct ApplyArgs {
+    int band0, nb;
+    const void *x, *beam;
+    double scale, sigmainv;
+    void* out;
+    const void *dot_with, *dot_with2;
+    bool per_band;
+    hipStream_t st;
+};
 // fftconv_pow2.hip: the fast path's entry points
 bool pow2_supported(const pfb_conv_plan* p);
-int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
-               double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
-               bool per_band, hipStream_t st);
+int pow2_apply(pfb_conv_plan* p, const ApplyArgs& a);
 int pow2_prepare(pfb_conv_plan* p);
 void pow2_release(pfb_conv_plan* p);
 int pow2_rows_per_wg(const pfb_conv_plan* p);

@@ -314,22 +314,22 @@ static size_t long_apply_ws_bytes(int nb, int nx, int M, int P) {
 
 // the convolution off the fast path: three stage calls, all in LDS or (long_lines plan) all as global passes
 template <typename T>
-static int apply_coverage(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam,
-                          double scale, double sigmainv, void* out, const void* dot_with,
-                          const void* dot_with2, hipStream_t st) {
+static int apply_coverage(pfb_conv_plan* p, const ApplyArgs& a) {
     const bool lds = !p->long_lines;
     cplx<T>* ws = (cplx<T>*)p->long_ws;
     const size_t img = (size_t)p->nx * p->ny;
-    const RealView<const T> xin{(const T*)x, img, p->ny, p->nx, p->Q, p->ny, 0, 0};
-    const RealView<T> xout{(T*)out, img, p->ny, p->nx, p->Q, p->ny, 0, 0};
-    const SpecView<T> Tv{(cplx<T>*)p->T + (size_t)band0 * p->T_elems_per_band, p->T_elems_per_band, 1, (size_t)p->nx};
-    const Epilogue<T> e{(const T*)x, (const T*)beam, (const T*)dot_with, (const T*)dot_with2, p->partials, (T)scale, (T)sigmainv};
+    const hipStream_t st = a.st;
+    const RealView<const T> xin{(const T*)a.x, img, p->ny, p->nx, p->Q, p->ny, 0, 0};
+    const RealView<T> xout{(T*)a.out, img, p->ny, p->nx, p->Q, p->ny, 0, 0};
+    const SpecView<T> Tv{(cplx<T>*)p->T + (size_t)a.band0 * p->T_elems_per_band, p->T_elems_per_band, 1, (size_t)p->nx};
+    const Epilogue<T> e{(const T*)a.x, (const T*)a.beam, (const T*)a.dot_with, (const T*)a.dot_with2, p->partials,
+                        (T)a.scale, (T)a.sigmainv};
     prof_mark(p, st, 0);
-    int rc = rows_r2c<T>(xin, (const T*)beam, Tv, nb, p->frow, (const cplx<T>*)p->twQ, lds, ws, st);
+    int rc = rows_r2c<T>(xin, (const T*)a.beam, Tv, a.nb, p->frow, (const cplx<T>*)p->twQ, lds, ws, st);
     prof_mark(p, st, 1);
-    if (rc == PFB_OK) rc = conv_cols<T>(p, band0, nb, lds, ws, st);
+    if (rc == PFB_OK) rc = conv_cols<T>(p, a.band0, a.nb, lds, ws, st);
     prof_mark(p, st, 2);
-    if (rc == PFB_OK) rc = rows_c2r<T>(Tv, xout, e, nb, p->frow, (const cplx<T>*)p->twQ, lds, ws, st);
+    if (rc == PFB_OK) rc = rows_c2r<T>(Tv, xout, e, a.nb, p->frow, (const cplx<T>*)p->twQ, lds, ws, st);
     prof_mark(p, st, 3);
     if (rc != PFB_OK) return rc;
     PFB_HIP_CHECK(hipGetLastError());
@@ -623,11 +623,12 @@ static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, cons
     hipStream_t st = as_stream(stream);
     double scale = 1.0 / ((double)p->P * (double)p->Q);
     if (wsum > 0) scale /= wsum;
+    const ApplyArgs a{band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st};
     int rc;
     // slot k of the plain / coverage kernels is band k / ppb's; the persistent row-inverse kernel writes fewer
     p->last = {p->partials_per_band * nb, p->partials_per_band, p->partials_per_band * nb, p->partials_per_band};
     if (p->fast)
-        rc = pow2_apply(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
+        rc = pow2_apply(p, a);
     else {
         if (p->long_lines) {                                  // the global passes' scratch: grown on demand, freed with the plan
             const size_t need = p->dtype == PFB_F32 ? long_apply_ws_bytes<float>(nb, p->nx, p->M, p->P)
@@ -643,9 +644,7 @@ static int apply_common(pfb_conv_plan* p, int band0, int nb, const void* x, cons
                 p->long_ws_bytes = need;
             }
         }
-        rc = p->dtype == PFB_F32
-            ? apply_coverage<float>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st)
-            : apply_coverage<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, st);
+        rc = p->dtype == PFB_F32 ? apply_coverage<float>(p, a) : apply_coverage<double>(p, a);
     }
     if (rc != PFB_OK) return rc;
     if (dot_with && ndots > 0 && per_band) {

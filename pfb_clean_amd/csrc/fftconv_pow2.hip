@@ -35,30 +35,24 @@
 //   k_row_inv_pow2  mirror image of row_fwd with the fused epilogue
 //                   (1/(PQ wsum), beam, + sigmainv x, <dot_with, out> partials)
 // Host side (below the kernels): which variant serves a class and what it needs is stated once -- ColCfg / ColKernels,
-// RowFwdK, RowInvK -- and read by the launchers, the LDS-attribute set-up and the table set-up.
+// RowFwdK, RowInvK -- and read by the launchers, the LDS-attribute set-up and the table set-up.  An axis is served
+// through ONE seam, a record of function pointers (ColPass for nx, RowPass for ny / 2), whichever object owns its classes.
+//
+// This file is compiled into THREE objects (csrc/Makefile, FLAGS_fftconv_pow2 / _col / _mix).  Everything up to the entry
+// blocks at the end of the file -- configuration, kernels, class descriptions, table set-up, launchers: all templates or
+// inlines -- is seen by all three; an object holds the kernels its own entry block instantiates and no others:
+//   PFB_POW2_PART=1  the fast path's public entry points (pow2_*) and the power-of-two rows
+//   PFB_POW2_PART=2  the power-of-two columns, built with LLVM's max-ILP machine scheduler (-mllvm
+//                    -amdgpu-sched-strategy=max-ilp).  Their occupancy is pinned by the launch bounds, so the default
+//                    occupancy-driven scheduling only costs them instruction-level parallelism: col 0.977 -> 0.904 ms fp32
+//                    and 1.152 -> 1.078 ms fp64 at 4096^2; the row kernels LOSE 5-25 % under the same switch, hence the split
+//   PFB_POW2_PART=3  the columns and rows of the lengths 3 2^k and 5 2^k (plain kernels; an object of their own: see
+//                    ColKernels::all on what a new instantiation does to its object's other kernels)
 #include "conv_plan.hpp"
 #include "fft_pow2.hpp"
 #include <vector>
 #include <cstdlib>
 #include <type_traits>
-
-// This file is compiled into THREE objects (csrc/Makefile, FLAGS_fftconv_pow2 / _col / _mix): PFB_POW2_PART=1
-// -- everything but the column kernels -- PFB_POW2_PART=3 -- the plain kernels of the 3 2^k and 5 2^k lengths with their
-// launchers (pow2_mix_*; an object of their own: see ColKernels::all on what a new instantiation does to its object's other
-// kernels) -- and PFB_POW2_PART=2 -- the power-of-two column kernels with their host description, table
-// set-up and launchers (pow2_col_*), built with LLVM's max-ILP machine
-// scheduler (-mllvm -amdgpu-sched-strategy=max-ilp).  Their occupancy is pinned by the launch bounds, so
-// the default occupancy-driven scheduling only costs them instruction-level parallelism: col 0.977 ->
-// 0.904 ms fp32 and 1.152 -> 1.078 ms fp64 at 4096^2; the row kernels LOSE 5-25 % under the same switch,
-// hence the split.  (0 = one object with everything, default scheduler.)
-#ifndef PFB_POW2_PART
-#define PFB_POW2_PART 0
-#endif
-#define PFB_POW2_COL  (PFB_POW2_PART == 0 || PFB_POW2_PART == 2)    // the objects' host entry points ...
-#define PFB_POW2_REST (PFB_POW2_PART == 0 || PFB_POW2_PART == 1)
-#define PFB_POW2_MIX  (PFB_POW2_PART == 0 || PFB_POW2_PART == 3)
-#define PFB_POW2_COLK  (PFB_POW2_COL || PFB_POW2_MIX)               // ... and the kernel / launcher templates they instantiate
-#define PFB_POW2_RESTK (PFB_POW2_REST || PFB_POW2_MIX)
 
 namespace pfb {
 
@@ -254,7 +248,6 @@ __host__ __device__ inline size_t psf_off(int blk, int u, int c, int H, int nvb,
                 : (((size_t)blk * 2 + (u & 1)) * (size_t)H + (u >> 1)) * nvb + c;
 }
 
-#if PFB_POW2_RESTK
 // psf_l[band][blk][pu][mu][c] = psfhat[band][2 mu + pu][v]
 template <typename T>
 __global__ void k_relayout_psf_pow2(const cplx<T>* __restrict__ psfhat, cplx<T>* __restrict__ psf_l,
@@ -304,9 +297,6 @@ __global__ void k_unrelayout_psf_pow2(const cplx<T>* __restrict__ psf_l, cplx<T>
     }
 }
 
-#endif  // PFB_POW2_RESTK
-
-#if PFB_POW2_COLK
 // ------------------------------------------------------------------------ column
 template <typename T, int H, int E>
 __global__ void __launch_bounds__((col_groups<H, E>() * (H / E)), (col_waves<T>(E)))
@@ -899,9 +889,6 @@ k_col_fwd_pow2(const cplx<T>* __restrict__ Tq, cplx<T>* __restrict__ psf_b,
     }
 }
 
-#endif  // PFB_POW2_COLK
-
-#if PFB_POW2_RESTK
 // ------------------------------------------------------------------- row forward
 // Hermitian post-processing of one parity: the group's transform Z (registers, natural order)
 // goes to LDS, then every lane produces the NVB bins of one block for one row and the G lanes
@@ -1970,23 +1957,6 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
     }
 }
 
-#endif  // PFB_POW2_RESTK
-
-#if PFB_STAMP
-#if PFB_POW2_COL
-int pow2_col_set_stamp(unsigned long long* buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &buf, sizeof(buf)) == hipSuccess ? PFB_OK : PFB_ERR_HIP;
-}
-#endif
-#if PFB_POW2_REST
-int pow2_col_set_stamp(unsigned long long* buf);
-int pow2_set_stamp(unsigned long long* buf) {
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &buf, sizeof(buf)) != hipSuccess) return PFB_ERR_HIP;
-    return pow2_col_set_stamp(buf);
-}
-#endif
-#endif
-
 // -------------------------------------------------------------------- host side
 // Every fact about which kernel variant serves a size / type class and what it needs is stated ONCE below: ColCfg /
 // ColKernels for the column pass (nx), RowFwdK / RowInvK for the row passes (ny / 2).  The launchers, the LDS-attribute
@@ -2041,21 +2011,35 @@ struct FastTables {            // stored behind p->fast_tables
     void* tab[NTAB];
     int num_cu;
 };
-// the column object's entry points (defined under PFB_POW2_COL below)
-int pow2_col_prepare(pfb_conv_plan* p, FastTables* ft);
-int pow2_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st);
-int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st);
-// the third object's (PFB_POW2_MIX): the same for an nx, and the row passes for an ny / 2, of 3 2^k or 5 2^k
-int pow2_mix_col_prepare(pfb_conv_plan* p, FastTables* ft);
-int pow2_mix_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st);
-int pow2_mix_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st);
-int pow2_mix_row_prepare(pfb_conv_plan* p, FastTables* ft);
-int pow2_mix_rows_per_wg(const pfb_conv_plan* p);
-int pow2_mix_row_fwd_launch(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
-                            const void* beam, size_t xpitch, size_t xband, hipStream_t st);
-int pow2_mix_row_inv_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x, const void* beam,
-                            double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
-                            bool per_band, hipStream_t st);
+
+// The seam between the objects: what serves an axis, as a record of functions.  Each object defines the tables of the
+// classes it owns (its entry block at the end of the file); the two selectors are the only place that maps a length to
+// its family, and a length that the family has no class for is reported by the family's class dispatch (unsupported_len).
+struct ColPass {               // the column pass (nx)
+    int (*prepare)(pfb_conv_plan* p, FastTables* ft);                        // tables and LDS attributes
+    int (*launch)(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st);
+    int (*fwd_launch)(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st);   // PSFHAT producer
+};
+struct RowPass {               // the two row passes (ny / 2)
+    int (*prepare)(pfb_conv_plan* p, FastTables* ft);
+    int (*rows_per_wg)(const pfb_conv_plan* p);                              // of the plain inverse kernel (0: no such class)
+    int (*fwd_launch)(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
+                      const void* beam, size_t xpitch, size_t xband, hipStream_t st);
+    int (*inv_launch)(pfb_conv_plan* p, const FastTables* ft, const ApplyArgs& a);
+};
+// (reached through functions: a namespace-scope constant would also be emitted, host addresses and all, into the code object)
+const ColPass& col_pass_pow2();     // object 2
+const RowPass& row_pass_pow2();     // object 1
+const ColPass& col_pass_mix();      // object 3
+const RowPass& row_pass_mix();
+inline const ColPass& col_pass(const pfb_conv_plan* p) { return mix_col_len(p->nx) ? col_pass_mix() : col_pass_pow2(); }
+inline const RowPass& row_pass(const pfb_conv_plan* p) {
+    return mix_row_len(p->ny / 2, p->dtype == PFB_F32) ? row_pass_mix() : row_pass_pow2();
+}
+static int unsupported_len(const char* axis, int n) {
+    set_error("pow2: unsupported %s %d", axis, n);
+    return PFB_ERR_UNSUPPORTED;
+}
 
 // n table entries written by fill(cplx<T>*) -> a new device array
 template <typename T, typename Fill>
@@ -2077,7 +2061,6 @@ static int set_lds_max(K* kernel) {
     return PFB_OK;
 }
 
-#if PFB_POW2_COLK
 // Grid of the persistent column kernel k_col_pow2p: not all `maxgrid` resident workgroups but as many as give every one of them the same number
 // of trips.  `need` is rarely a multiple of the CU count (a band is 2^k + 1 column blocks), and a last trip with a handful
 // of workgroups runs at their latency while the rest of the chip idles -- the same work on slightly fewer workgroups is
@@ -2165,7 +2148,7 @@ template <typename T, int H> struct ColKernels {
 };
 
 template <typename T, int H>
-static void launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
+static int launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
     using C = ColCfg<T, H>;
     using CK = ColKernels<T, H>;
     constexpr auto S = C::shape();
@@ -2194,11 +2177,12 @@ static void launch_col(pfb_conv_plan* p, const FastTables* ft, int band0, int nb
                                p->psf_elems_per_band, band_first, -1);
         });
     }
+    return PFB_OK;
 }
 
 // PSFHAT producer: the four quadrant spectra in Tq (slots of T_elems_per_band) -> psf_l of `band`
 template <typename T, int H>
-static void launch_col_fwd(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
+static int launch_col_fwd(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
     using C = ColCfg<T, H>;
     using CK = ColKernels<T, H>;
     const int L = p->ny / 2;
@@ -2207,6 +2191,7 @@ static void launch_col_fwd(pfb_conv_plan* p, const FastTables* ft, const void* T
                        (const cplx<T>*)Tq, (cplx<T>*)p->psf_l + (size_t)band * p->psf_elems_per_band,
                        (const cplx<T>*)p->twP, (const cplx<T>*)ft->tab[PTW_COL], nblk, nbe, p->T_elems_per_band,
                        col_two_level(H));
+    return PFB_OK;
 }
 
 // tables and LDS attributes of class (T, H)
@@ -2220,30 +2205,21 @@ static int col_prepare(FastTables* ft) {
     return rc;
 }
 
-#endif  // PFB_POW2_COLK
+// The ColPass of a class family.  D::each(p, f) is the family's class dispatch: f(T{}, std::integral_constant<int, H>) -> int
+// for the plan's type and nx, or unsupported_len.
+template <typename D> struct ColPassOf {
+    static int prepare(pfb_conv_plan* p, FastTables* ft) {
+        return D::each(p, [&](auto t, auto h) { return col_prepare<decltype(t), h()>(ft); });
+    }
+    static int launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
+        return D::each(p, [&](auto t, auto h) { return launch_col<decltype(t), h()>(p, ft, band0, nb, st); });
+    }
+    static int fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
+        return D::each(p, [&](auto t, auto h) { return launch_col_fwd<decltype(t), h()>(p, ft, Tq, band, st); });
+    }
+    static constexpr ColPass table = {prepare, launch, fwd_launch};
+};
 
-#if PFB_POW2_COL
-// f(T{}, std::integral_constant<int, H>) for the plan's type and nx
-template <typename Fn>
-static int for_col_class(const pfb_conv_plan* p, Fn&& f) {
-    const bool ok = for_pow2_size(p->nx, [&](auto h) { if (p->dtype == PFB_F32) f(float{}, h); else f(double{}, h); });
-    if (!ok) set_error("pow2: unsupported nx");
-    return ok ? PFB_OK : PFB_ERR_UNSUPPORTED;
-}
-int pow2_col_prepare(pfb_conv_plan* p, FastTables* ft) {
-    int rc = PFB_OK;
-    const int rs = for_col_class(p, [&](auto t, auto h) { rc = col_prepare<decltype(t), h()>(ft); });
-    return rs != PFB_OK ? rs : rc;
-}
-int pow2_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
-    return for_col_class(p, [&](auto t, auto h) { launch_col<decltype(t), h()>(p, ft, band0, nb, st); });
-}
-int pow2_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
-    return for_col_class(p, [&](auto t, auto h) { launch_col_fwd<decltype(t), h()>(p, ft, Tq, band, st); });
-}
-#endif  // PFB_POW2_COL
-
-#if PFB_POW2_RESTK
 // The forward row kernels of class (T, L = ny / 2): the persistent one where FwdP::OK, else the plain one.
 // (FwdP is written for power-of-two rows and is not even instantiated for the others)
 template <typename T, int L> constexpr bool fwdp_ok() {
@@ -2312,97 +2288,8 @@ static int row_prepare(FastTables* ft) {
     return rc;
 }
 
-template <typename T>
-static int prep_tables(pfb_conv_plan* p, FastTables* ft) {
-    const int L = p->ny / 2;
-    int rc = is_pow2(p->nx) ? pow2_col_prepare(p, ft) : pow2_mix_col_prepare(p, ft);
-    if (rc != PFB_OK) return rc;
-    if (!is_pow2(L)) rc = pow2_mix_row_prepare(p, ft);
-    else if (!for_pow2_size(L, [&](auto l) { rc = row_prepare<T, l()>(ft); })) return PFB_ERR_UNSUPPORTED;
-    if (rc != PFB_OK) return rc;
-    // twM[n] = exp(-2 pi i n / M), n < L  (M = ny)
-    return upload_table<T>(&ft->tab[TW_M], L, [&](cplx<T>* h) {
-        const long double two_pi = 6.283185307179586476925286766559005768L;
-        for (int n = 0; n < L; ++n) {
-            long double a = two_pi * (long double)n / (long double)p->ny;
-            h[n] = cplx<T>((T)cosl(a), (T)(-sinl(a)));
-        }
-    });
-}
-
-#if PFB_POW2_REST
-bool pow2_supported(const pfb_conv_plan* p) {
-    const bool f32 = p->dtype == PFB_F32;
-    if (p->P != 2 * p->nx || p->Q != 2 * p->ny || p->ny % 2) return false;
-    if (!(is_pow2(p->nx) && p->nx >= 64 && p->nx <= 8192) && !mix_col_len(p->nx)) return false;
-    // rows: one length-ny/2 complex transform per image row in LDS: 8192 complex64 (ny = 16384) fit, complex128 do not
-    if (!(is_pow2(p->ny) && p->ny >= 128 && p->ny <= (f32 ? 16384 : 8192)) && !mix_row_len(p->ny / 2, f32)) return false;
-    // the row launchers run nx / G workgroups of G rows, G <= ROW_TILE_MAX a power of two: G must divide nx (this is what
-    // keeps nx = 80 out: the shortest rows are tiled 32 to a workgroup)
-    return p->nx % ROW_TILE_MAX == 0;
-}
-#endif
-
 template <typename T, int L>
 static int rows_per_wg() { return row_groups<T, L, RowCfg<T, L, true>::E, RowCfg<T, L, true>::GMAX>(); }
-
-#if PFB_POW2_REST
-int pow2_rows_per_wg(const pfb_conv_plan* p) {
-    const bool f32 = p->dtype == PFB_F32;
-    int g = 0;
-    if (!is_pow2(p->ny / 2)) return pow2_mix_rows_per_wg(p);
-    for_pow2_size(p->ny / 2, [&](auto l) { g = f32 ? rows_per_wg<float, l()>() : rows_per_wg<double, l()>(); });
-    return g;
-}
-
-int pow2_nblocks(const pfb_conv_plan* p) {
-    return fast_nblocks(p->ny / 2, p->dtype == PFB_F32 ? FastCfg<float>::NVB : FastCfg<double>::NVB);
-}
-int pow2_nvb(const pfb_conv_plan* p) {
-    return p->dtype == PFB_F32 ? FastCfg<float>::NVB : FastCfg<double>::NVB;
-}
-
-int pow2_prepare(pfb_conv_plan* p) {
-    FastTables* ft = (FastTables*)calloc(1, sizeof(FastTables));
-    PFB_REQUIRE(ft != nullptr, PFB_ERR_ALLOC, "pow2_prepare: host alloc failed");
-    p->fast_tables = ft;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-        ft->num_cu = prop.multiProcessorCount;
-    if (ft->num_cu <= 0) ft->num_cu = 256;
-    return p->dtype == PFB_F32 ? prep_tables<float>(p, ft) : prep_tables<double>(p, ft);
-}
-
-void pow2_release(pfb_conv_plan* p) {
-    FastTables* ft = (FastTables*)p->fast_tables;
-    if (!ft) return;
-    if (ft->tab[PTWC_ROW_INV_P] == ft->tab[PTWC_ROW_INV]) ft->tab[PTWC_ROW_INV_P] = nullptr;      // the alias
-    for (void* t : ft->tab)
-        if (t) (void)hipFree(t);
-    free(ft);
-    p->fast_tables = nullptr;
-}
-#endif  // PFB_POW2_REST
-
-template <typename T>
-static int set_psfhat_t(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
-    const int nv = p->M + 1;
-    // the dummy partner of the last even bin (and nothing else) is never written: zero all
-    PFB_HIP_CHECK(hipMemsetAsync(p->psf_l, 0, sizeof(cplx<T>) * p->psf_elems_per_band * p->nband, st));
-    dim3 grid((nv + 31) / 32, (p->P + 31) / 32, p->nband);
-    hipLaunchKernelGGL((k_relayout_psf_pow2<T>), grid, dim3(256), 0, st, (const cplx<T>*)psfhat,
-                       (cplx<T>*)p->psf_l, p->P, nv, p->ny / 2, FastCfg<T>::NVB, p->psf_elems_per_band,
-                       col_two_level(p->nx));
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
-
-#if PFB_POW2_REST
-int pow2_set_psfhat(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
-    return p->dtype == PFB_F32 ? set_psfhat_t<float>(p, psfhat, st) : set_psfhat_t<double>(p, psfhat, st);
-}
-#endif
 
 static FastDims fast_dims(const pfb_conv_plan* p, size_t xpitch, size_t xband) {
     return FastDims{p->nx, p->ny, p->M, p->T_elems_per_band, p->psf_elems_per_band, xpitch, xband};
@@ -2417,8 +2304,8 @@ static cplx<T> wq1_of(const pfb_conv_plan* p) {
 // Tbuf: the half-spectrum buffer to fill (the plan's T, or the PSFHAT producer's quadrant scratch: `band0`
 // is then the slot); xpitch / xband: elements between rows / bands of x (and beam)
 template <typename T, int L>
-static void launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
-                           const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
+static int launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
+                          const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
     using K = RowFwdK<T, L>;
     const FastDims d = fast_dims(p, xpitch, xband);
     if constexpr (K::PERSISTENT) {
@@ -2443,6 +2330,176 @@ static void launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, i
                            (const T*)x, (const T*)beam, (cplx<T>*)Tbuf, (const cplx<T>*)p->twQ,
                            (const cplx<T>*)ft->tab[TW_M], (const cplx<T>*)ft->tab[PTW_ROW], d, band0);
     }
+    return PFB_OK;
+}
+
+template <typename T, int L>
+static int launch_row_inv(pfb_conv_plan* p, const FastTables* ft, const ApplyArgs& a) {
+    using K = RowInvK<T, L>;
+    const FastDims d = fast_dims(p, (size_t)p->ny, (size_t)p->nx * p->ny);
+    const int band0 = a.band0, nb = a.nb;
+    if constexpr (K::PERSISTENT) {
+        // pipelined persistent kernel: inner products only against x itself (+ dot_with2)
+        const bool plain_dots = !a.dot_with || (a.dot_with == a.x);
+        if (plain_dots && !(a.dot_with2 && !a.dot_with)) {
+            using IP = typename K::IP;
+            const cplx<T> wq1 = wq1_of<T>(p);
+            // the (mode, beam given, pb) instantiation over bands [b0, b0 + nbl) on `grid` workgroups; the operands of
+            // band b0 lie `off` elements into x / beam / dot_with2 / out
+            auto launch = [&](int mode, bool pb, int b0, int nbl, int grid, size_t off, double* part) {
+                K::persistent([&](auto* k, int m, bool bm, bool pbv) {
+                    if (m != mode || bm != (a.beam != nullptr) || pbv != pb) return;
+                    hipLaunchKernelGGL(k, dim3(grid), dim3(IP::NT), IP::LDS, a.st,
+                                       (const cplx<T>*)p->T, (const cplx<T>*)ft->tab[TW_M],
+                                       (const cplx<T>*)ft->tab[PTWC_ROW_INV_P], (const T*)a.x + off,
+                                       a.beam ? (const T*)a.beam + off : nullptr,
+                                       a.dot_with2 ? (const T*)a.dot_with2 + off : nullptr, (T*)a.out + off, part, d,
+                                       b0, p->nx / IP::G, p->nx / IP::G * nbl, (T)a.scale, (T)a.sigmainv, wq1);
+                });
+            };
+            const int mode = !a.dot_with ? 0 : !a.dot_with2 ? 1 : 2;
+            const int tiles_per_band = p->nx / IP::G, ntiles = tiles_per_band * nb;
+            int grid = ntiles < IP::WG_PER_CU * ft->num_cu ? ntiles : IP::WG_PER_CU * ft->num_cu;
+            if (a.per_band && a.dot_with) {
+                if constexpr (K::PER_BAND) {
+                    if (a.dot_with2) {            // one launch, partials [3][nb][grid]
+                        if ((size_t)grid * nb > (size_t)p->nx * p->nband) grid = p->nx * p->nband / nb;   // partials: nx x nband
+                        launch(2, true, band0, nb, grid, 0, p->partials);
+                        p->last = {grid * nb, grid, grid * nb, grid};
+                        return PFB_OK;
+                    }
+                }
+                // the whole-cube kernel once per band (the same launches a band-by-band solve makes): band bl's
+                // partials land at [bl][3][grid1]
+                const int grid1 = tiles_per_band < IP::WG_PER_CU * ft->num_cu ? tiles_per_band : IP::WG_PER_CU * ft->num_cu;
+                const size_t bandel = (size_t)p->nx * p->ny;
+                for (int bl = 0; bl < nb; ++bl)
+                    launch(mode, false, band0 + bl, 1, grid1, bl * bandel, p->partials + (size_t)bl * 3 * grid1);
+                p->last = {grid1 * nb, grid1, grid1, 3 * grid1};
+                return PFB_OK;
+            }
+            p->last = {grid, nb == 1 ? grid : 0, grid, grid};
+            launch(mode, false, band0, nb, grid, 0, p->partials);
+            return PFB_OK;
+        }
+    }
+    constexpr int E = K::E;
+    using F = RegFft<T, L, E, RowCfg<T, L, true>::WAVE>;
+    constexpr int G = row_groups<T, L, E, RowCfg<T, L, true>::GMAX>();
+    static_assert(ROW_TILE_MAX % G == 0, "pow2_supported: the row tile divides nx");
+    const size_t lds = 384 + sizeof(cplx<T>) * ((size_t)((F::PTWC + 1) & ~1) + (size_t)G * (F::LDS_ELEMS + 4) * (InvDb<T, L>::ON ? 2 : 1));
+    hipLaunchKernelGGL(K::plain(), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, a.st,
+                       (const cplx<T>*)p->T, (const cplx<T>*)p->twQ, (const cplx<T>*)ft->tab[TW_M],
+                       (const cplx<T>*)ft->tab[PTWC_ROW_INV], (const T*)a.x, (const T*)a.beam, (const T*)a.dot_with,
+                       (const T*)a.dot_with2, (T*)a.out, p->partials, d, band0, (T)a.scale, (T)a.sigmainv);
+    return PFB_OK;
+}
+
+// The RowPass of a class family; D::each(p, f): f(T{}, std::integral_constant<int, L>) -> int for the plan's type and ny / 2
+template <typename D> struct RowPassOf {
+    static int prepare(pfb_conv_plan* p, FastTables* ft) {
+        return D::each(p, [&](auto t, auto l) { return row_prepare<decltype(t), l()>(ft); });
+    }
+    static int rows_per_wg(const pfb_conv_plan* p) {
+        int g = 0;
+        (void)D::each(p, [&](auto t, auto l) { g = pfb::rows_per_wg<decltype(t), l()>(); return PFB_OK; });
+        return g;
+    }
+    static int fwd_launch(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
+                          const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
+        return D::each(p, [&](auto t, auto l) {
+            return launch_row_fwd<decltype(t), l()>(p, ft, Tbuf, band0, nb, x, beam, xpitch, xband, st);
+        });
+    }
+    static int inv_launch(pfb_conv_plan* p, const FastTables* ft, const ApplyArgs& a) {
+        return D::each(p, [&](auto t, auto l) { return launch_row_inv<decltype(t), l()>(p, ft, a); });
+    }
+    static constexpr RowPass table = {prepare, rows_per_wg, fwd_launch, inv_launch};
+};
+
+// ---------------------------------------------------------------------------------------------- the objects' entry blocks
+// (the order in which a class dispatch walks types and lengths is the order in which its object's kernels are instantiated
+// and laid out: all of fp32 before fp64 for the rows, length by length for the columns -- kept as the objects were measured)
+#if PFB_POW2_PART == 1
+// ------------------------------------------------- object 1: the power-of-two rows and the fast path's public entry points
+struct for_row_class {
+    template <typename T, typename Fn> static int lengths(const pfb_conv_plan* p, Fn& f) {
+        int rc = PFB_OK;
+        return for_pow2_size(p->ny / 2, [&](auto l) { rc = f(T{}, l); }) ? rc : unsupported_len("ny / 2", p->ny / 2);
+    }
+    template <typename Fn> static int each(const pfb_conv_plan* p, Fn&& f) {
+        return p->dtype == PFB_F32 ? lengths<float>(p, f) : lengths<double>(p, f);
+    }
+};
+const RowPass& row_pass_pow2() { return RowPassOf<for_row_class>::table; }
+
+bool pow2_supported(const pfb_conv_plan* p) {
+    const bool f32 = p->dtype == PFB_F32;
+    if (p->P != 2 * p->nx || p->Q != 2 * p->ny || p->ny % 2) return false;
+    if (!(is_pow2(p->nx) && p->nx >= 64 && p->nx <= 8192) && !mix_col_len(p->nx)) return false;
+    // rows: one length-ny/2 complex transform per image row in LDS: 8192 complex64 (ny = 16384) fit, complex128 do not
+    if (!(is_pow2(p->ny) && p->ny >= 128 && p->ny <= (f32 ? 16384 : 8192)) && !mix_row_len(p->ny / 2, f32)) return false;
+    // the row launchers run nx / G workgroups of G rows, G <= ROW_TILE_MAX a power of two: G must divide nx (this is what
+    // keeps nx = 80 out: the shortest rows are tiled 32 to a workgroup)
+    return p->nx % ROW_TILE_MAX == 0;
+}
+int pow2_rows_per_wg(const pfb_conv_plan* p) { return row_pass(p).rows_per_wg(p); }
+int pow2_nblocks(const pfb_conv_plan* p) {
+    return fast_nblocks(p->ny / 2, p->dtype == PFB_F32 ? FastCfg<float>::NVB : FastCfg<double>::NVB);
+}
+int pow2_nvb(const pfb_conv_plan* p) {
+    return p->dtype == PFB_F32 ? FastCfg<float>::NVB : FastCfg<double>::NVB;
+}
+
+template <typename T>
+static int prep_tables(pfb_conv_plan* p, FastTables* ft) {
+    const int L = p->ny / 2;
+    if (int rc = col_pass(p).prepare(p, ft); rc != PFB_OK) return rc;
+    if (int rc = row_pass(p).prepare(p, ft); rc != PFB_OK) return rc;
+    // twM[n] = exp(-2 pi i n / M), n < L  (M = ny)
+    return upload_table<T>(&ft->tab[TW_M], L, [&](cplx<T>* h) {
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        for (int n = 0; n < L; ++n) {
+            long double a = two_pi * (long double)n / (long double)p->ny;
+            h[n] = cplx<T>((T)cosl(a), (T)(-sinl(a)));
+        }
+    });
+}
+int pow2_prepare(pfb_conv_plan* p) {
+    FastTables* ft = (FastTables*)calloc(1, sizeof(FastTables));
+    PFB_REQUIRE(ft != nullptr, PFB_ERR_ALLOC, "pow2_prepare: host alloc failed");
+    p->fast_tables = ft;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+        ft->num_cu = prop.multiProcessorCount;
+    if (ft->num_cu <= 0) ft->num_cu = 256;
+    return p->dtype == PFB_F32 ? prep_tables<float>(p, ft) : prep_tables<double>(p, ft);
+}
+void pow2_release(pfb_conv_plan* p) {
+    FastTables* ft = (FastTables*)p->fast_tables;
+    if (!ft) return;
+    if (ft->tab[PTWC_ROW_INV_P] == ft->tab[PTWC_ROW_INV]) ft->tab[PTWC_ROW_INV_P] = nullptr;      // the alias
+    for (void* t : ft->tab)
+        if (t) (void)hipFree(t);
+    free(ft);
+    p->fast_tables = nullptr;
+}
+
+template <typename T>
+static int set_psfhat_t(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
+    const int nv = p->M + 1;
+    // the dummy partner of the last even bin (and nothing else) is never written: zero all
+    PFB_HIP_CHECK(hipMemsetAsync(p->psf_l, 0, sizeof(cplx<T>) * p->psf_elems_per_band * p->nband, st));
+    dim3 grid((nv + 31) / 32, (p->P + 31) / 32, p->nband);
+    hipLaunchKernelGGL((k_relayout_psf_pow2<T>), grid, dim3(256), 0, st, (const cplx<T>*)psfhat,
+                       (cplx<T>*)p->psf_l, p->P, nv, p->ny / 2, FastCfg<T>::NVB, p->psf_elems_per_band,
+                       col_two_level(p->nx));
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+int pow2_set_psfhat(pfb_conv_plan* p, const void* psfhat, hipStream_t st) {
+    return p->dtype == PFB_F32 ? set_psfhat_t<float>(p, psfhat, st) : set_psfhat_t<double>(p, psfhat, st);
 }
 
 // psfhat = r2c(ifftshift(psf)) with the fast path's own kernels (see k_col_fwd_pow2), band by band:
@@ -2460,18 +2517,13 @@ static int set_psf_t(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStr
     int rc = PFB_OK;
     for (int band = 0; band < p->nband && rc == PFB_OK; ++band) {
         const T* pb = (const T*)psf + (size_t)band * P * Q;
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < 4 && rc == PFB_OK; ++q) {
             // quadrant (a, b) of the SHIFTED PSF = quadrant (1 - a, 1 - b) of the centred one
             const int a = q >> 1, b = q & 1;
             const T* src = pb + (size_t)((1 - a) * nx) * Q + (size_t)(1 - b) * ny;
-            if (!is_pow2(L)) {
-                if (rc == PFB_OK) rc = pow2_mix_row_fwd_launch(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st);
-            } else if (!for_pow2_size(L, [&](auto l) { launch_row_fwd<T, l()>(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st); })) {
-                set_error("pow2_set_psf: unsupported ny");
-                rc = PFB_ERR_UNSUPPORTED;
-            }
+            rc = row_pass(p).fwd_launch(p, ft, Tq, q, 1, src, nullptr, (size_t)Q, (size_t)0, st);
         }
-        if (rc == PFB_OK) rc = is_pow2(nx) ? pow2_col_fwd_launch(p, ft, Tq, band, st) : pow2_mix_col_fwd_launch(p, ft, Tq, band, st);
+        if (rc == PFB_OK) rc = col_pass(p).fwd_launch(p, ft, Tq, band, st);
     }
     if (rc == PFB_OK && psfhat_out) {
         const int nv = p->M + 1;
@@ -2486,186 +2538,90 @@ static int set_psf_t(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStr
     (void)hipFree(Tq);
     return rc;
 }
-
-#if PFB_POW2_REST
 int pow2_set_psf(pfb_conv_plan* p, const void* psf, void* psfhat_out, hipStream_t st) {
     return p->dtype == PFB_F32 ? set_psf_t<float>(p, psf, psfhat_out, st) : set_psf_t<double>(p, psf, psfhat_out, st);
 }
-#endif
 
-template <typename T, int L>
-static void launch_row_inv(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x,
-                           const void* beam, double scale, double sigmainv, void* out,
-                           const void* dot_with, const void* dot_with2, bool per_band, hipStream_t st) {
-    using K = RowInvK<T, L>;
-    const FastDims d = fast_dims(p, (size_t)p->ny, (size_t)p->nx * p->ny);
-    if constexpr (K::PERSISTENT) {
-        // pipelined persistent kernel: inner products only against x itself (+ dot_with2)
-        const bool plain_dots = !dot_with || (dot_with == x);
-        if (plain_dots && !(dot_with2 && !dot_with)) {
-            using IP = typename K::IP;
-            const cplx<T> wq1 = wq1_of<T>(p);
-            // the (mode, beam given, pb) instantiation over bands [b0, b0 + nbl) on `grid` workgroups; the operands of
-            // band b0 lie `off` elements into x / beam / dot_with2 / out
-            auto launch = [&](int mode, bool pb, int b0, int nbl, int grid, size_t off, double* part) {
-                K::persistent([&](auto* k, int m, bool bm, bool pbv) {
-                    if (m != mode || bm != (beam != nullptr) || pbv != pb) return;
-                    hipLaunchKernelGGL(k, dim3(grid), dim3(IP::NT), IP::LDS, st,
-                                       (const cplx<T>*)p->T, (const cplx<T>*)ft->tab[TW_M],
-                                       (const cplx<T>*)ft->tab[PTWC_ROW_INV_P], (const T*)x + off,
-                                       beam ? (const T*)beam + off : nullptr,
-                                       dot_with2 ? (const T*)dot_with2 + off : nullptr, (T*)out + off, part, d,
-                                       b0, p->nx / IP::G, p->nx / IP::G * nbl, (T)scale, (T)sigmainv, wq1);
-                });
-            };
-            const int mode = !dot_with ? 0 : !dot_with2 ? 1 : 2;
-            const int tiles_per_band = p->nx / IP::G, ntiles = tiles_per_band * nb;
-            int grid = ntiles < IP::WG_PER_CU * ft->num_cu ? ntiles : IP::WG_PER_CU * ft->num_cu;
-            if (per_band && dot_with) {
-                if constexpr (K::PER_BAND) {
-                    if (dot_with2) {              // one launch, partials [3][nb][grid]
-                        if ((size_t)grid * nb > (size_t)p->nx * p->nband) grid = p->nx * p->nband / nb;   // partials: nx x nband
-                        launch(2, true, band0, nb, grid, 0, p->partials);
-                        p->last = {grid * nb, grid, grid * nb, grid};
-                        return;
-                    }
-                }
-                // the whole-cube kernel once per band (the same launches a band-by-band solve makes): band bl's
-                // partials land at [bl][3][grid1]
-                const int grid1 = tiles_per_band < IP::WG_PER_CU * ft->num_cu ? tiles_per_band : IP::WG_PER_CU * ft->num_cu;
-                const size_t bandel = (size_t)p->nx * p->ny;
-                for (int bl = 0; bl < nb; ++bl)
-                    launch(mode, false, band0 + bl, 1, grid1, bl * bandel, p->partials + (size_t)bl * 3 * grid1);
-                p->last = {grid1 * nb, grid1, grid1, 3 * grid1};
-                return;
-            }
-            p->last = {grid, nb == 1 ? grid : 0, grid, grid};
-            launch(mode, false, band0, nb, grid, 0, p->partials);
-            return;
-        }
-    }
-    constexpr int E = K::E;
-    using F = RegFft<T, L, E, RowCfg<T, L, true>::WAVE>;
-    constexpr int G = row_groups<T, L, E, RowCfg<T, L, true>::GMAX>();
-    static_assert(ROW_TILE_MAX % G == 0, "pow2_supported: the row tile divides nx");
-    const size_t lds = 384 + sizeof(cplx<T>) * ((size_t)((F::PTWC + 1) & ~1) + (size_t)G * (F::LDS_ELEMS + 4) * (InvDb<T, L>::ON ? 2 : 1));
-    hipLaunchKernelGGL(K::plain(), dim3(p->nx / G, nb), dim3(G * F::TPB), lds, st,
-                       (const cplx<T>*)p->T, (const cplx<T>*)p->twQ, (const cplx<T>*)ft->tab[TW_M],
-                       (const cplx<T>*)ft->tab[PTWC_ROW_INV], (const T*)x, (const T*)beam, (const T*)dot_with,
-                       (const T*)dot_with2, (T*)out, p->partials, d, band0, (T)scale, (T)sigmainv);
-}
-
-template <typename T>
-static int apply_t(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam, double scale,
-                   double sigmainv, void* out, const void* dot_with, const void* dot_with2, bool per_band,
-                   hipStream_t st) {
+// forward rows, columns, inverse rows: each axis through its seam
+int pow2_apply(pfb_conv_plan* p, const ApplyArgs& a) {
     const FastTables* ft = (const FastTables*)p->fast_tables;
-    const int L = p->ny / 2;
-    const bool rows_mix = !is_pow2(L);         // each axis on its own: 2^k -> this object's / the column object's launchers
-    prof_mark(p, st, 0);
-    if (rows_mix) {
-        if (int rc = pow2_mix_row_fwd_launch(p, ft, p->T, band0, nb, x, beam, (size_t)p->ny, (size_t)p->nx * p->ny, st); rc != PFB_OK)
-            return rc;
-    } else if (!for_pow2_size(L, [&](auto l) {
-            launch_row_fwd<T, l()>(p, ft, p->T, band0, nb, x, beam, (size_t)p->ny, (size_t)p->nx * p->ny, st);
-        })) {
-        set_error("pow2_apply: unsupported ny");
-        return PFB_ERR_UNSUPPORTED;
-    }
-    prof_mark(p, st, 1);
-    if (int rc = is_pow2(p->nx) ? pow2_col_launch(p, ft, band0, nb, st) : pow2_mix_col_launch(p, ft, band0, nb, st); rc != PFB_OK)
+    const RowPass& rows = row_pass(p);
+    prof_mark(p, a.st, 0);
+    if (int rc = rows.fwd_launch(p, ft, p->T, a.band0, a.nb, a.x, a.beam, (size_t)p->ny, (size_t)p->nx * p->ny, a.st); rc != PFB_OK)
         return rc;
-    prof_mark(p, st, 2);
-    if (rows_mix) {
-        if (int rc = pow2_mix_row_inv_launch(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
-            rc != PFB_OK)
-            return rc;
-    } else
-    for_pow2_size(L, [&](auto l) {
-        launch_row_inv<T, l()>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
-    });
-    prof_mark(p, st, 3);
+    prof_mark(p, a.st, 1);
+    if (int rc = col_pass(p).launch(p, ft, a.band0, a.nb, a.st); rc != PFB_OK) return rc;
+    prof_mark(p, a.st, 2);
+    if (int rc = rows.inv_launch(p, ft, a); rc != PFB_OK) return rc;
+    prof_mark(p, a.st, 3);
     PFB_HIP_CHECK(hipGetLastError());
     return PFB_OK;
 }
 
-#if PFB_POW2_REST
-int pow2_apply(pfb_conv_plan* p, int band0, int nb, const void* x, const void* beam, double scale,
-               double sigmainv, void* out, const void* dot_with, const void* dot_with2, bool per_band, hipStream_t st) {
-    return p->dtype == PFB_F32
-        ? apply_t<float>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st)
-        : apply_t<double>(p, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
+#if PFB_STAMP
+// diagnostic build only: buf = 3 * 1024 * PFB_STAMP_ITS * 16 device uint64 (NULL switches the stamps off); this object's
+// copy of g_stamp_buf and the column object's
+int pow2_col_set_stamp(unsigned long long* buf);
+extern "C" int pfb_debug_set_stamps(void* buf) {
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &buf, sizeof(buf)) != hipSuccess) return PFB_ERR_HIP;
+    return pow2_col_set_stamp((unsigned long long*)buf);
 }
 #endif
-#endif  // PFB_POW2_RESTK
 
-#if PFB_POW2_MIX
-// ------------------------------------------------- the lengths 3 2^k and 5 2^k (third object)
+#elif PFB_POW2_PART == 2
+// ------------------------------------------------- object 2: the power-of-two columns
+struct for_col_class {
+    template <typename Fn> static int each(const pfb_conv_plan* p, Fn&& f) {
+        int rc = PFB_OK;
+        const bool ok = for_pow2_size(p->nx, [&](auto h) { rc = p->dtype == PFB_F32 ? f(float{}, h) : f(double{}, h); });
+        return ok ? rc : unsupported_len("nx", p->nx);
+    }
+};
+const ColPass& col_pass_pow2() { return ColPassOf<for_col_class>::table; }
+
+#if PFB_STAMP
+int pow2_col_set_stamp(unsigned long long* buf) {
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &buf, sizeof(buf)) == hipSuccess ? PFB_OK : PFB_ERR_HIP;
+}
+#endif
+
+#elif PFB_POW2_PART == 3
+// ------------------------------------------------- object 3: the columns and rows of the lengths 3 2^k and 5 2^k
 // The classes are those of for_mix_size; a class is described by the same ColCfg / ColKernels / RowFwdK / RowInvK as a
 // power-of-two one (every one of them Plain / not PERSISTENT by construction) and launched by the same templates.
-// f(T{}, std::integral_constant<int, N>) for the plan's type and the length n; rows: only what mix_row_len allows
-template <bool ROWS, typename Fn>
-static int for_mix_class(const pfb_conv_plan* p, int n, Fn&& f) {
-    const bool f32 = p->dtype == PFB_F32;
-    bool ok = ROWS ? mix_row_len(n, f32) : mix_col_len(n);
-    ok = ok && for_mix_size(n, [&](auto c) {
-        constexpr int N = decltype(c)::value;
-        if constexpr (ROWS) {
-            if (f32) f(float{}, c);
-            else if constexpr (N <= mix_row_max(false)) f(double{}, c);
-        } else if constexpr (N >= MIX_COL_MIN) {
-            if (f32) f(float{}, c); else f(double{}, c);
-        }
-    });
-    if (!ok) set_error("pow2: unsupported %s %d", ROWS ? "ny / 2" : "nx", n);
-    return ok ? PFB_OK : PFB_ERR_UNSUPPORTED;
-}
-int pow2_mix_col_prepare(pfb_conv_plan* p, FastTables* ft) {
-    int rc = PFB_OK;
-    const int rs = for_mix_class<false>(p, p->nx, [&](auto t, auto h) {
-        static_assert(ColCfg<decltype(t), h()>::KIND == ColKind::Plain && !col_two_level(h()), "plain column kernel");
-        rc = col_prepare<decltype(t), h()>(ft);
-    });
-    return rs != PFB_OK ? rs : rc;
-}
-int pow2_mix_col_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, hipStream_t st) {
-    return for_mix_class<false>(p, p->nx, [&](auto t, auto h) { launch_col<decltype(t), h()>(p, ft, band0, nb, st); });
-}
-int pow2_mix_col_fwd_launch(pfb_conv_plan* p, const FastTables* ft, const void* Tq, int band, hipStream_t st) {
-    return for_mix_class<false>(p, p->nx, [&](auto t, auto h) { launch_col_fwd<decltype(t), h()>(p, ft, Tq, band, st); });
-}
-int pow2_mix_row_prepare(pfb_conv_plan* p, FastTables* ft) {
-    int rc = PFB_OK;
-    const int rs = for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) {
-        using T = decltype(t);
-        static_assert(!RowFwdK<T, l()>::PERSISTENT && !RowInvK<T, l()>::PERSISTENT && !RowInvK<T, l()>::PER_BAND, "plain row kernels");
-        rc = row_prepare<T, l()>(ft);
-    });
-    return rs != PFB_OK ? rs : rc;
-}
-int pow2_mix_rows_per_wg(const pfb_conv_plan* p) {
-    int g = 0;
-    for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) { g = rows_per_wg<decltype(t), l()>(); });
-    return g;
-}
-int pow2_mix_row_fwd_launch(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, int band0, int nb, const void* x,
-                            const void* beam, size_t xpitch, size_t xband, hipStream_t st) {
-    return for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) {
-        launch_row_fwd<decltype(t), l()>(p, ft, Tbuf, band0, nb, x, beam, xpitch, xband, st);
-    });
-}
-int pow2_mix_row_inv_launch(pfb_conv_plan* p, const FastTables* ft, int band0, int nb, const void* x, const void* beam,
-                            double scale, double sigmainv, void* out, const void* dot_with, const void* dot_with2,
-                            bool per_band, hipStream_t st) {
-    return for_mix_class<true>(p, p->ny / 2, [&](auto t, auto l) {
-        launch_row_inv<decltype(t), l()>(p, ft, band0, nb, x, beam, scale, sigmainv, out, dot_with, dot_with2, per_band, st);
-    });
-}
-#endif  // PFB_POW2_MIX
+// f(T{}, std::integral_constant<int, N>) -> int for the plan's type and axis length; rows: fp64 up to mix_row_max only
+template <bool ROWS> struct for_mix_class {
+    template <typename Fn> static int each(const pfb_conv_plan* p, Fn&& f) {
+        const bool f32 = p->dtype == PFB_F32;
+        const int n = ROWS ? p->ny / 2 : p->nx;
+        int rc = PFB_OK;
+        bool ok = false;                                  // stays where (type, n) has no class
+        for_mix_size(n, [&](auto c) {
+            constexpr int N = decltype(c)::value;
+            auto plain = [&](auto t) {
+                using T = decltype(t);
+                if constexpr (ROWS)
+                    static_assert(!RowFwdK<T, N>::PERSISTENT && !RowInvK<T, N>::PERSISTENT && !RowInvK<T, N>::PER_BAND, "plain row kernels");
+                else
+                    static_assert(ColCfg<T, N>::KIND == ColKind::Plain && !col_two_level(N), "plain column kernel");
+                ok = true;
+                return f(t, c);
+            };
+            if constexpr (ROWS) {
+                if (f32) rc = plain(float{});
+                else if constexpr (N <= mix_row_max(false)) rc = plain(double{});
+            } else if constexpr (N >= MIX_COL_MIN) {
+                rc = f32 ? plain(float{}) : plain(double{});
+            }
+        });
+        return ok ? rc : unsupported_len(ROWS ? "ny / 2" : "nx", n);
+    }
+};
+const ColPass& col_pass_mix() { return ColPassOf<for_mix_class<false>>::table; }
+const RowPass& row_pass_mix() { return RowPassOf<for_mix_class<true>>::table; }
+
+#else
+#error "PFB_POW2_PART must be 1, 2 or 3 (csrc/Makefile: FLAGS_fftconv_pow2 / _col / _mix)"
+#endif
 
 }  // namespace pfb
-
-#if PFB_STAMP && PFB_POW2_REST
-// diagnostic build only: buf = 3 * 1024 * PFB_STAMP_ITS * 16 device uint64 (NULL switches the stamps off)
-extern "C" int pfb_debug_set_stamps(void* buf) { return pfb::pow2_set_stamp((unsigned long long*)buf); }
-#endif

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Register / scratch use of the kernels the BASELINE configs launch (hipcc -Rpass-analysis=kernel-resource-usage on the two
-# objects of fftconv_pow2.hip and on cgvec.hip / wavelet.hip, built by csrc/Makefile with its flags); exits non-zero if one
-# of them uses scratch.
+# of fftconv_pow2.hip's three objects that hold them -- the power-of-two rows and columns -- and on cgvec.hip / wavelet.hip,
+# built by csrc/Makefile with its flags); exits non-zero if one of them uses scratch.
 #   tools/check_scratch.sh [output.md]
 set -e
 cd "$(dirname "$0")/.."
