@@ -1,8 +1,8 @@
 """Ownership of the library's native plans: who may use a plan, on which stream, and when it is freed.
 
 A plan is single-owner in the C ABI (one stream and one host thread at a time: its device workspace is per plan).  A
-plan that several host threads share -- one handed out by a PlanCache -- is used under its `lock`, with
-`_enter_stream()` called before each enqueue.  A plan is destroyed by close() or when its last holder drops it.
+plan that several host threads share -- one handed out by a PlanCache -- is used through `run()`: its `lock` held,
+the stream ordered behind the previous user's.  A plan is destroyed by close() or when its last holder drops it.
 """
 import ctypes as C
 import threading
@@ -33,7 +33,8 @@ class NativePlan:
         dependency (an event recorded behind the previous user's enqueue, waited for by the current stream), never a
         host wait: with the reference's dask-thread pattern (several threads, one plan, a stream per thread,
         pcg.py:346-356) a host synchronize here would stall every thread queued on the lock until the previous thread's
-        whole stream had drained.  Same stream: stream order already serialises the kernels."""
+        whole stream had drained.  Same stream: stream order already serialises the kernels.  Returns the current
+        stream's handle."""
         cur = torch.cuda.current_stream()
         last = self.__dict__.get('_last_stream')
         if last is not None and last != cur:
@@ -41,6 +42,14 @@ class NativePlan:
             ev.record(last)               # behind everything the previous user has enqueued so far (it holds no lock now)
             cur.wait_event(ev)
         self._last_stream = cur
+        return cur.cuda_stream
+
+    def run(self, fn_name, *args):
+        """Enqueue the library's `fn_name(handle, *args, stream)` on the current stream: under `lock`, behind the
+        previous user's work (_enter_stream), the status checked.  THE way into a native plan."""
+        with self.lock:
+            stream = self._enter_stream()
+            _lib.check(getattr(self._lib, fn_name)(self._h, *args, stream))
 
     def close(self):
         """Destroy the plan once the device is idle; later calls do nothing."""

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .. import _dev, _lib
-from .psf import plan_for, PsfConvPlan, psf_convolve_cube
+from .psf import plan_for, PsfConvPlan, psf_convolve_cube, _run
 
 
 class HessianPsf:
@@ -69,13 +69,9 @@ class HessianPsf:
     def apply_dots(self, x, out, dots_out):
         """out = A(x) for contiguous device cubes of the plan's own grid, with <x, A x> left in dots_out[0] and
         <A x, A x> in dots_out[2] (device fp64) out of the convolution's epilogue."""
-        plan = self.plan
-        with plan.lock:
-            plan._enter_stream()
-            _lib.check(_lib.load().pfb_psfconv_apply_dots(
-                plan.handle, self.band0, self.nb, _dev.ptr(x), _dev.ptr(self.beam),
-                self.wsum if self.wsum is not None else 0.0, self.sigmainv, _dev.ptr(out), _dev.ptr(x), None,
-                _dev.ptr(dots_out), _dev.stream()))
+        self.plan.run('pfb_psfconv_apply_dots', self.band0, self.nb, _dev.ptr(x), _dev.ptr(self.beam),
+                      self.wsum if self.wsum is not None else 0.0, self.sigmainv, _dev.ptr(out), _dev.ptr(x), None,
+                      _dev.ptr(dots_out))
 
 
 class hessian_psf_slice:
@@ -125,29 +121,12 @@ class hessian_psf_slice:
         self.wsum = wsum
 
 
-def _hess(psfhat, beam, lastsize, x, xout, sigmainv, wsum):
-    xd = _dev.to_dev(x)
-    nx, ny = xd.shape[-2:]
-    plan = plan_for(psfhat, nx, ny, lastsize)
-    if xd.dtype != plan.rdtype:
-        raise TypeError(f"x is {xd.dtype} but psfhat is {psfhat.dtype}")
-    bd = None
-    if beam is not None:
-        bd = _dev.to_dev(beam, plan.rdtype)
-        if tuple(bd.shape) != tuple(xd.shape):
-            raise ValueError('Beam has incorrect shape')
-    res = plan.apply(xd, beam=bd, wsum=wsum, sigmainv=sigmainv)
-    if xout is not None:
-        _dev.deliver(res, xout)
-    return _dev.host_like(res, x)
-
-
 def _hessian_psf_slice(xpad, xhat, xout, psfhat, beam, lastsize, x,
                        nthreads=1, sigmainv=1, wsum=None):
     """pfb/operators/hessian.py:129-158 -- note (psfhat, beam) order."""
     if x.ndim != 2:
         raise ValueError("_hessian_psf_slice expects a 2-D image")
-    return _hess(psfhat, beam, lastsize, x, xout, sigmainv, wsum)
+    return _run(psfhat, lastsize, x, xout, beam, wsum, sigmainv, fresh=True)
 
 
 def hessian_psf_cube(xpad, xhat, xout, beam, psfhat, lastsize, x,
@@ -155,7 +134,7 @@ def hessian_psf_cube(xpad, xhat, xout, beam, psfhat, lastsize, x,
     """pfb/operators/hessian.py:254-281 -- note (beam, psfhat) order."""
     if x.ndim != 3:
         raise ValueError("hessian_psf_cube expects a (nband, nx, ny) cube")
-    return _hess(psfhat, beam, lastsize, x, xout, sigmainv, wsum)
+    return _run(psfhat, lastsize, x, xout, beam, wsum, sigmainv, fresh=True)
 
 
 # --------------------------------------------------- the parametrised forward step (workers/fwdbwd.py:246-252)
@@ -181,7 +160,8 @@ class ParamHessian:
     construction (x0 is copied); a new x0 needs a new ParamHessian, which is what pcg / power_method build per call from
     the worker's partial.  psfhat: as HessianPsf, or a PsfConvPlan.
     Callable on GPU tensors or numpy arrays of shape (nband, nx, ny); recognised by opt/pcg.py (pfb_pcg_solve_param),
-    opt/power_method.py and opt/primal_dual.py::ParamGradient.  More than 16 bands: `fused` is False and a call
+    opt/power_method.py and opt/primal_dual.py::ParamGradient.  On an embedded plan e lives on the plan's grid, zero
+    outside the image (the padded domain, operators/psf.py), and a call stages v like PsfConvPlan.apply.  More than 16 bands: `fused` is False and a call
     evaluates the closure composition as it stands."""
 
     def __init__(self, psfhat, nx, ny, lastsize, x0, sigmainv, dfunc, dhfunc):
@@ -210,11 +190,7 @@ class ParamHessian:
         if self.mode == 'exp':
             from ..utils.misc import _freqmul
             self.e = torch.exp(_freqmul(Lh, self.x0))           # the closures' own statement, once
-        if plan.embed is not None:
-            # embedded plan: the operator runs in the zero-padded domain with e ZERO outside the image ('id': a mask of
-            # ones inside).  There the convolution's output is exactly zero, and so are both mixes of zeros and the
-            # Tikhonov term of a zero-padded v: the same argument as opt/pcg.py::_Staged
-            self.e = plan._pad(torch.ones_like(self.x0) if self.e is None else self.e, nb)
+        self.e = plan.grid_beam(self.e, nb)      # embedded plan: e takes the beam's place in the padded domain (psf.py)
         nbytes = _lib.load().pfb_hessparam_work_bytes(plan.handle)
         self._work = torch.empty(nbytes, dtype=torch.uint8, device=self.x0.device)
 
@@ -235,33 +211,16 @@ class ParamHessian:
                 out.copy_(res)
                 res = out
             return _dev.host_like(res, x)
-        xs = xd if plan.embed is None else plan._pad(xd, self.nb)
-        buf = _dev.out_buffer(out, xs, alias=False)
-        with plan.lock:
-            plan._enter_stream()
-            _lib.check(_lib.load().pfb_hessparam_apply(plan.handle, _dev.ptr(self.L), _dev.ptr(self.LH),
-                                                       _dev.ptr(self.e), self.sigmainv, _dev.ptr(xs), _dev.ptr(buf),
-                                                       _dev.ptr(self._work), _dev.stream()))
-        if plan.embed is not None:
-            buf = plan._crop(buf)
-            if out is not None:
-                out.copy_(buf)
-                buf = out
-            else:
-                buf = buf.contiguous()
-        elif out is not None and buf is not out:
-            out.copy_(buf)
-            buf = out
-        return _dev.host_like(buf, x)
+        buf = _dev.out_buffer(out, xd, alias=False)
+        plan._on_grid('pfb_hessparam_apply', xd, buf, lambda xs, os_: (
+            _dev.ptr(self.L), _dev.ptr(self.LH), _dev.ptr(self.e), self.sigmainv, _dev.ptr(xs), _dev.ptr(os_),
+            _dev.ptr(self._work)))
+        return _dev.host_like(_dev.deliver(buf, out), x)
 
     def apply_dots(self, x, out, dots_out):
         """As HessianPsf.apply_dots, the sums out of the second band mix."""
-        plan = self.plan
-        with plan.lock:
-            plan._enter_stream()
-            _lib.check(_lib.load().pfb_hessparam_apply_dots(
-                plan.handle, _dev.ptr(self.L), _dev.ptr(self.LH), _dev.ptr(self.e), self.sigmainv, _dev.ptr(x),
-                _dev.ptr(out), _dev.ptr(x), None, _dev.ptr(dots_out), _dev.ptr(self._work), _dev.stream()))
+        self.plan.run('pfb_hessparam_apply_dots', _dev.ptr(self.L), _dev.ptr(self.LH), _dev.ptr(self.e), self.sigmainv,
+                      _dev.ptr(x), _dev.ptr(out), _dev.ptr(x), None, _dev.ptr(dots_out), _dev.ptr(self._work))
 
 
 def hessian_psf(psfo, x0, sigmainv, df, dhf, v, _nofuse=False):

@@ -117,7 +117,7 @@ class PsfConvPlan(NativePlan):
 
     plan_for() hands the SAME plan to every host thread that presents the same psfhat (the reference's dask threads
     do, pcg.py:346-356), so `lock` is held for the enqueue of an apply and for a whole fused solve, and a caller on a
-    different stream than the previous user first waits for that stream's work (NativePlan._enter_stream).
+    different stream than the previous user first waits for that stream's work (NativePlan.run).
 
     `psf` (keyword, what from_psf passes instead of psfhat): the real PSF cube as a contiguous device tensor of a
     fast-path size; the library transforms it itself, into `psfhat_out` as well when that is given."""
@@ -202,15 +202,58 @@ class PsfConvPlan(NativePlan):
                 break
         return None
 
-    def _pad(self, t, nb):
-        """(nb, nx, ny) -> zero-padded (nb, nx2, ny2) (embedded plans only)."""
+    # ---- the padded domain.  An embedded plan computes on `embed`, a grid larger than the (nx, ny) image.  The image sits
+    # in its corner and everything outside is ZERO: the input, and the beam (ones where the caller has none) of whoever
+    # iterates there.  Outside the image a zero beam makes [beam*]conv([beam*]x) vanish, the operator reduces to sigmainv x
+    # and maps zero to zero, so an iteration that starts from zero-padded arrays (a fused solve's b, x0 and with them
+    # r, y, p; ParamHessian's e and both band mixes) stays exactly zero there and every inner product, step length and
+    # stopping decision equals the un-padded one's.  A single apply needs no beam for that: its output is cropped.
+    @property
+    def grid(self):
+        """The (nx, ny) the native plan computes on: `embed`, or the image's own."""
+        return self.embed or (self.nx, self.ny)
+
+    def to_grid(self, t, nb):
+        """(nb, nx, ny) image cube -> a fresh zero-padded (nb,) + grid copy; t itself (None included) when not embedded."""
+        if t is None or self.embed is None:
+            return t
         z = torch.zeros((nb,) + self.embed, dtype=self.rdtype, device=t.device)
         z[:, :self.nx, :self.ny] = t
         return z
 
-    def _crop(self, t):
-        """The image part of a padded (nb, nx2, ny2) cube, as a view (embedded plans only)."""
-        return t[:, :self.nx, :self.ny]
+    def from_grid(self, t):
+        """The image part of a (nb,) + grid cube, contiguous; t itself when not embedded."""
+        return t if self.embed is None else t[:, :self.nx, :self.ny].contiguous()
+
+    def grid_beam(self, beam, nb):
+        """The beam an iteration on the grid multiplies by: `beam` -- ones where there is none -- zero outside the image;
+        `beam` itself when not embedded."""
+        if beam is None and self.embed is not None:
+            beam = torch.ones((nb, self.nx, self.ny), dtype=self.rdtype, device=self.device)
+        return self.to_grid(beam, nb)
+
+    def _staging(self, nb, stream):
+        """The cached (in, out) pair of (nb,) + grid buffers an embedded apply goes through, per stream (its handle) and
+        host thread like _solve_work.  The margins of `in` are written once (zeros) and never again: a call costs one
+        copy in and one out.  Only _on_grid touches them, inside the plan's critical section."""
+        cache = self.__dict__.setdefault('_pad_cache', {})
+        key = (nb, self.device, stream, threading.get_ident())
+        if key not in cache:
+            cache[key] = (torch.zeros((nb,) + self.embed, dtype=self.rdtype, device=self.device),
+                          torch.empty((nb,) + self.embed, dtype=self.rdtype, device=self.device))
+        return cache[key]
+
+    def _on_grid(self, fn_name, x, out, args):
+        """out = fn_name(x) for contiguous (nb, nx, ny) image cubes: run(fn_name, *args(xs, os)) with xs, os the cubes
+        themselves or, embedded, the staging pair -- filled, used and copied out under `lock`, after the stream
+        dependency, so that no earlier user of the pair can still be reading it."""
+        if self.embed is None:
+            return self.run(fn_name, *args(x, out))
+        with self.lock:
+            xs, os_ = self._staging(x.shape[0], self._enter_stream())
+            xs[:, :self.nx, :self.ny] = x
+            self.run(fn_name, *args(xs, os_))
+            out.copy_(os_[:, :self.nx, :self.ny])
 
     def _solve_work(self, kind, nb):
         """Device scratch of a fused solve (opt/pcg.py) in the layout `kind` ('' the cube solve's, 'bands_', 'param_':
@@ -225,18 +268,23 @@ class PsfConvPlan(NativePlan):
         return cache[key]
 
     @classmethod
-    def from_psf(cls, psf, nx, ny, want_psfhat=False):
+    def from_psf(cls, psf, nx, ny, want_psfhat=False, *, image=None):
         """Build the plan straight from the real PSF cube (nband, nx_psf, ny_psf) | (nx_psf, ny_psf):
         psfhat = r2c(ifftshift(psf)) is produced by the library's own kernels
         (pfb_psfconv_set_psf; gridder.py:712-714) and never leaves the device.  With
-        want_psfhat=True also returns it in the reference's layout."""
+        want_psfhat=True also returns it in the reference's layout.
+        image: the shape of the images the plan is applied to when they are SMALLER than (nx, ny) -- a kernel that was
+        laid out on a fast-path grid (nx, ny | 2 nx, 2 ny) for them; the plan is then embedded in that grid."""
         p = _dev.to_dev(psf)
         if p.ndim == 2:
             p = p[None]
         if p.ndim != 3 or p.dtype not in (torch.float32, torch.float64):
             raise ValueError("psf must be a real (nband, nx_psf, ny_psf) or (nx_psf, ny_psf) array")
         nband, nx_psf, ny_psf = (int(v) for v in p.shape)
+        image = None if image is None or tuple(image) == (nx, ny) else tuple(int(v) for v in image)
         if _embed_grid(int(nx), int(ny), nx_psf, ny_psf, p.dtype) is not None:
+            if image is not None:
+                raise ValueError(f"image {image}: ({nx}, {ny} | {nx_psf}, {ny_psf}) is not a fast-path grid to embed it in")
             # not a fast-path size: transform on the PSF's own grid first, then let the constructor
             # re-grid it onto the fast-path plan (operators/fft.py picks the native producer)
             from .fft import psfhat_from_psf
@@ -246,12 +294,17 @@ class PsfConvPlan(NativePlan):
         ph = torch.empty((nband, nx_psf, ny_psf // 2 + 1), dtype=_dev.CPLX_OF[p.dtype],
                          device=p.device) if want_psfhat else None
         plan = cls(None, nx, ny, ny_psf, psf=p, psfhat_out=ph)
+        if image is not None:
+            if image[0] > plan.nx or image[1] > plan.ny:
+                raise ValueError(f"image {image} does not fit the ({plan.nx}, {plan.ny}) grid")
+            plan.embed, (plan.nx, plan.ny) = (plan.nx, plan.ny), image
         return (plan, ph) if want_psfhat else plan
 
     def apply(self, x, out=None, beam=None, wsum=None, sigmainv=0.0, band0=0,
               dot_with=None, dot_out=None):
         """out = [beam*]conv([beam*]x)[/wsum] + sigmainv*x on bands
-        [band0, band0+nb) where nb = x.shape[0] (x is (nb, nx, ny) or (nx, ny))."""
+        [band0, band0+nb) where nb = x.shape[0] (x is (nb, nx, ny) or (nx, ny)).  Embedded plans take and return
+        images all the same: the padded domain (above) is inside."""
         squeeze = x.ndim == 2
         x3 = x[None] if squeeze else x
         if x3.dtype != self.rdtype or not x3.is_cuda:
@@ -273,33 +326,10 @@ class PsfConvPlan(NativePlan):
             beam = beam.contiguous()
         if dot_with is not None:
             dot_with = dot_with.contiguous()
-        if self.embed is not None:
-            # padded input / output buffers are kept per (band count, host thread): the margins of the input
-            # buffer are written once (zeros) and never touched again, so a call costs one copy in and one out
-            cache = self.__dict__.setdefault('_pad_cache', {})
-            key = (nb, x3.device, threading.get_ident())
-            if key not in cache:
-                cache[key] = (torch.zeros((nb,) + self.embed, dtype=self.rdtype, device=x3.device),
-                              torch.empty((nb,) + self.embed, dtype=self.rdtype, device=x3.device))
-            xs, os_ = cache[key]
-            xs[:, :self.nx, :self.ny] = x3
-            bs = None if beam is None else self._pad(beam, nb)
-            ds = None if dot_with is None else self._pad(dot_with if dot_with.ndim == 3 else dot_with[None], nb)
-            with self.lock:
-                self._enter_stream()
-                _lib.check(self._lib.pfb_psfconv_apply(
-                    self._h, int(band0), int(nb), _dev.ptr(xs), _dev.ptr(bs),
-                    float(wsum) if wsum is not None else 0.0, float(sigmainv), _dev.ptr(os_),
-                    _dev.ptr(ds), _dev.ptr(dot_out), _dev.stream()))
-                out3.copy_(os_[:, :self.nx, :self.ny])
-            return out3[0] if squeeze else out3
-        xs, bs, ds, os_ = x3, beam, dot_with, out3
-        with self.lock:
-            self._enter_stream()
-            _lib.check(self._lib.pfb_psfconv_apply(
-                self._h, int(band0), int(nb), _dev.ptr(xs), _dev.ptr(bs),
-                float(wsum) if wsum is not None else 0.0, float(sigmainv), _dev.ptr(os_),
-                _dev.ptr(ds), _dev.ptr(dot_out), _dev.stream()))
+        bs, ds = self.to_grid(beam, nb), self.to_grid(dot_with, nb)      # embedded: cropped afterwards (the padded domain)
+        self._on_grid('pfb_psfconv_apply', x3, out3, lambda xs, os_: (
+            int(band0), int(nb), _dev.ptr(xs), _dev.ptr(bs), float(wsum) if wsum is not None else 0.0, float(sigmainv),
+            _dev.ptr(os_), _dev.ptr(ds), _dev.ptr(dot_out)))
         return out3[0] if squeeze else out3
 
     def set_profiling(self, on):
@@ -346,16 +376,25 @@ def clear_plan_cache():
 
 
 # ---------------------------------------------------------------- reference API
-def _run(psfhat, lastsize, x, xout, beam=None, wsum=None, sigmainv=0.0):
+def _run(psfhat, lastsize, x, xout, beam=None, wsum=None, sigmainv=0.0, fresh=False):
+    """Stage x (and the beam, which must have x's shape), apply the cached plan, deliver: into and as `xout` -- or,
+    fresh=True (operators/hessian.py), as a NEW array that `xout` receives as well."""
     xd = _dev.to_dev(x)
     nx, ny = xd.shape[-2:]
     plan = plan_for(psfhat, nx, ny, lastsize)
     if xd.dtype != plan.rdtype:
         raise TypeError(f"x is {xd.dtype} but psfhat is {psfhat.dtype}")
     bd = _dev.to_dev(beam, plan.rdtype) if beam is not None else None
-    buf = _dev.out_buffer(xout, xd, alias=False)          # never overwrite x: stage when xout aliases it
+    if bd is not None and tuple(bd.shape) != tuple(xd.shape):
+        raise ValueError('Beam has incorrect shape')
+    # never overwrite x: stage when xout aliases it
+    buf = torch.empty_like(xd) if fresh else _dev.out_buffer(xout, xd, alias=False)
     plan.apply(xd, out=buf, beam=bd, wsum=wsum, sigmainv=sigmainv)
-    return _dev.deliver(buf, xout, like=x)
+    if not fresh:
+        return _dev.deliver(buf, xout, like=x)
+    if xout is not None:
+        _dev.deliver(buf, xout)
+    return _dev.host_like(buf, x)
 
 
 def psf_convolve_slice(xpad, xhat, xout, psfhat, lastsize, x, nthreads=1):

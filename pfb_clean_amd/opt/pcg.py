@@ -120,9 +120,11 @@ def _backtrack_mode(backtrack):
 
 
 class _Staged:
-    """What pcg_fused and pcg_fused_bands share around the native call: the checks on b, the contiguous copies, the
-    embedded plan's padding, the work buffer (kept on the plan, PsfConvPlan._solve_work), the call itself and the way
-    back (crop).  `kind`: the work buffer's layout for a HessianPsf, '' (the cube solve's) or 'bands_'."""
+    """What pcg_fused and pcg_fused_bands share around the native call: the checks on b, the contiguous copies on the
+    plan's grid (an embedded plan solves in its padded domain, operators/psf.py: zero-padded b and x0, a beam that is
+    zero outside the image; a ParamHessian's e is one already), the work buffer (kept on the plan,
+    PsfConvPlan._solve_work), the call itself and the way back.  `kind`: the work buffer's layout for a HessianPsf, ''
+    (the cube solve's) or 'bands_'."""
 
     def __init__(self, A, b3, x0, return_resid, kind=''):
         self.plan = plan = A.plan
@@ -136,16 +138,8 @@ class _Staged:
             raise TypeError(f"b is {b3.dtype}, operator is {plan.rdtype}")
         x = torch.zeros_like(b3) if x0 is None else x0.contiguous().clone()
         param = isinstance(A, ParamHessian)
-        beam = A.e if param else A.beam
-        if plan.embed is not None:
-            # Embedded plan (arbitrary size on the power-of-two kernels, operators/psf.py): solve in the
-            # zero-padded domain with a beam that is ZERO outside the image.  There A' x' = sigmainv x',
-            # b' = 0 and x0' = 0, so r, y, p stay exactly zero outside and every inner product, step
-            # length and stopping decision equals the un-padded solve's.  A ParamHessian's e is padded already.
-            b3, x = plan._pad(b3, nb), plan._pad(x, nb)
-            if not param:
-                beam = plan._pad(torch.ones((nb, plan.nx, plan.ny), dtype=plan.rdtype, device=b3.device)
-                                 if beam is None else beam, nb)
+        b3, x = plan.to_grid(b3, nb), plan.to_grid(x, nb)
+        beam = A.e if param else plan.grid_beam(A.beam, nb)
         self.b, self.x, self.beam = b3, x, beam
         self.r = torch.empty_like(b3) if return_resid else None
         self.work = plan._solve_work('param_' if param else kind, nb)
@@ -157,19 +151,12 @@ class _Staged:
             self.args = (A.band0, nb, ptr(b3), ptr(x), ptr(self.r), ptr(beam),
                          A.wsum if A.wsum is not None else 0.0, A.sigmainv)
 
-    def solve(self, fn, mdiv, tol, maxit, minit, backtrack, *tail):
-        """fn(plan, *args, mdiv .. backtrack, work, *tail, stream), one solve at a time per plan (a plan is single-owner,
-        include/pfb_hip.h).  Returns (x, r|None) in the caller's domain."""
-        plan = self.plan
-        with plan.lock:
-            plan._enter_stream()
-            _lib.check(fn(plan.handle, *self.args, float(mdiv), float(tol), int(maxit), int(minit),
-                          _backtrack_mode(backtrack), _dev.ptr(self.work), *tail, _dev.stream()))
-        x, r = self.x, self.r
-        if plan.embed is not None:
-            x = plan._crop(x).contiguous()
-            r = None if r is None else plan._crop(r).contiguous()
-        return x, r
+    def solve(self, fn_name, mdiv, tol, maxit, minit, backtrack, *tail):
+        """fn_name(plan, *args, mdiv .. backtrack, work, *tail, stream), one solve at a time per plan (a plan is
+        single-owner, include/pfb_hip.h).  Returns (x, r|None) in the caller's domain."""
+        self.plan.run(fn_name, *self.args, float(mdiv), float(tol), int(maxit), int(minit), _backtrack_mode(backtrack),
+                      _dev.ptr(self.work), *tail)
+        return self.plan.from_grid(self.x), None if self.r is None else self.plan.from_grid(self.r)
 
 
 def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack=True,
@@ -178,7 +165,6 @@ def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack
     (x, r|None, PcgResult).  distributed=True: the bands of this call are one rank's
     shard of a cube solve; every inner product is all-reduced over `group`
     (pfb_clean_amd.dist.AllReduceHook, RCCL)."""
-    lib = _lib.load()
     param = isinstance(A, ParamHessian)
     if param and distributed:
         raise ValueError("a ParamHessian couples every band: it cannot be solved on a band shard")
@@ -207,9 +193,9 @@ def pcg_fused(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, backtrack
                 return 1
         cb = _lib.ALLREDUCE_FN(_hook)
     if param:                        # no hook argument: a band shard cannot apply the mix
-        x, r = s.solve(lib.pfb_pcg_solve_param, mdiv, tol, maxit, minit, backtrack, C.byref(res))
+        x, r = s.solve('pfb_pcg_solve_param', mdiv, tol, maxit, minit, backtrack, C.byref(res))
     else:
-        x, r = s.solve(lib.pfb_pcg_solve, mdiv, tol, maxit, minit, backtrack, cb, cb_ctx, C.byref(res))
+        x, r = s.solve('pfb_pcg_solve', mdiv, tol, maxit, minit, backtrack, cb, cb_ctx, C.byref(res))
     if distributed:                  # bench.py reports which exchange ran and what the hook costs the host
         res.exchange = 'rccl-native' if native is not None else 'torch-hook'
         res.hook_calls, res.hook_host_s = (0, 0.0) if native is not None else (allreduce.calls, allreduce.host_s)
@@ -227,7 +213,7 @@ def pcg_fused_bands(A, b, x0=None, mdiv=0.0, tol=1e-5, maxit=500, minit=100, bac
     PFB_PCG_EXACT_BACKTRACK=1) has no batched form: the library raises PfbHipError (unsupported)."""
     s = _Staged(A, b, x0, return_resid, kind='bands_')
     res = (_lib.PcgResult * s.nb)()
-    x, r = s.solve(_lib.load().pfb_pcg_solve_bands, mdiv, tol, maxit, minit, backtrack, res)
+    x, r = s.solve('pfb_pcg_solve_bands', mdiv, tol, maxit, minit, backtrack, res)
     return x, r, list(res)
 
 

@@ -10,7 +10,6 @@ The three pfb/utils/misc.py helpers that sit on the hot path.
     fitcleanbeam                          misc.py:506-584   (clean beam, utils/beamfit.py)
 """
 import math
-import threading
 
 import numpy as np
 import torch
@@ -288,34 +287,21 @@ def _engine_grid(nx, ny, rdtype):
 
 
 class _BeamPlan:
-    """A PsfConvPlan holding restoring-beam kernels for (nx, ny) images, with the zero-padded staging buffers its
-    image size needs.  `shared` (model branch of convolve2gaussres): the plan has one band that serves every band of
-    the cube; otherwise band b of the cube meets kernel b."""
+    """A PsfConvPlan holding restoring-beam kernels for (nx, ny) images -- an embedded one where the engine grid is
+    larger than the image.  `shared` (model branch of convolve2gaussres): the plan has one band that serves every band
+    of the cube; otherwise band b of the cube meets kernel b."""
 
-    def __init__(self, plan, nx, ny, shared):
-        self.plan, self.nx, self.ny, self.shared = plan, nx, ny, shared
-        self._stage = {}
+    def __init__(self, plan, shared):
+        self.plan, self.shared = plan, shared
 
     def apply(self, x):
         """x: (nb, nx, ny) contiguous device tensor of the plan's dtype -> new tensor, x untouched."""
-        plan, nb = self.plan, x.shape[0]
         out = torch.empty_like(x)
-        padded = (plan.nx, plan.ny) != (self.nx, self.ny)
-        n1 = 1 if self.shared else nb
-        if padded:
-            key = (n1, x.device, threading.get_ident())
-            if key not in self._stage:       # margins written once (zeros), never touched again
-                self._stage[key] = (torch.zeros((n1, plan.nx, plan.ny), dtype=x.dtype, device=x.device),
-                                    torch.empty((n1, plan.nx, plan.ny), dtype=x.dtype, device=x.device))
-            xs, os_ = self._stage[key]
-        for b in (range(nb) if self.shared else (0,)):
-            xb = x[b:b + n1]
-            if padded:
-                xs[:, :self.nx, :self.ny] = xb
-                plan.apply(xs, out=os_)
-                out[b:b + n1] = os_[:, :self.nx, :self.ny]
-            else:
-                plan.apply(xb, out=out[b:b + n1])
+        if self.shared:
+            for b in range(x.shape[0]):
+                self.plan.apply(x[b:b + 1], out=out[b:b + 1])
+        else:
+            self.plan.apply(x, out=out)
         return out
 
 
@@ -348,7 +334,7 @@ def _model_plan(xd, yd, gausspars, nx, ny, rdtype, pfrac, norm_kernel):
     _lib.check(_lib.load().pfb_gauss_kernel_grid(_dev.code(rdtype), _dev.ptr(xd), _dev.ptr(yd), nx, ny, padding[1][0],
                                                  padding[2][0], P, Q, _dev.ptr(pars), _dev.ptr(norm), len(gausspars),
                                                  1, P2, Q2, _dev.ptr(k2), _dev.stream()))
-    return PsfConvPlan.from_psf(k2, pnx, pny)
+    return PsfConvPlan.from_psf(k2, pnx, pny, image=(nx, ny))
 
 
 def _ratio_plan(xd, yd, gaussparf, gausspari, nx, ny, rdtype, pfrac, norm_kernel):
@@ -381,13 +367,13 @@ def _ratio_plan(xd, yd, gaussparf, gausspari, nx, ny, rdtype, pfrac, norm_kernel
     k2 = torch.empty((nband, P2, Q2), dtype=rdtype, device=xd.device)
     _lib.check(lib.pfb_kernel_gather(_dev.code(rdtype), _dev.ptr(kern), nband, nx, ny, P, Q, 0, 0, P2, Q2,
                                      _dev.ptr(k2), _dev.stream()))
-    return PsfConvPlan.from_psf(k2, pnx, pny)
+    return PsfConvPlan.from_psf(k2, pnx, pny, image=(nx, ny))
 
 
 def _beam_plan(xx, yy, coord_key, gaussparf, gausspari, nx, ny, rdtype, pfrac, norm_kernel, per_band=False):
-    """Cached _BeamPlan.  gaussparf: one parameter triple -- or, with per_band, one per band (restore_image's model
-    step); gausspari: None (model branch) or one triple per band (ratio branch).  xx, yy may be callables that
-    build the coordinates: they are only needed on a miss."""
+    """Cached _BeamPlan.  gaussparf: one parameter triple -- or, with per_band, one per band
+    (restore_image's model step); gausspari: None (model branch) or one triple per band (ratio branch).  xx, yy may be
+    callables that build the coordinates: they are only needed on a miss."""
     tup = lambda g: tuple(float(v) for v in g)
     gpf = tuple(tup(g) for g in gaussparf) if per_band else tup(gaussparf)
     gpi = None if gausspari is None else tuple(tup(g) for g in gausspari)
@@ -404,7 +390,7 @@ def _beam_plan(xx, yy, coord_key, gaussparf, gausspari, nx, ny, rdtype, pfrac, n
             plan = _model_plan(xd, yd, gpf if per_band else [gpf], nx, ny, rdtype, pfrac, norm_kernel)
         # device coordinate tensors are kept so that their address cannot be re-used by others while the entry lives
         keep = [a for a in (xs, ys) if isinstance(a, torch.Tensor)]
-        return _BeamPlan(plan, nx, ny, shared=gpi is None and not per_band), keep
+        return _BeamPlan(plan, shared=gpi is None and not per_band), keep
     return _beam_cache.get(key, make)[0]
 
 

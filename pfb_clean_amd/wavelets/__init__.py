@@ -18,7 +18,7 @@ that asks for the same one; numpy arguments are staged through the GPU, torch-RO
 """
 import numpy as np
 
-from .. import _lib, _dev
+from .. import _dev
 from .._plan import PlanCache, PsiPlan
 from .filters import filter_bank, dwt_max_level  # noqa: F401
 
@@ -60,8 +60,7 @@ _plans = PlanCache(32)                           # a handful of shapes is the us
 
 def _single_basis_plan(nx, ny, f_lo, f_hi, analysis, nlevel, dtype):
     """Shared PsiPlan for ONE band and ONE basis whose four filters follow from the pair handed in (orthogonal banks:
-    the synthesis pair is the analysis pair reversed, psi.py:38-41).  Enqueue on it under its lock, after
-    _enter_stream()."""
+    the synthesis pair is the analysis pair reversed, psi.py:38-41).  Enqueue on it with run()."""
     lo = np.ascontiguousarray(f_lo, dtype=np.float64)
     hi = np.ascontiguousarray(f_hi, dtype=np.float64)
     F = lo.size
@@ -104,9 +103,7 @@ def dwt2d(image, coeffs, cbuff, cbuffT, ix, iy, sx, sy, dec_lo, dec_hi, nlevel):
     xd = _dev.to_dev(image)
     plan = _single_basis_plan(nx, ny, dec_lo, dec_hi, True, nlevel, xd.dtype)
     cd = _dev.to_dev(coeffs, xd.dtype)          # coeffs itself when it is a contiguous GPU tensor of the image's dtype
-    with plan.lock:
-        plan._enter_stream()
-        _lib.check(plan._lib.pfb_psi_dot(plan.handle, _dev.ptr(xd), _dev.ptr(cd), _dev.stream()))
+    plan.run('pfb_psi_dot', _dev.ptr(xd), _dev.ptr(cd))
     return _dev.deliver(cd, coeffs)
 
 
@@ -121,9 +118,7 @@ def idwt2d(coeffs, image, alpha, cbuff, cbuffT, ix, iy, sx, sy, spx, spy, rec_lo
     cd = _dev.to_dev(coeffs)
     plan = _single_basis_plan(nx, ny, rec_lo, rec_hi, False, nlevel, cd.dtype)
     xd = _dev.out_buffer(image, cd, shape=(nx, ny))
-    with plan.lock:
-        plan._enter_stream()
-        _lib.check(plan._lib.pfb_psi_hdot(plan.handle, _dev.ptr(cd), _dev.ptr(xd), _dev.stream()))
+    plan.run('pfb_psi_hdot', _dev.ptr(cd), _dev.ptr(xd))
     return _dev.deliver(xd, image)
 
 

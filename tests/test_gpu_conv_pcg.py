@@ -745,6 +745,66 @@ def test_one_plan_shared_by_concurrent_host_threads(amd, golden):
     amd.psf.clear_plan_cache()
 
 
+@pmp('op', ['apply', 'param_hessian', 'convolve2gaussres'])
+def test_embedded_plan_on_two_streams_of_one_host_thread(amd, op):
+    """An embedded plan goes through padded staging buffers that live on the plan.  ONE host thread that uses the plan
+    on stream A and at once on stream B must not overwrite on B what A's kernels have yet to read: the buffers are per
+    stream and are filled inside the plan's critical section, behind the stream dependency.  A is kept busy with
+    unrelated work, the operation is enqueued on A for input a and straight away on B for input b, no host
+    synchronisation in between; both results must equal the one-stream, synchronised ones bitwise.  fp64:
+    2 x 100 x 120 embedded in 128 x 128 (plan.apply), 2 x 64 x 64 with a 128 x 128 PSF grid (ParamHessian), and
+    2 x 64 x 64 on the 64 x 128 engine grid of the restoring beam (model branch: one staging pair serves band after band)."""
+    dev = torch.device('cuda')
+    gen = torch.Generator(device=dev).manual_seed(11)
+
+    def rand(*shape, dtype=torch.float64):
+        return torch.randn(shape, dtype=dtype, device=dev, generator=gen)
+    amd.misc.clear_beam_cache()
+    if op == 'apply':
+        nb, nx, ny = 2, 100, 120
+        plan = amd.psf.PsfConvPlan(rand(nb, 2 * nx, ny + 1, dtype=torch.complex128), nx, ny, 2 * ny)
+
+        def f(x):
+            return plan.apply(x, sigmainv=0.5)
+    elif op == 'param_hessian':
+        nb, nx, ny = 2, 64, 64
+        _, _, dfunc, dhfunc = amd.misc.setup_parametrisation('exp', sigma=0.8, freq=np.linspace(1e9, 2e9, nb), lscale=0.5)
+        f = amd.hessian.ParamHessian(rand(nb, 128, 65, dtype=torch.complex128), nx, ny, 128, 0.1 * rand(nb, nx, ny), 0.5,
+                                     dfunc, dhfunc)
+        assert f.fused
+        plan = f.plan
+    else:
+        nb, nx, ny = 2, 64, 64
+        xx, yy = torch.meshgrid(torch.arange(-nx / 2, nx / 2, dtype=torch.float64, device=dev),
+                                torch.arange(-ny / 2, ny / 2, dtype=torch.float64, device=dev), indexing='ij')
+
+        def f(x):
+            return amd.misc.convolve2gaussres(x, xx, yy, (40.0, 24.0, 33.0), 1)
+    a, b = rand(nb, nx, ny), rand(nb, nx, ny)
+    ya = f(a).clone()
+    torch.cuda.synchronize()
+    yb = f(b).clone()
+    torch.cuda.synchronize()
+    if op == 'convolve2gaussres':
+        plan = next(reversed(amd.misc._beam_cache._entries.values()))[0].plan
+    assert plan.embed == {'apply': (128, 128), 'param_hessian': (64, 128), 'convolve2gaussres': (64, 128)}[op]
+    m = rand(4096, 4096, dtype=torch.float32)
+    m @ m                                           # the first product's one-off set-up stays out of the overlap
+    A, B = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(A):
+        for _ in range(8):                          # a few milliseconds of unrelated work ahead of the operation
+            m @ m
+        ga = f(a)
+    with torch.cuda.stream(B):
+        gb = f(b)
+    A.synchronize()
+    B.synchronize()
+    assert torch.equal(ga, ya), "stream A computed on what stream B staged"
+    assert torch.equal(gb, yb), "stream B computed on what stream A staged after it"
+    amd.misc.clear_beam_cache()
+
+
 @pmp('n,nb', [(512, 2), (1024, 1)])
 def test_fp32_predictive_backtracking_matches_reference_loop(amd, n, nb):
     """fp32 parity of the default line search: backtrack=True runs the PREDICTIVE search (three fused

@@ -850,14 +850,12 @@ def native_solve(amd, plan, kind, rdt, b, beam, sig, bt, k=0):
     work = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
     assert work.data_ptr() % 256 == 0
     res = (amd._lib.PcgResult * nb)()
-    head = (plan.handle, 0, nb, bb.ptr, bx.ptr, br.ptr, None if bbeam is None else bbeam.ptr, 0.0, sig, sig, 0.0, 8, 8, bt,
+    head = (0, nb, bb.ptr, bx.ptr, br.ptr, None if bbeam is None else bbeam.ptr, 0.0, sig, sig, 0.0, 8, 8, bt,
             work.data_ptr())
-    with plan.lock:
-        plan._enter_stream()
-        if bands:
-            ok(amd, amd.lib.pfb_pcg_solve_bands(*head, res, amd.dev.stream()))
-        else:
-            ok(amd, amd.lib.pfb_pcg_solve(*head, amd._lib.ALLREDUCE_FN(0), None, C.byref(res[0]), amd.dev.stream()))
+    if bands:
+        plan.run('pfb_pcg_solve_bands', *head, res)
+    else:
+        plan.run('pfb_pcg_solve', *head, amd._lib.ALLREDUCE_FN(0), None, C.byref(res[0]))
     check_buffers(written=[bx, br], read=[bb] + ([bbeam] if bbeam is not None else []))
     return bx.numpy(), br.numpy(), [(r.status, r.iters, r.matvecs, r.backtracks) for r in res[:nb if bands else 1]]
 

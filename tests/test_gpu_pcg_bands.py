@@ -91,9 +91,7 @@ def test_conv_dots_per_band(amd, case, with_beam):
     x = torch.randn((nb, nx, ny), dtype=rtype, device=dev, generator=g)
     w = torch.randn((nb, nx, ny), dtype=rtype, device=dev, generator=g)
     beam = (0.5 + torch.rand((nb, nx, ny), dtype=rtype, device=dev, generator=g)) if with_beam else None
-    if plan.embed is not None:
-        x, w = plan._pad(x, nb), plan._pad(w, nb)
-        beam = plan._pad(torch.ones_like(w[:, :nx, :ny]) if beam is None else beam, nb)
+    x, w, beam = plan.to_grid(x, nb), plan.to_grid(w, nb), plan.grid_beam(beam, nb)      # themselves unless embedded
     for w2 in (True, False):
         per, cube, o, same = _dots_bands(amd, plan, x, w, beam, nb, w2)
         xn, wn = x.cpu().numpy().astype(np.float64), w.cpu().numpy().astype(np.float64)
@@ -348,18 +346,12 @@ def _guarded_solve(amd, plan, solve, nb, bt, b, L, slack):
     x, LH = torch.zeros_like(b), L.T.contiguous()
     res = (_lib.PcgResult * nb)()
     tail = (1.0, 1.0, 0.0, 3, 3, bt, work)           # sigmainv, mdiv, tol, maxit, minit, backtrack, work
-    with plan.lock:
-        plan._enter_stream()
-        if solve == 'cube':
-            rc = lib.pfb_pcg_solve(plan.handle, 0, nb, _dev.ptr(b), _dev.ptr(x), None, None, 0.0, *tail,
-                                   _lib.ALLREDUCE_FN(0), None, res, _dev.stream())
-        elif solve == 'bands':
-            rc = lib.pfb_pcg_solve_bands(plan.handle, 0, nb, _dev.ptr(b), _dev.ptr(x), None, None, 0.0, *tail, res,
-                                         _dev.stream())
-        else:
-            rc = lib.pfb_pcg_solve_param(plan.handle, nb, _dev.ptr(L), _dev.ptr(LH), None, _dev.ptr(b),
-                                         _dev.ptr(x), None, *tail, res, _dev.stream())
-    _lib.check(rc)
+    if solve == 'cube':
+        plan.run('pfb_pcg_solve', 0, nb, _dev.ptr(b), _dev.ptr(x), None, None, 0.0, *tail, _lib.ALLREDUCE_FN(0), None, res)
+    elif solve == 'bands':
+        plan.run('pfb_pcg_solve_bands', 0, nb, _dev.ptr(b), _dev.ptr(x), None, None, 0.0, *tail, res)
+    else:
+        plan.run('pfb_pcg_solve_param', nb, _dev.ptr(L), _dev.ptr(LH), None, _dev.ptr(b), _dev.ptr(x), None, *tail, res)
     torch.cuda.synchronize()
     nres = nb if solve == 'bands' else 1
     fields = [tuple(getattr(r, f) for f, _ in _lib.PcgResult._fields_) for r in res[:nres]]
