@@ -532,6 +532,55 @@ int pfb_comps_interp(int dtype, const double* image, int nxi, int nyi, int npad_
                      int nx_pad, const double* yin, int ny_pad, const double* xo, int nxo, const double* yo, int nyo,
                      void* out, void* stream);
 
+/* ------------------------------------------------------------------ spectral index
+ * What pfb/utils/spi.py:18-70 (fit_spi) does on image-sized arrays, and the per-component fit it hands to
+ * fit_spi_components: the model m_b = I0 B_b x_b^alpha, x_b = freqs_b / ref_freq, fitted to the data d_b with band
+ * weights w_b by Gauss-Newton from alpha = -0.7, I0 = d[ref]:
+ *   j1_b = B_b exp(alpha ln x_b), j0_b = I0 j1_b ln x_b, r_b = d_b - I0 j1_b,
+ *   h00 = sum w j0^2, h01 = sum w j0 j1, h11 = sum w j1^2, g0 = sum w j0 r, g1 = sum w j1 r, det = h00 h11 - h01^2,
+ *   alpha += (h11 g0 - h01 g1) / det, I0 += (-h01 g0 + h00 g1) / det, eps = max(|d alpha|, |d I0|),
+ * while eps > tol and fewer than maxiter steps were taken (eps starts at 1).  The errors are taken at the returned
+ * parameters: alpha_err = sqrt(h11 / det chi2 / dof), I0_err = sqrt(h00 / det chi2 / dof), chi2 = sum w r^2,
+ * dof = max(nband - 2, 1).  A det that is 0 or not finite, in a step or at the end, gives NaN in all four outputs of
+ * that component only.  A component that takes maxiter steps returns its last iterate and is counted in *notconv.
+ * All arithmetic is fp64 whatever the image dtype, the band sums run in ascending order.
+ *
+ * The host keeps what is tiny: ln x_b and w_b (HOST arrays of nband doubles, copied into the kernel arguments at the
+ * call) and ref = argmin |freqs - ref_freq|.  Two numbers cross to the host: the component count between pfb_spi_mask
+ * and pfb_comps_compact (it sizes Ix / Iy and decides fit_spi's ValueError), and *notconv after the fit (it decides the
+ * warning).  Nothing is allocated, there is no plan and no global state; asynchronous on `stream`.  nband <= 64, else
+ * PFB_ERR_UNSUPPORTED.
+ *
+ * `work` is device scratch of pfb_spi_work_bytes(npix) bytes, 8-byte aligned.  It BEGINS with the layout of
+ * pfb_comps_mask -- pfb_comps_work_bytes(npix) bytes: the bit mask, the scanned per-workgroup counts and, in the last 8
+ * of them, the component count as an int64 -- so that pfb_comps_compact(npix, ny, work, Ix, Iy) yields the components
+ * in np.argwhere's order.  Behind it: the partial maxima of the pass and, in the LAST 8 bytes of `work`, image.max()
+ * after the beam cut as a double, NaN-propagating (spi.py:39; read only to word the ValueError). */
+
+/* Bytes of `work` for cubes of npix pixels per plane; 0 when npix is out of range. */
+size_t pfb_spi_work_bytes(size_t npix);
+
+/* spi.py:29-35: one pass over image and beam, both (nband, npix) of `dtype`.  Per value c = beam > pb_min ? image : 0 (a
+ * NaN beam fails the comparison); a pixel is set iff every band's c > threshold (a NaN c fails, as np.amin propagates
+ * it).  The comparisons are made on the exact fp64 values of the inputs.  16-byte loads; planes that do not start on a
+ * 16-byte boundary (odd npix in fp32) are read from their first aligned vector on, with a peel of up to 3 pixels. */
+int pfb_spi_mask(int dtype, const void* image, const void* beam, int nband, size_t npix, double pb_min, double threshold,
+                 void* work, void* stream);
+
+/* spi.py:40-68: the fit of component c at pixel q = Ix[c] * ny + Iy[c], one component per lane.  Its data are the cut
+ * values c_b of pfb_spi_mask, its beam values the raw beam[b, q].  maps: (4, npix) of `dtype` -- alpha, alpha_err, I0,
+ * I0_err -- written at the components only (the caller fills it with NaN first).  The 2 nband inputs of a component
+ * are re-read on every step.  ncomps <= npix; notconv: one device int64, cleared and then counted into. */
+int pfb_spi_fit(int dtype, const void* image, const void* beam, int nband, size_t npix, int ny, const long long* Ix,
+                const long long* Iy, long long ncomps, const double* lnx, const double* w, int ref, double pb_min,
+                double tol, int maxiter, void* maps, long long* notconv, void* stream);
+
+/* The same fit of a dense component list.  data: (ncomps, nband) device doubles; beam: the same shape, or NULL for 1;
+ * alphai, I0i: (ncomps) device doubles that replace the starting values, or NULL; out: (4, ncomps) device doubles. */
+int pfb_spi_fit_components(const double* data, const double* beam, int nband, long long ncomps, const double* lnx,
+                           const double* w, int ref, const double* alphai, const double* I0i, double tol, int maxiter,
+                           double* out, long long* notconv, void* stream);
+
 /* ----------------------------------------------------------------------- clean beam
  * What pfb/utils/misc.py:506-584 (psf_errorsq, fitcleanbeam) do on image-sized arrays.  The host keeps the optimiser
  * (scipy's fmin_l_bfgs_b, misc.py:577-581) and calls pfb_beamfit_objective from its callback.  All fit arithmetic is

@@ -115,6 +115,10 @@ SIGNATURES = {
     'pfb_comps_fit': (_i, [_i, _vp, _i, _sz, _i, _vp, _vp, C.c_longlong, _vp, _i, _vp, _vp]),
     'pfb_comps_eval': (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp]),
     'pfb_comps_interp': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    'pfb_spi_work_bytes': (_sz, [_sz]),
+    'pfb_spi_mask': (_i, [_i, _vp, _vp, _i, _sz, _d, _d, _vp, _vp]),
+    'pfb_spi_fit': (_i, [_i, _vp, _vp, _i, _sz, _i, _vp, _vp, C.c_longlong, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    'pfb_spi_fit_components': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _i, _vp, _vp, _d, _i, _vp, _vp, _vp]),
     'pfb_beamfit_work_bytes': (_sz, [_i, _sz]),
     'pfb_beamfit_max': (_i, [_i, _vp, _i, _sz, _vp, _vp]),
     'pfb_beamfit_lobe': (_i, [_i, _vp, _i, _i, _i, _d, _d, _vp, _vp]),
