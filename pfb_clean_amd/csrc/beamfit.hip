@@ -43,7 +43,7 @@ __device__ __forceinline__ T neg_inf() { return -std::numeric_limits<T>::infinit
 
 // grid (G, nband).  A plane that starts a elements past a 16-byte boundary is read as `head` = (V - a) mod V single
 // elements, 16-byte vectors from there, and the rest of the plane (fewer than V elements) singly: the peel of
-// k_comps_mask_peel, which here needs no shifting because a maximum does not care where an element sits.
+// load_own (pixmask.hpp), which here needs no shifting because a maximum does not care where an element sits.
 template <typename T>
 __global__ void __launch_bounds__(BF_BLOCK)
 k_beamfit_max(const T* __restrict__ img, size_t npix, size_t nwords, double* __restrict__ part,

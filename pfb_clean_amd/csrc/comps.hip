@@ -1,9 +1,9 @@
 // comps.hip -- the component model: what pfb/utils/misc.py:1084-1313 (fit_image_cube, eval_coeffs_to_cube,
 // eval_coeffs_to_slice) do on image-sized arrays.  The design matrix, its LU factors, the basis values and the
 // coordinate arrays are tiny and come from the host (utils/comps.py); these kernels do the rest:
-//   k_comps_mask     one pass over the (nplane, npix) cube: np.any over the planes as a bit mask (one 64-bit word per
-//                    64 pixels) and the number of set bits per workgroup (k_comps_mask_peel: planes off 16 bytes)
-//   k_comps_scan     exclusive scan of the workgroup counts, the total behind them (one workgroup)
+//   k_pixmask        (pixmask.hpp, with the rule AnyNonzero) one pass over the (nplane, npix) cube: np.any over the
+//                    planes as a bit mask (one 64-bit word per 64 pixels) and the number of set bits per workgroup
+//   k_count_scan     (pixmask.hpp) exclusive scan of the workgroup counts, the total behind them (one workgroup)
 //   k_comps_compact  Ix, Iy in row-major order (np.where) from the mask, the scanned offsets and a popcount
 //   k_comps_fit      one component per lane: gather, rhs = (Xfit^T diag(w)) beta, LU substitution, all fp64
 //   k_comps_eval     scatter of sum_p E[plane][p] coeffs[p][c] to (Ix[c], Iy[c])
@@ -12,166 +12,24 @@
 // No FMA contraction in this file: the interpolation must take scipy's weights on grid-aligned points (a distance of
 // exactly 0 or 1 returns the corner value itself), and the dot products round like numpy's multiply-then-add.
 #pragma clang fp contract(off)
-#include "comps_layout.hpp"
+#include "pixmask.hpp"
 
 namespace pfb {
 
-constexpr int CP_SCAN_BLOCK = 256;
 constexpr int CP_FIT_BLOCK = 64;
 constexpr int CP_MAX_ROWS = 64;
 constexpr int CP_MAX_PARAMS = 32;
 
-// Workgroup g owns mask words [64 g, 64 g + 64), wave w of it the 16 words from 64 g + 16 w.  A lane holds V consecutive
-// pixels (V = 16 bytes of T), so one iteration of a wave covers V words.  A pixel is set iff any plane value != 0: NaN
-// counts, -0.0 does not.  This form needs every plane on a 16-byte boundary (then npix % V == 0 and no vector
-// straddles npix); k_comps_mask_peel takes the rest.  counts[g] = set bits of the workgroup's words.
-template <typename T, int V>
-__global__ void __launch_bounds__(CP_BLOCK)
-k_comps_mask(const T* __restrict__ img, int nplane, size_t npix, size_t nwords, u64* __restrict__ mask,
-             i64* __restrict__ counts) {
-    __shared__ int cnt[CP_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t w0 = (size_t)blockIdx.x * CP_WORDS + (size_t)wave * CP_WAVE_WORDS;
-    int c = 0;
-#pragma unroll
-    for (int it = 0; it < CP_WAVE_WORDS / V; ++it) {
-        const size_t wbase = w0 + (size_t)it * V;
-        const size_t pix = wbase * 64 + (size_t)lane * V;
-        bool flag[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) flag[k] = false;
-        if (pix < npix) {
-#pragma unroll 8
-            for (int p = 0; p < nplane; ++p) {
-                const Pack<T, V> v = ld_nt<T, V>(img + (size_t)p * npix, pix / V);
-#pragma unroll
-                for (int k = 0; k < V; ++k) flag[k] |= (v.e[k] != (T)0);
-            }
-        }
-        u64 b[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            b[k] = __ballot(flag[k]);
-            c += __popcll(b[k]);
-        }
-        if (lane < V && wbase + lane < nwords) mask[wbase + lane] = mask_word<V>(b, lane);
-    }
-    if (lane == 0) cnt[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < CP_WAVES; ++w) s += cnt[w];
-        counts[blockIdx.x] = s;
-    }
-}
+// The mask rule of np.any: a pixel is set iff any plane value != 0, compared in T: NaN counts, -0.0 does not.  The
+// aligned form streams with a wave's iterations unrolled and the planes by 8.
+struct AnyNonzero {
+    static constexpr int NCUBE = 1, PLANE_UNROLL = 8;
+    static constexpr bool START = false, HAS_MAX = false, UNROLL_ITS = true;
+    template <typename T> __device__ __forceinline__ T value(T e, T) const { return e; }
+    template <typename T> __device__ __forceinline__ bool update(bool flag, T x) const { return flag | (x != (T)0); }
+};
 
-// The same for planes that do not all start on a 16-byte boundary (odd npix in fp32, say).  Plane p starts a_p
-// elements past a boundary, so its aligned vectors begin at pixel h_p = (V - a_p) mod V, its head: a lane then loads the
-// vector h_p pixels AFTER its own V pixels, and the flags of the planes of one head h form the iteration's 64 V-bit
-// mask shifted up by h bits.  The h pixels that the shift leaves open at the bottom are read one per lane; the h bits
-// pushed out at the top belong to the next iteration, which reads them as ITS bottom.  A vector that would straddle
-// npix is read element by element.
-template <typename T>
-__global__ void __launch_bounds__(CP_BLOCK)
-k_comps_mask_peel(const T* __restrict__ img, int nplane, size_t npix, size_t nwords, u64* __restrict__ mask,
-                  i64* __restrict__ counts) {
-    constexpr int V = V16<T>::N;
-    __shared__ int cnt[CP_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t w0 = (size_t)blockIdx.x * CP_WORDS + (size_t)wave * CP_WAVE_WORDS;
-    const unsigned a0 = (unsigned)((reinterpret_cast<uintptr_t>(img) / sizeof(T)) % V);
-    const unsigned step = (unsigned)(npix % V);
-    const int j = lane & (V - 1);
-    int c = 0;
-#pragma unroll 1
-    for (int it = 0; it < CP_WAVE_WORDS / V; ++it) {
-        const size_t wbase = w0 + (size_t)it * V;
-        const size_t pix0 = wbase * 64;
-        u64 word = 0;                                    // word j of the iteration, in lanes j < V
-#pragma unroll
-        for (int h = 0; h < V; ++h) {
-            const size_t pix = pix0 + (size_t)lane * V + h;
-            bool flag[V], low = false;
-#pragma unroll
-            for (int k = 0; k < V; ++k) flag[k] = false;
-            for (int p = 0; p < nplane; ++p) {
-                if ((V - (a0 + p * step) % V) % V != (unsigned)h) continue;          // wave-uniform
-                const T* plane = img + (size_t)p * npix;
-                if (pix + V <= npix) {
-                    const Pack<T, V> v = ld_nt<T, V>(plane + h, (pix - h) / V);
-#pragma unroll
-                    for (int k = 0; k < V; ++k) flag[k] |= (v.e[k] != (T)0);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < V; ++k)
-                        if (pix + k < npix) flag[k] |= (plane[pix + k] != (T)0);
-                }
-                if (lane < h && pix0 + lane < npix) low |= (plane[pix0 + lane] != (T)0);
-            }
-            u64 b[V];
-#pragma unroll
-            for (int k = 0; k < V; ++k) b[k] = __ballot(flag[k]);
-            const u64 lowbits = __ballot(low);
-            if (lane < V) {
-                const u64 here = mask_word<V>(b, j);
-                if (h == 0) {
-                    word |= here;
-                } else {
-                    const u64 below = j > 0 ? mask_word<V>(b, j - 1) : lowbits << (64 - h);
-                    word |= (here << h) | (below >> (64 - h));
-                }
-            }
-        }
-        if (lane < V && wbase + lane < nwords) {
-            mask[wbase + lane] = word;
-            c += __popcll(word);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if (lane == 0) cnt[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < CP_WAVES; ++w) s += cnt[w];
-        counts[blockIdx.x] = s;
-    }
-}
-
-// one workgroup: offs[g] <- sum_{h < g} offs[h] in place, offs[n] <- the total
-__global__ void __launch_bounds__(CP_SCAN_BLOCK)
-k_comps_scan(i64* __restrict__ offs, int n) {
-    __shared__ i64 wsum[CP_SCAN_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    i64 carry = 0;
-    for (int base = 0; base < n; base += CP_SCAN_BLOCK) {
-        const int i = base + threadIdx.x;
-        const i64 c = i < n ? offs[i] : 0;
-        i64 inc = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const i64 t = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        i64 before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < CP_SCAN_BLOCK / 64; ++w) {
-            const i64 s = wsum[w];
-            if (w < wave) before += s;
-            total += s;
-        }
-        if (i < n) offs[i] = carry + before + inc - c;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) offs[n] = carry;
-}
-
-// same ownership of words as k_comps_mask; pixel q = 64 word + bit is component offs[g] + (set bits before it in the
+// same ownership of words as k_pixmask; pixel q = 64 word + bit is component offs[g] + (set bits before it in the
 // workgroup's words), i.e. components are numbered in pixel order: the order of np.where on the (nx, ny) mask
 __global__ void __launch_bounds__(CP_BLOCK)
 k_comps_compact(const u64* __restrict__ mask, const i64* __restrict__ offs, size_t nwords, i64 ny,
@@ -308,20 +166,6 @@ k_comps_interp(const double* __restrict__ img, InterpGeom g, const double* __res
     }
 }
 
-template <typename T>
-static void mask_launch(const void* img, int nplane, size_t npix, u64* mask, i64* counts, hipStream_t st) {
-    const size_t nwords = comps_nwords(npix);
-    const dim3 grid((unsigned)comps_nblocks(npix));
-    constexpr int V = V16<T>::N;
-    // every plane starts on a 16-byte boundary
-    if (aligned16(img) && (npix * sizeof(T)) % 16 == 0)
-        hipLaunchKernelGGL((k_comps_mask<T, V>), grid, dim3(CP_BLOCK), 0, st, (const T*)img, nplane, npix, nwords,
-                           mask, counts);
-    else
-        hipLaunchKernelGGL(k_comps_mask_peel<T>, grid, dim3(CP_BLOCK), 0, st, (const T*)img, nplane, npix, nwords, mask,
-                           counts);
-}
-
 }  // namespace pfb
 
 using namespace pfb;
@@ -334,21 +178,7 @@ size_t pfb_comps_work_bytes(size_t npix) {
 }
 
 int pfb_comps_mask(int dtype, const void* image, int nplane, size_t npix, void* work, void* stream) {
-    PFB_REQUIRE(image && work, PFB_ERR_INVALID, "comps_mask: null argument");
-    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "comps_mask: bad dtype %d", dtype);
-    PFB_REQUIRE(nplane >= 1 && npix >= 1 && npix <= CP_MAX_PIX, PFB_ERR_INVALID,
-                "comps_mask: nplane %d / npix %zu out of range", nplane, npix);
-    PFB_REQUIRE(((uintptr_t)work & 7u) == 0, PFB_ERR_INVALID, "comps_mask: work must be 8-byte aligned");
-    PFB_REQUIRE((uintptr_t)image % (dtype == PFB_F32 ? 4 : 8) == 0, PFB_ERR_INVALID,
-                "comps_mask: image is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    u64* mask = (u64*)work;
-    i64* offs = (i64*)work + comps_nwords(npix);
-    if (dtype == PFB_F32) mask_launch<float>(image, nplane, npix, mask, offs, st);
-    else                  mask_launch<double>(image, nplane, npix, mask, offs, st);
-    hipLaunchKernelGGL(k_comps_scan, dim3(1), dim3(CP_SCAN_BLOCK), 0, st, offs, (int)comps_nblocks(npix));
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return pixmask_run("comps_mask", AnyNonzero{}, INT_MAX, dtype, image, nullptr, nplane, npix, work, stream);
 }
 
 int pfb_comps_compact(size_t npix, int ny, const void* work, long long* Ix, long long* Iy, void* stream) {

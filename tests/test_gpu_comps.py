@@ -17,6 +17,8 @@ Bounds:
   slice         the eval bound + 32 * 2.2e-16 max|ref| for the bilinear weights and their four-term sum.
   at scale      Ix, Iy equal to np.where(np.any(image, axis=(0, 1))); eval(fit) equals the cube on the components
                 within atol 1e-10, the criterion of the reference's own test (test_model2comps.py:106).
+  mask edges    Ix, Iy equal to np.where(np.any(cube, axis=0)) at every base offset and around every word, wave and
+                workgroup edge of the mask pass.
 Every input image is the stored float32 array; the fp64 runs use its upcast, as the reference run did.
 """
 import os
@@ -130,6 +132,69 @@ def test_compaction_at_scale(dtype, shape):
     diff = (cube - imd.double()).abs().max().item()
     print(f'{shape} {np.dtype(dtype).name}: ncomps {wIx.size}, max |eval(fit) - cube| {diff:.2e}')
     assert diff <= 1e-10
+
+
+def edge_pixels(npix, V):
+    """Flat indices of the first and the last pixel, both sides of the 64-pixel (mask word) boundaries near the start
+    and near the end, and the first V - 1 pixels of wave iterations (64 V pixels each; the pixels lane 0 reads singly
+    when a plane is off the 16-byte grid) at the start, around a wave's share (1024 px), around a workgroup (4096 px)
+    and at the end."""
+    q = {0, npix - 1}
+    nb = (npix - 1) // 64
+    for b in (1, 2, 3, nb - 2, nb - 1, nb):
+        q |= {64 * b - 1, 64 * b}
+    span = 64 * V
+    its = {0, 1, 2, (npix - 1) // span - 1, (npix - 1) // span}
+    for edge in (1024 // span, 4096 // span):
+        its |= {edge - 1, edge, edge + 1}
+    for s in its:
+        q |= {span * s + j for j in range(V - 1)}
+    return np.array(sorted(p for p in q if 0 <= p < npix))
+
+
+def device_where(cube, a):
+    """Ix, Iy of the device route (mask, scan, count read, compaction) on a copy of the (nplane, nx, ny) cube that
+    starts `a` elements past a 16-byte boundary."""
+    from pfb_clean_amd.utils.comps import _components
+    nplane, nx, ny = cube.shape
+    buf = torch.zeros(cube.size + 8, dtype=torch.from_numpy(cube).dtype, device='cuda')
+    buf[a:a + cube.size] = torch.from_numpy(cube).cuda().reshape(-1)
+    dev = buf[a:a + cube.size].view(nplane, nx * ny)
+    assert dev.is_contiguous() and dev.data_ptr() % 16 == a * cube.itemsize
+    Ix, Iy = _components(dev, nx, ny)
+    assert Ix.dtype == torch.int64 and Iy.dtype == torch.int64
+    return Ix.cpu().numpy(), Iy.cpu().numpy()
+
+
+# On either side of a word (64 px), a wave's share (1024 px) and a workgroup (4096 px); every value of npix % V, a
+# vector straddling npix included.  With 3 planes and npix % V != 0 every plane has a head of its own.
+@pytest.mark.parametrize('shape', [(1, 1), (1, 3), (7, 9), (8, 8), (5, 13), (63, 65), (64, 64), (17, 241), (3, 2731)])
+@pytest.mark.parametrize('dtype,a', [(np.float32, 0), (np.float32, 1), (np.float32, 2), (np.float32, 3),
+                                     (np.float64, 0), (np.float64, 1)])
+def test_mask_edges(dtype, a, shape):
+    """Ix, Iy equal np.where(np.any(cube, axis=0)) with every edge pixel set in exactly one plane, every plane in
+    turn, so that each plane's head is the only witness; a NaN counts, -0.0 does not."""
+    nx, ny = shape
+    npix, V = nx * ny, 16 // np.dtype(dtype).itemsize
+    q = edge_pixels(npix, V)
+    assert q[0] == 0 and q[-1] == npix - 1
+
+    def check(cube, what):
+        wIx, wIy = np.where(np.any(cube, axis=0))
+        Ix, Iy = device_where(cube, a)
+        assert np.array_equal(Ix, wIx) and np.array_equal(Iy, wIy), (what, shape, a)
+        return Ix.size
+
+    for value in (1.5, np.nan):
+        for turn in range(3):
+            cube = np.zeros((3, npix), dtype=dtype)
+            cube[(np.arange(q.size) + turn) % 3, q] = value
+            assert check(cube.reshape(3, nx, ny), f'{value} turn {turn}') == q.size
+    cube = np.zeros((3, npix), dtype=dtype)
+    cube[np.arange(q.size) % 3, q] = -0.0
+    assert np.signbit(cube).sum() == q.size and check(cube.reshape(3, nx, ny), '-0.0') == 0
+    assert check(np.zeros((3, nx, ny), dtype=dtype), 'zeros') == 0
+    assert check(np.ones((3, nx, ny), dtype=dtype), 'ones') == npix
 
 
 # ------------------------------------------------------------------------------------------------ eval

@@ -12,7 +12,8 @@ rho <= 0.5 on the stored cases):
                 most tol, and with rho <= 0.5 what is left of the way to the limit is at most tol as well.
   nband = 2     only alpha and I0 are compared: the fit interpolates, chi2 is rounding noise, the errors are noise
                 over noise.
-  mask          equal to numpy's, the maps NaN exactly off it.
+  mask          equal to numpy's, the maps NaN exactly off it; also with more workgroups (259) than one 256-entry tile
+                of the scan, where the counts' carry and the maximum must cross tiles.
 threshold and pb_min are exactly representable in float32, so numpy's scalar casting cannot matter.
 """
 import io
@@ -353,6 +354,75 @@ def test_empty_mask(dtype, kind):
         assert str(got.value) == str(want.value)
         assert str(got.value).endswith("threshold.Max of convolved model is " + ("nan" if with_nan else
                                        "%3.2e" % np.where(beam > PB_MIN, image, 0).max()))
+
+
+# ------------------------------------------------------------------------------------ more than one tile of the scan
+# 259 workgroups of 4096 pixels each, one more than a 256-entry tile of the scan, so that its carry and its maximum
+# across tiles are exercised: odd npix (no plane but the first on the 16-byte grid) and npix a multiple of 16 bytes
+SCAN_SHAPES = [(1031, 1025), (1030, 1026)]
+
+
+def scan_cube(nx, ny):
+    """Case 0 (2 bands), fp32, with 36 components: the first and the last pixel, the first, one inner and the last
+    pixel of workgroups 255, 256 and 257, the rest seeded.  Returns the case, the cubes and the flat pixel indices."""
+    c = sc.case(0)
+    npix = nx * ny
+    assert (npix + 4095) // 4096 == 259
+    flat = [0] + [4096 * g + o for g in (255, 256, 257) for o in (0, 1234, 4095)]
+    rng = np.random.default_rng([422, nx])
+    flat += [int(q) for q in rng.choice(npix, size=64, replace=False) if q not in flat][:25] + [npix - 1]
+    assert len(set(flat)) == 36
+    image, beam = sc.cube_of(c, nx, ny, [(q // ny, q % ny) for q in flat])
+    return c, image, beam, sorted(flat)
+
+
+def device_idx(image, beam, threshold):
+    """(ncomps, 2) int64: what pfb_spi_mask and pfb_comps_compact make of the device cubes, as fit_spi calls them."""
+    from pfb_clean_amd import _lib, _dev
+    lib = _lib.load()
+    nband, nx, ny = image.shape
+    npix = nx * ny
+    img, bm = torch.from_numpy(image).cuda(), torch.from_numpy(beam).cuda()
+    work = torch.empty(lib.pfb_spi_work_bytes(npix) // 8, dtype=torch.int64, device='cuda')
+    _lib.check(lib.pfb_spi_mask(_dev.code(img.dtype), _dev.ptr(img), _dev.ptr(bm), nband, npix, PB_MIN, threshold,
+                                _dev.ptr(work), _dev.stream()))
+    ncomps = int(work[lib.pfb_comps_work_bytes(npix) // 8 - 1].item())
+    Ix, Iy = (torch.empty(ncomps, dtype=torch.int64, device='cuda') for _ in range(2))
+    _lib.check(lib.pfb_comps_compact(npix, ny, _dev.ptr(work), _dev.ptr(Ix), _dev.ptr(Iy), _dev.stream()))
+    return torch.stack((Ix, Iy), dim=1).cpu().numpy()
+
+
+@pytest.mark.parametrize('shape', SCAN_SHAPES)
+def test_scan_beyond_one_tile(shape):
+    c, image, beam, flat = scan_cube(*shape)
+    omaps, idx, _, spread = oracle_cube(image, beam, c, tol=1e-10)
+    assert (idx[:, 0] * shape[1] + idx[:, 1]).tolist() == flat
+    assert np.array_equal(device_idx(image, beam, THRESHOLD), idx)
+    maps, said = run_cube(image, beam, c, 'tensor', tol=1e-10)
+    assert said.startswith("Fitting 36 components\n")
+    check_cube(maps, omaps, idx, spread, c['nband'], f'scan beyond one tile {shape}')
+
+
+@pytest.mark.parametrize('shape', SCAN_SHAPES)
+def test_empty_mask_beyond_one_tile(shape):
+    """The maximum of the cut, then a NaN, in the last workgroup only: both must cross the scan's tiles."""
+    c, image, beam, flat = scan_cube(*shape)
+    npix = shape[0] * shape[1]
+    top, bad = npix - 2, npix - 3
+    assert min(top, bad) >= 4096 * 258 and top not in flat and bad not in flat
+    image = image.copy()
+    image[1].reshape(-1)[top] = 100.0
+    cut = np.where(beam > PB_MIN, image, 0).reshape(2, -1)
+    assert cut[:, :4096 * 258].max() < 100.0 == cut.max()
+    for with_nan in (False, True):
+        if with_nan:
+            image[0].reshape(-1)[bad] = np.nan
+        with pytest.raises(ValueError) as want:
+            sc.fit_spi(image, beam, c['freqs'], c['weights'], 1024.0, PB_MIN, c['ref_freq'])
+        with pytest.raises(ValueError) as got:
+            run_cube(image, beam, c, 'tensor', threshold=1024.0)
+        assert str(got.value) == str(want.value)
+        assert str(got.value).endswith("threshold.Max of convolved model is " + ("nan" if with_nan else "1.00e+02"))
 
 
 def test_zero_weights():

@@ -12,9 +12,11 @@ Reports the median over --runs warm runs of
            the binary has been built, or given with --stream-tbs)
   host     a device-to-host copy of the cube followed by the numpy statement of the fit
            (np.any / np.where / gather / normal equations / np.linalg.solve)
-and prints one JSON line.
+and prints one JSON line.  --shape NX NY takes the place of --n for a plane that is not square (4097 x 4095: odd npix,
+the form of the mask pass for planes off the 16-byte grid); --mask-only times the mask pass alone (median, min and max
+of --runs device-event times), which is what an A/B of two builds of the library (PFB_HIP_LIB) needs.
 
-    python tools/time_comps.py [--n 4096] [--nband 8] [--runs 20] [--host-runs 20]
+    python tools/time_comps.py [--n 4096 | --shape NX NY] [--nband 8] [--runs 20] [--host-runs 20] [--mask-only]
 """
 import argparse
 import json
@@ -49,7 +51,7 @@ def median_ms(fn, runs, warm=3):
     return statistics.median(out)
 
 
-def event_ms(fn, runs, warm=3):
+def event_times(fn, runs, warm=3):
     for _ in range(warm):
         fn()
     out = []
@@ -60,7 +62,11 @@ def event_ms(fn, runs, warm=3):
         e1.record()
         e1.synchronize()
         out.append(e0.elapsed_time(e1))
-    return statistics.median(out)
+    return out
+
+
+def event_ms(fn, runs, warm=3):
+    return statistics.median(event_times(fn, runs, warm))
 
 
 def stream_rate():
@@ -82,6 +88,8 @@ def host_fit(time_, freq, image, Xfit):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=4096)
+    ap.add_argument('--shape', type=int, nargs=2, default=None, metavar=('NX', 'NY'))
+    ap.add_argument('--mask-only', action='store_true')
     ap.add_argument('--nband', type=int, default=8)
     ap.add_argument('--runs', type=int, default=20)
     ap.add_argument('--host-runs', type=int, default=20)
@@ -90,29 +98,40 @@ def main():
 
     dev = _dev.require_device()
     lib = _lib.load()
-    n, nband = a.n, a.nband
-    cube = torch.stack([synth_model(b, n, n, torch.float32, dev) for b in range(nband)])[None].contiguous()
+    nband = a.nband
+    nx, ny = a.shape or (a.n, a.n)
+    cube = torch.stack([synth_model(b, nx, ny, torch.float32, dev) for b in range(nband)])[None].contiguous()
     time_, freq = np.array([3600.0]), 1e9 * (1.0 + 0.1 * np.arange(nband))
     nbytes = cube.numel() * cube.element_size()
+
+    npix = nx * ny
+    flat = cube.view(nband, npix)
+    work = torch.empty(lib.pfb_comps_work_bytes(npix) // 8, dtype=torch.int64, device=dev)
+    st = _dev.stream()
+
+    def run_mask():
+        _lib.check(lib.pfb_comps_mask(_lib.PFB_F32, _dev.ptr(flat), nband, npix, _dev.ptr(work), st))
+    if a.mask_only:
+        t = event_times(run_mask, a.runs)
+        med = statistics.median(t)
+        print(json.dumps({'shape': [nband, nx, ny], 'dtype': 'float32', 'lib': _lib.LIB_PATH, 'cube_MB': nbytes / 1e6,
+                          'ncomps': int(work[-1].item()), 'runs': a.runs,
+                          'mask_ms': {'median': med, 'min': min(t), 'max': max(t), 'TBps_median': nbytes / med / 1e9}}))
+        return
 
     res = comps.fit_image_cube(time_, freq, cube, nbasisf=nband, method='Legendre')
     ncomps = res[1].numel()
     t_fit = median_ms(lambda: comps.fit_image_cube(time_, freq, cube, nbasisf=nband, method='Legendre'), a.runs)
 
     # the stages on their own
-    npix = n * n
-    flat = cube.view(nband, npix)
-    work = torch.empty(lib.pfb_comps_work_bytes(npix) // 8, dtype=torch.int64, device=dev)
     Ix, Iy = torch.empty_like(res[1]), torch.empty_like(res[2])
     coeffs = torch.empty_like(res[0])
     Xfit = comps.fit_design(time_, freq, None, nband, 'Legendre')[0]
     sysd = torch.from_numpy(comps._fit_system(Xfit, None, 0)).to(dev)
-    st = _dev.stream()
-    t_mask = event_ms(lambda: _lib.check(lib.pfb_comps_mask(_lib.PFB_F32, _dev.ptr(flat), nband, npix, _dev.ptr(work),
-                                                            st)), a.runs)
-    t_compact = event_ms(lambda: _lib.check(lib.pfb_comps_compact(npix, n, _dev.ptr(work), _dev.ptr(Ix), _dev.ptr(Iy),
+    t_mask = event_ms(run_mask, a.runs)
+    t_compact = event_ms(lambda: _lib.check(lib.pfb_comps_compact(npix, ny, _dev.ptr(work), _dev.ptr(Ix), _dev.ptr(Iy),
                                                                   st)), a.runs)
-    t_solve = event_ms(lambda: _lib.check(lib.pfb_comps_fit(_lib.PFB_F32, _dev.ptr(flat), nband, npix, n, _dev.ptr(Ix),
+    t_solve = event_ms(lambda: _lib.check(lib.pfb_comps_fit(_lib.PFB_F32, _dev.ptr(flat), nband, npix, ny, _dev.ptr(Ix),
                                                             _dev.ptr(Iy), ncomps, _dev.ptr(sysd), nband,
                                                             _dev.ptr(coeffs), st)), a.runs)
     assert torch.equal(Ix, res[1]) and torch.equal(Iy, res[2])
@@ -127,7 +146,7 @@ def main():
     t_numpy = median_ms(lambda: host_fit(time_, freq, host, Xfit), a.host_runs, warm=1)
 
     tbs = a.stream_tbs if a.stream_tbs is not None else stream_rate()
-    out = {'n': n, 'nband': nband, 'dtype': 'float32', 'ncomps': ncomps, 'cube_MB': nbytes / 1e6,
+    out = {'shape': [nband, nx, ny], 'nband': nband, 'dtype': 'float32', 'ncomps': ncomps, 'cube_MB': nbytes / 1e6,
            'device_fit_ms': t_fit, 'mask_ms': t_mask, 'compact_ms': t_compact, 'fit_kernel_ms': t_solve,
            'mask_GBps': nbytes / 1e6 / t_mask, 'hbm_stream_read_GBps': None if tbs is None else 1e3 * tbs,
            'host_d2h_ms': t_d2h, 'host_numpy_ms': t_numpy, 'host_route_ms': t_d2h + t_numpy,

@@ -14,9 +14,12 @@ Reports, per fraction
              of tests/spi_cases.py.  Above --host-comps components the oracle's fit runs on the first --host-comps
              of them and its time is scaled to all (stated in the output); its maps are checked against the device's
              on the components it did fit
-and prints one JSON line.  There is no pass / fail threshold.
+and prints one JSON line.  There is no pass / fail threshold.  --shape NX NY takes the place of --n for a plane that is
+not square (4097 x 4095: odd npix, the form of the mask pass for planes off the 16-byte grid); --mask-only stops after
+the mask pass, which is what an A/B of two builds of the library (PFB_HIP_LIB) needs.
 
-    python tools/time_spi.py [--n 4096] [--nband 8] [--runs 10] [--fractions 0.01 1.0] [--json FILE]
+    python tools/time_spi.py [--n 4096 | --shape NX NY] [--nband 8] [--runs 10] [--fractions 0.01 1.0] [--mask-only]
+                             [--json FILE]
 """
 import argparse
 import io
@@ -39,15 +42,14 @@ import spi_cases as sc  # noqa: E402
 THRESHOLD, PB_MIN = 2.0 ** -14, 0.25
 
 
-def cubes(nband, n, frac, freqs, ref_freq, dev):
+def cubes(nband, shape, frac, freqs, ref_freq, dev):
     g = torch.Generator(device=dev)
     g.manual_seed(420)
-    shape = (n, n)
     alpha = torch.rand(shape, generator=g, device=dev, dtype=torch.float64) * 3.0 - 2.0
     I0 = 10.0 ** (torch.rand(shape, generator=g, device=dev, dtype=torch.float64) * 4.0 - 3.0)
     on = torch.rand(shape, generator=g, device=dev) < frac
-    image = torch.empty((nband, n, n), dtype=torch.float32, device=dev)
-    beam = torch.empty((nband, n, n), dtype=torch.float32, device=dev)
+    image = torch.empty((nband,) + shape, dtype=torch.float32, device=dev)
+    beam = torch.empty((nband,) + shape, dtype=torch.float32, device=dev)
     for b in range(nband):
         beam[b] = torch.rand(shape, generator=g, device=dev) * 0.7 + 0.3
         noise = 1.0 + 0.05 * torch.randn(shape, generator=g, device=dev, dtype=torch.float64)
@@ -73,23 +75,26 @@ def stats(t):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=4096)
+    ap.add_argument('--shape', type=int, nargs=2, default=None, metavar=('NX', 'NY'))
+    ap.add_argument('--mask-only', action='store_true')
     ap.add_argument('--nband', type=int, default=8)
     ap.add_argument('--runs', type=int, default=10)
     ap.add_argument('--fractions', type=float, nargs='+', default=[0.01, 1.0])
     ap.add_argument('--host-comps', type=int, default=1 << 18)
     ap.add_argument('--json', default=None)
     args = ap.parse_args()
-    nband, n = args.nband, args.n
-    npix = n * n
+    nband = args.nband
+    nx, ny = args.shape or (args.n, args.n)
+    npix = nx * ny
     dev = _dev.require_device()
     lib = _lib.load()
     freqs = np.linspace(0.9e9, 1.7e9, nband)
     weights = np.linspace(0.5, 2.0, nband)
     ref_freq = 1.3e9
     lnx, w, ref = spi._bands(freqs, weights, ref_freq)
-    res = {'shape': [nband, n, n], 'dtype': 'float32', 'runs': args.runs, 'cases': []}
+    res = {'shape': [nband, nx, ny], 'dtype': 'float32', 'lib': _lib.LIB_PATH, 'runs': args.runs, 'cases': []}
     for frac in args.fractions:
-        image, beam = cubes(nband, n, frac, freqs, ref_freq, dev)
+        image, beam = cubes(nband, (nx, ny), frac, freqs, ref_freq, dev)
         code, nbytes = _dev.code(image.dtype), 2 * image.numel() * 4
         work = torch.empty(lib.pfb_spi_work_bytes(npix) // 8, dtype=torch.int64, device=dev)
 
@@ -98,14 +103,20 @@ def main():
                                         work.data_ptr(), _dev.stream()))
         run_mask()
         ncomps = int(work[lib.pfb_comps_work_bytes(npix) // 8 - 1].item())
+        if args.mask_only:
+            torch.cuda.synchronize()
+            tm = [event_ms(run_mask) for _ in range(args.runs)]
+            res['cases'].append({'fraction': frac, 'ncomps': ncomps, 'GB_read': nbytes / 1e9,
+                                 'mask_ms': dict(stats(tm), TBps_median=nbytes / float(np.median(tm)) / 1e9)})
+            continue
         Ix = torch.empty(ncomps, dtype=torch.int64, device=dev)
         Iy = torch.empty(ncomps, dtype=torch.int64, device=dev)
-        _lib.check(lib.pfb_comps_compact(npix, n, work.data_ptr(), Ix.data_ptr(), Iy.data_ptr(), _dev.stream()))
-        maps = torch.full((4, n, n), float('nan'), dtype=image.dtype, device=dev)
+        _lib.check(lib.pfb_comps_compact(npix, ny, work.data_ptr(), Ix.data_ptr(), Iy.data_ptr(), _dev.stream()))
+        maps = torch.full((4, nx, ny), float('nan'), dtype=image.dtype, device=dev)
         notconv = torch.empty(1, dtype=torch.int64, device=dev)
 
         def run_fit():
-            _lib.check(lib.pfb_spi_fit(code, image.data_ptr(), beam.data_ptr(), nband, npix, n, Ix.data_ptr(),
+            _lib.check(lib.pfb_spi_fit(code, image.data_ptr(), beam.data_ptr(), nband, npix, ny, Ix.data_ptr(),
                                        Iy.data_ptr(), ncomps, lnx.ctypes.data, w.ctypes.data, ref, PB_MIN, 1e-5, 100,
                                        maps.data_ptr(), notconv.data_ptr(), _dev.stream()))
         run_fit()
