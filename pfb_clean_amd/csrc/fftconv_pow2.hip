@@ -208,21 +208,20 @@ __device__ __forceinline__ cplx<T> root32(int k) {              // exp(-2 pi i k
     return cplx<T>(cs(k), -cs(k - 8));
 }
 
-// XCD-aware row-group order of the plain row kernels.  A workgroup of G rows touches T in G x 16-byte pieces; 8 rows
-// make a 128-byte line.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share an L2), so the
-// SH = 8 / G row groups of one line are given to blocks b, b + 8, .. b + 8 (SH - 1): their pieces meet in ONE L2 and
-// leave it (or are fetched into it) as a full line (speed only: any bijection is correct).
-template <int G>
-__device__ __forceinline__ int xcd_row_group(int bx, int nbx) {
-    constexpr int SH = 8 / G;
-    if constexpr (SH > 1) {
-        if (nbx % (8 * SH) == 0) {
-            const int q = bx / (8 * SH), rem = bx % (8 * SH);
-            return SH * (q * 8 + (rem & 7)) + (rem >> 3);
-        }
-    }
-    return bx;
+// XCD-aware order of the row groups (plain row kernels: workgroups; persistent ones: tiles of a band).  A group of G rows
+// touches T in G x 16-byte pieces; 8 rows make a 128-byte line.  Workgroups are dealt round-robin over the 8 XCDs (blocks
+// b and b + 8 share an L2), so the SH = 8 / G row groups of one line are given to blocks b, b + 8, .. b + 8 (SH - 1):
+// their pieces meet in ONE L2 and leave it (or are fetched into it) as a full line (speed only: any bijection is
+// correct; on whenever the `n` groups are a multiple of 8 SH).
+__device__ __forceinline__ int xcd_paired(int rg, int SH) {
+    const int q = rg / (8 * SH), rem = rg % (8 * SH);
+    return SH * (q * 8 + (rem & 7)) + (rem >> 3);
 }
+__device__ __forceinline__ int xcd_line_pair(int rg, int n, int SH) {
+    return SH > 1 && n % (8 * SH) == 0 ? xcd_paired(rg, SH) : rg;
+}
+template <int G>
+__device__ __forceinline__ int xcd_row_group(int bx, int nbx) { return xcd_line_pair(bx, nbx, 8 / G); }
 
 struct FastDims {
     int nx, ny, M;              // M = ny (packed length), nv = M + 1 columns
@@ -232,14 +231,17 @@ struct FastDims {
 };
 
 // ---------------------------------------------------------------- psfhat re-layout
+// blocks of the even bins (m <= L: L + 1 of them) and of the odd bins (m < L) of a half spectrum of L + 1 + L columns
+__host__ __device__ constexpr int nblocks_even(int L, int nvb) { return (L + nvb) / nvb; }
+__host__ __device__ constexpr int nblocks_odd(int L, int nvb) { return L / nvb; }
 // column v of the half spectrum -> (block, slot) of the pair layout
 __host__ __device__ inline void block_of_bin(int v, int L, int nvb, int* blk, int* c) {
     const int m = v >> 1;
-    const int nbe = (L + nvb) / nvb;
+    const int nbe = nblocks_even(L, nvb);
     *blk = ((v & 1) ? nbe : 0) + m / nvb;
     *c = m % nvb;
 }
-inline int fast_nblocks(int L, int nvb) { return (L + nvb) / nvb + L / nvb; }
+inline int fast_nblocks(int L, int nvb) { return nblocks_even(L, nvb) + nblocks_odd(L, nvb); }
 // element offset of psfhat[u][v(blk, c)] inside a band of psf_l (H = nx = P / 2 rows per parity).
 //   four = 0: parity-major  psf_l[blk][u & 1][u >> 1][c]     (k_col_pow2, k_col_pow2p)
 //   four = 1: class-major   psf_l[blk][u & 3][u >> 2][c]     (k_col_pow2x: the two-level column transform)
@@ -321,82 +323,47 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
     // L2" going to HBM: +1 GB per 8-band launch).  aw = a .* w_P^n is formed at load time and
     // parked in registers; its live range (first FFT pair) does not overlap ev's (second pair),
     // so the peak register demand is unchanged.
-    // PREQ2 (8192-point fp32 column pairs): a .* w_P^n is NOT parked in registers -- the second parity re-reads a
-    // (an L2 / Infinity-Cache hit: this workgroup fetched it microseconds ago) -- and its registers take the PSF slices,
-    // requested a few per FFT pass: psf_e lands during the first transform, psf_o during the second.  2.19 -> 2.00 ms
-    // per 2 x 8192^2 (128 VGPRs + 244 B of scratch; with the even-bin result round-tripping through T as well: 160 B,
-    // 2.03 ms).  The same idea lost on the fp64 columns (fp64-issue and LDS bound); this one is latency bound.
-    constexpr bool PREQ2 = sizeof(T) == 4 && H >= 8192;
-    cplx<T> vv[NVB][E], aw[PREQ2 ? 1 : NVB][PREQ2 ? 1 : E];
+    cplx<T> vv[NVB][E], aw[NVB][E];
     {
         const cplx<T>* tw2 = twP + t;
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             Blk<T, NVB> a;
             if (active) a = loadb<T, NVB>(col + NVB * TPB * j);
-            [[maybe_unused]] cplx<T> w;
-            if constexpr (!PREQ2) w = tw2[TPB * j];
+            const cplx<T> w = tw2[TPB * j];
 #pragma unroll
             for (int c = 0; c < NVB; ++c) {
                 vv[c][j] = active ? a.c[c] : cplx<T>(0, 0);
-                if constexpr (!PREQ2) aw[c][j] = vv[c][j] * w;
+                aw[c][j] = vv[c][j] * w;
             }
         }
     }
     // (Requesting psf_e before the first transform and psf_o before the second in the 8192-point fp64 columns: vv + aw + q
     // are 192 registers before the radix-16 butterfly's own 64, 84 -> 556 bytes of scratch per lane.)
-    constexpr int NPQ = F::NPASS;
     // MIXL: the 3 2^k / 5 2^k columns launder the thread index per transform (LAUNDER_EARLY): with up to ten passes per
     // transform the LDS addresses of all of them, computed once and kept across the four transforms, cost 130 registers
     // (5120-point fp32 columns: 256 VGPRs + 132 B of scratch -> 132 VGPRs).  (Spelled as a branch per call: behind a
     // helper -- a lambda or launder_if<MIXL>(t), both tried -- the power-of-two instantiations of this object compile to a
     // different register allocation and schedule than the one all its measurements were taken with.)
     constexpr bool MIXL = odd_part(H) > 1;
-    Blk<T, NVB> q[PREQ2 ? E : 1];
     // ---- even bins of the column transform
-    if constexpr (PREQ2) {
-        F::template runN<false, NVB>(vv, lds, t, ptw, [&](auto k) {
-            constexpr int K = decltype(k)::value;
-#pragma unroll
-            for (int j = (K * E) / NPQ; j < ((K + 1) * E) / NPQ; ++j) q[j] = loadb<T, NVB>(pe + NVB * TPB * j);
-        });
-    } else if constexpr (MIXL) F::template runN<false, NVB>(vv, lds, launder(t), ptw);
+    if constexpr (MIXL) F::template runN<false, NVB>(vv, lds, launder(t), ptw);
     else
     F::template runN<false, NVB>(vv, lds, t, ptw);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-        Blk<T, NVB> p;
-        if constexpr (PREQ2) p = q[j]; else p = loadb<T, NVB>(pe + NVB * TPB * j);
+        const Blk<T, NVB> p = loadb<T, NVB>(pe + NVB * TPB * j);
 #pragma unroll
         for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * p.c[c];
     }
-    if constexpr (PREQ2) {
-        F::template runN<true, NVB>(vv, lds, t, ptw, [&](auto k) {
-            constexpr int K = decltype(k)::value;
-#pragma unroll
-            for (int j = (K * E) / NPQ; j < ((K + 1) * E) / NPQ; ++j) q[j] = loadb<T, NVB>(po + NVB * TPB * j);
-        });
-    } else if constexpr (MIXL) F::template runN<true, NVB>(vv, lds, launder(t), ptw);
+    if constexpr (MIXL) F::template runN<true, NVB>(vv, lds, launder(t), ptw);
     else
     F::template runN<true, NVB>(vv, lds, t, ptw);
     cplx<T> ev[NVB][E];
 #pragma unroll
     for (int j = 0; j < E; ++j) {
 #pragma unroll
-        for (int c = 0; c < NVB; ++c) { ev[c][j] = vv[c][j]; if constexpr (!PREQ2) vv[c][j] = aw[c][j]; }
-    }
-    if constexpr (PREQ2) {
-        const cplx<T>* tw2 = twP + t;
-        cplx<T>* col2 = opaque(col);
-        Blk<T, NVB> a2[E];
-#pragma unroll
-        for (int j = 0; j < E; ++j) if (active) a2[j] = loadb<T, NVB>(col2 + NVB * TPB * j);
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            const cplx<T> w = tw2[TPB * j];
-#pragma unroll
-            for (int c = 0; c < NVB; ++c) vv[c][j] = active ? a2[j].c[c] * w : cplx<T>(0, 0);
-        }
+        for (int c = 0; c < NVB; ++c) { ev[c][j] = vv[c][j]; vv[c][j] = aw[c][j]; }
     }
     // ---- odd bins
     if constexpr (MIXL) F::template runN<false, NVB>(vv, lds, launder(t), ptw);
@@ -404,8 +371,7 @@ k_col_pow2(cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ psf_l,
     F::template runN<false, NVB>(vv, lds, t, ptw);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-        Blk<T, NVB> p;
-        if constexpr (PREQ2) p = q[j]; else p = loadb<T, NVB>(po + NVB * TPB * j);
+        const Blk<T, NVB> p = loadb<T, NVB>(po + NVB * TPB * j);
 #pragma unroll
         for (int c = 0; c < NVB; ++c) vv[c][j] = vv[c][j] * p.c[c];
     }
@@ -914,18 +880,18 @@ __device__ __forceinline__ void row_fwd_post(const cplx<T> (&z)[E], const cplx<T
     //   even v = 2m   : Z -> Ze[m mod L], Ze[(L-m) mod L]      m = 0..L
     //   odd  v = 2m+1 : Z -> Zo[m],       Zo[L-1-m]            m = 0..L-1
     constexpr int NVB = FastCfg<T>::NVB;
-    constexpr int NBE = (L + NVB) / NVB;
-    constexpr int NBP = PAR ? L / NVB : NBE;                 // blocks of this parity
+    constexpr int NBE = nblocks_even(L, NVB), NBO = nblocks_odd(L, NVB);
+    constexpr int NBP = PAR ? NBO : NBE;                     // blocks of this parity
     constexpr int BSTEP = NT / G;
     cplx<T>* Tp = Tb + ((size_t)(PAR ? NBE : 0) * nx + i0 + rr) * NVB;
     constexpr int MS = NVB * BSTEP;               // m advances by MS per trip
     // (fp32: 0.0564 -> 0.0547 ms at 2048^2 x 4; the fp64 sweeps measured 1-2 % slower with it and keep the plain form)
-    if constexpr (sizeof(T) == 4 && (L / NVB) % BSTEP == 0 && MS % 16 == 0) {
-        // incremental addressing (see fwdp_post_lin): the trip advances every index by a multiple of 16, so the two
+    if constexpr (sizeof(T) == 4 && NBO % BSTEP == 0 && MS % 16 == 0) {
+        // incremental addressing (see fwdp_post): the trip advances every index by a multiple of 16, so the two
         // padded LDS streams, the twiddle stream and the store address move by constants instead of being rebuilt
         // from the block index (selects, two pad()s, a 64-bit multiply per trip); the Nyquist block of the even
         // bins -- the one trip only bi = 0 makes -- is handled after the loop.
-        constexpr int NREG = (L / NVB) / BSTEP;
+        constexpr int NREG = NBO / BSTEP;
         const int m0 = NVB * bi;
         const cplx<T>* za = zr + F::pad(m0);
         const cplx<T>* zb[NVB];
@@ -1037,68 +1003,40 @@ template <typename T, int L>
 struct FwdP {
     // 128 threads per row, 8 rows per workgroup -- and for the 4096-point rows of 8192-pixel lines (BIG) 256 threads per
     // row, 4 rows (64-byte pieces, XCD-paired to full lines), with the twiddle table w_M^n cut down to the 512 entries a
-    // sweep step spans (SMT): the full table (32 KB) does not fit next to four 4096-point rows.  Both transforms use 16
-    // elements per thread, and with M = 2 L = 32 TPB every other twiddle is a table entry times a 32nd root of unity:
-    //     w_M^(t + TPB j)      = w_M^t       root32(j)        (odd-bin pre-multiply, j = register index)
+    // sweep step spans: the full table (32 KB) does not fit next to four 4096-point rows.  Both transforms use 16
+    // elements per thread, and with M = 2 L = 32 TPR every other twiddle is a table entry times a 32nd root of unity:
+    //     w_M^(t + TPR j)      = w_M^t       root32(j)        (odd-bin pre-multiply, j = register index)
     //     w_M^(m0 + h + MS K)  = w_M^(m0+h)  root32(2 K)      (sweep step K, MS = NVB BSTEP = M / 16)
+    // The kernel serves fp32 rows of 2048 and 4096 points (OK; the alternatives and their timings: DESIGN 8).  RowFwdK
+    // reads OK for every class, so every member is well-formed at every power-of-two L.
     static constexpr bool BIG = L >= 4096;
-    static constexpr int E = BIG ? 16 : L / 128;
-    static constexpr int EOK = (E == 8 || E == 16) ? E : 8;
-    using F = RegFft<T, L, EOK, false, 0, true, true>;
-    static constexpr int TPR = L / EOK;               // threads per row
-    // fp64 rows of 4096 points: two rows fill the LDS -> 512-thread workgroups (256 registers per thread)
-    static constexpr int NT = (BIG && sizeof(T) == 8) ? 512 : 1024;
+    static constexpr int E = L >= 2048 ? 16 : 8;
+    using F = RegFft<T, L, E, false, 0, true, true>;
+    static constexpr int TPR = L / E;                 // threads per row
+    static constexpr int NT = 1024;
     static constexpr int G = NT / TPR;
     static constexpr int STRIDE = F::LDS_ELEMS + 4;
     static constexpr int NVB = FastCfg<T>::NVB;
-    static constexpr int NBE = (L + NVB) / NVB;
-    static constexpr int NBO = L / NVB;
+    static constexpr int NBE = nblocks_even(L, NVB);
+    static constexpr int NBO = nblocks_odd(L, NVB);
     static constexpr int BSTEP = NT / G;
-    static constexpr bool SMT = BIG;
-    static constexpr int NTM = SMT ? NVB * BSTEP : L; // entries of the w_M table kept in the LDS
-    static constexpr int WG_PER_CU = 1;
+    static constexpr int NTM = BIG ? NVB * BSTEP : L; // entries of the w_M table kept in the LDS
     static constexpr int PTWP = (F::PTWC + 1) & ~1;
     static constexpr size_t LDS = sizeof(cplx<T>) * ((size_t)PTWP + NTM + (size_t)G * STRIDE);
-    // (an fp64 version with two-row 512-thread tiles -- what the LDS allows -- writes 32-byte pieces and
-    // measured 0.90 vs 0.54 ms for the plain kernel: not used)
-    // measured: 0.50 -> 0.42 ms at ny = 4096 (x 8 bands of 4096 rows); at ny = 2048 the plain
-    // wave-per-row kernel (E = 16, barrier-free exchanges) is 6 % faster than this one with E = 8
-    // (at 8 elements per thread, fp32 ny = 2048: 0.0633 ms against 0.0561 ms for the plain kernel at 2048^2 x 4)
     // sweep step K advances the bin index by MS = NVB BSTEP: w_M^(MS K) = root32(KR K)
     static constexpr int KR = (32 * NVB * BSTEP) / (2 * L);
-    // fp64 rows of 4096 points as 2-row 512-thread persistent tiles: 1.87 against 1.21 ms per 2 x 8192^2 for the plain
-    // kernel (profiles/r03_i_*; the same verdict as at 2048 points in round 1): not used
     static constexpr bool OK = E == 16 && LDS <= (size_t)LDS_MAX && !(BIG && sizeof(T) == 8) &&
-                               (!SMT || (EOK == 16 && 32 * TPR == 2 * L && KR * 2 * L == 32 * NVB * BSTEP && NTM >= TPR));
+                               (!BIG || (32 * TPR == 2 * L && KR * 2 * L == 32 * NVB * BSTEP && NTM >= TPR));
     // w_M^(t + TPR j) from the table in the LDS
     __device__ __forceinline__ static cplx<T> tw_row(const cplx<T>* ltm, int t, int j) {
-        if constexpr (SMT) return j == 0 ? ltm[t] : ltm[t] * root32<T>(j);
+        if constexpr (BIG) return j == 0 ? ltm[t] : ltm[t] * root32<T>(j);
         else return ltm[t + TPR * j];
     }
-    // tile v of a band -> first row: G < 8 rows make G x 16-byte pieces of T; tiles b and b + 8 (dealt to the same XCD,
-    // hence one L2) take the pieces of ONE 128-byte line (cf. k_row_inv_pow2p)
+    // tile rg of a band -> first row (xcd_line_pair: tiles b and b + 8 take the pieces of ONE 128-byte line)
     __device__ __forceinline__ static int tile_row(int rg, int tiles_per_band) {
-        constexpr int SH = 8 / G;
-        if constexpr (SH > 1) {
-            if (tiles_per_band % (8 * SH) == 0) {
-                const int q = rg / (8 * SH), rem = rg % (8 * SH);
-                rg = SH * (q * 8 + (rem & 7)) + (rem >> 3);
-            }
-        }
-        return rg * G;
+        return xcd_line_pair(rg, tiles_per_band, 8 / G) * G;
     }
 };
-
-// hook(PassIdx<k>): called at the top of sweep step k (the kernel issues a slice of the next tile's loads there)
-template <typename T, int L, int PAR, typename Hook>
-__device__ __forceinline__ void fwdp_post_lin(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1,
-                                              cplx<T>* __restrict__ Tb, int nx, int i0, int rr, int bi, const Hook& hook);
-template <typename T, int L, int PAR, typename Hook = NoPassHook>
-__device__ __forceinline__ void fwdp_post(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1,
-                                          cplx<T>* __restrict__ Tb, int nx, int i0, int rr, int bi,
-                                          const Hook& hook = Hook()) {
-    fwdp_post_lin<T, L, PAR, Hook>(zr, ltm, wq1, Tb, nx, i0, rr, bi, hook);
-}
 
 // ---- the sweep with strength-reduced addressing.
 // The plain form of the sweep (removed, the code is at commit e9a762c) recomputed for every step the clamped block
@@ -1121,7 +1059,7 @@ __device__ __forceinline__ void post_steps_lin(const cplx<T>* const (&za)[FastCf
 #pragma unroll
         for (int h = 0; h < NVB; ++h) {
             cplx<T> w;
-            if constexpr (P::SMT) w = K == 0 ? lw[h] : lw[h] * root32<T>(P::KR * K);  // w_M^(m0 + h + MS K), MS = KR M / 32
+            if constexpr (P::BIG) w = K == 0 ? lw[h] : lw[h] * root32<T>(P::KR * K);  // w_M^(m0 + h + MS K), MS = KR M / 32
             else w = lw[MS * K + h];
             if (PAR) w = w * wq1;
             const cplx<T> zv = za[h][F::cpad(MS * K)];
@@ -1135,10 +1073,11 @@ __device__ __forceinline__ void post_steps_lin(const cplx<T>* const (&za)[FastCf
     }
 }
 
-template <typename T, int L, int PAR, typename Hook>
-__device__ __forceinline__ void fwdp_post_lin(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1,
-                                              cplx<T>* __restrict__ Tb, int nx, int i0, int rr, int bi,
-                                              const Hook& hook) {
+// hook(PassIdx<k>): called at the top of sweep step k (the kernel issues a slice of the next tile's loads there)
+template <typename T, int L, int PAR, typename Hook = NoPassHook>
+__device__ __forceinline__ void fwdp_post(const cplx<T>* zr, const cplx<T>* ltm, cplx<T> wq1,
+                                          cplx<T>* __restrict__ Tb, int nx, int i0, int rr, int bi,
+                                          const Hook& hook = Hook()) {
     using P = FwdP<T, L>;
     using F = typename P::F;
     constexpr int NVB = P::NVB, BS = P::BSTEP, MS = NVB * BS;
@@ -1192,7 +1131,7 @@ k_row_fwd_pow2q(const T* __restrict__ x, const T* __restrict__ beam, cplx<T>* __
                 const cplx<T>* __restrict__ ptwc, FastDims d, int band0, int tiles_per_band, int ntiles,
                 cplx<T> wq1) {
     using P = FwdP<T, L>;
-    constexpr int E = P::EOK;
+    constexpr int E = P::E;
     using F = RegFft<T, L, E, false, 0, true, false>;        // one transform at a time, twiddles from LDS
     constexpr int TPB = F::TPB, G = P::G, NT = P::NT, NP = F::NPASS;
     using V2 = typename vec2<T>::type;
@@ -1316,8 +1255,8 @@ __device__ __forceinline__ void row_inv_phase(PF&& after_loads_issued, const cpl
     cplx<T>* yr = lds0 + (size_t)rr * STRIDE;
     __syncthreads();                            // previous phase done with the LDS
     constexpr int NVB = FastCfg<T>::NVB;
-    constexpr int NBE = (L + NVB) / NVB;
-    constexpr int NBP = PAR ? L / NVB : NBE;
+    constexpr int NBE = nblocks_even(L, NVB);
+    constexpr int NBP = PAR ? nblocks_odd(L, NVB) : NBE;
     constexpr int BSTEP = NT / G;
     const cplx<T>* Tp = Tb + ((size_t)(PAR ? NBE : 0) * nx + i0 + rr) * NVB;
     // issue ALL strided loads of this thread before the first LDS write: a rolled loop
@@ -1474,7 +1413,17 @@ k_row_inv_pow2(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twQ,
 // 2 x 8192^2 fp64 1.644 -> 1.450, fp32 0.749 -> 0.679, with beam 0.720 -> 0.635; bit-identical results
 // (profiles/r03_ab_tile_rotation.md).  The forward rows and the column kernel show no such spread and no effect.
 constexpr int INV_ROT = 3;
-constexpr int INV_HOIST_B = 8;      // operand samples per batch of the HOIST epilogue (InvP::NXE)
+constexpr int INV_HOIST_B = 8;      // operand samples per batch of the batched epilogue (InvP::NXE)
+// The persistent tiles that exist (OK, with E = InvPE<T, L>::E) and what tells them apart:
+//   class             E   PARK OPF SMT NXT   next tile's even-bin pieces                 epilogue operands
+//   fp32 1024 / 2048   8    1    1   0   1    prefetched across the epilogue              prefetched into registers; even-bin result
+//                                                                                         parked in LDS; stores deferred
+//   fp64 1024 / 2048   8    0    1   0   1    prefetched across the epilogue              prefetched into registers; even-bin result
+//                                                                                         kept in registers
+//   fp64 4096         16    0    0   1   1    prefetched across the epilogue              read in place
+//   fp32 4096         16    0    0   1   0    requested behind the last operand batch     read in batches of INV_HOIST_B samples
+//                                             (beam + two inner products: at the top of
+//                                             the tile's own trip)
 template <typename T, int L, int E>
 struct InvP {
     using C = RowCfg<T, L, true>;
@@ -1483,46 +1432,40 @@ struct InvP {
     // fp64: two rows = 512 threads (the exchange buffers of four complex128 rows alone fill the LDS): with
     // one such workgroup per CU every thread may use 256 VGPRs, so the even-bin result stays in registers
     // (PARK = false) and the prefetched pieces / operands fit as well.
-    static constexpr bool PARK = sizeof(T) == 4 && E < 16;     // (E = 16: eight rows fill the LDS, the even-bin result stays in registers)
-    static constexpr int WG_PER_CU = 1;
+    static constexpr bool PARK = sizeof(T) == 4 && E < 16;     // (E = 16: four rows fill the LDS, the even-bin result stays in registers)
     static constexpr int G = (sizeof(T) == 4 ? 1024 : 512) / F::TPB;
     static constexpr int NT = G * F::TPB;
     static constexpr int STRIDE = F::LDS_ELEMS + 4;
     static constexpr int NVB = FastCfg<T>::NVB;
-    static constexpr int NBE = (L + NVB) / NVB;
-    static constexpr int NBO = L / NVB;
+    static constexpr int NBE = nblocks_even(L, NVB);
+    static constexpr int NBO = nblocks_odd(L, NVB);
     static constexpr int BSTEP = NT / G;
     static constexpr int NITE = (NBE + BSTEP - 1) / BSTEP;
     static constexpr int NITO = (NBO + BSTEP - 1) / BSTEP;
     static constexpr int PTWP = (F::PTWC + 1) & ~1;
-    // 4096-point fp32 rows (8192-pixel lines), 16 elements per thread, 4 rows: the exchange buffers of four rows leave no
-    // room for the full table w_M^n (32 KB) nor for the parked even-bin result.  SMT: only w_M^t, t < TPB, is kept and
+    // 16 elements per thread (4096-point rows): the exchange buffers of the tile's rows leave no room for the full table
+    // w_M^n (32 KB) nor for the parked even-bin result.  SMT: only w_M^t, t < TPB, is kept and
     // w_M^(t + TPB j) = w_M^t root32(j) (M = 2 L = 32 TPB).  OPF = false: the epilogue operands (x, dot_with2, beam) are
-    // NOT prefetched into registers (vv + ev + the strided pieces already take 100 of the 128) but read where they are
-    // used; what the persistent kernel still buys over the plain one are the tables loaded once and the strided pieces of
-    // the next phase / next tile in flight during every transform.
-    static constexpr bool SMT = E >= 16 && (L >= 4096 || sizeof(T) == 8);
+    // NOT prefetched into registers (fp32: vv + ev + the strided pieces already take 100 of the 128) but read where they
+    // are used; what the persistent kernel still buys over the plain one are the tables loaded once and the strided
+    // pieces of the next phase / next tile in flight during every transform.
+    static constexpr bool SMT = E >= 16;
     static constexpr bool OPF = E < 16;
     // NXT: the NEXT tile's even-bin pieces are requested during the odd-bin transform and stay in flight across the
     // epilogue (always with OPF; without it only where registers remain: the 512-thread fp64 tiles have 256).
     // 2 x 8192^2 fp64: 1.376 -> 1.195 ms (239 VGPRs, no scratch).  It had measured a tie (1.612 / 1.618) while one XCD set
-    // the pace of every variant (INV_ROT)
+    // the pace of every variant (INV_ROT).  With it the barrier between the odd-bin transform's last exchange and the
+    // next tile's scatter sits right behind that transform instead of at the top of the next trip (8 x 4096^2 fp32
+    // 0.6293 -> 0.6229 ms, 2 x 8192^2 fp64 1.673 -> 1.643); not without it -- there the barrier was the only thing the
+    // loads requested at the top of the trip were in flight across (0.706 -> 0.732)
     static constexpr bool NXT = OPF || sizeof(T) == 8;
-    // NXE: neither -- but the next tile's even-bin pieces are requested at the START of the epilogue (the transforms are
-    // over, their temporaries gone) instead of at the top of the next trip, where they were waited for right away
-    // (profiles/r03_q_phase_stamps_8192x2_*: 8.4 us of a 45 us trip).  Only for fp32: fp64 measured 1.955 vs 1.639 ms per
-    // 2 x 8192^2 (the pieces queue behind the epilogue's own loads).  The fp32 16-element tiles (4096-point rows) read their
-    // operand rows in batches of INV_HOIST_B samples and request the next tile's even-bin pieces behind the last batch:
-    // 2 x 8192^2 fp32 0.682 -> 0.665 ms (no change with beam)
-    static constexpr bool NXE = !NXT && sizeof(T) == 4;
-    // HOIST (fp32 NXE): all operand rows of the tile requested at once behind the combine loop (the even-bin result is dead
-    // by then), the next tile's even-bin pieces half way through the loop that consumes them, in the registers it has freed
-    static constexpr bool HOIST = NXE && sizeof(T) == 4;
-    // BARUP: the barrier between the odd-bin transform's last exchange and the next tile's scatter sits right behind that
-    // transform instead of at the top of the next trip (8 x 4096^2 fp32 0.6293 -> 0.6229 ms, 2 x 8192^2 fp64 1.673 -> 1.643); not
-    // for the fp32 tiles that request a tile's pieces at the top of its own trip -- there the barrier was the only thing
-    // those loads were in flight across (0.706 -> 0.732)
-    static constexpr bool BARUP = NXT || sizeof(T) == 8;
+    // NXE (the fp32 16-element tile, the only one without NXT): the operand rows are read in batches of INV_HOIST_B
+    // samples behind the combine loop (the even-bin result is dead by then), and the next tile's even-bin pieces are
+    // requested behind the last batch, in the registers the loop has freed, instead of at the top of the next trip,
+    // where they were waited for right away (profiles/r03_q_phase_stamps_8192x2_*: 8.4 us of a 45 us trip):
+    // 2 x 8192^2 fp32 0.682 -> 0.665 ms (no change with beam).  fp64 measured 1.955 vs 1.639 ms per 2 x 8192^2 with
+    // the request at the start of the epilogue (the pieces queue behind the epilogue's own loads)
+    static constexpr bool NXE = !NXT;
     static constexpr int NTM = SMT ? F::TPB : L;
     static constexpr size_t LDS = 384 + sizeof(cplx<T>) * ((size_t)PTWP + NTM + (size_t)G * STRIDE + (PARK ? (size_t)G * L : 0));
     static constexpr bool OK = odd_part(L) == 1 && LDS <= (size_t)LDS_MAX && !C::WAVE && (!SMT || 32 * F::TPB == 2 * L) &&
@@ -1545,10 +1488,23 @@ template <typename T, int L> struct InvPE {
 // the per-band variant (PB) of k_row_inv_pow2p exists for every persistent tile but the 4096-point fp32 one (SMT, 16
 // elements per thread): that tile is at the 128-VGPR cap already, and its per-band flush kept 20-136 B of scratch however
 // it was written.  There the launcher runs the whole-cube kernel once per band instead (launch_row_inv).
+// the rows of the table above InvP.  SMT = (E >= 16), NXE = !NXT, the barrier that moves with NXT and the batched
+// epilogue that comes with NXE were separate, type- and length-dependent flags once (commit 4085cbe) that coincide over
+// these classes: a new class that needs them apart does not compile until it has a row here
+template <typename T, int L>
+constexpr bool invp_class(int e, bool park, bool opf, bool smt, bool nxt) {
+    using P = InvP<T, L, InvPE<T, L>::E>;
+    return P::OK && InvPE<T, L>::E == e && P::PARK == park && P::OPF == opf && P::SMT == smt && P::NXT == nxt &&
+           P::NXE == !nxt && P::SMT == !opf && (nxt || sizeof(T) == 4);
+}
+static_assert(invp_class<float, 1024>(8, true, true, false, true) && invp_class<float, 2048>(8, true, true, false, true));
+static_assert(invp_class<double, 1024>(8, false, true, false, true) && invp_class<double, 2048>(8, false, true, false, true));
+static_assert(invp_class<double, 4096>(16, false, false, true, true) && invp_class<float, 4096>(16, false, false, true, false));
+
 template <typename T, int L, int E>
 constexpr bool inv_pb_ok() { return odd_part(L) == 1 && !(sizeof(T) == 4 && InvP<T, L, E>::SMT); }
 
-// strength-reduced addressing of the strided pieces (see fwdp_post_lin): the blocks of a thread are BSTEP apart, so the
+// strength-reduced addressing of the strided pieces (see fwdp_post): the blocks of a thread are BSTEP apart, so the
 // load address is a workgroup-uniform base (band, parity, step) + a 32-bit per-thread offset that never changes, and
 // the padded LDS index of the scatter is one base + compile-time offsets.  Regular whenever BSTEP divides the odd-bin
 // block count; the even bins then have exactly one more block (the Nyquist column), fetched by every thread in the last step.
@@ -1683,7 +1639,7 @@ __device__ __forceinline__ void inv_build(const cplx<T>* lds, const cplx<T>* ltm
 // visits.  The tiles of trip s are [s grid, (s + 1) grid) under the rotated map, so a workgroup's band never decreases
 // along its trips: one flush per band boundary it crosses.  PB = false compiles to the whole-cube kernel unchanged.
 template <typename T, int L, int E, int MODE, bool BEAM, bool PB = false>
-__global__ void __launch_bounds__((InvP<T, L, E>::NT), (InvP<T, L, E>::NT / 256 * InvP<T, L, E>::WG_PER_CU))
+__global__ void __launch_bounds__((InvP<T, L, E>::NT), (InvP<T, L, E>::NT / 256))
 k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 const cplx<T>* __restrict__ ptw, const T* __restrict__ x, const T* __restrict__ beam,
                 const T* __restrict__ dot_with2, T* __restrict__ out,
@@ -1694,8 +1650,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
     constexpr int TPB = F::TPB, G = P::G, NT = P::NT;
     // (the batched-operand variant of the fp32 16-element tiles keeps 12 B of scratch with beam + two inner products: that
     // instantiation stays on the plain order -- a tile's pieces requested at the top of its own trip)
-    constexpr bool NXEK = P::NXE && !(P::HOIST && BEAM && MODE == 2), HOISTK = P::HOIST && NXEK;
-    constexpr bool NXTK = P::NXT;
+    constexpr bool BATCH = P::NXE && !(BEAM && MODE == 2);
     constexpr int NP = F::NPASS, NPA = NP / 2 > 0 ? NP / 2 : 1, NPB = NP - NPA > 0 ? NP - NPA : 1;
     using V2 = typename vec2<T>::type;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1709,14 +1664,12 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
     for (int k = threadIdx.x; k < F::PTWC; k += NT) ltw[k] = ptw[k];
     for (int k = threadIdx.x; k < P::NTM; k += NT) ltm[k] = twM[k];
     constexpr int SH = 128 / (G * (int)sizeof(cplx<T>) * P::NVB) > 1 ? 128 / (G * (int)sizeof(cplx<T>) * P::NVB) : 1;
+    // (xcd_line_pair with its condition evaluated here, once: tested inside `tile` the kernel compiles to another schedule)
     const bool pairing = SH > 1 && (tiles_per_band % (8 * SH)) == 0;
     auto tile = [&](int v, int& bl, int& i0) {
         bl = v / tiles_per_band;
         int rg = v - bl * tiles_per_band;
-        if (pairing) {                      // see k_row_inv_pow2: blocks b, b+8, .. share an XCD's L2: give
-            const int q = rg / (8 * SH), rem = rg % (8 * SH);       // THEM the SH pieces of one 128-byte line
-            rg = SH * (q * 8 + (rem & 7)) + (rem >> 3);
-        }
+        if (pairing) rg = xcd_paired(rg, SH);
         i0 = rg * G;
     };
     int bl, i0;
@@ -1724,7 +1677,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
     Blk<T, P::NVB> y[P::NITE];
     // OPF kernels keep the NEXT tile's even-bin pieces in flight across the epilogue; without the registers for that
     // (!OPF: 16 elements per thread) a tile's even-bin pieces are requested at the top of its own trip instead
-    if constexpr (NXTK || NXEK)
+    if constexpr (P::NXT || BATCH)
         inv_issue<T, L, E, 0>(Tw + (size_t)(band0 + bl) * d.T_band, d.nx, i0, threadIdx.x % G, threadIdx.x / G, y);
     double acc[3] = {0.0, 0.0, 0.0};
     if constexpr (PB && MODE >= 1) {      // every slot of this workgroup starts at zero: a band it never visits reads 0
@@ -1747,7 +1700,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
         int bln, i0n;
         tile(vbn, bln, i0n);
         const cplx<T>* Tb = Tw + (size_t)(band0 + bl) * d.T_band;
-        if constexpr (!NXTK && !NXEK) {
+        if constexpr (!P::NXT && !BATCH) {
             const int tid = launder((int)threadIdx.x);
             inv_issue<T, L, E, 0>(Tb, d.nx, i0, tid % G, tid / G, y);
         }
@@ -1759,7 +1712,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             const int tid = launder((int)threadIdx.x);
             const int g = tid / TPB, t = tid % TPB, rr = tid % G, bi = tid / G;
             cplx<T>* lds = lds0 + (size_t)g * P::STRIDE;
-            if (!P::BARUP || sit == 0) __syncthreads();      // (BARUP: the barrier that protects lds0 sits behind the odd-bin transform)
+            if (!P::NXT || sit == 0) __syncthreads();        // (NXT: the barrier that protects lds0 sits behind the odd-bin transform)
             STAMP(2, sit, 1);
             inv_scatter<T, L, E, 0>(y, lds0 + (size_t)rr * P::STRIDE, bi);
             STAMP(2, sit, 2);
@@ -1830,7 +1783,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                         constexpr int KK = K - NPA;
                         inv_issue_slice<T, L, E, 0, (KK * P::NITE) / NPB, ((KK + 1) * P::NITE) / NPB>(Tbn, d.nx, i0n, rr, bi, y);
                     }
-                } else if constexpr (NXTK) {
+                } else if constexpr (P::NXT) {
                     inv_issue_slice<T, L, E, 0, (K * P::NITE) / NP, ((K + 1) * P::NITE) / NP>(Tbn, d.nx, i0n, rr, bi, y);
                 }
             });
@@ -1838,11 +1791,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
             // the last exchange's readers are done BEFORE the epilogue instead of at the top of the next trip: the waves are
             // still in step here (cheap), and a wave that is through with its epilogue scatters the next tile's pieces while
             // the others finish theirs -- the skew is absorbed by the barrier behind the scatter
-            if constexpr (P::BARUP) __syncthreads();
-        }
-        if constexpr (NXEK && !HOISTK) {
-            const int tid = launder((int)threadIdx.x);
-            inv_issue<T, L, E, 0>(Tw + (size_t)(band0 + bln) * d.T_band, d.nx, i0n, tid % G, tid / G, y);
+            if constexpr (P::NXT) __syncthreads();
         }
         // ---- z[n] = e[n] + conj(w_M^n) o[n] ;  y[2n] = Re z, y[2n+1] = Im z
         {
@@ -1865,7 +1814,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 for (int j = 0; j < E; ++j) vv[j] = ev[j] + mulc(vv[j], P::tw_row(ltm, t, j));
                 __builtin_amdgcn_sched_barrier(0);
             }
-            [[maybe_unused]] V2 xh[HOISTK ? E : 1], rh[(HOISTK && MODE == 2) ? E : 1], bh[(HOISTK && BEAM) ? E : 1];
+            [[maybe_unused]] V2 xh[BATCH ? E : 1], rh[(BATCH && MODE == 2) ? E : 1], bh[(BATCH && BEAM) ? E : 1];
 
 #pragma unroll
             for (int j = 0; j < E; ++j) {
@@ -1876,7 +1825,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                     if constexpr (P::PARK) e0 = park[j * NT + tid]; else e0 = ev[j];
                     zz = e0 + mulc(vv[j], P::tw_row(ltm, t, j));
                 }
-                if constexpr (HOISTK) {
+                if constexpr (BATCH) {
                     // operand rows in batches of HB samples; behind the LAST batch the next tile's even-bin pieces (in order:
                     // nothing the epilogue still waits for is queued behind them)
                     constexpr int HB = INV_HOIST_B;
@@ -1897,7 +1846,7 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 V2 xx;
                 [[maybe_unused]] V2 bb;
                 if constexpr (OPF) { xx = xq[j]; if constexpr (BEAM) bb = bq[j]; }
-                else if constexpr (HOISTK) { xx = xh[j]; if constexpr (BEAM) bb = bh[j]; }
+                else if constexpr (BATCH) { xx = xh[j]; if constexpr (BEAM) bb = bh[j]; }
                 else { xx = xr_e[TPB * j]; if constexpr (BEAM) bb = br_e[TPB * j]; }
                 if constexpr (BEAM) {
                     val.x = zz.x * scale * bb.x + sigmainv * xx.x;
@@ -1909,12 +1858,12 @@ k_row_inv_pow2p(const cplx<T>* __restrict__ Tw, const cplx<T>* __restrict__ twM,
                 if constexpr (P::PARK) ov[j] = val; else orow[TPB * j] = val;
                 // operands read in place (!OPF): a few samples at a time, or every x / dot_with2 load of the tile is
                 // hoisted to the top of the loop and spills
-                if constexpr (!OPF && !HOISTK) { if (sizeof(T) == 4 && (j & 3) == 3) __builtin_amdgcn_sched_barrier(0); }
+                if constexpr (!OPF && !BATCH) { if (sizeof(T) == 4 && (j & 3) == 3) __builtin_amdgcn_sched_barrier(0); }
                 if constexpr (MODE >= 1) {
                     acc[0] += (double)xx.x * (double)val.x + (double)xx.y * (double)val.y;
                     if constexpr (MODE == 2) {
                         V2 d2;
-                        if constexpr (OPF) d2 = rq[j]; else if constexpr (HOISTK) d2 = rh[j];
+                        if constexpr (OPF) d2 = rq[j]; else if constexpr (BATCH) d2 = rh[j];
                         else d2 = dr_e[TPB * j];
                         acc[1] += (double)d2.x * (double)val.x + (double)d2.y * (double)val.y;
                     }
@@ -2132,9 +2081,9 @@ template <typename T, int H> struct ColKernels {
     }
     // all of them, f(kernel)
     template <typename Fn> static void all(Fn&& f) {
-        // (the plain kernel is launched only where KIND is Plain; it stays instantiated for every H: the kernels of one
-        // object share their transforms' code, and the object's kernel set is the one all measurements were taken with)
-        f(plain());
+        // (the plain kernel exists only where it is launched: without its six never-launched instantiations of the
+        // persistent and two-level classes every other kernel of the object compiles to the same instructions)
+        if constexpr (C::KIND == ColKind::Plain) f(plain());
         f(fwd());
         serving([&](auto* k, bool) { f(k); });
         // KEPT INSTANTIATED, NEVER LAUNCHED: k_col_pow2x<double, 4096> -- the one-level kernel serves 4096-point columns -- shares
@@ -2186,7 +2135,7 @@ static int launch_col_fwd(pfb_conv_plan* p, const FastTables* ft, const void* Tq
     using C = ColCfg<T, H>;
     using CK = ColKernels<T, H>;
     const int L = p->ny / 2;
-    const int nblk = fast_nblocks(L, C::NVB), nbe = (L + C::NVB) / C::NVB;
+    const int nblk = fast_nblocks(L, C::NVB), nbe = nblocks_even(L, C::NVB);
     hipLaunchKernelGGL(CK::fwd(), dim3((nblk + C::GC1 - 1) / C::GC1), dim3(C::NT1), C::XB1, st,
                        (const cplx<T>*)Tq, (cplx<T>*)p->psf_l + (size_t)band * p->psf_elems_per_band,
                        (const cplx<T>*)p->twP, (const cplx<T>*)ft->tab[PTW_COL], nblk, nbe, p->T_elems_per_band,
@@ -2229,7 +2178,7 @@ template <typename T, int L> constexpr bool fwdp_ok() {
 template <typename T, int L> struct RowFwdK {
     using FP = FwdP<T, L>;
     static constexpr bool PERSISTENT = fwdp_ok<T, L>();
-    static constexpr int E = [] { if constexpr (PERSISTENT) return FP::EOK; else return RowCfg<T, L, false>::E; }();
+    static constexpr int E = [] { if constexpr (PERSISTENT) return FP::E; else return RowCfg<T, L, false>::E; }();
     static constexpr auto plain() { return k_row_fwd_pow2<T, L, E>; }
     // the instantiations launch_row_fwd can reach: f(kernel, beam) (the plain kernel takes `beam` at run time)
     template <typename Fn> static void reachable(Fn&& f) {
@@ -2312,7 +2261,7 @@ static int launch_row_fwd(pfb_conv_plan* p, const FastTables* ft, void* Tbuf, in
         // persistent kernel: parities in sequence, next rows requested inside the second transform
         using FP = typename K::FP;
         const int tiles_per_band = p->nx / FP::G, ntiles = tiles_per_band * nb;
-        const int grid = ntiles < ft->num_cu * FP::WG_PER_CU ? ntiles : ft->num_cu * FP::WG_PER_CU;
+        const int grid = ntiles < ft->num_cu ? ntiles : ft->num_cu;            // one resident workgroup per CU
         const cplx<T> wq1 = wq1_of<T>(p);
         K::reachable([&](auto* k, bool bm) {
             if (bm != (beam != nullptr)) return;
@@ -2359,7 +2308,7 @@ static int launch_row_inv(pfb_conv_plan* p, const FastTables* ft, const ApplyArg
             };
             const int mode = !a.dot_with ? 0 : !a.dot_with2 ? 1 : 2;
             const int tiles_per_band = p->nx / IP::G, ntiles = tiles_per_band * nb;
-            int grid = ntiles < IP::WG_PER_CU * ft->num_cu ? ntiles : IP::WG_PER_CU * ft->num_cu;
+            int grid = ntiles < ft->num_cu ? ntiles : ft->num_cu;                  // one resident workgroup per CU
             if (a.per_band && a.dot_with) {
                 if constexpr (K::PER_BAND) {
                     if (a.dot_with2) {            // one launch, partials [3][nb][grid]
@@ -2371,7 +2320,7 @@ static int launch_row_inv(pfb_conv_plan* p, const FastTables* ft, const ApplyArg
                 }
                 // the whole-cube kernel once per band (the same launches a band-by-band solve makes): band bl's
                 // partials land at [bl][3][grid1]
-                const int grid1 = tiles_per_band < IP::WG_PER_CU * ft->num_cu ? tiles_per_band : IP::WG_PER_CU * ft->num_cu;
+                const int grid1 = tiles_per_band < ft->num_cu ? tiles_per_band : ft->num_cu;
                 const size_t bandel = (size_t)p->nx * p->ny;
                 for (int bl = 0; bl < nb; ++bl)
                     launch(mode, false, band0 + bl, 1, grid1, bl * bandel, p->partials + (size_t)bl * 3 * grid1);

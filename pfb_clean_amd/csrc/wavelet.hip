@@ -387,131 +387,13 @@ __device__ __forceinline__ void dwt_tile(T* smem, const T* __restrict__ flo, con
                                          const T* __restrict__ src, int ldin, int nxin, int nyin,
                                          T* __restrict__ dst, int ldc, int Cx, int Cy, T* __restrict__ approx,
                                          int ox0, int oy0) {
-    constexpr int VW0 = 16 / (int)sizeof(T);
-    if (ldin % VW0 == 0 && nyin % VW0 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && TA % (2 * VW0) == 0) {
-        dwt_tile_fast<T, F, TA, true>(smem, flo, fhi, src, ldin, nxin, nyin, dst, ldc, Cx, Cy, approx, ox0, oy0);
-        return;
-    }
-    if constexpr (TA % (2 * VW0) == 0 && (2 * TA + F - 2) / 2 <= 64) {
-        dwt_tile_fast<T, F, TA, false>(smem, flo, fhi, src, ldin, nxin, nyin, dst, ldc, Cx, Cy, approx, ox0, oy0);
-        return;
-    }
-    constexpr int NI = 2 * TA + F - 2;        // input samples per tile edge
-    // Both passes decimate by two (index 2q + d): with a plain row the 32 lanes of a half-wave touch only 16
-    // banks (2-way conflicts, 46 % of the LDS-busy cycles in rocprofv3).  A and B are therefore stored
-    // PARITY-SPLIT along the decimated axis -- even samples / rows first, odd ones AO / BO elements later --
-    // so that a tap of fixed parity walks consecutive addresses.
-    constexpr int SA = NI / 2;                // samples of one parity per tile row (NI is even)
-    constexpr int AO = NI * SA;               // offset of the odd-sample half of A
-    constexpr int SB = 2 * TA + 1;
-    constexpr int BO = (NI / 2) * SB;         // offset of the odd-row half of B
-    T* A = smem;                              // [NI][SA]   input tile  A[lx][ly]
-    T* B = A + 2 * AO;                        // [NI][SB]   after the y pass  B[lx][q] (rows parity-split)
-    T* LL = A;                                // [TA][TA+1] LL quadrant for the approx copy: aliases A, which is dead
-                                              // after the y pass (42 -> 38 KB at F = 8: four workgroups per CU, not three)
-    const int gx0 = 2 * ox0 + 1 - (F - 1), gy0 = 2 * oy0 + 1 - (F - 1);
-    T lo[F], hi[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) { lo[j] = flo[j]; hi[j] = fhi[j]; }
-    // 1. stage the input tile (zero extension outside the signal)
     constexpr int VW = 16 / (int)sizeof(T);                      // elements per 16-byte access
-    if (ldin % VW == 0 && nyin % VW == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-        // rows are 16-byte aligned (the finest level of an image whose width is a multiple of 4):
-        // aligned 16-byte loads of a slightly wider window -- 4x fewer load instructions, and every
-        // vector lies entirely inside or entirely outside [0, nyin)
-        struct alignas(16) Vec { T e[VW]; };
-        const int ga = gy0 - (((gy0 % VW) + VW) % VW);           // window start, rounded down
-        constexpr int NWV = (NI + 2 * (VW - 1) + VW - 1) / VW;   // vectors per tile row (upper bound)
-        constexpr int NLV = (NI * NWV + 255) / 256;
-        Vec stage[NLV];
-#pragma unroll
-        for (int k = 0; k < NLV; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int lx = e / NWV, w = e - lx * NWV;
-            const int gx = gx0 + lx, gy = ga + VW * w;
-            Vec v;
-#pragma unroll
-            for (int c = 0; c < VW; ++c) v.e[c] = 0;
-            if (e < NI * NWV && gx >= 0 && gx < nxin && gy >= 0 && gy < nyin)
-                v = *reinterpret_cast<const Vec*>(src + (size_t)gx * ldin + gy);
-            stage[k] = v;
-        }
-#pragma unroll
-        for (int k = 0; k < NLV; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int lx = e / NWV, w = e - lx * NWV;
-            const int ly0 = ga - gy0 + VW * w;
-            if (e < NI * NWV) {
-#pragma unroll
-                for (int c = 0; c < VW; ++c)
-                    if (ly0 + c >= 0 && ly0 + c < NI) A[((ly0 + c) & 1) * AO + lx * SA + ((ly0 + c) >> 1)] = stage[k].e[c];
-            }
-        }
-    } else {
-        constexpr int NLD = (NI * NI + 255) / 256;
-        T stage[NLD];
-#pragma unroll
-        for (int k = 0; k < NLD; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int lx = e / NI, ly = e - lx * NI;
-            const int gx = gx0 + lx, gy = gy0 + ly;
-            T v = 0;
-            if (e < NI * NI && gx >= 0 && gx < nxin && gy >= 0 && gy < nyin) v = src[(size_t)gx * ldin + gy];
-            stage[k] = v;
-        }
-#pragma unroll
-        for (int k = 0; k < NLD; ++k) {
-            const int e = threadIdx.x + 256 * k;
-            const int lx = e / NI, ly = e - lx * NI;
-            if (e < NI * NI) A[(ly & 1) * AO + lx * SA + (ly >> 1)] = stage[k];
-        }
-    }
-    __syncthreads();
-    // 2. y pass: B[lx][q] = sum_j filt[j] A[lx][2q' + F-1-j]   (q < TA: lo, q >= TA: hi)
-    for (int e = threadIdx.x; e < NI * TA; e += 256) {
-        const int lx = e / TA, qq = e - lx * TA;
-        const T* a = A + lx * SA + qq;
-        T sl = 0, sh = 0;
-#pragma unroll
-        for (int j = 0; j < F; ++j) {                          // sample 2 qq + d, d = F-1-j
-            const int d = F - 1 - j;
-            const T v = a[(d & 1) * AO + (d >> 1)];
-            sl += lo[j] * v; sh += hi[j] * v;
-        }
-        T* brow = B + (lx & 1) * BO + (lx >> 1) * SB;
-        brow[qq] = sl;
-        brow[TA + qq] = sh;
-    }
-    __syncthreads();
-    // 3. x pass + store: out[r][c], r < 2TA (y coefficient, lo|hi), c (x coefficient) lo & hi
-    for (int e = threadIdx.x; e < 2 * TA * TA; e += 256) {
-        const int r = e / TA, cc = e - r * TA;
-        const T* b = B + cc * SB + r;
-        T sl = 0, sh = 0;
-#pragma unroll
-        for (int j = 0; j < F; ++j) {                          // row 2 cc + d, d = F-1-j
-            const int d = F - 1 - j;
-            const T v = b[(d & 1) * BO + (d >> 1) * SB];
-            sl += lo[j] * v; sh += hi[j] * v;
-        }
-        const bool hiy = r >= TA;
-        const int rr = hiy ? r - TA : r;
-        const int gy = oy0 + rr, gx = ox0 + cc;
-        if (gy < Cy && gx < Cx) {
-            T* row = dst + (size_t)((hiy ? Cy : 0) + gy) * ldc;
-            row[gx] = sl;
-            row[Cx + gx] = sh;
-        }
-        if (!hiy) LL[cc * (TA + 1) + rr] = sl;
-    }
-    if (approx) {
-        __syncthreads();
-        T* ap = approx;
-        for (int e = threadIdx.x; e < TA * TA; e += 256) {
-            const int cc = e / TA, rr = e - cc * TA;           // rr (y) fastest: coalesced
-            if (ox0 + cc < Cx && oy0 + rr < Cy) ap[(size_t)(ox0 + cc) * Cy + oy0 + rr] = LL[cc * (TA + 1) + rr];
-        }
-    }
+    static_assert(TA % (2 * VW) == 0 && (2 * TA + F - 2) / 2 <= 64, "the staged tile serves every tile edge and filter");
+    // rows 16-byte aligned (the finest level of an image whose width is a multiple of 4): aligned 16-byte loads
+    if (ldin % VW == 0 && nyin % VW == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0)
+        dwt_tile_fast<T, F, TA, true>(smem, flo, fhi, src, ldin, nxin, nyin, dst, ldc, Cx, Cy, approx, ox0, oy0);
+    else
+        dwt_tile_fast<T, F, TA, false>(smem, flo, fhi, src, ldin, nxin, nyin, dst, ldc, Cx, Cy, approx, ox0, oy0);
 }
 
 template <typename T, int TA, int FMAX>
@@ -1078,14 +960,9 @@ k_idwt_batched2(const T* __restrict__ alpha, size_t aband, int ldc, const T* __r
                                  P.nxw, P.nyw, ix0, iy0);
 }
 
+// dynamic LDS of k_dwt_batched for filters up to F taps (dwt_tile_fast)
 template <typename T>
-static size_t dwt_lds(int F) {
-    constexpr int TA = Tile<T>::TA;
-    const int NI = 2 * TA + F - 2;
-    const size_t plain = (size_t)NI * (NI + 1) + (size_t)NI * (2 * TA + 1);       // dwt_tile's non-register-blocked tile (LL aliases A)
-    const size_t fast = DwtFast<T>::elems(TA, F);                                // dwt_tile_fast
-    return sizeof(T) * (plain > fast ? plain : fast);
-}
+static size_t dwt_lds(int F) { return sizeof(T) * DwtFast<T>::elems(Tile<T>::TA, F); }
 
 // the batched kernels exist for FMAX = 8 and 18 (longest filter they hold): launch the one the plan `p` needs, block
 // 256, on stream `st`
@@ -1213,8 +1090,7 @@ static int psi_dot_t(const pfb_psi_plan* p, const T* x, T* alpha, hipStream_t st
     constexpr int TA = Tile<T>::TA;
     // finest level of all bases (and the first 'self' plane) in one kernel when the image rows are 16-byte aligned
     constexpr int VW = 16 / (int)sizeof(T);
-    const bool l1_fused = p->nwb > 0 && p->ny % VW == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                          TA % (2 * VW) == 0;
+    const bool l1_fused = p->nwb > 0 && p->ny % VW == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     long long self_off = -1;
     for (int ib = 0; ib < p->nbasis; ++ib) {
         if (p->bases[ib].K != 0) continue;

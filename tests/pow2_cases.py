@@ -271,23 +271,17 @@ class FwdP:
     def __init__(self, dtype, L):
         cs, nvb = CSZ[dtype], NVB[dtype]
         self.BIG = L >= 4096
-        self.E = 16 if self.BIG else L // 128
-        self.EOK = self.E if self.E in (8, 16) else 8
-        f = RegFft(dtype, L, self.EOK)
-        self.TPR = L // self.EOK
-        self.NT = 512 if self.BIG and dtype == F64 else 1024
+        self.E = 16 if L >= 2048 else 8
+        f = RegFft(dtype, L, self.E)
+        self.TPR = L // self.E
+        self.NT = 1024
         self.G = self.NT // self.TPR
-        self.WG_PER_CU = 1
-        if self.G == 0:                                    # (never instantiated by the library: OK is false)
-            self.OK = False
-            return
         self.BSTEP = self.NT // self.G
-        self.SMT = self.BIG
-        self.NTM = nvb * self.BSTEP if self.SMT else L
+        self.NTM = nvb * self.BSTEP if self.BIG else L
         self.LDS = cs * (f.PTWP + self.NTM + self.G * (f.LDS_ELEMS + 4))
         self.KR = (32 * nvb * self.BSTEP) // (2 * L)
         self.OK = (self.E == 16 and self.LDS <= LDS_MAX and not (self.BIG and dtype == F64) and
-                   (not self.SMT or (self.EOK == 16 and 32 * self.TPR == 2 * L and self.KR * 2 * L == 32 * nvb * self.BSTEP
+                   (not self.BIG or (32 * self.TPR == 2 * L and self.KR * 2 * L == 32 * nvb * self.BSTEP
                                      and self.NTM >= self.TPR)))
         self.SH = 8 // self.G                              # FwdP::tile_row: SH
 
@@ -306,10 +300,9 @@ class InvP:
         c = RowCfg(dtype, L, True)
         f = RegFft(dtype, L, E)
         self.PARK = dtype == F32 and E < 16
-        self.WG_PER_CU = 1
         self.G = (1024 if dtype == F32 else 512) // f.TPB
         self.NT = self.G * f.TPB
-        self.SMT = E >= 16 and (L >= 4096 or dtype == F64)
+        self.SMT = E >= 16
         self.NTM = f.TPB if self.SMT else L
         self.LDS = 384 + cs * (f.PTWP + self.NTM + self.G * (f.LDS_ELEMS + 4) + (self.G * L if self.PARK else 0))
         size_ok = (self.NT == 1024 and 4 <= self.G <= 16) if dtype == F32 else (self.NT == 512 and self.G in (2, 4) and L >= 1024)
@@ -319,12 +312,12 @@ class InvP:
 
 
 def pairing(SH, tiles_per_band):
-    """FwdP::tile_row, k_row_inv_pow2p `pairing`, xcd_row_group: the XCD piece pairing is on"""
+    """xcd_line_pair (FwdP::tile_row, xcd_row_group) and k_row_inv_pow2p `pairing`: the XCD piece pairing is on"""
     return SH > 1 and tiles_per_band % (8 * SH) == 0
 
 
 def tile_row(rg, tiles_per_band, SH, G):
-    """FwdP::tile_row / the `tile` lambda of k_row_inv_pow2p: tile rg of a band -> its first image row"""
+    """FwdP::tile_row / the `tile` lambda of k_row_inv_pow2p (xcd_paired): tile rg of a band -> its first image row"""
     if pairing(SH, tiles_per_band):
         q, rem = divmod(rg, 8 * SH)
         rg = SH * (q * 8 + (rem & 7)) + (rem >> 3)
@@ -338,7 +331,7 @@ class RowFwd:
         fp = FwdP(dtype, L)
         self.dtype, self.L, self.PERSISTENT = dtype, L, fp.OK
         if fp.OK:
-            self.E, self.G, self.SH, self.wg_per_cu = fp.EOK, fp.G, fp.SH, fp.WG_PER_CU
+            self.E, self.G, self.SH, self.wg_per_cu = fp.E, fp.G, fp.SH, 1     # one resident workgroup per CU
         else:
             c = RowCfg(dtype, L, False)
             self.E, self.G, self.wg_per_cu = c.E, row_groups(dtype, L, c.E, c.GMAX), 0
@@ -410,7 +403,7 @@ class RowInv:
             ip = self.ip
             mode = 0 if dw is None else 1 if dw2 is None else 2
             tpb = nx // ip.G
-            ntiles, cap = tpb * nb, ip.WG_PER_CU * ncu
+            ntiles, cap = tpb * nb, ncu                                      # one resident workgroup per CU
             grid = min(ntiles, cap)
             if entry == 'bands' and dw:
                 if self.PER_BAND and dw2:

@@ -2,10 +2,10 @@
 The case table of tests/test_gpu_pow2_edges.py (tests/pow2_cases.py), checked on the CPU:
 
   * the mirror of the launch bookkeeping reproduces the constants of csrc/fftconv_pow2.hip and the grids its comments
-    quote.  The constants are the tables COL and ROW below, printed once from the source's own constexprs by a host
-    program that included the file.  Nothing ties the tables to the .hip file: a change of a tile, of elements per thread
-    or of an LDS size there does not fail this module until the tables are printed again -- it makes the mirror, and with
-    it the properties the cases are chosen by, describe the library as it was;
+    quote.  The constants are the tables COL, ROW and FWDP_LDS below, and test_tables_are_the_source_constants ties them
+    to the .hip file: it writes a translation unit that includes the file and holds one static_assert per table entry
+    against the source's own constexprs, and has hipcc check it (host side, syntax only).  A change of a tile, of
+    elements per thread or of an LDS size there fails that test until table and mirror follow;
   * every case has the property it exists for at 256 CUs and at 304: the band-count rule follows the CU count;
   * the coverage matrices built from the table have no empty cell:
       columns      {persistent, two-level} x {fp32, fp64} x {single trip, second trip, inactive slot, band crossing, band
@@ -26,6 +26,10 @@ class (1024-point rows) is 8 tiles and 5 MB in T, psf_l, x and out, so that even
 These cases, the column trips and the non-temporal cases (200 MiB of PSF by definition) are held to 512 MB, the three-trip
 row cases (more than two tiles per CU: 513 tiles and more) to 768 MB; the largest is 693 MB.  Every case is run.
 """
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -38,7 +42,7 @@ F32, F64 = pc.F32, pc.F64
 CUS = (256, 304)
 ids = [c.id for c in pc.CASES]
 
-# the source's constexprs, printed once by a host program that includes csrc/fftconv_pow2.hip:
+# the source's constexprs (test_tables_are_the_source_constants):
 # (format, H) -> ColCfg::E1, KIND, DB and shape(): gc, threads, lds, wg_per_cu
 COL = {(F32, 64): (4, 'plain', False, 16, 256, 20480, 0), (F32, 96): (12, 'plain', False, 32, 256, 59392, 0),
        (F32, 128): (4, 'plain', False, 8, 256, 20480, 0), (F32, 256): (4, 'plain', False, 4, 256, 20480, 0),
@@ -89,6 +93,39 @@ def test_mirror_reproduces_the_source_constants():
             assert pc.FwdP(d, L).LDS == FWDP_LDS[(d, L)]
     assert set(ROW) == {(d, L) for d in pc.DTYPES for L in pc.row_lengths(d)}
     assert pc.fast_nblocks(64, 2) == 65 and pc.fast_nblocks(64, 1) == 129 and pc.fast_nblocks(2048, 2) == 2049
+
+
+def test_tables_are_the_source_constants(tmp_path):
+    """COL, ROW and FWDP_LDS against csrc/fftconv_pow2.hip itself: one static_assert per entry, compiled on the host side."""
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    if not os.path.exists(hipcc):
+        pytest.skip('no hipcc: the tables cannot be compiled against csrc/fftconv_pow2.hip')
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'pfb_clean_amd', 'csrc')
+    ty = {F32: 'float', F64: 'double'}
+    kind = {'plain': 'Plain', 'persistent': 'Persistent', 'twolevel': 'TwoLevel'}
+    b = {False: 'false', True: 'true'}
+    tu = ['#define PFB_POW2_PART 1', '#include "fftconv_pow2.hip"', 'namespace pfb {',
+          'template <typename T, int L, bool INVK> constexpr int plain_rows() {',
+          '    return row_groups<T, L, RowCfg<T, L, INVK>::E, RowCfg<T, L, INVK>::GMAX>(); }',
+          'template <typename T, int L> constexpr int fwd_rows() {',
+          '    if constexpr (RowFwdK<T, L>::PERSISTENT) return FwdP<T, L>::G; else return plain_rows<T, L, false>(); }']
+    for (d, H), (e1, k, db, gc, nt, lds, wg) in COL.items():
+        c = f'ColCfg<{ty[d]}, {H}>'
+        tu.append(f'static_assert({c}::E1 == {e1} && {c}::KIND == ColKind::{kind[k]} && {c}::DB == {b[db]} && '
+                  f'{c}::shape().gc == {gc} && {c}::shape().threads == {nt} && {c}::shape().lds == {lds} && '
+                  f'{c}::shape().wg_per_cu == {wg}, "COL {d} {H}");')
+    for (d, L), ((fp, fe, fg), (ip, ipb, ie, iep, ig, ipg, ilds)) in ROW.items():
+        a, f, i = f'{ty[d]}, {L}', f'RowFwdK<{ty[d]}, {L}>', f'RowInvK<{ty[d]}, {L}>'
+        tu.append(f'static_assert({f}::PERSISTENT == {b[fp]} && {f}::E == {fe} && fwd_rows<{a}>() == {fg}, "ROW fwd {d} {L}");')
+        tu.append(f'static_assert({i}::PERSISTENT == {b[ip]} && {i}::PER_BAND == {b[ipb]} && {i}::E == {ie} && {i}::EP == {iep} && '
+                  f'plain_rows<{a}, true>() == {ig} && {i}::IP::G == {ipg} && {i}::IP::LDS == {ilds}, "ROW inv {d} {L}");')
+    for (d, L), lds in FWDP_LDS.items():
+        tu.append(f'static_assert(FwdP<{ty[d]}, {L}>::OK && FwdP<{ty[d]}, {L}>::LDS == {lds}, "FWDP_LDS {d} {L}");')
+    src = tmp_path / 'pow2_tables.hip'
+    src.write_text('\n'.join(tu + ['}', '']))
+    r = subprocess.run([hipcc, '-std=c++17', '--offload-arch=gfx950', '--offload-host-only', '-fsyntax-only', '-I', csrc, str(src)],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-4000:]
 
 
 def test_mirror_reproduces_the_grids_the_source_quotes():
