@@ -690,6 +690,80 @@ int pfb_mask_close(int dtype, const void* cube, int nband, const unsigned char* 
 int pfb_masked_problem(int dtype, const void* residual, const unsigned char* mask, const void* beam, int nband_beam,
                        const void* seed, int nband, size_t npix, void* b, void* x0, void* beam_eff, void* stream);
 
+/* ------------------------------------------------------------------------- w-gridder
+ * pfb/operators/hessian.py:62-106 (_hessian_impl): ducc0's dirty2vis and vis2dirty, defined by the direct Fourier sums
+ *   (u, v, w) = uvw[r] * freq[k] / 299792458,  l_i = (i - nx/2) pixsize_x + center_x,  m_j likewise,
+ *   nm1 = -(l^2 + m^2) / (1 + sqrt(1 - l^2 - m^2))   (0 without w-gridding),   phase = u l + v m - w nm1,
+ *   vis2dirty: dirty[i,j] = f_ij sum_{mask != 0} Re(wgt vis exp(+2 pi i phase)),
+ *   dirty2vis: vis[r,k]   = wgt sum_ij f_ij dirty[i,j] exp(-2 pi i phase), 0 where mask == 0,
+ * evaluated by w-stacking on a (2 nx, 2 ny) grid with the kernel exp(2.3 W (sqrt(1 - x^2) - 1)) of `support` = W cells
+ * (DESIGN 4.10).  The additive family leaves PFB_ABI_VERSION at 1, like every family added since the first.
+ *
+ * A plan is a host record of the geometry: it owns no device memory, launches nothing on creation and is immutable, so
+ * one plan may serve any number of streams; the single-owner rule applies to the caller's arrays (grid, acc, val, img).
+ * The caller owns, as device arrays:
+ *   keys   (nrow * nchan) int: the sort key of a visibility, -1 where masked;
+ *   work   pfb_wgrid_work_bytes(plan) bytes, 4-byte aligned: the key histogram (nkeys ints, which the caller scans
+ *          into `offsets`, nkeys exclusive prefix sums as int64) and the placement cursors behind it;
+ *   idx    (nsorted) int: visibility r * nchan + k of a slot;  coord (3, nsorted) double: its position in grid cells
+ *          (u pixsize_x 2 nx, v pixsize_y 2 ny) and in planes ((w - w0) / dw);
+ *   val / acc (nsorted) complex: what is gridded / what degridding sums, per slot;
+ *   grid   (2 nx, 2 ny) complex, one w plane;  img (nx, ny) complex: the sum of the planes' images;
+ *   corr   (nx, ny) double: 1 / (c_u(i) c_v(j) c_w(i,j)) [/ n_ij], the kernel correction with divide_by_n folded in;
+ *   nm1    (nx, ny) double, or NULL without w-gridding.
+ * Plane p lies at w0 + p dw and takes the slots whose first plane is in [p - W + 1, p]: one contiguous range [s0, s1)
+ * of the order, which the caller reads off `offsets`.  A slot of the range that does not reach the plane is skipped.
+ * Between pfb_wgrid_grid and pfb_wgrid_image_adjoint (pfb_wgrid_image_forward and pfb_wgrid_degrid) the caller
+ * transforms the grid: unnormalised c2c, sign + (sign -).  Every function is asynchronous on `stream`.
+ *
+ * pfb_wgrid_grid accumulates with floating-point atomic adds: its sums depend on arrival order and vis2dirty differs
+ * in the last bits from run to run.  dirty2vis uses none and is reproducible bit for bit. */
+
+/* support: 4 .. 12.  nplanes == 1: one plane at w0 and no w kernel (dw ignored); else nplanes > support, dw > 0.
+ * nx, ny even.  PFB_ERR_UNSUPPORTED: a support outside the range, a grid narrower than the support, too many keys. */
+int pfb_wgrid_plan_create(int dtype, int nx, int ny, double pixsize_x, double pixsize_y, double center_x,
+                          double center_y, int support, int nplanes, double w0, double dw, void** plan);
+int pfb_wgrid_plan_destroy(void* plan);
+/* nkeys = np0 * (uv tiles); np0 = number of first planes (nplanes - support + 1, or 1); tile: the tile edge in cells.
+ * Slots with first plane q occupy [offsets[q * nkeys / np0], offsets[(q + 1) * nkeys / np0]). */
+int pfb_wgrid_plan_info(void* plan, int* nkeys, int* np0, int* tile);
+/* Bytes of `work`; host only; 0 for a NULL plan. */
+size_t pfb_wgrid_work_bytes(void* plan);
+
+/* The order, step 1: keys and their histogram (work is cleared first).  uvw (nrow, 3), freq (nchan) double;
+ * mask (nrow, nchan) unsigned char or NULL.  nrow * nchan < 2^31. */
+int pfb_wgrid_order_count(void* plan, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow,
+                          int nchan, int* keys, void* work, void* stream);
+/* Step 2, after the caller's scan: place every unmasked visibility.  nsorted = the histogram's total (>= 1).  The order
+ * within one key is the arrival order of the lanes. */
+int pfb_wgrid_order_fill(void* plan, const double* uvw, const double* freq, size_t nrow, int nchan, const int* keys,
+                         const long long* offsets, void* work, size_t nsorted, int* idx, double* coord, void* stream);
+
+/* val[s] = wgt vis exp(+2 pi i (u center_x + v center_y)); wgt (nrow, nchan) of `dtype`, or NULL for 1. */
+int pfb_wgrid_prep(void* plan, const void* vis, const void* wgt, const int* idx, const double* coord, size_t nsorted,
+                   void* val, void* stream);
+/* vis = 0, then vis[idx[s]] = wgt acc[s] exp(-2 pi i (u center_x + v center_y)); vis holds nvis = nrow * nchan. */
+int pfb_wgrid_finish(void* plan, const void* acc, const void* wgt, const int* idx, const double* coord, size_t nsorted,
+                     void* vis, size_t nvis, void* stream);
+/* val[s] = wgt acc[s]: degridding handed straight to gridding (the Hessian; the centre phases cancel). */
+int pfb_wgrid_weight(void* plan, const void* acc, const void* wgt, const int* idx, size_t nsorted, void* val,
+                     void* stream);
+
+/* grid = 0, then the slots [s0, s1) are added to plane `plane`. */
+int pfb_wgrid_grid(void* plan, int plane, const void* val, const double* coord, size_t nsorted, size_t s0, size_t s1,
+                   void* grid, void* stream);
+/* acc[s] += the footprint sum of slot s on plane `plane`, s in [s0, s1). */
+int pfb_wgrid_degrid(void* plan, int plane, const void* grid, const double* coord, size_t nsorted, size_t s0, size_t s1,
+                     void* acc, void* stream);
+
+/* grid = 0, then its centred window = dirty corr [beam] exp(+2 pi i w_p nm1).  beam (nx, ny) of `dtype`, or NULL. */
+int pfb_wgrid_image_forward(void* plan, int plane, const void* dirty, const void* beam, const double* corr,
+                            const double* nm1, void* grid, void* stream);
+/* img += window(grid) exp(-2 pi i w_p nm1). */
+int pfb_wgrid_image_adjoint(void* plan, int plane, const void* grid, const double* nm1, void* img, void* stream);
+/* dirty = Re(img) corr [beam]. */
+int pfb_wgrid_image_correct(void* plan, const void* img, const double* corr, const void* beam, void* dirty, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

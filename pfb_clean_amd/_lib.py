@@ -127,6 +127,21 @@ SIGNATURES = {
     'pfb_bandsum_stats': (_i, [_i, _vp, _i, _i, _sz, _vp, _i, _vp, _vp, _vp, _vp]),
     'pfb_mask_close': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _d, _i, _vp, _vp]),
     'pfb_masked_problem': (_i, [_i, _vp, _vp, _vp, _i, _vp, _i, _sz, _vp, _vp, _vp, _vp]),
+    # the w-gridder (hessian.py:62-106): plan, order, slots, one plane's gridding / degridding, the image side
+    'pfb_wgrid_plan_create': (_i, [_i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _d, C.POINTER(_vp)]),
+    'pfb_wgrid_plan_destroy': (_i, [_vp]),
+    'pfb_wgrid_plan_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    'pfb_wgrid_work_bytes': (_sz, [_vp]),
+    'pfb_wgrid_order_count': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    'pfb_wgrid_order_fill': (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'pfb_wgrid_prep': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'pfb_wgrid_finish': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'pfb_wgrid_weight': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'pfb_wgrid_grid': (_i, [_vp, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    'pfb_wgrid_degrid': (_i, [_vp, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    'pfb_wgrid_image_forward': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pfb_wgrid_image_adjoint': (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    'pfb_wgrid_image_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,604 @@
+// wgrid.hip -- the visibility-space operators of the major cycle (pfb/operators/hessian.py:62-106: ducc0's dirty2vis and
+// vis2dirty) by w-stacking on a twice oversampled grid with the kernel phi(x) = exp(2.3 W (sqrt(1 - x^2) - 1)), |x| < 1,
+// of W cells.  The plane transform itself is the caller's (torch.fft, operators/gridder.py); this file is
+// everything around it:
+//   k_order_count / k_order_fill   counting sort of the unmasked visibilities by (first w plane, uv tile): histogram, the
+//                                  caller's scan, placement.  Plane p's visibilities are then one contiguous range
+//   k_prep / k_finish / k_weight   visibility <-> sorted slot: weight, centre phase, the zero of masked samples
+//   k_grid                         one plane: 2 W lanes per visibility, a lane owns one real of a footprint row and adds
+//                                  down the W rows with float atomics (2 W contiguous reals per slot and instruction)
+//   k_degrid                       one plane: a lane per visibility gathers its W x W footprint; no atomics, each slot's
+//                                  sum has a fixed order
+//   k_image_forward / _adjoint / _correct   the image side: window <-> grid with the plane's w phase, the kernel
+//                                  correction with 1/n and the beam fused in
+// Coordinates (u, v, w -> cells and planes) and every phase are fp64 whatever the data type: a phase of some tens of
+// turns leaves 1e-6 of a turn in fp32.  Kernel values, grids and sums are in the data's type.
+//
+// Every index is reduced modulo the grid before it is used, so no coordinate, however wild, addresses outside it.
+#include "common.hpp"
+#include <new>
+
+namespace pfb {
+
+typedef unsigned char u8;
+
+constexpr int WG_BLOCK = 256;
+constexpr int WG_MIN_W = 4, WG_MAX_W = 12;
+constexpr int WG_MAX_TILES = 4096;        // uv tiles of the sort key; the tile edge doubles from 16 until they fit
+constexpr double WG_C = 299792458.0;
+
+struct WgridPlan {
+    int dtype, nx, ny, Nu, Nv, W, nplanes, np0, tile, ntu, ntv;
+    double px, py, cx, cy, w0, dw;
+    bool wkernel() const { return nplanes > 1; }
+    int nkeys() const { return np0 * ntu * ntv; }
+};
+
+template <typename T>
+__device__ __forceinline__ T wg_phi(T x, T beta) {
+    const T q = T(1) - x * x;
+    return q > T(0) ? exp(beta * (sqrt(q) - T(1))) : T(0);
+}
+
+// first cell of a footprint around g, and the same reduced to [0, N)
+__device__ __forceinline__ double wg_first(double g, double h) { return ceil(g - h); }
+__device__ __forceinline__ int wg_wrap(double a0, int N) {
+    const double m = a0 - N * floor(a0 / N);
+    const int i = (int)m;
+    return i < 0 ? 0 : (i >= N ? N - 1 : i);
+}
+
+__device__ __forceinline__ void wg_atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
+__device__ __forceinline__ void wg_atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }
+
+struct WgGeom {
+    int Nu, Nv, W, np0, tile, ntv, wk;
+    double su, sv, w0, dw, h;          // su = pixsize_x Nu: u -> cells
+};
+
+// ---------------------------------------------------------------------------------------------------- the order
+__device__ __forceinline__ void wg_coords(const double* __restrict__ uvw, const double* __restrict__ freq, size_t t,
+                                          int nchan, const WgGeom& g, double& ug, double& vg, double& pg) {
+    const size_t r = t / nchan;
+    const double f = freq[t - r * nchan];
+    ug = uvw[3 * r] * f / WG_C * g.su;
+    vg = uvw[3 * r + 1] * f / WG_C * g.sv;
+    pg = g.wk ? (uvw[3 * r + 2] * f / WG_C - g.w0) / g.dw : 0.0;
+}
+
+__global__ void __launch_bounds__(WG_BLOCK)
+k_order_count(const double* __restrict__ uvw, const double* __restrict__ freq, const u8* __restrict__ mask, size_t nvis,
+              int nchan, WgGeom g, int* __restrict__ keys, int* __restrict__ counts) {
+    const size_t t = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (t >= nvis) return;
+    if (mask && !mask[t]) { keys[t] = -1; return; }
+    double ug, vg, pg;
+    wg_coords(uvw, freq, t, nchan, g, ug, vg, pg);
+    const int a = wg_wrap(wg_first(ug, g.h), g.Nu), b = wg_wrap(wg_first(vg, g.h), g.Nv);
+    int p0 = 0;
+    if (g.wk) {
+        const double p = wg_first(pg, g.h);
+        p0 = p > 0.0 ? (p < g.np0 - 1 ? (int)p : g.np0 - 1) : 0;
+    }
+    const int ntiles = ((g.Nu + g.tile - 1) / g.tile) * g.ntv;
+    const int key = p0 * ntiles + (a / g.tile) * g.ntv + b / g.tile;
+    keys[t] = key;
+    atomicAdd(&counts[key], 1);
+}
+
+__global__ void __launch_bounds__(WG_BLOCK)
+k_order_fill(const double* __restrict__ uvw, const double* __restrict__ freq, size_t nvis, int nchan, WgGeom g,
+             const int* __restrict__ keys, const long long* __restrict__ offsets, int* __restrict__ cursor,
+             size_t nsorted, int* __restrict__ idx, double* __restrict__ coord) {
+    const size_t t = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (t >= nvis) return;
+    const int key = keys[t];
+    if (key < 0) return;
+    const size_t s = (size_t)offsets[key] + (size_t)atomicAdd(&cursor[key], 1);
+    if (s >= nsorted) return;          // cannot happen with the counts of k_order_count; never write past the arrays
+    double ug, vg, pg;
+    wg_coords(uvw, freq, t, nchan, g, ug, vg, pg);
+    idx[s] = (int)t;
+    coord[s] = ug;
+    coord[nsorted + s] = vg;
+    coord[2 * nsorted + s] = pg;
+}
+
+// ------------------------------------------------------------------------------------- visibility <-> sorted slot
+// turns of the centre phase of slot s: u center_x + v center_y
+__device__ __forceinline__ double wg_centre_turns(const double* __restrict__ coord, size_t ns, size_t s, double cxs,
+                                                  double cys) {
+    return coord[s] * cxs + coord[ns + s] * cys;
+}
+template <typename T>
+__device__ __forceinline__ cplx<T> wg_cis(double turns) {
+    double sn, cs;
+    sincospi(2.0 * turns, &sn, &cs);
+    return cplx<T>((T)cs, (T)sn);
+}
+
+// val[s] = wgt vis exp(+2 pi i (u cx + v cy))
+template <typename T>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_prep(const cplx<T>* __restrict__ vis, const T* __restrict__ wgt, const int* __restrict__ idx,
+       const double* __restrict__ coord, size_t ns, double cxs, double cys, int centre, cplx<T>* __restrict__ val) {
+    const size_t s = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (s >= ns) return;
+    const int t = idx[s];
+    cplx<T> v = vis[t];
+    if (wgt) v = wgt[t] * v;
+    if (centre) v = v * wg_cis<T>(wg_centre_turns(coord, ns, s, cxs, cys));
+    val[s] = v;
+}
+
+// vis[idx[s]] = wgt acc[s] exp(-2 pi i (u cx + v cy)); vis was zeroed by the launcher
+template <typename T>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_finish(const cplx<T>* __restrict__ acc, const T* __restrict__ wgt, const int* __restrict__ idx,
+         const double* __restrict__ coord, size_t ns, double cxs, double cys, int centre, cplx<T>* __restrict__ vis) {
+    const size_t s = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (s >= ns) return;
+    const int t = idx[s];
+    cplx<T> v = acc[s];
+    if (centre) v = v * wg_cis<T>(-wg_centre_turns(coord, ns, s, cxs, cys));
+    if (wgt) v = wgt[t] * v;
+    vis[t] = v;
+}
+
+// val[s] = wgt acc[s]: the Hessian's hand-over from degridding to gridding (the two centre phases cancel)
+template <typename T>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_weight(const cplx<T>* __restrict__ acc, const T* __restrict__ wgt, const int* __restrict__ idx, size_t ns,
+         cplx<T>* __restrict__ val) {
+    const size_t s = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (s >= ns) return;
+    cplx<T> v = acc[s];
+    if (wgt) v = wgt[idx[s]] * v;
+    val[s] = v;
+}
+
+// ------------------------------------------------------------------------------------------- gridding, one plane
+// 2 W consecutive lanes per slot: lane (b, c) owns the real (c = 0) or imaginary part of column b of the footprint and
+// walks down its W rows.  One atomic wave-instruction then lands 2 W contiguous reals per slot (but for the wrap) in
+// about 64 / (2 W) rows; with a lane per ROW instead, its 64 adds went to 64 different rows, the slowest shape there is
+// (5.5e2 us per plane for either data type).  Every lane re-evaluates the W row values: arithmetic is
+// cheap next to the adds, and a slot's lanes may straddle two waves, so they cannot be shuffled
+template <typename T, int W>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_grid(const cplx<T>* __restrict__ val, const double* __restrict__ coord, size_t ns, size_t s0, size_t s1, int plane,
+       WgGeom g, T* __restrict__ grid) {
+    constexpr int L = 2 * W;
+    const size_t tid = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    const size_t s = s0 + tid / L;
+    const int j = (int)(tid % L), b = j >> 1, c = j & 1;
+    if (s >= s1) return;
+    const T beta = T(2.3) * W;
+    const double h = 0.5 * W;
+    T ww = T(1);
+    if (g.wk) {
+        ww = wg_phi<T>((T)((plane - coord[2 * ns + s]) / h), beta);
+        if (ww == T(0)) return;
+    }
+    const double ug = coord[s], vg = coord[ns + s];
+    const double a0 = wg_first(ug, h), b0 = wg_first(vg, h);
+    const cplx<T> v = val[s];
+    const T part = (c ? v.y : v.x) * ww * wg_phi<T>((T)((b0 + b - vg) / h), beta);
+    int col = wg_wrap(b0, g.Nv) + b;
+    if (col >= g.Nv) col -= g.Nv;
+    int row = wg_wrap(a0, g.Nu);
+    T* __restrict__ cell = grid + 2 * (size_t)col + c;
+#pragma unroll
+    for (int a = 0; a < W; ++a) {
+        const T fu = wg_phi<T>((T)((a0 + a - ug) / h), beta);
+        wg_atomic_add(cell + 2 * (size_t)row * g.Nv, fu * part);
+        if (++row == g.Nu) row = 0;
+    }
+}
+
+// ----------------------------------------------------------------------------------------- degridding, one plane
+template <typename T, int W>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_degrid(const cplx<T>* __restrict__ grid, const double* __restrict__ coord, size_t ns, size_t s0, size_t s1, int plane,
+         WgGeom g, cplx<T>* __restrict__ acc) {
+    const size_t s = s0 + (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (s >= s1) return;
+    const T beta = T(2.3) * W;
+    const double h = 0.5 * W;
+    T ww = T(1);
+    if (g.wk) {
+        ww = wg_phi<T>((T)((plane - coord[2 * ns + s]) / h), beta);
+        if (ww == T(0)) return;
+    }
+    const double ug = coord[s], vg = coord[ns + s];
+    const double a0 = wg_first(ug, h), b0 = wg_first(vg, h);
+    T fv[W];
+#pragma unroll
+    for (int b = 0; b < W; ++b) fv[b] = wg_phi<T>((T)((b0 + b - vg) / h), beta);
+    int row = wg_wrap(a0, g.Nu);
+    const int col0 = wg_wrap(b0, g.Nv);
+    T sx = T(0), sy = T(0);
+#pragma unroll 1          // one row of loads in flight: unrolled, the fp64 kernels of W = 11, 12 spill
+    for (int a = 0; a < W; ++a) {
+        const T fu = wg_phi<T>((T)((a0 + a - ug) / h), beta);
+        const cplx<T>* __restrict__ line = grid + (size_t)row * g.Nv;
+        int col = col0;
+        T rx = T(0), ry = T(0);
+#pragma unroll
+        for (int b = 0; b < W; ++b) {
+            const cplx<T> c = line[col];
+            rx += fv[b] * c.x;
+            ry += fv[b] * c.y;
+            if (++col == g.Nv) col = 0;
+        }
+        sx += fu * rx;
+        sy += fu * ry;
+        if (++row == g.Nu) row = 0;
+    }
+    cplx<T> r = acc[s];
+    r.x += ww * sx;
+    r.y += ww * sy;
+    acc[s] = r;
+}
+
+// ------------------------------------------------------------------------------------------------ the image side
+// pixel (i, j) of the image <-> cell ((i - nx/2) mod Nu, (j - ny/2) mod Nv) of the grid
+__device__ __forceinline__ size_t wg_cell(int i, int j, int nx, int ny, int Nu, int Nv) {
+    const int gi = i < nx / 2 ? i - nx / 2 + Nu : i - nx / 2;
+    const int gj = j < ny / 2 ? j - ny / 2 + Nv : j - ny / 2;
+    return (size_t)gi * Nv + gj;
+}
+
+// grid (zeroed by the launcher) <- dirty corr [beam] exp(+2 pi i w_p nm1)
+template <typename T>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_image_forward(const T* __restrict__ dirty, const T* __restrict__ beam, const double* __restrict__ corr,
+                const double* __restrict__ nm1, double wp, int nx, int ny, int Nu, int Nv, cplx<T>* __restrict__ grid) {
+    const size_t q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (q >= (size_t)nx * ny) return;
+    const int i = (int)(q / ny), j = (int)(q - (size_t)i * ny);
+    double d = (double)dirty[q] * corr[q];
+    if (beam) d *= (double)beam[q];
+    cplx<T> v((T)d, T(0));
+    if (nm1) {
+        double sn, cs;
+        sincospi(2.0 * wp * nm1[q], &sn, &cs);
+        v = cplx<T>((T)(d * cs), (T)(d * sn));
+    }
+    grid[wg_cell(i, j, nx, ny, Nu, Nv)] = v;
+}
+
+// img += window(grid) exp(-2 pi i w_p nm1)
+template <typename T>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_image_adjoint(const cplx<T>* __restrict__ grid, const double* __restrict__ nm1, double wp, int nx, int ny, int Nu,
+                int Nv, cplx<T>* __restrict__ img) {
+    const size_t q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (q >= (size_t)nx * ny) return;
+    const int i = (int)(q / ny), j = (int)(q - (size_t)i * ny);
+    const cplx<T> c = grid[wg_cell(i, j, nx, ny, Nu, Nv)];
+    cplx<T> r = img[q];
+    if (nm1) {
+        double sn, cs;
+        sincospi(-2.0 * wp * nm1[q], &sn, &cs);
+        const T cx = (T)cs, sx = (T)sn;
+        r.x += c.x * cx - c.y * sx;
+        r.y += c.x * sx + c.y * cx;
+    } else {
+        r.x += c.x;
+        r.y += c.y;
+    }
+    img[q] = r;
+}
+
+// dirty = Re(img) corr [beam]
+template <typename T>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_image_correct(const cplx<T>* __restrict__ img, const double* __restrict__ corr, const T* __restrict__ beam, size_t npix,
+                T* __restrict__ dirty) {
+    const size_t q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (q >= npix) return;
+    double d = (double)img[q].x * corr[q];
+    if (beam) d *= (double)beam[q];
+    dirty[q] = (T)d;
+}
+
+// ------------------------------------------------------------------------------------------------------ launchers
+static inline unsigned wg_blocks(size_t n) { return (unsigned)((n + WG_BLOCK - 1) / WG_BLOCK); }
+constexpr size_t WG_MAX_THREADS = (size_t)0x7fffffff * WG_BLOCK;        // one launch's grid limit
+
+static WgGeom wg_geom(const WgridPlan& p) {
+    WgGeom g;
+    g.Nu = p.Nu; g.Nv = p.Nv; g.W = p.W; g.np0 = p.np0; g.tile = p.tile; g.ntv = p.ntv; g.wk = p.wkernel();
+    g.su = p.px * p.Nu; g.sv = p.py * p.Nv; g.w0 = p.w0; g.dw = p.dw; g.h = 0.5 * p.W;
+    return g;
+}
+
+template <typename T, int W>
+static void wg_launch_grid(const WgridPlan& p, int plane, const void* val, const double* coord, size_t ns, size_t s0,
+                           size_t s1, void* grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_grid<T, W>), dim3(wg_blocks((s1 - s0) * 2 * W)), dim3(WG_BLOCK), 0, st, (const cplx<T>*)val, coord,
+                       ns, s0, s1, plane, wg_geom(p), (T*)grid);
+}
+template <typename T, int W>
+static void wg_launch_degrid(const WgridPlan& p, int plane, const void* grid, const double* coord, size_t ns, size_t s0,
+                             size_t s1, void* acc, hipStream_t st) {
+    hipLaunchKernelGGL((k_degrid<T, W>), dim3(wg_blocks(s1 - s0)), dim3(WG_BLOCK), 0, st, (const cplx<T>*)grid, coord, ns,
+                       s0, s1, plane, wg_geom(p), (cplx<T>*)acc);
+}
+
+// one instantiation per support: the footprint loops unroll and the row of kernel values stays in registers
+#define WG_BY_SUPPORT(FN, T, W, ...)                                         \
+    switch (W) {                                                             \
+        case 4:  FN<T, 4>(__VA_ARGS__);  break;                              \
+        case 5:  FN<T, 5>(__VA_ARGS__);  break;                              \
+        case 6:  FN<T, 6>(__VA_ARGS__);  break;                              \
+        case 7:  FN<T, 7>(__VA_ARGS__);  break;                              \
+        case 8:  FN<T, 8>(__VA_ARGS__);  break;                              \
+        case 9:  FN<T, 9>(__VA_ARGS__);  break;                              \
+        case 10: FN<T, 10>(__VA_ARGS__); break;                              \
+        case 11: FN<T, 11>(__VA_ARGS__); break;                              \
+        default: FN<T, 12>(__VA_ARGS__); break;                              \
+    }
+
+static size_t wg_esize(int dtype) { return dtype == PFB_F32 ? 4 : 8; }
+static bool wg_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+}  // namespace pfb
+
+using namespace pfb;
+
+#define WG_PLAN(name)                                                                        \
+    PFB_REQUIRE(plan, PFB_ERR_INVALID, name ": null plan");                                   \
+    const WgridPlan& p = *static_cast<const WgridPlan*>(plan)
+#define WG_RANGE(name)                                                                                         \
+    PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, name ": plane %d of %d", plane, p.nplanes);   \
+    PFB_REQUIRE(s0 <= s1 && s1 <= nsorted, PFB_ERR_INVALID, name ": range [%zu, %zu) of %zu slots", s0, s1, nsorted); \
+    PFB_REQUIRE((s1 - s0) * 2 * (size_t)p.W <= WG_MAX_THREADS, PFB_ERR_UNSUPPORTED, name ": %zu slots in one launch", s1 - s0)
+
+extern "C" {
+
+int pfb_wgrid_plan_create(int dtype, int nx, int ny, double pixsize_x, double pixsize_y, double center_x,
+                          double center_y, int support, int nplanes, double w0, double dw, void** plan) {
+    PFB_REQUIRE(plan, PFB_ERR_INVALID, "wgrid_plan_create: null plan pointer");
+    *plan = nullptr;
+    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "wgrid_plan_create: bad dtype %d", dtype);
+    PFB_REQUIRE(nx >= 2 && ny >= 2 && nx % 2 == 0 && ny % 2 == 0, PFB_ERR_INVALID,
+                "wgrid_plan_create: nx %d, ny %d must be even and >= 2", nx, ny);
+    PFB_REQUIRE(nx <= (1 << 29) && ny <= (1 << 29), PFB_ERR_UNSUPPORTED, "wgrid_plan_create: image %d x %d too large", nx, ny);
+    PFB_REQUIRE(support >= WG_MIN_W && support <= WG_MAX_W, PFB_ERR_UNSUPPORTED,
+                "wgrid_plan_create: support %d outside [%d, %d]", support, WG_MIN_W, WG_MAX_W);
+    PFB_REQUIRE(2 * nx >= support && 2 * ny >= support, PFB_ERR_UNSUPPORTED,
+                "wgrid_plan_create: grid %d x %d narrower than the support %d", 2 * nx, 2 * ny, support);
+    PFB_REQUIRE(std::isfinite(pixsize_x) && std::isfinite(pixsize_y) && pixsize_x > 0 && pixsize_y > 0 &&
+                std::isfinite(center_x) && std::isfinite(center_y), PFB_ERR_INVALID,
+                "wgrid_plan_create: pixel sizes must be positive and finite, the centre finite");
+    PFB_REQUIRE(nplanes == 1 || (nplanes > support && std::isfinite(w0) && std::isfinite(dw) && dw > 0), PFB_ERR_INVALID,
+                "wgrid_plan_create: %d planes need a finite w0, dw > 0 and more planes than the support %d", nplanes, support);
+    PFB_REQUIRE(nplanes >= 1 && nplanes <= (1 << 20), PFB_ERR_UNSUPPORTED, "wgrid_plan_create: %d planes", nplanes);
+    int tile = 16;
+    while ((size_t)((2 * nx + tile - 1) / tile) * ((2 * ny + tile - 1) / tile) > (size_t)WG_MAX_TILES) tile *= 2;
+    const int ntu = (2 * nx + tile - 1) / tile, ntv = (2 * ny + tile - 1) / tile;
+    const int np0 = nplanes > 1 ? nplanes - support + 1 : 1;
+    PFB_REQUIRE((size_t)np0 * ntu * ntv <= (size_t)0x3fffffff, PFB_ERR_UNSUPPORTED,
+                "wgrid_plan_create: %d planes x %d tiles exceed the key range", nplanes, ntu * ntv);
+    WgridPlan* q = new (std::nothrow) WgridPlan();
+    PFB_REQUIRE(q, PFB_ERR_ALLOC, "wgrid_plan_create: out of host memory");
+    q->dtype = dtype; q->nx = nx; q->ny = ny; q->Nu = 2 * nx; q->Nv = 2 * ny; q->W = support; q->nplanes = nplanes;
+    q->np0 = np0;
+    q->px = pixsize_x; q->py = pixsize_y; q->cx = center_x; q->cy = center_y;
+    q->w0 = std::isfinite(w0) ? w0 : 0.0; q->dw = nplanes > 1 ? dw : 1.0;
+    q->tile = tile; q->ntu = ntu; q->ntv = ntv;
+    *plan = q;
+    return PFB_OK;
+}
+
+int pfb_wgrid_plan_destroy(void* plan) {
+    delete static_cast<WgridPlan*>(plan);
+    return PFB_OK;
+}
+
+int pfb_wgrid_plan_info(void* plan, int* nkeys, int* np0, int* tile) {
+    WG_PLAN("wgrid_plan_info");
+    if (nkeys) *nkeys = p.nkeys();
+    if (np0) *np0 = p.np0;
+    if (tile) *tile = p.tile;
+    return PFB_OK;
+}
+
+size_t pfb_wgrid_work_bytes(void* plan) {
+    if (!plan) return 0;
+    return 2 * sizeof(int) * (size_t)static_cast<const WgridPlan*>(plan)->nkeys();
+}
+
+int pfb_wgrid_order_count(void* plan, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow,
+                          int nchan, int* keys, void* work, void* stream) {
+    WG_PLAN("wgrid_order_count");
+    PFB_REQUIRE(uvw && freq && keys && work, PFB_ERR_INVALID, "wgrid_order_count: null argument");
+    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff / (size_t)nchan, PFB_ERR_UNSUPPORTED,
+                "wgrid_order_count: %zu rows x %d channels outside [1, 2^31)", nrow, nchan);
+    PFB_REQUIRE(wg_aligned(uvw, 8) && wg_aligned(freq, 8) && wg_aligned(keys, 4) && wg_aligned(work, 4), PFB_ERR_INVALID,
+                "wgrid_order_count: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    const size_t nvis = nrow * (size_t)nchan;
+    PFB_HIP_CHECK(hipMemsetAsync(work, 0, pfb_wgrid_work_bytes(plan), st));
+    hipLaunchKernelGGL(k_order_count, dim3(wg_blocks(nvis)), dim3(WG_BLOCK), 0, st, uvw, freq, mask, nvis, nchan,
+                       wg_geom(p), keys, (int*)work);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_order_fill(void* plan, const double* uvw, const double* freq, size_t nrow, int nchan, const int* keys,
+                         const long long* offsets, void* work, size_t nsorted, int* idx, double* coord, void* stream) {
+    WG_PLAN("wgrid_order_fill");
+    PFB_REQUIRE(uvw && freq && keys && offsets && work && idx && coord, PFB_ERR_INVALID, "wgrid_order_fill: null argument");
+    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff / (size_t)nchan, PFB_ERR_UNSUPPORTED,
+                "wgrid_order_fill: %zu rows x %d channels outside [1, 2^31)", nrow, nchan);
+    const size_t nvis = nrow * (size_t)nchan;
+    PFB_REQUIRE(nsorted >= 1 && nsorted <= nvis, PFB_ERR_INVALID, "wgrid_order_fill: %zu slots for %zu visibilities",
+                nsorted, nvis);
+    PFB_REQUIRE(wg_aligned(offsets, 8) && wg_aligned(coord, 8) && wg_aligned(idx, 4), PFB_ERR_INVALID,
+                "wgrid_order_fill: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(k_order_fill, dim3(wg_blocks(nvis)), dim3(WG_BLOCK), 0, st, uvw, freq, nvis, nchan, wg_geom(p),
+                       keys, offsets, (int*)work + p.nkeys(), nsorted, idx, coord);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+#define WG_SLOTS(name)                                                                                             \
+    PFB_REQUIRE(nsorted >= 1 && nsorted <= (size_t)0x7fffffff, PFB_ERR_INVALID, name ": %zu slots", nsorted);      \
+    PFB_REQUIRE(idx && coord, PFB_ERR_INVALID, name ": null order")
+
+int pfb_wgrid_prep(void* plan, const void* vis, const void* wgt, const int* idx, const double* coord, size_t nsorted,
+                   void* val, void* stream) {
+    WG_PLAN("wgrid_prep");
+    WG_SLOTS("wgrid_prep");
+    PFB_REQUIRE(vis && val, PFB_ERR_INVALID, "wgrid_prep: null argument");
+    PFB_REQUIRE(wg_aligned(vis, 2 * wg_esize(p.dtype)) && wg_aligned(val, 2 * wg_esize(p.dtype)) &&
+                wg_aligned(wgt, wg_esize(p.dtype)), PFB_ERR_INVALID, "wgrid_prep: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    const double cxs = p.cx / (p.px * p.Nu), cys = p.cy / (p.py * p.Nv);
+    const int centre = p.cx != 0.0 || p.cy != 0.0;
+    if (p.dtype == PFB_F32)
+        hipLaunchKernelGGL(k_prep<float>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)vis,
+                           (const float*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<float>*)val);
+    else
+        hipLaunchKernelGGL(k_prep<double>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)vis,
+                           (const double*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<double>*)val);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_finish(void* plan, const void* acc, const void* wgt, const int* idx, const double* coord, size_t nsorted,
+                     void* vis, size_t nvis, void* stream) {
+    WG_PLAN("wgrid_finish");
+    WG_SLOTS("wgrid_finish");
+    PFB_REQUIRE(acc && vis && nsorted <= nvis && nvis <= (size_t)0x7fffffff, PFB_ERR_INVALID,
+                "wgrid_finish: null argument, or %zu slots for %zu visibilities", nsorted, nvis);
+    PFB_REQUIRE(wg_aligned(vis, 2 * wg_esize(p.dtype)) && wg_aligned(acc, 2 * wg_esize(p.dtype)) &&
+                wg_aligned(wgt, wg_esize(p.dtype)), PFB_ERR_INVALID, "wgrid_finish: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    const double cxs = p.cx / (p.px * p.Nu), cys = p.cy / (p.py * p.Nv);
+    const int centre = p.cx != 0.0 || p.cy != 0.0;
+    PFB_HIP_CHECK(hipMemsetAsync(vis, 0, 2 * wg_esize(p.dtype) * nvis, st));
+    if (p.dtype == PFB_F32)
+        hipLaunchKernelGGL(k_finish<float>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)acc,
+                           (const float*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<float>*)vis);
+    else
+        hipLaunchKernelGGL(k_finish<double>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)acc,
+                           (const double*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<double>*)vis);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_weight(void* plan, const void* acc, const void* wgt, const int* idx, size_t nsorted, void* val,
+                     void* stream) {
+    WG_PLAN("wgrid_weight");
+    PFB_REQUIRE(nsorted >= 1 && nsorted <= (size_t)0x7fffffff && acc && val && idx, PFB_ERR_INVALID,
+                "wgrid_weight: null argument or %zu slots", nsorted);
+    PFB_REQUIRE(wg_aligned(val, 2 * wg_esize(p.dtype)) && wg_aligned(acc, 2 * wg_esize(p.dtype)) &&
+                wg_aligned(wgt, wg_esize(p.dtype)), PFB_ERR_INVALID, "wgrid_weight: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    if (p.dtype == PFB_F32)
+        hipLaunchKernelGGL(k_weight<float>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)acc,
+                           (const float*)wgt, idx, nsorted, (cplx<float>*)val);
+    else
+        hipLaunchKernelGGL(k_weight<double>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)acc,
+                           (const double*)wgt, idx, nsorted, (cplx<double>*)val);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_grid(void* plan, int plane, const void* val, const double* coord, size_t nsorted, size_t s0, size_t s1,
+                   void* grid, void* stream) {
+    WG_PLAN("wgrid_grid");
+    WG_RANGE("wgrid_grid");
+    PFB_REQUIRE(val && coord && grid, PFB_ERR_INVALID, "wgrid_grid: null argument");
+    PFB_REQUIRE(wg_aligned(val, 2 * wg_esize(p.dtype)) && wg_aligned(grid, 2 * wg_esize(p.dtype)) && wg_aligned(coord, 8),
+                PFB_ERR_INVALID, "wgrid_grid: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, 2 * wg_esize(p.dtype) * (size_t)p.Nu * p.Nv, st));
+    if (s1 > s0) {
+        if (p.dtype == PFB_F32) { WG_BY_SUPPORT(wg_launch_grid, float, p.W, p, plane, val, coord, nsorted, s0, s1, grid, st) }
+        else { WG_BY_SUPPORT(wg_launch_grid, double, p.W, p, plane, val, coord, nsorted, s0, s1, grid, st) }
+    }
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_degrid(void* plan, int plane, const void* grid, const double* coord, size_t nsorted, size_t s0, size_t s1,
+                     void* acc, void* stream) {
+    WG_PLAN("wgrid_degrid");
+    WG_RANGE("wgrid_degrid");
+    PFB_REQUIRE(acc && coord && grid, PFB_ERR_INVALID, "wgrid_degrid: null argument");
+    PFB_REQUIRE(wg_aligned(acc, 2 * wg_esize(p.dtype)) && wg_aligned(grid, 2 * wg_esize(p.dtype)) && wg_aligned(coord, 8),
+                PFB_ERR_INVALID, "wgrid_degrid: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    if (s1 > s0) {
+        if (p.dtype == PFB_F32) { WG_BY_SUPPORT(wg_launch_degrid, float, p.W, p, plane, grid, coord, nsorted, s0, s1, acc, st) }
+        else { WG_BY_SUPPORT(wg_launch_degrid, double, p.W, p, plane, grid, coord, nsorted, s0, s1, acc, st) }
+    }
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_image_forward(void* plan, int plane, const void* dirty, const void* beam, const double* corr,
+                            const double* nm1, void* grid, void* stream) {
+    WG_PLAN("wgrid_image_forward");
+    PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, "wgrid_image_forward: plane %d of %d", plane, p.nplanes);
+    PFB_REQUIRE(dirty && corr && grid, PFB_ERR_INVALID, "wgrid_image_forward: null argument");
+    PFB_REQUIRE(wg_aligned(dirty, wg_esize(p.dtype)) && wg_aligned(beam, wg_esize(p.dtype)) && wg_aligned(corr, 8) &&
+                wg_aligned(nm1, 8) && wg_aligned(grid, 2 * wg_esize(p.dtype)), PFB_ERR_INVALID,
+                "wgrid_image_forward: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    const size_t npix = (size_t)p.nx * p.ny;
+    const double wp = p.w0 + plane * (p.wkernel() ? p.dw : 0.0);
+    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, 2 * wg_esize(p.dtype) * (size_t)p.Nu * p.Nv, st));
+    if (p.dtype == PFB_F32)
+        hipLaunchKernelGGL(k_image_forward<float>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const float*)dirty,
+                           (const float*)beam, corr, nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<float>*)grid);
+    else
+        hipLaunchKernelGGL(k_image_forward<double>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const double*)dirty,
+                           (const double*)beam, corr, nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<double>*)grid);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_image_adjoint(void* plan, int plane, const void* grid, const double* nm1, void* img, void* stream) {
+    WG_PLAN("wgrid_image_adjoint");
+    PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, "wgrid_image_adjoint: plane %d of %d", plane, p.nplanes);
+    PFB_REQUIRE(grid && img, PFB_ERR_INVALID, "wgrid_image_adjoint: null argument");
+    PFB_REQUIRE(wg_aligned(img, 2 * wg_esize(p.dtype)) && wg_aligned(nm1, 8) && wg_aligned(grid, 2 * wg_esize(p.dtype)),
+                PFB_ERR_INVALID, "wgrid_image_adjoint: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    const size_t npix = (size_t)p.nx * p.ny;
+    const double wp = p.w0 + plane * (p.wkernel() ? p.dw : 0.0);
+    if (p.dtype == PFB_F32)
+        hipLaunchKernelGGL(k_image_adjoint<float>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)grid,
+                           nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<float>*)img);
+    else
+        hipLaunchKernelGGL(k_image_adjoint<double>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)grid,
+                           nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<double>*)img);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+int pfb_wgrid_image_correct(void* plan, const void* img, const double* corr, const void* beam, void* dirty, void* stream) {
+    WG_PLAN("wgrid_image_correct");
+    PFB_REQUIRE(img && corr && dirty, PFB_ERR_INVALID, "wgrid_image_correct: null argument");
+    PFB_REQUIRE(wg_aligned(img, 2 * wg_esize(p.dtype)) && wg_aligned(corr, 8) && wg_aligned(beam, wg_esize(p.dtype)) &&
+                wg_aligned(dirty, wg_esize(p.dtype)), PFB_ERR_INVALID,
+                "wgrid_image_correct: an array is not aligned to its element size");
+    hipStream_t st = as_stream(stream);
+    const size_t npix = (size_t)p.nx * p.ny;
+    if (p.dtype == PFB_F32)
+        hipLaunchKernelGGL(k_image_correct<float>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)img,
+                           corr, (const float*)beam, npix, (float*)dirty);
+    else
+        hipLaunchKernelGGL(k_image_correct<double>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)img,
+                           corr, (const double*)beam, npix, (double*)dirty);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,10 @@ HessianPsf is the object form used by the fused PCG (opt/pcg.py): it carries the
 and the operator parameters so that `pcg(A, b, ...)` can run the whole solve inside
 libpfb_hip.so when A is one of these.
 
+_hessian_impl / hessian / hessian_xds are the VISIBILITY-space Hessian (hessian.py:11-126): dirty2vis then vis2dirty
+through operators/gridder.py, the visibilities never leaving their sorted slots in between.
+hessian_psf_slice.compute_residual uses it when the dataset carries UVW / WEIGHT / VIS_MASK / FREQ.
+
 ParamHessian / hessian_psf are the band-coupled Hessian of the parametrised forward step
 (workers/fwdbwd.py:246-252):  2 dhf(psf_convolve(df(v))) + sigmainv v  with the closures of
 utils/misc.py::setup_parametrisation, as band mix -> convolution with the e sandwich -> band mix
@@ -26,7 +30,57 @@ import numpy as np
 import torch
 
 from .. import _dev, _lib
+from . import gridder
 from .psf import plan_for, PsfConvPlan, psf_convolve_cube, _run
+
+
+# ------------------------------------------------------------------ the visibility-space Hessian (hessian.py:11-126)
+def _hessian_impl(x, uvw, weight, vis_mask, freq, beam, x0=0.0, y0=0.0, cell=None, do_wgridding=None, epsilon=None,
+                  double_accum=None, nthreads=None):
+    """pfb/operators/hessian.py:62-106: beam * vis2dirty(weight * dirty2vis(beam * x)), divide_by_n=False both ways,
+    image centre (x0, y0), square pixels of `cell`.  An all-zero x answers zeros without a launch of the gridder.
+    beam and weight may be None.  double_accum with a float32 x runs the fp64 kernels on the data cast up.  `nthreads`
+    is accepted and ignored.  numpy in gives numpy out."""
+    if cell is None or do_wgridding is None or epsilon is None:
+        raise TypeError("cell, do_wgridding and epsilon are required")
+    xd = _dev.to_dev(x)
+    if xd.ndim != 2 or xd.dtype not in _dev.CPLX_OF:
+        raise TypeError(f"x must be a 2-D float32 or float64 image, got {xd.dtype} {tuple(xd.shape)}")
+    if not _dev.any_nonzero(xd):
+        return _dev.host_like(torch.zeros_like(xd), x)
+    rdt = torch.float64 if double_accum else xd.dtype
+    nx, ny = xd.shape
+    plan = gridder.plan_for(uvw, freq, vis_mask, nx, ny, cell, cell, x0, y0, epsilon, do_wgridding, rdt)
+    out = plan.hessian(xd.to(rdt), _dev.to_dev(weight, rdt), _dev.to_dev(beam, rdt))
+    return _dev.host_like(out.to(xd.dtype), x)
+
+
+def hessian(x, uvw, weight, vis_mask, freq, beam, hessopts):
+    """hessian.py:113-126 without dask: _hessian_impl on one band's arrays with the options of `hessopts`."""
+    return _hessian_impl(x, uvw, weight, vis_mask, freq, beam, **hessopts)
+
+
+def hessian_xds(x, xds, hessopts, wsum, sigmainv, mask, compute=True, use_beam=True):
+    """hessian.py:11-59 over a list of in-memory datasets (variables with `.values`: UVW, FREQ, WEIGHT, MASK [, BEAM],
+    and `bandid`): per dataset the Hessian of x[bandid] with beam = BEAM * mask (the mask alone with use_beam=False),
+    summed per band, divided by wsum, plus x * sigmainv**2.  x (nband, nx, ny); mask (nx, ny).  `compute` is accepted
+    and ignored.  numpy in gives numpy out."""
+    xd = _dev.to_dev(x)
+    if xd.ndim != 3:
+        raise ValueError("hessian_xds expects a (nband, nx, ny) cube")
+    md = _dev.to_dev(mask, xd.dtype)
+    if md.ndim != 2:
+        raise ValueError("mask must be 2-D")
+    convim = torch.zeros_like(xd)
+    for ds in xds:
+        b = ds.bandid
+        beam = _dev.to_dev(ds.BEAM.values, xd.dtype) * md if use_beam else md
+        convim[b] += _hessian_impl(xd[b], ds.UVW.values, ds.WEIGHT.values, ds.MASK.values, ds.FREQ.values, beam,
+                                   **hessopts)
+    convim /= wsum
+    if sigmainv:
+        convim += xd * sigmainv ** 2
+    return _dev.host_like(convim, x)
 
 
 class HessianPsf:
@@ -81,7 +135,8 @@ class hessian_psf_slice:
     (torch tensors), `__call__` is _hessian_psf_slice through the band's own plan with the
     wsum given to set_wsum.  `ds` is the reference's per-band dataset or anything exposing the
     same variables with `.values` (DIRTY, PSFHAT, PSF, BEAM, WSUM [, MODEL, DUAL, RESIDUAL])
-    and `bandid`.  compute_residual is visibility space (wgridder) -- outside this package."""
+    and `bandid`.  With UVW, WEIGHT, VIS_MASK and FREQ in the dataset compute_residual is the reference's
+    dirty - _hessian_impl(beam * x, ...); without them it raises NotImplementedError."""
 
     def __init__(self, ds, nbasis, nmax, nthreads, sigmainv, cell=None, do_wgridding=None,
                  epsilon=None, double_accum=None):
@@ -105,6 +160,10 @@ class hessian_psf_slice:
             self.dual = torch.zeros((nbasis, nmax), dtype=rdt, device=self.dirty.device)
         self.residual = (_dev.to_dev(ds.RESIDUAL.values, rdt) if 'RESIDUAL' in ds
                          else self.dirty.clone())
+        self.uvw = self.wgt = self.vmask = self.freq = None
+        if all(k in ds for k in ('UVW', 'WEIGHT', 'VIS_MASK', 'FREQ')):
+            self.uvw, self.freq = _dev.to_dev(ds.UVW.values), _dev.to_dev(ds.FREQ.values)
+            self.wgt, self.vmask = _dev.to_dev(ds.WEIGHT.values), _dev.to_dev(ds.VIS_MASK.values)
         nx, ny = self.dirty.shape
         self._op = HessianPsf(self.psfhat, nx, ny, self.lastsize, beam=self.beam, sigmainv=sigmainv)
 
@@ -114,6 +173,13 @@ class hessian_psf_slice:
         return self._op(x)
 
     def compute_residual(self, x):
+        """hessian.py:236-247: dirty - _hessian_impl(beam * x, uvw, wgt, vmask, freq, None, ...)."""
+        if self.uvw is not None:
+            xd = _dev.to_dev(x, self.dirty.dtype)
+            hx = _hessian_impl(self.beam * xd, self.uvw, self.wgt, self.vmask, self.freq, None, cell=self.cell,
+                               do_wgridding=self.do_wgridding, epsilon=self.epsilon, double_accum=self.double_accum,
+                               nthreads=self.nthreads)
+            return _dev.host_like(self.dirty - hx, x)
         raise NotImplementedError("visibility-space residual (wgridder) is outside the PSF-convolution "
                                   "hot path; use the reference's _hessian_impl")
 
