@@ -83,10 +83,31 @@ class PsiPlan(NativePlan):
         self.Nymax, self.Nxmax = ny_.value, nx_.value
 
 
+def array_key(a):
+    """"Is this the array the caller presented last time?" as a hashable key.  numpy: address, shape, dtype, strides and
+    the sum of a strided sample of at most 257 elements (as a complex number: exact for real, integer and bool arrays,
+    and the imaginary part of a complex one counts).  Tensors: data_ptr, shape, dtype, version counter and device.
+    None is None; anything else is its identity."""
+    if a is None:
+        return None
+    if isinstance(a, np.ndarray):
+        flat = a.reshape(-1)
+        samp = flat[::max(1, flat.size // 257)][:257]
+        return ('np', a.__array_interface__['data'][0], a.shape, str(a.dtype), a.strides, complex(samp.sum()))
+    if isinstance(a, torch.Tensor):
+        return ('t', a.data_ptr(), tuple(a.shape), str(a.dtype), a._version, str(a.device))
+    return ('o', id(a))
+
+
 class PlanCache:
     """Bounded LRU of shared plans.  get(key, make) returns the cached plan or stores make()'s; beyond `maxsize`
     entries the least recently used is dropped.  Dropping (and clear()) only releases the cache's reference: a plan
-    is destroyed when its last holder lets go, so a thread that has fetched one can go on using it."""
+    is destroyed when its last holder lets go, so a thread that has fetched one can go on using it.
+
+    A key made with array_key() holds an address, so an entry has to keep the array behind it alive: freed, its memory
+    could come back as DIFFERENT data under the same key.  What is kept differs per cache, on purpose: operators/psf.py
+    keeps tensors only (a pinned numpy psfhat cube can be gigabytes; its key samples the content), operators/gridder.py
+    keeps all three of uvw, freq and mask, utils/misc.py keeps its coordinate tensors."""
 
     def __init__(self, maxsize):
         self.maxsize = maxsize

@@ -32,6 +32,14 @@ struct WgridPlan {
     double px, py, cx, cy, w0, dw;
     bool wkernel() const { return nplanes > 1; }
     int nkeys() const { return np0 * ntu * ntv; }
+    // what the entry points derive from the record, each written once
+    size_t esize() const { return dtype == PFB_F32 ? 4 : 8; }
+    size_t npix() const { return (size_t)nx * ny; }
+    size_t grid_bytes() const { return 2 * esize() * (size_t)Nu * Nv; }
+    double wp(int plane) const { return w0 + plane * (wkernel() ? dw : 0.0); }
+    double cxs() const { return cx / (px * Nu); }          // turns of the centre phase per cell of u, of v
+    double cys() const { return cy / (py * Nv); }
+    int centre() const { return cx != 0.0 || cy != 0.0; }
 };
 
 template <typename T>
@@ -303,6 +311,8 @@ k_image_correct(const cplx<T>* __restrict__ img, const double* __restrict__ corr
 }
 
 // ------------------------------------------------------------------------------------------------------ launchers
+// An entry point is: wg_check on its plan and pointers, its size checks, then wg_launch from a wg_by_type (and, for the
+// footprint kernels, wg_by_support) lambda.  A new one needs nothing else ("The entry layer").
 static inline unsigned wg_blocks(size_t n) { return (unsigned)((n + WG_BLOCK - 1) / WG_BLOCK); }
 constexpr size_t WG_MAX_THREADS = (size_t)0x7fffffff * WG_BLOCK;        // one launch's grid limit
 
@@ -313,47 +323,76 @@ static WgGeom wg_geom(const WgridPlan& p) {
     return g;
 }
 
-template <typename T, int W>
-static void wg_launch_grid(const WgridPlan& p, int plane, const void* val, const double* coord, size_t ns, size_t s0,
-                           size_t s1, void* grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_grid<T, W>), dim3(wg_blocks((s1 - s0) * 2 * W)), dim3(WG_BLOCK), 0, st, (const cplx<T>*)val, coord,
-                       ns, s0, s1, plane, wg_geom(p), (T*)grid);
+// a void pointer of the C ABI becomes the kernel parameter it is passed for; every other argument goes as it is
+template <typename P, typename A>
+static P wg_arg(A a) {
+    if constexpr (std::is_void_v<std::remove_pointer_t<A>>) return static_cast<P>(a);
+    else return a;
 }
-template <typename T, int W>
-static void wg_launch_degrid(const WgridPlan& p, int plane, const void* grid, const double* coord, size_t ns, size_t s0,
-                             size_t s1, void* acc, hipStream_t st) {
-    hipLaunchKernelGGL((k_degrid<T, W>), dim3(wg_blocks(s1 - s0)), dim3(WG_BLOCK), 0, st, (const cplx<T>*)grid, coord, ns,
-                       s0, s1, plane, wg_geom(p), (cplx<T>*)acc);
+// `kernel` with a lane per element of n, on the stream
+template <typename... P, typename... A>
+static int wg_launch(void (*kernel)(P...), size_t n, void* stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(wg_blocks(n)), dim3(WG_BLOCK), 0, as_stream(stream), wg_arg<P>(args)...);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
 }
 
-// one instantiation per support: the footprint loops unroll and the row of kernel values stays in registers
-#define WG_BY_SUPPORT(FN, T, W, ...)                                         \
-    switch (W) {                                                             \
-        case 4:  FN<T, 4>(__VA_ARGS__);  break;                              \
-        case 5:  FN<T, 5>(__VA_ARGS__);  break;                              \
-        case 6:  FN<T, 6>(__VA_ARGS__);  break;                              \
-        case 7:  FN<T, 7>(__VA_ARGS__);  break;                              \
-        case 8:  FN<T, 8>(__VA_ARGS__);  break;                              \
-        case 9:  FN<T, 9>(__VA_ARGS__);  break;                              \
-        case 10: FN<T, 10>(__VA_ARGS__); break;                              \
-        case 11: FN<T, 11>(__VA_ARGS__); break;                              \
-        default: FN<T, 12>(__VA_ARGS__); break;                              \
+// f(float{}) or f(double{}): the plan's data type
+template <typename F>
+static int wg_by_type(const WgridPlan& p, F&& f) { return p.dtype == PFB_F32 ? f(float{}) : f(double{}); }
+// f(std::integral_constant<int, W>{}), W = 4 .. 12 (anything else: 12): one instantiation per support, so that the
+// footprint loops unroll and the row of kernel values stays in registers
+template <int W = WG_MIN_W, typename F>
+static int wg_by_support(int w, F&& f) {
+    if constexpr (W < WG_MAX_W) {
+        if (w != W) return wg_by_support<W + 1>(w, f);
     }
+    return f(std::integral_constant<int, W>{});
+}
 
-static size_t wg_esize(int dtype) { return dtype == PFB_F32 ? 4 : 8; }
-static bool wg_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// a pointer argument: what it points to (REAL, CPLX: of the plan's type) and whether it may be null
+enum WgKind { WG_REAL, WG_CPLX, WG_F64, WG_I32, WG_I64 };
+struct WgArray { const void* ptr; WgKind kind; bool optional = false; };
+
+// the plan and the pointers of entry point `name`: none null that may not be, each aligned to its element
+static int wg_check(const void* plan, const char* name, std::initializer_list<WgArray> arrays) {
+    PFB_REQUIRE(plan, PFB_ERR_INVALID, "%s: null plan", name);
+    const size_t e = static_cast<const WgridPlan*>(plan)->esize();
+    for (const WgArray& a : arrays) PFB_REQUIRE(a.ptr || a.optional, PFB_ERR_INVALID, "%s: null argument", name);
+    for (const WgArray& a : arrays) {
+        const size_t align = a.kind == WG_REAL ? e : a.kind == WG_CPLX ? 2 * e : a.kind == WG_I32 ? 4 : 8;
+        PFB_REQUIRE(((uintptr_t)a.ptr & (align - 1)) == 0, PFB_ERR_INVALID, "%s: an array is not aligned to its element size", name);
+    }
+    return PFB_OK;
+}
+static const WgridPlan& wg_plan(const void* plan) { return *static_cast<const WgridPlan*>(plan); }
+
+// the size checks: nrow x nchan visibilities that an int indexes; as many slots; a plane; slots [s0, s1) of a plane,
+// few enough for one launch of k_grid (2 W lanes a slot)
+static int wg_nvis(const char* name, size_t nrow, int nchan) {
+    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff / (size_t)nchan, PFB_ERR_UNSUPPORTED,
+                "%s: %zu rows x %d channels outside [1, 2^31)", name, nrow, nchan);
+    return PFB_OK;
+}
+static int wg_slots(const char* name, size_t nsorted) {
+    PFB_REQUIRE(nsorted >= 1 && nsorted <= (size_t)0x7fffffff, PFB_ERR_INVALID, "%s: %zu slots", name, nsorted);
+    return PFB_OK;
+}
+static int wg_plane(const WgridPlan& p, const char* name, int plane) {
+    PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, "%s: plane %d of %d", name, plane, p.nplanes);
+    return PFB_OK;
+}
+static int wg_range(const WgridPlan& p, const char* name, int plane, size_t s0, size_t s1, size_t nsorted) {
+    if (int rc = wg_plane(p, name, plane); rc != PFB_OK) return rc;
+    PFB_REQUIRE(s0 <= s1 && s1 <= nsorted, PFB_ERR_INVALID, "%s: range [%zu, %zu) of %zu slots", name, s0, s1, nsorted);
+    PFB_REQUIRE((s1 - s0) * 2 * (size_t)p.W <= WG_MAX_THREADS, PFB_ERR_UNSUPPORTED, "%s: %zu slots in one launch", name,
+                s1 - s0);
+    return PFB_OK;
+}
 
 }  // namespace pfb
 
 using namespace pfb;
-
-#define WG_PLAN(name)                                                                        \
-    PFB_REQUIRE(plan, PFB_ERR_INVALID, name ": null plan");                                   \
-    const WgridPlan& p = *static_cast<const WgridPlan*>(plan)
-#define WG_RANGE(name)                                                                                         \
-    PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, name ": plane %d of %d", plane, p.nplanes);   \
-    PFB_REQUIRE(s0 <= s1 && s1 <= nsorted, PFB_ERR_INVALID, name ": range [%zu, %zu) of %zu slots", s0, s1, nsorted); \
-    PFB_REQUIRE((s1 - s0) * 2 * (size_t)p.W <= WG_MAX_THREADS, PFB_ERR_UNSUPPORTED, name ": %zu slots in one launch", s1 - s0)
 
 extern "C" {
 
@@ -398,207 +437,137 @@ int pfb_wgrid_plan_destroy(void* plan) {
 }
 
 int pfb_wgrid_plan_info(void* plan, int* nkeys, int* np0, int* tile) {
-    WG_PLAN("wgrid_plan_info");
+    if (int rc = wg_check(plan, "wgrid_plan_info", {}); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
     if (nkeys) *nkeys = p.nkeys();
     if (np0) *np0 = p.np0;
     if (tile) *tile = p.tile;
     return PFB_OK;
 }
 
-size_t pfb_wgrid_work_bytes(void* plan) {
-    if (!plan) return 0;
-    return 2 * sizeof(int) * (size_t)static_cast<const WgridPlan*>(plan)->nkeys();
-}
+size_t pfb_wgrid_work_bytes(void* plan) { return plan ? 2 * sizeof(int) * (size_t)wg_plan(plan).nkeys() : 0; }
 
 int pfb_wgrid_order_count(void* plan, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow,
                           int nchan, int* keys, void* work, void* stream) {
-    WG_PLAN("wgrid_order_count");
-    PFB_REQUIRE(uvw && freq && keys && work, PFB_ERR_INVALID, "wgrid_order_count: null argument");
-    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff / (size_t)nchan, PFB_ERR_UNSUPPORTED,
-                "wgrid_order_count: %zu rows x %d channels outside [1, 2^31)", nrow, nchan);
-    PFB_REQUIRE(wg_aligned(uvw, 8) && wg_aligned(freq, 8) && wg_aligned(keys, 4) && wg_aligned(work, 4), PFB_ERR_INVALID,
-                "wgrid_order_count: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
+    if (int rc = wg_check(plan, "wgrid_order_count", {{uvw, WG_F64}, {freq, WG_F64}, {keys, WG_I32}, {work, WG_I32}});
+        rc != PFB_OK) return rc;
+    if (int rc = wg_nvis("wgrid_order_count", nrow, nchan); rc != PFB_OK) return rc;
     const size_t nvis = nrow * (size_t)nchan;
-    PFB_HIP_CHECK(hipMemsetAsync(work, 0, pfb_wgrid_work_bytes(plan), st));
-    hipLaunchKernelGGL(k_order_count, dim3(wg_blocks(nvis)), dim3(WG_BLOCK), 0, st, uvw, freq, mask, nvis, nchan,
-                       wg_geom(p), keys, (int*)work);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    PFB_HIP_CHECK(hipMemsetAsync(work, 0, pfb_wgrid_work_bytes(plan), as_stream(stream)));
+    return wg_launch(k_order_count, nvis, stream, uvw, freq, mask, nvis, nchan, wg_geom(wg_plan(plan)), keys, work);
 }
 
 int pfb_wgrid_order_fill(void* plan, const double* uvw, const double* freq, size_t nrow, int nchan, const int* keys,
                          const long long* offsets, void* work, size_t nsorted, int* idx, double* coord, void* stream) {
-    WG_PLAN("wgrid_order_fill");
-    PFB_REQUIRE(uvw && freq && keys && offsets && work && idx && coord, PFB_ERR_INVALID, "wgrid_order_fill: null argument");
-    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff / (size_t)nchan, PFB_ERR_UNSUPPORTED,
-                "wgrid_order_fill: %zu rows x %d channels outside [1, 2^31)", nrow, nchan);
+    if (int rc = wg_check(plan, "wgrid_order_fill", {{uvw, WG_F64}, {freq, WG_F64}, {keys, WG_I32}, {offsets, WG_I64},
+                                                     {work, WG_I32}, {idx, WG_I32}, {coord, WG_F64}});
+        rc != PFB_OK) return rc;
+    if (int rc = wg_nvis("wgrid_order_fill", nrow, nchan); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
     const size_t nvis = nrow * (size_t)nchan;
     PFB_REQUIRE(nsorted >= 1 && nsorted <= nvis, PFB_ERR_INVALID, "wgrid_order_fill: %zu slots for %zu visibilities",
                 nsorted, nvis);
-    PFB_REQUIRE(wg_aligned(offsets, 8) && wg_aligned(coord, 8) && wg_aligned(idx, 4), PFB_ERR_INVALID,
-                "wgrid_order_fill: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_order_fill, dim3(wg_blocks(nvis)), dim3(WG_BLOCK), 0, st, uvw, freq, nvis, nchan, wg_geom(p),
-                       keys, offsets, (int*)work + p.nkeys(), nsorted, idx, coord);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return wg_launch(k_order_fill, nvis, stream, uvw, freq, nvis, nchan, wg_geom(p), keys, offsets, (int*)work + p.nkeys(),
+                     nsorted, idx, coord);
 }
-
-#define WG_SLOTS(name)                                                                                             \
-    PFB_REQUIRE(nsorted >= 1 && nsorted <= (size_t)0x7fffffff, PFB_ERR_INVALID, name ": %zu slots", nsorted);      \
-    PFB_REQUIRE(idx && coord, PFB_ERR_INVALID, name ": null order")
 
 int pfb_wgrid_prep(void* plan, const void* vis, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                    void* val, void* stream) {
-    WG_PLAN("wgrid_prep");
-    WG_SLOTS("wgrid_prep");
-    PFB_REQUIRE(vis && val, PFB_ERR_INVALID, "wgrid_prep: null argument");
-    PFB_REQUIRE(wg_aligned(vis, 2 * wg_esize(p.dtype)) && wg_aligned(val, 2 * wg_esize(p.dtype)) &&
-                wg_aligned(wgt, wg_esize(p.dtype)), PFB_ERR_INVALID, "wgrid_prep: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    const double cxs = p.cx / (p.px * p.Nu), cys = p.cy / (p.py * p.Nv);
-    const int centre = p.cx != 0.0 || p.cy != 0.0;
-    if (p.dtype == PFB_F32)
-        hipLaunchKernelGGL(k_prep<float>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)vis,
-                           (const float*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<float>*)val);
-    else
-        hipLaunchKernelGGL(k_prep<double>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)vis,
-                           (const double*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<double>*)val);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_prep", {{vis, WG_CPLX}, {wgt, WG_REAL, true}, {idx, WG_I32}, {coord, WG_F64},
+                                               {val, WG_CPLX}});
+        rc != PFB_OK) return rc;
+    if (int rc = wg_slots("wgrid_prep", nsorted); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    return wg_by_type(p, [&](auto t) {
+        return wg_launch(k_prep<decltype(t)>, nsorted, stream, vis, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), val);
+    });
 }
 
 int pfb_wgrid_finish(void* plan, const void* acc, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                      void* vis, size_t nvis, void* stream) {
-    WG_PLAN("wgrid_finish");
-    WG_SLOTS("wgrid_finish");
-    PFB_REQUIRE(acc && vis && nsorted <= nvis && nvis <= (size_t)0x7fffffff, PFB_ERR_INVALID,
-                "wgrid_finish: null argument, or %zu slots for %zu visibilities", nsorted, nvis);
-    PFB_REQUIRE(wg_aligned(vis, 2 * wg_esize(p.dtype)) && wg_aligned(acc, 2 * wg_esize(p.dtype)) &&
-                wg_aligned(wgt, wg_esize(p.dtype)), PFB_ERR_INVALID, "wgrid_finish: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    const double cxs = p.cx / (p.px * p.Nu), cys = p.cy / (p.py * p.Nv);
-    const int centre = p.cx != 0.0 || p.cy != 0.0;
-    PFB_HIP_CHECK(hipMemsetAsync(vis, 0, 2 * wg_esize(p.dtype) * nvis, st));
-    if (p.dtype == PFB_F32)
-        hipLaunchKernelGGL(k_finish<float>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)acc,
-                           (const float*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<float>*)vis);
-    else
-        hipLaunchKernelGGL(k_finish<double>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)acc,
-                           (const double*)wgt, idx, coord, nsorted, cxs, cys, centre, (cplx<double>*)vis);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_finish", {{acc, WG_CPLX}, {wgt, WG_REAL, true}, {idx, WG_I32}, {coord, WG_F64},
+                                                 {vis, WG_CPLX}});
+        rc != PFB_OK) return rc;
+    if (int rc = wg_slots("wgrid_finish", nsorted); rc != PFB_OK) return rc;
+    PFB_REQUIRE(nsorted <= nvis && nvis <= (size_t)0x7fffffff, PFB_ERR_INVALID,
+                "wgrid_finish: %zu slots for %zu visibilities", nsorted, nvis);
+    const WgridPlan& p = wg_plan(plan);
+    PFB_HIP_CHECK(hipMemsetAsync(vis, 0, 2 * p.esize() * nvis, as_stream(stream)));
+    return wg_by_type(p, [&](auto t) {
+        return wg_launch(k_finish<decltype(t)>, nsorted, stream, acc, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), vis);
+    });
 }
 
 int pfb_wgrid_weight(void* plan, const void* acc, const void* wgt, const int* idx, size_t nsorted, void* val,
                      void* stream) {
-    WG_PLAN("wgrid_weight");
-    PFB_REQUIRE(nsorted >= 1 && nsorted <= (size_t)0x7fffffff && acc && val && idx, PFB_ERR_INVALID,
-                "wgrid_weight: null argument or %zu slots", nsorted);
-    PFB_REQUIRE(wg_aligned(val, 2 * wg_esize(p.dtype)) && wg_aligned(acc, 2 * wg_esize(p.dtype)) &&
-                wg_aligned(wgt, wg_esize(p.dtype)), PFB_ERR_INVALID, "wgrid_weight: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    if (p.dtype == PFB_F32)
-        hipLaunchKernelGGL(k_weight<float>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)acc,
-                           (const float*)wgt, idx, nsorted, (cplx<float>*)val);
-    else
-        hipLaunchKernelGGL(k_weight<double>, dim3(wg_blocks(nsorted)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)acc,
-                           (const double*)wgt, idx, nsorted, (cplx<double>*)val);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_weight", {{acc, WG_CPLX}, {wgt, WG_REAL, true}, {idx, WG_I32}, {val, WG_CPLX}});
+        rc != PFB_OK) return rc;
+    if (int rc = wg_slots("wgrid_weight", nsorted); rc != PFB_OK) return rc;
+    return wg_by_type(wg_plan(plan), [&](auto t) {
+        return wg_launch(k_weight<decltype(t)>, nsorted, stream, acc, wgt, idx, nsorted, val);
+    });
 }
 
 int pfb_wgrid_grid(void* plan, int plane, const void* val, const double* coord, size_t nsorted, size_t s0, size_t s1,
                    void* grid, void* stream) {
-    WG_PLAN("wgrid_grid");
-    WG_RANGE("wgrid_grid");
-    PFB_REQUIRE(val && coord && grid, PFB_ERR_INVALID, "wgrid_grid: null argument");
-    PFB_REQUIRE(wg_aligned(val, 2 * wg_esize(p.dtype)) && wg_aligned(grid, 2 * wg_esize(p.dtype)) && wg_aligned(coord, 8),
-                PFB_ERR_INVALID, "wgrid_grid: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, 2 * wg_esize(p.dtype) * (size_t)p.Nu * p.Nv, st));
-    if (s1 > s0) {
-        if (p.dtype == PFB_F32) { WG_BY_SUPPORT(wg_launch_grid, float, p.W, p, plane, val, coord, nsorted, s0, s1, grid, st) }
-        else { WG_BY_SUPPORT(wg_launch_grid, double, p.W, p, plane, val, coord, nsorted, s0, s1, grid, st) }
-    }
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_grid", {{val, WG_CPLX}, {coord, WG_F64}, {grid, WG_CPLX}}); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_range(p, "wgrid_grid", plane, s0, s1, nsorted); rc != PFB_OK) return rc;
+    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes(), as_stream(stream)));
+    if (s1 == s0) return PFB_OK;
+    return wg_by_type(p, [&](auto t) {
+        return wg_by_support(p.W, [&](auto w) {
+            return wg_launch(k_grid<decltype(t), w()>, (s1 - s0) * 2 * w(), stream, val, coord, nsorted, s0, s1, plane,
+                             wg_geom(p), grid);
+        });
+    });
 }
 
 int pfb_wgrid_degrid(void* plan, int plane, const void* grid, const double* coord, size_t nsorted, size_t s0, size_t s1,
                      void* acc, void* stream) {
-    WG_PLAN("wgrid_degrid");
-    WG_RANGE("wgrid_degrid");
-    PFB_REQUIRE(acc && coord && grid, PFB_ERR_INVALID, "wgrid_degrid: null argument");
-    PFB_REQUIRE(wg_aligned(acc, 2 * wg_esize(p.dtype)) && wg_aligned(grid, 2 * wg_esize(p.dtype)) && wg_aligned(coord, 8),
-                PFB_ERR_INVALID, "wgrid_degrid: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    if (s1 > s0) {
-        if (p.dtype == PFB_F32) { WG_BY_SUPPORT(wg_launch_degrid, float, p.W, p, plane, grid, coord, nsorted, s0, s1, acc, st) }
-        else { WG_BY_SUPPORT(wg_launch_degrid, double, p.W, p, plane, grid, coord, nsorted, s0, s1, acc, st) }
-    }
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_degrid", {{grid, WG_CPLX}, {coord, WG_F64}, {acc, WG_CPLX}}); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_range(p, "wgrid_degrid", plane, s0, s1, nsorted); rc != PFB_OK) return rc;
+    if (s1 == s0) return PFB_OK;
+    return wg_by_type(p, [&](auto t) {
+        return wg_by_support(p.W, [&](auto w) {
+            return wg_launch(k_degrid<decltype(t), w()>, s1 - s0, stream, grid, coord, nsorted, s0, s1, plane, wg_geom(p), acc);
+        });
+    });
 }
 
 int pfb_wgrid_image_forward(void* plan, int plane, const void* dirty, const void* beam, const double* corr,
                             const double* nm1, void* grid, void* stream) {
-    WG_PLAN("wgrid_image_forward");
-    PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, "wgrid_image_forward: plane %d of %d", plane, p.nplanes);
-    PFB_REQUIRE(dirty && corr && grid, PFB_ERR_INVALID, "wgrid_image_forward: null argument");
-    PFB_REQUIRE(wg_aligned(dirty, wg_esize(p.dtype)) && wg_aligned(beam, wg_esize(p.dtype)) && wg_aligned(corr, 8) &&
-                wg_aligned(nm1, 8) && wg_aligned(grid, 2 * wg_esize(p.dtype)), PFB_ERR_INVALID,
-                "wgrid_image_forward: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    const size_t npix = (size_t)p.nx * p.ny;
-    const double wp = p.w0 + plane * (p.wkernel() ? p.dw : 0.0);
-    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, 2 * wg_esize(p.dtype) * (size_t)p.Nu * p.Nv, st));
-    if (p.dtype == PFB_F32)
-        hipLaunchKernelGGL(k_image_forward<float>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const float*)dirty,
-                           (const float*)beam, corr, nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<float>*)grid);
-    else
-        hipLaunchKernelGGL(k_image_forward<double>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const double*)dirty,
-                           (const double*)beam, corr, nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<double>*)grid);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_image_forward", {{dirty, WG_REAL}, {beam, WG_REAL, true}, {corr, WG_F64},
+                                                        {nm1, WG_F64, true}, {grid, WG_CPLX}});
+        rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_plane(p, "wgrid_image_forward", plane); rc != PFB_OK) return rc;
+    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes(), as_stream(stream)));
+    return wg_by_type(p, [&](auto t) {
+        return wg_launch(k_image_forward<decltype(t)>, p.npix(), stream, dirty, beam, corr, nm1, p.wp(plane), p.nx, p.ny,
+                         p.Nu, p.Nv, grid);
+    });
 }
 
 int pfb_wgrid_image_adjoint(void* plan, int plane, const void* grid, const double* nm1, void* img, void* stream) {
-    WG_PLAN("wgrid_image_adjoint");
-    PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, "wgrid_image_adjoint: plane %d of %d", plane, p.nplanes);
-    PFB_REQUIRE(grid && img, PFB_ERR_INVALID, "wgrid_image_adjoint: null argument");
-    PFB_REQUIRE(wg_aligned(img, 2 * wg_esize(p.dtype)) && wg_aligned(nm1, 8) && wg_aligned(grid, 2 * wg_esize(p.dtype)),
-                PFB_ERR_INVALID, "wgrid_image_adjoint: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    const size_t npix = (size_t)p.nx * p.ny;
-    const double wp = p.w0 + plane * (p.wkernel() ? p.dw : 0.0);
-    if (p.dtype == PFB_F32)
-        hipLaunchKernelGGL(k_image_adjoint<float>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)grid,
-                           nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<float>*)img);
-    else
-        hipLaunchKernelGGL(k_image_adjoint<double>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)grid,
-                           nm1, wp, p.nx, p.ny, p.Nu, p.Nv, (cplx<double>*)img);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_image_adjoint", {{grid, WG_CPLX}, {nm1, WG_F64, true}, {img, WG_CPLX}});
+        rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_plane(p, "wgrid_image_adjoint", plane); rc != PFB_OK) return rc;
+    return wg_by_type(p, [&](auto t) {
+        return wg_launch(k_image_adjoint<decltype(t)>, p.npix(), stream, grid, nm1, p.wp(plane), p.nx, p.ny, p.Nu, p.Nv, img);
+    });
 }
 
 int pfb_wgrid_image_correct(void* plan, const void* img, const double* corr, const void* beam, void* dirty, void* stream) {
-    WG_PLAN("wgrid_image_correct");
-    PFB_REQUIRE(img && corr && dirty, PFB_ERR_INVALID, "wgrid_image_correct: null argument");
-    PFB_REQUIRE(wg_aligned(img, 2 * wg_esize(p.dtype)) && wg_aligned(corr, 8) && wg_aligned(beam, wg_esize(p.dtype)) &&
-                wg_aligned(dirty, wg_esize(p.dtype)), PFB_ERR_INVALID,
-                "wgrid_image_correct: an array is not aligned to its element size");
-    hipStream_t st = as_stream(stream);
-    const size_t npix = (size_t)p.nx * p.ny;
-    if (p.dtype == PFB_F32)
-        hipLaunchKernelGGL(k_image_correct<float>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<float>*)img,
-                           corr, (const float*)beam, npix, (float*)dirty);
-    else
-        hipLaunchKernelGGL(k_image_correct<double>, dim3(wg_blocks(npix)), dim3(WG_BLOCK), 0, st, (const cplx<double>*)img,
-                           corr, (const double*)beam, npix, (double*)dirty);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    if (int rc = wg_check(plan, "wgrid_image_correct", {{img, WG_CPLX}, {corr, WG_F64}, {beam, WG_REAL, true},
+                                                        {dirty, WG_REAL}});
+        rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    return wg_by_type(p, [&](auto t) {
+        return wg_launch(k_image_correct<decltype(t)>, p.npix(), stream, img, corr, beam, p.npix(), dirty);
+    });
 }
 
 }  // extern "C"

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _dev, _lib
-from .._plan import NativePlan, PlanCache
+from .._plan import NativePlan, PlanCache, array_key
 
 C_LIGHT = 299792458.0
 EPS_MAX = 1e-2
@@ -44,26 +44,30 @@ def check_epsilon(epsilon, rdtype):
     return eps
 
 
+def _quadrature(W):
+    """(x, f) of the correction integral below: the Gauss-Legendre nodes in theta as x = sin(theta) -- a node's
+    frequency in t is 2 pi h x -- and phi(x) cos(theta) times the node's weight."""
+    th, wq = np.polynomial.legendre.leggauss(_QUAD_NODES)
+    th, wq = th * (np.pi / 2), wq * (np.pi / 2)
+    return np.sin(th), np.exp(2.3 * W * (np.cos(th) - 1.0)) * np.cos(th) * wq
+
+
 def kernel_correction(W, t):
     """c(t) = h int_-1^1 phi(x) cos(2 pi h t x) dx, h = W / 2, phi(x) = exp(2.3 W (sqrt(1 - x^2) - 1)): Gauss-Legendre
     in theta, x = sin(theta), where the integrand is smooth up to the ends.  fp64 on the host."""
     t = np.asarray(t, dtype=np.float64)
     h = 0.5 * W
-    th, wq = np.polynomial.legendre.leggauss(_QUAD_NODES)
-    th, wq = th * (np.pi / 2), wq * (np.pi / 2)
-    f = np.exp(2.3 * W * (np.cos(th) - 1.0)) * np.cos(th) * wq
-    return h * (np.cos(2 * np.pi * h * t[..., None] * np.sin(th)) * f).sum(-1)
+    x, f = _quadrature(W)
+    return h * (np.cos(2 * np.pi * h * t[..., None] * x) * f).sum(-1)
 
 
 def _kernel_correction_dev(W, t):
     """kernel_correction on a device fp64 tensor, node by node: the (nx, ny) table of the w axis is summed where it
     will live instead of as an (nx, ny, nodes) array on the host."""
     h = 0.5 * W
-    th, wq = np.polynomial.legendre.leggauss(_QUAD_NODES)
-    th, wq = th * (np.pi / 2), wq * (np.pi / 2)
-    f = np.exp(2.3 * W * (np.cos(th) - 1.0)) * np.cos(th) * wq
+    x, f = _quadrature(W)
     acc = torch.zeros_like(t)
-    for a, fq in zip(2 * np.pi * h * np.sin(th), f):
+    for a, fq in zip(2 * np.pi * h * x, f):
         acc.add_(torch.cos(t * float(a)), alpha=float(fq))
     return acc.mul_(h)
 
@@ -267,25 +271,13 @@ _cache = PlanCache(8)
 cache_stats = {'miss': 0}           # plans built (each builds one order): the tests count these
 
 
-def _fingerprint(a):
-    if a is None:
-        return None
-    if isinstance(a, np.ndarray):
-        flat = a.reshape(-1)
-        samp = flat[::max(1, flat.size // 257)][:257]
-        return ('np', a.__array_interface__['data'][0], a.shape, str(a.dtype), a.strides,
-                float(np.asarray(samp, dtype=np.float64).sum()))
-    if isinstance(a, torch.Tensor):
-        return ('t', a.data_ptr(), tuple(a.shape), str(a.dtype), a._version, str(a.device))
-    return ('o', id(a))
-
-
 def plan_for(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, rdtype):
-    """The cached plan of these arrays on this geometry.  numpy arrays are keyed on address, layout and a strided
-    content sample, tensors on data_ptr and version counter; the entry keeps the arrays alive, so that their memory
-    cannot come back as DIFFERENT data under the same key (clear_plan_cache() releases plans and references)."""
-    key = (_fingerprint(uvw), _fingerprint(freq), _fingerprint(mask), int(nx), int(ny), float(pixsize_x),
-           float(pixsize_y), float(center_x), float(center_y), float(epsilon), bool(do_wgridding), str(rdtype))
+    """The cached plan of these arrays on this geometry.  The arrays are keyed by _plan.array_key (numpy: address, layout
+    and a strided content sample; tensors: data_ptr and version counter); the entry keeps the arrays alive, so that
+    their memory cannot come back as DIFFERENT data under the same key (clear_plan_cache() releases plans and
+    references)."""
+    key = (array_key(uvw), array_key(freq), array_key(mask), int(nx), int(ny), float(pixsize_x), float(pixsize_y),
+           float(center_x), float(center_y), float(epsilon), bool(do_wgridding), str(rdtype))
 
     def make():
         cache_stats['miss'] += 1

@@ -18,11 +18,10 @@ with functools.partial (workers/spotless.py:175-183).
 import ctypes as C
 import threading
 
-import numpy as np
 import torch
 
 from .. import _lib, _dev
-from .._plan import NativePlan, PlanCache
+from .._plan import NativePlan, PlanCache, array_key
 
 
 def _pow2ceil(n):
@@ -349,24 +348,13 @@ class PsfConvPlan(NativePlan):
 _cache = PlanCache(8)
 
 
-def _fingerprint(psfhat):
-    if isinstance(psfhat, np.ndarray):
-        flat = psfhat.reshape(-1)
-        step = max(1, flat.size // 257)
-        samp = flat[::step][:257]
-        return ('np', psfhat.__array_interface__['data'][0], psfhat.shape, str(psfhat.dtype),
-                complex(samp.sum()))
-    return ('t', psfhat.data_ptr(), tuple(psfhat.shape), str(psfhat.dtype), psfhat._version,
-            str(psfhat.device))
-
-
 def plan_for(psfhat, nx, ny, lastsize):
     """Plan cache for the reference-shaped call sites (a functools.partial re-presents the same
-    psfhat on every call).  numpy arrays are keyed on address + shape + a strided content sample;
-    tensors on data_ptr + shape + version counter, and the cache entry keeps a reference to the
-    tensor so that its memory cannot be freed and re-used by a DIFFERENT psfhat at the same
-    address while the entry lives (clear_plan_cache() releases plans and references)."""
-    key = (_fingerprint(psfhat), int(nx), int(ny), int(lastsize))
+    psfhat on every call).  The key is _plan.array_key: numpy arrays on address + layout + a strided
+    content sample; tensors on data_ptr + shape + version counter, and the cache entry keeps a
+    reference to the tensor so that its memory cannot be freed and re-used by a DIFFERENT psfhat at
+    the same address while the entry lives (clear_plan_cache() releases plans and references)."""
+    key = (array_key(psfhat), int(nx), int(ny), int(lastsize))
     return _cache.get(key, lambda: (PsfConvPlan(psfhat, nx, ny, lastsize),
                                     psfhat if isinstance(psfhat, torch.Tensor) else None))[0]
 

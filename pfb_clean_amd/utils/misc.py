@@ -16,7 +16,7 @@ import torch
 
 from .. import _lib, _dev
 from .._dev import norm_diff_sums
-from .._plan import PlanCache
+from .._plan import PlanCache, array_key
 from ..operators.psf import PsfConvPlan
 from .comps import fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice  # noqa: F401
 from .beamfit import fitcleanbeam  # noqa: F401
@@ -314,12 +314,13 @@ def clear_beam_cache():
 
 def _coord_key(a):
     """Content fingerprint of a coordinate array (the caller may rebuild xx, yy for every call): shape, dtype and a
-    strided sample for numpy; identity + version for a device tensor, which the cache entry keeps alive."""
+    strided sample for numpy; identity + version (array_key) for a device tensor, which the cache entry keeps alive."""
     if isinstance(a, np.ndarray):
+        # no address in this key, on purpose: the rebuilt xx, yy of the next call are the same coordinates elsewhere
         flat = a.reshape(-1)
         samp = flat[::max(1, flat.size // 257)][:257]
         return ('np', a.shape, str(a.dtype), float(flat[0]), float(flat[-1]), float(samp.sum()))
-    return ('t', a.data_ptr(), tuple(a.shape), str(a.dtype), a._version, str(a.device))
+    return array_key(a)
 
 
 def _model_plan(xd, yd, gausspars, nx, ny, rdtype, pfrac, norm_kernel):

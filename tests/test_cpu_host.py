@@ -120,7 +120,7 @@ def test_shard_bands():
 
 
 def test_plan_cache_fingerprint_distinguishes_content():
-    from pfb_clean_amd.operators.psf import _fingerprint
+    from pfb_clean_amd._plan import array_key as _fingerprint        # the key of operators/psf.py's plan cache
     a = np.zeros((2, 16, 9), dtype=np.complex128)
     fa = _fingerprint(a)
     a[1, 3, 4] = 1.0
@@ -128,6 +128,42 @@ def test_plan_cache_fingerprint_distinguishes_content():
     a[...] = 2.0
     assert _fingerprint(a) != fa              # ... but never a rewrite of the array
     assert _fingerprint(a[0]) != _fingerprint(a[1]) or a[0].__array_interface__['data'][0] != a[1].__array_interface__['data'][0]
+
+
+def test_array_key():
+    """_plan.array_key, the one key of the psf, gridder and beam plan caches: equal for the array presented again,
+    different for another address, other contents at a sampled position, another layout of the same buffer, or a
+    tensor written in place."""
+    import torch
+    from pfb_clean_amd._plan import array_key
+    a = np.arange(40 * 40, dtype=np.float64).reshape(40, 40)          # 1600 elements: every 6th is sampled
+    a = a + a.T                                                       # symmetric: a.T differs in its strides alone
+    ka = array_key(a)
+    assert array_key(a) == ka and hash(ka) == hash(array_key(a))
+    assert array_key(a.copy()) != ka                                  # the same numbers at another address
+    assert array_key(a.T) != ka and a.T.shape == a.shape              # the same buffer and shape, other strides
+    a[0, 6] += 1.0                                                    # flat index 6: a sampled position
+    assert array_key(a) != ka
+    # the imaginary part counts
+    z = np.ones(1000, dtype=np.complex128)
+    kz = array_key(z)
+    z.imag[::3] = 0.5                                                 # step 1000 // 257 = 3: sampled positions
+    assert array_key(z) != kz
+    # the masks the gridder passes
+    for dt in (np.bool_, np.uint8):
+        m = np.zeros((63, 3), dtype=dt)
+        km = array_key(m)
+        assert array_key(m) == km
+        m[0, 0] = 1
+        assert array_key(m) != km
+    t = torch.zeros(8, dtype=torch.float64)
+    kt = array_key(t)
+    assert array_key(t) == kt and array_key(t.clone()) != kt
+    t.add_(1.0)
+    assert array_key(t) != kt
+    assert array_key(None) is None
+    o = [1.0, 2.0]
+    assert array_key(o) == ('o', id(o))
 
 
 def test_plan_cache_evicts_the_oldest_and_never_destroys_a_plan_still_held():

@@ -71,6 +71,23 @@ def test_correction_tables_against_brute_force(W):
     assert np.abs(wc.correction(W, ts, nodes=256) - got).max() <= 1e-14 * got[0]
 
 
+@pytest.mark.parametrize('W', [4, 9, 12])
+def test_correction_tables_keep_their_bits(W):
+    """kernel_correction through the shared quadrature against the formula as it stood before there was one, operation
+    for operation: the same bits."""
+    from pfb_clean_amd.operators import gridder
+    t = np.linspace(-0.25, 0.25, 33)
+    h = 0.5 * W
+    th, wq = np.polynomial.legendre.leggauss(128)
+    th, wq = th * (np.pi / 2), wq * (np.pi / 2)
+    f = np.exp(2.3 * W * (np.cos(th) - 1.0)) * np.cos(th) * wq
+    was = h * (np.cos(2 * np.pi * h * t[..., None] * np.sin(th)) * f).sum(-1)
+    assert np.array_equal(gridder.kernel_correction(W, t), was)
+    # the device table's nodes: the same frequencies and weights, in the same order
+    x, fq = gridder._quadrature(W)
+    assert np.array_equal(2 * np.pi * h * x, 2 * np.pi * h * np.sin(th)) and np.array_equal(fq, f)
+
+
 _model_err = {}
 
 

@@ -299,3 +299,82 @@ def test_plan_reuse_builds_no_new_order():
     uvw.mul_(1.0)
     gridder.dirty2vis(uvw, freq, x, mask=mask, **kws)
     assert gridder.cache_stats['miss'] == n + 1
+
+
+# ------------------------------------------------------------------------------------------- the native refusals
+def test_native_entry_points_refuse_as_before():
+    """What csrc/wgrid.hip refuses, status by status, through the C ABI itself.  Every case but the last is refused
+    before any launch; the pointers are real device arrays all the same, so that a check that wrongly let one through
+    would address nothing wild."""
+    import ctypes as C
+    from pfb_clean_amd import _lib
+    lib = _lib.load()
+    OK, INV, UNS = _lib.PFB_OK, _lib.PFB_ERR_INVALID, _lib.PFB_ERR_UNSUPPORTED
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def create(dtype=_lib.PFB_F32, nx=16, ny=16, support=4, nplanes=1, w0=0.0, dw=1.0):
+        h = C.c_void_p()
+        return lib.pfb_wgrid_plan_create(dtype, nx, ny, 1e-3, 1e-3, 0.0, 0.0, support, nplanes, w0, dw, C.byref(h)), h
+
+    assert lib.pfb_wgrid_plan_create(_lib.PFB_F32, 16, 16, 1e-3, 1e-3, 0.0, 0.0, 4, 1, 0.0, 1.0, None) == INV
+    assert create(dtype=2)[0] == INV
+    assert create(support=3)[0] == UNS and create(support=13)[0] == UNS
+    assert create(nx=15)[0] == INV
+    assert create(nplanes=2)[0] == INV and create(nplanes=4)[0] == INV       # nplanes == 1 || nplanes > support
+    assert lib.pfb_wgrid_plan_info(None, None, None, None) == INV
+
+    def call(name, args):
+        return getattr(lib, 'pfb_wgrid_' + name)(*args, stream)
+
+    def changed(args, **at):
+        out = list(args)
+        for k, v in at.items():
+            out[int(k[1:])] = v
+        return out
+
+    # entry point -> positions of the plane, the slot count and the required pointers in its argument list
+    where = {'order_count': (None, None, (1, 2, 6, 7)), 'order_fill': (None, None, (1, 2, 5, 6, 7, 9, 10)),
+             'prep': (None, 5, (1, 3, 4, 6)), 'finish': (None, 5, (1, 3, 4, 6)), 'weight': (None, 4, (1, 3, 5)),
+             'grid': (1, None, (2, 3, 7)), 'degrid': (1, None, (2, 3, 7)), 'image_forward': (1, None, (2, 4, 6)),
+             'image_adjoint': (1, None, (2, 4)), 'image_correct': (None, None, (1, 2, 4))}
+    plans = []
+    try:
+        for dtype, rdt, cdt, nplanes in ((_lib.PFB_F32, torch.float32, torch.complex64, 1),
+                                         (_lib.PFB_F64, torch.float64, torch.complex128, 6)):
+            rc, h = create(dtype=dtype, nplanes=nplanes)
+            assert rc == OK
+            plans.append(h)
+            n, nrow, nchan = 8, 4, 2
+            bufs = [torch.zeros(32 * 32 + 1, dtype=cdt, device='cuda'), torch.zeros(16 * 16 + 1, dtype=rdt, device='cuda'),
+                    torch.zeros(16 * 16 + 1, dtype=torch.float64, device='cuda'),
+                    torch.zeros(64, dtype=torch.int32, device='cuda'), torch.zeros(16, dtype=torch.int64, device='cuda')]
+            c, r, f64, i32, i64 = (b.data_ptr() for b in bufs)
+            good = {'order_count': [h, f64, f64, None, nrow, nchan, i32, i32],
+                    'order_fill': [h, f64, f64, nrow, nchan, i32, i64, i32, n, i32, f64],
+                    'prep': [h, c, r, i32, f64, n, c], 'finish': [h, c, r, i32, f64, n, c, n],
+                    'weight': [h, c, r, i32, n, c], 'grid': [h, 0, c, f64, n, 0, n, c],
+                    'degrid': [h, 0, c, f64, n, 0, n, c], 'image_forward': [h, 0, r, r, f64, f64, c],
+                    'image_adjoint': [h, 0, c, f64, c], 'image_correct': [h, c, f64, r, r]}
+            for name, args in good.items():
+                plane, slots, required = where[name]
+                assert call(name, changed(args, a0=None)) == INV, name
+                if plane is not None:
+                    assert call(name, changed(args, a1=-1)) == INV and call(name, changed(args, a1=nplanes)) == INV, name
+                if slots is not None:
+                    assert call(name, changed(args, **{f'a{slots}': 0})) == INV, name
+                for k in required:
+                    assert call(name, changed(args, **{f'a{k}': None})) == INV, (name, k)
+            for name in ('grid', 'degrid'):
+                assert call(name, changed(good[name], a5=5, a6=4)) == INV and call(name, changed(good[name], a6=n + 1)) == INV
+            # each kind of pointer off by half its element
+            half_r = bufs[1].element_size() // 2
+            assert call('prep', changed(good['prep'], a1=c + 2 * half_r)) == INV           # complex of the plan's type
+            assert call('prep', changed(good['prep'], a2=r + half_r)) == INV               # real of the plan's type
+            assert call('grid', changed(good['grid'], a3=f64 + 4)) == INV                  # fp64 coord
+            assert call('order_fill', changed(good['order_fill'], a9=i32 + 2)) == INV      # int32 idx
+            # the optional pointers may be null: one launch on 16 x 16
+            assert call('image_correct', changed(good['image_correct'], a3=None)) == OK
+            torch.cuda.synchronize()
+    finally:
+        for h in plans:
+            lib.pfb_wgrid_plan_destroy(h)
