@@ -151,8 +151,24 @@ def test_table_covers_every_axis_and_edge():
             by_edge.setdefault(e, []).append(c)
     # ---- axes
     f64 = [c for c in CASES if c['dtype'] == 'f64']
-    for image in wc.IMAGES:
+    assert list(wc.IMAGES)[:3] == ['32x24', '48x16', '16x64']
+    for image in list(wc.IMAGES)[:3]:
         assert {c['eps'] for c in f64 if c['image'] == image} >= {1e-3, 1e-5, 1e-7, 1e-9}
+    # every support 4 .. 12 is launched, the first and the last rung of the dispatch included (W = 6 in fp32 only:
+    # test_gpu_wgrid_kernels.py runs every support in both types)
+    assert {wc.support(c['eps']) for c in CASES} == set(range(4, 13))
+    assert {wc.support(c['eps']) for c in f64} == set(range(4, 13)) - {6}
+    for W in (4, 10, 12):
+        assert any(wc.support(c['eps']) == W and (c['nx'] * c['ny']) % 256 != 0 for c in f64)
+    # a partial last block of the image kernels, nx / 2 and ny / 2 odd, and a grid exactly as wide as the footprint
+    for c in by_edge['partial_block']:
+        assert (c['nx'] * c['ny']) % 256 != 0 and (c['nx'] // 2) % 2 == 1
+        assert c['wgt'] is not None and 0 < c['mask'].sum() < c['mask'].size and c['uvw'].shape[0] == 257
+    assert any(c['nx'] * c['ny'] > 256 for c in by_edge['partial_block'])
+    assert any(c['nx'] * c['ny'] < 256 for c in by_edge['partial_block'])
+    narrow = by_edge['grid_eq_support']
+    assert {(2 * c['nx'] == wc.support(c['eps']), 2 * c['ny'] == wc.support(c['eps'])) for c in narrow} \
+        == {(True, False), (False, True)}
     assert {c['eps'] for c in CASES if c['dtype'] == 'f32'} == {1e-3, 1e-4}
     shapes = {(c['uvw'].shape[0], c['freq'].size) for c in CASES}
     assert {n for n, _ in shapes} >= {1, 63, 65, 257} and {k for _, k in shapes} == {1, 3}

@@ -4,7 +4,7 @@ the direct Fourier sums of tests/wgrid_cases.py.
 
 Bounds
   accuracy      ducc0's statement: |result - exact|_2 / |exact|_2 <= epsilon, every case, both directions.
-                tests/test_cpu_wgrid.py shows that the recipe in exact arithmetic sits at 0.11 - 0.28 epsilon on these
+                tests/test_cpu_wgrid.py shows that the recipe in exact arithmetic sits at 0.11 - 0.51 epsilon on these
                 cases, so the bound leaves room for rounding only.  An all-zero mask gives exact zeros.
   adjointness   Re<v, dirty2vis(d)> against <vis2dirty(v), d>, fp64, relative to the product, worst of four random
                 pairs.  The two sides differ by rounding and summation order alone, as they do in the numpy model: the

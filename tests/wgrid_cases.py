@@ -14,7 +14,9 @@ import math
 import numpy as np
 
 C_LIGHT = 299792458.0
-IMAGES = {'32x24': (32, 24, 0.012, 0.03), '48x16': (48, 16, 0.012, 0.03), '16x64': (16, 64, 0.03, 0.008)}
+IMAGES = {'32x24': (32, 24, 0.012, 0.03), '48x16': (48, 16, 0.012, 0.03), '16x64': (16, 64, 0.03, 0.008),
+          # npix % 256 != 0, nx / 2 and ny / 2 odd; 6x8 and 10x6: a grid as narrow as the footprint of W = 12
+          '34x26': (34, 26, 0.012, 0.03), '6x8': (6, 8, 0.05, 0.04), '10x6': (10, 6, 0.05, 0.06)}
 
 
 # ------------------------------------------------------------------------------------------------- the contract
@@ -273,7 +275,7 @@ def _build():
     rows = [(257, 1), (63, 3), (65, 3), (85, 3)]
     wmaxs = [20.0, 60.0, 200.0]
     k = 0
-    for image in IMAGES:
+    for image in ('32x24', '48x16', '16x64'):
         for eps in (1e-3, 1e-5, 1e-7, 1e-9):
             nrow, nchan = rows[k % 4]
             add(make_case(f'{image}-eps{eps:g}', image, eps, 100 + k, nrow=nrow, nchan=nchan, wmax=wmaxs[k % 3],
@@ -332,6 +334,11 @@ def _build():
         wp[0] = -15.0                                                                  # wmin itself
         add(make_case(f'w-planes-{tag}', '32x24', eps, 405, uvw_wl=np.stack([u, v, wp], 1),
                       edges=('w_on_plane', 'w_half_plane')))
+    # ---- the supports no case above launches (W = 4, 10, 12), on images of npix % 256 != 0 and on grids of W cells
+    for j, (image, eps) in enumerate((('34x26', 1e-2), ('34x26', 1e-8), ('34x26', 1e-10), ('6x8', 1e-2), ('6x8', 1e-10),
+                                      ('10x6', 1e-10))):
+        add(make_case(f'{image}-eps{eps:g}', image, eps, 500 + j, wgt=True, mask='partial',
+                      edges=('partial_block',) + (('grid_eq_support',) if image != '34x26' and eps == 1e-10 else ())))
     return cases
 
 
