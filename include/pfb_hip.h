@@ -764,6 +764,60 @@ int pfb_wgrid_image_adjoint(void* plan, int plane, const void* grid, const doubl
 /* dirty = Re(img) corr [beam]. */
 int pfb_wgrid_image_correct(void* plan, const void* img, const double* corr, const void* beam, void* dirty, void* stream);
 
+/* --------------------------------------------------------------------- imaging weights
+ * pfb/utils/weighting.py:43-171 (_compute_counts, _counts_to_weights) and the l2reweight_dof block of
+ * pfb/operators/gridder.py:604-615.  No plan: every function is one asynchronous launch (behind a clear
+ * of what it accumulates into) on `stream`.  `dtype` is the type T of counts and weights; visibilities are complex T.
+ * uvw (nrow, 3) and freq (nchan) are double, mask (nrow, nchan) is unsigned char and required; nrow * nchan < 2^31.
+ *
+ * The grid coordinate of a visibility, in fp64 and with every operation rounded on its own, as the reference writes it:
+ *   ug = (uvw[r][0] * (freq[c] / 299792458) + umax) / u_cell,   vg likewise,
+ * with u_cell = 1 / (nx cell_size_x) and umax = |-1 / cell_size_x / 2 - u_cell / 2| evaluated by the caller, in this
+ * order, in double.  A visibility whose cell (floor ug, floor vg) lies outside [0, nx) x [0, ny), or whose coordinate is
+ * not finite, contributes nothing and gets weight 0, and a footprint cell outside the grid is skipped (the reference
+ * wraps a negative index and writes past the array at the top): no input addresses outside the arrays.
+ *
+ * The sums go to device records of PFB_IMW_RECORD doubles and never to the host; no floating-point atomics but in the
+ * counts. */
+#define PFB_IMW_RECORD 3
+/* Doubles of the `work` scratch of the functions that sum (8-byte aligned device memory, the caller's, one per stream in
+ * use): one partial per workgroup and quantity, added by a second, one-workgroup launch in a fixed order -- the sums
+ * are the same bits from run to run. */
+#define PFB_IMW_WORK_DOUBLES 6144
+
+/* counts (ngrid, nx, ny) of `dtype`, cleared first.  Row r adds to grid g of the partition in bins of nrow / ngrid rows,
+ * the first nrow % ngrid bins one longer.  k == 0: 1 to cell (floor ug, floor vg) of every visibility with mask != 0.
+ * k = 2, 4, .. 16, h = k / 2: phi(x / h) phi(y / h) to the cells (rint ug + i, rint vg + j), i, j in [-h, h), rint
+ * rounding halves to even, x = cell - ug + 0.5, phi(t) = exp(2.3 k (sqrt((1 - t)(1 + t)) - 1)); phi and the product in
+ * fp64, rounded once to `dtype`.  Floating-point atomic adds: for k > 0 the sums depend on arrival order in the last
+ * bits; for k == 0 they are integers and exact (below 2^24 per cell in float). */
+int pfb_imw_counts(int dtype, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow, int nchan,
+                   int nx, int ny, double u_cell, double umax, double v_cell, double vmax, int k, int ngrid, void* counts,
+                   void* stream);
+/* rec = [sum c, sum c^2, number of cells with c != 0] over the n cells of counts, accumulated in fp64. */
+int pfb_imw_moments(int dtype, const void* counts, size_t n, double* rec, double* work, void* stream);
+/* weights (nrow, nchan) of `dtype` for EVERY visibility (no mask, as in the reference) from counts (nx, ny) and their
+ * record `rec`, c = counts[floor ug, floor vg]:
+ *   briggs == 0 (robust <= -2): 1 / c where c != 0, else 0;
+ *   briggs != 0: 1 / (1 + c ssq), ssq = numsqrt^2 / (rec[1] / rec[0]) formed in fp64 and rounded to `dtype`, the rest in
+ *     `dtype` (the reference replaces counts by 1 + counts ssq BEFORE the lookup: an empty cell gives 1);
+ *   all-zero counts (rec[2] == 0): zeros. */
+int pfb_imw_weights(int dtype, const void* counts, const double* rec, const double* uvw, const double* freq, size_t nrow,
+                    int nchan, int nx, int ny, double u_cell, double umax, double v_cell, double vmax, int briggs,
+                    double numsqrt, void* weights, void* stream);
+/* residual_vis = (vis - model_vis) * mask, all complex `dtype` of nvis elements; rec = [sum |residual_vis|^2, sum mask,
+ * 0], accumulated in fp64. */
+int pfb_imw_l2_residual(int dtype, const void* vis, const void* model_vis, const unsigned char* mask, size_t nvis,
+                        void* residual_vis, double* rec, double* work, void* stream);
+/* After pfb_imw_l2_residual on the same rec, and only when rec[1] != 0 (the caller's one look at the record):
+ * wgt = (dof + 1) / (dof + |residual_vis|^2 / ovar) / ovar, ovar = rec[0] / rec[1] rounded to `dtype`, times imwgt where
+ * imwgt (nvis of `dtype`) is not NULL; rec[2] = sum of wgt where mask != 0, in fp64. */
+int pfb_imw_l2_weights(int dtype, const void* residual_vis, const unsigned char* mask, const void* imwgt, size_t nvis,
+                       double dof, double* rec, void* wgt, double* work, void* stream);
+/* rec[0] = sum of wgt where mask != 0, in fp64. */
+int pfb_imw_wsum(int dtype, const void* wgt, const unsigned char* mask, size_t nvis, double* rec, double* work,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

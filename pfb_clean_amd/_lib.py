@@ -142,6 +142,13 @@ SIGNATURES = {
     'pfb_wgrid_image_forward': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pfb_wgrid_image_adjoint': (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     'pfb_wgrid_image_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    # imaging weights (weighting.py:43-171, gridder.py:604-615): counts, their moments, weights, the l2 reweight, wsum
+    'pfb_imw_counts': (_i, [_i, _vp, _vp, _vp, _sz, _i, _i, _i, _d, _d, _d, _d, _i, _i, _vp, _vp]),
+    'pfb_imw_moments': (_i, [_i, _vp, _sz, _vp, _vp, _vp]),
+    'pfb_imw_weights': (_i, [_i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _d, _d, _d, _d, _i, _d, _vp, _vp]),
+    'pfb_imw_l2_residual': (_i, [_i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    'pfb_imw_l2_weights': (_i, [_i, _vp, _vp, _vp, _sz, _d, _vp, _vp, _vp, _vp]),
+    'pfb_imw_wsum': (_i, [_i, _vp, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -13,6 +13,9 @@ The c2c transform of a plane is torch.fft (the precedent of operators/fft.py); e
 A WgridPlan holds what one (uvw, freq, mask) set and one image geometry share between calls: support, planes, the
 correction tables and the visibilities' sorted order.  Plans live in a PlanCache: a major cycle that presents the same
 arrays again builds nothing.  numpy in gives numpy out, tensors in give tensors out; there is no CPU path.
+
+image_data_products (pfb/operators/gridder.py:551-740) composes these with utils/weighting.py into the grid worker's
+products: WEIGHT, WSUM, DIRTY, PSF, PSFHAT and RESIDUAL of one band.
 """
 import ctypes as C
 import math
@@ -22,6 +25,8 @@ import torch
 
 from .. import _dev, _lib
 from .._plan import NativePlan, PlanCache, array_key
+from ..utils import weighting
+from .fft import psfhat_from_psf
 
 C_LIGHT = 299792458.0
 EPS_MAX = 1e-2
@@ -333,3 +338,85 @@ def dirty2vis(uvw, freq, dirty, wgt=None, mask=None, pixsize_x=None, pixsize_y=N
     nx, ny = dd.shape
     plan = plan_for(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, dd.dtype)
     return _dev.host_like(plan.dirty2vis(dd, wd, divide_by_n), dirty)
+
+
+# --------------------------------------------------------------------------- the grid worker's products, in one go
+def image_data_products(uvw, freq, vis, wgt, mask, counts, nx, ny, nx_psf, ny_psf, cellx, celly, model=None,
+                        robustness=None, x0=0.0, y0=0.0, nthreads=1, epsilon=1e-7, do_wgridding=True, double_accum=True,
+                        l2reweight_dof=None, do_dirty=True, do_psf=True, do_weight=True):
+    """pfb/operators/gridder.py:551-740: the image-space data products of one band in one go, with the reference's
+    keys -- WEIGHT (if do_weight), WSUM (1,), DIRTY, PSF and PSFHAT (if do_psf), RESIDUAL (if a model is given) -- and its
+    statements in its order: model visibilities, the l2 reweight, the imaging weights of `robustness` from `counts`
+    multiplied into wgt, the dirty image, the PSF on (nx_psf, ny_psf) (from unit visibilities, or for a centre
+    (x0, y0) != 0 from the degridded 128 x 128 delta), its transform, the residual image.  divide_by_n=False throughout.
+
+    One plan of the cache per geometry: the (nx, ny) plan serves model, dirty and residual, the (nx_psf, ny_psf) plan the
+    PSF (and a 128 x 128 one the delta).  They work in float64 when double_accum is set and in the type of vis otherwise.
+    The model is degridded WITH the mask -- which the plan carries -- since residual_vis is multiplied by it anyway.
+
+    Differences from the reference: the caller's wgt is never written (the reference's `wgt *= imwgt` writes into it);
+    no weights at all (wgt None, no robustness, no l2 reweight, or an l2 reweight with an all-zero mask and no
+    robustness) is a ValueError here and a TypeError on `None[...]` there.  `nthreads` and `do_dirty` are accepted and
+    ignored (the reference ignores do_dirty too).  numpy in gives numpy out; with tensors in, the l2 reweight's
+    sum of the mask is the one number that is read on the host."""
+    if model is None and l2reweight_dof:
+        raise ValueError('Requested l2 reweight but no model passed in. '
+                         'Perhaps transfer model from somewhere?')
+    if robustness is not None and counts is None:
+        raise ValueError('counts are None but robustness specified. '
+                         'This is probably a bug!')
+    vd = _dev.to_dev(vis)
+    if vd.dtype not in _dev.REAL_OF or vd.ndim != 2:
+        raise TypeError(f"vis must be a (nrow, nchan) complex64 or complex128 array, got {vd.dtype} {tuple(vd.shape)}")
+    cdt_in, rdt_in = vd.dtype, _dev.REAL_OF[vd.dtype]
+    rdt = torch.float64 if double_accum else rdt_in
+    cdt = _dev.CPLX_OF[rdt]
+    md = weighting._mask(mask, vd.shape)
+    wd = _dev.to_dev(wgt)
+    if wd is not None and (wd.dtype != rdt_in or wd.shape != vd.shape):
+        raise TypeError(f"wgt must be {rdt_in} of the shape of vis, got {wd.dtype} {tuple(wd.shape)}")
+    nx, ny = int(nx), int(ny)
+
+    def plan(npx, npy):
+        return plan_for(uvw, freq, mask, npx, npy, cellx, celly, x0, y0, epsilon, do_wgridding, rdt)
+
+    def image(p, v, w):
+        return p.vis2dirty(v.to(cdt), None if w is None else w.to(rdt), False).to(rdt_in)
+
+    def degrid(p, img):
+        return p.dirty2vis(img.to(rdt), None, False).to(cdt_in)
+
+    out = {}
+    imwgt = None
+    if robustness is not None:
+        imwgt = weighting._counts_to_weights(_dev.to_dev(counts, rdt_in), _dev.to_dev(uvw), _dev.to_dev(freq), nx, ny,
+                                             cellx, celly, robustness)
+    residual_vis = wsum = None
+    if model is not None:
+        xd = _dev.to_dev(model)
+        if xd.dtype not in _dev.CPLX_OF or tuple(xd.shape) != (nx, ny):
+            raise TypeError(f"model must be a float32 or float64 image of shape {(nx, ny)}")
+        model_vis = degrid(plan(nx, ny), xd)            # no weights in this direction
+        residual_vis, wl2, wsum = weighting._l2_reweight_dev(vd, model_vis, md, l2reweight_dof, imwgt)
+        if l2reweight_dof:
+            wd, imwgt = wl2, (None if wl2 is not None else imwgt)         # the product was formed in the kernel
+    if imwgt is not None:
+        wd = imwgt if wd is None else wd * imwgt
+    if wd is None:
+        raise ValueError('no weights: wgt is None and neither robustness nor an l2 reweight gives any')
+    if do_weight:
+        out['WEIGHT'] = wd
+    out['WSUM'] = wsum if wsum is not None else weighting.masked_sum(wd, md)
+    out['DIRTY'] = image(plan(nx, ny), vd, wd)
+    if do_psf:
+        if x0 or y0:
+            delta = torch.zeros((128, 128), dtype=rdt, device=vd.device)
+            delta[64, 64] = 1.0
+            psf_vis = degrid(plan(128, 128), delta)
+        else:
+            psf_vis = torch.ones(vd.shape, dtype=cdt_in, device=vd.device)
+        out['PSF'] = image(plan(int(nx_psf), int(ny_psf)), psf_vis, wd)
+        out['PSFHAT'] = psfhat_from_psf(out['PSF'])
+    if model is not None:
+        out['RESIDUAL'] = image(plan(nx, ny), residual_vis, wd)
+    return {key: _dev.host_like(t, vis) for key, t in out.items()}
