@@ -818,6 +818,44 @@ int pfb_imw_l2_weights(int dtype, const void* residual_vis, const unsigned char*
 int pfb_imw_wsum(int dtype, const void* wgt, const unsigned char* mask, size_t nvis, double* rec, double* work,
                  void* stream);
 
+/* ---------------------------------------------------------------- Stokes visibilities and weights
+ * pfb/utils/weighting.py:281-350 (_weight_data over the functions pfb/utils/stokes.py generates) with the preparation
+ * of pfb/utils/stokes2im.py:98-195 fused in, one pass.  Per (row, channel), with Gp, Gq the 2 x 2 Jones matrices of
+ * ant1[row], ant2[row] at the row's time bin and the channel, direction 0, V the correlations, w their weights and B the
+ * basis matrix:
+ *     vis = 1/2 tr(B^H Gp^-1 V Gq^-H)          wgt = sum_ab w_ab |(Gp B Gq^H)_ab|^2
+ * basis 0: [[1,0],[0,1]]   1: [[1,0],[0,-1]]   2: [[0,1],[1,0]]   3: [[0,i],[-i,0]].
+ * Jones modes: `jones` is (ntime, nant, nchan, ndir, 2) with the diagonal (DIAG4, DIAG2), (ntime, nant, nchan, ndir, 2, 2)
+ * (FULL4) or not read (NOJ4, NOJ2: unit Jones terms); the last digit is the number of correlations of data, data2,
+ * weight and flag.  With two correlations v01 = v10 = 0 and w01 = w10 = 1, as in the reference. */
+#define PFB_STOKES_DIAG4 0
+#define PFB_STOKES_DIAG2 1
+#define PFB_STOKES_FULL4 2
+#define PFB_STOKES_NOJ4  3
+#define PFB_STOKES_NOJ2  4
+/* weight forms: ones (weight not read); weight holds sigma (nrow, nchan, ncorr), w = 1 / (sigma sigma); a weight
+ * spectrum (nrow, nchan, ncorr); a row weight (nrow, ncorr) */
+#define PFB_STOKES_W_NONE     0
+#define PFB_STOKES_W_SIGMA    1
+#define PFB_STOKES_W_SPECTRUM 2
+#define PFB_STOKES_W_ROW      3
+/* data, data2 (or NULL; data - data2 when subtract, else data + data2): complex `dtype` (nrow, nchan, ncorr).
+ * flag: nflagcorr bytes per visibility, nflagcorr = ncorr (any of them flags), 1, or 0 (flag not read); frow (nrow) or
+ * NULL; autocorr != 0 flags rows with ant1 == ant2.  Row r belongs to time bin t when
+ * tbin_idx[t] - tbin_off <= r < tbin_idx[t] - tbin_off + tbin_counts[t]; the bins ascend and do not overlap (the
+ * caller's check), tbin_off is their minimum; found per row by a binary search on the device.
+ * Out: vis complex (nrow, nchan), wgt real (nrow, nchan), mask bytes (nrow, nchan) = !flagged, wsum[0] = the fp64 sum of
+ * wgt over unflagged visibilities (work: PFB_REDUCE_WS_DOUBLES doubles of scratch; a fixed order, the same bits from run
+ * to run).  A flagged visibility, a row no bin covers and a row with an antenna outside [0, nant) get vis = wgt = 0 by
+ * selection: NaN or Inf in their data or weights do not reach an output.  A singular Jones matrix on a live visibility
+ * gives IEEE inf / nan, as in the reference.  data, data2, weight, jones must be aligned to their vector loads
+ * (min(16, bytes per visibility)), else PFB_ERR_INVALID. */
+int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void* data2, int subtract, const void* weight,
+                   int wform, const unsigned char* flag, int nflagcorr, const unsigned char* frow, int autocorr,
+                   const void* jones, int ndir, int ntime, int nant, const long long* tbin_idx,
+                   const long long* tbin_counts, long long tbin_off, const int* ant1, const int* ant2, size_t nrow,
+                   int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum, double* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,321 @@
+// stokes.hip -- Stokes visibilities and weights from correlations and Jones terms (pfb/utils/weighting.py:281-350 over
+// the functions that pfb/utils/stokes.py generates, and the preparation of pfb/utils/stokes2im.py:98-195), DESIGN 4.12:
+//   k_stokes   one streaming pass: a (row, channel) visibility per thread, channels fastest.  With Gp, Gq the 2 x 2 Jones
+//              matrices of the row's two antennas at its time bin and channel, V the 2 x 2 matrix of its correlations,
+//              w their weights and B the Stokes basis matrix,
+//                  vis = 1/2 tr(B^H Gp^-1 V Gq^-H)            wgt = sum_ab w_ab |(Gp B Gq^H)_ab|^2
+//              the closed form of the reference's generated expressions (the weights cancel out of its C).  Fused into
+//              the pass: data +- data2, the weight forms (ones, 1 / sigma^2, a spectrum, a row weight), the flag
+//              any(flag[row, chan, :]) | frow[row] | ant1[row] == ant2[row], mask = !flag as bytes, and the fp64 sum of
+//              the unflagged wgt (a partial per workgroup, then k_final_sum of common.hpp: the same bits every run).
+// Templated on the type, the Jones mode (diagonal with 4 or 2 correlations, full 2 x 2 with 4, none with 4 or 2) and the
+// basis; the weight form, the flags and the second column are uniform branches.
+//
+// A workgroup takes STK_BLOCK / nchan whole rows at a time (one row when nchan > STK_BLOCK): its first lanes find their
+// row's time bin by a binary search over tbin_idx and leave (bin, ant1, ant2) in LDS, then every lane takes visibilities
+// of those rows, consecutive lanes consecutive (row, channel) pairs: the correlations, weights and flags of a wave are
+// one contiguous stretch read in 16-byte pieces, the Jones terms of a row contiguous along its channels, the three stores
+// coalesced.  Flagged or uncovered visibilities are SELECTED to zero: whatever their data and weights hold (NaN, Inf)
+// never reaches an output.  A row whose antenna is outside [0, nant) counts as uncovered: nothing addresses outside
+// the arrays, whatever the input.  Every index is a size_t.
+#include "common.hpp"
+
+namespace pfb {
+
+typedef unsigned char u8;
+
+constexpr int STK_BLOCK = 256;
+static_assert(STK_BLOCK == RED_BLOCK, "emit_partials reduces RED_BLOCK threads");
+// at most this many workgroups stride over the row groups: one partial each in the reduction scratch
+constexpr int STK_MAX_GROUPS = 4096;
+static_assert(STK_MAX_GROUPS <= PFB_REDUCE_WS_DOUBLES, "one fp64 partial per workgroup");
+
+struct StkArgs {
+    const void* data; const void* data2; const void* weight; const void* jones;
+    const u8* flag; const u8* frow;
+    const int* ant1; const int* ant2;
+    const long long* tbin_idx; const long long* tbin_counts;
+    long long tbin_off;
+    size_t nrow, ngroups;
+    int nchan, rows_per_group, ntime, nant, ndir, wform, nflagcorr, autocorr, subtract;
+    void* vis; void* wgt; u8* mask;
+    double* ws;
+};
+
+constexpr bool stk_has_jones(int mode) { return mode <= PFB_STOKES_FULL4; }
+constexpr int stk_ncorr(int mode) { return mode == PFB_STOKES_DIAG2 || mode == PFB_STOKES_NOJ2 ? 2 : 4; }
+constexpr int stk_njones(int mode) { return mode == PFB_STOKES_FULL4 ? 4 : 2; }
+
+// BYTES contiguous bytes at p (aligned to min(BYTES, 16)) in the widest loads; NT: read once, keep out of the caches' way
+template <int BYTES, bool NT>
+__device__ __forceinline__ void stk_load(const void* __restrict__ p, void* __restrict__ dst) {
+    if constexpr (BYTES >= 16) {
+        typedef float v4f __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int i = 0; i < BYTES / 16; ++i) {
+            const v4f v = NT ? __builtin_nontemporal_load(static_cast<const v4f*>(p) + i) : static_cast<const v4f*>(p)[i];
+            memcpy(static_cast<char*>(dst) + 16 * i, &v, 16);
+        }
+    } else if constexpr (BYTES == 8) {
+        const v2f v = NT ? __builtin_nontemporal_load(static_cast<const v2f*>(p)) : *static_cast<const v2f*>(p);
+        memcpy(dst, &v, 8);
+    } else if constexpr (BYTES == 4) {
+        const unsigned v = NT ? __builtin_nontemporal_load(static_cast<const unsigned*>(p)) : *static_cast<const unsigned*>(p);
+        memcpy(dst, &v, 4);
+    } else {
+        static_assert(BYTES == 2, "2, 4, 8 or a multiple of 16 bytes");
+        const unsigned short v = NT ? __builtin_nontemporal_load(static_cast<const unsigned short*>(p))
+                                    : *static_cast<const unsigned short*>(p);
+        memcpy(dst, &v, 2);
+    }
+}
+
+template <typename T> __device__ __forceinline__ T stk_abs2(cplx<T> a) { return a.x * a.x + a.y * a.y; }
+// a / d
+template <typename T> __device__ __forceinline__ cplx<T> stk_div(cplx<T> a, cplx<T> d) {
+    const cplx<T> n = mulc(a, d);
+    const T s = stk_abs2(d);
+    return {n.x / s, n.y / s};
+}
+// 1/2 tr(B^H X) from the two entries of X that the basis reads: (x00, x11) for B = 1, diag(1, -1); (x01, x10) for
+// [[0, 1], [1, 0]], [[0, i], [-i, 0]]
+template <int BASIS, typename T> __device__ __forceinline__ cplx<T> stk_trace(cplx<T> a, cplx<T> b) {
+    if constexpr (BASIS == 0 || BASIS == 2) return T(0.5) * (a + b);
+    else if constexpr (BASIS == 1) return T(0.5) * (a - b);
+    else return T(0.5) * mul_i(b - a);
+}
+
+// v: the correlations (v00, v01, v10, v11), or (v00, v11) of two; w: their weights; gp, gq: the Jones terms (g00, g11)
+// or (g00, g01, g10, g11)
+template <typename T, int MODE, int BASIS>
+__device__ __forceinline__ void stk_eval(const cplx<T>* v, const T* w, const cplx<T>* gp, const cplx<T>* gq, cplx<T>& vis,
+                                         T& wgt) {
+    constexpr bool offdiag = BASIS >= 2;
+    constexpr int NC = stk_ncorr(MODE);
+    // the two correlations and weights that a diagonal Jones term pairs with this basis; with two correlations the
+    // reference takes v01 = v10 = 0 and w01 = w10 = 1
+    cplx<T> va, vb;
+    T wa, wb;
+    if constexpr (NC == 4) {
+        va = v[offdiag ? 1 : 0]; vb = v[offdiag ? 2 : 3];
+        wa = w[offdiag ? 1 : 0]; wb = w[offdiag ? 2 : 3];
+    } else if constexpr (offdiag) {
+        va = vb = cplx<T>(T(0), T(0));
+        wa = wb = T(1);
+    } else {
+        va = v[0]; vb = v[1];
+        wa = w[0]; wb = w[1];
+    }
+    if constexpr (!stk_has_jones(MODE)) {
+        vis = stk_trace<BASIS>(va, vb);
+        wgt = wa + wb;
+    } else if constexpr (MODE != PFB_STOKES_FULL4) {
+        // x_ab = v_ab / (gp_aa conj(gq_bb)), (Gp B Gq^H)_ab = +- gp_aa conj(gq_bb) on the basis' two entries
+        const cplx<T> da = mulc(gp[0], gq[offdiag ? 1 : 0]), db = mulc(gp[1], gq[offdiag ? 0 : 1]);
+        vis = stk_trace<BASIS>(stk_div(va, da), stk_div(vb, db));
+        wgt = wa * stk_abs2(da) + wb * stk_abs2(db);
+    } else {
+        // X = adj(Gp) V adj(Gq)^H / (det Gp conj(det Gq)), adj G = [[g11, -g01], [-g10, g00]]
+        const cplx<T> m00 = gp[3] * v[0] - gp[1] * v[2], m01 = gp[3] * v[1] - gp[1] * v[3];
+        const cplx<T> m10 = gp[0] * v[2] - gp[2] * v[0], m11 = gp[0] * v[3] - gp[2] * v[1];
+        cplx<T> xa, xb;
+        if constexpr (!offdiag) {
+            xa = mulc(m00, gq[3]) - mulc(m01, gq[1]);           // x00 = m00 conj(c00) + m01 conj(c01)
+            xb = mulc(m11, gq[0]) - mulc(m10, gq[2]);           // x11 = m10 conj(c10) + m11 conj(c11)
+        } else {
+            xa = mulc(m01, gq[0]) - mulc(m00, gq[2]);           // x01 = m00 conj(c10) + m01 conj(c11)
+            xb = mulc(m10, gq[3]) - mulc(m11, gq[1]);           // x10 = m10 conj(c00) + m11 conj(c01)
+        }
+        const cplx<T> dp = gp[0] * gp[3] - gp[1] * gp[2], dq = gq[0] * gq[3] - gq[1] * gq[2];
+        vis = stk_div(stk_trace<BASIS>(xa, xb), mulc(dp, dq));
+        // E_ab = gp_a0 conj(gq_b{0|1}) +- gp_a1 conj(gq_b{1|0})
+        wgt = T(0);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const cplx<T> e0 = mulc(gp[2 * a], gq[2 * b + (offdiag ? 1 : 0)]);
+                const cplx<T> e1 = mulc(gp[2 * a + 1], gq[2 * b + (offdiag ? 0 : 1)]);
+                wgt += w[2 * a + b] * stk_abs2((BASIS == 0 || BASIS == 2) ? e0 + e1 : e0 - e1);
+            }
+        }
+    }
+}
+
+template <typename T, int MODE, int BASIS>
+__global__ void __launch_bounds__(STK_BLOCK)
+k_stokes(StkArgs a) {
+    constexpr int NC = stk_ncorr(MODE), NJ = stk_njones(MODE);
+    __shared__ int s_bin[STK_BLOCK], s_p[STK_BLOCK], s_q[STK_BLOCK];
+    const cplx<T>* __restrict__ data = static_cast<const cplx<T>*>(a.data);
+    const cplx<T>* __restrict__ data2 = static_cast<const cplx<T>*>(a.data2);
+    const T* __restrict__ weight = static_cast<const T*>(a.weight);
+    const cplx<T>* __restrict__ jones = static_cast<const cplx<T>*>(a.jones);
+    cplx<T>* __restrict__ vis = static_cast<cplx<T>*>(a.vis);
+    T* __restrict__ wgt = static_cast<T*>(a.wgt);
+    const unsigned nchan = (unsigned)a.nchan;
+    double acc[1] = {0.0};
+    for (size_t g = blockIdx.x; g < a.ngroups; g += gridDim.x) {
+        const size_t r0 = g * (size_t)a.rows_per_group;
+        const unsigned nr = (unsigned)(a.nrow - r0 < (size_t)a.rows_per_group ? a.nrow - r0 : (size_t)a.rows_per_group);
+        __syncthreads();                                        // the readers of the group before
+        if (threadIdx.x < nr) {
+            // the last bin that starts at or before the row (bins ascend; empty ones share their start with the next)
+            const size_t r = r0 + threadIdx.x;
+            const long long row = (long long)r;
+            int lo = 0, hi = a.ntime;                           // tbin_idx[lo] - off <= row (lo = 0: off is the minimum)
+            while (hi - lo > 1) {
+                const int mid = lo + (hi - lo) / 2;
+                if (a.tbin_idx[mid] - a.tbin_off <= row) lo = mid; else hi = mid;
+            }
+            const int p = a.ant1[r], q = a.ant2[r];
+            const bool covered = row - (a.tbin_idx[lo] - a.tbin_off) < a.tbin_counts[lo] &&
+                                 p >= 0 && p < a.nant && q >= 0 && q < a.nant;
+            bool frow = a.autocorr && p == q;
+            if (a.frow) frow = frow || a.frow[r] != 0;
+            s_bin[threadIdx.x] = frow ? -2 : covered ? lo : -1;
+            s_p[threadIdx.x] = p;
+            s_q[threadIdx.x] = q;
+        }
+        __syncthreads();
+        const unsigned n = nr * nchan;                          // <= STK_BLOCK, or one row
+        for (unsigned i = threadIdx.x; i < n; i += STK_BLOCK) {
+            const unsigned lr = a.rows_per_group == 1 ? 0u : i / nchan;
+            const unsigned chan = i - lr * nchan;
+            const size_t r = r0 + lr;
+            const size_t t = r * nchan + chan;
+            const int bin = s_bin[lr];
+            bool flagged = bin == -2;
+            if (a.nflagcorr == 1) {
+                flagged = flagged || __builtin_nontemporal_load(a.flag + t) != 0;
+            } else if (a.nflagcorr) {
+                unsigned f = 0;
+                stk_load<NC, true>(a.flag + t * NC, &f);
+                flagged = flagged || f != 0;
+            }
+            const bool live = !flagged && bin >= 0;
+            cplx<T> v[NC];
+            stk_load<NC * (int)sizeof(cplx<T>), true>(data + t * NC, v);
+            if (data2) {
+                cplx<T> d[NC];
+                stk_load<NC * (int)sizeof(cplx<T>), true>(data2 + t * NC, d);
+#pragma unroll
+                for (int c = 0; c < NC; ++c) v[c] = a.subtract ? v[c] - d[c] : v[c] + d[c];
+            }
+            T w[NC];
+            if (a.wform == PFB_STOKES_W_NONE) {
+#pragma unroll
+                for (int c = 0; c < NC; ++c) w[c] = T(1);
+            } else if (a.wform == PFB_STOKES_W_ROW) {
+                stk_load<NC * (int)sizeof(T), false>(weight + r * NC, w);
+            } else {
+                stk_load<NC * (int)sizeof(T), true>(weight + t * NC, w);
+                if (a.wform == PFB_STOKES_W_SIGMA) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) w[c] = T(1) / (w[c] * w[c]);
+                }
+            }
+            cplx<T> gp[NJ], gq[NJ];
+            if constexpr (stk_has_jones(MODE)) {
+                // an uncovered row reads the first entry and drops the result
+                const size_t tb = live ? (size_t)bin : 0, p = live ? (size_t)s_p[lr] : 0, q = live ? (size_t)s_q[lr] : 0;
+                const size_t step = (size_t)a.ndir * NJ;
+                stk_load<NJ * (int)sizeof(cplx<T>), false>(jones + ((tb * a.nant + p) * nchan + chan) * step, gp);
+                stk_load<NJ * (int)sizeof(cplx<T>), false>(jones + ((tb * a.nant + q) * nchan + chan) * step, gq);
+            }
+            cplx<T> ov;
+            T ow;
+            stk_eval<T, MODE, BASIS>(v, w, gp, gq, ov, ow);
+            vis[t] = live ? ov : cplx<T>(T(0), T(0));
+            wgt[t] = live ? ow : T(0);
+            a.mask[t] = flagged ? 0 : 1;
+            acc[0] += live ? (double)ow : 0.0;
+        }
+    }
+    emit_partials<1>(acc, a.ws);
+}
+
+// ------------------------------------------------------------------------------------------------------ launchers
+// The entry layer of imweight.hip: stk_check on the type code and the pointers, the size checks, then one typed launch
+// from the stk_by_type / stk_by_mode / stk_by_basis lambdas.
+template <typename F>
+static int stk_by_type(int dtype, F&& f) { return dtype == PFB_F32 ? f(float{}) : f(double{}); }
+// f(std::integral_constant<int, M>{}), M = 0 .. LAST (checked before)
+template <int LAST, int M = 0, typename F>
+static int stk_by_index(int m, F&& f) {
+    if constexpr (M < LAST) {
+        if (m != M) return stk_by_index<LAST, M + 1>(m, f);
+    }
+    return f(std::integral_constant<int, M>{});
+}
+
+struct StkArray { const void* ptr; size_t align; bool optional = false; };
+
+static int stk_check(int dtype, const char* name, std::initializer_list<StkArray> arrays) {
+    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "%s: bad dtype %d", name, dtype);
+    for (const StkArray& a : arrays) PFB_REQUIRE(a.ptr || a.optional, PFB_ERR_INVALID, "%s: null argument", name);
+    for (const StkArray& a : arrays)
+        PFB_REQUIRE(((uintptr_t)a.ptr & (a.align - 1)) == 0, PFB_ERR_INVALID, "%s: an array is not aligned to its vector loads", name);
+    return PFB_OK;
+}
+
+template <typename T, int MODE, int BASIS>
+static int stk_launch(const StkArgs& a, void* stream) {
+    const size_t groups = a.ngroups < (size_t)STK_MAX_GROUPS ? a.ngroups : (size_t)STK_MAX_GROUPS;
+    hipLaunchKernelGGL((k_stokes<T, MODE, BASIS>), dim3((unsigned)groups), dim3(STK_BLOCK), 0, as_stream(stream), a);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+}  // namespace pfb
+
+using namespace pfb;
+
+extern "C" {
+
+int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void* data2, int subtract, const void* weight,
+                   int wform, const unsigned char* flag, int nflagcorr, const unsigned char* frow, int autocorr,
+                   const void* jones, int ndir, int ntime, int nant, const long long* tbin_idx,
+                   const long long* tbin_counts, long long tbin_off, const int* ant1, const int* ant2, size_t nrow,
+                   int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum, double* work, void* stream) {
+    PFB_REQUIRE(mode >= PFB_STOKES_DIAG4 && mode <= PFB_STOKES_NOJ2, PFB_ERR_INVALID, "stokes_vis: bad Jones mode %d", mode);
+    PFB_REQUIRE(basis >= 0 && basis <= 3, PFB_ERR_INVALID, "stokes_vis: bad basis %d", basis);
+    PFB_REQUIRE(wform >= PFB_STOKES_W_NONE && wform <= PFB_STOKES_W_ROW, PFB_ERR_INVALID, "stokes_vis: bad weight form %d", wform);
+    const size_t e = dtype == PFB_F32 ? 4 : 8, nc = (size_t)stk_ncorr(mode), nj = (size_t)stk_njones(mode);
+    const size_t valign = 2 * e * nc < 16 ? 2 * e * nc : 16, walign = e * nc < 16 ? e * nc : 16;
+    PFB_REQUIRE(nflagcorr == 0 || nflagcorr == 1 || nflagcorr == (int)nc, PFB_ERR_INVALID,
+                "stokes_vis: %d flags per visibility of %zu correlations", nflagcorr, nc);
+    if (int rc = stk_check(dtype, "stokes_vis",
+                           {{data, valign}, {data2, valign, true}, {weight, walign, wform == PFB_STOKES_W_NONE},
+                            {flag, nflagcorr > 1 ? nc : 1, nflagcorr == 0}, {frow, 1, true},
+                            {jones, 2 * e * nj < 16 ? 2 * e * nj : 16, !stk_has_jones(mode)}, {tbin_idx, 8},
+                            {tbin_counts, 8}, {ant1, 4}, {ant2, 4}, {vis, 2 * e}, {wgt, e}, {mask, 1}, {wsum, 8},
+                            {work, 8}});
+        rc != PFB_OK) return rc;
+    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED,
+                "stokes_vis: %zu rows x %d channels outside [1, 2^31) each", nrow, nchan);
+    PFB_REQUIRE(ntime >= 1 && nant >= 1 && ndir >= 1, PFB_ERR_INVALID, "stokes_vis: ntime %d, nant %d, ndir %d must be positive",
+                ntime, nant, ndir);
+    StkArgs a;
+    a.data = data; a.data2 = data2; a.weight = weight; a.jones = jones; a.flag = flag; a.frow = frow;
+    a.ant1 = ant1; a.ant2 = ant2; a.tbin_idx = tbin_idx; a.tbin_counts = tbin_counts; a.tbin_off = tbin_off;
+    a.nrow = nrow; a.nchan = nchan;
+    a.rows_per_group = nchan >= STK_BLOCK ? 1 : STK_BLOCK / nchan;
+    a.ngroups = (nrow + (size_t)a.rows_per_group - 1) / (size_t)a.rows_per_group;
+    a.ntime = ntime; a.nant = nant; a.ndir = ndir; a.wform = wform; a.nflagcorr = nflagcorr; a.autocorr = autocorr != 0;
+    a.subtract = subtract != 0;
+    a.vis = vis; a.wgt = wgt; a.mask = mask; a.ws = work;
+    const int rc = stk_by_type(dtype, [&](auto t) {
+        return stk_by_index<PFB_STOKES_NOJ2>(mode, [&](auto m) {
+            return stk_by_index<3>(basis, [&](auto b) { return stk_launch<decltype(t), m(), b()>(a, stream); });
+        });
+    });
+    if (rc != PFB_OK) return rc;
+    const int groups = (int)(a.ngroups < (size_t)STK_MAX_GROUPS ? a.ngroups : (size_t)STK_MAX_GROUPS);
+    hipLaunchKernelGGL(k_final_sum<STK_BLOCK>, dim3(1), dim3(STK_BLOCK), 0, as_stream(stream), (const double*)work, groups,
+                       1, wsum);
+    PFB_HIP_CHECK(hipGetLastError());
+    return PFB_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,8 @@ l2reweight_dof block of pfb/operators/gridder.py:604-615 (csrc/imweight.hip, DES
     _counts_to_weights / counts_to_weights     uniform (robust <= -2) or Briggs weights of EVERY visibility
     _filter_extreme_counts / filter_extreme_counts   positive counts raised to median / level
     l2_reweight                                residual visibilities, Student-t weights and their masked sum
+    _weight_data / weight_data                 Stokes visibilities and weights from correlations and Jones terms
+                                               (weighting.py:281-350; csrc/stokes.hip, DESIGN 4.12, utils/stokes.py)
 
 The grid coordinate of a visibility is the reference's, operation by operation in fp64; u_cell and umax are evaluated
 here in Python floats exactly as the reference writes them, so cell indices agree bit for bit.  numpy in gives numpy out,
@@ -14,13 +16,14 @@ tensors in give tensors out; there is no CPU path.  With tensors in nothing cros
 Where this differs from the reference, by definition:
   * a visibility whose cell is outside [0, nx) x [0, ny) contributes nothing and gets weight 0, and a footprint cell
     outside the grid is skipped (the reference wraps a negative index and writes past the array at the top);
-  * _filter_extreme_counts returns a new array (the reference writes into its argument and returns it).
-weight_data (the Stokes conversion with Jones terms) is not provided.
+  * _filter_extreme_counts returns a new array (the reference writes into its argument and returns it);
+  * weight_data: see its docstring.
 """
 import numpy as np
 import torch
 
 from .. import _dev, _lib
+from . import stokes as _stokes
 
 SUPPORTS = tuple(range(0, 17, 2))
 RECORD = 3          # PFB_IMW_RECORD
@@ -200,3 +203,35 @@ def l2_reweight(vis, model_vis, mask, dof, imwgt=None):
     md = _mask(mask, vd.shape)
     out = _l2_reweight_dev(vd, _dev.to_dev(model_vis), md, dof, _dev.to_dev(imwgt))
     return tuple(None if t is None else _dev.host_like(t, vis) for t in out)
+
+
+# --------------------------------------------------------------------------------------------------- weight_data
+def _weight_data(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc):
+    """weighting.py:298-350: (vis, wgt), each (nrow, nchan), of the Stokes `product` from data (nrow, nchan, ncorr)
+    complex, weight (nrow, nchan, ncorr) of data's real type, flag (nrow, nchan) and jones of data's type:
+    (ntime, nant, nchan, ndir, 2) is the DIAG mode, (ntime, nant, nchan, ndir, 2, 2) the FULL mode; direction 0 is
+    read.  nc is '2' / '4' or the integers and must be data's number of correlations.  Row r takes the Jones terms of
+    the time bin t with tbin_idx[t] <= r + min(tbin_idx) < tbin_idx[t] + tbin_counts[t], found on the device by a
+    binary search per row.  A flagged visibility and a row that no bin covers get vis = wgt = 0 whatever their data and
+    weights hold.  One kernel (utils/stokes.py states the closed form).
+
+    Differences from the reference, by definition: tbin_idx is never modified (the reference subtracts its minimum in
+    place; here on read); the time bins must be ascending and must not overlap, else ValueError (tbin_idx and tbin_counts
+    are index metadata of ntime entries and are read on the host for that check); an unknown pol, product or nc, and
+    FULL Jones terms with 2 correlations, are a ValueError (the reference: NameError / IndexError); a singular Jones
+    matrix on an unflagged visibility gives IEEE inf / nan, as in the reference."""
+    basis = _stokes.basis_index(pol, product)
+    n = _stokes.ncorr_of(nc)
+    dd = _dev.to_dev(data)
+    if dd.ndim != 3 or dd.shape[2] != n:
+        raise ValueError(f"data must be (nrow, nchan, {n}) for nc={nc!r}, got {tuple(dd.shape)}")
+    fd = _stokes._flags(flag, tuple(dd.shape[:2]), 'flag')
+    vis, wgt, _, _ = _stokes.run(dd, _dev.to_dev(weight), _stokes.W_SPECTRUM, fd, None, False, _dev.to_dev(jones),
+                                 tbin_idx, tbin_counts, ant1, ant2, basis)
+    return _dev.host_like(vis, data), _dev.host_like(wgt, data)
+
+
+def weight_data(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc):
+    """weighting.py:281-295: {'vis', 'wgt'} of _weight_data."""
+    vis, wgt = _weight_data(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc)
+    return {'vis': vis, 'wgt': wgt}
