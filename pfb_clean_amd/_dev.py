@@ -103,6 +103,25 @@ def norm_diff_sums(x, xp):
     return out[:2]
 
 
+# ---- the visibility side's arrays on their way in
+def uvw_freq(uvw, freq):
+    """(uvw, freq) on the device: float64, (nrow, 3) and (nchan,)."""
+    ud, fd = to_dev(uvw), to_dev(freq)
+    if ud.dtype != torch.float64 or fd.dtype != torch.float64:
+        raise TypeError("uvw and freq must be float64")
+    if ud.ndim != 2 or ud.shape[1] != 3 or fd.ndim != 1:
+        raise ValueError("uvw must be (nrow, 3) and freq (nchan,)")
+    return ud, fd
+
+
+def byte_mask(a, shape, name='mask'):
+    """The bool or uint8 array `a` of `shape` (a mask, flags) as a uint8 device tensor; bool is viewed, not copied."""
+    d = to_dev(a)
+    if d is None or d.dtype not in (torch.uint8, torch.bool) or tuple(d.shape) != tuple(shape):
+        raise ValueError(f"{name} must be uint8 or bool of shape {tuple(shape)}")
+    return d.view(torch.uint8) if d.dtype == torch.bool else d
+
+
 # ---- the array boundary: results go back in the kind of array the caller handed in
 def host_like(t, like):
     """Device tensor t as the caller's kind: a numpy copy when `like` is numpy, else t itself."""

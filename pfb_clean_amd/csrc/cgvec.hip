@@ -12,9 +12,11 @@
 // fused out of the convolution epilogue (fftconv*.hip) -- or, in the parametrised solve (pfb_pcg_solve_param), out of the
 // second band mix of hessparam.hip: the two forms of the operator step PcgOp, the driver's whole view of A.
 // The 16-byte packs (V16, Pack, ld / st and their non-temporal forms), can_vec, emit_partials and k_final_sum live in
-// common.hpp, shared with the prox / primal-dual kernels of wavelet.hip.
+// common.hpp, shared with the prox / primal-dual kernels of wavelet.hip; final_sum, k_final_sum's launch with its status,
+// in entry.hpp.
 #include "conv_plan.hpp"
 #include "pcg_state.hpp"
+#include "entry.hpp"
 #include <chrono>
 #include <unistd.h>
 #include <cstring>
@@ -386,27 +388,21 @@ static int dot_impl(const void* a, const void* b, size_t n, double* out, double*
     int G_used = 0;
     using PL = std::initializer_list<const void*>;
     PFB_LAUNCH_VEC(T, k_dot, n, (PL{a, b}), (const T*)a, (const T*)b);
-    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, out);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return final_sum(ws, G_used, 1, out, st);
 }
 template <typename T>
 static int nd_impl(const void* x, const void* xp, size_t n, double* out, double* ws, hipStream_t st) {
     int G_used = 0;
     using PL = std::initializer_list<const void*>;
     PFB_LAUNCH_VEC(T, k_norm_diff, n, (PL{x, xp}), (const T*)x, (const T*)xp);
-    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 2, out);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return final_sum(ws, G_used, 2, out, st);
 }
 template <typename T>
 static int any_impl(const void* a, size_t n, double* out, double* ws, hipStream_t st) {
     int G_used = 0;
     using PL = std::initializer_list<const void*>;
     PFB_LAUNCH_VEC(T, k_any, n, (PL{a}), (const T*)a);
-    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G_used, 1, out);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return final_sum(ws, G_used, 1, out, st);
 }
 template <typename T>
 static int axpby_impl(double a, const void* x, double b, void* y, size_t n, hipStream_t st) {

@@ -16,6 +16,7 @@
 // them with bs = qs = grid, bst = 0.
 #include "conv_plan.hpp"
 #include "pcg_state.hpp"
+#include "entry.hpp"
 
 namespace pfb {
 
@@ -147,9 +148,7 @@ int pfb_bandmix_dots(int dtype, const void* A, const void* c, int nband, size_t 
     int G = 0;
     const int rc = bandmix_partials(dtype, A, c, nband, npix, sigmainv, p, r, out, dots3 ? ws : nullptr, &G, st);
     if (rc != PFB_OK || !dots3) return rc;
-    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, (const double*)ws, G, 3, dots3);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return final_sum(ws, G, 3, dots3, st);
 }
 
 size_t pfb_hessparam_work_bytes(const pfb_conv_plan* plan) {
@@ -173,10 +172,7 @@ static int hessparam_checked(pfb_conv_plan* plan, const void* L, const void* LH,
     int G = 0;
     const int rc = hessparam_apply_partials(plan, L, LH, e, sigmainv, x, out, dot_with2, work, partials, &G, st);
     if (rc != PFB_OK || !dots_out) return rc;
-    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, (const double*)partials, G, 3,
-                       dots_out);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return final_sum(partials, G, 3, dots_out, st);
 }
 
 int pfb_hessparam_apply(pfb_conv_plan* plan, const void* L, const void* LH, const void* e, double sigmainv,

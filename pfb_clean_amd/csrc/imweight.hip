@@ -19,16 +19,12 @@
 //
 // A visibility whose cell (floor ug, floor vg) is outside [0, nx) x [0, ny), or whose coordinate is not finite, is
 // dropped, and so is every footprint cell outside the grid: nothing addresses outside the arrays, whatever the input.
-#include "common.hpp"
+#include "entry.hpp"
 
 namespace pfb {
 
-typedef unsigned char u8;
-
-constexpr int IMW_BLOCK = 256;
-static_assert(IMW_BLOCK == RED_BLOCK, "emit_partials reduces RED_BLOCK threads");
+constexpr int IMW_BLOCK = ENTRY_BLOCK;
 constexpr int IMW_MAX_K = 16;
-constexpr double IMW_C = 299792458.0;
 
 struct ImwGeom {
     int nx, ny;
@@ -44,15 +40,12 @@ struct ImwBins {
     }
 };
 
-__device__ __forceinline__ void imw_atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
-__device__ __forceinline__ void imw_atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }
-
 // (ug, vg) of visibility t = r * nchan + c; true iff its cell is inside the grid
 __device__ __forceinline__ bool imw_coords(const double* __restrict__ uvw, const double* __restrict__ freq, size_t t,
                                            int nchan, const ImwGeom& g, double& ug, double& vg) {
 #pragma clang fp contract(off)
     const size_t r = t / nchan;
-    const double nf = freq[t - r * nchan] / IMW_C;
+    const double nf = freq[t - r * nchan] / C_LIGHT;
     const double ut = uvw[3 * r] * nf, vt = uvw[3 * r + 1] * nf;
     ug = (ut + g.umax) / g.u_cell;
     vg = (vt + g.vmax) / g.v_cell;
@@ -80,7 +73,7 @@ k_counts(const double* __restrict__ uvw, const double* __restrict__ freq, const 
     if (!imw_coords(uvw, freq, t, nchan, g, ug, vg)) return;
     T* __restrict__ grid = counts + bins.of(t / nchan) * ((size_t)g.nx * g.ny);
     if constexpr (K == 0) {
-        imw_atomic_add(grid + (size_t)floor(ug) * g.ny + (size_t)floor(vg), T(1));
+        atomic_add(grid + (size_t)floor(ug) * g.ny + (size_t)floor(vg), T(1));
     } else {
         constexpr int ko2 = K / 2;
         const double betak = 2.3 * K;
@@ -95,7 +88,7 @@ k_counts(const double* __restrict__ uvw, const double* __restrict__ freq, const 
             const int x_idx = u_idx + i;
             if (x_idx < 0 || x_idx >= g.nx) continue;
             const double x = x_idx - ug + 0.5;
-            imw_atomic_add(cell + (size_t)x_idx * g.ny, (T)(imw_phi(x / ko2, betak) * fy));
+            atomic_add(cell + (size_t)x_idx * g.ny, (T)(imw_phi(x / ko2, betak) * fy));
         }
     }
 }
@@ -192,67 +185,11 @@ k_wsum(const T* __restrict__ wgt, const u8* __restrict__ mask, size_t n, double*
 }
 
 // ------------------------------------------------------------------------------------------------------ launchers
-// The entry layer of wgrid.hip without a plan: imw_check on the type code and the pointers, the size checks, then
-// imw_launch from an imw_by_type (and, for the counts, imw_by_support) lambda.
-static inline unsigned imw_blocks(size_t n) { return (unsigned)((n + IMW_BLOCK - 1) / IMW_BLOCK); }
 // the streaming sums: at most IMW_MAX_GROUPS workgroups stride over the array
 constexpr int IMW_MAX_GROUPS = PFB_IMW_WORK_DOUBLES / PFB_IMW_RECORD;
 static inline size_t imw_stream_threads(size_t n) {
     const size_t cap = (size_t)IMW_MAX_GROUPS * IMW_BLOCK;
     return n < cap ? n : cap;
-}
-// rec[0 .. nq) = the sums of the partials that a streaming kernel over n elements left in ws
-static int imw_final(size_t n, int nq, double* ws, double* rec, void* stream) {
-    hipLaunchKernelGGL(k_final_sum<IMW_BLOCK>, dim3(1), dim3(IMW_BLOCK), 0, as_stream(stream), (const double*)ws,
-                       (int)imw_blocks(imw_stream_threads(n)), nq, rec);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
-
-template <typename P, typename A>
-static P imw_arg(A a) {
-    if constexpr (std::is_void_v<std::remove_pointer_t<A>>) return static_cast<P>(a);
-    else return a;
-}
-// `kernel` with n lanes, on the stream
-template <typename... P, typename... A>
-static int imw_launch(void (*kernel)(P...), size_t n, void* stream, A... args) {
-    hipLaunchKernelGGL(kernel, dim3(imw_blocks(n)), dim3(IMW_BLOCK), 0, as_stream(stream), imw_arg<P>(args)...);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
-template <typename F>
-static int imw_by_type(int dtype, F&& f) { return dtype == PFB_F32 ? f(float{}) : f(double{}); }
-// f(std::integral_constant<int, K>{}), K = 0, 2, .., 16 (checked before)
-template <int K = 0, typename F>
-static int imw_by_support(int k, F&& f) {
-    if constexpr (K < IMW_MAX_K) {
-        if (k != K) return imw_by_support<K + 2>(k, f);
-    }
-    return f(std::integral_constant<int, K>{});
-}
-
-enum ImwKind { IMW_REAL, IMW_CPLX, IMW_F64, IMW_U8 };
-struct ImwArray { const void* ptr; ImwKind kind; bool optional = false; };
-
-static int imw_check(int dtype, const char* name, std::initializer_list<ImwArray> arrays) {
-    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "%s: bad dtype %d", name, dtype);
-    const size_t e = dtype == PFB_F32 ? 4 : 8;
-    for (const ImwArray& a : arrays) PFB_REQUIRE(a.ptr || a.optional, PFB_ERR_INVALID, "%s: null argument", name);
-    for (const ImwArray& a : arrays) {
-        const size_t align = a.kind == IMW_REAL ? e : a.kind == IMW_CPLX ? 2 * e : a.kind == IMW_F64 ? 8 : 1;
-        PFB_REQUIRE(((uintptr_t)a.ptr & (align - 1)) == 0, PFB_ERR_INVALID, "%s: an array is not aligned to its element size", name);
-    }
-    return PFB_OK;
-}
-static int imw_nvis(const char* name, size_t nrow, int nchan) {
-    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff / (size_t)nchan, PFB_ERR_UNSUPPORTED,
-                "%s: %zu rows x %d channels outside [1, 2^31)", name, nrow, nchan);
-    return PFB_OK;
-}
-static int imw_count(const char* name, size_t n) {
-    PFB_REQUIRE(n >= 1 && n <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED, "%s: %zu elements outside [1, 2^31)", name, n);
-    return PFB_OK;
 }
 static int imw_geom(const char* name, int nx, int ny, double u_cell, double umax, double v_cell, double vmax, ImwGeom& g) {
     PFB_REQUIRE(nx >= 1 && ny >= 1 && (size_t)nx * (size_t)ny <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED,
@@ -272,90 +209,93 @@ extern "C" {
 int pfb_imw_counts(int dtype, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow, int nchan,
                    int nx, int ny, double u_cell, double umax, double v_cell, double vmax, int k, int ngrid, void* counts,
                    void* stream) {
-    if (int rc = imw_check(dtype, "imw_counts", {{uvw, IMW_F64}, {freq, IMW_F64}, {mask, IMW_U8}, {counts, IMW_REAL}});
+    if (int rc = check(dtype, "imw_counts", {{uvw, F64}, {freq, F64}, {mask, U8}, {counts, REAL}});
         rc != PFB_OK) return rc;
-    if (int rc = imw_nvis("imw_counts", nrow, nchan); rc != PFB_OK) return rc;
+    if (int rc = check_nvis("imw_counts", nrow, nchan); rc != PFB_OK) return rc;
     ImwGeom g;
     if (int rc = imw_geom("imw_counts", nx, ny, u_cell, umax, v_cell, vmax, g); rc != PFB_OK) return rc;
     PFB_REQUIRE(k >= 0 && k <= IMW_MAX_K && k % 2 == 0, PFB_ERR_INVALID, "imw_counts: support %d not in {0, 2, .., %d}", k, IMW_MAX_K);
     PFB_REQUIRE(ngrid >= 1, PFB_ERR_INVALID, "imw_counts: %d grids", ngrid);
     PFB_REQUIRE((size_t)ngrid <= (size_t)0x7fffffff / ((size_t)nx * ny), PFB_ERR_UNSUPPORTED,
                 "imw_counts: %d grids of %d x %d exceed 2^31 cells", ngrid, nx, ny);
-    const size_t nvis = nrow * (size_t)nchan, e = dtype == PFB_F32 ? 4 : 8;
-    PFB_HIP_CHECK(hipMemsetAsync(counts, 0, e * (size_t)ngrid * nx * ny, as_stream(stream)));
+    const size_t nvis = nrow * (size_t)nchan;
+    PFB_HIP_CHECK(hipMemsetAsync(counts, 0, esize(dtype) * (size_t)ngrid * nx * ny, as_stream(stream)));
     const ImwBins bins{nrow / (size_t)ngrid, nrow % (size_t)ngrid};
-    return imw_by_type(dtype, [&](auto t) {
-        return imw_by_support(k, [&](auto kk) {
-            return imw_launch(k_counts<decltype(t), kk()>, nvis * (kk() ? kk() : 1), stream, uvw, freq, mask, nvis, nchan,
-                              g, bins, counts);
+    return by_type(dtype, [&](auto t) {
+        return by_int<0, IMW_MAX_K, 2>(k, [&](auto kk) {
+            return launch(k_counts<decltype(t), kk()>, nvis * (kk() ? kk() : 1), stream, uvw, freq, mask, nvis, nchan,
+                          g, bins, counts);
         });
     });
 }
 
 int pfb_imw_moments(int dtype, const void* counts, size_t n, double* rec, double* work, void* stream) {
-    if (int rc = imw_check(dtype, "imw_moments", {{counts, IMW_REAL}, {rec, IMW_F64}, {work, IMW_F64}}); rc != PFB_OK)
+    if (int rc = check(dtype, "imw_moments", {{counts, REAL}, {rec, F64}, {work, F64}}); rc != PFB_OK)
         return rc;
-    if (int rc = imw_count("imw_moments", n); rc != PFB_OK) return rc;
-    const int rc = imw_by_type(dtype, [&](auto t) {
-        return imw_launch(k_moments<decltype(t)>, imw_stream_threads(n), stream, counts, n, work);
+    if (int rc = check_count("imw_moments", n, PFB_ERR_UNSUPPORTED); rc != PFB_OK) return rc;
+    const unsigned groups = blocks(imw_stream_threads(n));
+    const int rc = by_type(dtype, [&](auto t) {
+        return launch_groups(k_moments<decltype(t)>, groups, stream, counts, n, work);
     });
-    return rc != PFB_OK ? rc : imw_final(n, 3, work, rec, stream);
+    return rc != PFB_OK ? rc : final_sum(work, groups, 3, rec, stream);
 }
 
 int pfb_imw_weights(int dtype, const void* counts, const double* rec, const double* uvw, const double* freq, size_t nrow,
                     int nchan, int nx, int ny, double u_cell, double umax, double v_cell, double vmax, int briggs,
                     double numsqrt, void* weights, void* stream) {
-    if (int rc = imw_check(dtype, "imw_weights", {{counts, IMW_REAL}, {rec, IMW_F64}, {uvw, IMW_F64}, {freq, IMW_F64},
-                                                  {weights, IMW_REAL}});
+    if (int rc = check(dtype, "imw_weights", {{counts, REAL}, {rec, F64}, {uvw, F64}, {freq, F64}, {weights, REAL}});
         rc != PFB_OK) return rc;
-    if (int rc = imw_nvis("imw_weights", nrow, nchan); rc != PFB_OK) return rc;
+    if (int rc = check_nvis("imw_weights", nrow, nchan); rc != PFB_OK) return rc;
     ImwGeom g;
     if (int rc = imw_geom("imw_weights", nx, ny, u_cell, umax, v_cell, vmax, g); rc != PFB_OK) return rc;
     PFB_REQUIRE(!briggs || (std::isfinite(numsqrt) && numsqrt > 0), PFB_ERR_INVALID, "imw_weights: numsqrt must be positive and finite");
     const size_t nvis = nrow * (size_t)nchan;
-    return imw_by_type(dtype, [&](auto t) {
-        return imw_launch(k_weights<decltype(t)>, nvis, stream, counts, rec, uvw, freq, nvis, nchan, g, briggs,
-                          numsqrt * numsqrt, weights);
+    return by_type(dtype, [&](auto t) {
+        return launch(k_weights<decltype(t)>, nvis, stream, counts, rec, uvw, freq, nvis, nchan, g, briggs,
+                      numsqrt * numsqrt, weights);
     });
 }
 
 int pfb_imw_l2_residual(int dtype, const void* vis, const void* model_vis, const unsigned char* mask, size_t nvis,
                         void* residual_vis, double* rec, double* work, void* stream) {
-    if (int rc = imw_check(dtype, "imw_l2_residual", {{vis, IMW_CPLX}, {model_vis, IMW_CPLX}, {mask, IMW_U8},
-                                                      {residual_vis, IMW_CPLX}, {rec, IMW_F64}, {work, IMW_F64}});
+    if (int rc = check(dtype, "imw_l2_residual", {{vis, CPLX}, {model_vis, CPLX}, {mask, U8},
+                                                  {residual_vis, CPLX}, {rec, F64}, {work, F64}});
         rc != PFB_OK) return rc;
-    if (int rc = imw_count("imw_l2_residual", nvis); rc != PFB_OK) return rc;
+    if (int rc = check_count("imw_l2_residual", nvis, PFB_ERR_UNSUPPORTED); rc != PFB_OK) return rc;
     PFB_HIP_CHECK(hipMemsetAsync(rec, 0, PFB_IMW_RECORD * sizeof(double), as_stream(stream)));
-    const int rc = imw_by_type(dtype, [&](auto t) {
-        return imw_launch(k_l2_residual<decltype(t)>, imw_stream_threads(nvis), stream, vis, model_vis, mask, nvis,
-                          residual_vis, work);
+    const unsigned groups = blocks(imw_stream_threads(nvis));
+    const int rc = by_type(dtype, [&](auto t) {
+        return launch_groups(k_l2_residual<decltype(t)>, groups, stream, vis, model_vis, mask, nvis,
+                             residual_vis, work);
     });
-    return rc != PFB_OK ? rc : imw_final(nvis, 2, work, rec, stream);
+    return rc != PFB_OK ? rc : final_sum(work, groups, 2, rec, stream);
 }
 
 int pfb_imw_l2_weights(int dtype, const void* residual_vis, const unsigned char* mask, const void* imwgt, size_t nvis,
                        double dof, double* rec, void* wgt, double* work, void* stream) {
-    if (int rc = imw_check(dtype, "imw_l2_weights", {{residual_vis, IMW_CPLX}, {mask, IMW_U8}, {imwgt, IMW_REAL, true},
-                                                     {rec, IMW_F64}, {wgt, IMW_REAL}, {work, IMW_F64}});
+    if (int rc = check(dtype, "imw_l2_weights", {{residual_vis, CPLX}, {mask, U8}, {imwgt, REAL, true},
+                                                 {rec, F64}, {wgt, REAL}, {work, F64}});
         rc != PFB_OK) return rc;
-    if (int rc = imw_count("imw_l2_weights", nvis); rc != PFB_OK) return rc;
+    if (int rc = check_count("imw_l2_weights", nvis, PFB_ERR_UNSUPPORTED); rc != PFB_OK) return rc;
     PFB_REQUIRE(std::isfinite(dof), PFB_ERR_INVALID, "imw_l2_weights: dof must be finite");
-    const int rc = imw_by_type(dtype, [&](auto t) {
-        return imw_launch(k_l2_weights<decltype(t)>, imw_stream_threads(nvis), stream, residual_vis, mask, imwgt, nvis,
-                          dof, rec, wgt, work);
+    const unsigned groups = blocks(imw_stream_threads(nvis));
+    const int rc = by_type(dtype, [&](auto t) {
+        return launch_groups(k_l2_weights<decltype(t)>, groups, stream, residual_vis, mask, imwgt, nvis,
+                             dof, rec, wgt, work);
     });
-    return rc != PFB_OK ? rc : imw_final(nvis, 1, work, rec + 2, stream);
+    return rc != PFB_OK ? rc : final_sum(work, groups, 1, rec + 2, stream);
 }
 
 int pfb_imw_wsum(int dtype, const void* wgt, const unsigned char* mask, size_t nvis, double* rec, double* work,
                  void* stream) {
-    if (int rc = imw_check(dtype, "imw_wsum", {{wgt, IMW_REAL}, {mask, IMW_U8}, {rec, IMW_F64}, {work, IMW_F64}});
+    if (int rc = check(dtype, "imw_wsum", {{wgt, REAL}, {mask, U8}, {rec, F64}, {work, F64}});
         rc != PFB_OK) return rc;
-    if (int rc = imw_count("imw_wsum", nvis); rc != PFB_OK) return rc;
-    const int rc = imw_by_type(dtype, [&](auto t) {
-        return imw_launch(k_wsum<decltype(t)>, imw_stream_threads(nvis), stream, wgt, mask, nvis, work);
+    if (int rc = check_count("imw_wsum", nvis, PFB_ERR_UNSUPPORTED); rc != PFB_OK) return rc;
+    const unsigned groups = blocks(imw_stream_threads(nvis));
+    const int rc = by_type(dtype, [&](auto t) {
+        return launch_groups(k_wsum<decltype(t)>, groups, stream, wgt, mask, nvis, work);
     });
-    return rc != PFB_OK ? rc : imw_final(nvis, 1, work, rec, stream);
+    return rc != PFB_OK ? rc : final_sum(work, groups, 1, rec, stream);
 }
 
 }  // extern "C"

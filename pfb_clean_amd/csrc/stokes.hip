@@ -18,14 +18,11 @@
 // coalesced.  Flagged or uncovered visibilities are SELECTED to zero: whatever their data and weights hold (NaN, Inf)
 // never reaches an output.  A row whose antenna is outside [0, nant) counts as uncovered: nothing addresses outside
 // the arrays, whatever the input.  Every index is a size_t.
-#include "common.hpp"
+#include "entry.hpp"
 
 namespace pfb {
 
-typedef unsigned char u8;
-
-constexpr int STK_BLOCK = 256;
-static_assert(STK_BLOCK == RED_BLOCK, "emit_partials reduces RED_BLOCK threads");
+constexpr int STK_BLOCK = ENTRY_BLOCK;
 // at most this many workgroups stride over the row groups: one partial each in the reduction scratch
 constexpr int STK_MAX_GROUPS = 4096;
 static_assert(STK_MAX_GROUPS <= PFB_REDUCE_WS_DOUBLES, "one fp64 partial per workgroup");
@@ -235,38 +232,6 @@ k_stokes(StkArgs a) {
     emit_partials<1>(acc, a.ws);
 }
 
-// ------------------------------------------------------------------------------------------------------ launchers
-// The entry layer of imweight.hip: stk_check on the type code and the pointers, the size checks, then one typed launch
-// from the stk_by_type / stk_by_mode / stk_by_basis lambdas.
-template <typename F>
-static int stk_by_type(int dtype, F&& f) { return dtype == PFB_F32 ? f(float{}) : f(double{}); }
-// f(std::integral_constant<int, M>{}), M = 0 .. LAST (checked before)
-template <int LAST, int M = 0, typename F>
-static int stk_by_index(int m, F&& f) {
-    if constexpr (M < LAST) {
-        if (m != M) return stk_by_index<LAST, M + 1>(m, f);
-    }
-    return f(std::integral_constant<int, M>{});
-}
-
-struct StkArray { const void* ptr; size_t align; bool optional = false; };
-
-static int stk_check(int dtype, const char* name, std::initializer_list<StkArray> arrays) {
-    PFB_REQUIRE(dtype == PFB_F32 || dtype == PFB_F64, PFB_ERR_INVALID, "%s: bad dtype %d", name, dtype);
-    for (const StkArray& a : arrays) PFB_REQUIRE(a.ptr || a.optional, PFB_ERR_INVALID, "%s: null argument", name);
-    for (const StkArray& a : arrays)
-        PFB_REQUIRE(((uintptr_t)a.ptr & (a.align - 1)) == 0, PFB_ERR_INVALID, "%s: an array is not aligned to its vector loads", name);
-    return PFB_OK;
-}
-
-template <typename T, int MODE, int BASIS>
-static int stk_launch(const StkArgs& a, void* stream) {
-    const size_t groups = a.ngroups < (size_t)STK_MAX_GROUPS ? a.ngroups : (size_t)STK_MAX_GROUPS;
-    hipLaunchKernelGGL((k_stokes<T, MODE, BASIS>), dim3((unsigned)groups), dim3(STK_BLOCK), 0, as_stream(stream), a);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
-
 }  // namespace pfb
 
 using namespace pfb;
@@ -281,16 +246,17 @@ int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void*
     PFB_REQUIRE(mode >= PFB_STOKES_DIAG4 && mode <= PFB_STOKES_NOJ2, PFB_ERR_INVALID, "stokes_vis: bad Jones mode %d", mode);
     PFB_REQUIRE(basis >= 0 && basis <= 3, PFB_ERR_INVALID, "stokes_vis: bad basis %d", basis);
     PFB_REQUIRE(wform >= PFB_STOKES_W_NONE && wform <= PFB_STOKES_W_ROW, PFB_ERR_INVALID, "stokes_vis: bad weight form %d", wform);
-    const size_t e = dtype == PFB_F32 ? 4 : 8, nc = (size_t)stk_ncorr(mode), nj = (size_t)stk_njones(mode);
-    const size_t valign = 2 * e * nc < 16 ? 2 * e * nc : 16, walign = e * nc < 16 ? e * nc : 16;
+    const size_t e = esize(dtype), nc = (size_t)stk_ncorr(mode), nj = (size_t)stk_njones(mode);
+    // what one vector load reads: a visibility's correlations, its weights, an antenna's Jones terms; 16 bytes at most
+    const auto vload = [](size_t n) { return bytes(n < 16 ? n : 16); };
     PFB_REQUIRE(nflagcorr == 0 || nflagcorr == 1 || nflagcorr == (int)nc, PFB_ERR_INVALID,
                 "stokes_vis: %d flags per visibility of %zu correlations", nflagcorr, nc);
-    if (int rc = stk_check(dtype, "stokes_vis",
-                           {{data, valign}, {data2, valign, true}, {weight, walign, wform == PFB_STOKES_W_NONE},
-                            {flag, nflagcorr > 1 ? nc : 1, nflagcorr == 0}, {frow, 1, true},
-                            {jones, 2 * e * nj < 16 ? 2 * e * nj : 16, !stk_has_jones(mode)}, {tbin_idx, 8},
-                            {tbin_counts, 8}, {ant1, 4}, {ant2, 4}, {vis, 2 * e}, {wgt, e}, {mask, 1}, {wsum, 8},
-                            {work, 8}});
+    if (int rc = check(dtype, "stokes_vis",
+                       {{data, vload(2 * e * nc)}, {data2, vload(2 * e * nc), true},
+                        {weight, vload(e * nc), wform == PFB_STOKES_W_NONE},
+                        {flag, bytes(nflagcorr > 1 ? nc : 1), nflagcorr == 0}, {frow, U8, true},
+                        {jones, vload(2 * e * nj), !stk_has_jones(mode)}, {tbin_idx, I64}, {tbin_counts, I64},
+                        {ant1, I32}, {ant2, I32}, {vis, CPLX}, {wgt, REAL}, {mask, U8}, {wsum, F64}, {work, F64}});
         rc != PFB_OK) return rc;
     PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED,
                 "stokes_vis: %zu rows x %d channels outside [1, 2^31) each", nrow, nchan);
@@ -305,17 +271,15 @@ int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void*
     a.ntime = ntime; a.nant = nant; a.ndir = ndir; a.wform = wform; a.nflagcorr = nflagcorr; a.autocorr = autocorr != 0;
     a.subtract = subtract != 0;
     a.vis = vis; a.wgt = wgt; a.mask = mask; a.ws = work;
-    const int rc = stk_by_type(dtype, [&](auto t) {
-        return stk_by_index<PFB_STOKES_NOJ2>(mode, [&](auto m) {
-            return stk_by_index<3>(basis, [&](auto b) { return stk_launch<decltype(t), m(), b()>(a, stream); });
+    const size_t groups = a.ngroups < (size_t)STK_MAX_GROUPS ? a.ngroups : (size_t)STK_MAX_GROUPS;
+    const int rc = by_type(dtype, [&](auto t) {
+        return by_int<0, PFB_STOKES_NOJ2>(mode, [&](auto m) {
+            return by_int<0, 3>(basis, [&](auto b) {
+                return launch_groups(k_stokes<decltype(t), m(), b()>, groups, stream, a);
+            });
         });
     });
-    if (rc != PFB_OK) return rc;
-    const int groups = (int)(a.ngroups < (size_t)STK_MAX_GROUPS ? a.ngroups : (size_t)STK_MAX_GROUPS);
-    hipLaunchKernelGGL(k_final_sum<STK_BLOCK>, dim3(1), dim3(STK_BLOCK), 0, as_stream(stream), (const double*)work, groups,
-                       1, wsum);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return rc != PFB_OK ? rc : final_sum(work, (int)groups, 1, wsum, stream);
 }
 
 }  // extern "C"

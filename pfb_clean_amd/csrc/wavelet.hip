@@ -19,6 +19,7 @@
 //   synthesis 1-D:  out[2m+p] = sum_{j<F/2} lo[2j+p] a[m+h-1-j] + sum_j hi[2j+p] d[m+h-1-j]
 //                   m = 0 .. N-h,  h = F/2                           (wavelets.py:99-123)
 #include "common.hpp"
+#include "entry.hpp"
 #include <vector>
 #include <cstring>
 
@@ -1236,9 +1237,7 @@ static int pd_primal_t(const void* xp, const void* xout, const void* xprev, cons
                            (const T*)g, (const T*)gsub, (T)tau, positivity, nband, n, (T*)x, ws);
     };
     if (vec) launch(k_pd_primal_vec<T, V16<T>::N>); else launch(k_pd_primal_vec<T, 1>);
-    hipLaunchKernelGGL(k_final_sum<RED_BLOCK>, dim3(1), dim3(RED_BLOCK), 0, st, ws, G, 3, sums);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
+    return final_sum(ws, G, 3, sums, st);
 }
 
 }  // namespace pfb

@@ -15,17 +15,14 @@
 // turns leaves 1e-6 of a turn in fp32.  Kernel values, grids and sums are in the data's type.
 //
 // Every index is reduced modulo the grid before it is used, so no coordinate, however wild, addresses outside it.
-#include "common.hpp"
+#include "entry.hpp"
 #include <new>
 
 namespace pfb {
 
-typedef unsigned char u8;
-
-constexpr int WG_BLOCK = 256;
+constexpr int WG_BLOCK = ENTRY_BLOCK;
 constexpr int WG_MIN_W = 4, WG_MAX_W = 12;
 constexpr int WG_MAX_TILES = 4096;        // uv tiles of the sort key; the tile edge doubles from 16 until they fit
-constexpr double WG_C = 299792458.0;
 
 struct WgridPlan {
     int dtype, nx, ny, Nu, Nv, W, nplanes, np0, tile, ntu, ntv;
@@ -56,9 +53,6 @@ __device__ __forceinline__ int wg_wrap(double a0, int N) {
     return i < 0 ? 0 : (i >= N ? N - 1 : i);
 }
 
-__device__ __forceinline__ void wg_atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
-__device__ __forceinline__ void wg_atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }
-
 struct WgGeom {
     int Nu, Nv, W, np0, tile, ntv, wk;
     double su, sv, w0, dw, h;          // su = pixsize_x Nu: u -> cells
@@ -69,9 +63,9 @@ __device__ __forceinline__ void wg_coords(const double* __restrict__ uvw, const 
                                           int nchan, const WgGeom& g, double& ug, double& vg, double& pg) {
     const size_t r = t / nchan;
     const double f = freq[t - r * nchan];
-    ug = uvw[3 * r] * f / WG_C * g.su;
-    vg = uvw[3 * r + 1] * f / WG_C * g.sv;
-    pg = g.wk ? (uvw[3 * r + 2] * f / WG_C - g.w0) / g.dw : 0.0;
+    ug = uvw[3 * r] * f / C_LIGHT * g.su;
+    vg = uvw[3 * r + 1] * f / C_LIGHT * g.sv;
+    pg = g.wk ? (uvw[3 * r + 2] * f / C_LIGHT - g.w0) / g.dw : 0.0;
 }
 
 __global__ void __launch_bounds__(WG_BLOCK)
@@ -198,7 +192,7 @@ k_grid(const cplx<T>* __restrict__ val, const double* __restrict__ coord, size_t
 #pragma unroll
     for (int a = 0; a < W; ++a) {
         const T fu = wg_phi<T>((T)((a0 + a - ug) / h), beta);
-        wg_atomic_add(cell + 2 * (size_t)row * g.Nv, fu * part);
+        atomic_add(cell + 2 * (size_t)row * g.Nv, fu * part);
         if (++row == g.Nu) row = 0;
     }
 }
@@ -311,9 +305,8 @@ k_image_correct(const cplx<T>* __restrict__ img, const double* __restrict__ corr
 }
 
 // ------------------------------------------------------------------------------------------------------ launchers
-// An entry point is: wg_check on its plan and pointers, its size checks, then wg_launch from a wg_by_type (and, for the
-// footprint kernels, wg_by_support) lambda.  A new one needs nothing else ("The entry layer").
-static inline unsigned wg_blocks(size_t n) { return (unsigned)((n + WG_BLOCK - 1) / WG_BLOCK); }
+// The entry layer is entry.hpp; what follows is the w-gridder's own: the geometry record of the kernels, the plan in
+// front of check(), and the size checks that speak of planes and slots.
 constexpr size_t WG_MAX_THREADS = (size_t)0x7fffffff * WG_BLOCK;        // one launch's grid limit
 
 static WgGeom wg_geom(const WgridPlan& p) {
@@ -323,61 +316,14 @@ static WgGeom wg_geom(const WgridPlan& p) {
     return g;
 }
 
-// a void pointer of the C ABI becomes the kernel parameter it is passed for; every other argument goes as it is
-template <typename P, typename A>
-static P wg_arg(A a) {
-    if constexpr (std::is_void_v<std::remove_pointer_t<A>>) return static_cast<P>(a);
-    else return a;
-}
-// `kernel` with a lane per element of n, on the stream
-template <typename... P, typename... A>
-static int wg_launch(void (*kernel)(P...), size_t n, void* stream, A... args) {
-    hipLaunchKernelGGL(kernel, dim3(wg_blocks(n)), dim3(WG_BLOCK), 0, as_stream(stream), wg_arg<P>(args)...);
-    PFB_HIP_CHECK(hipGetLastError());
-    return PFB_OK;
-}
-
-// f(float{}) or f(double{}): the plan's data type
-template <typename F>
-static int wg_by_type(const WgridPlan& p, F&& f) { return p.dtype == PFB_F32 ? f(float{}) : f(double{}); }
-// f(std::integral_constant<int, W>{}), W = 4 .. 12 (anything else: 12): one instantiation per support, so that the
-// footprint loops unroll and the row of kernel values stays in registers
-template <int W = WG_MIN_W, typename F>
-static int wg_by_support(int w, F&& f) {
-    if constexpr (W < WG_MAX_W) {
-        if (w != W) return wg_by_support<W + 1>(w, f);
-    }
-    return f(std::integral_constant<int, W>{});
-}
-
-// a pointer argument: what it points to (REAL, CPLX: of the plan's type) and whether it may be null
-enum WgKind { WG_REAL, WG_CPLX, WG_F64, WG_I32, WG_I64 };
-struct WgArray { const void* ptr; WgKind kind; bool optional = false; };
-
-// the plan and the pointers of entry point `name`: none null that may not be, each aligned to its element
-static int wg_check(const void* plan, const char* name, std::initializer_list<WgArray> arrays) {
-    PFB_REQUIRE(plan, PFB_ERR_INVALID, "%s: null plan", name);
-    const size_t e = static_cast<const WgridPlan*>(plan)->esize();
-    for (const WgArray& a : arrays) PFB_REQUIRE(a.ptr || a.optional, PFB_ERR_INVALID, "%s: null argument", name);
-    for (const WgArray& a : arrays) {
-        const size_t align = a.kind == WG_REAL ? e : a.kind == WG_CPLX ? 2 * e : a.kind == WG_I32 ? 4 : 8;
-        PFB_REQUIRE(((uintptr_t)a.ptr & (align - 1)) == 0, PFB_ERR_INVALID, "%s: an array is not aligned to its element size", name);
-    }
-    return PFB_OK;
-}
 static const WgridPlan& wg_plan(const void* plan) { return *static_cast<const WgridPlan*>(plan); }
+// the plan and the pointers of entry point `name` (REAL, CPLX: of the plan's type)
+static int wg_check(const void* plan, const char* name, std::initializer_list<Array> arrays) {
+    PFB_REQUIRE(plan, PFB_ERR_INVALID, "%s: null plan", name);
+    return check(wg_plan(plan).dtype, name, arrays);
+}
 
-// the size checks: nrow x nchan visibilities that an int indexes; as many slots; a plane; slots [s0, s1) of a plane,
-// few enough for one launch of k_grid (2 W lanes a slot)
-static int wg_nvis(const char* name, size_t nrow, int nchan) {
-    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff / (size_t)nchan, PFB_ERR_UNSUPPORTED,
-                "%s: %zu rows x %d channels outside [1, 2^31)", name, nrow, nchan);
-    return PFB_OK;
-}
-static int wg_slots(const char* name, size_t nsorted) {
-    PFB_REQUIRE(nsorted >= 1 && nsorted <= (size_t)0x7fffffff, PFB_ERR_INVALID, "%s: %zu slots", name, nsorted);
-    return PFB_OK;
-}
+// a plane; slots [s0, s1) of a plane, few enough for one launch of k_grid (2 W lanes a slot)
 static int wg_plane(const WgridPlan& p, const char* name, int plane) {
     PFB_REQUIRE(plane >= 0 && plane < p.nplanes, PFB_ERR_INVALID, "%s: plane %d of %d", name, plane, p.nplanes);
     return PFB_OK;
@@ -449,124 +395,122 @@ size_t pfb_wgrid_work_bytes(void* plan) { return plan ? 2 * sizeof(int) * (size_
 
 int pfb_wgrid_order_count(void* plan, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow,
                           int nchan, int* keys, void* work, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_order_count", {{uvw, WG_F64}, {freq, WG_F64}, {keys, WG_I32}, {work, WG_I32}});
+    if (int rc = wg_check(plan, "wgrid_order_count", {{uvw, F64}, {freq, F64}, {keys, I32}, {work, I32}});
         rc != PFB_OK) return rc;
-    if (int rc = wg_nvis("wgrid_order_count", nrow, nchan); rc != PFB_OK) return rc;
+    if (int rc = check_nvis("wgrid_order_count", nrow, nchan); rc != PFB_OK) return rc;
     const size_t nvis = nrow * (size_t)nchan;
     PFB_HIP_CHECK(hipMemsetAsync(work, 0, pfb_wgrid_work_bytes(plan), as_stream(stream)));
-    return wg_launch(k_order_count, nvis, stream, uvw, freq, mask, nvis, nchan, wg_geom(wg_plan(plan)), keys, work);
+    return launch(k_order_count, nvis, stream, uvw, freq, mask, nvis, nchan, wg_geom(wg_plan(plan)), keys, work);
 }
 
 int pfb_wgrid_order_fill(void* plan, const double* uvw, const double* freq, size_t nrow, int nchan, const int* keys,
                          const long long* offsets, void* work, size_t nsorted, int* idx, double* coord, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_order_fill", {{uvw, WG_F64}, {freq, WG_F64}, {keys, WG_I32}, {offsets, WG_I64},
-                                                     {work, WG_I32}, {idx, WG_I32}, {coord, WG_F64}});
+    if (int rc = wg_check(plan, "wgrid_order_fill", {{uvw, F64}, {freq, F64}, {keys, I32}, {offsets, I64},
+                                                     {work, I32}, {idx, I32}, {coord, F64}});
         rc != PFB_OK) return rc;
-    if (int rc = wg_nvis("wgrid_order_fill", nrow, nchan); rc != PFB_OK) return rc;
+    if (int rc = check_nvis("wgrid_order_fill", nrow, nchan); rc != PFB_OK) return rc;
     const WgridPlan& p = wg_plan(plan);
     const size_t nvis = nrow * (size_t)nchan;
     PFB_REQUIRE(nsorted >= 1 && nsorted <= nvis, PFB_ERR_INVALID, "wgrid_order_fill: %zu slots for %zu visibilities",
                 nsorted, nvis);
-    return wg_launch(k_order_fill, nvis, stream, uvw, freq, nvis, nchan, wg_geom(p), keys, offsets, (int*)work + p.nkeys(),
-                     nsorted, idx, coord);
+    return launch(k_order_fill, nvis, stream, uvw, freq, nvis, nchan, wg_geom(p), keys, offsets, (int*)work + p.nkeys(),
+                  nsorted, idx, coord);
 }
 
 int pfb_wgrid_prep(void* plan, const void* vis, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                    void* val, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_prep", {{vis, WG_CPLX}, {wgt, WG_REAL, true}, {idx, WG_I32}, {coord, WG_F64},
-                                               {val, WG_CPLX}});
+    if (int rc = wg_check(plan, "wgrid_prep", {{vis, CPLX}, {wgt, REAL, true}, {idx, I32}, {coord, F64}, {val, CPLX}});
         rc != PFB_OK) return rc;
-    if (int rc = wg_slots("wgrid_prep", nsorted); rc != PFB_OK) return rc;
+    if (int rc = check_count("wgrid_prep", nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
     const WgridPlan& p = wg_plan(plan);
-    return wg_by_type(p, [&](auto t) {
-        return wg_launch(k_prep<decltype(t)>, nsorted, stream, vis, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), val);
+    return by_type(p.dtype, [&](auto t) {
+        return launch(k_prep<decltype(t)>, nsorted, stream, vis, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), val);
     });
 }
 
 int pfb_wgrid_finish(void* plan, const void* acc, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                      void* vis, size_t nvis, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_finish", {{acc, WG_CPLX}, {wgt, WG_REAL, true}, {idx, WG_I32}, {coord, WG_F64},
-                                                 {vis, WG_CPLX}});
+    if (int rc = wg_check(plan, "wgrid_finish", {{acc, CPLX}, {wgt, REAL, true}, {idx, I32}, {coord, F64},
+                                                 {vis, CPLX}});
         rc != PFB_OK) return rc;
-    if (int rc = wg_slots("wgrid_finish", nsorted); rc != PFB_OK) return rc;
+    if (int rc = check_count("wgrid_finish", nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
     PFB_REQUIRE(nsorted <= nvis && nvis <= (size_t)0x7fffffff, PFB_ERR_INVALID,
                 "wgrid_finish: %zu slots for %zu visibilities", nsorted, nvis);
     const WgridPlan& p = wg_plan(plan);
     PFB_HIP_CHECK(hipMemsetAsync(vis, 0, 2 * p.esize() * nvis, as_stream(stream)));
-    return wg_by_type(p, [&](auto t) {
-        return wg_launch(k_finish<decltype(t)>, nsorted, stream, acc, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), vis);
+    return by_type(p.dtype, [&](auto t) {
+        return launch(k_finish<decltype(t)>, nsorted, stream, acc, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), vis);
     });
 }
 
 int pfb_wgrid_weight(void* plan, const void* acc, const void* wgt, const int* idx, size_t nsorted, void* val,
                      void* stream) {
-    if (int rc = wg_check(plan, "wgrid_weight", {{acc, WG_CPLX}, {wgt, WG_REAL, true}, {idx, WG_I32}, {val, WG_CPLX}});
+    if (int rc = wg_check(plan, "wgrid_weight", {{acc, CPLX}, {wgt, REAL, true}, {idx, I32}, {val, CPLX}});
         rc != PFB_OK) return rc;
-    if (int rc = wg_slots("wgrid_weight", nsorted); rc != PFB_OK) return rc;
-    return wg_by_type(wg_plan(plan), [&](auto t) {
-        return wg_launch(k_weight<decltype(t)>, nsorted, stream, acc, wgt, idx, nsorted, val);
+    if (int rc = check_count("wgrid_weight", nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
+    return by_type(wg_plan(plan).dtype, [&](auto t) {
+        return launch(k_weight<decltype(t)>, nsorted, stream, acc, wgt, idx, nsorted, val);
     });
 }
 
 int pfb_wgrid_grid(void* plan, int plane, const void* val, const double* coord, size_t nsorted, size_t s0, size_t s1,
                    void* grid, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_grid", {{val, WG_CPLX}, {coord, WG_F64}, {grid, WG_CPLX}}); rc != PFB_OK) return rc;
+    if (int rc = wg_check(plan, "wgrid_grid", {{val, CPLX}, {coord, F64}, {grid, CPLX}}); rc != PFB_OK) return rc;
     const WgridPlan& p = wg_plan(plan);
     if (int rc = wg_range(p, "wgrid_grid", plane, s0, s1, nsorted); rc != PFB_OK) return rc;
     PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes(), as_stream(stream)));
     if (s1 == s0) return PFB_OK;
-    return wg_by_type(p, [&](auto t) {
-        return wg_by_support(p.W, [&](auto w) {
-            return wg_launch(k_grid<decltype(t), w()>, (s1 - s0) * 2 * w(), stream, val, coord, nsorted, s0, s1, plane,
-                             wg_geom(p), grid);
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<WG_MIN_W, WG_MAX_W>(p.W, [&](auto w) {
+            return launch(k_grid<decltype(t), w()>, (s1 - s0) * 2 * w(), stream, val, coord, nsorted, s0, s1, plane,
+                          wg_geom(p), grid);
         });
     });
 }
 
 int pfb_wgrid_degrid(void* plan, int plane, const void* grid, const double* coord, size_t nsorted, size_t s0, size_t s1,
                      void* acc, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_degrid", {{grid, WG_CPLX}, {coord, WG_F64}, {acc, WG_CPLX}}); rc != PFB_OK) return rc;
+    if (int rc = wg_check(plan, "wgrid_degrid", {{grid, CPLX}, {coord, F64}, {acc, CPLX}}); rc != PFB_OK) return rc;
     const WgridPlan& p = wg_plan(plan);
     if (int rc = wg_range(p, "wgrid_degrid", plane, s0, s1, nsorted); rc != PFB_OK) return rc;
     if (s1 == s0) return PFB_OK;
-    return wg_by_type(p, [&](auto t) {
-        return wg_by_support(p.W, [&](auto w) {
-            return wg_launch(k_degrid<decltype(t), w()>, s1 - s0, stream, grid, coord, nsorted, s0, s1, plane, wg_geom(p), acc);
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<WG_MIN_W, WG_MAX_W>(p.W, [&](auto w) {
+            return launch(k_degrid<decltype(t), w()>, s1 - s0, stream, grid, coord, nsorted, s0, s1, plane, wg_geom(p), acc);
         });
     });
 }
 
 int pfb_wgrid_image_forward(void* plan, int plane, const void* dirty, const void* beam, const double* corr,
                             const double* nm1, void* grid, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_image_forward", {{dirty, WG_REAL}, {beam, WG_REAL, true}, {corr, WG_F64},
-                                                        {nm1, WG_F64, true}, {grid, WG_CPLX}});
+    if (int rc = wg_check(plan, "wgrid_image_forward", {{dirty, REAL}, {beam, REAL, true}, {corr, F64},
+                                                        {nm1, F64, true}, {grid, CPLX}});
         rc != PFB_OK) return rc;
     const WgridPlan& p = wg_plan(plan);
     if (int rc = wg_plane(p, "wgrid_image_forward", plane); rc != PFB_OK) return rc;
     PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes(), as_stream(stream)));
-    return wg_by_type(p, [&](auto t) {
-        return wg_launch(k_image_forward<decltype(t)>, p.npix(), stream, dirty, beam, corr, nm1, p.wp(plane), p.nx, p.ny,
-                         p.Nu, p.Nv, grid);
+    return by_type(p.dtype, [&](auto t) {
+        return launch(k_image_forward<decltype(t)>, p.npix(), stream, dirty, beam, corr, nm1, p.wp(plane), p.nx, p.ny,
+                      p.Nu, p.Nv, grid);
     });
 }
 
 int pfb_wgrid_image_adjoint(void* plan, int plane, const void* grid, const double* nm1, void* img, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_image_adjoint", {{grid, WG_CPLX}, {nm1, WG_F64, true}, {img, WG_CPLX}});
+    if (int rc = wg_check(plan, "wgrid_image_adjoint", {{grid, CPLX}, {nm1, F64, true}, {img, CPLX}});
         rc != PFB_OK) return rc;
     const WgridPlan& p = wg_plan(plan);
     if (int rc = wg_plane(p, "wgrid_image_adjoint", plane); rc != PFB_OK) return rc;
-    return wg_by_type(p, [&](auto t) {
-        return wg_launch(k_image_adjoint<decltype(t)>, p.npix(), stream, grid, nm1, p.wp(plane), p.nx, p.ny, p.Nu, p.Nv, img);
+    return by_type(p.dtype, [&](auto t) {
+        return launch(k_image_adjoint<decltype(t)>, p.npix(), stream, grid, nm1, p.wp(plane), p.nx, p.ny, p.Nu, p.Nv, img);
     });
 }
 
 int pfb_wgrid_image_correct(void* plan, const void* img, const double* corr, const void* beam, void* dirty, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_image_correct", {{img, WG_CPLX}, {corr, WG_F64}, {beam, WG_REAL, true},
-                                                        {dirty, WG_REAL}});
+    if (int rc = wg_check(plan, "wgrid_image_correct", {{img, CPLX}, {corr, F64}, {beam, REAL, true}, {dirty, REAL}});
         rc != PFB_OK) return rc;
     const WgridPlan& p = wg_plan(plan);
-    return wg_by_type(p, [&](auto t) {
-        return wg_launch(k_image_correct<decltype(t)>, p.npix(), stream, img, corr, beam, p.npix(), dirty);
+    return by_type(p.dtype, [&](auto t) {
+        return launch(k_image_correct<decltype(t)>, p.npix(), stream, img, corr, beam, p.npix(), dirty);
     });
 }
 

@@ -117,20 +117,10 @@ class WgridPlan(NativePlan):
         self.W = W = support_for(self.epsilon)
         self.nx, self.ny = nx, ny
         self.do_wgridding = bool(do_wgridding)
-        self.uvw = _dev.to_dev(uvw)
-        self.freq = _dev.to_dev(freq)
-        if self.uvw.dtype != torch.float64 or self.freq.dtype != torch.float64:
-            raise TypeError("uvw and freq must be float64")
-        if self.uvw.ndim != 2 or self.uvw.shape[1] != 3 or self.freq.ndim != 1:
-            raise ValueError("uvw must be (nrow, 3) and freq (nchan,)")
+        self.uvw, self.freq = _dev.uvw_freq(uvw, freq)
         self.nrow, self.nchan = int(self.uvw.shape[0]), int(self.freq.shape[0])
         self.nvis = self.nrow * self.nchan
-        self.mask = None
-        if mask is not None:
-            md = _dev.to_dev(mask)
-            if md.dtype not in (torch.uint8, torch.bool) or tuple(md.shape) != (self.nrow, self.nchan):
-                raise ValueError("mask must be uint8 or bool of shape (nrow, nchan)")
-            self.mask = md.to(torch.uint8).contiguous()
+        self.mask = None if mask is None else _dev.byte_mask(mask, (self.nrow, self.nchan))
         if self.do_wgridding:
             nm1 = image_lmn(nx, ny, pixsize_x, pixsize_y, center_x, center_y)[2]
         else:
@@ -371,7 +361,7 @@ def image_data_products(uvw, freq, vis, wgt, mask, counts, nx, ny, nx_psf, ny_ps
     cdt_in, rdt_in = vd.dtype, _dev.REAL_OF[vd.dtype]
     rdt = torch.float64 if double_accum else rdt_in
     cdt = _dev.CPLX_OF[rdt]
-    md = weighting._mask(mask, vd.shape)
+    md = _dev.byte_mask(mask, vd.shape)
     wd = _dev.to_dev(wgt)
     if wd is not None and (wd.dtype != rdt_in or wd.shape != vd.shape):
         raise TypeError(f"wgt must be {rdt_in} of the shape of vis, got {wd.dtype} {tuple(wd.shape)}")

@@ -71,13 +71,6 @@ def _aligned(t, nbytes):
     return t if t is None or t.data_ptr() % min(nbytes, 16) == 0 else t.clone()
 
 
-def _flags(a, shape, name):
-    d = _dev.to_dev(a)
-    if d.dtype not in (torch.uint8, torch.bool) or tuple(d.shape) != tuple(shape):
-        raise ValueError(f"{name} must be bool or uint8 of shape {tuple(shape)}")
-    return d.view(torch.uint8) if d.dtype == torch.bool else d
-
-
 def _time_bins(tbin_idx, tbin_counts, dev):
     """(tbin_idx, tbin_counts) as int64 device tensors -- copies, the caller's arrays stay as they are -- and the
     minimum of tbin_idx, after the host's check that the bins ascend without overlap."""
@@ -191,8 +184,8 @@ def stokes_vis(data, ant1, ant2, tbin_idx, tbin_counts, poltype, product, data2=
         wform = W_ROW if wd.ndim == 2 else W_SPECTRUM
     else:
         wd, wform = None, W_NONE
-    fd = None if flag is None else _flags(flag, (nrow, nchan, nc), 'flag')
-    fr = None if frow is None else _flags(frow, (nrow,), 'frow')
+    fd = None if flag is None else _dev.byte_mask(flag, (nrow, nchan, nc), 'flag')
+    fr = None if frow is None else _dev.byte_mask(frow, (nrow,), 'frow')
     jd = None
     if jones is not None:
         jd = _dev.to_dev(jones)

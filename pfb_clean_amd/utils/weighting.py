@@ -52,22 +52,6 @@ def uv_cells(nx, ny, cell_size_x, cell_size_y):
     return float(u_cell), float(umax), float(v_cell), float(vmax)
 
 
-def _coords(uvw, freq):
-    ud, fd = _dev.to_dev(uvw), _dev.to_dev(freq)
-    if ud.dtype != torch.float64 or fd.dtype != torch.float64:
-        raise TypeError("uvw and freq must be float64")
-    if ud.ndim != 2 or ud.shape[1] != 3 or fd.ndim != 1:
-        raise ValueError("uvw must be (nrow, 3) and freq (nchan,)")
-    return ud, fd
-
-
-def _mask(mask, shape):
-    md = _dev.to_dev(mask)
-    if md is None or md.dtype not in (torch.uint8, torch.bool) or tuple(md.shape) != tuple(shape):
-        raise ValueError(f"mask must be uint8 or bool of shape {tuple(shape)}")
-    return md.view(torch.uint8) if md.dtype == torch.bool else md
-
-
 def _record(dev):
     return torch.empty(RECORD, dtype=torch.float64, device=dev)
 
@@ -87,9 +71,9 @@ def _compute_counts(uvw, freq, mask, nx, ny, cell_size_x, cell_size_y, dtype, k=
     nx, ny, ngrid = int(nx), int(ny), int(ngrid)
     if ngrid < 1:
         raise ValueError(f"ngrid must be >= 1, got {ngrid}")
-    ud, fd = _coords(uvw, freq)
+    ud, fd = _dev.uvw_freq(uvw, freq)
     nrow, nchan = int(ud.shape[0]), int(fd.shape[0])
-    md = _mask(mask, (nrow, nchan))
+    md = _dev.byte_mask(mask, (nrow, nchan))
     counts = torch.empty((ngrid, nx, ny), dtype=rdt, device=ud.device)
     if nrow * nchan == 0:
         counts.zero_()
@@ -115,7 +99,7 @@ def _counts_to_weights(counts, uvw, freq, nx, ny, cell_size_x, cell_size_y, robu
     nx, ny = int(nx), int(ny)
     if cd.dtype not in (torch.float32, torch.float64) or tuple(cd.shape) != (nx, ny):
         raise ValueError(f"counts must be float32 or float64 of shape {(nx, ny)}, got {cd.dtype} {tuple(cd.shape)}")
-    ud, fd = _coords(uvw, freq)
+    ud, fd = _dev.uvw_freq(uvw, freq)
     nrow, nchan = int(ud.shape[0]), int(fd.shape[0])
     weights = torch.zeros((nrow, nchan), dtype=cd.dtype, device=cd.device)
     if nrow * nchan:
@@ -200,7 +184,7 @@ def _l2_reweight_dev(vis, model_vis, mask, dof, imwgt=None):
 def l2_reweight(vis, model_vis, mask, dof, imwgt=None):
     """gridder.py:604-615 as a function: (residual_vis, wgt, wsum), see _l2_reweight_dev; numpy in gives numpy out."""
     vd = _dev.to_dev(vis)
-    md = _mask(mask, vd.shape)
+    md = _dev.byte_mask(mask, vd.shape)
     out = _l2_reweight_dev(vd, _dev.to_dev(model_vis), md, dof, _dev.to_dev(imwgt))
     return tuple(None if t is None else _dev.host_like(t, vis) for t in out)
 
@@ -225,7 +209,7 @@ def _weight_data(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, p
     dd = _dev.to_dev(data)
     if dd.ndim != 3 or dd.shape[2] != n:
         raise ValueError(f"data must be (nrow, nchan, {n}) for nc={nc!r}, got {tuple(dd.shape)}")
-    fd = _stokes._flags(flag, tuple(dd.shape[:2]), 'flag')
+    fd = _dev.byte_mask(flag, tuple(dd.shape[:2]), 'flag')
     vis, wgt, _, _ = _stokes.run(dd, _dev.to_dev(weight), _stokes.W_SPECTRUM, fd, None, False, _dev.to_dev(jones),
                                  tbin_idx, tbin_counts, ant1, ant2, basis)
     return _dev.host_like(vis, data), _dev.host_like(wgt, data)

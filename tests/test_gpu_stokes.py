@@ -287,6 +287,56 @@ def test_value_errors():
     check(case, *(weight_data(**dict(a, nc=4))[k] for k in ('vis', 'wgt')), 'f64')
 
 
+def test_c_abi_refusals():
+    """pfb_stokes_vis itself: the smallest good call answers PFB_OK and stokes_vis's sum; with one argument changed at a
+    time it answers the status below before any launch -- the pointers real all the same -- and writes nothing."""
+    from pfb_clean_amd import _lib
+    from pfb_clean_amd.utils import stokes as st
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    INV, UNS = _lib.PFB_ERR_INVALID, _lib.PFB_ERR_UNSUPPORTED
+    nrow, nchan, nc = 2, 2, 2
+    data = dev(np.arange(1, 1 + 2 * nrow * nchan * nc, dtype=np.float64).view(np.complex128).reshape(nrow, nchan, nc))
+    ti, tcnt = dev(np.array([0], dtype=np.int64)), dev(np.array([nrow], dtype=np.int64))
+    a1, a2 = dev(np.array([0, 0], dtype=np.int32)), dev(np.array([1, 1], dtype=np.int32))
+    vis = torch.empty((nrow, nchan), dtype=torch.complex128, device='cuda')
+    wgt = torch.empty((nrow, nchan), dtype=torch.float64, device='cuda')
+    mask = torch.empty((nrow, nchan), dtype=torch.uint8, device='cuda')
+    wsum = torch.empty(1, dtype=torch.float64, device='cuda')
+    work = torch.zeros(_lib.REDUCE_WS_DOUBLES, dtype=torch.float64, device='cuda')
+    names = ('dtype mode basis data data2 subtract weight wform flag nflagcorr frow autocorr jones ndir ntime nant '
+             'tbin_idx tbin_counts tbin_off ant1 ant2 nrow nchan vis wgt mask wsum work').split()
+    good = dict(zip(names, [_lib.PFB_F64, st.NOJ2, 0, data.data_ptr(), None, 0, None, st.W_NONE, None, 0, None, 0, None,
+                            1, 1, 2, ti.data_ptr(), tcnt.data_ptr(), 0, a1.data_ptr(), a2.data_ptr(), nrow, nchan,
+                            vis.data_ptr(), wgt.data_ptr(), mask.data_ptr(), wsum.data_ptr(), work.data_ptr()]))
+    assert len(good) == len(names) == 28
+
+    def call(**over):
+        return lib.pfb_stokes_vis(*dict(good, **over).values(), stream)
+
+    assert call() == _lib.PFB_OK
+    want = st.stokes_vis(data, a1, a2, ti, tcnt, 'linear', 'I', precision='double')
+    assert float(wsum[0]) == float(want[3][0]) == nrow * nchan * float(want[1][0, 0])       # 4 x the one wgt value
+    assert torch.equal(vis, want[0]) and torch.equal(wgt, want[1]) and torch.equal(mask, want[2])
+
+    vis.fill_(-7 - 7j), wgt.fill_(-7.0), mask.fill_(0xAB), wsum.fill_(-7.0)
+    refused = [dict(dtype=2), dict(mode=-1), dict(mode=st.NOJ2 + 1), dict(basis=4), dict(wform=-1),
+               dict(wform=st.W_ROW + 1), dict(nflagcorr=3)]
+    refused += [{name: None} for name in ('data', 'tbin_idx', 'tbin_counts', 'ant1', 'ant2', 'vis', 'wgt', 'mask', 'wsum',
+                                          'work')]
+    refused += [dict(wform=st.W_SPECTRUM), dict(mode=st.DIAG2)]          # weight / jones null where they are read
+    # the 16-byte vector loads of data, and every array's element
+    refused += [{name: good[name] + off} for name, off in (('data', 8), ('vis', 8), ('wgt', 4), ('ant1', 2),
+                                                          ('tbin_idx', 4))]
+    refused += [dict(ntime=0), dict(nant=0), dict(ndir=0)]
+    for over in refused:
+        assert call(**over) == INV, over
+    for over in (dict(nrow=0), dict(nchan=0)):
+        assert call(**over) == UNS, over
+    torch.cuda.synchronize()
+    assert (vis == -7 - 7j).all() and (wgt == -7.0).all() and (mask == 0xAB).all() and (wsum == -7.0).all()
+
+
 @pytest.mark.parametrize('tag', TAGS)
 def test_a_singular_jones_matrix_is_not_an_error(tag):
     """IEEE inf / nan on the unflagged visibilities that read it, as in the reference; everything else as before."""
