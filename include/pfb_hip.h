@@ -745,6 +745,22 @@ int pfb_wgrid_prep(void* plan, const void* vis, const void* wgt, const int* idx,
 /* vis = 0, then vis[idx[s]] = wgt acc[s] exp(-2 pi i (u center_x + v center_y)); vis holds nvis = nrow * nchan. */
 int pfb_wgrid_finish(void* plan, const void* acc, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                      void* vis, size_t nvis, void* stream);
+/* The block form of pfb_wgrid_finish, for the predict step (pfb/operators/gridder.py:492-548): `plan` is a plan on a
+ * block of rows and channels, (.., nchan_blk) visibilities without a mask, and `out` a (nrow_out, nchan_out, ncorr)
+ * complex array of `out_dtype` -- the plan's type, or PFB_F32 under a double-precision plan (the worker's
+ * astype(complex64), one rounding).  For slot s, t = idx[s], r = t / nchan_blk, c = t % nchan_blk and
+ * v = acc[s] exp(-2 pi i (u center_x + v center_y)) formed as pfb_wgrid_finish forms it:
+ *   out[row0 + r, chan0 + c, k] = (out type) v            for k = 0 and k = ncorr - 1,
+ *   out[row0 + r, chan0 + c, k] += (out type) v           with accumulate != 0: cast first, then add in the out type.
+ * No weight (the reference applies none in this direction), no memset and no other cell written: zeroing is the
+ * caller's.  ncorr in 1 .. 4, chan0 + nchan_blk <= nchan_out, every row0 + r inside out (the caller's check: out's
+ * extent is not passed).  PFB_ERR_INVALID: a complex128 output under a single-precision plan. */
+int pfb_wgrid_finish_block(void* plan, const void* acc, const int* idx, const double* coord, size_t nsorted,
+                           int nchan_blk, void* out, int out_dtype, size_t row0, int nchan_out, int chan0, int ncorr,
+                           int accumulate, void* stream);
+/* pfb/utils/misc.py:498-503 (_restore_corrs): out (nvis, ncorr) complex `dtype`, out[v, 0] = out[v, ncorr - 1] = vis[v]
+ * and zero between, every element written by one launch (no memset).  ncorr in 1 .. 4, nvis < 2^31. */
+int pfb_vis_restore_corrs(int dtype, const void* vis, size_t nvis, int ncorr, void* out, void* stream);
 /* val[s] = wgt acc[s]: degridding handed straight to gridding (the Hessian; the centre phases cancel). */
 int pfb_wgrid_weight(void* plan, const void* acc, const void* wgt, const int* idx, size_t nsorted, void* val,
                      void* stream);

@@ -136,6 +136,8 @@ SIGNATURES = {
     'pfb_wgrid_order_fill': (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     'pfb_wgrid_prep': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'pfb_wgrid_finish': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'pfb_wgrid_finish_block': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _i, _sz, _i, _i, _i, _i, _vp]),
+    'pfb_vis_restore_corrs': (_i, [_i, _vp, _sz, _i, _vp, _vp]),
     'pfb_wgrid_weight': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'pfb_wgrid_grid': (_i, [_vp, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     'pfb_wgrid_degrid': (_i, [_vp, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),

@@ -5,6 +5,7 @@
 //   k_order_count / k_order_fill   counting sort of the unmasked visibilities by (first w plane, uv tile): histogram, the
 //                                  caller's scan, placement.  Plane p's visibilities are then one contiguous range
 //   k_prep / k_finish / k_weight   visibility <-> sorted slot: weight, centre phase, the zero of masked samples
+//   k_finish_block / k_restore_corrs   the predict step: a block's slots into a strided (row, chan, corr) model column
 //   k_grid                         one plane: 2 W lanes per visibility, a lane owns one real of a footprint row and adds
 //                                  down the W rows with float atomics (2 W contiguous reals per slot and instruction)
 //   k_degrid                       one plane: a lane per visibility gathers its W x W footprint; no atomics, each slot's
@@ -145,6 +146,39 @@ k_finish(const cplx<T>* __restrict__ acc, const T* __restrict__ wgt, const int* 
     if (centre) v = v * wg_cis<T>(-wg_centre_turns(coord, ns, s, cxs, cys));
     if (wgt) v = wgt[t] * v;
     vis[t] = v;
+}
+
+// the block form of k_finish: slot s is visibility (r, c) = (t / nchan_blk, t % nchan_blk) of a block of rows and
+// channels, landed at row0 + r, chan0 + c of a (.., nchan_out, ncorr) array in correlations 0 and ncorr - 1, cast to the
+// output's type O and then stored, or added in O.  No other cell is touched
+template <typename T, typename O>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_finish_block(const cplx<T>* __restrict__ acc, const int* __restrict__ idx, const double* __restrict__ coord, size_t ns,
+               double cxs, double cys, int centre, int nchan_blk, cplx<O>* __restrict__ out, size_t row0,
+               size_t nchan_out, size_t chan0, int ncorr, int accumulate) {
+    const size_t s = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (s >= ns) return;
+    const int t = idx[s];
+    if (t < 0) return;                 // an order never holds one; never address below the array
+    cplx<T> v = acc[s];
+    if (centre) v = v * wg_cis<T>(-wg_centre_turns(coord, ns, s, cxs, cys));
+    const cplx<O> o((O)v.x, (O)v.y);
+    const size_t r = (size_t)t / (size_t)nchan_blk, c = (size_t)t - r * (size_t)nchan_blk;
+    cplx<O>* cell = out + ((row0 + r) * nchan_out + chan0 + c) * (size_t)ncorr;
+    cell[0] = accumulate ? cell[0] + o : o;
+    if (ncorr > 1) cell[ncorr - 1] = accumulate ? cell[ncorr - 1] + o : o;
+}
+
+// out (nvis, ncorr): vis in correlations 0 and ncorr - 1, zero between; a lane per OUTPUT element, so a wave's stores
+// are consecutive
+template <typename T>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_restore_corrs(const cplx<T>* __restrict__ vis, size_t n, int ncorr, cplx<T>* __restrict__ out) {
+    const size_t e = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (e >= n) return;
+    const size_t v = e / (size_t)ncorr;
+    const int k = (int)(e - v * (size_t)ncorr);
+    out[e] = (k == 0 || k == ncorr - 1) ? vis[v] : cplx<T>(T(0), T(0));
 }
 
 // val[s] = wgt acc[s]: the Hessian's hand-over from degridding to gridding (the two centre phases cancel)
@@ -440,6 +474,44 @@ int pfb_wgrid_finish(void* plan, const void* acc, const void* wgt, const int* id
     PFB_HIP_CHECK(hipMemsetAsync(vis, 0, 2 * p.esize() * nvis, as_stream(stream)));
     return by_type(p.dtype, [&](auto t) {
         return launch(k_finish<decltype(t)>, nsorted, stream, acc, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), vis);
+    });
+}
+
+int pfb_wgrid_finish_block(void* plan, const void* acc, const int* idx, const double* coord, size_t nsorted,
+                           int nchan_blk, void* out, int out_dtype, size_t row0, int nchan_out, int chan0, int ncorr,
+                           int accumulate, void* stream) {
+    PFB_REQUIRE(out_dtype == PFB_F32 || out_dtype == PFB_F64, PFB_ERR_INVALID, "wgrid_finish_block: bad out_dtype %d",
+                out_dtype);
+    if (int rc = wg_check(plan, "wgrid_finish_block", {{acc, CPLX}, {idx, I32}, {coord, F64},
+                                                       {out, bytes(2 * esize(out_dtype))}});
+        rc != PFB_OK) return rc;
+    if (int rc = check_count("wgrid_finish_block", nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    PFB_REQUIRE(out_dtype == p.dtype || out_dtype == PFB_F32, PFB_ERR_INVALID,
+                "wgrid_finish_block: a complex128 output under a single-precision plan");
+    PFB_REQUIRE(ncorr >= 1 && ncorr <= 4, PFB_ERR_INVALID, "wgrid_finish_block: %d correlations outside 1 .. 4", ncorr);
+    PFB_REQUIRE(nchan_blk >= 1 && chan0 >= 0 && nchan_out >= 1 &&
+                (size_t)chan0 + (size_t)nchan_blk <= (size_t)nchan_out, PFB_ERR_INVALID,
+                "wgrid_finish_block: channels %d .. + %d of %d", chan0, nchan_blk, nchan_out);
+    return by_type(p.dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (std::is_same_v<T, double>) {
+            if (out_dtype == PFB_F32)
+                return launch(k_finish_block<T, float>, nsorted, stream, acc, idx, coord, nsorted, p.cxs(), p.cys(),
+                              p.centre(), nchan_blk, out, row0, (size_t)nchan_out, (size_t)chan0, ncorr, accumulate);
+        }
+        return launch(k_finish_block<T, T>, nsorted, stream, acc, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(),
+                      nchan_blk, out, row0, (size_t)nchan_out, (size_t)chan0, ncorr, accumulate);
+    });
+}
+
+int pfb_vis_restore_corrs(int dtype, const void* vis, size_t nvis, int ncorr, void* out, void* stream) {
+    if (int rc = check(dtype, "vis_restore_corrs", {{vis, CPLX}, {out, CPLX}}); rc != PFB_OK) return rc;
+    if (int rc = check_count("vis_restore_corrs", nvis, PFB_ERR_INVALID); rc != PFB_OK) return rc;
+    PFB_REQUIRE(ncorr >= 1 && ncorr <= 4, PFB_ERR_INVALID, "vis_restore_corrs: %d correlations outside 1 .. 4", ncorr);
+    const size_t n = nvis * (size_t)ncorr;
+    return by_type(dtype, [&](auto t) {
+        return launch(k_restore_corrs<decltype(t)>, n, stream, vis, n, ncorr, out);
     });
 }
 

@@ -16,9 +16,15 @@ arrays again builds nothing.  numpy in gives numpy out, tensors in give tensors 
 
 image_data_products (pfb/operators/gridder.py:551-740) composes these with utils/weighting.py into the grid worker's
 products: WEIGHT, WSUM, DIRTY, PSF, PSFHAT and RESIDUAL of one band.
+
+The predict step (pfb/operators/gridder.py:258-548) degrids on BLOCKS of rows and channels: im2vis a cube's
+bands into their channels, comps2vis the component model of every (time bin, band) into a (row, chan, corr) model column
+(pfb_wgrid_finish_block lands the sorted slots there), loc2psf_vis the PSF's visibilities.  A block's plan takes nm1 and
+the correction tables from the GeomTables of its geometry, which are built once, and never enters the plan cache.
 """
 import ctypes as C
 import math
+import threading
 
 import numpy as np
 import torch
@@ -26,6 +32,7 @@ import torch
 from .. import _dev, _lib
 from .._plan import NativePlan, PlanCache, array_key
 from ..utils import weighting
+from ..utils.comps import _render
 from .fft import psfhat_from_psf
 
 C_LIGHT = 299792458.0
@@ -100,13 +107,61 @@ def plane_layout(wmin, wmax, max_nm1, W, epsilon, do_wgridding):
     return int(math.ceil((wmax - wmin) / dw)) + W + 1, wmin - 0.5 * W * dw, dw
 
 
+class GeomTables:
+    """What every plan on one image geometry, support and do_wgridding shares, whatever its visibilities: nm1, and the
+    kernel correction 1 / (c_u c_v) with and without 1 / c_w(dw nm1) -- dw = 1 / (4 max|nm1|) is the geometry's too.
+    fp64 device tables, each formed on first use; use through tables_for."""
+
+    def __init__(self, nx, ny, pixsize_x, pixsize_y, center_x, center_y, W, do_wgridding, dev):
+        self.W, self.do_wgridding = W, bool(do_wgridding)
+        if self.do_wgridding:
+            nm1 = image_lmn(nx, ny, pixsize_x, pixsize_y, center_x, center_y)[2]
+        else:
+            nm1 = np.zeros((nx, ny))            # without w-gridding nm1 := 0 and n := 1
+        self.max_nm1 = float(np.abs(nm1).max())
+        tu = (np.arange(nx) - nx // 2) / (2.0 * nx)
+        tv = (np.arange(ny) - ny // 2) / (2.0 * ny)
+        cuv = kernel_correction(W, tu)[:, None] * kernel_correction(W, tv)[None, :]
+        self.nm1 = torch.from_numpy(np.ascontiguousarray(nm1)).to(dev) if self.do_wgridding else None
+        self._corr = {(False, False): (1.0 / torch.from_numpy(cuv).to(dev)).contiguous()}
+        self._lock = threading.Lock()
+
+    def corr(self, wkernel, divide_by_n):
+        """1 / (c_u c_v [c_w]) [/ n]: c_w for a plan of more than one plane."""
+        wkernel, by_n = bool(wkernel), bool(divide_by_n) and self.do_wgridding          # without w-gridding n := 1
+        with self._lock:
+            if (True, False) not in self._corr and wkernel:
+                dw = 1.0 / (4.0 * self.max_nm1)            # plane_layout's, whatever the w range
+                cw = _kernel_correction_dev(self.W, dw * self.nm1)
+                self._corr[True, False] = (self._corr[False, False] / cw).contiguous()
+            if (wkernel, by_n) not in self._corr:
+                self._corr[wkernel, True] = (self._corr[wkernel, False] / (1.0 + self.nm1)).contiguous()
+            return self._corr[wkernel, by_n]
+
+
+_tables = PlanCache(8)
+
+
+def tables_for(nx, ny, pixsize_x, pixsize_y, center_x, center_y, W, do_wgridding, dev):
+    """The cached GeomTables of a geometry; cache_stats['tables'] counts the constructions."""
+    key = (int(nx), int(ny), float(pixsize_x), float(pixsize_y), float(center_x), float(center_y), int(W),
+           bool(do_wgridding), str(dev))
+
+    def make():
+        cache_stats['tables'] += 1
+        return GeomTables(int(nx), int(ny), pixsize_x, pixsize_y, center_x, center_y, int(W), do_wgridding, dev)
+    return _tables.get(key, make)
+
+
 class WgridPlan(NativePlan):
     """One (uvw, freq, mask) set on one image geometry: the native geometry record, the sorted order (idx, coord, the
-    planes' slot ranges), nm1 and the correction tables, and the per-call buffers (one grid, val / acc, the complex
-    image).  Use through vis2dirty / dirty2vis / hessian, which hold `lock`."""
+    planes' slot ranges), nm1 and the correction tables (the geometry's GeomTables), and the per-call buffers (one grid,
+    val / acc, the complex image).  Use through vis2dirty / dirty2vis / hessian, which hold `lock`.  `degrid_only`: a
+    block plan of the predict step, which holds the grid and one slot vector and has dirty2vis_into only."""
     _destroy = 'pfb_wgrid_plan_destroy'
 
-    def __init__(self, uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, rdtype):
+    def __init__(self, uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, rdtype,
+                 degrid_only=False):
         super().__init__()
         dev = _dev.require_device()
         nx, ny = int(nx), int(ny)
@@ -121,10 +176,8 @@ class WgridPlan(NativePlan):
         self.nrow, self.nchan = int(self.uvw.shape[0]), int(self.freq.shape[0])
         self.nvis = self.nrow * self.nchan
         self.mask = None if mask is None else _dev.byte_mask(mask, (self.nrow, self.nchan))
-        if self.do_wgridding:
-            nm1 = image_lmn(nx, ny, pixsize_x, pixsize_y, center_x, center_y)[2]
-        else:
-            nm1 = np.zeros((nx, ny))            # without w-gridding nm1 := 0 and n := 1
+        self.tables = tables_for(nx, ny, pixsize_x, pixsize_y, center_x, center_y, W, self.do_wgridding, dev)
+        self.nm1 = self.tables.nm1
         # ---- the w range of the unmasked visibilities -> planes
         self.nsorted = 0
         w = self.uvw[:, 2:3] * self.freq[None, :] / C_LIGHT
@@ -136,16 +189,8 @@ class WgridPlan(NativePlan):
         del w
         if not (math.isfinite(wmin) and math.isfinite(wmax)):
             raise ValueError("uvw / freq hold a non-finite value")
-        self.nplanes, self.w0, self.dw = plane_layout(wmin, wmax, float(np.abs(nm1).max()), W, self.epsilon,
+        self.nplanes, self.w0, self.dw = plane_layout(wmin, wmax, self.tables.max_nm1, W, self.epsilon,
                                                       self.do_wgridding)
-        tu = (np.arange(nx) - nx // 2) / (2.0 * nx)
-        tv = (np.arange(ny) - ny // 2) / (2.0 * ny)
-        cuv = kernel_correction(W, tu)[:, None] * kernel_correction(W, tv)[None, :]
-        self.nm1 = torch.from_numpy(np.ascontiguousarray(nm1)).to(dev) if self.do_wgridding else None
-        self._corr1 = 1.0 / torch.from_numpy(cuv).to(dev)
-        if self.nplanes > 1:
-            self._corr1 /= _kernel_correction_dev(W, self.dw * self.nm1)
-        self._corr = {}
         _lib.check(self._lib.pfb_wgrid_plan_create(_dev.code(rdtype), nx, ny, float(pixsize_x), float(pixsize_y),
                                                    float(center_x), float(center_y), W, self.nplanes, self.w0, self.dw,
                                                    C.byref(self._h)))
@@ -154,8 +199,8 @@ class WgridPlan(NativePlan):
         self.nkeys, self.np0, self.tile = nkeys.value, np0.value, tile.value
         self._build_order(dev)
         self._grid = torch.empty((2 * nx, 2 * ny), dtype=self.cdtype, device=dev)
-        self._slots = torch.empty((2, self.nsorted), dtype=self.cdtype, device=dev)
-        self._img = torch.empty((nx, ny), dtype=self.cdtype, device=dev)
+        self._slots = torch.empty((1 if degrid_only else 2, self.nsorted), dtype=self.cdtype, device=dev)
+        self._img = None if degrid_only else torch.empty((nx, ny), dtype=self.cdtype, device=dev)
 
     def _build_order(self, dev):
         """Counting sort by (first plane, uv tile): histogram kernel, torch.cumsum, placement kernel.  One number -- the
@@ -176,11 +221,8 @@ class WgridPlan(NativePlan):
 
     # ------------------------------------------------------------------------------------------------ pieces
     def corr(self, divide_by_n):
-        """1 / (c_u c_v c_w) [/ n] as a device fp64 table."""
-        key = bool(divide_by_n) and self.do_wgridding            # without w-gridding n := 1
-        if key not in self._corr:
-            self._corr[key] = (self._corr1 / (1.0 + self.nm1)).contiguous() if key else self._corr1.contiguous()
-        return self._corr[key]
+        """1 / (c_u c_v c_w) [/ n] as a device fp64 table: with c_w where the plan has more than one plane."""
+        return self.tables.corr(self.nplanes > 1, divide_by_n)
 
     def plane_ranges(self):
         """(plane, s0, s1) of every plane that has slots: first planes p - W + 1 .. p."""
@@ -246,6 +288,30 @@ class WgridPlan(NativePlan):
                      self.nsorted, _dev.ptr(vis), self.nvis)
         return vis
 
+    def dirty2vis_into(self, dirty, out, row0, chan0, accumulate=False, divide_by_n=True):
+        """dirty2vis of this plan's rows and channels -- a block without mask or weights -- landed in the caller's `out`
+        (nrow_out, nchan_out, ncorr) at rows row0 .., channels chan0 .., correlations 0 and ncorr - 1, assigned or (with
+        `accumulate`) added; no other cell of `out` is touched.  `out` is of the plan's complex type, or complex64
+        under an fp64 plan: narrowed in the kernel, cast first and then added."""
+        self._check('dirty', dirty, self.rdtype, (self.nx, self.ny))
+        if self.mask is not None:
+            raise ValueError("a block plan has no mask")
+        if (out.ndim != 3 or not out.is_contiguous() or out.dtype not in (self.cdtype, torch.complex64)
+                or not 1 <= out.shape[2] <= 4):
+            raise ValueError(f"out must be a contiguous (nrow, nchan, 1 .. 4) tensor of {self.cdtype} or complex64: "
+                             f"{out.dtype} {tuple(out.shape)}")
+        row0, chan0 = int(row0), int(chan0)
+        if row0 < 0 or chan0 < 0 or row0 + self.nrow > out.shape[0] or chan0 + self.nchan > out.shape[1]:
+            raise ValueError(f"block rows {row0} .. + {self.nrow}, channels {chan0} .. + {self.nchan} outside out "
+                             f"{tuple(out.shape)}")
+        if self.nsorted == 0:
+            return
+        with self.lock:
+            acc = self._degrid_all(dirty, None, divide_by_n)
+            self.run('pfb_wgrid_finish_block', _dev.ptr(acc), _dev.ptr(self.idx), _dev.ptr(self.coord), self.nsorted,
+                     self.nchan, _dev.ptr(out), _dev.code(_dev.REAL_OF[out.dtype]), row0, int(out.shape[1]), chan0,
+                     int(out.shape[2]), int(bool(accumulate)))
+
     def hessian(self, x, wgt=None, beam=None):
         """beam * vis2dirty(wgt * dirty2vis(beam * x)), divide_by_n=False both ways (hessian.py:62-106): the
         visibilities stay in sorted slots between the two halves and the beam rides in the image-side kernels."""
@@ -263,7 +329,8 @@ class WgridPlan(NativePlan):
 
 # ------------------------------------------------------------------------------------------------------ plan cache
 _cache = PlanCache(8)
-cache_stats = {'miss': 0}           # plans built (each builds one order): the tests count these
+# plans of the cache built (each builds one order) and GeomTables built: the tests count these
+cache_stats = {'miss': 0, 'tables': 0}
 
 
 def plan_for(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, rdtype):
@@ -283,6 +350,7 @@ def plan_for(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, 
 
 def clear_plan_cache():
     _cache.clear()
+    _tables.clear()
 
 
 # ---------------------------------------------------------------------------------------------------- ducc0's API
@@ -410,3 +478,216 @@ def image_data_products(uvw, freq, vis, wgt, mask, counts, nx, ny, nx_psf, ny_ps
     if model is not None:
         out['RESIDUAL'] = image(plan(nx, ny), residual_vis, wd)
     return {key: _dev.host_like(t, vis) for key, t in out.items()}
+
+
+# ------------------------------------------------------------------------- the predict step: degridding on blocks
+def _degrid_blocks(uvw_d, freq_d, blocks, images, out, cellx, celly, x0, y0, epsilon, do_wgridding, divide_by_n,
+                   accumulate):
+    """images[k] degridded on blocks[k] = (r0, r1, c0, c1) of the device arrays uvw_d, freq_d into out (nrow, nchan,
+    ncorr).
+    A block's plan -- on uvw[r0:r1], freq[c0:c1], no mask -- is not put into the plan cache, so that a predict call
+    evicts nothing that plan_for holds; it takes its tables from the geometry's GeomTables and is closed after use."""
+    for (r0, r1, c0, c1), img in zip(blocks, images):
+        plan = WgridPlan(uvw_d[r0:r1], freq_d[c0:c1], None, img.shape[0], img.shape[1], cellx, celly, x0, y0, epsilon,
+                         do_wgridding, img.dtype, degrid_only=True)
+        try:
+            plan.dirty2vis_into(img, out, r0, c0, accumulate, divide_by_n)
+        finally:
+            plan.close()
+
+
+def _host_ints(a, name):
+    """A bin array as int64 numpy (a device tensor comes to the host: bins are tiny)."""
+    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.ndim != 1 or a.dtype.kind not in 'iu':
+        raise ValueError(f"{name} must be a 1-D integer array, got {a.dtype} {a.shape}")
+    return a.astype(np.int64)
+
+
+def _outside(a, n):
+    """Does the index array hold an entry outside [0, n)?  numpy is looked at on the host, a tensor where it lives."""
+    if len(a) == 0:
+        return False
+    return bool(a.min() < 0) or bool(a.max() >= n)
+
+
+def _host_floats(a):
+    return (a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float64)
+
+
+def _bins(idx, cnts, size, name):
+    """(start, stop) of every bin, idx shifted by its minimum as the reference shifts it; ValueError for a negative
+    count or a bin that reaches outside [0, size)."""
+    idx, cnts = _host_ints(idx, name + '_idx'), _host_ints(cnts, name + '_cnts')
+    if idx.size == 0 or idx.shape != cnts.shape:
+        raise ValueError(f"{name}_idx and {name}_cnts must be non-empty and of one length")
+    if (cnts < 0).any():
+        raise ValueError(f"{name}_cnts holds a negative count")
+    start = idx - idx.min()
+    stop = start + cnts
+    if stop.max() > size:
+        raise ValueError(f"a bin of {name}_idx reaches {int(stop.max())}, beyond the {size} entries it indexes")
+    return start, stop
+
+
+def _im2vis_impl(uvw, freq, image, cellx, celly, freq_bin_idx, freq_bin_counts, x0=0, y0=0, epsilon=1e-7, flip_v=False,
+                 do_wgridding=True, divide_by_n=False, nthreads=1):
+    """pfb/operators/gridder.py:258-294: band i of the (nband, nx, ny) cube degridded into the channels
+    freq_bin_idx[i] - freq_bin_idx.min() .. + freq_bin_counts[i] of a (nrow, nchan) array of result_type(image,
+    complex64); channels that no band covers are zero.  A band's channels are what dirty2vis(uvw, freq[ind], image[i])
+    gives, bit for bit.  flip_v is not implemented (the w-gridder here has no flip); `nthreads` is accepted and
+    ignored."""
+    if flip_v:
+        raise NotImplementedError("flip_v: the w-gridder has no flip")
+    xd = _dev.to_dev(image)
+    if xd.dtype not in _dev.CPLX_OF or xd.ndim != 3:
+        raise TypeError(f"image must be a (nband, nx, ny) float32 or float64 cube, got {xd.dtype} {tuple(xd.shape)}")
+    ud, fd = _dev.uvw_freq(uvw, freq)
+    nrow, nchan = int(ud.shape[0]), int(fd.shape[0])
+    start, stop = _bins(freq_bin_idx, freq_bin_counts, nchan, 'freq_bin')
+    if start.size != xd.shape[0]:
+        raise ValueError(f"{start.size} frequency bins for {xd.shape[0]} bands")
+    check_epsilon(epsilon, xd.dtype)
+    vis = torch.zeros((nrow, nchan, 1), dtype=_dev.CPLX_OF[xd.dtype], device=xd.device)
+    live = [i for i in range(start.size) if stop[i] > start[i] and nrow]
+    _degrid_blocks(ud, fd, [(0, nrow, int(start[i]), int(stop[i])) for i in live], [xd[i] for i in live], vis, cellx,
+                   celly, x0, y0, epsilon, do_wgridding, divide_by_n, False)
+    return _dev.host_like(vis.view(nrow, nchan), image)
+
+
+def _basis_rows(modelf, touts, fouts, nparam):
+    """E (len(touts) * len(fouts), nparam): the factor of parameter p at (tout, fout) is modelf(tout, fout, *e_p) -- one
+    scalar call per unit vector.  modelf must be linear in its parameters: checked once, at the first (tout, fout), on a
+    fixed parameter vector (1.25, -1.625, 2, ..: no entry 0 or 1, where a power of a parameter is the parameter, and a
+    sum other than 1, which a constant term would survive), to 1e-12 relative."""
+    unit = np.eye(nparam)
+    E = np.empty((len(touts), len(fouts), nparam))
+    for i, t in enumerate(touts):
+        for j, f in enumerate(fouts):
+            E[i, j] = [float(modelf(t, f, *unit[p])) for p in range(nparam)]
+    if E.size:
+        probe = np.array([(-1.0) ** p * (1.25 + 0.375 * p) for p in range(nparam)])
+        got, want = float(modelf(touts[0], fouts[0], *probe)), float(E[0, 0] @ probe)
+        if not abs(got - want) <= 1e-12 * np.abs(E[0, 0] * probe).sum():
+            raise ValueError("modelf is not linear in its parameters: the component model cannot be rendered from its "
+                             f"factors (modelf gives {got!r}, the factors {want!r})")
+    return E.reshape(len(touts) * len(fouts), nparam)
+
+
+def _comps2vis_impl(uvw, utime, freq, rbin_idx, rbin_cnts, tbin_idx, tbin_cnts, fbin_idx, fbin_cnts, comps, Ix, Iy,
+                    modelf, tfunc, ffunc, nx, ny, cellx, celly, x0=0, y0=0, epsilon=1e-7, nthreads=1, do_wgridding=True,
+                    divide_by_n=False, ncorr_out=4, *, out=None, accumulate=False, out_dtype=None):
+    """pfb/operators/gridder.py:492-548, the predict step of the degrid worker: the component model (comps (nparam,
+    ncomps) at pixels Ix, Iy; modelf, tfunc, ffunc the callables the worker lambdifies) rendered per time bin and band and
+    degridded into vis (nrow, nchan, ncorr_out), correlations 0 and -1, of result_type(comps, complex64).
+
+    Time bin t takes the unique times indt = tbin_idx[t] .. + tbin_cnts[t] and the rows indr = rbin_idx[indt][0] ..
+    rbin_idx[indt][-1] + rbin_cnts[indt][-1], band b the channels indf = fbin_idx[b] .. + fbin_cnts[b], every index array
+    shifted by its minimum; the image of (t, b) is the model at (tfunc(mean(utime[indt])), ffunc(mean(freq[indf]))).  It
+    is rendered by the component kernel from the factors modelf(tout, fout, *e_p) -- modelf must be linear in its
+    parameters (ValueError otherwise) --, one launch per time bin for all its bands, in the type of comps.
+
+    One deliberate reading of the reference: it hands dirty2vis the WHOLE uvw, not uvw[indr], which runs only where indr
+    covers every row -- one time bin per call, as its worker calls it; two time bins in one call raise a broadcast
+    ValueError there.  Here a block degrids uvw[indr]: the same wherever the reference runs, and a call with several time
+    bins equals the concatenation of the single-bin calls, bit for bit.
+
+    Keyword-only, for the worker's tail: `out` a contiguous (nrow, nchan, ncorr_out) device tensor to write into (zeroed
+    first unless `accumulate`: then the model is ADDED, vis += model column); `out_dtype` complex64 narrows an fp64
+    model in the kernel (the worker's astype(complex64): cast first, then store or add).  A bin outside utime, uvw or
+    freq, a negative count, ncorr_out outside 1 .. 4 and a component outside (nx, ny) are ValueErrors before any launch.
+    Empty bins are skipped.  `nthreads` is accepted and ignored.  numpy in gives numpy out."""
+    nx, ny, ncorr_out = int(nx), int(ny), int(ncorr_out)
+    if not 1 <= ncorr_out <= 4:
+        raise ValueError(f"ncorr_out must be 1 .. 4, got {ncorr_out}")
+    ud, fd = _dev.uvw_freq(uvw, freq)
+    nrow, nchan = int(ud.shape[0]), int(fd.shape[0])
+    ut, fh = _host_floats(utime), _host_floats(freq)
+    t0, t1 = _bins(tbin_idx, tbin_cnts, ut.size, 'tbin')
+    f0, f1 = _bins(fbin_idx, fbin_cnts, nchan, 'fbin')
+    rbin_idx, rbin_cnts = _host_ints(rbin_idx, 'rbin_idx'), _host_ints(rbin_cnts, 'rbin_cnts')
+    if rbin_idx.shape != rbin_cnts.shape or rbin_idx.size < t1.max():
+        raise ValueError(f"a time bin reaches {int(t1.max())}, beyond the {rbin_idx.size} entries of rbin_idx / "
+                         "rbin_cnts")
+    if (rbin_cnts < 0).any():
+        raise ValueError("rbin_cnts holds a negative count")
+    rbin_idx2 = rbin_idx - rbin_idx.min()
+    cd = _dev.to_dev(comps)
+    if cd.dtype not in _dev.CPLX_OF or cd.ndim != 2:
+        raise TypeError(f"comps must be a (nparam, ncomps) float32 or float64 array, got {cd.dtype} {tuple(cd.shape)}")
+    rdt = cd.dtype
+    check_epsilon(epsilon, rdt)
+    if _outside(Ix, nx) or _outside(Iy, ny):
+        raise ValueError(f"Ix / Iy hold a pixel outside the ({nx}, {ny}) image")
+    ixd, iyd = _dev.to_dev(Ix, torch.int64), _dev.to_dev(Iy, torch.int64)
+    # ---- the blocks: rows of every live time bin, channels of every live band
+    tlive = [t for t in range(t0.size) if t1[t] > t0[t]]
+    blive = [b for b in range(f0.size) if f1[b] > f0[b]]
+    rows = []
+    for t in tlive:
+        r0, r1 = int(rbin_idx2[t0[t]]), int(rbin_idx2[t1[t] - 1] + rbin_cnts[t1[t] - 1])
+        if r0 > r1 or r1 > nrow:
+            raise ValueError(f"time bin {t} maps to rows {r0} .. {r1}, outside the {nrow} rows of uvw")
+        rows.append((r0, r1))
+    # ---- the output
+    cdt = _dev.CPLX_OF[rdt]
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous()
+                and tuple(out.shape) == (nrow, nchan, ncorr_out) and out.dtype in _dev.REAL_OF):
+            raise ValueError(f"out must be a contiguous complex device tensor of shape {(nrow, nchan, ncorr_out)}")
+        odt = out.dtype
+        if out_dtype is not None and _cplx_dtype(out_dtype) != odt:
+            raise ValueError(f"out is {odt} but out_dtype asks for {out_dtype}")
+    else:
+        odt = cdt if out_dtype is None else _cplx_dtype(out_dtype)
+    if odt == torch.complex128 and rdt == torch.float32:
+        raise ValueError("a complex128 model column from float32 comps: the kernel narrows, it does not widen")
+    touts = [tfunc(np.mean(ut[t0[t]:t1[t]])) for t in tlive]
+    fouts = [ffunc(np.mean(fh[f0[b]:f1[b]])) for b in blive]
+    E = _basis_rows(modelf, touts, fouts, int(cd.shape[0]))
+    # ---- launches
+    if out is None:
+        vis = torch.zeros((nrow, nchan, ncorr_out), dtype=odt, device=cd.device)
+    else:
+        vis = out if accumulate else out.zero_()
+    nb = len(blive)
+    for k, (r0, r1) in enumerate(rows):
+        if r1 == r0 or nb == 0 or cd.shape[1] == 0:          # nothing to degrid, or a model without components
+            continue
+        images = _render(E[k * nb:(k + 1) * nb], nx, ny, cd, ixd, iyd, rdt)
+        _degrid_blocks(ud, fd, [(r0, r1, int(f0[b]), int(f1[b])) for b in blive], images, vis, cellx, celly, x0, y0,
+                       epsilon, do_wgridding, divide_by_n, accumulate)
+    return vis if out is not None else _dev.host_like(vis, uvw)
+
+
+def _cplx_dtype(dtype):
+    if isinstance(dtype, torch.dtype):
+        t = dtype
+    else:
+        t = _dev._NP2T.get(np.dtype(dtype))
+    if t not in _dev.REAL_OF:
+        raise ValueError(f"out_dtype must be complex64 or complex128, got {dtype}")
+    return t
+
+
+def _loc2psf_vis_impl(uvw, freq, cell, x0=0, y0=0, do_wgridding=True, epsilon=1e-7, nthreads=1, precision='single',
+                      divide_by_n=False, convention='CASA'):
+    """pfb/operators/gridder.py:298-341: the visibilities of a unit source at the phase centre, (nrow, nchan) complex64
+    ('single') or complex128: ones, or for a centre (x0, y0) != 0 the degridded 128 x 128 delta at epsilon 1e-7, the
+    reference's fixed value whatever `epsilon`.  That accuracy is below the fp32 kernels' range, so 'single' degrids in
+    fp64 and narrows in the landing kernel.  `nthreads` and `convention` are accepted and ignored."""
+    ud, fd = _dev.uvw_freq(uvw, freq)
+    nrow, nchan = int(ud.shape[0]), int(fd.shape[0])
+    cdt = torch.complex64 if precision == 'single' else torch.complex128
+    if not (x0 or y0):
+        return _dev.host_like(torch.ones((nrow, nchan), dtype=cdt, device=ud.device), uvw)
+    delta = torch.zeros((128, 128), dtype=torch.float64, device=ud.device)
+    delta[64, 64] = 1.0
+    vis = torch.zeros((nrow, nchan, 1), dtype=cdt, device=ud.device)
+    if nrow and nchan:
+        _degrid_blocks(ud, fd, [(0, nrow, 0, nchan)], [delta], vis, cell, cell, x0, y0, 1e-7, do_wgridding, divide_by_n,
+                       False)
+    return _dev.host_like(vis.view(nrow, nchan), uvw)
+
+
+im2vis, comps2vis, loc2psf_vis = _im2vis_impl, _comps2vis_impl, _loc2psf_vis_impl

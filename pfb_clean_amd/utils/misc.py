@@ -8,6 +8,7 @@ The three pfb/utils/misc.py helpers that sit on the hot path.
     Gaussian2D, get_padding_info, convolve2gaussres   misc.py:109-238 (restoring-beam convolution)
     fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice   misc.py:1084-1313 (component model, utils/comps.py)
     fitcleanbeam                          misc.py:506-584   (clean beam, utils/beamfit.py)
+    restore_corrs                         misc.py:490-503   (a Stokes model column back into the correlations)
 """
 import math
 
@@ -32,6 +33,25 @@ def norm_diff(x, xp):
         raise ValueError("norm_diff: x and xp must have the same shape and dtype")
     num, den = norm_diff_sums(xd, xpd).tolist()
     return math.sqrt(num / (1e-12 + den))
+
+
+def _restore_corrs(vis, ncorr):
+    """misc.py:498-503: (nrow, nchan, ncorr) of the type of vis with vis in correlations 0 and -1 and zeros between, every
+    element written by one launch."""
+    vd = _dev.to_dev(vis)
+    if vd.dtype not in _dev.REAL_OF or vd.ndim != 2:
+        raise TypeError(f"vis must be a (nrow, nchan) complex64 or complex128 array, got {vd.dtype} {tuple(vd.shape)}")
+    ncorr = int(ncorr)
+    if not 1 <= ncorr <= 4:
+        raise ValueError(f"ncorr must be 1 .. 4, got {ncorr}")
+    out = torch.empty(tuple(vd.shape) + (ncorr,), dtype=vd.dtype, device=vd.device)
+    if vd.numel():
+        _lib.check(_lib.load().pfb_vis_restore_corrs(_dev.code(_dev.REAL_OF[vd.dtype]), _dev.ptr(vd), vd.numel(), ncorr,
+                                                     _dev.ptr(out), _dev.stream()))
+    return _dev.host_like(out, vis)
+
+
+restore_corrs = _restore_corrs          # the reference's name is the dask wrapper of the same function
 
 
 def l1reweight_func(psiH, outvar, rmsfactor, rms_comps, model, alpha=4, group=None):
