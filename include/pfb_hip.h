@@ -872,6 +872,39 @@ int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void*
                    const long long* tbin_counts, long long tbin_off, const int* ant1, const int* ant2, size_t nrow,
                    int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum, double* work, void* stream);
 
+/* ------------------------------------------------ band / time concatenation and beam resampling
+ * The grid worker's merge of its input datasets (pfb/workers/grid.py:150-214, 404-412): sum_overlap and _sum_beam of
+ * pfb/utils/misc.py:1009-1067 and _eval_beam of pfb/utils/beam.py:120-140.  Asynchronous on `stream`, no atomics: the
+ * same bits from run to run.  Arrays of pointers (vis, wgt, mask, beams) and nrows, nchans are HOST arrays of nds
+ * entries, read before the call returns; what they point to is device memory. */
+/* Sources travel to a kernel by value, this many per launch; a later launch accumulates onto the first one's partial
+ * sums (of the data's type: the round trip is exact), the last one closes. */
+#define PFB_VIS_BATCH 8
+/* Source i: vis complex, wgt real, mask bytes, each (nrows[i], nchans[i]).  chan_map: DEVICE int (nds, nchan_out), the
+ * channel of source i that lands in output channel c or -1 (an entry outside [0, nchans[i]) is read as -1).
+ *   viso = sum_i vis wgt mask, wgto = sum_i wgt mask, masko = 1 where any source mask != 0 else 0, summed in source
+ *   order in `dtype`, every operation rounded on its own; viso /= wgto where masko (a plain IEEE division: weights that
+ *   sum to zero on an unflagged sample give inf / nan, as in the reference); where masko == 0 all three are exactly 0.
+ * All (nrow, nchan_out).  PFB_ERR_INVALID: a null array, a source whose nrows[i] != nrow. */
+int pfb_vis_sum_overlap(int dtype, int nds, const void* const* vis, const void* const* wgt,
+                        const unsigned char* const* mask, const size_t* nrows, const int* nchans, const int* chan_map,
+                        size_t nrow, int nchan_out, void* viso, void* wgto, unsigned char* masko, void* stream);
+/* rec[0] = the sum of ALL n elements of wgt (no mask, as _sum_beam has it), in fp64 (work: PFB_IMW_WORK_DOUBLES doubles
+ * of scratch; a fixed order). */
+int pfb_vis_weight_sums(int dtype, const void* wgt, size_t n, double* rec, double* work, void* stream);
+/* out = sum_i wsum[i] beams[i], divided by sum_i wsum[i] where that is not zero; wsum: the DEVICE record of nds doubles
+ * that pfb_vis_weight_sums filled, each rounded to `dtype`; summed in source order in `dtype`.  npix pixels each. */
+int pfb_beam_combine(int dtype, int nds, const void* const* beams, const double* wsum, size_t npix, void* out,
+                     void* stream);
+/* Bilinear interpolation of beam (nl, nm) of `dtype`, given on the ascending axes l_in (nl), m_in (nm), at (nxo, nyo)
+ * points: coord2d == 0: (l_out[i], m_out[j]) of l_out (nxo), m_out (nyo); else l_out, m_out are (nxo, nyo).  The cell
+ * of x is the i of g[i] <= x < g[i + 1] clipped to [0, n - 2] (binary search: any spacing), the distance
+ * (x - g[i]) / (g[i + 1] - g[i]): points outside are linearly extrapolated from the edge cell, a NaN gives NaN.
+ * Coordinates and weights are fp64; out is of `out_dtype`, rounded at the store.  nl, nm >= 2. */
+int pfb_beam_eval(int dtype, const void* beam, int nl, int nm, const double* l_in, const double* m_in,
+                  const double* l_out, const double* m_out, int coord2d, int nxo, int nyo, int out_dtype, void* out,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

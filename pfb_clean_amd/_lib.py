@@ -154,6 +154,11 @@ SIGNATURES = {
     # Stokes visibilities and weights from correlations and Jones terms (weighting.py:281-350, stokes2im.py:98-195)
     'pfb_stokes_vis': (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, C.c_longlong,
                             _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # band / time concatenation and beam resampling (misc.py:1009-1067, beam.py:120-140)
+    'pfb_vis_sum_overlap': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
+    'pfb_vis_weight_sums': (_i, [_i, _vp, _sz, _vp, _vp, _vp]),
+    'pfb_beam_combine': (_i, [_i, _i, _vp, _vp, _sz, _vp, _vp]),
+    'pfb_beam_eval': (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

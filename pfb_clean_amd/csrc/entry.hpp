@@ -1,8 +1,8 @@
-// entry.hpp -- the host side of a C entry point of the visibility-side files (wgrid.hip, imweight.hip, stokes.hip;
-// DESIGN 4.10, "The entry layer").  An entry point reads top to bottom: check() on its type code and pointers, its size
-// checks, its memset, then one launch from a by_type (and by_int) lambda; a sum ends in final_sum.  A new one needs
-// nothing else.  cgvec.hip, wavelet.hip and hessparam.hip take final_sum from here.  Templates and inline functions only,
-// no state.
+// entry.hpp -- the host side of a C entry point of the visibility-side files (wgrid.hip, imweight.hip, stokes.hip,
+// visconcat.hip; DESIGN 4.10, "The entry layer").  An entry point reads top to bottom: check() on its type code and
+// pointers, its size checks, its memset, then one launch from a by_type (and by_int) lambda; a sum ends in final_sum.
+// A new one needs nothing else.  cgvec.hip, wavelet.hip and hessparam.hip take final_sum from here.  Templates and
+// inline functions only, no state.
 #pragma once
 #include "common.hpp"
 #include <type_traits>

@@ -9,6 +9,7 @@ The three pfb/utils/misc.py helpers that sit on the hot path.
     fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice   misc.py:1084-1313 (component model, utils/comps.py)
     fitcleanbeam                          misc.py:506-584   (clean beam, utils/beamfit.py)
     restore_corrs                         misc.py:490-503   (a Stokes model column back into the correlations)
+    concat_row, concat_chan, sum_overlap, sum_beam, _sum_beam   misc.py:776-1067 (the grid worker's merge, utils/concat.py)
 """
 import math
 
@@ -21,6 +22,7 @@ from .._plan import PlanCache, array_key
 from ..operators.psf import PsfConvPlan
 from .comps import fit_image_cube, eval_coeffs_to_cube, eval_coeffs_to_slice  # noqa: F401
 from .beamfit import fitcleanbeam  # noqa: F401
+from .concat import VisDataset, concat_row, concat_chan, sum_overlap, sum_beam, _sum_beam  # noqa: F401
 
 
 def norm_diff(x, xp):
