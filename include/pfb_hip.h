@@ -780,6 +780,33 @@ int pfb_wgrid_image_adjoint(void* plan, int plane, const void* grid, const doubl
 /* dirty = Re(img) corr [beam]. */
 int pfb_wgrid_image_correct(void* plan, const void* img, const double* corr, const void* beam, void* dirty, void* stream);
 
+/* The same operators with a product axis ("Several products under one order"): nprod = 1 .. 4 planes --
+ * the Stokes products of one chunk -- share the plan and its order, and every array that holds values gains a leading
+ * axis, product-major and contiguous:
+ *   vis, wgt (nprod, nvis);  val / acc (nprod, nsorted);  grid (nprod, 2 nx, 2 ny);  img, dirty (nprod, nx, ny).
+ * idx, coord, corr, nm1 and beam stay single: they do not depend on the product.  wgt is NULL for 1, one (nvis) plane
+ * for every product with wgt_shared != 0, else (nprod, nvis).  Per plane each function computes what its single form
+ * computes; what does not depend on the values -- a slot's centre phase, a footprint's cells and kernel values, a
+ * pixel's w phase, correction and beam -- is formed once and applied to all planes.  The caller transforms the grids
+ * between the calls as before (torch.fft batches over the leading axis).  nprod == 1 is the single form.
+ * PFB_ERR_INVALID: nprod outside 1 .. 4 (before anything else; nothing is written), and what the single forms refuse.
+ * pfb_wgrid_prep_multi takes nvis, the plane stride of vis and wgt: nsorted <= nvis < 2^31. */
+int pfb_wgrid_prep_multi(void* plan, int nprod, const void* vis, const void* wgt, int wgt_shared, const int* idx,
+                         const double* coord, size_t nsorted, size_t nvis, void* val, void* stream);
+int pfb_wgrid_finish_multi(void* plan, int nprod, const void* acc, const void* wgt, int wgt_shared, const int* idx,
+                           const double* coord, size_t nsorted, void* vis, size_t nvis, void* stream);
+/* every grid = 0, then the slots [s0, s1) of every plane of val are added to `plane` of its grid. */
+int pfb_wgrid_grid_multi(void* plan, int nprod, int plane, const void* val, const double* coord, size_t nsorted,
+                         size_t s0, size_t s1, void* grid, void* stream);
+int pfb_wgrid_degrid_multi(void* plan, int nprod, int plane, const void* grid, const double* coord, size_t nsorted,
+                           size_t s0, size_t s1, void* acc, void* stream);
+int pfb_wgrid_image_forward_multi(void* plan, int nprod, int plane, const void* dirty, const void* beam,
+                                  const double* corr, const double* nm1, void* grid, void* stream);
+int pfb_wgrid_image_adjoint_multi(void* plan, int nprod, int plane, const void* grid, const double* nm1, void* img,
+                                  void* stream);
+int pfb_wgrid_image_correct_multi(void* plan, int nprod, const void* img, const double* corr, const void* beam,
+                                  void* dirty, void* stream);
+
 /* --------------------------------------------------------------------- imaging weights
  * pfb/utils/weighting.py:43-171 (_compute_counts, _counts_to_weights) and the l2reweight_dof block of
  * pfb/operators/gridder.py:604-615.  No plan: every function is one asynchronous launch (behind a clear
@@ -871,6 +898,18 @@ int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void*
                    const void* jones, int ndir, int ntime, int nant, const long long* tbin_idx,
                    const long long* tbin_counts, long long tbin_off, const int* ant1, const int* ant2, size_t nrow,
                    int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum, double* work, void* stream);
+/* pfb_stokes_vis for nprod = 1 .. 4 products in ONE pass: `basis` is a HOST array of nprod distinct basis indices (0 .. 3,
+ * read before the call returns), in the order of the output planes.  The correlations, weights, flags and Jones terms of
+ * a visibility are read once.  Out: vis complex and wgt real (nprod, nrow, nchan), product-major; mask (nrow, nchan), the
+ * same for every product; wsum[k], k < nprod, the fp64 sum of plane k's wgt over unflagged visibilities.  Everything
+ * else as pfb_stokes_vis, per plane.  PFB_ERR_INVALID: nprod outside 1 .. 4, a NULL basis list, a basis outside 0 .. 3
+ * or asked for twice, and what pfb_stokes_vis refuses; nothing is written. */
+int pfb_stokes_vis_multi(int dtype, int mode, int nprod, const int* basis, const void* data, const void* data2,
+                         int subtract, const void* weight, int wform, const unsigned char* flag, int nflagcorr,
+                         const unsigned char* frow, int autocorr, const void* jones, int ndir, int ntime, int nant,
+                         const long long* tbin_idx, const long long* tbin_counts, long long tbin_off, const int* ant1,
+                         const int* ant2, size_t nrow, int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum,
+                         double* work, void* stream);
 
 /* ------------------------------------------------ band / time concatenation and beam resampling
  * The grid worker's merge of its input datasets (pfb/workers/grid.py:150-214, 404-412): sum_overlap and _sum_beam of

@@ -154,6 +154,17 @@ SIGNATURES = {
     # Stokes visibilities and weights from correlations and Jones terms (weighting.py:281-350, stokes2im.py:98-195)
     'pfb_stokes_vis': (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, C.c_longlong,
                             _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # ... for up to four products in one pass (nprod and a host array of basis indices in the place of basis)
+    'pfb_stokes_vis_multi': (_i, [_i, _i, _i, C.POINTER(_i), _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp,
+                                  _vp, C.c_longlong, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the w-gridder with a product axis: nprod after the plan, (wgt, wgt_shared) for wgt, nvis for prep
+    'pfb_wgrid_prep_multi': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _sz, _vp, _vp]),
+    'pfb_wgrid_finish_multi': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'pfb_wgrid_grid_multi': (_i, [_vp, _i, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    'pfb_wgrid_degrid_multi': (_i, [_vp, _i, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    'pfb_wgrid_image_forward_multi': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pfb_wgrid_image_adjoint_multi': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'pfb_wgrid_image_correct_multi': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     # band / time concatenation and beam resampling (misc.py:1009-1067, beam.py:120-140)
     'pfb_vis_sum_overlap': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
     'pfb_vis_weight_sums': (_i, [_i, _vp, _sz, _vp, _vp, _vp]),

@@ -8,6 +8,8 @@
 //              the pass: data +- data2, the weight forms (ones, 1 / sigma^2, a spectrum, a row weight), the flag
 //              any(flag[row, chan, :]) | frow[row] | ant1[row] == ant2[row], mask = !flag as bytes, and the fp64 sum of
 //              the unflagged wgt (a partial per workgroup, then k_final_sum of common.hpp: the same bits every run).
+//   k_stokes_multi   the same pass for up to four products at once: every input of a visibility is read once, product k
+//              lands in plane k of vis and wgt (nprod, nrow, nchan); what the bases share is formed once
 // Templated on the type, the Jones mode (diagonal with 4 or 2 correlations, full 2 x 2 with 4, none with 4 or 2) and the
 // basis; the weight form, the flags and the second column are uniform branches.
 //
@@ -232,6 +234,226 @@ k_stokes(StkArgs a) {
     emit_partials<1>(acc, a.ws);
 }
 
+// --------------------------------------------------------------------------------- several products in one pass
+// Up to four products of one chunk: the correlations, weights, flags and Jones terms of a visibility are read once, and
+// product k lands in plane k of vis and wgt, (nprod, nrow, nchan); the mask does not depend on the product.
+constexpr int STK_MAX_PROD = 4;
+// four partials per workgroup in the reduction scratch
+constexpr int STK_MULTI_MAX_GROUPS = 2048;
+static_assert(STK_MAX_PROD * STK_MULTI_MAX_GROUPS <= PFB_REDUCE_WS_DOUBLES, "four fp64 partials per workgroup");
+
+struct StkMultiArgs {
+    StkArgs s;                         // vis, wgt: plane 0
+    int nprod;
+    int basis[STK_MAX_PROD];           // of plane k < nprod
+    int plane[4];                      // of basis b, or -1
+};
+
+// what stk_eval<T, MODE, B> gives for the two bases of a family -- (0, 1), or (2, 3) with OFFDIAG -- with everything
+// they share formed once: the two entries of X, the divisors, the products of the Jones terms.  m, dpq: the FULL mode's
+// adj(Gp) V and det Gp conj(det Gq), the same for both families
+template <typename T, int MODE, bool OFFDIAG>
+__device__ __forceinline__ void stk_eval_family(const cplx<T>* v, const T* w, const cplx<T>* gp, const cplx<T>* gq,
+                                                const cplx<T>* m, cplx<T> dpq, cplx<T>& vis_sum, cplx<T>& vis_dif,
+                                                T& wgt_sum, T& wgt_dif) {
+    constexpr int NC = stk_ncorr(MODE);
+    constexpr int BS = OFFDIAG ? 2 : 0, BD = OFFDIAG ? 3 : 1;
+    cplx<T> va, vb;
+    T wa, wb;
+    if constexpr (NC == 4) {
+        va = v[OFFDIAG ? 1 : 0]; vb = v[OFFDIAG ? 2 : 3];
+        wa = w[OFFDIAG ? 1 : 0]; wb = w[OFFDIAG ? 2 : 3];
+    } else if constexpr (OFFDIAG) {
+        va = vb = cplx<T>(T(0), T(0));
+        wa = wb = T(1);
+    } else {
+        va = v[0]; vb = v[1];
+        wa = w[0]; wb = w[1];
+    }
+    if constexpr (!stk_has_jones(MODE)) {
+        vis_sum = stk_trace<BS>(va, vb);
+        vis_dif = stk_trace<BD>(va, vb);
+        wgt_sum = wgt_dif = wa + wb;
+    } else if constexpr (MODE != PFB_STOKES_FULL4) {
+        const cplx<T> da = mulc(gp[0], gq[OFFDIAG ? 1 : 0]), db = mulc(gp[1], gq[OFFDIAG ? 0 : 1]);
+        const cplx<T> xa = stk_div(va, da), xb = stk_div(vb, db);
+        vis_sum = stk_trace<BS>(xa, xb);
+        vis_dif = stk_trace<BD>(xa, xb);
+        wgt_sum = wgt_dif = wa * stk_abs2(da) + wb * stk_abs2(db);
+    } else {
+        cplx<T> xa, xb;
+        if constexpr (!OFFDIAG) {
+            xa = mulc(m[0], gq[3]) - mulc(m[1], gq[1]);
+            xb = mulc(m[3], gq[0]) - mulc(m[2], gq[2]);
+        } else {
+            xa = mulc(m[1], gq[0]) - mulc(m[0], gq[2]);
+            xb = mulc(m[2], gq[3]) - mulc(m[3], gq[1]);
+        }
+        vis_sum = stk_div(stk_trace<BS>(xa, xb), dpq);
+        vis_dif = stk_div(stk_trace<BD>(xa, xb), dpq);
+        wgt_sum = wgt_dif = T(0);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const cplx<T> e0 = mulc(gp[2 * a], gq[2 * b + (OFFDIAG ? 1 : 0)]);
+                const cplx<T> e1 = mulc(gp[2 * a + 1], gq[2 * b + (OFFDIAG ? 0 : 1)]);
+                wgt_sum += w[2 * a + b] * stk_abs2(e0 + e1);
+                wgt_dif += w[2 * a + b] * stk_abs2(e0 - e1);
+            }
+        }
+    }
+}
+
+template <typename T, int MODE>
+__global__ void __launch_bounds__(STK_BLOCK)
+k_stokes_multi(StkMultiArgs ma) {
+    constexpr int NC = stk_ncorr(MODE), NJ = stk_njones(MODE);
+    __shared__ int s_bin[STK_BLOCK], s_p[STK_BLOCK], s_q[STK_BLOCK];
+    const StkArgs& a = ma.s;
+    const cplx<T>* __restrict__ data = static_cast<const cplx<T>*>(a.data);
+    const cplx<T>* __restrict__ data2 = static_cast<const cplx<T>*>(a.data2);
+    const T* __restrict__ weight = static_cast<const T*>(a.weight);
+    const cplx<T>* __restrict__ jones = static_cast<const cplx<T>*>(a.jones);
+    cplx<T>* __restrict__ vis = static_cast<cplx<T>*>(a.vis);
+    T* __restrict__ wgt = static_cast<T*>(a.wgt);
+    const unsigned nchan = (unsigned)a.nchan;
+    const size_t nvis = a.nrow * (size_t)nchan;                 // a plane
+    const bool fam0 = ma.plane[0] >= 0 || ma.plane[1] >= 0, fam1 = ma.plane[2] >= 0 || ma.plane[3] >= 0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};                       // by basis
+    for (size_t g = blockIdx.x; g < a.ngroups; g += gridDim.x) {
+        const size_t r0 = g * (size_t)a.rows_per_group;
+        const unsigned nr = (unsigned)(a.nrow - r0 < (size_t)a.rows_per_group ? a.nrow - r0 : (size_t)a.rows_per_group);
+        __syncthreads();                                        // the readers of the group before
+        if (threadIdx.x < nr) {
+            const size_t r = r0 + threadIdx.x;
+            const long long row = (long long)r;
+            int lo = 0, hi = a.ntime;
+            while (hi - lo > 1) {
+                const int mid = lo + (hi - lo) / 2;
+                if (a.tbin_idx[mid] - a.tbin_off <= row) lo = mid; else hi = mid;
+            }
+            const int p = a.ant1[r], q = a.ant2[r];
+            const bool covered = row - (a.tbin_idx[lo] - a.tbin_off) < a.tbin_counts[lo] &&
+                                 p >= 0 && p < a.nant && q >= 0 && q < a.nant;
+            bool frow = a.autocorr && p == q;
+            if (a.frow) frow = frow || a.frow[r] != 0;
+            s_bin[threadIdx.x] = frow ? -2 : covered ? lo : -1;
+            s_p[threadIdx.x] = p;
+            s_q[threadIdx.x] = q;
+        }
+        __syncthreads();
+        const unsigned n = nr * nchan;                          // <= STK_BLOCK, or one row
+        for (unsigned i = threadIdx.x; i < n; i += STK_BLOCK) {
+            const unsigned lr = a.rows_per_group == 1 ? 0u : i / nchan;
+            const unsigned chan = i - lr * nchan;
+            const size_t r = r0 + lr;
+            const size_t t = r * nchan + chan;
+            const int bin = s_bin[lr];
+            bool flagged = bin == -2;
+            if (a.nflagcorr == 1) {
+                flagged = flagged || __builtin_nontemporal_load(a.flag + t) != 0;
+            } else if (a.nflagcorr) {
+                unsigned f = 0;
+                stk_load<NC, true>(a.flag + t * NC, &f);
+                flagged = flagged || f != 0;
+            }
+            const bool live = !flagged && bin >= 0;
+            cplx<T> v[NC];
+            stk_load<NC * (int)sizeof(cplx<T>), true>(data + t * NC, v);
+            if (data2) {
+                cplx<T> d[NC];
+                stk_load<NC * (int)sizeof(cplx<T>), true>(data2 + t * NC, d);
+#pragma unroll
+                for (int c = 0; c < NC; ++c) v[c] = a.subtract ? v[c] - d[c] : v[c] + d[c];
+            }
+            T w[NC];
+            if (a.wform == PFB_STOKES_W_NONE) {
+#pragma unroll
+                for (int c = 0; c < NC; ++c) w[c] = T(1);
+            } else if (a.wform == PFB_STOKES_W_ROW) {
+                stk_load<NC * (int)sizeof(T), false>(weight + r * NC, w);
+            } else {
+                stk_load<NC * (int)sizeof(T), true>(weight + t * NC, w);
+                if (a.wform == PFB_STOKES_W_SIGMA) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) w[c] = T(1) / (w[c] * w[c]);
+                }
+            }
+            cplx<T> gp[NJ], gq[NJ];
+            if constexpr (stk_has_jones(MODE)) {
+                const size_t tb = live ? (size_t)bin : 0, p = live ? (size_t)s_p[lr] : 0, q = live ? (size_t)s_q[lr] : 0;
+                const size_t step = (size_t)a.ndir * NJ;
+                stk_load<NJ * (int)sizeof(cplx<T>), false>(jones + ((tb * a.nant + p) * nchan + chan) * step, gp);
+                stk_load<NJ * (int)sizeof(cplx<T>), false>(jones + ((tb * a.nant + q) * nchan + chan) * step, gq);
+            }
+            cplx<T> m[4], dpq;
+            if constexpr (MODE == PFB_STOKES_FULL4) {
+                m[0] = gp[3] * v[0] - gp[1] * v[2]; m[1] = gp[3] * v[1] - gp[1] * v[3];
+                m[2] = gp[0] * v[2] - gp[2] * v[0]; m[3] = gp[0] * v[3] - gp[2] * v[1];
+                dpq = mulc(gp[0] * gp[3] - gp[1] * gp[2], gq[0] * gq[3] - gq[1] * gq[2]);
+            }
+            cplx<T> ov[4];
+            T ow[4];
+            if (fam0) stk_eval_family<T, MODE, false>(v, w, gp, gq, m, dpq, ov[0], ov[1], ow[0], ow[1]);
+            if (fam1) stk_eval_family<T, MODE, true>(v, w, gp, gq, m, dpq, ov[2], ov[3], ow[2], ow[3]);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int k = ma.plane[b];
+                if (k < 0) continue;
+                const size_t o = (size_t)k * nvis + t;
+                vis[o] = live ? ov[b] : cplx<T>(T(0), T(0));
+                wgt[o] = live ? ow[b] : T(0);
+                acc[b] += live ? (double)ow[b] : 0.0;
+            }
+            a.mask[t] = flagged ? 0 : 1;
+        }
+    }
+    // the partials in the order of the planes
+    double part[STK_MAX_PROD];
+#pragma unroll
+    for (int k = 0; k < STK_MAX_PROD; ++k) {
+        const int b = ma.basis[k];
+        part[k] = k >= ma.nprod ? 0.0 : b == 0 ? acc[0] : b == 1 ? acc[1] : b == 2 ? acc[2] : acc[3];
+    }
+    emit_partials<STK_MAX_PROD>(part, a.ws);
+}
+
+// the checks and the kernel record that both entry points share; vis, wgt: plane 0 of the outputs
+static int stk_setup(const char* name, int dtype, int mode, const void* data, const void* data2, int subtract,
+                     const void* weight, int wform, const unsigned char* flag, int nflagcorr, const unsigned char* frow,
+                     int autocorr, const void* jones, int ndir, int ntime, int nant, const long long* tbin_idx,
+                     const long long* tbin_counts, long long tbin_off, const int* ant1, const int* ant2, size_t nrow,
+                     int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum, double* work, StkArgs& a) {
+    PFB_REQUIRE(mode >= PFB_STOKES_DIAG4 && mode <= PFB_STOKES_NOJ2, PFB_ERR_INVALID, "%s: bad Jones mode %d", name, mode);
+    PFB_REQUIRE(wform >= PFB_STOKES_W_NONE && wform <= PFB_STOKES_W_ROW, PFB_ERR_INVALID, "%s: bad weight form %d", name, wform);
+    const size_t e = esize(dtype), nc = (size_t)stk_ncorr(mode), nj = (size_t)stk_njones(mode);
+    // what one vector load reads: a visibility's correlations, its weights, an antenna's Jones terms; 16 bytes at most
+    const auto vload = [](size_t n) { return bytes(n < 16 ? n : 16); };
+    PFB_REQUIRE(nflagcorr == 0 || nflagcorr == 1 || nflagcorr == (int)nc, PFB_ERR_INVALID,
+                "%s: %d flags per visibility of %zu correlations", name, nflagcorr, nc);
+    if (int rc = check(dtype, name,
+                       {{data, vload(2 * e * nc)}, {data2, vload(2 * e * nc), true},
+                        {weight, vload(e * nc), wform == PFB_STOKES_W_NONE},
+                        {flag, bytes(nflagcorr > 1 ? nc : 1), nflagcorr == 0}, {frow, U8, true},
+                        {jones, vload(2 * e * nj), !stk_has_jones(mode)}, {tbin_idx, I64}, {tbin_counts, I64},
+                        {ant1, I32}, {ant2, I32}, {vis, CPLX}, {wgt, REAL}, {mask, U8}, {wsum, F64}, {work, F64}});
+        rc != PFB_OK) return rc;
+    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED,
+                "%s: %zu rows x %d channels outside [1, 2^31) each", name, nrow, nchan);
+    PFB_REQUIRE(ntime >= 1 && nant >= 1 && ndir >= 1, PFB_ERR_INVALID, "%s: ntime %d, nant %d, ndir %d must be positive",
+                name, ntime, nant, ndir);
+    a.data = data; a.data2 = data2; a.weight = weight; a.jones = jones; a.flag = flag; a.frow = frow;
+    a.ant1 = ant1; a.ant2 = ant2; a.tbin_idx = tbin_idx; a.tbin_counts = tbin_counts; a.tbin_off = tbin_off;
+    a.nrow = nrow; a.nchan = nchan;
+    a.rows_per_group = nchan >= STK_BLOCK ? 1 : STK_BLOCK / nchan;
+    a.ngroups = (nrow + (size_t)a.rows_per_group - 1) / (size_t)a.rows_per_group;
+    a.ntime = ntime; a.nant = nant; a.ndir = ndir; a.wform = wform; a.nflagcorr = nflagcorr; a.autocorr = autocorr != 0;
+    a.subtract = subtract != 0;
+    a.vis = vis; a.wgt = wgt; a.mask = mask; a.ws = work;
+    return PFB_OK;
+}
+
 }  // namespace pfb
 
 using namespace pfb;
@@ -245,32 +467,11 @@ int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void*
                    int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum, double* work, void* stream) {
     PFB_REQUIRE(mode >= PFB_STOKES_DIAG4 && mode <= PFB_STOKES_NOJ2, PFB_ERR_INVALID, "stokes_vis: bad Jones mode %d", mode);
     PFB_REQUIRE(basis >= 0 && basis <= 3, PFB_ERR_INVALID, "stokes_vis: bad basis %d", basis);
-    PFB_REQUIRE(wform >= PFB_STOKES_W_NONE && wform <= PFB_STOKES_W_ROW, PFB_ERR_INVALID, "stokes_vis: bad weight form %d", wform);
-    const size_t e = esize(dtype), nc = (size_t)stk_ncorr(mode), nj = (size_t)stk_njones(mode);
-    // what one vector load reads: a visibility's correlations, its weights, an antenna's Jones terms; 16 bytes at most
-    const auto vload = [](size_t n) { return bytes(n < 16 ? n : 16); };
-    PFB_REQUIRE(nflagcorr == 0 || nflagcorr == 1 || nflagcorr == (int)nc, PFB_ERR_INVALID,
-                "stokes_vis: %d flags per visibility of %zu correlations", nflagcorr, nc);
-    if (int rc = check(dtype, "stokes_vis",
-                       {{data, vload(2 * e * nc)}, {data2, vload(2 * e * nc), true},
-                        {weight, vload(e * nc), wform == PFB_STOKES_W_NONE},
-                        {flag, bytes(nflagcorr > 1 ? nc : 1), nflagcorr == 0}, {frow, U8, true},
-                        {jones, vload(2 * e * nj), !stk_has_jones(mode)}, {tbin_idx, I64}, {tbin_counts, I64},
-                        {ant1, I32}, {ant2, I32}, {vis, CPLX}, {wgt, REAL}, {mask, U8}, {wsum, F64}, {work, F64}});
-        rc != PFB_OK) return rc;
-    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED,
-                "stokes_vis: %zu rows x %d channels outside [1, 2^31) each", nrow, nchan);
-    PFB_REQUIRE(ntime >= 1 && nant >= 1 && ndir >= 1, PFB_ERR_INVALID, "stokes_vis: ntime %d, nant %d, ndir %d must be positive",
-                ntime, nant, ndir);
     StkArgs a;
-    a.data = data; a.data2 = data2; a.weight = weight; a.jones = jones; a.flag = flag; a.frow = frow;
-    a.ant1 = ant1; a.ant2 = ant2; a.tbin_idx = tbin_idx; a.tbin_counts = tbin_counts; a.tbin_off = tbin_off;
-    a.nrow = nrow; a.nchan = nchan;
-    a.rows_per_group = nchan >= STK_BLOCK ? 1 : STK_BLOCK / nchan;
-    a.ngroups = (nrow + (size_t)a.rows_per_group - 1) / (size_t)a.rows_per_group;
-    a.ntime = ntime; a.nant = nant; a.ndir = ndir; a.wform = wform; a.nflagcorr = nflagcorr; a.autocorr = autocorr != 0;
-    a.subtract = subtract != 0;
-    a.vis = vis; a.wgt = wgt; a.mask = mask; a.ws = work;
+    if (int rc = stk_setup("stokes_vis", dtype, mode, data, data2, subtract, weight, wform, flag, nflagcorr, frow, autocorr,
+                           jones, ndir, ntime, nant, tbin_idx, tbin_counts, tbin_off, ant1, ant2, nrow, nchan, vis, wgt,
+                           mask, wsum, work, a);
+        rc != PFB_OK) return rc;
     const size_t groups = a.ngroups < (size_t)STK_MAX_GROUPS ? a.ngroups : (size_t)STK_MAX_GROUPS;
     const int rc = by_type(dtype, [&](auto t) {
         return by_int<0, PFB_STOKES_NOJ2>(mode, [&](auto m) {
@@ -280,6 +481,39 @@ int pfb_stokes_vis(int dtype, int mode, int basis, const void* data, const void*
         });
     });
     return rc != PFB_OK ? rc : final_sum(work, (int)groups, 1, wsum, stream);
+}
+
+int pfb_stokes_vis_multi(int dtype, int mode, int nprod, const int* basis, const void* data, const void* data2,
+                         int subtract, const void* weight, int wform, const unsigned char* flag, int nflagcorr,
+                         const unsigned char* frow, int autocorr, const void* jones, int ndir, int ntime, int nant,
+                         const long long* tbin_idx, const long long* tbin_counts, long long tbin_off, const int* ant1,
+                         const int* ant2, size_t nrow, int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum,
+                         double* work, void* stream) {
+    PFB_REQUIRE(nprod >= 1 && nprod <= STK_MAX_PROD, PFB_ERR_INVALID, "stokes_vis_multi: %d products outside 1 .. %d",
+                nprod, STK_MAX_PROD);
+    PFB_REQUIRE(basis, PFB_ERR_INVALID, "stokes_vis_multi: null basis list");
+    StkMultiArgs ma;
+    for (int b = 0; b < 4; ++b) ma.plane[b] = -1;
+    for (int k = 0; k < STK_MAX_PROD; ++k) ma.basis[k] = 0;
+    for (int k = 0; k < nprod; ++k) {
+        const int b = basis[k];                                 // a host array
+        PFB_REQUIRE(b >= 0 && b <= 3, PFB_ERR_INVALID, "stokes_vis_multi: bad basis %d", b);
+        PFB_REQUIRE(ma.plane[b] < 0, PFB_ERR_INVALID, "stokes_vis_multi: basis %d asked for twice", b);
+        ma.plane[b] = k;
+        ma.basis[k] = b;
+    }
+    ma.nprod = nprod;
+    if (int rc = stk_setup("stokes_vis_multi", dtype, mode, data, data2, subtract, weight, wform, flag, nflagcorr, frow,
+                           autocorr, jones, ndir, ntime, nant, tbin_idx, tbin_counts, tbin_off, ant1, ant2, nrow, nchan,
+                           vis, wgt, mask, wsum, work, ma.s);
+        rc != PFB_OK) return rc;
+    const size_t groups = ma.s.ngroups < (size_t)STK_MULTI_MAX_GROUPS ? ma.s.ngroups : (size_t)STK_MULTI_MAX_GROUPS;
+    const int rc = by_type(dtype, [&](auto t) {
+        return by_int<0, PFB_STOKES_NOJ2>(mode, [&](auto m) {
+            return launch_groups(k_stokes_multi<decltype(t), m()>, groups, stream, ma);
+        });
+    });
+    return rc != PFB_OK ? rc : final_sum(work, (int)groups, nprod, wsum, stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@
 //                                  sum has a fixed order
 //   k_image_forward / _adjoint / _correct   the image side: window <-> grid with the plane's w phase, the kernel
 //                                  correction with 1/n and the beam fused in
+// The slot, footprint and image kernels carry a product axis NP = 1 .. 4 (the Stokes products of one chunk under ONE
+// order; pfb_wgrid_*_multi): what does not depend on the values is formed once and applied to every plane.
 // Coordinates (u, v, w -> cells and planes) and every phase are fp64 whatever the data type: a phase of some tens of
 // turns leaves 1e-6 of a turn in fp32.  Kernel values, grids and sums are in the data's type.
 //
@@ -120,32 +122,55 @@ __device__ __forceinline__ cplx<T> wg_cis(double turns) {
     return cplx<T>((T)cs, (T)sn);
 }
 
-// val[s] = wgt vis exp(+2 pi i (u cx + v cy))
-template <typename T>
+// The kernels below carry a product axis: NP planes (Stokes products) of slot values, grids and images, product-major,
+// under ONE order.  What does not depend on the values -- the slot's index and centre phase, the footprint's cells and
+// kernel values, a pixel's w phase, correction and beam -- is formed once and applied to every plane.  NP = 1 is the
+// single operator.  Plane k of the visibilities and weights starts at k nvis, of the slot values at k ns; with
+// `wshared` every plane takes the weights' plane 0.
+constexpr int WG_MAX_PROD = 4;
+
+// val[k][s] = wgt vis exp(+2 pi i (u cx + v cy))
+template <typename T, int NP>
 __global__ void __launch_bounds__(WG_BLOCK)
-k_prep(const cplx<T>* __restrict__ vis, const T* __restrict__ wgt, const int* __restrict__ idx,
-       const double* __restrict__ coord, size_t ns, double cxs, double cys, int centre, cplx<T>* __restrict__ val) {
+k_prep(const cplx<T>* __restrict__ vis, const T* __restrict__ wgt, int wshared, const int* __restrict__ idx,
+       const double* __restrict__ coord, size_t ns, size_t nvis, double cxs, double cys, int centre,
+       cplx<T>* __restrict__ val) {
     const size_t s = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
     if (s >= ns) return;
     const int t = idx[s];
-    cplx<T> v = vis[t];
-    if (wgt) v = wgt[t] * v;
-    if (centre) v = v * wg_cis<T>(wg_centre_turns(coord, ns, s, cxs, cys));
-    val[s] = v;
+    cplx<T> ph;                        // formed with the first product, under the same uniform branch as its use
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        cplx<T> v = vis[k * nvis + t];
+        if (wgt) v = wgt[(wshared ? 0 : k * nvis) + t] * v;
+        if (centre) {
+            if (k == 0) ph = wg_cis<T>(wg_centre_turns(coord, ns, s, cxs, cys));
+            v = v * ph;
+        }
+        val[k * ns + s] = v;
+    }
 }
 
-// vis[idx[s]] = wgt acc[s] exp(-2 pi i (u cx + v cy)); vis was zeroed by the launcher
-template <typename T>
+// vis[k][idx[s]] = wgt acc[k][s] exp(-2 pi i (u cx + v cy)); vis was zeroed by the launcher
+template <typename T, int NP>
 __global__ void __launch_bounds__(WG_BLOCK)
-k_finish(const cplx<T>* __restrict__ acc, const T* __restrict__ wgt, const int* __restrict__ idx,
-         const double* __restrict__ coord, size_t ns, double cxs, double cys, int centre, cplx<T>* __restrict__ vis) {
+k_finish(const cplx<T>* __restrict__ acc, const T* __restrict__ wgt, int wshared, const int* __restrict__ idx,
+         const double* __restrict__ coord, size_t ns, size_t nvis, double cxs, double cys, int centre,
+         cplx<T>* __restrict__ vis) {
     const size_t s = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
     if (s >= ns) return;
     const int t = idx[s];
-    cplx<T> v = acc[s];
-    if (centre) v = v * wg_cis<T>(-wg_centre_turns(coord, ns, s, cxs, cys));
-    if (wgt) v = wgt[t] * v;
-    vis[t] = v;
+    cplx<T> ph;                        // as in k_prep
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        cplx<T> v = acc[k * ns + s];
+        if (centre) {
+            if (k == 0) ph = wg_cis<T>(-wg_centre_turns(coord, ns, s, cxs, cys));
+            v = v * ph;
+        }
+        if (wgt) v = wgt[(wshared ? 0 : k * nvis) + t] * v;
+        vis[k * nvis + t] = v;
+    }
 }
 
 // the block form of k_finish: slot s is visibility (r, c) = (t / nchan_blk, t % nchan_blk) of a block of rows and
@@ -199,7 +224,9 @@ k_weight(const cplx<T>* __restrict__ acc, const T* __restrict__ wgt, const int* 
 // about 64 / (2 W) rows; with a lane per ROW instead, its 64 adds went to 64 different rows, the slowest shape there is
 // (5.5e2 us per plane for either data type).  Every lane re-evaluates the W row values: arithmetic is
 // cheap next to the adds, and a slot's lanes may straddle two waves, so they cannot be shuffled
-template <typename T, int W>
+// With NP products a lane forms its coordinates, w weight, column value and each row's value once and issues NP adds
+// per row, one into each product's grid
+template <typename T, int W, int NP>
 __global__ void __launch_bounds__(WG_BLOCK)
 k_grid(const cplx<T>* __restrict__ val, const double* __restrict__ coord, size_t ns, size_t s0, size_t s1, int plane,
        WgGeom g, T* __restrict__ grid) {
@@ -217,22 +244,30 @@ k_grid(const cplx<T>* __restrict__ val, const double* __restrict__ coord, size_t
     }
     const double ug = coord[s], vg = coord[ns + s];
     const double a0 = wg_first(ug, h), b0 = wg_first(vg, h);
-    const cplx<T> v = val[s];
-    const T part = (c ? v.y : v.x) * ww * wg_phi<T>((T)((b0 + b - vg) / h), beta);
+    const T fv = wg_phi<T>((T)((b0 + b - vg) / h), beta);
+    T part[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const cplx<T> v = val[k * ns + s];
+        part[k] = (c ? v.y : v.x) * ww * fv;
+    }
     int col = wg_wrap(b0, g.Nv) + b;
     if (col >= g.Nv) col -= g.Nv;
     int row = wg_wrap(a0, g.Nu);
+    const size_t gplane = 2 * (size_t)g.Nu * g.Nv;
     T* __restrict__ cell = grid + 2 * (size_t)col + c;
 #pragma unroll
     for (int a = 0; a < W; ++a) {
         const T fu = wg_phi<T>((T)((a0 + a - ug) / h), beta);
-        atomic_add(cell + 2 * (size_t)row * g.Nv, fu * part);
+#pragma unroll
+        for (int k = 0; k < NP; ++k) atomic_add(cell + k * gplane + 2 * (size_t)row * g.Nv, fu * part[k]);
         if (++row == g.Nu) row = 0;
     }
 }
 
 // ----------------------------------------------------------------------------------------- degridding, one plane
-template <typename T, int W>
+// With NP products the W column values and each row's value are formed once; NP running sums
+template <typename T, int W, int NP>
 __global__ void __launch_bounds__(WG_BLOCK)
 k_degrid(const cplx<T>* __restrict__ grid, const double* __restrict__ coord, size_t ns, size_t s0, size_t s1, int plane,
          WgGeom g, cplx<T>* __restrict__ acc) {
@@ -252,28 +287,37 @@ k_degrid(const cplx<T>* __restrict__ grid, const double* __restrict__ coord, siz
     for (int b = 0; b < W; ++b) fv[b] = wg_phi<T>((T)((b0 + b - vg) / h), beta);
     int row = wg_wrap(a0, g.Nu);
     const int col0 = wg_wrap(b0, g.Nv);
-    T sx = T(0), sy = T(0);
+    const size_t gplane = (size_t)g.Nu * g.Nv;
+    T sx[NP], sy[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) sx[k] = sy[k] = T(0);
 #pragma unroll 1          // one row of loads in flight: unrolled, the fp64 kernels of W = 11, 12 spill
     for (int a = 0; a < W; ++a) {
         const T fu = wg_phi<T>((T)((a0 + a - ug) / h), beta);
-        const cplx<T>* __restrict__ line = grid + (size_t)row * g.Nv;
-        int col = col0;
-        T rx = T(0), ry = T(0);
 #pragma unroll
-        for (int b = 0; b < W; ++b) {
-            const cplx<T> c = line[col];
-            rx += fv[b] * c.x;
-            ry += fv[b] * c.y;
-            if (++col == g.Nv) col = 0;
+        for (int k = 0; k < NP; ++k) {
+            const cplx<T>* __restrict__ line = grid + k * gplane + (size_t)row * g.Nv;
+            int col = col0;
+            T rx = T(0), ry = T(0);
+#pragma unroll
+            for (int b = 0; b < W; ++b) {
+                const cplx<T> c = line[col];
+                rx += fv[b] * c.x;
+                ry += fv[b] * c.y;
+                if (++col == g.Nv) col = 0;
+            }
+            sx[k] += fu * rx;
+            sy[k] += fu * ry;
         }
-        sx += fu * rx;
-        sy += fu * ry;
         if (++row == g.Nu) row = 0;
     }
-    cplx<T> r = acc[s];
-    r.x += ww * sx;
-    r.y += ww * sy;
-    acc[s] = r;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        cplx<T> r = acc[k * ns + s];
+        r.x += ww * sx[k];
+        r.y += ww * sy[k];
+        acc[k * ns + s] = r;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the image side
@@ -285,57 +329,71 @@ __device__ __forceinline__ size_t wg_cell(int i, int j, int nx, int ny, int Nu, 
 }
 
 // grid (zeroed by the launcher) <- dirty corr [beam] exp(+2 pi i w_p nm1)
-template <typename T>
+// NP images and grids, product-major; corr, beam and the w phase of a pixel are the same for every product
+template <typename T, int NP>
 __global__ void __launch_bounds__(WG_BLOCK)
 k_image_forward(const T* __restrict__ dirty, const T* __restrict__ beam, const double* __restrict__ corr,
                 const double* __restrict__ nm1, double wp, int nx, int ny, int Nu, int Nv, cplx<T>* __restrict__ grid) {
-    const size_t q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
-    if (q >= (size_t)nx * ny) return;
+    const size_t npix = (size_t)nx * ny, q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (q >= npix) return;
     const int i = (int)(q / ny), j = (int)(q - (size_t)i * ny);
-    double d = (double)dirty[q] * corr[q];
-    if (beam) d *= (double)beam[q];
-    cplx<T> v((T)d, T(0));
-    if (nm1) {
-        double sn, cs;
-        sincospi(2.0 * wp * nm1[q], &sn, &cs);
-        v = cplx<T>((T)(d * cs), (T)(d * sn));
+    const double cq = corr[q], bq = beam ? (double)beam[q] : 1.0;
+    double sn = 0.0, cs = 1.0;
+    if (nm1) sincospi(2.0 * wp * nm1[q], &sn, &cs);
+    const size_t cell = wg_cell(i, j, nx, ny, Nu, Nv), gplane = (size_t)Nu * Nv;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        double d = (double)dirty[k * npix + q] * cq;
+        if (beam) d *= bq;
+        grid[k * gplane + cell] = nm1 ? cplx<T>((T)(d * cs), (T)(d * sn)) : cplx<T>((T)d, T(0));
     }
-    grid[wg_cell(i, j, nx, ny, Nu, Nv)] = v;
 }
 
 // img += window(grid) exp(-2 pi i w_p nm1)
-template <typename T>
+template <typename T, int NP>
 __global__ void __launch_bounds__(WG_BLOCK)
 k_image_adjoint(const cplx<T>* __restrict__ grid, const double* __restrict__ nm1, double wp, int nx, int ny, int Nu,
                 int Nv, cplx<T>* __restrict__ img) {
-    const size_t q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
-    if (q >= (size_t)nx * ny) return;
+    const size_t npix = (size_t)nx * ny, q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (q >= npix) return;
     const int i = (int)(q / ny), j = (int)(q - (size_t)i * ny);
-    const cplx<T> c = grid[wg_cell(i, j, nx, ny, Nu, Nv)];
-    cplx<T> r = img[q];
-    if (nm1) {
-        double sn, cs;
-        sincospi(-2.0 * wp * nm1[q], &sn, &cs);
-        const T cx = (T)cs, sx = (T)sn;
-        r.x += c.x * cx - c.y * sx;
-        r.y += c.x * sx + c.y * cx;
-    } else {
-        r.x += c.x;
-        r.y += c.y;
+    const size_t cell = wg_cell(i, j, nx, ny, Nu, Nv), gplane = (size_t)Nu * Nv;
+    T cx, sx;                          // the pixel's w phase: formed with the first product, under the branch of its use
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const cplx<T> c = grid[k * gplane + cell];
+        cplx<T> r = img[k * npix + q];
+        if (nm1) {
+            if (k == 0) {
+                double sn, cs;
+                sincospi(-2.0 * wp * nm1[q], &sn, &cs);
+                cx = (T)cs;
+                sx = (T)sn;
+            }
+            r.x += c.x * cx - c.y * sx;
+            r.y += c.x * sx + c.y * cx;
+        } else {
+            r.x += c.x;
+            r.y += c.y;
+        }
+        img[k * npix + q] = r;
     }
-    img[q] = r;
 }
 
 // dirty = Re(img) corr [beam]
-template <typename T>
+template <typename T, int NP>
 __global__ void __launch_bounds__(WG_BLOCK)
 k_image_correct(const cplx<T>* __restrict__ img, const double* __restrict__ corr, const T* __restrict__ beam, size_t npix,
                 T* __restrict__ dirty) {
     const size_t q = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
     if (q >= npix) return;
-    double d = (double)img[q].x * corr[q];
-    if (beam) d *= (double)beam[q];
-    dirty[q] = (T)d;
+    const double cq = corr[q], bq = beam ? (double)beam[q] : 1.0;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        double d = (double)img[k * npix + q].x * cq;
+        if (beam) d *= bq;
+        dirty[k * npix + q] = (T)d;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------ launchers
@@ -368,6 +426,117 @@ static int wg_range(const WgridPlan& p, const char* name, int plane, size_t s0, 
     PFB_REQUIRE((s1 - s0) * 2 * (size_t)p.W <= WG_MAX_THREADS, PFB_ERR_UNSUPPORTED, "%s: %zu slots in one launch", name,
                 s1 - s0);
     return PFB_OK;
+}
+static int wg_nprod(const char* name, int nprod) {
+    PFB_REQUIRE(nprod >= 1 && nprod <= WG_MAX_PROD, PFB_ERR_INVALID, "%s: %d products outside 1 .. %d", name, nprod,
+                WG_MAX_PROD);
+    return PFB_OK;
+}
+
+// The entry points with a product axis, under both of their names: pfb_wgrid_X is X with one product,
+// pfb_wgrid_X_multi with nprod (checked there).  One body each, so the two cannot drift apart.
+static int wg_prep(const char* name, void* plan, int nprod, const void* vis, const void* wgt, int wshared, const int* idx,
+                   const double* coord, size_t nsorted, size_t nvis, void* val, void* stream) {
+    if (int rc = wg_check(plan, name, {{vis, CPLX}, {wgt, REAL, true}, {idx, I32}, {coord, F64}, {val, CPLX}});
+        rc != PFB_OK) return rc;
+    if (int rc = check_count(name, nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+            return launch(k_prep<decltype(t), np()>, nsorted, stream, vis, wgt, wshared, idx, coord, nsorted, nvis,
+                          p.cxs(), p.cys(), p.centre(), val);
+        });
+    });
+}
+
+static int wg_finish(const char* name, void* plan, int nprod, const void* acc, const void* wgt, int wshared,
+                     const int* idx, const double* coord, size_t nsorted, void* vis, size_t nvis, void* stream) {
+    if (int rc = wg_check(plan, name, {{acc, CPLX}, {wgt, REAL, true}, {idx, I32}, {coord, F64}, {vis, CPLX}});
+        rc != PFB_OK) return rc;
+    if (int rc = check_count(name, nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
+    PFB_REQUIRE(nsorted <= nvis && nvis <= (size_t)0x7fffffff, PFB_ERR_INVALID, "%s: %zu slots for %zu visibilities",
+                name, nsorted, nvis);
+    const WgridPlan& p = wg_plan(plan);
+    PFB_HIP_CHECK(hipMemsetAsync(vis, 0, 2 * p.esize() * nvis * (size_t)nprod, as_stream(stream)));
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+            return launch(k_finish<decltype(t), np()>, nsorted, stream, acc, wgt, wshared, idx, coord, nsorted, nvis,
+                          p.cxs(), p.cys(), p.centre(), vis);
+        });
+    });
+}
+
+static int wg_grid(const char* name, void* plan, int nprod, int plane, const void* val, const double* coord,
+                   size_t nsorted, size_t s0, size_t s1, void* grid, void* stream) {
+    if (int rc = wg_check(plan, name, {{val, CPLX}, {coord, F64}, {grid, CPLX}}); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_range(p, name, plane, s0, s1, nsorted); rc != PFB_OK) return rc;
+    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes() * (size_t)nprod, as_stream(stream)));
+    if (s1 == s0) return PFB_OK;
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<WG_MIN_W, WG_MAX_W>(p.W, [&](auto w) {
+            return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+                return launch(k_grid<decltype(t), w(), np()>, (s1 - s0) * 2 * w(), stream, val, coord, nsorted, s0, s1,
+                              plane, wg_geom(p), grid);
+            });
+        });
+    });
+}
+
+static int wg_degrid(const char* name, void* plan, int nprod, int plane, const void* grid, const double* coord,
+                     size_t nsorted, size_t s0, size_t s1, void* acc, void* stream) {
+    if (int rc = wg_check(plan, name, {{grid, CPLX}, {coord, F64}, {acc, CPLX}}); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_range(p, name, plane, s0, s1, nsorted); rc != PFB_OK) return rc;
+    if (s1 == s0) return PFB_OK;
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<WG_MIN_W, WG_MAX_W>(p.W, [&](auto w) {
+            return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+                return launch(k_degrid<decltype(t), w(), np()>, s1 - s0, stream, grid, coord, nsorted, s0, s1, plane,
+                              wg_geom(p), acc);
+            });
+        });
+    });
+}
+
+static int wg_image_forward(const char* name, void* plan, int nprod, int plane, const void* dirty, const void* beam,
+                            const double* corr, const double* nm1, void* grid, void* stream) {
+    if (int rc = wg_check(plan, name, {{dirty, REAL}, {beam, REAL, true}, {corr, F64}, {nm1, F64, true}, {grid, CPLX}});
+        rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_plane(p, name, plane); rc != PFB_OK) return rc;
+    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes() * (size_t)nprod, as_stream(stream)));
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+            return launch(k_image_forward<decltype(t), np()>, p.npix(), stream, dirty, beam, corr, nm1, p.wp(plane), p.nx,
+                          p.ny, p.Nu, p.Nv, grid);
+        });
+    });
+}
+
+static int wg_image_adjoint(const char* name, void* plan, int nprod, int plane, const void* grid, const double* nm1,
+                            void* img, void* stream) {
+    if (int rc = wg_check(plan, name, {{grid, CPLX}, {nm1, F64, true}, {img, CPLX}}); rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_plane(p, name, plane); rc != PFB_OK) return rc;
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+            return launch(k_image_adjoint<decltype(t), np()>, p.npix(), stream, grid, nm1, p.wp(plane), p.nx, p.ny, p.Nu,
+                          p.Nv, img);
+        });
+    });
+}
+
+static int wg_image_correct(const char* name, void* plan, int nprod, const void* img, const double* corr,
+                            const void* beam, void* dirty, void* stream) {
+    if (int rc = wg_check(plan, name, {{img, CPLX}, {corr, F64}, {beam, REAL, true}, {dirty, REAL}}); rc != PFB_OK)
+        return rc;
+    const WgridPlan& p = wg_plan(plan);
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+            return launch(k_image_correct<decltype(t), np()>, p.npix(), stream, img, corr, beam, p.npix(), dirty);
+        });
+    });
 }
 
 }  // namespace pfb
@@ -453,28 +622,26 @@ int pfb_wgrid_order_fill(void* plan, const double* uvw, const double* freq, size
 
 int pfb_wgrid_prep(void* plan, const void* vis, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                    void* val, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_prep", {{vis, CPLX}, {wgt, REAL, true}, {idx, I32}, {coord, F64}, {val, CPLX}});
-        rc != PFB_OK) return rc;
-    if (int rc = check_count("wgrid_prep", nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
-    const WgridPlan& p = wg_plan(plan);
-    return by_type(p.dtype, [&](auto t) {
-        return launch(k_prep<decltype(t)>, nsorted, stream, vis, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), val);
-    });
+    return wg_prep("wgrid_prep", plan, 1, vis, wgt, 0, idx, coord, nsorted, 0, val, stream);
+}
+
+int pfb_wgrid_prep_multi(void* plan, int nprod, const void* vis, const void* wgt, int wgt_shared, const int* idx,
+                         const double* coord, size_t nsorted, size_t nvis, void* val, void* stream) {
+    if (int rc = wg_nprod("wgrid_prep_multi", nprod); rc != PFB_OK) return rc;
+    PFB_REQUIRE(nsorted <= nvis && nvis <= (size_t)0x7fffffff, PFB_ERR_INVALID,
+                "wgrid_prep_multi: %zu slots for %zu visibilities", nsorted, nvis);
+    return wg_prep("wgrid_prep_multi", plan, nprod, vis, wgt, wgt_shared != 0, idx, coord, nsorted, nvis, val, stream);
 }
 
 int pfb_wgrid_finish(void* plan, const void* acc, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                      void* vis, size_t nvis, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_finish", {{acc, CPLX}, {wgt, REAL, true}, {idx, I32}, {coord, F64},
-                                                 {vis, CPLX}});
-        rc != PFB_OK) return rc;
-    if (int rc = check_count("wgrid_finish", nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
-    PFB_REQUIRE(nsorted <= nvis && nvis <= (size_t)0x7fffffff, PFB_ERR_INVALID,
-                "wgrid_finish: %zu slots for %zu visibilities", nsorted, nvis);
-    const WgridPlan& p = wg_plan(plan);
-    PFB_HIP_CHECK(hipMemsetAsync(vis, 0, 2 * p.esize() * nvis, as_stream(stream)));
-    return by_type(p.dtype, [&](auto t) {
-        return launch(k_finish<decltype(t)>, nsorted, stream, acc, wgt, idx, coord, nsorted, p.cxs(), p.cys(), p.centre(), vis);
-    });
+    return wg_finish("wgrid_finish", plan, 1, acc, wgt, 0, idx, coord, nsorted, vis, nvis, stream);
+}
+
+int pfb_wgrid_finish_multi(void* plan, int nprod, const void* acc, const void* wgt, int wgt_shared, const int* idx,
+                           const double* coord, size_t nsorted, void* vis, size_t nvis, void* stream) {
+    if (int rc = wg_nprod("wgrid_finish_multi", nprod); rc != PFB_OK) return rc;
+    return wg_finish("wgrid_finish_multi", plan, nprod, acc, wgt, wgt_shared != 0, idx, coord, nsorted, vis, nvis, stream);
 }
 
 int pfb_wgrid_finish_block(void* plan, const void* acc, const int* idx, const double* coord, size_t nsorted,
@@ -527,63 +694,55 @@ int pfb_wgrid_weight(void* plan, const void* acc, const void* wgt, const int* id
 
 int pfb_wgrid_grid(void* plan, int plane, const void* val, const double* coord, size_t nsorted, size_t s0, size_t s1,
                    void* grid, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_grid", {{val, CPLX}, {coord, F64}, {grid, CPLX}}); rc != PFB_OK) return rc;
-    const WgridPlan& p = wg_plan(plan);
-    if (int rc = wg_range(p, "wgrid_grid", plane, s0, s1, nsorted); rc != PFB_OK) return rc;
-    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes(), as_stream(stream)));
-    if (s1 == s0) return PFB_OK;
-    return by_type(p.dtype, [&](auto t) {
-        return by_int<WG_MIN_W, WG_MAX_W>(p.W, [&](auto w) {
-            return launch(k_grid<decltype(t), w()>, (s1 - s0) * 2 * w(), stream, val, coord, nsorted, s0, s1, plane,
-                          wg_geom(p), grid);
-        });
-    });
+    return wg_grid("wgrid_grid", plan, 1, plane, val, coord, nsorted, s0, s1, grid, stream);
+}
+
+int pfb_wgrid_grid_multi(void* plan, int nprod, int plane, const void* val, const double* coord, size_t nsorted,
+                         size_t s0, size_t s1, void* grid, void* stream) {
+    if (int rc = wg_nprod("wgrid_grid_multi", nprod); rc != PFB_OK) return rc;
+    return wg_grid("wgrid_grid_multi", plan, nprod, plane, val, coord, nsorted, s0, s1, grid, stream);
 }
 
 int pfb_wgrid_degrid(void* plan, int plane, const void* grid, const double* coord, size_t nsorted, size_t s0, size_t s1,
                      void* acc, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_degrid", {{grid, CPLX}, {coord, F64}, {acc, CPLX}}); rc != PFB_OK) return rc;
-    const WgridPlan& p = wg_plan(plan);
-    if (int rc = wg_range(p, "wgrid_degrid", plane, s0, s1, nsorted); rc != PFB_OK) return rc;
-    if (s1 == s0) return PFB_OK;
-    return by_type(p.dtype, [&](auto t) {
-        return by_int<WG_MIN_W, WG_MAX_W>(p.W, [&](auto w) {
-            return launch(k_degrid<decltype(t), w()>, s1 - s0, stream, grid, coord, nsorted, s0, s1, plane, wg_geom(p), acc);
-        });
-    });
+    return wg_degrid("wgrid_degrid", plan, 1, plane, grid, coord, nsorted, s0, s1, acc, stream);
+}
+
+int pfb_wgrid_degrid_multi(void* plan, int nprod, int plane, const void* grid, const double* coord, size_t nsorted,
+                           size_t s0, size_t s1, void* acc, void* stream) {
+    if (int rc = wg_nprod("wgrid_degrid_multi", nprod); rc != PFB_OK) return rc;
+    return wg_degrid("wgrid_degrid_multi", plan, nprod, plane, grid, coord, nsorted, s0, s1, acc, stream);
 }
 
 int pfb_wgrid_image_forward(void* plan, int plane, const void* dirty, const void* beam, const double* corr,
                             const double* nm1, void* grid, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_image_forward", {{dirty, REAL}, {beam, REAL, true}, {corr, F64},
-                                                        {nm1, F64, true}, {grid, CPLX}});
-        rc != PFB_OK) return rc;
-    const WgridPlan& p = wg_plan(plan);
-    if (int rc = wg_plane(p, "wgrid_image_forward", plane); rc != PFB_OK) return rc;
-    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes(), as_stream(stream)));
-    return by_type(p.dtype, [&](auto t) {
-        return launch(k_image_forward<decltype(t)>, p.npix(), stream, dirty, beam, corr, nm1, p.wp(plane), p.nx, p.ny,
-                      p.Nu, p.Nv, grid);
-    });
+    return wg_image_forward("wgrid_image_forward", plan, 1, plane, dirty, beam, corr, nm1, grid, stream);
+}
+
+int pfb_wgrid_image_forward_multi(void* plan, int nprod, int plane, const void* dirty, const void* beam,
+                                  const double* corr, const double* nm1, void* grid, void* stream) {
+    if (int rc = wg_nprod("wgrid_image_forward_multi", nprod); rc != PFB_OK) return rc;
+    return wg_image_forward("wgrid_image_forward_multi", plan, nprod, plane, dirty, beam, corr, nm1, grid, stream);
 }
 
 int pfb_wgrid_image_adjoint(void* plan, int plane, const void* grid, const double* nm1, void* img, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_image_adjoint", {{grid, CPLX}, {nm1, F64, true}, {img, CPLX}});
-        rc != PFB_OK) return rc;
-    const WgridPlan& p = wg_plan(plan);
-    if (int rc = wg_plane(p, "wgrid_image_adjoint", plane); rc != PFB_OK) return rc;
-    return by_type(p.dtype, [&](auto t) {
-        return launch(k_image_adjoint<decltype(t)>, p.npix(), stream, grid, nm1, p.wp(plane), p.nx, p.ny, p.Nu, p.Nv, img);
-    });
+    return wg_image_adjoint("wgrid_image_adjoint", plan, 1, plane, grid, nm1, img, stream);
+}
+
+int pfb_wgrid_image_adjoint_multi(void* plan, int nprod, int plane, const void* grid, const double* nm1, void* img,
+                                  void* stream) {
+    if (int rc = wg_nprod("wgrid_image_adjoint_multi", nprod); rc != PFB_OK) return rc;
+    return wg_image_adjoint("wgrid_image_adjoint_multi", plan, nprod, plane, grid, nm1, img, stream);
 }
 
 int pfb_wgrid_image_correct(void* plan, const void* img, const double* corr, const void* beam, void* dirty, void* stream) {
-    if (int rc = wg_check(plan, "wgrid_image_correct", {{img, CPLX}, {corr, F64}, {beam, REAL, true}, {dirty, REAL}});
-        rc != PFB_OK) return rc;
-    const WgridPlan& p = wg_plan(plan);
-    return by_type(p.dtype, [&](auto t) {
-        return launch(k_image_correct<decltype(t)>, p.npix(), stream, img, corr, beam, p.npix(), dirty);
-    });
+    return wg_image_correct("wgrid_image_correct", plan, 1, img, corr, beam, dirty, stream);
+}
+
+int pfb_wgrid_image_correct_multi(void* plan, int nprod, const void* img, const double* corr, const void* beam,
+                                  void* dirty, void* stream) {
+    if (int rc = wg_nprod("wgrid_image_correct_multi", nprod); rc != PFB_OK) return rc;
+    return wg_image_correct("wgrid_image_correct_multi", plan, nprod, img, corr, beam, dirty, stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@ exp(2.3 W (sqrt(1 - x^2) - 1)) of W = ceil(log10(1/epsilon)) + 2 cells (DESIGN 4
 
 The c2c transform of a plane is torch.fft (the precedent of operators/fft.py); everything else is csrc/wgrid.hip.
 
+Beyond ducc0: vis (nprod, nrow, nchan) / dirty (nprod, nx, ny), nprod <= 4 -- the Stokes products of one chunk, e.g. of
+utils.stokes.stokes_vis(product='IQUV') -- go through both operators in ONE call under one plan and order
+(pfb_wgrid_*_multi: what depends on the coordinates alone is computed once for all planes).
+
 A WgridPlan holds what one (uvw, freq, mask) set and one image geometry share between calls: support, planes, the
 correction tables and the visibilities' sorted order.  Plans live in a PlanCache: a major cycle that presents the same
 arrays again builds nothing.  numpy in gives numpy out, tensors in give tensors out; there is no CPU path.
@@ -37,6 +41,7 @@ from .fft import psfhat_from_psf
 
 C_LIGHT = 299792458.0
 EPS_MAX = 1e-2
+MAX_PROD = 4            # planes of a stacked call (WG_MAX_PROD of csrc/wgrid.hip): the Stokes products
 # lower bounds of epsilon: fp64 by the support range of the kernels (W <= 12); fp32 measured: the lowest decade tried
 # (1e-3, 1e-4, 1e-5) at which every case of tests/wgrid_cases.py stays under epsilon / 3 on the MI355X
 EPS_MIN = {torch.float64: 1e-10, torch.float32: 1e-5}
@@ -156,7 +161,7 @@ def tables_for(nx, ny, pixsize_x, pixsize_y, center_x, center_y, W, do_wgridding
 class WgridPlan(NativePlan):
     """One (uvw, freq, mask) set on one image geometry: the native geometry record, the sorted order (idx, coord, the
     planes' slot ranges), nm1 and the correction tables (the geometry's GeomTables), and the per-call buffers (one grid,
-    val / acc, the complex image).  Use through vis2dirty / dirty2vis / hessian, which hold `lock`.  `degrid_only`: a
+    val / acc, the complex image; and their stacks of up to MAX_PROD planes once a stacked call has come).  Use through vis2dirty / dirty2vis / hessian, which hold `lock`.  `degrid_only`: a
     block plan of the predict step, which holds the grid and one slot vector and has dirty2vis_into only."""
     _destroy = 'pfb_wgrid_plan_destroy'
 
@@ -180,6 +185,7 @@ class WgridPlan(NativePlan):
         self.nm1 = self.tables.nm1
         # ---- the w range of the unmasked visibilities -> planes
         self.nsorted = 0
+        self._stack = None              # the buffers of stacked calls (_buffers)
         w = self.uvw[:, 2:3] * self.freq[None, :] / C_LIGHT
         if self.mask is not None:
             w = w[self.mask != 0]
@@ -238,54 +244,110 @@ class WgridPlan(NativePlan):
         if t.dtype != dtype or tuple(t.shape) != tuple(shape):
             raise ValueError(f"{name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
 
-    def _degrid_all(self, x, beam, divide_by_n):
-        """acc (the first slot vector) = the footprint sums of every slot over all planes, from image x."""
-        g = self._grid
-        acc = self._slots[0]
+    # A stacked call carries `nprod` planes (Stokes products) through every step under the plan's one order; nprod None
+    # is the single operator, on the plan's own buffers and through the single entry points.
+    def _buffers(self, nprod):
+        """(grid, slots (2, ..), img) of a call: the plan's own, or the first nprod planes of its stacks -- grid
+        (nprod, 2 nx, 2 ny), two slot stacks (nprod, nsorted), the complex images (nprod, nx, ny) --, which are allocated
+        on the first stacked call, grown by a call with more planes, and kept."""
+        if nprod is None:
+            return self._grid, self._slots, self._img
+        if self._stack is None or self._stack[0].shape[0] < nprod:
+            dev = self.idx.device
+            self._stack = (torch.empty((nprod, 2 * self.nx, 2 * self.ny), dtype=self.cdtype, device=dev),
+                           torch.empty((2, nprod, self.nsorted), dtype=self.cdtype, device=dev),
+                           torch.empty((nprod, self.nx, self.ny), dtype=self.cdtype, device=dev))
+        if self._stack[0].shape[0] == nprod:
+            return self._stack
+        # fewer planes than the stacks hold: every plane has to follow its predecessor, so the slots are re-cut
+        g, slots, img = self._stack
+        return g[:nprod], slots.view(-1)[:2 * nprod * self.nsorted].view(2, nprod, self.nsorted), img[:nprod]
+
+    def _step(self, name, nprod, *args):
+        """pfb_wgrid_<name>, or pfb_wgrid_<name>_multi with nprod in front of its arguments."""
+        if nprod is None:
+            self.run('pfb_wgrid_' + name, *args)
+        else:
+            self.run('pfb_wgrid_' + name + '_multi', nprod, *args)
+
+    def _degrid_all(self, x, beam, divide_by_n, nprod=None):
+        """acc (the first slot vector, or stack) = the footprint sums of every slot over all planes, from image x."""
+        g, slots, _ = self._buffers(nprod)
+        acc = slots[0]
         acc.zero_()
         corr = self.corr(divide_by_n)
         for p, s0, s1 in self.plane_ranges():
-            self.run('pfb_wgrid_image_forward', p, _dev.ptr(x), _dev.ptr(beam), _dev.ptr(corr), _dev.ptr(self.nm1),
-                     _dev.ptr(g))
+            self._step('image_forward', nprod, p, _dev.ptr(x), _dev.ptr(beam), _dev.ptr(corr), _dev.ptr(self.nm1),
+                       _dev.ptr(g))
             gh = torch.fft.fft2(g).contiguous()       # a fresh tensor: `out=` costs a copy of the grid per transform
-            self.run('pfb_wgrid_degrid', p, _dev.ptr(gh), _dev.ptr(self.coord), self.nsorted, s0, s1, _dev.ptr(acc))
+            self._step('degrid', nprod, p, _dev.ptr(gh), _dev.ptr(self.coord), self.nsorted, s0, s1, _dev.ptr(acc))
         return acc
 
-    def _grid_all(self, val, beam, divide_by_n):
-        """The (nx, ny) real image of the slot values `val`, corrected."""
-        g = self._grid
-        self._img.zero_()
+    def _grid_all(self, val, beam, divide_by_n, nprod=None):
+        """The (nx, ny) real image, or the (nprod, nx, ny) images, of the slot values `val`, corrected."""
+        g, _, img = self._buffers(nprod)
+        img.zero_()
         for p, s0, s1 in self.plane_ranges():
-            self.run('pfb_wgrid_grid', p, _dev.ptr(val), _dev.ptr(self.coord), self.nsorted, s0, s1, _dev.ptr(g))
+            self._step('grid', nprod, p, _dev.ptr(val), _dev.ptr(self.coord), self.nsorted, s0, s1, _dev.ptr(g))
             gh = torch.fft.ifft2(g, norm='forward').contiguous()
-            self.run('pfb_wgrid_image_adjoint', p, _dev.ptr(gh), _dev.ptr(self.nm1), _dev.ptr(self._img))
-        out = torch.empty((self.nx, self.ny), dtype=self.rdtype, device=val.device)
-        self.run('pfb_wgrid_image_correct', _dev.ptr(self._img), _dev.ptr(self.corr(divide_by_n)), _dev.ptr(beam),
-                 _dev.ptr(out))
+            self._step('image_adjoint', nprod, p, _dev.ptr(gh), _dev.ptr(self.nm1), _dev.ptr(img))
+        out = torch.empty(img.shape, dtype=self.rdtype, device=val.device)
+        self._step('image_correct', nprod, _dev.ptr(img), _dev.ptr(self.corr(divide_by_n)), _dev.ptr(beam),
+                   _dev.ptr(out))
         return out
+
+    def _stacked(self, name, x, plane_shape, dtype, wgt):
+        """What a call is: (None, wgt, 0) for a 2-D x -- checked as always --, else (nprod, wgt, shared) for x
+        (nprod, *plane_shape) with 1 <= nprod <= 4 and wgt None, (nprod, nrow, nchan), or (nrow, nchan) shared by every
+        plane."""
+        vshape = (self.nrow, self.nchan)
+        if x.ndim != 3:
+            self._check(name, x, dtype, plane_shape)
+            self._check('wgt', wgt, self.rdtype, vshape)
+            return None, wgt, 0
+        nprod = int(x.shape[0])
+        if not 1 <= nprod <= MAX_PROD:
+            raise ValueError(f"{name} stacks {nprod} planes: 1 to {MAX_PROD} products share a call")
+        self._check(name, x, dtype, (nprod,) + tuple(plane_shape))
+        shared = wgt is not None and wgt.ndim == 2
+        self._check('wgt', wgt, self.rdtype, vshape if shared else (nprod,) + vshape)
+        return nprod, (None if wgt is None else wgt.contiguous()), int(shared)
 
     # ---------------------------------------------------------------------------------------------- operators
     def vis2dirty(self, vis, wgt=None, divide_by_n=True):
-        self._check('vis', vis, self.cdtype, (self.nrow, self.nchan))
-        self._check('wgt', wgt, self.rdtype, (self.nrow, self.nchan))
+        """dirty (nx, ny) of vis (nrow, nchan), or (nprod, nx, ny) of a stack vis (nprod, nrow, nchan), nprod <= 4, with
+        wgt None, one (nrow, nchan) plane for every product, or (nprod, nrow, nchan)."""
+        nprod, wgt, shared = self._stacked('vis', vis, (self.nrow, self.nchan), self.cdtype, wgt)
         if self.nsorted == 0:
-            return torch.zeros((self.nx, self.ny), dtype=self.rdtype, device=vis.device)
+            return torch.zeros(vis.shape[:-2] + (self.nx, self.ny), dtype=self.rdtype, device=vis.device)
+        vis = vis if nprod is None else vis.contiguous()
         with self.lock:
-            val = self._slots[1]
-            self.run('pfb_wgrid_prep', _dev.ptr(vis), _dev.ptr(wgt), _dev.ptr(self.idx), _dev.ptr(self.coord),
-                     self.nsorted, _dev.ptr(val))
-            return self._grid_all(val, None, divide_by_n)
+            val = self._buffers(nprod)[1][1]
+            if nprod is None:
+                self.run('pfb_wgrid_prep', _dev.ptr(vis), _dev.ptr(wgt), _dev.ptr(self.idx), _dev.ptr(self.coord),
+                         self.nsorted, _dev.ptr(val))
+            else:
+                self.run('pfb_wgrid_prep_multi', nprod, _dev.ptr(vis), _dev.ptr(wgt), shared,
+                         _dev.ptr(self.idx), _dev.ptr(self.coord), self.nsorted, self.nvis, _dev.ptr(val))
+            return self._grid_all(val, None, divide_by_n, nprod)
 
     def dirty2vis(self, dirty, wgt=None, divide_by_n=True):
-        self._check('dirty', dirty, self.rdtype, (self.nx, self.ny))
-        self._check('wgt', wgt, self.rdtype, (self.nrow, self.nchan))
+        """vis (nrow, nchan) of dirty (nx, ny), or (nprod, nrow, nchan) of a stack dirty (nprod, nx, ny); wgt as in
+        vis2dirty."""
+        nprod, wgt, shared = self._stacked('dirty', dirty, (self.nx, self.ny), self.rdtype, wgt)
+        vshape = dirty.shape[:-2] + (self.nrow, self.nchan)
         if self.nsorted == 0:
-            return torch.zeros((self.nrow, self.nchan), dtype=self.cdtype, device=dirty.device)
-        vis = torch.empty((self.nrow, self.nchan), dtype=self.cdtype, device=dirty.device)
+            return torch.zeros(vshape, dtype=self.cdtype, device=dirty.device)
+        vis = torch.empty(vshape, dtype=self.cdtype, device=dirty.device)
+        dirty = dirty if nprod is None else dirty.contiguous()
         with self.lock:
-            acc = self._degrid_all(dirty, None, divide_by_n)
-            self.run('pfb_wgrid_finish', _dev.ptr(acc), _dev.ptr(wgt), _dev.ptr(self.idx), _dev.ptr(self.coord),
-                     self.nsorted, _dev.ptr(vis), self.nvis)
+            acc = self._degrid_all(dirty, None, divide_by_n, nprod)
+            if nprod is None:
+                self.run('pfb_wgrid_finish', _dev.ptr(acc), _dev.ptr(wgt), _dev.ptr(self.idx), _dev.ptr(self.coord),
+                         self.nsorted, _dev.ptr(vis), self.nvis)
+            else:
+                self.run('pfb_wgrid_finish_multi', nprod, _dev.ptr(acc), _dev.ptr(wgt), shared, _dev.ptr(self.idx),
+                         _dev.ptr(self.coord), self.nsorted, _dev.ptr(vis), self.nvis)
         return vis
 
     def dirty2vis_into(self, dirty, out, row0, chan0, accumulate=False, divide_by_n=True):
@@ -363,7 +425,11 @@ def vis2dirty(uvw, freq, vis, wgt=None, mask=None, npix_x=None, npix_y=None, pix
               center_x=0.0, center_y=0.0, epsilon=None, do_wgridding=None, divide_by_n=True,
               double_precision_accumulation=False, nthreads=1):
     """ducc0.wgridder.experimental.vis2dirty: dirty (npix_x, npix_y) in the real type of vis.  `nthreads` is accepted
-    and ignored.  double_precision_accumulation with complex64 input runs the fp64 kernels on the data cast up."""
+    and ignored.  double_precision_accumulation with complex64 input runs the fp64 kernels on the data cast up.
+
+    Beyond ducc0: vis (nprod, nrow, nchan), nprod <= 4 -- the Stokes products of utils.stokes.stokes_vis(product='IQUV')
+    -- gives dirty (nprod, npix_x, npix_y) under ONE plan and order, the one a 2-D call on the same arrays finds in the
+    cache; wgt is None, (nrow, nchan) for every plane, or (nprod, nrow, nchan)."""
     _check_flags(do_wgridding, epsilon, pixsize_x, pixsize_y)
     if npix_x is None or npix_y is None:
         raise TypeError("npix_x and npix_y are required")
@@ -385,15 +451,17 @@ def vis2dirty(uvw, freq, vis, wgt=None, mask=None, npix_x=None, npix_y=None, pix
 
 def dirty2vis(uvw, freq, dirty, wgt=None, mask=None, pixsize_x=None, pixsize_y=None, center_x=0.0, center_y=0.0,
               epsilon=None, do_wgridding=None, divide_by_n=True, nthreads=1):
-    """ducc0.wgridder.experimental.dirty2vis: vis (nrow, nchan) in the complex type of dirty, 0 where mask == 0."""
+    """ducc0.wgridder.experimental.dirty2vis: vis (nrow, nchan) in the complex type of dirty, 0 where mask == 0.
+    Beyond ducc0: dirty (nprod, nx, ny), nprod <= 4, gives vis (nprod, nrow, nchan); wgt as in vis2dirty."""
     _check_flags(do_wgridding, epsilon, pixsize_x, pixsize_y)
     dd = _dev.to_dev(dirty)
-    if dd.dtype not in _dev.CPLX_OF or dd.ndim != 2:
-        raise TypeError(f"dirty must be a 2-D float32 or float64 image, got {dd.dtype} {tuple(dd.shape)}")
+    if dd.dtype not in _dev.CPLX_OF or dd.ndim not in (2, 3):
+        raise TypeError(f"dirty must be a float32 or float64 image (nx, ny) or a stack (nprod, nx, ny) of them, got "
+                        f"{dd.dtype} {tuple(dd.shape)}")
     wd = _dev.to_dev(wgt)
     if wd is not None and wd.dtype != dd.dtype:
         raise TypeError(f"wgt must be {dd.dtype} like dirty, got {wd.dtype}")
-    nx, ny = dd.shape
+    nx, ny = dd.shape[-2:]
     plan = plan_for(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, dd.dtype)
     return _dev.host_like(plan.dirty2vis(dd, wd, divide_by_n), dirty)
 

@@ -4,7 +4,8 @@ workers do between reading a chunk and the `vis, wgt, mask` that the grid worker
 pfb/utils/weighting.py:281-350, pfb/utils/stokes2im.py:98-195; csrc/stokes.hip).
 
     stokes_basis   the 2 x 2 basis matrix B of (pol, product)
-    stokes_vis     vis, wgt, mask, wsum from the raw columns of a chunk, one kernel
+    stokes_vis     vis, wgt, mask, wsum from the raw columns of a chunk, one kernel: of one product, or of up to four
+                   ('IQUV') as leading planes from one pass over the columns
 
 The reference generates its per-visibility functions with sympy; they have the closed form
 
@@ -25,6 +26,8 @@ Where this differs from the reference, by definition:
   * a singular Jones matrix on an unflagged visibility gives IEEE inf / nan as in the reference; it is not an error;
   * a row with an antenna index outside the Jones term's antenna axis gets zeros (the reference: IndexError).
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -46,6 +49,38 @@ def basis_index(pol, product):
     except KeyError:
         raise ValueError(f"unknown polarisation type / product ({pol!r}, {product!r}): pol is 'linear' or 'circular', "
                          "product one of 'I', 'Q', 'U', 'V'") from None
+
+
+def product_letters(product):
+    """`product` as its letters: None for ONE product given as a one-letter string (the 2-D results of always), else
+    the tuple of letters of a stacked call -- a string of 2 to 4 letters ('IQUV', 'QU', 'VI') or a sequence of one-letter
+    strings (('U', 'I', 'Q'); a sequence of one letter is a stack of one plane) --, in the order asked.  No letters, more
+    than four and a repeated letter are a ValueError; what a letter means is basis_index's to say."""
+    if isinstance(product, str):
+        if len(product) == 1:
+            return None
+        letters = tuple(product)
+    else:
+        try:
+            letters = tuple(product)
+        except TypeError:
+            raise ValueError(f"product must be a string of letters from 'IQUV' or a sequence of them, got {product!r}") from None
+        if not all(isinstance(p, str) and len(p) == 1 for p in letters):
+            raise ValueError(f"a sequence of products holds one letter each, got {product!r}")
+    if not 1 <= len(letters) <= 4:
+        raise ValueError(f"1 to 4 products in one call, got {product!r}")
+    if len(set(letters)) != len(letters):
+        raise ValueError(f"a product is asked for twice in {product!r}")
+    return letters
+
+
+def basis_list(pol, product):
+    """The basis index of a single product, or the list of them -- one per plane, in the order asked -- of a stacked
+    one (product_letters)."""
+    letters = product_letters(product)
+    if letters is None:
+        return basis_index(pol, product)
+    return [basis_index(pol, p) for p in letters]
 
 
 def stokes_basis(pol, product):
@@ -92,8 +127,10 @@ def run(data, weight, wform, flag, frow, autocorr, jones, tbin_idx, tbin_counts,
         subtract=False):
     """The one launch.  Device tensors of their final types in: data, data2 complex (nrow, nchan, 2 | 4); weight real per
     wform; flag uint8 (nrow, nchan) or (nrow, nchan, ncorr) or None; frow uint8 (nrow,) or None; jones
-    (ntime, nant, nchan, ndir, 2[, 2]) or None.  Returns vis, wgt, mask (nrow, nchan) and the fp64 one-element sum of the
-    unflagged wgt, all on the device; nothing is read back."""
+    (ntime, nant, nchan, ndir, 2[, 2]) or None.  `basis` is a basis index -- vis, wgt, mask (nrow, nchan) and the fp64
+    one-element sum of the unflagged wgt -- or a list of nprod distinct ones (basis_list): vis, wgt (nprod, nrow, nchan),
+    the planes in the list's order, mask (nrow, nchan) and nprod sums, from one pass over the inputs.  All on the device;
+    nothing is read back."""
     if data.ndim != 3 or data.dtype not in _dev.REAL_OF:
         raise TypeError("data must be complex64 or complex128 of shape (nrow, nchan, ncorr)")
     rdt = _dev.REAL_OF[data.dtype]
@@ -128,16 +165,24 @@ def run(data, weight, wform, flag, frow, autocorr, jones, tbin_idx, tbin_counts,
     a1, a2 = (_dev.to_dev(a).to(torch.int32) for a in (ant1, ant2))
     if tuple(a1.shape) != (nrow,) or tuple(a2.shape) != (nrow,):
         raise ValueError(f"ant1 and ant2 must have shape ({nrow},)")
-    vis = torch.empty((nrow, nchan), dtype=data.dtype, device=dev)
-    wgt = torch.empty((nrow, nchan), dtype=rdt, device=dev)
+    # one product: (nrow, nchan) through pfb_stokes_vis; a list of them: a leading axis through pfb_stokes_vis_multi
+    stacked = isinstance(basis, (list, tuple))
+    lead = (len(basis),) if stacked else ()
+    vis = torch.empty(lead + (nrow, nchan), dtype=data.dtype, device=dev)
+    wgt = torch.empty(lead + (nrow, nchan), dtype=rdt, device=dev)
     mask = torch.empty((nrow, nchan), dtype=torch.uint8, device=dev)
-    rec = torch.zeros(1, dtype=torch.float64, device=dev)
+    rec = torch.zeros(len(basis) if stacked else 1, dtype=torch.float64, device=dev)
     if nrow * nchan:
         data, data2 = _aligned(data, 2 * esize * nc), _aligned(data2, 2 * esize * nc)
         weight = None if wform == W_NONE else _aligned(weight, esize * nc)
         flag = _aligned(flag, nfc) if nfc > 1 else flag
-        _lib.check(_lib.load().pfb_stokes_vis(
-            _dev.code(rdt), mode, basis, _dev.ptr(data), _dev.ptr(data2), int(bool(subtract)), _dev.ptr(weight), wform,
+        lib = _lib.load()
+        if stacked:
+            entry, which = lib.pfb_stokes_vis_multi, (len(basis), (C.c_int * len(basis))(*basis))
+        else:
+            entry, which = lib.pfb_stokes_vis, (basis,)
+        _lib.check(entry(
+            _dev.code(rdt), mode, *which, _dev.ptr(data), _dev.ptr(data2), int(bool(subtract)), _dev.ptr(weight), wform,
             _dev.ptr(flag), nfc, _dev.ptr(frow), int(bool(autocorr)), _dev.ptr(jones), ndir, ti.numel(), nant,
             _dev.ptr(ti), _dev.ptr(tc), off, _dev.ptr(a1), _dev.ptr(a2), nrow, nchan, _dev.ptr(vis), _dev.ptr(wgt),
             _dev.ptr(mask), _dev.ptr(rec), _dev.ptr(_dev.scratch()[0]), _dev.stream()))
@@ -160,12 +205,17 @@ def stokes_vis(data, ant1, ant2, tbin_idx, tbin_counts, poltype, product, data2=
     vis (nrow, nchan) complex and wgt (nrow, nchan) real of `precision`; mask = (~flag) as uint8; wsum the sum of wgt
     over unflagged visibilities, accumulated in fp64, as a one-element array of wgt's type.  Flagged visibilities and
     rows that no time bin covers get vis = wgt = 0, whatever their data hold.  Differences from the reference: see the
-    module."""
+    module.
+
+    Several products in one pass (the reference has none: its fastim worker refuses anything but one letter): `product`
+    a string of 2 to 4 distinct letters ('IQUV', 'QU', 'VI') or a sequence of letters gives vis and wgt
+    (nprod, nrow, nchan), the planes in the order asked, mask (nrow, nchan) -- it does not depend on the product -- and
+    wsum (nprod,).  Every input is read once.  A repeated or unknown letter is a ValueError."""
     if str(precision).lower() not in _PRECISION:
         raise ValueError(f"precision must be 'single' or 'double', got {precision!r}")
     cdt = _PRECISION[str(precision).lower()]
     rdt = _dev.REAL_OF[cdt]
-    basis = basis_index(poltype, product)
+    basis = basis_list(poltype, product)
     dd = _dev.to_dev(data)
     if dd.ndim != 3 or not dd.is_complex():
         raise TypeError("data must be complex of shape (nrow, nchan, ncorr)")

@@ -203,8 +203,11 @@ def _weight_data(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, p
     place; here on read); the time bins must be ascending and must not overlap, else ValueError (tbin_idx and tbin_counts
     are index metadata of ntime entries and are read on the host for that check); an unknown pol, product or nc, and
     FULL Jones terms with 2 correlations, are a ValueError (the reference: NameError / IndexError); a singular Jones
-    matrix on an unflagged visibility gives IEEE inf / nan, as in the reference."""
-    basis = _stokes.basis_index(pol, product)
+    matrix on an unflagged visibility gives IEEE inf / nan, as in the reference.
+
+    A `product` of several letters ('IQUV', 'QU', a sequence of letters: utils/stokes.py) gives vis and wgt
+    (nprod, nrow, nchan), the planes in the order asked, from one pass over the inputs."""
+    basis = _stokes.basis_list(pol, product)
     n = _stokes.ncorr_of(nc)
     dd = _dev.to_dev(data)
     if dd.ndim != 3 or dd.shape[2] != n:
