@@ -860,6 +860,23 @@ int pfb_imw_l2_weights(int dtype, const void* residual_vis, const unsigned char*
 /* rec[0] = sum of wgt where mask != 0, in fp64. */
 int pfb_imw_wsum(int dtype, const void* wgt, const unsigned char* mask, size_t nvis, double* rec, double* work,
                  void* stream);
+/* Planes (Stokes products) of one pfb_imw_residual_weigh call. */
+#define PFB_IMW_MAX_PROD 4
+/* The three passes between the stages of a fastim chunk in one (stokes2im.py:268, 279-295), IN PLACE on
+ * nprod (1 .. PFB_IMW_MAX_PROD) planes of nvis visibilities each, vis (nprod, nvis) complex and wgt (nprod, nvis) real of
+ * `dtype`:
+ *   vis[p, i] = (vis[p, i] - model_vis[model_of[p], i]) * mask[i]   for the planes with model_of[p] >= 0; a plane with
+ *     model_of[p] < 0 is not touched.  model_of: nprod ints on the HOST, read before the call returns; model_vis
+ *     (nmodel, nvis) complex of `dtype`, NULL with nmodel == 0; every model_of[p] < nmodel;
+ *   wgt[p, i] = wgt[p, i] * imwgt[i]   the product formed in fp64 and rounded once to `dtype` (numpy's in-place multiply
+ *     of a float32 array by a float64 one); imwgt: nvis DOUBLES whatever `dtype`, one plane for all products; NULL
+ *     leaves wgt as it is;
+ *   rec[p] = sum of wgt[p, i] over mask[i] != 0, of the weights as stored, accumulated in fp64: nprod device doubles.
+ * work: PFB_IMW_WORK_DOUBLES doubles of scratch; a fixed order, no atomics: the same bits from run to run.  nvis == 0
+ * launches nothing and clears rec.  vis, wgt, model_vis, imwgt and mask must not overlap. */
+int pfb_imw_residual_weigh(int dtype, int nprod, void* vis, const void* model_vis, int nmodel, const int* model_of,
+                           const unsigned char* mask, const double* imwgt, size_t nvis, void* wgt, double* rec,
+                           double* work, void* stream);
 
 /* ---------------------------------------------------------------- Stokes visibilities and weights
  * pfb/utils/weighting.py:281-350 (_weight_data over the functions pfb/utils/stokes.py generates) with the preparation

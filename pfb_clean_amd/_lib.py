@@ -151,6 +151,8 @@ SIGNATURES = {
     'pfb_imw_l2_residual': (_i, [_i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     'pfb_imw_l2_weights': (_i, [_i, _vp, _vp, _vp, _sz, _d, _vp, _vp, _vp, _vp]),
     'pfb_imw_wsum': (_i, [_i, _vp, _vp, _sz, _vp, _vp, _vp]),
+    # the fastim chunk's residual, weight product and weight sums in one pass (stokes2im.py:268, 279-295)
+    'pfb_imw_residual_weigh': (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     # Stokes visibilities and weights from correlations and Jones terms (weighting.py:281-350, stokes2im.py:98-195)
     'pfb_stokes_vis': (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, C.c_longlong,
                             _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

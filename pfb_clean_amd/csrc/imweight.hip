@@ -13,6 +13,8 @@
 //   k_l2_residual   residual_vis = (vis - model_vis) * mask with sum |residual_vis|^2 and sum mask
 //   k_l2_weights    the Student-t weights (dof + 1) / (dof + |r|^2 / ovar) / ovar [* imwgt] with their masked sum
 //   k_wsum          sum wgt[mask != 0]
+//   k_residual_weigh  the fastim chunk's three passes between its stages in one (stokes2im.py:268, 279-295, DESIGN
+//                   4.15): vis = (vis - model_vis) * mask on the planes that have a model, wgt *= imwgt, sum wgt[mask != 0]
 // The grid coordinate of a visibility is formed as the reference forms it -- freq / c, u * that, (. + umax) / u_cell, in
 // fp64, every operation rounded on its own (no contraction) -- so that cell indices are the reference's bit for bit.
 // u_cell and umax come from the host, which evaluates the reference's expressions in Python floats.
@@ -184,6 +186,46 @@ k_wsum(const T* __restrict__ wgt, const u8* __restrict__ mask, size_t n, double*
     emit_partials<1>(acc, ws);
 }
 
+// ------------------------------------------------------------------------------------------- the fastim chunk
+// plane p of vis has model plane m[p], or none (m[p] < 0)
+constexpr int IMW_RW_MAX_PROD = 4;
+struct RwMap { int m[IMW_RW_MAX_PROD]; };
+
+// NP planes of n visibilities, in place: vis[p] = (vis[p] - model_vis[m[p]]) * mask where m[p] >= 0, wgt[p] = (T)((double)
+// wgt[p] * imwgt) where imwgt is given -- the product in fp64, rounded once --, and [sum wgt[p][mask != 0]], p < NP, of the
+// weights as stored.  A lane loads one complex (8 or 16 bytes) per plane and element: a wave reads whole cache lines.
+// mask and imwgt are read once for all planes.  m[] and the imwgt test are uniform: no lane diverges but on mask
+template <typename T, int NP>
+__global__ void __launch_bounds__(IMW_BLOCK)
+k_residual_weigh(cplx<T>* __restrict__ vis, const cplx<T>* __restrict__ model_vis, RwMap map,
+                 const u8* __restrict__ mask, const double* __restrict__ imwgt, size_t n, T* __restrict__ wgt,
+                 double* __restrict__ ws) {
+#pragma clang fp contract(off)
+    double acc[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p] = 0.0;
+    for (size_t i = (size_t)blockIdx.x * IMW_BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * IMW_BLOCK) {
+        const u8 mk = mask[i];
+        const T f = (T)mk;
+        const double g = imwgt ? imwgt[i] : 1.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const size_t e = (size_t)p * n + i;
+            if (map.m[p] >= 0) {
+                const cplx<T> v = vis[e], m = model_vis[(size_t)map.m[p] * n + i];
+                vis[e] = cplx<T>((v.x - m.x) * f, (v.y - m.y) * f);
+            }
+            T w = wgt[e];
+            if (imwgt) {
+                w = (T)((double)w * g);
+                wgt[e] = w;
+            }
+            if (mk) acc[p] += (double)w;
+        }
+    }
+    emit_partials<NP>(acc, ws);
+}
+
 // ------------------------------------------------------------------------------------------------------ launchers
 // the streaming sums: at most IMW_MAX_GROUPS workgroups stride over the array
 constexpr int IMW_MAX_GROUPS = PFB_IMW_WORK_DOUBLES / PFB_IMW_RECORD;
@@ -191,6 +233,9 @@ static inline size_t imw_stream_threads(size_t n) {
     const size_t cap = (size_t)IMW_MAX_GROUPS * IMW_BLOCK;
     return n < cap ? n : cap;
 }
+// k_residual_weigh leaves up to IMW_RW_MAX_PROD partials per workgroup in the same scratch
+constexpr int IMW_RW_MAX_GROUPS = PFB_IMW_WORK_DOUBLES / IMW_RW_MAX_PROD;
+static_assert(IMW_RW_MAX_PROD == PFB_IMW_MAX_PROD, "the header states the planes of pfb_imw_residual_weigh");
 static int imw_geom(const char* name, int nx, int ny, double u_cell, double umax, double v_cell, double vmax, ImwGeom& g) {
     PFB_REQUIRE(nx >= 1 && ny >= 1 && (size_t)nx * (size_t)ny <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED,
                 "%s: grid %d x %d outside [1, 2^31) cells", name, nx, ny);
@@ -296,6 +341,39 @@ int pfb_imw_wsum(int dtype, const void* wgt, const unsigned char* mask, size_t n
         return launch_groups(k_wsum<decltype(t)>, groups, stream, wgt, mask, nvis, work);
     });
     return rc != PFB_OK ? rc : final_sum(work, groups, 1, rec, stream);
+}
+
+int pfb_imw_residual_weigh(int dtype, int nprod, void* vis, const void* model_vis, int nmodel, const int* model_of,
+                           const unsigned char* mask, const double* imwgt, size_t nvis, void* wgt, double* rec,
+                           double* work, void* stream) {
+    if (int rc = check(dtype, "imw_residual_weigh", {{vis, CPLX}, {model_vis, CPLX, true}, {mask, U8}, {imwgt, F64, true},
+                                                     {wgt, REAL}, {rec, F64}, {work, F64}});
+        rc != PFB_OK) return rc;
+    PFB_REQUIRE(nprod >= 1 && nprod <= IMW_RW_MAX_PROD, PFB_ERR_INVALID, "imw_residual_weigh: %d planes outside 1 .. %d",
+                nprod, IMW_RW_MAX_PROD);
+    PFB_REQUIRE(model_of && nmodel >= 0 && nmodel <= IMW_RW_MAX_PROD && (nmodel == 0 || model_vis), PFB_ERR_INVALID,
+                "imw_residual_weigh: %d model planes need a table and, above 0, model_vis; at most %d", nmodel,
+                IMW_RW_MAX_PROD);
+    RwMap map;
+    for (int p = 0; p < IMW_RW_MAX_PROD; ++p) {
+        map.m[p] = p < nprod && model_of[p] >= 0 ? model_of[p] : -1;
+        PFB_REQUIRE(map.m[p] < nmodel, PFB_ERR_INVALID, "imw_residual_weigh: plane %d reads model plane %d of %d", p,
+                    map.m[p], nmodel);
+    }
+    PFB_REQUIRE(nvis <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED, "imw_residual_weigh: %zu elements outside [0, 2^31)", nvis);
+    if (nvis == 0) {            // nothing to launch: the sums of no weights
+        PFB_HIP_CHECK(hipMemsetAsync(rec, 0, (size_t)nprod * sizeof(double), as_stream(stream)));
+        return PFB_OK;
+    }
+    const size_t cap = (size_t)IMW_RW_MAX_GROUPS * IMW_BLOCK;
+    const unsigned groups = blocks(nvis < cap ? nvis : cap);
+    const int rc = by_type(dtype, [&](auto t) {
+        return by_int<1, IMW_RW_MAX_PROD>(nprod, [&](auto np) {
+            return launch_groups(k_residual_weigh<decltype(t), np()>, groups, stream, vis, model_vis, map, mask, imwgt,
+                                 nvis, wgt, work);
+        });
+    });
+    return rc != PFB_OK ? rc : final_sum(work, groups, nprod, rec, stream);
 }
 
 }  // extern "C"
