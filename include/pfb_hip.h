@@ -927,6 +927,21 @@ int pfb_stokes_vis_multi(int dtype, int mode, int nprod, const int* basis, const
                          const long long* tbin_idx, const long long* tbin_counts, long long tbin_off, const int* ant1,
                          const int* ant2, size_t nrow, int nchan, void* vis, void* wgt, unsigned char* mask, double* wsum,
                          double* work, void* stream);
+/* Channel averaging (what africanus.averaging.time_and_channel does for pfb/utils/stokes2vis.py:174-203 with
+ * time_bin_secs -> 0) of vis complex and wgt real (nprod, nrow, nchan), nprod = 1 .. 4, with their one mask (nrow, nchan),
+ * as the two entry points above leave them.  With n = chan_average >= 1, nchan_out = ceil(nchan / n); bin j of a row
+ * covers its channels [j n, min((j + 1) n, nchan)).  Per row, bin and plane, over the bin's LIVE samples (mask != 0) in
+ * channel order:
+ *     wgt_out = sum wgt_i    vis_out = sum wgt_i vis_i / wgt_out, exactly 0 where wgt_out == 0    mask_out = any(mask_i)
+ * Samples that are not live are selected out, never multiplied by zero: what a masked sample holds reaches no output.  A
+ * product wgt_i vis_i is formed in `dtype`, the sums in fp64 and rounded to `dtype` once, in front of the division.
+ * Out: viso, wgto (nprod, nrow, nchan_out), masko (nrow, nchan_out), wsum[k], k < nprod, the fp64 sum of plane k's wgt_out
+ * over mask_out != 0 (work: PFB_REDUCE_WS_DOUBLES doubles of scratch).  A fixed order, no atomics: the same bits from
+ * run to run.  The outputs must not overlap the inputs.  PFB_ERR_INVALID: nprod outside 1 .. 4, chan_average < 1, a null
+ * or misaligned array; PFB_ERR_UNSUPPORTED: nrow or nchan outside [1, 2^31); nothing is written. */
+int pfb_chan_average(int dtype, int nprod, const void* vis, const void* wgt, const unsigned char* mask, size_t nrow,
+                     int nchan, int chan_average, void* viso, void* wgto, unsigned char* masko, double* wsum,
+                     double* work, void* stream);
 
 /* ------------------------------------------------ band / time concatenation and beam resampling
  * The grid worker's merge of its input datasets (pfb/workers/grid.py:150-214, 404-412): sum_overlap and _sum_beam of

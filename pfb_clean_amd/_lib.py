@@ -159,6 +159,8 @@ SIGNATURES = {
     # ... for up to four products in one pass (nprod and a host array of basis indices in the place of basis)
     'pfb_stokes_vis_multi': (_i, [_i, _i, _i, C.POINTER(_i), _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp,
                                   _vp, C.c_longlong, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the weighted mean of vis, wgt, mask over bins of chan_average channels (stokes2vis.py:174-203)
+    'pfb_chan_average': (_i, [_i, _i, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     # the w-gridder with a product axis: nprod after the plan, (wgt, wgt_shared) for wgt, nvis for prep
     'pfb_wgrid_prep_multi': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _sz, _vp, _vp]),
     'pfb_wgrid_finish_multi': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _sz, _vp]),

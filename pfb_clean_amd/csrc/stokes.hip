@@ -10,8 +10,10 @@
 //              the unflagged wgt (a partial per workgroup, then k_final_sum of common.hpp: the same bits every run).
 //   k_stokes_multi   the same pass for up to four products at once: every input of a visibility is read once, product k
 //              lands in plane k of vis and wgt (nprod, nrow, nchan); what the bases share is formed once
-// Templated on the type, the Jones mode (diagonal with 4 or 2 correlations, full 2 x 2 with 4, none with 4 or 2) and the
-// basis; the weight form, the flags and the second column are uniform branches.
+//   k_chan_average, k_chan_average_lane   the weighted mean of vis, wgt, mask over bins of chan_average channels, a pass
+//              of its own behind the ones above
+// The Stokes kernels are templated on the type, the Jones mode (diagonal with 4 or 2 correlations, full 2 x 2 with 4,
+// none with 4 or 2) and the basis; the weight form, the flags and the second column are uniform branches.
 //
 // A workgroup takes STK_BLOCK / nchan whole rows at a time (one row when nchan > STK_BLOCK): its first lanes find their
 // row's time bin by a binary search over tbin_idx and leave (bin, ant1, ant2) in LDS, then every lane takes visibilities
@@ -419,6 +421,159 @@ k_stokes_multi(StkMultiArgs ma) {
     emit_partials<STK_MAX_PROD>(part, a.ws);
 }
 
+// -------------------------------------------------------------------------------------------- channel averaging
+// DESIGN 4.16.  With n = chan_average, bin j of a row covers its channels [j n, min((j + 1) n, nchan)), nout =
+// ceil(nchan / n) bins; per row, bin and product plane, over the bin's LIVE samples (mask != 0) in channel order:
+//     wgt_out = sum wgt_i     vis_out = sum wgt_i vis_i / wgt_out, exactly 0 where wgt_out == 0     mask_out = any(mask_i)
+// The samples that are not live are selected out, never multiplied by zero: what a masked sample holds is not read into a
+// sum (an unflagged sample that no time bin covers has mask 1 and vis = wgt = 0, and adds its zeros).  A product
+// wgt_i vis_i is formed in T and rounded on its own (no fused multiply-add, so that both kernels give the same bits);
+// the sums run in fp64 in channel order -- an order that depends on the shapes only: the same bits every run -- and are
+// rounded to T once, in front of the division.
+//   k_chan_average        STK_AVG_LANE_MAX < n <= STK_BLOCK: the lanes take consecutive (row, channel) samples, as in k_stokes, so the loads
+//                         are coalesced; they leave wgt vis, wgt and the mask byte in LDS -- 3 T per lane and plane, 24 KB
+//                         for four fp64 planes -- and after one barrier the first lanes sum a bin each, divide and store.
+//                         nchan <= STK_BLOCK / 2: a workgroup holds whole rows, so a bin never leaves it.  Else it
+//                         strides over its one row in stretches of floor(STK_BLOCK / n) n channels, so that no bin
+//                         straddles a stretch
+//   k_chan_average_lane   any n: a lane per (row, bin), which walks its n channels.  Launched for n <= STK_AVG_LANE_MAX,
+//                         where a lane's n samples fill whole 32-byte sectors and the barriers of the other kernel cost
+//                         more than its coalescing gains (DESIGN 4.16 has the figures), and for n > STK_BLOCK
+
+// the largest chan_average of the lane-per-bin kernel below STK_BLOCK (measured at 4 and 16 only)
+constexpr int STK_AVG_LANE_MAX = 4;
+
+__device__ __forceinline__ float stk_mul_rn(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ double stk_mul_rn(double a, double b) { return __dmul_rn(a, b); }
+
+// the sums of a bin and what its lane does with them: round, divide, store, and the fp64 sum of wgt_out over
+// mask_out != 0
+template <typename T>
+struct StkBinSum {
+    double vx = 0.0, vy = 0.0, w = 0.0;
+    // a live sample: its wgt vis (formed in T) and its wgt
+    __device__ __forceinline__ void add(T wvx, T wvy, T wgt) { vx += (double)wvx; vy += (double)wvy; w += (double)wgt; }
+    __device__ __forceinline__ void store(bool any_mask, cplx<T>* __restrict__ vis, T* __restrict__ wgt, size_t o,
+                                          double& acc) const {
+        const T sw = (T)w, sx = (T)vx, sy = (T)vy;
+        vis[o] = sw == T(0) ? cplx<T>(T(0), T(0)) : cplx<T>(sx / sw, sy / sw);
+        wgt[o] = sw;
+        acc += any_mask ? (double)sw : 0.0;
+    }
+};
+
+struct AvgArgs {
+    const void* vis; const void* wgt; const u8* mask;
+    size_t nrow, nbins, ngroups;       // nbins = nrow nout
+    int nprod, nchan, nout, n, rows_per_group;
+    void* viso; void* wgto; u8* masko;
+    double* ws;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(STK_BLOCK)
+k_chan_average(AvgArgs a) {
+    __shared__ T s_vx[STK_MAX_PROD][STK_BLOCK], s_vy[STK_MAX_PROD][STK_BLOCK], s_w[STK_MAX_PROD][STK_BLOCK];
+    __shared__ u8 s_m[STK_BLOCK];
+    const cplx<T>* __restrict__ vis = static_cast<const cplx<T>*>(a.vis);
+    const T* __restrict__ wgt = static_cast<const T*>(a.wgt);
+    cplx<T>* __restrict__ viso = static_cast<cplx<T>*>(a.viso);
+    T* __restrict__ wgto = static_cast<T*>(a.wgto);
+    const unsigned nchan = (unsigned)a.nchan, navg = (unsigned)a.n, nout = (unsigned)a.nout;
+    const size_t plane_in = a.nrow * (size_t)nchan;
+    const bool one_row = a.rows_per_group == 1;
+    // the channels a pass of the workgroup takes: whole rows, or whole bins of its one row
+    const unsigned width = one_row ? STK_BLOCK / navg * navg : nchan;
+    double acc[STK_MAX_PROD] = {0.0, 0.0, 0.0, 0.0};
+    for (size_t g = blockIdx.x; g < a.ngroups; g += gridDim.x) {
+        const size_t r0 = g * (size_t)a.rows_per_group;
+        const unsigned nr = (unsigned)(a.nrow - r0 < (size_t)a.rows_per_group ? a.nrow - r0 : (size_t)a.rows_per_group);
+        for (unsigned c0 = 0; c0 < nchan; c0 += width) {        // one pass unless one_row; uniform over the workgroup
+            __syncthreads();                                    // the bins' readers of the pass before
+            // the samples of this pass: nr whole rows, or channels [c0, c0 + len) of the one row
+            const unsigned len = nchan - c0 < width ? nchan - c0 : width;
+            const unsigned nin = one_row ? len : nr * nchan;    // <= STK_BLOCK
+            if (threadIdx.x < nin) {
+                const unsigned i = threadIdx.x;
+                const unsigned lr = one_row ? 0u : i / nchan;
+                const unsigned chan = one_row ? c0 + i : i - lr * nchan;
+                const size_t t = (r0 + lr) * nchan + chan;
+                const u8 m = a.mask[t];
+                s_m[i] = m;
+                if (m) {
+#pragma unroll
+                    for (int k = 0; k < STK_MAX_PROD; ++k) {
+                        if (k >= a.nprod) break;
+                        const T w = wgt[(size_t)k * plane_in + t];
+                        const cplx<T> v = vis[(size_t)k * plane_in + t];
+                        s_vx[k][i] = stk_mul_rn(w, v.x);
+                        s_vy[k][i] = stk_mul_rn(w, v.y);
+                        s_w[k][i] = w;
+                    }
+                }
+            }
+            __syncthreads();
+            // the bins of this pass, a lane each: of nr rows (nout each), or the ceil(len / n) of the stretch
+            const unsigned per_row = one_row ? (len + navg - 1) / navg : nout;
+            const unsigned nb = one_row ? per_row : nr * nout;  // <= nin
+            if (threadIdx.x < nb) {
+                const unsigned lr = threadIdx.x / per_row, j = threadIdx.x - lr * per_row;
+                const unsigned row_len = one_row ? len : nchan;
+                const unsigned i0 = lr * row_len + j * navg;
+                const unsigned i1 = lr * row_len + (row_len - j * navg < navg ? row_len : (j + 1) * navg);
+                const size_t o = (r0 + lr) * nout + (one_row ? c0 / navg : 0u) + j;
+                bool any_mask = false;
+                for (unsigned i = i0; i < i1; ++i) any_mask = any_mask || s_m[i] != 0;
+                a.masko[o] = any_mask ? 1 : 0;
+#pragma unroll
+                for (int k = 0; k < STK_MAX_PROD; ++k) {
+                    if (k >= a.nprod) break;
+                    StkBinSum<T> sum;
+                    for (unsigned i = i0; i < i1; ++i) {
+                        if (s_m[i]) sum.add(s_vx[k][i], s_vy[k][i], s_w[k][i]);
+                    }
+                    sum.store(any_mask, viso, wgto, (size_t)k * a.nbins + o, acc[k]);
+                }
+            }
+        }
+    }
+    emit_partials<STK_MAX_PROD>(acc, a.ws);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(STK_BLOCK)
+k_chan_average_lane(AvgArgs a) {
+    const cplx<T>* __restrict__ vis = static_cast<const cplx<T>*>(a.vis);
+    const T* __restrict__ wgt = static_cast<const T*>(a.wgt);
+    cplx<T>* __restrict__ viso = static_cast<cplx<T>*>(a.viso);
+    T* __restrict__ wgto = static_cast<T*>(a.wgto);
+    const size_t nout = (size_t)a.nout, nchan = (size_t)a.nchan, n = (size_t)a.n;
+    const size_t plane_in = a.nrow * nchan;
+    double acc[STK_MAX_PROD] = {0.0, 0.0, 0.0, 0.0};
+    for (size_t b = (size_t)blockIdx.x * STK_BLOCK + threadIdx.x; b < a.nbins; b += (size_t)gridDim.x * STK_BLOCK) {
+        const size_t r = b / nout, j = b - r * nout;
+        const size_t c0 = j * n, c1 = nchan - c0 < n ? nchan : c0 + n;
+        const size_t t0 = r * nchan;
+        bool any_mask = false;
+        for (size_t c = c0; c < c1; ++c) any_mask = any_mask || a.mask[t0 + c] != 0;
+        a.masko[b] = any_mask ? 1 : 0;
+#pragma unroll
+        for (int k = 0; k < STK_MAX_PROD; ++k) {
+            if (k >= a.nprod) break;
+            StkBinSum<T> sum;
+            for (size_t c = c0; c < c1; ++c) {
+                if (a.mask[t0 + c] == 0) continue;
+                const size_t t = (size_t)k * plane_in + t0 + c;
+                const T w = wgt[t];
+                const cplx<T> v = vis[t];
+                sum.add(stk_mul_rn(w, v.x), stk_mul_rn(w, v.y), w);
+            }
+            sum.store(any_mask, viso, wgto, (size_t)k * a.nbins + b, acc[k]);
+        }
+    }
+    emit_partials<STK_MAX_PROD>(acc, a.ws);
+}
+
 // the checks and the kernel record that both entry points share; vis, wgt: plane 0 of the outputs
 static int stk_setup(const char* name, int dtype, int mode, const void* data, const void* data2, int subtract,
                      const void* weight, int wform, const unsigned char* flag, int nflagcorr, const unsigned char* frow,
@@ -512,6 +667,34 @@ int pfb_stokes_vis_multi(int dtype, int mode, int nprod, const int* basis, const
         return by_int<0, PFB_STOKES_NOJ2>(mode, [&](auto m) {
             return launch_groups(k_stokes_multi<decltype(t), m()>, groups, stream, ma);
         });
+    });
+    return rc != PFB_OK ? rc : final_sum(work, (int)groups, nprod, wsum, stream);
+}
+
+int pfb_chan_average(int dtype, int nprod, const void* vis, const void* wgt, const unsigned char* mask, size_t nrow,
+                     int nchan, int chan_average, void* viso, void* wgto, unsigned char* masko, double* wsum,
+                     double* work, void* stream) {
+    PFB_REQUIRE(nprod >= 1 && nprod <= STK_MAX_PROD, PFB_ERR_INVALID, "chan_average: %d products outside 1 .. %d", nprod,
+                STK_MAX_PROD);
+    PFB_REQUIRE(chan_average >= 1, PFB_ERR_INVALID, "chan_average: chan_average %d < 1", chan_average);
+    if (int rc = check(dtype, "chan_average", {{vis, CPLX}, {wgt, REAL}, {mask, U8}, {viso, CPLX}, {wgto, REAL},
+                                               {masko, U8}, {wsum, F64}, {work, F64}});
+        rc != PFB_OK) return rc;
+    PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow <= (size_t)0x7fffffff, PFB_ERR_UNSUPPORTED,
+                "chan_average: %zu rows x %d channels outside [1, 2^31) each", nrow, nchan);
+    AvgArgs a;
+    a.vis = vis; a.wgt = wgt; a.mask = mask; a.nrow = nrow; a.nprod = nprod; a.nchan = nchan; a.n = chan_average;
+    a.nout = (int)(((long long)nchan + chan_average - 1) / chan_average);
+    a.nbins = nrow * (size_t)a.nout;
+    a.rows_per_group = nchan >= STK_BLOCK ? 1 : STK_BLOCK / nchan;
+    a.ngroups = (nrow + (size_t)a.rows_per_group - 1) / (size_t)a.rows_per_group;
+    a.viso = viso; a.wgto = wgto; a.masko = masko; a.ws = work;
+    const bool lane = chan_average <= STK_AVG_LANE_MAX || chan_average > STK_BLOCK;
+    const size_t need = lane ? (a.nbins + STK_BLOCK - 1) / STK_BLOCK : a.ngroups;
+    const size_t groups = need < (size_t)STK_MULTI_MAX_GROUPS ? need : (size_t)STK_MULTI_MAX_GROUPS;
+    const int rc = by_type(dtype, [&](auto t) {
+        return lane ? launch_groups(k_chan_average_lane<decltype(t)>, groups, stream, a)
+                    : launch_groups(k_chan_average<decltype(t)>, groups, stream, a);
     });
     return rc != PFB_OK ? rc : final_sum(work, (int)groups, nprod, wsum, stream);
 }

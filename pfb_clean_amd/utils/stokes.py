@@ -5,7 +5,10 @@ pfb/utils/weighting.py:281-350, pfb/utils/stokes2im.py:98-195; csrc/stokes.hip, 
 
     stokes_basis   the 2 x 2 basis matrix B of (pol, product)
     stokes_vis     vis, wgt, mask, wsum from the raw columns of a chunk, one kernel: of one product, or of up to four
-                   ('IQUV') as leading planes from one pass over the columns
+                   ('IQUV') as leading planes from one pass over the columns; chan_average=n then averages bins of n
+                   channels on the device
+    average_channels   that averaging of vis, wgt, mask that exist (a dataset an earlier run converted)
+    average_freq   the averaged channels' frequencies and widths, on the host
 
 The reference generates its per-visibility functions with sympy; they have the closed form
 
@@ -123,14 +126,43 @@ def _time_bins(tbin_idx, tbin_counts, dev):
     return torch.from_numpy(ti).to(dev), torch.from_numpy(tc).to(dev), int(ti[0])
 
 
+def check_chan_average(n):
+    """chan_average as an int >= 1; anything else: ValueError."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"chan_average must be an integer >= 1, got {n!r}")
+    if n > 0x7fffffff:
+        raise ValueError(f"chan_average {n} does not fit an int; one bin takes chan_average >= nchan")
+    return int(n)
+
+
+def _average_dev(vis, wgt, mask, n):
+    """pfb_chan_average on device tensors of their final types: vis, wgt ([nprod,] nrow, nchan), mask (nrow, nchan) ->
+    vis, wgt ([nprod,] nrow, nchan_out), mask (nrow, nchan_out) and the fp64 sums, one per plane."""
+    lead = tuple(vis.shape[:-2])
+    nrow, nchan = (int(k) for k in vis.shape[-2:])
+    nout = -(-nchan // n)
+    nprod = lead[0] if lead else 1
+    viso = torch.empty(lead + (nrow, nout), dtype=vis.dtype, device=vis.device)
+    wgto = torch.empty(lead + (nrow, nout), dtype=wgt.dtype, device=vis.device)
+    masko = torch.empty((nrow, nout), dtype=torch.uint8, device=vis.device)
+    rec = torch.zeros(nprod, dtype=torch.float64, device=vis.device)
+    if nrow * nchan:
+        _lib.check(_lib.load().pfb_chan_average(
+            _dev.code(wgt.dtype), nprod, _dev.ptr(vis), _dev.ptr(wgt), _dev.ptr(mask), nrow, nchan, n, _dev.ptr(viso),
+            _dev.ptr(wgto), _dev.ptr(masko), _dev.ptr(rec), _dev.ptr(_dev.scratch()[0]), _dev.stream()))
+    return viso, wgto, masko, rec
+
+
 def run(data, weight, wform, flag, frow, autocorr, jones, tbin_idx, tbin_counts, ant1, ant2, basis, data2=None,
-        subtract=False):
+        subtract=False, chan_average=1):
     """The one launch.  Device tensors of their final types in: data, data2 complex (nrow, nchan, 2 | 4); weight real per
     wform; flag uint8 (nrow, nchan) or (nrow, nchan, ncorr) or None; frow uint8 (nrow,) or None; jones
     (ntime, nant, nchan, ndir, 2[, 2]) or None.  `basis` is a basis index -- vis, wgt, mask (nrow, nchan) and the fp64
     one-element sum of the unflagged wgt -- or a list of nprod distinct ones (basis_list): vis, wgt (nprod, nrow, nchan),
     the planes in the list's order, mask (nrow, nchan) and nprod sums, from one pass over the inputs.  All on the device;
-    nothing is read back."""
+    nothing is read back.  chan_average = n > 1: the same with ceil(nchan / n) channels, the weighted means of DESIGN
+    4.16, by pfb_chan_average behind the pass; n = 1 is the call of always."""
+    n = check_chan_average(chan_average)
     if data.ndim != 3 or data.dtype not in _dev.REAL_OF:
         raise TypeError("data must be complex64 or complex128 of shape (nrow, nchan, ncorr)")
     rdt = _dev.REAL_OF[data.dtype]
@@ -186,11 +218,13 @@ def run(data, weight, wform, flag, frow, autocorr, jones, tbin_idx, tbin_counts,
             _dev.ptr(flag), nfc, _dev.ptr(frow), int(bool(autocorr)), _dev.ptr(jones), ndir, ti.numel(), nant,
             _dev.ptr(ti), _dev.ptr(tc), off, _dev.ptr(a1), _dev.ptr(a2), nrow, nchan, _dev.ptr(vis), _dev.ptr(wgt),
             _dev.ptr(mask), _dev.ptr(rec), _dev.ptr(_dev.scratch()[0]), _dev.stream()))
+    if n > 1:
+        return _average_dev(vis, wgt, mask, n)
     return vis, wgt, mask, rec
 
 
 def stokes_vis(data, ant1, ant2, tbin_idx, tbin_counts, poltype, product, data2=None, operator=None, sigma=None,
-               weight=None, flag=None, frow=None, jones=None, precision='single'):
+               weight=None, flag=None, frow=None, jones=None, precision='single', chan_average=1):
     """stokes2im.py:98-195 (and stokes2vis.py:76-160, 233-240) as one kernel: (vis, wgt, mask, wsum).
 
     data (nrow, nchan, ncorr) complex, ncorr 2 or 4; data2 with operator '+' or '-' is added or subtracted;
@@ -210,7 +244,14 @@ def stokes_vis(data, ant1, ant2, tbin_idx, tbin_counts, poltype, product, data2=
     Several products in one pass (the reference has none: its fastim worker refuses anything but one letter): `product`
     a string of 2 to 4 distinct letters ('IQUV', 'QU', 'VI') or a sequence of letters gives vis and wgt
     (nprod, nrow, nchan), the planes in the order asked, mask (nrow, nchan) -- it does not depend on the product -- and
-    wsum (nprod,).  Every input is read once.  A repeated or unknown letter is a ValueError."""
+    wsum (nprod,).  Every input is read once.  A repeated or unknown letter is a ValueError.
+
+    chan_average = n > 1 (stokes2vis.py:174-203) averages bins of n channels behind the pass, on the device: vis, wgt,
+    mask come out with ceil(nchan / n) channels -- the last bin may be short, n > nchan gives one -- as wgt = the sum of
+    the bin's live wgt, vis = their weighted mean (exactly 0 where that sum is 0), mask = any of the bin's; wsum is the
+    sum of the averaged wgt over the averaged mask.  average_freq gives the bins' frequencies.  n = 1 is the call of
+    always, the same bits."""
+    check_chan_average(chan_average)
     if str(precision).lower() not in _PRECISION:
         raise ValueError(f"precision must be 'single' or 'double', got {precision!r}")
     cdt = _PRECISION[str(precision).lower()]
@@ -245,5 +286,47 @@ def stokes_vis(data, ant1, ant2, tbin_idx, tbin_counts, poltype, product, data2=
         if jd.shape[-1] == 4:
             jd = jd.reshape(*jd.shape[:4], 2, 2)
     vis, wgt, mask, rec = run(dd, wd, wform, fd, fr, True, jd, tbin_idx, tbin_counts, ant1, ant2, basis, data2=d2,
-                              subtract=operator == '-')
+                              subtract=operator == '-', chan_average=chan_average)
     return tuple(_dev.host_like(t, data) for t in (vis, wgt, mask, rec.to(rdt)))
+
+
+def average_channels(vis, wgt, mask, n):
+    """Bins of n channels of vis, wgt (nrow, nchan), or (nprod <= 4, nrow, nchan) with the one mask (nrow, nchan), as
+    stokes_vis(..., chan_average=n) forms them: (vis, wgt, mask, wsum) with ceil(nchan / n) channels,
+        wgt_out = sum of wgt over the bin's samples with mask != 0, in channel order
+        vis_out = sum of wgt vis over them / wgt_out, exactly 0 where wgt_out == 0
+        mask_out = any(mask) as 0 / 1 bytes
+    and wsum the fp64 sum of wgt_out over mask_out != 0, one per plane, in wgt's type.  What a masked sample holds is
+    never read into a sum.  vis complex64 or complex128, wgt its real type; the products wgt vis are formed in that type,
+    the sums in fp64, in a fixed order: the same bits every run.  numpy in gives numpy out, tensors in give tensors
+    out."""
+    n = check_chan_average(n)
+    vd, wd = _dev.to_dev(vis), _dev.to_dev(wgt)
+    if vd.dtype not in _dev.REAL_OF or vd.ndim not in (2, 3):
+        raise TypeError("vis must be complex64 or complex128 of shape (nrow, nchan) or (nprod, nrow, nchan)")
+    if wd.dtype != _dev.REAL_OF[vd.dtype] or wd.shape != vd.shape:
+        raise TypeError(f"wgt must be {_dev.REAL_OF[vd.dtype]} of vis' shape {tuple(vd.shape)}, got {wd.dtype} "
+                        f"{tuple(wd.shape)}")
+    if vd.ndim == 3 and not 1 <= vd.shape[0] <= 4:
+        raise ValueError(f"1 to 4 product planes in one call, got {vd.shape[0]}")
+    md = _dev.byte_mask(mask, tuple(vd.shape[-2:]))
+    viso, wgto, masko, rec = _average_dev(vd, wd, md, n)
+    return tuple(_dev.host_like(t, vis) for t in (viso, wgto, masko, rec.to(wd.dtype)))
+
+
+def average_freq(freq, chan_width, n):
+    """(freq_out, chan_width_out) of the bins of n channels, float64 numpy arrays of ceil(nchan / n) entries: the mean of
+    a bin's frequencies and the sum of its widths.  Metadata of nchan entries: formed on the host in fp64."""
+    n = check_chan_average(n)
+    host = []
+    for a in (freq, chan_width):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host.append(a.astype(np.float64))
+    f, w = host
+    if f.ndim != 1 or f.shape != w.shape:
+        raise ValueError("freq and chan_width must be one-dimensional, of one length")
+    starts = np.arange(0, f.size, n)
+    if f.size == 0:
+        return f.copy(), w.copy()
+    counts = np.minimum(starts + n, f.size) - starts
+    return np.add.reduceat(f, starts) / counts, np.add.reduceat(w, starts)
