@@ -717,7 +717,8 @@ int pfb_masked_problem(int dtype, const void* residual, const unsigned char* mas
  * transforms the grid: unnormalised c2c, sign + (sign -).  Every function is asynchronous on `stream`.
  *
  * pfb_wgrid_grid accumulates with floating-point atomic adds: its sums depend on arrival order and vis2dirty differs
- * in the last bits from run to run.  dirty2vis uses none and is reproducible bit for bit. */
+ * in the last bits from run to run.  dirty2vis uses none and is reproducible bit for bit; pfb_wgrid_grid_tile (below) is
+ * the gridding step without atomics. */
 
 /* support: 4 .. 12.  nplanes == 1: one plane at w0 and no w kernel (dw ignored); else nplanes > support, dw > 0.
  * nx, ny even.  PFB_ERR_UNSUPPORTED: a support outside the range, a grid narrower than the support, too many keys. */
@@ -768,6 +769,39 @@ int pfb_wgrid_weight(void* plan, const void* acc, const void* wgt, const int* id
 /* grid = 0, then the slots [s0, s1) are added to plane `plane`. */
 int pfb_wgrid_grid(void* plan, int plane, const void* val, const double* coord, size_t nsorted, size_t s0, size_t s1,
                    void* grid, void* stream);
+/* The reproducible mode ("The tile-owned gridder"): pfb_wgrid_grid without atomics.  Every grid cell is
+ * summed by one lane in one fixed order, so the grid is identical bit for bit from run to run; each contribution is the
+ * value pfb_wgrid_grid adds.  It needs an order of its own and a map of it, both built once by the caller:
+ *
+ * The order.  pfb_wgrid_order_keys64 writes keys (nrow * nchan) long long: (p0 nfu + a / 16) nfv + b / 16 of a
+ * visibility with first plane p0 and first footprint cell (a, b), on FINE tiles of 16 x 16 cells whatever the grid
+ * (nfu = ceil(2 nx / 16), nfv = ceil(2 ny / 16)), and 2^63 - 1 where masked.  The caller sorts them STABLY: idx is the
+ * permutation's head of nsorted live entries (ascending visibility inside a key), and slots with first plane q occupy
+ * [lower_bound(q nfu nfv), lower_bound((q + 1) nfu nfv)) of the sorted keys.  pfb_wgrid_order_coords fills
+ * coord (3, nsorted) for that idx, bit for bit what pfb_wgrid_order_fill writes for the same visibility.  Every other
+ * function works on this order unchanged.
+ *
+ * The map, a CSR over the fine tiles that receive anything (device arrays):
+ *   tgt_tile (ntgt) int: tile fu nfv + fv, rows 16 fu .., columns 16 fv ..;  tgt_ptr (ntgt + 1) long long, from 0 to npair;
+ *   per pair p in [tgt_ptr[t], tgt_ptr[t + 1]): pair_start, pair_count (npair) long long, int -- a run of slots of one
+ *   key -- and pair_p0 (npair) int, its first plane.  Inside a target the pairs ascend by (first plane, source tile).
+ * A target must list every key whose footprints can reach it: first rows a with (r - a) mod 2 nx < W for a row r of the
+ * tile, likewise columns; each key once.  A cell's sum runs over its target's pairs with first plane in
+ * [plane - W + 1, plane], in list order, and over each pair's slots ascending.
+ *
+ * grid = 0, then the plane is summed; one workgroup per target.  The map is checked where it is first presented to a
+ * plan -- one small launch and one host read, the only wait in this family -- and remembered by its arrays and counts:
+ * the arrays of a map must not change while a plan uses them (the kernel never addresses outside the slots or the grid
+ * whatever they hold).  PFB_ERR_INVALID: ntgt or npair of 0 or beyond the tiles, a target outside the tiles, pointers
+ * that do not run from 0 to npair, a pair with count < 1, start + count > nsorted or a first plane outside the plan's,
+ * first planes that descend inside a target. */
+int pfb_wgrid_order_keys64(void* plan, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow,
+                           int nchan, long long* keys, void* stream);
+int pfb_wgrid_order_coords(void* plan, const double* uvw, const double* freq, size_t nrow, int nchan, const int* idx,
+                           size_t nsorted, double* coord, void* stream);
+int pfb_wgrid_grid_tile(void* plan, int plane, const void* val, const double* coord, size_t nsorted, const int* tgt_tile,
+                        const long long* tgt_ptr, const long long* pair_start, const int* pair_count, const int* pair_p0,
+                        size_t ntgt, size_t npair, void* grid, void* stream);
 /* acc[s] += the footprint sum of slot s on plane `plane`, s in [s0, s1). */
 int pfb_wgrid_degrid(void* plan, int plane, const void* grid, const double* coord, size_t nsorted, size_t s0, size_t s1,
                      void* acc, void* stream);
@@ -798,6 +832,11 @@ int pfb_wgrid_finish_multi(void* plan, int nprod, const void* acc, const void* w
 /* every grid = 0, then the slots [s0, s1) of every plane of val are added to `plane` of its grid. */
 int pfb_wgrid_grid_multi(void* plan, int nprod, int plane, const void* val, const double* coord, size_t nsorted,
                          size_t s0, size_t s1, void* grid, void* stream);
+/* pfb_wgrid_grid_tile on every plane of val: a lane holds the nprod sums of its cell. */
+int pfb_wgrid_grid_tile_multi(void* plan, int nprod, int plane, const void* val, const double* coord, size_t nsorted,
+                              const int* tgt_tile, const long long* tgt_ptr, const long long* pair_start,
+                              const int* pair_count, const int* pair_p0, size_t ntgt, size_t npair, void* grid,
+                              void* stream);
 int pfb_wgrid_degrid_multi(void* plan, int nprod, int plane, const void* grid, const double* coord, size_t nsorted,
                            size_t s0, size_t s1, void* acc, void* stream);
 int pfb_wgrid_image_forward_multi(void* plan, int nprod, int plane, const void* dirty, const void* beam,

@@ -166,6 +166,12 @@ SIGNATURES = {
     'pfb_wgrid_finish_multi': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     'pfb_wgrid_grid_multi': (_i, [_vp, _i, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     'pfb_wgrid_degrid_multi': (_i, [_vp, _i, _i, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    # the reproducible mode: its order (64-bit keys for a stable sort, coordinates of a given idx) and the tile-owned
+    # gridder on the map (tgt_tile, tgt_ptr, pair_start, pair_count, pair_p0, ntgt, npair)
+    'pfb_wgrid_order_keys64': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _vp]),
+    'pfb_wgrid_order_coords': (_i, [_vp, _vp, _vp, _sz, _i, _vp, _sz, _vp, _vp]),
+    'pfb_wgrid_grid_tile': (_i, [_vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    'pfb_wgrid_grid_tile_multi': (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
     'pfb_wgrid_image_forward_multi': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pfb_wgrid_image_adjoint_multi': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     'pfb_wgrid_image_correct_multi': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -8,6 +8,10 @@
 //   k_finish_block / k_restore_corrs   the predict step: a block's slots into a strided (row, chan, corr) model column
 //   k_grid                         one plane: 2 W lanes per visibility, a lane owns one real of a footprint row and adds
 //                                  down the W rows with float atomics (2 W contiguous reals per slot and instruction)
+//   k_order_keys64 / k_order_coords   the order of the reproducible mode: a 64-bit key per visibility on FINE tiles of
+//                                  16 x 16 cells for the caller's stable sort, and the coordinates of a given order
+//   k_grid_tile                    one plane without atomics: a workgroup owns a fine tile, a lane one cell, and sums the
+//                                  slots of the tile's pair list in list order ("The tile-owned gridder")
 //   k_degrid                       one plane: a lane per visibility gathers its W x W footprint; no atomics, each slot's
 //                                  sum has a fixed order
 //   k_image_forward / _adjoint / _correct   the image side: window <-> grid with the plane's w phase, the kernel
@@ -19,6 +23,7 @@
 //
 // Every index is reduced modulo the grid before it is used, so no coordinate, however wild, addresses outside it.
 #include "entry.hpp"
+#include <mutex>
 #include <new>
 
 namespace pfb {
@@ -26,6 +31,19 @@ namespace pfb {
 constexpr int WG_BLOCK = ENTRY_BLOCK;
 constexpr int WG_MIN_W = 4, WG_MAX_W = 12;
 constexpr int WG_MAX_TILES = 4096;        // uv tiles of the sort key; the tile edge doubles from 16 until they fit
+constexpr int WG_FINE = 16;               // the tile edge of the reproducible mode, whatever the grid: a workgroup's cells
+constexpr int WG_BATCH = 64;              // slots that k_grid_tile stages per round
+static_assert(WG_FINE * WG_FINE == WG_BLOCK, "a lane per cell of a fine tile");
+
+// the target map of pfb_wgrid_grid_tile as it was last checked (wg_tile_map)
+struct WgTileMap {
+    const void *tile = nullptr, *ptr = nullptr, *start = nullptr, *count = nullptr, *p0 = nullptr;
+    size_t ntgt = 0, npair = 0, nsorted = 0;
+    bool operator==(const WgTileMap& o) const {
+        return tile == o.tile && ptr == o.ptr && start == o.start && count == o.count && p0 == o.p0 && ntgt == o.ntgt &&
+               npair == o.npair && nsorted == o.nsorted;
+    }
+};
 
 struct WgridPlan {
     int dtype, nx, ny, Nu, Nv, W, nplanes, np0, tile, ntu, ntv;
@@ -40,6 +58,11 @@ struct WgridPlan {
     double cxs() const { return cx / (px * Nu); }          // turns of the centre phase per cell of u, of v
     double cys() const { return cy / (py * Nv); }
     int centre() const { return cx != 0.0 || cy != 0.0; }
+    int nfu() const { return (Nu + WG_FINE - 1) / WG_FINE; }        // fine tiles per axis
+    int nfv() const { return (Nv + WG_FINE - 1) / WG_FINE; }
+    // the one thing a plan remembers: the map that passed wg_tile_map last (the geometry above never changes)
+    mutable std::mutex map_lock;
+    mutable WgTileMap map_ok;
 };
 
 template <typename T>
@@ -104,6 +127,43 @@ k_order_fill(const double* __restrict__ uvw, const double* __restrict__ freq, si
     double ug, vg, pg;
     wg_coords(uvw, freq, t, nchan, g, ug, vg, pg);
     idx[s] = (int)t;
+    coord[s] = ug;
+    coord[nsorted + s] = vg;
+    coord[2 * nsorted + s] = pg;
+}
+
+// The order of the reproducible mode.  key = (p0 nfu + a / 16) nfv + b / 16 with a, b, p0 as k_order_count forms them, and
+// a sentinel above every key where masked: the caller's STABLE sort then puts the slots of a key in ascending t
+constexpr long long WG_KEY_MASKED = 0x7fffffffffffffffLL;
+
+__global__ void __launch_bounds__(WG_BLOCK)
+k_order_keys64(const double* __restrict__ uvw, const double* __restrict__ freq, const u8* __restrict__ mask, size_t nvis,
+               int nchan, WgGeom g, long long* __restrict__ keys) {
+    const size_t t = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (t >= nvis) return;
+    if (mask && !mask[t]) { keys[t] = WG_KEY_MASKED; return; }
+    double ug, vg, pg;
+    wg_coords(uvw, freq, t, nchan, g, ug, vg, pg);
+    const int a = wg_wrap(wg_first(ug, g.h), g.Nu), b = wg_wrap(wg_first(vg, g.h), g.Nv);
+    int p0 = 0;
+    if (g.wk) {
+        const double p = wg_first(pg, g.h);
+        p0 = p > 0.0 ? (p < g.np0 - 1 ? (int)p : g.np0 - 1) : 0;
+    }
+    const long long nfu = (g.Nu + WG_FINE - 1) / WG_FINE, nfv = (g.Nv + WG_FINE - 1) / WG_FINE;
+    keys[t] = (p0 * nfu + a / WG_FINE) * nfv + b / WG_FINE;
+}
+
+// coord[.][s] of visibility idx[s]: what k_order_fill writes for it, bit for bit
+__global__ void __launch_bounds__(WG_BLOCK)
+k_order_coords(const double* __restrict__ uvw, const double* __restrict__ freq, size_t nvis, int nchan, WgGeom g,
+               const int* __restrict__ idx, size_t nsorted, double* __restrict__ coord) {
+    const size_t s = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (s >= nsorted) return;
+    const int t = idx[s];
+    if (t < 0 || (size_t)t >= nvis) return;          // an order never holds one; never address outside the arrays
+    double ug, vg, pg;
+    wg_coords(uvw, freq, (size_t)t, nchan, g, ug, vg, pg);
     coord[s] = ug;
     coord[nsorted + s] = vg;
     coord[2 * nsorted + s] = pg;
@@ -262,6 +322,172 @@ k_grid(const cplx<T>* __restrict__ val, const double* __restrict__ coord, size_t
 #pragma unroll
         for (int k = 0; k < NP; ++k) atomic_add(cell + k * gplane + 2 * (size_t)row * g.Nv, fu * part[k]);
         if (++row == g.Nu) row = 0;
+    }
+}
+
+// ------------------------------------------------------------------------- gridding without atomics, one plane
+// A workgroup owns one fine tile of 16 x 16 cells -- target blockIdx.x of the map -- and lane (i, j) its cell
+// (r0 + i, c0 + j) for every product: NP complex sums in registers, stored once with plain stores.  The map lists per
+// target the pairs (start, count, p0): the slot segments whose footprints can reach the tile, sorted by (p0, source
+// tile).  The pairs of first planes plane - W + 1 .. plane are contiguous there; their slots are walked in list order,
+// WG_BATCH at a time (a batch runs across pair boundaries).  Per batch a lane stages a quarter of one slot's 2 W kernel
+// values -- the expressions and the type of k_grid -- next to the wrapped first cell and ww val[k] in LDS; after the
+// barrier every lane runs over the batch in order and adds fu[da] (val.c ww fv[db]) where its cell lies in the
+// footprint: k_grid's product order, each product rounded on its own (no fma), so a cell sums the contributions k_grid
+// would add -- in the slot order and nothing else.  No atomic, no shuffle.  A workgroup without a pair in range stores
+// nothing: the launcher has zeroed the grid
+template <typename T>
+__device__ __forceinline__ T wg_add_product(T acc, T a, T b) {
+#pragma clang fp contract(off)
+    const T p = a * b;
+    return acc + p;
+}
+
+template <typename T, int W, int NP>
+__global__ void __launch_bounds__(WG_BLOCK)
+k_grid_tile(const cplx<T>* __restrict__ val, const double* __restrict__ coord, size_t ns, int plane, WgGeom g,
+            const int* __restrict__ tgt_tile, const long long* __restrict__ tgt_ptr,
+            const long long* __restrict__ pair_start, const int* __restrict__ pair_count,
+            const int* __restrict__ pair_p0, cplx<T>* __restrict__ grid) {
+    __shared__ int s_a0[WG_BATCH], s_b0[WG_BATCH];
+    __shared__ T s_fu[WG_BATCH][W], s_fv[WG_BATCH][W];
+    __shared__ T s_vx[NP][WG_BATCH], s_vy[NP][WG_BATCH];
+    const int tid = threadIdx.x;
+    const int tile = tgt_tile[blockIdx.x], nfv = (g.Nv + WG_FINE - 1) / WG_FINE;
+    if (tile < 0) return;
+    const int row = (tile / nfv) * WG_FINE + (tid >> 4), col = (tile % nfv) * WG_FINE + (tid & 15);
+    const bool live = row < g.Nu && col < g.Nv;          // a partial last tile
+    // the pairs ascend by first plane: those below the plane's range and those up to its end are counted by all lanes
+    // at once, a chunk of WG_BLOCK pairs per round
+    const long long lo = tgt_ptr[blockIdx.x], hi = tgt_ptr[blockIdx.x + 1];
+    long long pbeg = lo, pend = lo;
+    for (long long base = lo; base < hi; base += WG_BLOCK) {
+        const int p0 = base + tid < hi ? pair_p0[base + tid] : 0x7fffffff;
+        pbeg += __syncthreads_count(p0 < plane - W + 1);
+        const int upto = __syncthreads_count(p0 <= plane);
+        pend += upto;
+        if (upto < WG_BLOCK) break;          // the same in every lane
+    }
+    if (pbeg >= pend) return;
+    const T beta = T(2.3) * W;
+    const double h = 0.5 * W;
+    const int sl = tid & (WG_BATCH - 1), part = tid / WG_BATCH;          // staging: slot of the batch, quarter of its work
+    T ax[NP], ay[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) ax[k] = ay[k] = T(0);
+    long long pi = pbeg, off = 0;          // the cursor, the same in every lane: pair, and slots of it already taken
+    while (pi < pend) {
+        // ---- stage: the slot sl places past the cursor
+        long long q = pi, o = off + sl;
+        for (; q < pend; ++q) {
+            const long long c = pair_count[q];
+            if (o < c) break;
+            o -= c;
+        }
+        bool on = q < pend;
+        size_t s = 0;
+        if (on) {
+            s = (size_t)(pair_start[q] + o);
+            on = s < ns;          // what the entry point has checked; never read past the slots
+        }
+        // the slot's loads leave together; the w weight decides afterwards whether it is staged
+        double ug = 0.0, vg = 0.0, pg = 0.0;
+        cplx<T> v(T(0), T(0));
+        if (on) {
+            ug = coord[s];
+            vg = coord[ns + s];
+            if (g.wk) pg = coord[2 * ns + s];
+            if (part < NP) v = val[part * ns + s];
+        }
+        T ww = T(1);
+        if (on && g.wk) {
+            ww = wg_phi<T>((T)((plane - pg) / h), beta);
+            on = ww != T(0);
+        }
+        if (on) {
+            const double a0 = wg_first(ug, h), b0 = wg_first(vg, h);
+#pragma unroll
+            for (int e = 0; e < 2 * W; ++e) {
+                if ((e & 3) != part) continue;
+                if (e < W) s_fu[sl][e] = wg_phi<T>((T)((a0 + e - ug) / h), beta);
+                else s_fv[sl][e - W] = wg_phi<T>((T)((b0 + (e - W) - vg) / h), beta);
+            }
+            if (part == 0) {
+                s_a0[sl] = wg_wrap(a0, g.Nu);
+                s_b0[sl] = wg_wrap(b0, g.Nv);
+            }
+            if (part < NP) {
+                s_vx[part][sl] = v.x * ww;
+                s_vy[part][sl] = v.y * ww;
+            }
+        } else if (part == 0) {
+            s_a0[sl] = -1;          // no slot here, or one that does not reach the plane
+        }
+        // ---- the batch's size and the next cursor: WG_BATCH places on
+        long long q2 = pi, o2 = off + WG_BATCH;
+        for (; q2 < pend; ++q2) {
+            const long long c = pair_count[q2];
+            if (o2 < c) break;
+            o2 -= c;
+        }
+        const int nb = q2 < pend ? WG_BATCH : (int)(WG_BATCH - (o2 < WG_BATCH ? o2 : WG_BATCH));
+        pi = q2;
+        off = o2;
+        __syncthreads();
+        // ---- accumulate, in slot order
+        if (live) {
+            for (int b = 0; b < nb; ++b) {
+                const int a0 = s_a0[b];
+                if (a0 < 0) continue;
+                int da = row - a0, db = col - s_b0[b];
+                if (da < 0) da += g.Nu;
+                if (db < 0) db += g.Nv;
+                if (da < W && db < W) {
+                    const T fu = s_fu[b][da], fv = s_fv[b][db];
+#pragma unroll
+                    for (int k = 0; k < NP; ++k) {
+                        ax[k] = wg_add_product(ax[k], fu, s_vx[k][b] * fv);
+                        ay[k] = wg_add_product(ay[k], fu, s_vy[k][b] * fv);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+    const size_t gplane = (size_t)g.Nu * g.Nv, cell = (size_t)row * g.Nv + col;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) grid[k * gplane + cell] = cplx<T>(ax[k], ay[k]);
+}
+
+// what pfb_wgrid_grid_tile requires of a map, a lane per pair and per target: bad[0] the targets (tile in range, ptr
+// from 0 to npair, never descending), bad[1] a pair outside the slots or the first planes, bad[2] first planes that
+// descend inside a target
+__global__ void __launch_bounds__(WG_BLOCK)
+k_tile_map_check(const int* __restrict__ tgt_tile, const long long* __restrict__ tgt_ptr,
+                 const long long* __restrict__ pair_start, const int* __restrict__ pair_count,
+                 const int* __restrict__ pair_p0, size_t ntgt, size_t npair, size_t nsorted, int ntiles, int np0,
+                 int* __restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (i < ntgt) {
+        const long long lo = tgt_ptr[i], hi = tgt_ptr[i + 1];
+        if (tgt_tile[i] < 0 || tgt_tile[i] >= ntiles || lo < 0 || hi < lo || hi > (long long)npair ||
+            (i == 0 && lo != 0) || (i == ntgt - 1 && hi != (long long)npair))
+            bad[0] = 1;
+    }
+    if (i < npair) {
+        const long long s = pair_start[i], c = pair_count[i];
+        if (s < 0 || c < 1 || (size_t)s > nsorted || (size_t)c > nsorted - (size_t)s || pair_p0[i] < 0 || pair_p0[i] >= np0)
+            bad[1] = 1;
+        if (i > 0 && pair_p0[i - 1] > pair_p0[i]) {
+            // a descent is right only where pair i opens a target: the last target whose ptr is <= i
+            size_t lo = 0, hi = ntgt;
+            while (lo < hi) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (tgt_ptr[mid] <= (long long)i) lo = mid + 1; else hi = mid;
+            }
+            if (lo == 0 || tgt_ptr[lo - 1] != (long long)i) bad[2] = 1;
+        }
     }
 }
 
@@ -483,6 +709,60 @@ static int wg_grid(const char* name, void* plan, int nprod, int plane, const voi
     });
 }
 
+// The map of a reproducible plan, checked where it is first presented to the plan: one small launch and ONE host read
+// (the only entry point that waits for the device).  A plan remembers the map that passed -- its arrays and counts -- and
+// takes it as read from then on: the arrays of a map do not change while a plan uses them, like idx and coord
+static int wg_tile_map(const WgridPlan& p, const char* name, const WgTileMap& m, void* stream) {
+    std::lock_guard<std::mutex> guard(p.map_lock);
+    if (p.map_ok == m) return PFB_OK;
+    int* bad = nullptr;
+    PFB_HIP_CHECK(hipMalloc(&bad, 3 * sizeof(int)));
+    int host[3] = {0, 0, 0};
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(host), as_stream(stream));
+    if (e == hipSuccess) {
+        const size_t n = m.ntgt > m.npair ? m.ntgt : m.npair;
+        hipLaunchKernelGGL(k_tile_map_check, dim3(blocks(n)), dim3(WG_BLOCK), 0, as_stream(stream), (const int*)m.tile,
+                           (const long long*)m.ptr, (const long long*)m.start, (const int*)m.count, (const int*)m.p0,
+                           m.ntgt, m.npair, m.nsorted, p.nfu() * p.nfv(), p.np0, bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(host, bad, sizeof(host), hipMemcpyDeviceToHost, as_stream(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    (void)hipFree(bad);
+    PFB_HIP_CHECK(e);
+    PFB_REQUIRE(!host[0], PFB_ERR_INVALID, "%s: a target outside the %d fine tiles, or pointers that do not run from 0 "
+                "to %zu pairs", name, p.nfu() * p.nfv(), m.npair);
+    PFB_REQUIRE(!host[1], PFB_ERR_INVALID, "%s: a pair outside the %zu slots or the %d first planes", name, m.nsorted,
+                p.np0);
+    PFB_REQUIRE(!host[2], PFB_ERR_INVALID, "%s: the pairs of a target do not ascend by first plane", name);
+    p.map_ok = m;
+    return PFB_OK;
+}
+
+static int wg_grid_tile(const char* name, void* plan, int nprod, int plane, const void* val, const double* coord,
+                        size_t nsorted, const int* tgt_tile, const long long* tgt_ptr, const long long* pair_start,
+                        const int* pair_count, const int* pair_p0, size_t ntgt, size_t npair, void* grid, void* stream) {
+    if (int rc = wg_check(plan, name, {{val, CPLX}, {coord, F64}, {tgt_tile, I32}, {tgt_ptr, I64}, {pair_start, I64},
+                                       {pair_count, I32}, {pair_p0, I32}, {grid, CPLX}});
+        rc != PFB_OK) return rc;
+    const WgridPlan& p = wg_plan(plan);
+    if (int rc = wg_plane(p, name, plane); rc != PFB_OK) return rc;
+    if (int rc = check_count(name, nsorted, PFB_ERR_INVALID); rc != PFB_OK) return rc;
+    PFB_REQUIRE(ntgt >= 1 && ntgt <= (size_t)p.nfu() * p.nfv() && npair >= ntgt && npair <= (size_t)0x7fffffff,
+                PFB_ERR_INVALID, "%s: %zu targets and %zu pairs for %d fine tiles", name, ntgt, npair, p.nfu() * p.nfv());
+    if (int rc = wg_tile_map(p, name, {tgt_tile, tgt_ptr, pair_start, pair_count, pair_p0, ntgt, npair, nsorted}, stream);
+        rc != PFB_OK) return rc;
+    PFB_HIP_CHECK(hipMemsetAsync(grid, 0, p.grid_bytes() * (size_t)nprod, as_stream(stream)));
+    return by_type(p.dtype, [&](auto t) {
+        return by_int<WG_MIN_W, WG_MAX_W>(p.W, [&](auto w) {
+            return by_int<1, WG_MAX_PROD>(nprod, [&](auto np) {
+                return launch_groups(k_grid_tile<decltype(t), w(), np()>, ntgt, stream, val, coord, nsorted, plane,
+                                     wg_geom(p), tgt_tile, tgt_ptr, pair_start, pair_count, pair_p0, grid);
+            });
+        });
+    });
+}
+
 static int wg_degrid(const char* name, void* plan, int nprod, int plane, const void* grid, const double* coord,
                      size_t nsorted, size_t s0, size_t s1, void* acc, void* stream) {
     if (int rc = wg_check(plan, name, {{grid, CPLX}, {coord, F64}, {acc, CPLX}}); rc != PFB_OK) return rc;
@@ -620,6 +900,25 @@ int pfb_wgrid_order_fill(void* plan, const double* uvw, const double* freq, size
                   nsorted, idx, coord);
 }
 
+int pfb_wgrid_order_keys64(void* plan, const double* uvw, const double* freq, const unsigned char* mask, size_t nrow,
+                           int nchan, long long* keys, void* stream) {
+    if (int rc = wg_check(plan, "wgrid_order_keys64", {{uvw, F64}, {freq, F64}, {keys, I64}}); rc != PFB_OK) return rc;
+    if (int rc = check_nvis("wgrid_order_keys64", nrow, nchan); rc != PFB_OK) return rc;
+    const size_t nvis = nrow * (size_t)nchan;
+    return launch(k_order_keys64, nvis, stream, uvw, freq, mask, nvis, nchan, wg_geom(wg_plan(plan)), keys);
+}
+
+int pfb_wgrid_order_coords(void* plan, const double* uvw, const double* freq, size_t nrow, int nchan, const int* idx,
+                           size_t nsorted, double* coord, void* stream) {
+    if (int rc = wg_check(plan, "wgrid_order_coords", {{uvw, F64}, {freq, F64}, {idx, I32}, {coord, F64}});
+        rc != PFB_OK) return rc;
+    if (int rc = check_nvis("wgrid_order_coords", nrow, nchan); rc != PFB_OK) return rc;
+    const size_t nvis = nrow * (size_t)nchan;
+    PFB_REQUIRE(nsorted >= 1 && nsorted <= nvis, PFB_ERR_INVALID, "wgrid_order_coords: %zu slots for %zu visibilities",
+                nsorted, nvis);
+    return launch(k_order_coords, nsorted, stream, uvw, freq, nvis, nchan, wg_geom(wg_plan(plan)), idx, nsorted, coord);
+}
+
 int pfb_wgrid_prep(void* plan, const void* vis, const void* wgt, const int* idx, const double* coord, size_t nsorted,
                    void* val, void* stream) {
     return wg_prep("wgrid_prep", plan, 1, vis, wgt, 0, idx, coord, nsorted, 0, val, stream);
@@ -701,6 +1000,22 @@ int pfb_wgrid_grid_multi(void* plan, int nprod, int plane, const void* val, cons
                          size_t s0, size_t s1, void* grid, void* stream) {
     if (int rc = wg_nprod("wgrid_grid_multi", nprod); rc != PFB_OK) return rc;
     return wg_grid("wgrid_grid_multi", plan, nprod, plane, val, coord, nsorted, s0, s1, grid, stream);
+}
+
+int pfb_wgrid_grid_tile(void* plan, int plane, const void* val, const double* coord, size_t nsorted, const int* tgt_tile,
+                        const long long* tgt_ptr, const long long* pair_start, const int* pair_count, const int* pair_p0,
+                        size_t ntgt, size_t npair, void* grid, void* stream) {
+    return wg_grid_tile("wgrid_grid_tile", plan, 1, plane, val, coord, nsorted, tgt_tile, tgt_ptr, pair_start, pair_count,
+                        pair_p0, ntgt, npair, grid, stream);
+}
+
+int pfb_wgrid_grid_tile_multi(void* plan, int nprod, int plane, const void* val, const double* coord, size_t nsorted,
+                              const int* tgt_tile, const long long* tgt_ptr, const long long* pair_start,
+                              const int* pair_count, const int* pair_p0, size_t ntgt, size_t npair, void* grid,
+                              void* stream) {
+    if (int rc = wg_nprod("wgrid_grid_tile_multi", nprod); rc != PFB_OK) return rc;
+    return wg_grid_tile("wgrid_grid_tile_multi", plan, nprod, plane, val, coord, nsorted, tgt_tile, tgt_ptr, pair_start,
+                        pair_count, pair_p0, ntgt, npair, grid, stream);
 }
 
 int pfb_wgrid_degrid(void* plan, int plane, const void* grid, const double* coord, size_t nsorted, size_t s0, size_t s1,

@@ -46,6 +46,7 @@ MAX_PROD = 4            # planes of a stacked call (WG_MAX_PROD of csrc/wgrid.hi
 # (1e-3, 1e-4, 1e-5) at which every case of tests/wgrid_cases.py stays under epsilon / 3 on the MI355X
 EPS_MIN = {torch.float64: 1e-10, torch.float32: 1e-5}
 _QUAD_NODES = 128
+FINE_TILE = 16          # the tile edge of the reproducible mode (WG_FINE of csrc/wgrid.hip): a workgroup's cells
 
 
 def support_for(epsilon):
@@ -158,16 +159,63 @@ def tables_for(nx, ny, pixsize_x, pixsize_y, center_x, center_y, W, do_wgridding
     return _tables.get(key, make)
 
 
+def _axis_targets(N, W):
+    """(ntiles, K) int64, -1 padded: the fine tiles of an axis of N cells that a footprint of W cells can reach when its
+    first cell lies in tile f -- tile t is fed by first cells a with (r - a) mod N < W for a cell r of t --, each once.
+    K is 2 on an ordinary axis, 1 where one tile is the axis (it is its own neighbour) and 3 where a partial last tile is
+    narrower than W - 1 cells (a footprint crosses it and wraps into tile 0)."""
+    nt = -(-N // FINE_TILE)
+    a = np.arange(N)
+    reach = ((a[:, None] + np.arange(W)) % N) // FINE_TILE
+    codes = np.unique((a // FINE_TILE)[:, None] * nt + reach)
+    src, tgt = codes // nt, codes % nt
+    cnt = np.bincount(src, minlength=nt)
+    table = np.full((nt, int(cnt.max())), -1, np.int64)
+    table[src, np.arange(codes.size) - (np.cumsum(cnt) - cnt)[src]] = tgt
+    return table
+
+
+def tile_map(ukeys, starts, counts, Nu, Nv, W):
+    """The target map of the tile-owned gridder from the non-empty segments (key, start, count) of a reproducible order,
+    key = (p0 nfu + fu) nfv + fv ascending: (tgt_tile int32 (nT), tgt_ptr int64 (nT + 1), pair_start int64, pair_count
+    int32, pair_p0 int32), a CSR over the fine tiles that receive anything.  A segment is listed under every tile its
+    footprints can reach (_axis_targets on either axis); inside a target the pairs ascend by (p0, source tile) -- the
+    segments' own order, kept by a stable sort on the target alone.  Device tensors in and out; no dense per-key table."""
+    dev = ukeys.device
+    nfu, nfv = -(-Nu // FINE_TILE), -(-Nv // FINE_TILE)
+    src = ukeys % (nfu * nfv)
+    tu = torch.from_numpy(_axis_targets(Nu, W)).to(dev)[src // nfv]          # (nseg, Ku)
+    tv = torch.from_numpy(_axis_targets(Nv, W)).to(dev)[src % nfv]           # (nseg, Kv)
+    tgt = tu[:, :, None] * nfv + tv[:, None, :]
+    valid = (tu >= 0)[:, :, None] & (tv >= 0)[:, None, :]
+    seg = torch.arange(ukeys.numel(), device=dev)[:, None, None].expand_as(tgt)[valid]          # segment-major
+    tgt, by_target = torch.sort(tgt[valid], stable=True)
+    seg = seg[by_target]
+    tgt_tile, per_target = torch.unique_consecutive(tgt, return_counts=True)
+    tgt_ptr = torch.zeros(tgt_tile.numel() + 1, dtype=torch.int64, device=dev)
+    tgt_ptr[1:] = torch.cumsum(per_target, 0)
+    return (tgt_tile.to(torch.int32), tgt_ptr, starts[seg].contiguous(), counts[seg].to(torch.int32),
+            (ukeys // (nfu * nfv))[seg].to(torch.int32))
+
+
 class WgridPlan(NativePlan):
     """One (uvw, freq, mask) set on one image geometry: the native geometry record, the sorted order (idx, coord, the
     planes' slot ranges), nm1 and the correction tables (the geometry's GeomTables), and the per-call buffers (one grid,
     val / acc, the complex image; and their stacks of up to MAX_PROD planes once a stacked call has come).  Use through vis2dirty / dirty2vis / hessian, which hold `lock`.  `degrid_only`: a
-    block plan of the predict step, which holds the grid and one slot vector and has dirty2vis_into only."""
+    block plan of the predict step, which holds the grid and one slot vector and has dirty2vis_into only.
+
+    `reproducible`: the plan grids without atomics (pfb_wgrid_grid_tile, DESIGN 4.10 "The tile-owned gridder"): its own
+    order -- keys on fine tiles of 16 x 16 cells, ascending visibility inside a key -- and the target map of that order
+    (`tile_map`).  Every result of such a plan is identical bit for bit from run to run and from plan to plan on the
+    same arrays; everything but the gridding step is the default plan's code on the other order."""
     _destroy = 'pfb_wgrid_plan_destroy'
 
     def __init__(self, uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, rdtype,
-                 degrid_only=False):
+                 degrid_only=False, reproducible=False):
         super().__init__()
+        if degrid_only and reproducible:
+            raise ValueError("reproducible: a block plan of the predict step (degrid_only) never grids")
+        self.reproducible = bool(reproducible)
         dev = _dev.require_device()
         nx, ny = int(nx), int(ny)
         if nx < 2 or ny < 2 or nx % 2 or ny % 2:
@@ -203,7 +251,10 @@ class WgridPlan(NativePlan):
         nkeys, np0, tile = C.c_int(), C.c_int(), C.c_int()
         _lib.check(self._lib.pfb_wgrid_plan_info(self._h, C.byref(nkeys), C.byref(np0), C.byref(tile)))
         self.nkeys, self.np0, self.tile = nkeys.value, np0.value, tile.value
-        self._build_order(dev)
+        if self.reproducible:
+            self._build_tile_order(dev)
+        else:
+            self._build_order(dev)
         self._grid = torch.empty((2 * nx, 2 * ny), dtype=self.cdtype, device=dev)
         self._slots = torch.empty((1 if degrid_only else 2, self.nsorted), dtype=self.cdtype, device=dev)
         self._img = None if degrid_only else torch.empty((nx, ny), dtype=self.cdtype, device=dev)
@@ -224,6 +275,27 @@ class WgridPlan(NativePlan):
         self.coord = torch.empty((3, self.nsorted), dtype=torch.float64, device=dev)
         self.run('pfb_wgrid_order_fill', _dev.ptr(self.uvw), _dev.ptr(self.freq), self.nrow, self.nchan, _dev.ptr(keys),
                  _dev.ptr(offsets), _dev.ptr(work), self.nsorted, _dev.ptr(self.idx), _dev.ptr(self.coord))
+
+    def _build_tile_order(self, dev):
+        """The order of the reproducible mode: 64-bit keys (first plane, fine tile) from the key kernel, a STABLE
+        torch.sort -- ascending visibility inside a key, where the counting sort's cursor leaves the arrival order --,
+        the coordinates of that order, and the target map of its segments.  The planes' offsets cross to the host."""
+        ntiles = (-(-2 * self.nx // FINE_TILE)) * (-(-2 * self.ny // FINE_TILE))
+        keys = torch.empty(self.nvis, dtype=torch.int64, device=dev)
+        self.run('pfb_wgrid_order_keys64', _dev.ptr(self.uvw), _dev.ptr(self.freq), _dev.ptr(self.mask), self.nrow,
+                 self.nchan, _dev.ptr(keys))
+        keys, order = torch.sort(keys, stable=True)
+        firsts = torch.arange(self.np0 + 1, dtype=torch.int64, device=dev) * ntiles          # below the mask's sentinel
+        self.plane_off = torch.searchsorted(keys, firsts).cpu().tolist()        # np0 + 1 entries
+        self.nsorted = self.plane_off[-1]
+        self.idx = order[:self.nsorted].to(torch.int32)
+        self.coord = torch.empty((3, self.nsorted), dtype=torch.float64, device=dev)
+        self.run('pfb_wgrid_order_coords', _dev.ptr(self.uvw), _dev.ptr(self.freq), self.nrow, self.nchan,
+                 _dev.ptr(self.idx), self.nsorted, _dev.ptr(self.coord))
+        ukeys, counts = torch.unique_consecutive(keys[:self.nsorted], return_counts=True)
+        self.tile_map = tile_map(ukeys, torch.cumsum(counts, 0) - counts, counts, 2 * self.nx, 2 * self.ny, self.W)
+        self._map_args = tuple(_dev.ptr(t) for t in self.tile_map) + (self.tile_map[0].numel(),
+                                                                      self.tile_map[2].numel())
 
     # ------------------------------------------------------------------------------------------------ pieces
     def corr(self, divide_by_n):
@@ -288,7 +360,11 @@ class WgridPlan(NativePlan):
         g, _, img = self._buffers(nprod)
         img.zero_()
         for p, s0, s1 in self.plane_ranges():
-            self._step('grid', nprod, p, _dev.ptr(val), _dev.ptr(self.coord), self.nsorted, s0, s1, _dev.ptr(g))
+            if self.reproducible:
+                self._step('grid_tile', nprod, p, _dev.ptr(val), _dev.ptr(self.coord), self.nsorted, *self._map_args,
+                           _dev.ptr(g))
+            else:
+                self._step('grid', nprod, p, _dev.ptr(val), _dev.ptr(self.coord), self.nsorted, s0, s1, _dev.ptr(g))
             gh = torch.fft.ifft2(g, norm='forward').contiguous()
             self._step('image_adjoint', nprod, p, _dev.ptr(gh), _dev.ptr(self.nm1), _dev.ptr(img))
         out = torch.empty(img.shape, dtype=self.rdtype, device=val.device)
@@ -395,18 +471,20 @@ _cache = PlanCache(8)
 cache_stats = {'miss': 0, 'tables': 0}
 
 
-def plan_for(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, rdtype):
-    """The cached plan of these arrays on this geometry.  The arrays are keyed by _plan.array_key (numpy: address, layout
+def plan_for(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding, rdtype,
+             reproducible=False):
+    """The cached plan of these arrays on this geometry; `reproducible` is part of the key, so a default call never finds
+    a reproducible plan or the reverse.  The arrays are keyed by _plan.array_key (numpy: address, layout
     and a strided content sample; tensors: data_ptr and version counter); the entry keeps the arrays alive, so that
     their memory cannot come back as DIFFERENT data under the same key (clear_plan_cache() releases plans and
     references)."""
     key = (array_key(uvw), array_key(freq), array_key(mask), int(nx), int(ny), float(pixsize_x), float(pixsize_y),
-           float(center_x), float(center_y), float(epsilon), bool(do_wgridding), str(rdtype))
+           float(center_x), float(center_y), float(epsilon), bool(do_wgridding), str(rdtype), bool(reproducible))
 
     def make():
         cache_stats['miss'] += 1
         return (WgridPlan(uvw, freq, mask, nx, ny, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding,
-                          rdtype), (uvw, freq, mask))
+                          rdtype, reproducible=reproducible), (uvw, freq, mask))
     return _cache.get(key, make)[0]
 
 
@@ -423,13 +501,16 @@ def _check_flags(do_wgridding, epsilon, pixsize_x, pixsize_y):
 
 def vis2dirty(uvw, freq, vis, wgt=None, mask=None, npix_x=None, npix_y=None, pixsize_x=None, pixsize_y=None,
               center_x=0.0, center_y=0.0, epsilon=None, do_wgridding=None, divide_by_n=True,
-              double_precision_accumulation=False, nthreads=1):
+              double_precision_accumulation=False, nthreads=1, reproducible=False):
     """ducc0.wgridder.experimental.vis2dirty: dirty (npix_x, npix_y) in the real type of vis.  `nthreads` is accepted
     and ignored.  double_precision_accumulation with complex64 input runs the fp64 kernels on the data cast up.
 
     Beyond ducc0: vis (nprod, nrow, nchan), nprod <= 4 -- the Stokes products of utils.stokes.stokes_vis(product='IQUV')
     -- gives dirty (nprod, npix_x, npix_y) under ONE plan and order, the one a 2-D call on the same arrays finds in the
-    cache; wgt is None, (nrow, nchan) for every plane, or (nprod, nrow, nchan)."""
+    cache; wgt is None, (nrow, nchan) for every plane, or (nprod, nrow, nchan).
+
+    reproducible=True grids without atomics, under a plan of its own: the result is identical bit for bit from run to
+    run for the same arrays in the same row order (another order of the same visibilities is another sum order)."""
     _check_flags(do_wgridding, epsilon, pixsize_x, pixsize_y)
     if npix_x is None or npix_y is None:
         raise TypeError("npix_x and npix_y are required")
@@ -444,7 +525,7 @@ def vis2dirty(uvw, freq, vis, wgt=None, mask=None, npix_x=None, npix_y=None, pix
     if rdt != rdt_in:
         vd, wd = vd.to(torch.complex128), (None if wd is None else wd.to(torch.float64))
     plan = plan_for(uvw, freq, mask, npix_x, npix_y, pixsize_x, pixsize_y, center_x, center_y, epsilon, do_wgridding,
-                    rdt)
+                    rdt, reproducible)
     out = plan.vis2dirty(vd, wd, divide_by_n)
     return _dev.host_like(out.to(rdt_in), vis)
 
@@ -469,7 +550,7 @@ def dirty2vis(uvw, freq, dirty, wgt=None, mask=None, pixsize_x=None, pixsize_y=N
 # --------------------------------------------------------------------------- the grid worker's products, in one go
 def image_data_products(uvw, freq, vis, wgt, mask, counts, nx, ny, nx_psf, ny_psf, cellx, celly, model=None,
                         robustness=None, x0=0.0, y0=0.0, nthreads=1, epsilon=1e-7, do_wgridding=True, double_accum=True,
-                        l2reweight_dof=None, do_dirty=True, do_psf=True, do_weight=True):
+                        l2reweight_dof=None, do_dirty=True, do_psf=True, do_weight=True, reproducible=False):
     """pfb/operators/gridder.py:551-740: the image-space data products of one band in one go, with the reference's
     keys -- WEIGHT (if do_weight), WSUM (1,), DIRTY, PSF and PSFHAT (if do_psf), RESIDUAL (if a model is given) -- and its
     statements in its order: model visibilities, the l2 reweight, the imaging weights of `robustness` from `counts`
@@ -479,6 +560,9 @@ def image_data_products(uvw, freq, vis, wgt, mask, counts, nx, ny, nx_psf, ny_ps
     One plan of the cache per geometry: the (nx, ny) plan serves model, dirty and residual, the (nx_psf, ny_psf) plan the
     PSF (and a 128 x 128 one the delta).  They work in float64 when double_accum is set and in the type of vis otherwise.
     The model is degridded WITH the mask -- which the plan carries -- since residual_vis is multiplied by it anyway.
+    reproducible=True takes the plans that grid without atomics: DIRTY, PSF, PSFHAT and RESIDUAL are then identical bit
+    for bit from run to run, given weights that are (counts of compute_counts with k = 0 are; with k > 0 they are
+    accumulated with float atomics and vary in their last bits).
 
     Differences from the reference: the caller's wgt is never written (the reference's `wgt *= imwgt` writes into it);
     no weights at all (wgt None, no robustness, no l2 reweight, or an l2 reweight with an all-zero mask and no
@@ -504,7 +588,7 @@ def image_data_products(uvw, freq, vis, wgt, mask, counts, nx, ny, nx_psf, ny_ps
     nx, ny = int(nx), int(ny)
 
     def plan(npx, npy):
-        return plan_for(uvw, freq, mask, npx, npy, cellx, celly, x0, y0, epsilon, do_wgridding, rdt)
+        return plan_for(uvw, freq, mask, npx, npy, cellx, celly, x0, y0, epsilon, do_wgridding, rdt, reproducible)
 
     def image(p, v, w):
         return p.vis2dirty(v.to(cdt), None if w is None else w.to(rdt), False).to(rdt_in)

@@ -36,11 +36,12 @@ from .psf import plan_for, PsfConvPlan, psf_convolve_cube, _run
 
 # ------------------------------------------------------------------ the visibility-space Hessian (hessian.py:11-126)
 def _hessian_impl(x, uvw, weight, vis_mask, freq, beam, x0=0.0, y0=0.0, cell=None, do_wgridding=None, epsilon=None,
-                  double_accum=None, nthreads=None):
+                  double_accum=None, nthreads=None, reproducible=False):
     """pfb/operators/hessian.py:62-106: beam * vis2dirty(weight * dirty2vis(beam * x)), divide_by_n=False both ways,
     image centre (x0, y0), square pixels of `cell`.  An all-zero x answers zeros without a launch of the gridder.
     beam and weight may be None.  double_accum with a float32 x runs the fp64 kernels on the data cast up.  `nthreads`
-    is accepted and ignored.  numpy in gives numpy out."""
+    is accepted and ignored.  reproducible (hessopts['reproducible']) grids without atomics: identical bits from run to
+    run.  numpy in gives numpy out."""
     if cell is None or do_wgridding is None or epsilon is None:
         raise TypeError("cell, do_wgridding and epsilon are required")
     xd = _dev.to_dev(x)
@@ -50,7 +51,7 @@ def _hessian_impl(x, uvw, weight, vis_mask, freq, beam, x0=0.0, y0=0.0, cell=Non
         return _dev.host_like(torch.zeros_like(xd), x)
     rdt = torch.float64 if double_accum else xd.dtype
     nx, ny = xd.shape
-    plan = gridder.plan_for(uvw, freq, vis_mask, nx, ny, cell, cell, x0, y0, epsilon, do_wgridding, rdt)
+    plan = gridder.plan_for(uvw, freq, vis_mask, nx, ny, cell, cell, x0, y0, epsilon, do_wgridding, rdt, reproducible)
     out = plan.hessian(xd.to(rdt), _dev.to_dev(weight, rdt), _dev.to_dev(beam, rdt))
     return _dev.host_like(out.to(xd.dtype), x)
 
@@ -139,8 +140,9 @@ class hessian_psf_slice:
     dirty - _hessian_impl(beam * x, ...); without them it raises NotImplementedError."""
 
     def __init__(self, ds, nbasis, nmax, nthreads, sigmainv, cell=None, do_wgridding=None,
-                 epsilon=None, double_accum=None):
+                 epsilon=None, double_accum=None, reproducible=False):
         self.nthreads = nthreads
+        self.reproducible = bool(reproducible)          # compute_residual grids without atomics
         self.sigmainv = sigmainv
         self.cell, self.do_wgridding, self.epsilon, self.double_accum = cell, do_wgridding, epsilon, double_accum
         self.lastsize = ds.PSF.shape[-1]
@@ -178,7 +180,7 @@ class hessian_psf_slice:
             xd = _dev.to_dev(x, self.dirty.dtype)
             hx = _hessian_impl(self.beam * xd, self.uvw, self.wgt, self.vmask, self.freq, None, cell=self.cell,
                                do_wgridding=self.do_wgridding, epsilon=self.epsilon, double_accum=self.double_accum,
-                               nthreads=self.nthreads)
+                               nthreads=self.nthreads, reproducible=self.reproducible)
             return _dev.host_like(self.dirty - hx, x)
         raise NotImplementedError("visibility-space residual (wgridder) is outside the PSF-convolution "
                                   "hot path; use the reference's _hessian_impl")
